@@ -49,6 +49,8 @@ import numpy as np  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 ADV_BYTES = 64                 # AdvanceWorld as its own kernel: r/w translation 12 + velocity 12 + ttl 8
+DUMP_SAMPLE = 1 << 18          # --dump-outputs: entity slots whose live state is written (a fixed, seeded sample of larger worlds)
+PREHEAT_TICKS_PER_MS = 20      # --dump-outputs: pre-heat ticks per requested millisecond (the headline tick is ~50 us)
 
 
 def dbg_hooks(w):
@@ -93,6 +95,27 @@ def alu_executed(frac_algorithmic, depth, components=2):
     if frac_algorithmic is None or not depth: return {}
     ratio = (4.0 * components * depth + 1.0) / (6.0 * components * depth)
     return {"executed_over_algorithmic": round(ratio, 4), "frac_executed": frac_algorithmic * ratio}
+
+
+def dump_outputs(d, w, ids, last_cs):
+    """--dump-outputs DIR: what the timed path handed its caller in the LAST timed step and the world it left behind, as .npy files.
+    checksums.npy: the step's D Checksum(u128)s, four little-endian 32-bit limbs each (float64, exact).  <Component>.npy: every word of the
+    component for the slots in slot.npy (all slots up to DUMP_SAMPLE, else a sorted sample drawn with seed 0), zero where the entity is dead
+    or lacks the component; 4-byte words as float32 (the f32 bits), others as float64.  alive.npy: the alive mask of those slots."""
+    os.makedirs(d, exist_ok=True)
+    arrays = {"checksums": np.frombuffer(last_cs, dtype="<u4").reshape(-1, 4).astype(np.float64)}
+    n = w.len
+    slot = np.arange(n) if n <= DUMP_SAMPLE else np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+    alive = w.alive_mask(n)
+    arrays["slot"], arrays["alive"] = slot.astype(np.float64), alive[slot].astype(np.float32)
+    for cid in ids:
+        name, wb, nw = w._comps[cid]
+        keep = (w.present_mask(cid, n) & alive)[slot]
+        words = np.stack([np.where(keep, w.download_word(cid, k, 0, n)[slot], 0) for k in range(nw)], axis=1)
+        arrays[name] = words.astype(np.uint32).view(np.float32) if wb == 4 else words.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, f"{name}.npy"), a)
+    return {"dir": d, "arrays": {k: list(a.shape) for k, a in arrays.items()}, "bytes": sum(a.nbytes for a in arrays.values())}
 
 
 def rss_mb():
@@ -489,9 +512,11 @@ def measure_single(bg, cm, torch, args, contig=False, light=False):
     # ---- pre-heat: the SAME tick on the SAME world for a fixed wall time, reported on its own (not part of `warmup`): the
     # chip clocks up over the first tens of milliseconds of load, and a 20-step timed region is 2.4 ms long
     pre_t0 = time.perf_counter(); pre_n = 0
+    # --dump-outputs: a fixed number of pre-heat ticks instead of a wall-clock span, so that the timed ticks start at the same frame in every run
+    pre_ticks = round(args.preheat_ms * PREHEAT_TICKS_PER_MS) if getattr(args, "dump_outputs", None) else None
     if args.preheat_ms > 0:
         run.enqueue(w.frame); pre_n = 1
-        while (time.perf_counter() - pre_t0) * 1e3 < args.preheat_ms:
+        while pre_n < pre_ticks if pre_ticks is not None else (time.perf_counter() - pre_t0) * 1e3 < args.preheat_ms:
             run.enqueue(w.frame); run.collect(); pre_n += 1
         run.collect()
         w.synchronize()
@@ -546,6 +571,9 @@ def measure_single(bg, cm, torch, args, contig=False, light=False):
                              "after_last_collect": round((t0 + secs - stamps[-1]) * 1e6, 1),      # the two synchronize calls that close the region
                              "note": "host interval between consecutive collects in the timed region (tick k+1 is already enqueued when tick k is collected)"}
     m["f_end"] = w.frame
+    if getattr(args, "dump_outputs", None) and gpu_cs:
+        m["dump"] = dump_outputs(args.dump_outputs, w, ids, gpu_cs[-1])
+        m["dump"]["frame"] = m["f_end"]
     if not args.sync and not light:
         m["host_timeline"] = timeline_pass(w, run, min(K, 50))
     # ---- instrumented pass for the per-kernel roofline: HIP events riding on every dispatch (kernel begin / end, what rocprofv3's kernel
@@ -947,6 +975,7 @@ def single_line(bg, cm, torch, args, dev):
         "preheat": m.get("preheat"), "roofline": roof,
     }
     if m.get("traffic_passes"): line["roofline"]["traffic_passes"] = m["traffic_passes"]
+    if m.get("dump"): line["dump_outputs"] = m["dump"]
     if grouped and n * bps * (D + 1) <= (256 << 20):
         # the whole ring fits the 256 MB Infinity Cache: launch / latency bound ("report it but do not judge it against HBM peak")
         n_prof_ = max(min(K, 50), 1)
@@ -1204,6 +1233,7 @@ def extra_configs(bg, cm, torch, base_args, dev, budget_s=60.0):
     def mk(**over):
         a = copy.copy(base_args)
         a.preheat_ms, a.parity_ticks, a.cpu_ticks, a.parity_only, a.schema, a.sync, a.no_cpu_baseline = 40.0, 6, 1, True, "headline", False, False
+        a.dump_outputs = None                   # the dump is the headline's
         for k, v in over.items(): setattr(a, k, v)
         return a
 
@@ -1303,7 +1333,12 @@ def main():
     ap.add_argument("--no-traffic", action="store_true", help="headline: do not start the two rocprofv3 counter passes that put MEASURED HBM bytes per launch into roofline.traffic")
     ap.add_argument("--no-lazy-live", action="store_true", help="A/B: every tick writes the live block (the library's test hook ggrs_dbg_set_lazy_live)")
     ap.add_argument("--no-checksum", action="store_true", help="DIAGNOSTIC ONLY: no component checksums registered (isolates the hash ALU cost; not a valid bench line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed -- its checksums and the live "
+                    "world it left (a seeded sample of large worlds) -- as DIR/<name>.npy; the pre-heat then runs a fixed number of ticks "
+                    f"({PREHEAT_TICKS_PER_MS} per --preheat-ms millisecond) so that every run computes the same frames (N = 1 SyncTest line: configs 2 / 3)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.gpus > 1 or args.fanout or args.config in (4, 5)):
+        ap.error("--dump-outputs covers the N = 1 SyncTest line (configs 2 / 3) only")
     if args.no_lazy_live: os.environ["BENCH_NO_LAZY_LIVE"] = "1"
     default_headline = (args.config == 3 and args.entities == 1_000_000 and args.depth == 8 and args.schema == "headline" and not (args.fanout or args.sync or args.unfused or args.no_groups
                         or args.nt or args.no_checksum or args.no_cpu_baseline or args.branches != 1))
@@ -1329,7 +1364,11 @@ def main():
 
     import torch
     import __graft_entry__ as ge
-    ge.build()
+    try:
+        ge.build()
+    except PermissionError as e:
+        # a tree built by another user and read-only for this one: measure what it holds (the import below fails loudly if that is nothing)
+        print(f"bench.py: build() could not write the tree ({e}); running the libraries already built there", file=sys.stderr)
     import bevy_ggrs_amd as bg
     import common as cm
 

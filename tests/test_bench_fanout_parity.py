@@ -125,3 +125,34 @@ def test_latency_floor_reports_a_lower_bound_against_the_timed_tick_and_keeps_th
     assert not bad["consistent"] and bench.floors_inconsistent({"latency_floor": bad})
     plain = bench.latency_floor(6.7, 1.0, 10.0)                                                        # no same-pass figures: priced against the tick given
     assert plain["frac"] == [round(8.15 / 10.0, 3), round(8.6 / 10.0, 3)] and "frac_same_pass" not in plain
+
+
+def test_dump_outputs_writes_the_last_steps_checksums_and_a_bounded_state_sample(tmp_path):
+    """bench.py --dump-outputs on an oracle world (same accessors as the device world): the step's Checksum(u128)s come back exactly from their
+    32-bit limbs, every registered component is written for the same slots, a world beyond DUMP_SAMPLE is sampled with a fixed seed, and the
+    whole dump of the largest schema stays under 64 MB."""
+    import bench
+    for n, schema in ((1000, "headline"), (bench.DUMP_SAMPLE + 5000, "full")):
+        w = OracleWorld(n + 16, 9, FLAT)
+        ids = cm.build_particles(w, schema=schema)
+        vel, ttl = cm.synthetic_particles(n, ttl="throughput")
+        cm.spawn_particles(w, ids, n, vel, ttl)
+        for _ in range(3): w.advance((0,))
+        w.set_depth(2)
+        cs = [w.save() | (k << 100) for k in range(8)]
+        raw = b"".join(c.to_bytes(16, "little") for c in cs)
+        outs = []
+        for rep in range(2):
+            d = str(tmp_path / f"{schema}{rep}")
+            info = bench.dump_outputs(d, w, ids, raw)
+            assert info["bytes"] <= 64 << 20
+            got = {f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)}
+            assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+            limbs = got["checksums"].astype(np.uint64)
+            assert [sum(int(limbs[j, k]) << (32 * k) for k in range(4)) for j in range(8)] == cs
+            slot = got["slot"].astype(np.int64)
+            assert len(slot) == min(n, bench.DUMP_SAMPLE) and np.all(np.diff(slot) > 0)
+            assert np.array_equal(got["Velocity"][:, 0], vel[slot, 0]) and np.all(got["Ttl"][:, 0] == (1 << 40) - 3)
+            assert {w._comps[c][0] for c in ids} <= set(got)
+            outs.append(got)
+        assert all(np.array_equal(outs[0][k], outs[1][k]) for k in outs[0])

@@ -367,7 +367,6 @@ def test_branch_lists_dead_snapshots_and_batches(n, flags, per_request, monkeypa
     targets a frame INSIDE the group's saves (not dead) and when a branch spawns (never dead)."""
     if per_request:                                            # the same lists without the run-time compiler: one launch per request, nothing eliminated
         monkeypatch.setenv("GGRS_TICK_JIT", "0")
-        if n > 100_000: pytest.skip("one big size is enough for the per-request path")
     D, B = 4, 6
     vel, ttl = cm.synthetic_particles(n, ttl="despawn")
     fn = cm.frame_spawn_fn(60)

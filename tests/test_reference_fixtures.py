@@ -1,8 +1,9 @@
 """Parity against the REAL bevy_ggrs.  tests/golden/reference_checksums.json is produced by the Rust fixture run (rust/fixtures:
 real bevy_ggrs 0.22 + ggrs under the reference's own SyncTest harness, fed this repo's synthetic inputs; rust/fixtures/README.md has
-the one-command run line).  No Rust toolchain exists in the builder's image, so the file is absent there and these tests SKIP; the
+the one-command run line).  No Rust toolchain exists in the builder's image, so the file is absent there and the oracle tests SKIP; the
 day it exists they are what turns "parity unpinned by the reference" into a pinned oracle: every Checksum(u128) the reference saved
-for a frame must equal the CPU oracle's -- and, under -m gpu, the HIP path's -- for that frame.
+for a frame must equal the CPU oracle's -- and, under -m gpu, the HIP path's -- for that frame.  The HIP tests run the fixture's
+scenarios (the recipe's parameters, RECIPE) against the CPU oracle whether or not the dump exists, and against the dump when it does.
 
 Scenarios (keys of the JSON): BASELINE configs 2 / 3 (stress_test at 10 k / 1 M, check distance 8), config 4's rollback shapes (100 k,
 one SyncTest session per rollback length 1..7), two despawn scenarios (tests/synctest.rs:26-75 with despawn() / despawn_rollback()) and
@@ -23,15 +24,49 @@ PARTICLES.update({f"config4_rollback_{r}": (100_000, "config3") for r in range(1
 DESPAWN = ("despawn_immediate", "despawn_rollback")
 
 
-def _load(case):
+def _box_initial_translation_bits(players=2):
+    """setup_system (box_game.rs:89-143): cube `handle` on a circle of radius PLANE_SIZE / 4 (cos / sin of numpy's libm; the dump carries the reference's)."""
+    rot = np.arange(players, dtype=np.float32) / np.float32(players) * np.float32(2.0) * np.float32(np.pi)
+    r = np.float32(5.0) / np.float32(4.0)
+    xyz = np.stack([r * np.cos(rot).astype(np.float32), np.full(players, np.float32(0.2) / np.float32(2.0)), r * np.sin(rot).astype(np.float32)], axis=1)
+    return cm.f32bits(xyz).tolist()
+
+
+# the scenarios of rust/fixtures (tests/dump_reference_checksums.rs, dump()) without what only the reference can say
+RECIPE = {"config2_particles_10k": {"entities": 10_000, "check_distance": 8, "ticks": 24},
+          "config3_particles_1m": {"entities": 1_000_000, "check_distance": 8, "ticks": 12},
+          "despawn_immediate": {"entities": 64, "check_distance": 5, "ticks": 30, "deferred": False},
+          "despawn_rollback": {"entities": 64, "check_distance": 5, "ticks": 30, "deferred": True},
+          "config1_box_game": {"players": 2, "check_distance": 7, "input_delay": 2, "ticks": 40, "initial_translation_bits": _box_initial_translation_bits()}}
+RECIPE.update({f"config4_rollback_{r}": {"entities": 100_000, "check_distance": r, "ticks": 16} for r in range(1, 8)})
+
+
+def _dump():
     if not os.path.exists(GOLDEN):
-        pytest.skip("tests/golden/reference_checksums.json is absent: run rust/fixtures (README.md there) on a machine with a Rust toolchain")
+        return {}
     doc = json.load(open(GOLDEN))
-    if case not in doc:
-        pytest.skip(f"{case} is not in the dump (config1_box_game needs `--features box_game`)")
     assert "after SaveWorldSystems::Snapshot" in doc.get("recorder", ""), \
         "this dump was made by the round-3 recorder, which was not ordered after ChecksumPlugin::update: regenerate it"
+    return doc
+
+
+def _load(case):
+    doc = _dump()
+    if not doc:
+        pytest.skip("tests/golden/reference_checksums.json is absent: run rust/fixtures (README.md there) on a machine with a Rust toolchain")
+    if case not in doc:
+        pytest.skip(f"{case} is not in the dump (config1_box_game needs `--features box_game`)")
     return doc[case]
+
+
+def _scenario(case):
+    """The reference's dump of `case` when there is one, else the recipe's parameters (no `saves`)."""
+    return _dump().get(case) or RECIPE[case]
+
+
+def _assert_same_checksums(case, got, want):
+    bad = [f for f in sorted(want) if got.get(f) != want[f]]
+    assert set(got) == set(want) and not bad, f"{case}: HIP and the CPU oracle differ at frames {bad[:8]} (of {len(want)})"
 
 
 def _first_saves(ref):
@@ -113,11 +148,19 @@ def test_oracle_equals_the_reference_particles(case):
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", sorted(PARTICLES))
 def test_hip_equals_the_reference_particles(case):
-    ref = _load(case)
+    from oracle.binding import FLAT, OracleWorld, lib as olib
+    ref = _scenario(case)
     n, tag = PARTICLES[case]
     tag_n = 10_000 if tag == "config2" else 1_000_000
-    got = _run_particles(bg.World(n, max_depth=ref["check_distance"] + 1), n, tag_n, ref["check_distance"], ref["ticks"])
-    _compare(case, _first_saves(ref), got)
+    cd, ticks = ref["check_distance"], ref["ticks"]
+    got = _run_particles(bg.World(n, max_depth=cd + 1), n, tag_n, cd, ticks)
+    olib.gor_set_num_threads(max(1, min(32, len(os.sched_getaffinity(0)))))
+    try:
+        want = _run_particles(OracleWorld(n, cd + 1, FLAT), n, tag_n, cd, ticks)
+    finally:
+        olib.gor_set_num_threads(max(1, min(8, len(os.sched_getaffinity(0)))))
+    _assert_same_checksums(case, got, want)
+    if "saves" in ref: _compare(case, _first_saves(ref), got)
 
 
 def _run_despawn(world, ref):
@@ -149,10 +192,15 @@ def test_oracle_equals_the_reference_despawn(case):
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", DESPAWN)
 def test_hip_equals_the_reference_despawn(case):
-    ref = _load(case)
+    from oracle.binding import FLAT, OracleWorld
+    ref = _scenario(case)
     got, alive = _run_despawn(bg.World(ref["entities"], max_depth=ref["check_distance"] + 1), ref)
-    assert alive == ref["alive_after_tick"]
-    _compare(case, _first_saves(ref), got)
+    want, want_alive = _run_despawn(OracleWorld(ref["entities"], ref["check_distance"] + 1, FLAT), ref)
+    assert alive == want_alive, f"{case}: live entities per tick differ from the CPU oracle's"
+    _assert_same_checksums(case, got, want)
+    if "saves" in ref:
+        assert alive == ref["alive_after_tick"]
+        _compare(case, _first_saves(ref), got)
 
 
 def _run_box_game(world, ref):
@@ -192,9 +240,14 @@ def test_oracle_equals_the_reference_box_game():
 
 @pytest.mark.gpu
 def test_hip_equals_the_reference_box_game():
-    ref = _load("config1_box_game")
+    from oracle.binding import FLAT, OracleWorld
+    ref = _scenario("config1_box_game")
     got = _run_box_game(bg.World(8, max_depth=ref["check_distance"] + 2), ref)
-    for t, (ours, theirs) in enumerate(zip(got, ref["after_tick"])):
+    want = _run_box_game(OracleWorld(8, ref["check_distance"] + 2, FLAT), ref)
+    assert len(got) == ref["ticks"]
+    for t, (ours, theirs) in enumerate(zip(got, want)):
+        assert ours == theirs, f"box_game (HIP): tick {t}: cube bits differ from the CPU oracle's"
+    for t, (ours, theirs) in enumerate(zip(got, ref.get("after_tick", []))):
         assert ours == theirs["cubes"], f"box_game (HIP): tick {t}: cube bits differ"
 
 
