@@ -224,6 +224,8 @@ JitSig jit_steady_sig(const ggrs_world* w) {
 int launch_jit(ggrs_world* w, hipFunction_t fn, uint32_t gx, uint32_t gy, uint32_t gz, uint32_t lds, GgrsJitArgs& j, uint64_t bytes, hipEvent_t done = nullptr) {
     w->spin_n = 0;                                               // a finalize before this launch is no longer the list's last GPU operation (arm_spin)
     ff_attach(w, j);
+    const bool streamed = w->dev_spawn && jit_dev_stream(w);
+    if (streamed) { j.sp_ticket_base = w->sp_ticket_base; w->sp_ticket_base += (uint64_t)(gx + j.ff_blocks) * gy * gz; }   // every workgroup takes one ticket
     j.skip_count = (w->prof && j.vtags) ? reinterpret_cast<ggrs_u64*>(w->d_skip) : nullptr;
     jit_pack(*w->jl, j, w->jit_argbuf.data());
     void* params[] = {w->jit_argbuf.data()};
@@ -233,7 +235,9 @@ int launch_jit(ggrs_world* w, hipFunction_t fn, uint32_t gx, uint32_t gy, uint32
         // spawns decided on the device: the workgroups meet inside -- a COOPERATIVE launch (every workgroup resident, the runtime lets no second one in beside it)
         hipEvent_t a = nullptr, b = nullptr;
         if (w->prof) { a = w->prof_event(); b = w->prof_event(); if (!a || !b) return w->fail(GGRS_E_HIP, "hipEventCreate failed"); w->prof_bytes[GGRS_KERNEL_TICK] += bytes; HIPCHK(w, hipEventRecord(a, w->stream)); }
-        HIPCHK(w, hipModuleLaunchCooperativeKernel(fn, gx, gy, gz, TPB, 1, 1, lds, w->stream, params));
+        // (the streamed form: an ordinary launch of any size -- its workgroups only ever wait on lower tickets)
+        if (streamed) HIPCHK(w, hipModuleLaunchKernel(fn, gx, gy, gz, TPB, 1, 1, lds, w->stream, params, nullptr));
+        else HIPCHK(w, hipModuleLaunchCooperativeKernel(fn, gx, gy, gz, TPB, 1, 1, lds, w->stream, params));
         if (w->prof) { HIPCHK(w, hipEventRecord(b, w->stream)); w->prof_events.push_back({a, b, GGRS_KERNEL_TICK}); }
         if (done) HIPCHK(w, hipEventRecord(done, w->stream));
         w->len_stale = true;
@@ -552,10 +556,17 @@ int run_request_groups_gen(ggrs_world* w, const ggrs_request* reqs, uint32_t n, 
         bytes_slot += rows_bytes_per_slot(w, j.load_rows, !j.src_is_live);
         j.src = gs.src->ptr; j.live = w->live.ptr; j.len = len_start;
         if (w->dev_spawn) {
+            const bool streamed = jit_dev_stream(w);
             if (w->sp_epoch > 0xF0000000u) {         // epochs never repeat: long before the 32-bit counter wraps (~65 M launches) the mailboxes start over, in stream order
-                HIPCHK(w, hipMemsetAsync(w->d_sp_sums, 0, (3 * (size_t)w->sp_tiles + 32) * 8, w->stream)); w->sp_epoch = 0;
+                if (streamed) {                      // (the descriptors, the records' flag words and the pool cursor; never the ticket counter)
+                    HIPCHK(w, hipMemsetAsync(w->d_sp_desc, 0, sp_desc_bytes(w), w->stream));
+                    HIPCHK(w, hipMemsetAsync(w->d_sp_recs, 0, sp_recs_bytes(w), w->stream));
+                    HIPCHK(w, hipMemsetAsync(w->d_sp_ctl + 1, 0, 8, w->stream));
+                } else HIPCHK(w, hipMemsetAsync(w->d_sp_sums, 0, (3 * (size_t)w->sp_tiles + 32) * 8, w->stream));
+                w->sp_epoch = 0;
             }
-            j.sp_sums = reinterpret_cast<ggrs_u64*>(w->d_sp_sums); j.sp_epoch = w->sp_epoch; w->sp_epoch += 2u * MAX_TICK_STEPS + 2u;
+            j.sp_sums = reinterpret_cast<ggrs_u64*>(w->d_sp_sums); j.sp_epoch = w->sp_epoch; w->sp_epoch += streamed ? MAX_TICK_STEPS + 2u : 2u * MAX_TICK_STEPS + 2u;
+            j.sp_ctl = reinterpret_cast<ggrs_u64*>(w->d_sp_ctl); j.sp_desc = reinterpret_cast<ggrs_u64*>(w->d_sp_desc); j.sp_recs = reinterpret_cast<ggrs_u64*>(w->d_sp_recs);
             j.sp_prec = w->d_sp_prec; j.sp_link = reinterpret_cast<ggrs_u64*>(w->d_sp_link);
             j.sp_len = reinterpret_cast<ggrs_u64*>(w->d_sp_len); j.sp_cap = w->capacity; j.sp_tiles = w->sp_tiles;
         }
@@ -635,7 +646,7 @@ int run_request_groups_gen(ggrs_world* w, const ggrs_request* reqs, uint32_t n, 
                 // the batch event of an enqueued list then completes WITH it (no marker packet between this tick's kernel and the next one's)
                 const bool last_gpu_op = (host_fold || ff || !j.n_saves) && !spawn_req && !w->prof;
                 hipEvent_t done = last_gpu_op ? w->batch_ev : nullptr;
-                rc = launch_jit(w, fn, jit_grid(g), j.dp_s ? (j.n_saves + j.dp_s) / j.dp_s : 1u, 1, jit_lane_fold_bytes(w, n_cks, j.n_saves), j, bytes_slot * w->len, done); if (rc) return rc;
+                rc = launch_jit(w, fn, w->dev_spawn && jit_dev_stream(w) ? g : jit_grid(g), j.dp_s ? (j.n_saves + j.dp_s) / j.dp_s : 1u, 1, jit_lane_fold_bytes(w, n_cks, j.n_saves), j, bytes_slot * w->len, done); if (rc) return rc;
                 w->batch_ev_attached = done != nullptr;
             }
             group_close(w, gs, j.n_saves, dead, wrote_live);

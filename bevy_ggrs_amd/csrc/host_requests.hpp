@@ -649,11 +649,11 @@ int len_sync(ggrs_world* w) {
     if (!w->dev_spawn || !w->len_stale || !w->h_sp_len) return GGRS_OK;
     HIPCHK(w, hipStreamSynchronize(w->stream));
     w->len_stale = false;
-    const uint64_t err = w->h_sp_len[1];
+    const uint64_t err = w->h_sp_len[1], tmo = w->h_sp_len[2 + MAX_TICK_SAVES];
     const uint64_t l_ = w->h_sp_len[0]; w->len = l_ < w->capacity ? l_ : w->capacity;
     w->live.dirty_len = std::max(w->live.dirty_len, w->len);
-    if (err) {
-        w->h_sp_len[1] = 0;
+    if (err || tmo) {                                            // (both: the capacity is the cause, a wait after it may have timed out)
+        w->h_sp_len[1] = 0; w->h_sp_len[2 + MAX_TICK_SAVES] = 0;
         return err == 1 ? w->fail(GGRS_E_CAPACITY, "entities spawned by the schedule's systems (e.spawn) exceed the world's capacity of %llu: that frame's spawns were dropped", (unsigned long long)w->capacity)
                         : w->fail(GGRS_E_HIP, "a grid barrier of a device-spawn launch timed out (the launch was not resident as a whole?)");
     }

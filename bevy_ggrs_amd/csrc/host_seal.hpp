@@ -15,12 +15,20 @@ void arena_release(ggrs_world* w) {
     w->arena = nullptr; w->arena_bytes = 0; w->own_arena = false;
 }
 
+// the streamed device-spawn form's arrays (ggrs_world::d_sp_desc, d_sp_recs): what seal allocates and an epoch start-over zeroes (the descriptors and record
+// offsets per step and tile, then one "has read its starting len" word per tile)
+size_t sp_desc_bytes(const ggrs_world* w) { return (2 * (size_t)MAX_TICK_STEPS + 1) * w->sp_tiles * 8; }
+size_t sp_recs_bytes(const ggrs_world* w) { return (size_t)w->capacity * 9 * 8; }
 void sp_release(ggrs_world* w) {
     if (w->d_sp_sums) (void)hipFree(w->d_sp_sums);
     if (w->d_sp_prec) (void)hipFree(w->d_sp_prec);
     if (w->d_sp_link) (void)hipFree(w->d_sp_link);
     if (w->h_sp_len) (void)hipHostFree((void*)w->h_sp_len);
     w->d_sp_sums = nullptr; w->d_sp_prec = nullptr; w->d_sp_link = nullptr; w->h_sp_len = nullptr; w->d_sp_len = nullptr;
+    if (w->d_sp_ctl) (void)hipFree(w->d_sp_ctl);
+    if (w->d_sp_desc) (void)hipFree(w->d_sp_desc);
+    if (w->d_sp_recs) (void)hipFree(w->d_sp_recs);
+    w->d_sp_ctl = nullptr; w->d_sp_desc = nullptr; w->d_sp_recs = nullptr;
 }
 int seal(ggrs_world* w) {
     if (w->layout_only) return w->fail(GGRS_E_NO_DEVICE, "GGRS_WORLD_LAYOUT_ONLY world: there is no device behind it");
@@ -247,7 +255,8 @@ int seal_impl(ggrs_world* w) {
     }
     if (w->vtags) { HIPCHK(w, hipMalloc((void**)&w->d_skip, 8)); HIPCHK(w, hipMemsetAsync(w->d_skip, 0, 8, w->stream)); }
     if (w->dev_spawn) {
-        // every launch of such a world covers its whole capacity and must be resident as a whole (grid barriers inside): what the device holds of this kernel bounds the world
+        // every launch of such a world covers its whole capacity.  The RESIDENT form must be resident as a whole (grid barriers inside): where the device cannot hold
+        // its grid, the world takes the STREAMED form instead (kernel_gen.hpp jit_dev_stream: tiles by ticket, children numbered by look-back), any size
         w->sp_tiles = (uint32_t)(((w->capacity + 63) / 64 + 3) / 4);                 // == the workgroups that own a tile when a launch covers `capacity` slots
         int per_cu = 0;
         HIPCHK(w, hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, w->jit_fn, TPB, jit_lane_fold_bytes(w, w->cks_args.n_cks, w->cap_saves)));
@@ -259,17 +268,42 @@ int seal_impl(ggrs_world* w) {
         w->sp_regs = (int)regs; w->sp_per_cu = per_cu;
         const uint64_t max_wgs = (uint64_t)std::max(per_cu, 0) * (uint64_t)w->n_cu;
         const uint32_t grid = 8u * ((w->sp_tiles + 7u) / 8u);
-        if (grid > max_wgs)
-            return w->fail(GGRS_E_CAPACITY, "a world whose systems spawn on the device runs as ONE resident launch: %u workgroups are needed for %llu slots, the device holds %llu of this kernel (at most %llu slots)",
-                           grid, (unsigned long long)w->capacity, (unsigned long long)max_wgs, (unsigned long long)(max_wgs / 8 * 8 * 256));
+        if (!jit_dev_stream(w) && grid > max_wgs) {
+            // a second text and a second compile (cached on disk like the first): the streamed form's argument block has fields of its own
+            w->sp_streamed = true;
+            std::string src;
+            if (!jit_source(w, src)) return w->fail(GGRS_E_INVALID, "the kernel generator does not cover the streamed device-spawn form of this world");
+            if (jit_cached(w, src, &w->jit_fn, &w->jit_entry, &w->jit_origin) != GGRS_OK) return w->fail(GGRS_E_INVALID, "the streamed device-spawn kernel was rejected: %s", w->err.substr(0, 300).c_str());
+            w->jit_src = src;
+            delete w->jl; w->jl = new JitLayout(jit_layout(w));
+            w->cap_saves = w->jl->cap_saves; w->cap_steps = w->jl->cap_steps;
+            w->jit_argbuf.assign(w->jl->bytes, 0);
+            w->sp_regs = w->jit_entry ? (int)w->jit_entry->vgprs : 0; w->sp_sregs = w->jit_entry ? (int)w->jit_entry->sgprs : 0;
+        }
+        // [0] len of the live world, [1] children beyond the capacity (the resident form: 2 = a timed-out wait), [2 + k] len at Save k, [2 + MAX_TICK_SAVES] a
+        // timed-out wait of the streamed form (each word only ever receives one value inside a launch: no atomics on host memory)
+        HIPCHK(w, hipHostMalloc((void**)&w->h_sp_len, (3 + MAX_TICK_SAVES) * 8, hipHostMallocMapped));
+        HIPCHK(w, hipHostGetDevicePointer((void**)&w->d_sp_len, (void*)w->h_sp_len, 0));
+        for (int k = 0; k < 3 + MAX_TICK_SAVES; ++k) w->h_sp_len[k] = 0;
+    }
+    if (w->dev_spawn && jit_dev_stream(w)) {
+        // (a step's child count travels in 31 bits, record offsets and tiles in 32)
+        if (w->capacity >= (1ull << 31)) return w->fail(GGRS_E_CAPACITY, "the streamed device-spawn form numbers children in 31 bits: capacity %llu is too large", (unsigned long long)w->capacity);
+        // the ticket counter and the record-pool cursor; the look-back descriptors and the parent tiles' record offsets, per step and tile; one record per child slot
+        HIPCHK(w, hipMalloc((void**)&w->d_sp_ctl, 64));
+        HIPCHK(w, hipMemsetAsync(w->d_sp_ctl, 0, 64, w->stream));
+        HIPCHK(w, hipMalloc((void**)&w->d_sp_desc, sp_desc_bytes(w)));
+        HIPCHK(w, hipMemsetAsync(w->d_sp_desc, 0, sp_desc_bytes(w), w->stream));
+        HIPCHK(w, hipMalloc((void**)&w->d_sp_recs, sp_recs_bytes(w)));
+        HIPCHK(w, hipMemsetAsync(w->d_sp_recs, 0, sp_recs_bytes(w), w->stream));
+        w->sp_ticket_base = 0;
+        w->sp_epoch = 0xF0000000u - 8u * (MAX_TICK_STEPS + 2u) + 1u;           // (the start-over on the 9th launch, as below)
+    } else if (w->dev_spawn) {
         HIPCHK(w, hipMalloc((void**)&w->d_sp_sums, (3 * (size_t)w->sp_tiles + 32) * 8));                 // the mailbox words {epoch, value}: counts, prefixes, done per tile; total; go
         HIPCHK(w, hipMemsetAsync(w->d_sp_sums, 0, (3 * (size_t)w->sp_tiles + 32) * 8, w->stream));
         w->sp_epoch = 0xF0000000u - 8u * (2u * MAX_TICK_STEPS + 2u) + 1u;      // (like jiffies: every world crosses the epochs' start-over on its 9th launch, so that path is run by every test and session)
         HIPCHK(w, hipMalloc((void**)&w->d_sp_prec, 2 * (size_t)std::max<uint64_t>(w->cap_pad, (uint64_t)w->sp_tiles * 256u) * 64));       // the parents' records, one set per step parity
         HIPCHK(w, hipMalloc((void**)&w->d_sp_link, (size_t)w->cap_pad * 16));
-        HIPCHK(w, hipHostMalloc((void**)&w->h_sp_len, (2 + MAX_TICK_SAVES) * 8, hipHostMallocMapped));
-        HIPCHK(w, hipHostGetDevicePointer((void**)&w->d_sp_len, (void*)w->h_sp_len, 0));
-        for (int k = 0; k < 2 + MAX_TICK_SAVES; ++k) w->h_sp_len[k] = 0;
     }
     HIPCHK(w, hipStreamSynchronize(w->stream));
     w->sealed = true;

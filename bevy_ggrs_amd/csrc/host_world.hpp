@@ -71,6 +71,8 @@ struct Knobs {
     std::string aot_dir;           // GGRS_AOT_DIR          shipped code objects (`make -C bevy_ggrs_amd/csrc aot`): looked up by source hash before the run-time compiler is asked
                                    //                       ("" = <directory of libggrs_hip.so>/aot; "0": none)
     bool no_hiprtc = false;        // GGRS_NO_HIPRTC=1      behave as if libhiprtc.so were absent (tests of the shipped-code-object path)
+    bool dev_spawn_streamed = false; // GGRS_TICK_JIT=2      as 1, and device-spawn worlds take the streamed form (tiles by ticket, decoupled look-back) even where the
+                                   //                       resident form fits (comparisons, tests); worlds the device cannot hold as one resident grid take it anyway
     static Knobs from_env() {
         Knobs k;
         auto num = [](const char* n, long long dflt) { const char* v = getenv(n); return v ? atoll(v) : dflt; };
@@ -84,6 +86,7 @@ struct Knobs {
         k.debug_poison = num("GGRS_DEBUG_POISON", 0) != 0;
         k.debug_jit = (int)num("GGRS_DEBUG_JIT", 0);
         k.no_hiprtc = num("GGRS_NO_HIPRTC", 0) != 0;
+        k.dev_spawn_streamed = num("GGRS_TICK_JIT", 1) == 2;
         if (const char* v = getenv("GGRS_JIT_CACHE_DIR")) k.jit_cache_dir = v;
         if (const char* v = getenv("GGRS_AOT_DIR")) k.aot_dir = v;
         return k;
@@ -214,6 +217,11 @@ struct ggrs_world {
     bool dev_spawn = false; bool len_stale = false;
     uint64_t* d_sp_sums = nullptr; uint8_t* d_sp_prec = nullptr; uint64_t* d_sp_link = nullptr;
     volatile uint64_t* h_sp_len = nullptr; uint64_t* d_sp_len = nullptr; uint32_t sp_tiles = 0, sp_epoch = 0; int sp_regs = 0, sp_sregs = 0, sp_per_cu = 0;
+    // the STREAMED form (sp_streamed: GGRS_TICK_JIT=2, or a world the device cannot hold as one resident grid): an ordinary launch whose workgroups take
+    // their tiles by ticket.  d_sp_ctl = {ticket counter (zeroed at seal, never reset), record-pool cursor {epoch, used}}; d_sp_desc = the look-back descriptors
+    // [MAX_TICK_STEPS][tiles], then where each tile's child records start [MAX_TICK_STEPS][tiles]; d_sp_recs = the child records (9 words each, `capacity` of them)
+    bool sp_streamed = false;
+    uint64_t* d_sp_ctl = nullptr; uint64_t* d_sp_desc = nullptr; uint64_t* d_sp_recs = nullptr; uint64_t sp_ticket_base = 0;
     std::vector<uint64_t> off_present, col_off;   // col_off: block-relative offset of the column's row in tile 0 (component words first, then the Stored words of strategy components)
     std::vector<uint32_t> col_wb, col_ts;          // word bytes / tile stride of every column (kernels.hpp col_at)
     std::vector<uint8_t> col_rb;                   // column is part of a rollback component (snapshotted)

@@ -218,6 +218,11 @@ struct GgrsJitArgs {
     // sp_link[child slot] = {parent slot, k}).  sp_sums = the rendezvous' mailboxes, one {epoch, value} word each: counts[tiles], prefixes[tiles], done[tiles],
     // total (at 3 x tiles), go (at 3 x tiles + 16); sp_epoch = this launch's first epoch (2 per step): no word is ever reset
     ggrs_u64* sp_sums; ggrs_u32 sp_epoch; unsigned char* sp_prec; ggrs_u64* sp_link; ggrs_u64* sp_len; ggrs_u64 sp_cap; ggrs_u32 sp_tiles;
+    // ... the STREAMED form (jit_dev_stream: an ordinary launch, any grid size): a workgroup's tile is its ticket (sp_ctl[0] counts every workgroup ever started,
+    // sp_ticket_base = the count before this launch); per step, children are numbered by a decoupled look-back over sp_desc[step][tile] {epoch, inclusive?, count}
+    // and each parent tile writes one record per child into sp_recs (9 words: the parent's bound words, then {epoch, k}) at a place it reserves from the pool
+    // cursor sp_ctl[1]; sp_desc[MAX_TICK_STEPS + step][tile] says where.  Epochs: sp_epoch + 1 + step, the cursor's sp_epoch + MAX_TICK_STEPS + 1
+    ggrs_u64* sp_ctl; ggrs_u64* sp_desc; ggrs_u64* sp_recs; ggrs_u64 sp_ticket_base;
     ggrs_u32 cached_saves;                           // with nt: bit i = Save i is stored through the L2 all the same (the snapshot the NEXT group is expected to load)
     ggrs_u32 ff_blocks, ff_nvals, ff_g, ff_stride, ff_istride, ff_split, ff_self;   // entry e of row r: ff_rows[r * ff_stride + e * ff_istride]
     ggrs_u32 dt_bits[24], aux_bits[24]; int step_frame[24], step_confirmed[24]; ggrs_u32 spawn_count[24];
@@ -242,7 +247,7 @@ struct JitLayout {
     struct Member { uint32_t bytes = 0, save_dst = 0, save_rows = 0, save_len = 0, spawn_payload = 0, spawn_first = 0, live = 0, live_rows = 0, save_pmask = 0, live_pmask = 0,
                     spawn_count = 0, n_inputs = 0, inputs = 0, save_tagok = 0, live_tagok = 0; } m;
 };
-struct JitNeeds { bool spawn, inputs, marks, box, vtags, devspawn; };
+struct JitNeeds { bool spawn, inputs, marks, box, vtags, devspawn, devstream; };
 JitNeeds jit_needs(const ggrs_world* w);
 // the device-side layout of this world's argument block: 8-byte fields first, then 4-byte, then bytes (no padding inside)
 JitLayout jit_layout(const ggrs_world* w) {
@@ -272,8 +277,10 @@ JitLayout jit_layout(const ggrs_world* w) {
         FA("int", save_frame, S, true); FA("ggrs_u32", save_pmask, S, true);
         F1("ggrs_u32", live_pmask, true); F1("ggrs_u32", nt_loads, true); F1("ggrs_u32", n_ops, true); F1("ggrs_u32", n_saves, true); F1("ggrs_u32", n_steps, true);
         F1("ggrs_u32", src_is_live, true); F1("ggrs_u32", skip_live, true); F1("ggrs_u32", dp_s, true); F1("ggrs_u32", part_stride, true); F1("ggrs_u32", part_tstride, true); F1("ggrs_u32", nt, true);
-        F1("ggrs_u64*", sp_sums, need.devspawn); F1("ggrs_u32", sp_epoch, need.devspawn); F1("unsigned char*", sp_prec, need.devspawn); F1("ggrs_u64*", sp_link, need.devspawn);
+        const bool resident = need.devspawn && !need.devstream;
+        F1("ggrs_u64*", sp_sums, resident); F1("ggrs_u32", sp_epoch, need.devspawn); F1("unsigned char*", sp_prec, resident); F1("ggrs_u64*", sp_link, resident);
         F1("ggrs_u64*", sp_len, need.devspawn); F1("ggrs_u64", sp_cap, need.devspawn);
+        F1("ggrs_u64*", sp_ctl, need.devstream); F1("ggrs_u64*", sp_desc, need.devstream); F1("ggrs_u64*", sp_recs, need.devstream); F1("ggrs_u64", sp_ticket_base, need.devstream);
         F1("ggrs_u32", n_units, true); F1("ggrs_u32", sp_tiles, need.devspawn); F1("ggrs_u32", vtags, need.vtags); F1("ggrs_u32", tag_base, need.vtags); F1("ggrs_u32", cached_saves, true); F1("ggrs_u32", ff_blocks, true); F1("ggrs_u32", ff_nvals, true); F1("ggrs_u32", ff_g, true); F1("ggrs_u32", ff_stride, true); F1("ggrs_u32", ff_istride, true); F1("ggrs_u32", ff_split, true); F1("ggrs_u32", ff_self, true);
         FS("ggrs_u32", dt_bits, true); FS("ggrs_u32", aux_bits, need.box); FS("int", step_frame, true); FS("int", step_confirmed, need.marks);
         FS("ggrs_u32", spawn_count, need.spawn);
@@ -466,11 +473,14 @@ bool jit_dev_spawn(const ggrs_world* w) {
     const int sp = jit_fused_spawn_system(w);
     return sp >= 0 && w->systems[sp].kind == GGRS_SYS_SPAWN_CUSTOM && w->spawn_customs[w->systems[sp].comp[0]].payload_stride == SPAWN_PAYLOAD_PARENT;
 }
+// ... in the streamed form: forced (GGRS_TICK_JIT=2), or chosen at seal because the device cannot hold the resident form's grid
+bool jit_dev_stream(const ggrs_world* w) { return jit_dev_spawn(w) && (w->sp_streamed || w->knobs.dev_spawn_streamed); }
 // which optional parts of the argument block this world's kernel reads
 JitNeeds jit_needs(const ggrs_world* w) {
-    JitNeeds n{false, false, false, false, false, false};
+    JitNeeds n{false, false, false, false, false, false, false};
     n.vtags = vtags_policy(w);
     n.devspawn = jit_dev_spawn(w);
+    n.devstream = jit_dev_stream(w);
     n.spawn = jit_fused_spawn_system(w) >= 0;
     for (auto& d : w->systems) {
         n.inputs |= d.kind == GGRS_SYS_CUSTOM || d.kind == GGRS_SYS_BOX_MOVE || d.kind == GGRS_SYS_SPAWN_CUSTOM;
@@ -498,6 +508,7 @@ bool jit_source(const ggrs_world* w, std::string& s) {
     const JitNeeds need = jit_needs(w);
     const bool marks = need.marks;
     const bool DEV = need.devspawn;                                  // spawns decided on the device (GGRS_SPAWN_PAYLOAD_PARENT): len lives on the device, the launch is cooperative
+    const bool STREAM = need.devstream;                              // ... or, in the streamed form, an ordinary launch of any size: tiles by ticket, children numbered by look-back
     bool lds_inputs = false;                                         // user code indexes PlayerInputs (possibly by a handle it read from a component): the bytes go through LDS
     for (auto& d : w->systems) {
         switch (d.kind) {
@@ -584,6 +595,30 @@ bool jit_source(const ggrs_world* w, std::string& s) {
          "namespace ggrs {\n";
     s += kJitPrelude;
     s += "\n}\nusing namespace ggrs;\n";
+    if (STREAM)
+        s += "// STREAMED device spawns: the grid need not be resident as a whole.  PROGRESS RULE: a workgroup only ever waits on a strictly lower ticket, or on its own\n"
+             "// workgroup behind a __syncthreads() that follows the writes.  A workgroup's tile IS its ticket (taken first thing), so the lowest unfinished ticket never\n"
+             "// waits on anyone that has not started; the look-back, the end-of-world tile's descriptor and a parent's child records all sit at lower or equal tiles.\n"
+             "// Every wait is bounded by the wall clock, as sp_await.  A descriptor {epoch:32 | inclusive:1 | count:31}: a tile posts its own count, looks back\n"
+             "// (64 predecessors per probe) until it meets an inclusive prefix, then posts its own inclusive prefix\n"
+             "__device__ __forceinline__ bool sp_await_inc(ggrs_u64* p, ggrs_u32 ep, ggrs_u32& v, unsigned long long t0_) {\n"
+             "    for (;;) {\n"
+             "        const ggrs_u64 x_ = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
+             "        if ((ggrs_u32)(x_ >> 32) == ep && (x_ & 0x80000000ull)) { v = (ggrs_u32)x_ & 0x7FFFFFFFu; return true; }\n"
+             "        if (wall_clock64() - t0_ > 100000000ull) return false;\n"
+             "        __builtin_amdgcn_s_sleep(1);\n"
+             "    }\n"
+             "}\n"
+             "// the grid's last tile, before it writes RollbackOrdered::len into the block every tile read its starting len from (a group run in place): every other tile\n"
+             "// has posted that it read it (one word per tile, a lower ticket each; wave-parallel, 64 per probe)\n"
+             "__device__ __forceinline__ bool sp_gate(ggrs_u64* f, uint32_t n, ggrs_u32 ep, uint32_t lane) {\n"
+             "    const unsigned long long t0_ = wall_clock64();\n"
+             "    for (uint32_t b_ = 0; b_ < n; b_ += 64u) { uint32_t v_ = 0; const bool g_ = b_ + lane >= n || sp_await(f + b_ + lane, ep, v_, t0_); if (__ballot(!g_) != 0ull) return false; }\n"
+             "    return true;\n"
+             "}\n";
+    if (STREAM) sfmt(s, "#define GGRS_SP_TIMEOUT %uu                                                        // sp_len[GGRS_SP_TIMEOUT] = 1: a wait timed out (sp_len[1] = 1: children beyond the capacity)\n"
+                        "#define GGRS_SP_READ %uu                                                           // sp_desc[GGRS_SP_READ x tiles + tile]: that tile has read its starting len\n",
+                     2u + (unsigned)MAX_TICK_SAVES, 2u * (unsigned)MAX_TICK_STEPS);
     s += GGRS_FRAME_TEXT;
     s += GGRS_ENTITY_TEXT;
     s += GGRS_COMPONENT_TEXT;
@@ -615,9 +650,15 @@ bool jit_source(const ggrs_world* w, std::string& s) {
         s += "\n}\n";
     }
     s += "#line 1 \"ggrs_jit_tick\"\n";
-    sfmt(s, "extern \"C\" __global__ __launch_bounds__(256) void ggrs_jit_tick(GgrsJitArgs a) {\n"
-            "    const uint32_t tid = threadIdx.x, lane = tid & 63u;\n"
-            "    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));   // wave-uniform, and the compiler knows it\n"
+    s += "extern \"C\" __global__ __launch_bounds__(256) void ggrs_jit_tick(GgrsJitArgs a) {\n"
+         "    const uint32_t tid = threadIdx.x, lane = tid & 63u;\n"
+         "    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));   // wave-uniform, and the compiler knows it\n";
+    if (STREAM)
+        s += "    // STREAMED: this workgroup's tile is its ticket -- the order in which workgroups START, whatever order the dispatcher picks (no fold-forward role here)\n"
+             "    __shared__ uint32_t s_tk;\n"
+             "    if (tid == 0) s_tk = (uint32_t)(atomicAdd((unsigned long long*)a.sp_ctl, 1ull) - a.sp_ticket_base);\n"
+             "    __syncthreads();\n";
+    else sfmt(s,
             "    // FOLD-FORWARD role: the first ff_blocks workgroups (a multiple of 8: the XCD mapping below is unchanged) do not own a tile -- each folds one row\n"
             "    // of partials the PREVIOUS launch on this stream left in device memory and hands the value, then its tag, to the host\n"
             "    if (blockIdx.x < a.ff_blocks) {\n"
@@ -629,7 +670,8 @@ bool jit_source(const ggrs_world* w, std::string& s) {
             "        }\n"
             "        return;\n"
             "    }\n"
-            "    const uint32_t bx = blockIdx.x - a.ff_blocks, gx = gridDim.x - a.ff_blocks;\n"
+            "    const uint32_t bx = blockIdx.x - a.ff_blocks, gx = gridDim.x - a.ff_blocks;\n", n_cks + 1, n_cks);
+    sfmt(s,
             "    // batch members (blockIdx.z) with records: what differs between the launch's groups comes from member z's record, the rest from the argument block\n"
             "    const GGRS_K unsigned char* const mb = a.mtab ? (const GGRS_K unsigned char*)(unsigned long)(a.mtab + (uint64_t)blockIdx.z * %uull) : (const GGRS_K unsigned char*)0ul;\n"
             "    const bool writes_live = (!a.src_is_live || a.n_steps) && !a.skip_live;\n"
@@ -641,7 +683,7 @@ bool jit_source(const ggrs_world* w, std::string& s) {
             "    __shared__ ggrs_u64 s_acc[16 * %u];\n"
             "%s"
             "    for (uint32_t i = tid; i < 16u * %uu; i += 256u) s_acc[i] = 0;\n",
-         n_cks + 1, n_cks, L.m.bytes, n_cks + 1,
+         L.m.bytes, n_cks + 1,
          vtags_policy(w) ? "    __shared__ ggrs_u64 s_skip;                                                // value tags, profiling: bytes this workgroup's Saves did not store\n    if (tid == 0) s_skip = 0;\n" : "",
          n_cks + 1);
     if (lane_fold) sfmt(s, "    extern __shared__ ggrs_u64 s_lane[];                                  // [Save][checksummed component][lane]: a.n_saves * %u * 64 cells (dynamic LDS)\n"
@@ -649,6 +691,12 @@ bool jit_source(const ggrs_world* w, std::string& s) {
     if (lds_inputs && IN_STRIDE)
         sfmt(s, "    __shared__ unsigned char s_in[%u * %u];                                  // PlayerInputs of every step of the group: [step][%u players x %u bytes | %u status bytes]\n"
                 "    for (uint32_t i = tid; i < a.n_steps * %uu; i += 256u) s_in[i] = mb ? (unsigned char)mb_u8(mb, %uu + i) : a.inputs[i / %uu][i %% %uu];\n", L.cap_steps, IN_STRIDE, MAXP, IB, MAXP, IN_STRIDE, L.m.inputs, IN_STRIDE, IN_STRIDE);
+    if (STREAM) s += "    __syncthreads();\n"
+                     "    const uint32_t tile = s_tk;                                               // ticket order == tile order (no XCD remap: look-back needs it)\n"
+                     "    if (tile * 4u >= a.n_units) return;\n"
+                     "    {\n"
+                     "    const uint32_t gu = tile * 4u + wave;                                     // this wave's 64-slot unit == its mask word\n";
+    else
     s += "    __syncthreads();\n"
          "    // XCD-aware tile mapping: workgroup b runs on XCD b % 8 (observed placement; used for speed only), and each XCD has its own\n"
          "    // L2.  Handing XCD x the x-th CONTIGUOUS eighth of the tiles makes the workgroups that write neighbouring 1 KiB pieces of a\n"
@@ -671,6 +719,22 @@ bool jit_source(const ggrs_world* w, std::string& s) {
          DEV ? "    uint64_t cur_len = *reinterpret_cast<const uint64_t*>(a.src);                // RollbackOrdered::len as the source block's header says: with spawns decided on the device the host only knows a bound\n"
                    "    __shared__ uint64_t s_sp[16];                                              // the workgroup's spawn bookkeeping of one step\n" : "",
          spawn_sys >= 0 ? "" : "const ", DEV ? "cur_len" : "a.len", spawn_sys >= 0 ? " (a spawn inside the group grows len)" : "", LT_SHIFT - 6, w->ts, (unsigned)(LAYOUT_TILE / 64 - 1));
+    if (STREAM)
+        s += "    // Only tiles at or above the END of the world -- the tile of slot len - 1 -- can hold children, and only they learn each step's total (from that tile's\n"
+             "    // descriptor: a lower ticket).  A tile below it stays below it (len only grows inside a group), has parents at most, and never needs the total: its\n"
+             "    // cur_len goes stale and it writes no len anywhere.  trk_: this tile still tracks cur_len exactly; the grid's last tile always does and writes it\n"
+             "    bool trk_ = tile >= (uint32_t)(cur_len ? (cur_len - 1u) >> 8 : 0u);\n"
+             "    const bool len_wr = tile == a.sp_tiles - 1u && wave == 0u && lane == 0u;         // the one lane that writes RollbackOrdered::len (headers, sp_len)\n"
+             "    const uint64_t len0_ = cur_len;                                                  // len at the launch's start: exact in every tile\n"
+             "    bool gated_ = false;                                                             // (the last tile: every tile has read its starting len)\n"
+             "    // tile 0 starts the record-pool cursor over (before its first descriptor: every reservation of this launch follows a look-back that reaches one of\n"
+             "    // tile 0's); every tile then says it has read its starting len\n"
+             "    asm volatile(\"s_waitcnt vmcnt(0)\" ::: \"memory\");\n"
+             "    __syncthreads();\n"
+             "    if (tid == 0) {\n"
+             "        if (tile == 0u) { (void)__hip_atomic_exchange(a.sp_ctl + 1, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); asm volatile(\"s_waitcnt vmcnt(0)\" ::: \"memory\"); }\n"
+             "        sp_post(a.sp_desc + (uint64_t)GGRS_SP_READ * a.sp_tiles + tile, a.sp_epoch + 1u + GGRS_SP_READ, 1u);\n"
+             "    }\n";
     // ---- masks and words of the lane's slot
     sfmt(s, "    const uint64_t mk_alive = *reinterpret_cast<const uint64_t*>(a.src + %lluull + wi8);\n"
             "    bool alive_0 = (mk_alive >> sh) & 1ull;\n", OFF_ALIVE);
@@ -907,12 +971,17 @@ bool jit_source(const ggrs_world* w, std::string& s) {
             "                const uint32_t pmask_s = mb ? mb_u32(mb, %uu + 4u * si) : a.save_pmask[si];\n", L.m.save_dst, L.m.save_rows, L.m.save_pmask);
     { char te[96]; snprintf(te, sizeof te, "(mb ? mb_u64(mb, %uu + 8u * si) : a.save_tagok[si])", L.m.save_tagok); emit_tag_filter("dst", "rows", te, "                ", "dtv[si]"); }
     emit_store("dst", "rows", "pmask_s", "alive_now", "                ", true);
-    sfmt(s, "                if (gu == 0 && lane == 0) {\n"
+    if (STREAM) sfmt(s, "                if (tile == a.sp_tiles - 1u && wave == 0u && !gated_ && (const unsigned char*)%s == a.src) {   // a write to the block every tile read len from\n"
+            "                    gated_ = true;\n"
+            "                    if (!sp_gate(a.sp_desc + (uint64_t)GGRS_SP_READ * a.sp_tiles, a.sp_tiles - 1u, a.sp_epoch + 1u + GGRS_SP_READ, lane) && lane == 0) a.sp_len[GGRS_SP_TIMEOUT] = 1ull;\n"
+            "                }\n", "dst");
+    sfmt(s, "                if (%s) {\n"
             "                    Header h; h.len = %s; h.frame = a.save_frame[si]; h.pad0 = 0; h.active = 0; h.checksum[0] = 0; h.checksum[1] = 0;\n"
             "                    *reinterpret_cast<Header*>(dst) = h;\n"
             "                }\n"
-            "            }\n", DEV ? "cur_len" : (std::string("mb ? mb_u64(mb, ") + std::to_string(L.m.save_len) + "u + 8u * si) : a.save_len[si]").c_str());
-    if (DEV) s += "            if (gu == 0 && lane == 0) a.sp_len[2u + si] = cur_len;                        // RollbackOrdered::len at this Save: k_gen_finalize's entity checksum and the host read it here\n";
+            "            }\n", STREAM ? "len_wr" : "gu == 0 && lane == 0", DEV ? "cur_len" : (std::string("mb ? mb_u64(mb, ") + std::to_string(L.m.save_len) + "u + 8u * si) : a.save_len[si]").c_str());
+    if (STREAM) s += "            if (len_wr) a.sp_len[2u + si] = cur_len;                                   // RollbackOrdered::len at this Save: k_gen_finalize's entity checksum and the host read it here\n";
+    else if (DEV) s += "            if (gu == 0 && lane == 0) a.sp_len[2u + si] = cur_len;                        // RollbackOrdered::len at this Save: k_gen_finalize's entity checksum and the host read it here\n";
     sfmt(s, "            ggrs_u64* acc = s_acc + si * %uu;                                 // this Save's partials of the workgroup (LDS)\n", n_cks + 1);
     for (uint32_t k = 0; k < n_cks; ++k) {
         const uint32_t c = cks_comp[k];
@@ -952,6 +1021,7 @@ bool jit_source(const ggrs_world* w, std::string& s) {
             "            // ---------------- AdvanceWorld: the registered systems, in order\n"
             "            const float dt = __uint_as_float(a.dt_bits[sj]);\n", n_cks);
     if (DEV) s += "            uint32_t spn_0 = 0u;                                                       // children this entity's systems asked for in this frame (e.spawn(n))\n";
+    if (STREAM) s += "            ggrs_u64 pw_[8] = {0, 0, 0, 0, 0, 0, 0, 0};                               // ... and the bound words that call left: its children's payload\n";
     // value tags: around every system, the columns IT may write as they were before it ran -- a column whose 64 values are not all what they were carries a
     // fresh identity from here on (wave-uniform; per system, so that at most one write set of old values is alive at a time)
     // (a step only RECORDS which columns changed -- one compare per column and scalar bookkeeping; the identities are renewed where they are needed, at the next store)
@@ -1045,7 +1115,11 @@ bool jit_source(const ggrs_world* w, std::string& s) {
                     "                GgrsEntity ent; ent.slot = e0; ent.kill = 0; ent.spawn_n = 0;\n", d.comp[0]);
             for (uint32_t b = 0; b < 8; ++b) { if (b < c.n_bind) sfmt(s, "                ent.w[%u] = w%u_0;\n", b, col(c.comp[b], c.word[b])); else if (DEV) sfmt(s, "                ent.w[%u] = 0;\n", b); }
             sfmt(s, "                ggrs_sys_%u::ggrs_system(ent, fr%zu);\n", d.comp[0], i);
-            if (DEV) s += "                if (ent.spawn_n) {                                        // e.spawn(n): the children are made after the frame's systems, from what THIS call left in e\n"
+            if (STREAM) s += "                if (ent.spawn_n) {                                        // e.spawn(n): the children are made after the frame's systems, from what THIS call left in e\n"
+                             "                    spn_0 = (uint32_t)ent.spawn_n;\n"
+                             "                    for (int b_ = 0; b_ < 8; ++b_) pw_[b_] = ent.w[b_];                 // (written to the children's records once their slots are known)\n"
+                             "                }\n";
+            else if (DEV) s += "                if (ent.spawn_n) {                                        // e.spawn(n): the children are made after the frame's systems, from what THIS call left in e\n"
                           "                    spn_0 = (uint32_t)ent.spawn_n;\n"
                           "                    GGRS_G ggrs_u64* pr_ = (GGRS_G ggrs_u64*)(a.sp_prec + ((uint64_t)(sj & 1u) * a.sp_tiles * 256u + e0) * 64u);   // two sets of records, by step parity: see the children's read\n"
                           "                    for (int b_ = 0; b_ < 8; ++b_) __hip_atomic_store(pr_ + b_, (ggrs_u64)ent.w[b_], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // sc1: read by another workgroup, maybe another XCD, later in this launch\n"
@@ -1070,7 +1144,105 @@ bool jit_source(const ggrs_world* w, std::string& s) {
         uint64_t bundle = 0;
         if (custom) bundle = w->spawn_customs[d.comp[0]].bundle_mask; else bundle = (1ull << d.comp[0]) | (1ull << d.comp[1]) | (1ull << d.comp[2]);
         if (custom) emit_frame("fr_spawn", d.fparam, d.iparam);
-        if (DEV) {
+        if (STREAM) {
+            // How many, and whose -- streamed: the same exclusive scan over wave and workgroup; then, per step, a decoupled look-back over the tiles' descriptors
+            // (slot order == RollbackOrdered order, as in the resident form).  A parent tile reserves one record per child from the pool and writes the parent's
+            // bound words, then {epoch, k}, into each; a lane whose slot falls among the step's new rows finds its parent's tile by the inclusive prefixes (a binary
+            // search over tiles at or below the end of the world) and polls its own record.  The end-of-world tile's inclusive prefix is the step's total: tiles
+            // above it read that one descriptor.  Children beyond the capacity: those tiles ignore the records (nothing spawns), the end-of-world tile tells the host
+            s += "            uint64_t sn_ = 0, sf_ = cur_len;\n"
+                    "            unsigned long long kk_ = 0;\n"
+                    "            ggrs_u64 prec_[8] = {0, 0, 0, 0, 0, 0, 0, 0};                              // the payload of a child: its parent's record, fetched past this XCD's L2 (sc1)\n"
+                    "            {\n"
+                    "                uint32_t inc_ = spn_0;                                                 // inclusive scan over the wave's 64 lanes\n"
+                    "                for (int o_ = 1; o_ < 64; o_ <<= 1) { const uint32_t up_ = __shfl_up(inc_, o_, 64); if ((int)lane >= o_) inc_ += up_; }\n"
+                    "                const uint32_t wtot_ = (uint32_t)__builtin_amdgcn_readlane((int)inc_, 63);\n"
+                    "                __syncthreads();                                                       // (s_sp of the previous step has been read by everyone)\n"
+                    "                if (lane == 0) s_sp[wave] = wtot_;\n"
+                    "                __syncthreads();\n"
+                    "                uint32_t wg_excl_ = 0, wg_tot_ = 0;\n"
+                    "                for (uint32_t q_ = 0; q_ < 4u; ++q_) { const uint32_t v_ = (uint32_t)s_sp[q_]; wg_tot_ += v_; if (q_ < wave) wg_excl_ += v_; }\n"
+                    "                const uint32_t T_ = a.sp_tiles, ep_ = a.sp_epoch + 1u + sj;\n"
+                    "                ggrs_u64* const dsc_ = a.sp_desc + (uint64_t)sj * T_;                  // this step's descriptors, one per tile\n";
+            sfmt(s, "                ggrs_u64* const rof_ = a.sp_desc + (uint64_t)(%uu + sj) * T_;          // {epoch, first record} of each parent tile of this step\n", (unsigned)MAX_TICK_STEPS);
+            s += "                const unsigned long long tb_ = wall_clock64();\n"
+                    "                const uint32_t own_ = (uint32_t)(cur_len ? (cur_len - 1u) >> 8 : 0u);   // the end of the world (exact where trk_)\n"
+                    "                if (tile < own_) trk_ = false;\n"
+                    "                const bool above_ = trk_ && tile > own_;                               // no live slot: waits for the total instead of posting\n"
+                    "                if (wave == 0u) {\n"
+                    "                    bool ok_ = true; uint64_t exc_ = 0; uint32_t tot_ = 0;\n"
+                    "                    if (!above_) {\n"
+                    "                        if (lane == 0) sp_post(dsc_ + tile, ep_, min(wg_tot_, 0x7FFFFFFFu));      // the aggregate: what this tile adds\n"
+                    "                        for (uint32_t hi_ = tile; hi_ > 0u; hi_ = hi_ > 64u ? hi_ - 64u : 0u) {   // look back: lane l reads tile hi_ - 1 - l (all lower tickets)\n"
+                    "                            const bool in_ = lane < hi_;\n"
+                    "                            uint32_t v_ = 0;\n"
+                    "                            const bool got_ = !in_ || sp_await(dsc_ + (hi_ - 1u - lane), ep_, v_, tb_);\n"
+                    "                            if (__ballot(!got_) != 0ull) { ok_ = false; break; }\n"
+                    "                            const uint64_t incm_ = __ballot(in_ && (v_ & 0x80000000u));     // the nearest inclusive prefix ends the walk\n"
+                    "                            const uint32_t stop_ = incm_ ? (uint32_t)__builtin_ctzll(incm_) : 63u;\n"
+                    "                            uint64_t c_ = (in_ && lane <= stop_) ? (uint64_t)(v_ & 0x7FFFFFFFu) : 0ull;\n"
+                    "                            for (int o_ = 32; o_ > 0; o_ >>= 1) c_ += __shfl_xor(c_, o_, 64);\n"
+                    "                            exc_ += c_;\n"
+                    "                            if (incm_) break;\n"
+                    "                        }\n"
+                    "                        const uint32_t incl_ = exc_ + wg_tot_ < 0x7FFFFFFFull ? (uint32_t)(exc_ + wg_tot_) : 0x7FFFFFFFu;   // (saturated: beyond any capacity)\n"
+                    "                        if (lane == 0 && ok_) sp_post(dsc_ + tile, ep_, 0x80000000u | incl_);\n"
+                    "                        if (trk_ && tile == own_) tot_ = incl_;\n"
+                    "                    } else if (lane == 0) ok_ = sp_await_inc(dsc_ + own_, ep_, tot_, tb_);   // the end-of-world tile: a lower ticket\n"
+                    "                    if (lane == 0) { s_sp[4] = exc_; s_sp[5] = tot_; s_sp[6] = ok_ ? 1ull : 0ull; }\n"
+                    "                }\n"
+                    "                __syncthreads();\n"
+                    "                const bool ok1_ = s_sp[6] != 0ull;\n"
+                    "                uint64_t all_ = trk_ ? s_sp[5] : 0ull;                                  // the step's total, where known\n"
+                    "                if (!ok1_) { if (tid == 0) a.sp_len[GGRS_SP_TIMEOUT] = 1ull; all_ = 0; }   // a wait that timed out: the host is told\n"
+                    "                const bool over_ = trk_ && cur_len + all_ > a.sp_cap;\n"
+                    "                if (over_) { if (tile == own_ && tid == 0) a.sp_len[1] = 1ull; all_ = 0; }   // children beyond the world's capacity: nothing spawns\n"
+                    "                if (!above_ && !over_ && ok1_ && wg_tot_) {                            // a parent tile: its children's records\n";
+            s += "                    // one returning add on the pool cursor (started over by tile 0).  A tile whose inclusive prefix alone exceeds what len0_ leaves room for is in a step\n"
+                 "                    // beyond the capacity: it reserves nothing, so every step spends at most capacity - len0_ records of the pool (capacity records)\n"
+                 "                    if (tid == 0) {\n"
+                 "                        uint32_t o_ = 0xFFFFFFFFu;\n"
+                 "                        if (s_sp[4] + wg_tot_ <= a.sp_cap - len0_) {\n"
+                 "                            const ggrs_u64 at_ = __hip_atomic_fetch_add(a.sp_ctl + 1, (ggrs_u64)wg_tot_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
+                 "                            if (at_ + wg_tot_ <= a.sp_cap) o_ = (uint32_t)at_;\n"
+                 "                        }\n"
+                 "                        s_sp[7] = o_; sp_post(rof_ + tile, ep_, o_);\n"
+                 "                    }\n";
+            s += "                    __syncthreads();\n"
+                    "                    const uint32_t o_ = (uint32_t)s_sp[7];\n"
+                    "                    if (o_ != 0xFFFFFFFFu && spn_0) {\n"
+                    "                        GGRS_G ggrs_u64* const r_ = (GGRS_G ggrs_u64*)a.sp_recs + ((uint64_t)o_ + wg_excl_ + (inc_ - spn_0)) * 9u;\n"
+                    "                        for (uint32_t k_ = 0; k_ < spn_0; ++k_)\n"
+                    "                            for (int b_ = 0; b_ < 8; ++b_) __hip_atomic_store(r_ + 9u * k_ + b_, pw_[b_], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
+                    "                        asm volatile(\"s_waitcnt vmcnt(0)\" ::: \"memory\");                    // the words have arrived where every XCD reads them: then the flags\n"
+                    "                        for (uint32_t k_ = 0; k_ < spn_0; ++k_) __hip_atomic_store(r_ + 9u * k_ + 8u, ((ggrs_u64)ep_ << 32) | k_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
+                    "                    }\n"
+                    "                    asm volatile(\"s_waitcnt vmcnt(0)\" ::: \"memory\");\n"
+                    "                }\n"
+                    "                __syncthreads();                                                       // (this workgroup's own records are written before its children read them)\n"
+                    "                if (all_ && e0 >= cur_len && e0 < cur_len + all_) {                    // a child: find its parent's tile, then poll its own record\n"
+                    "                    const uint32_t r_ = (uint32_t)(e0 - cur_len);\n"
+                    "                    uint32_t lo_ = 0, hi_ = own_, ex_ = 0; bool okc_ = true;\n"
+                    "                    while (lo_ < hi_ && okc_) { const uint32_t m_ = (lo_ + hi_) >> 1; uint32_t v_ = 0; okc_ = sp_await_inc(dsc_ + m_, ep_, v_, tb_); if (v_ > r_) hi_ = m_; else { lo_ = m_ + 1u; ex_ = v_; } }\n"
+                    "                    uint32_t o_ = 0xFFFFFFFFu;\n"
+                    "                    if (okc_) okc_ = sp_await(rof_ + lo_, ep_, o_, tb_);\n"
+                    "                    if (okc_ && o_ != 0xFFFFFFFFu) {\n"
+                    "                        GGRS_G ggrs_u64* const rc_ = (GGRS_G ggrs_u64*)a.sp_recs + ((uint64_t)o_ + (r_ - ex_)) * 9u;\n"
+                    "                        uint32_t k32_ = 0;\n"
+                    "                        okc_ = sp_await((ggrs_u64*)(rc_ + 8u), ep_, k32_, tb_); kk_ = k32_;\n"
+                    "                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, \"wavefront\");                 // (no instruction: the record's loads stay behind the poll)\n"
+                    "                        if (okc_) for (int b_ = 0; b_ < 8; ++b_) prec_[b_] = __hip_atomic_load(rc_ + b_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
+                    "                    }\n"
+                    "                    if (!okc_) a.sp_len[GGRS_SP_TIMEOUT] = 1ull;\n"
+                    "                    else if (o_ == 0xFFFFFFFFu) a.sp_len[1] = 1ull;                    // (the pool only runs dry after a step beyond the capacity: already reported)\n"
+                    "                }\n"
+                    "                sn_ = all_;\n"
+                    "            }\n"
+                    "            if (sn_) {                                                                 // uniform over the tile\n"
+                    "                const unsigned char* const spay_ = (const unsigned char*)prec_;\n"
+                    "                if (e0 >= sf_ && e0 < sf_ + sn_) {\n"
+                    "                    alive_0 = true;\n";
+        } else if (DEV) {
             // How many, and whose: the entities that called e.spawn(n), in slot order (== RollbackOrdered order, so every rank and every replay numbers the children
             // alike).  Per step: an exclusive scan over the wave and the workgroup (LDS); every workgroup posts its count, workgroup 0 gathers them, scans them in
             // tile order and hands each workgroup its prefix and everyone the total; a parent then knows its children's slots and leaves {parent slot, k} where the
@@ -1211,7 +1383,12 @@ bool jit_source(const ggrs_world* w, std::string& s) {
             "        const uint32_t live_pm_v = mb ? mb_u32(mb, %uu) : a.live_pmask;\n", L.m.live, L.m.live_rows, L.m.live_pmask);
     { char te[96]; snprintf(te, sizeof te, "(mb ? mb_u64(mb, %uu) : a.live_tagok)", L.m.live_tagok); emit_tag_filter("live_p", "live_rows_v", te, "        ", "dtl"); }
     emit_store("live_p", "live_rows_v", "live_pm_v", "alive_now", "        ", false);
-    if (DEV) s += "        if (gu == 0 && lane == 0) { *reinterpret_cast<uint64_t*>(live_p) = cur_len; a.sp_len[0] = cur_len; }      // the live block's header carries RollbackOrdered::len for whoever loads it next; the host reads it from pinned memory\n";
+    if (STREAM) sfmt(s, "        if (tile == a.sp_tiles - 1u && wave == 0u && !gated_ && (const unsigned char*)%s == a.src) {   // a write to the block every tile read len from\n"
+            "            gated_ = true;\n"
+            "            if (!sp_gate(a.sp_desc + (uint64_t)GGRS_SP_READ * a.sp_tiles, a.sp_tiles - 1u, a.sp_epoch + 1u + GGRS_SP_READ, lane) && lane == 0) a.sp_len[GGRS_SP_TIMEOUT] = 1ull;\n"
+            "        }\n", "live_p");
+    if (STREAM) s += "        if (len_wr) { *reinterpret_cast<uint64_t*>(live_p) = cur_len; a.sp_len[0] = cur_len; }      // (the last tile: it tracks cur_len exactly)\n";
+    else if (DEV) s += "        if (gu == 0 && lane == 0) { *reinterpret_cast<uint64_t*>(live_p) = cur_len; a.sp_len[0] = cur_len; }      // the live block's header carries RollbackOrdered::len for whoever loads it next; the host reads it from pinned memory\n";
     s += "    }\n";
     if (marks) {
         s += "    if (my_live && a.n_steps) {\n"

@@ -253,9 +253,10 @@ int ggrs_hip_set_input_layout(ggrs_world* w, uint32_t input_bytes, uint32_t max_
  *     ggrs_spawn(e, k, f, payload)   with payload = the parent's record: the 8 x ggrs_u64 bound words of the system that called e.spawn(n), as that call left them.
  * ggrs_request::spawn_count and its payload fields are ignored for such a world.  RollbackOrdered::len then lives on the device: ggrs_hip_len and every entry point that
  * needs it waits for the world's stream first; children beyond the world's capacity are dropped and reported (GGRS_E_CAPACITY at the next collect / blocking call).
- * Every launch of such a world covers its whole capacity and is a COOPERATIVE launch (all workgroups resident: grid barriers inside), which bounds the capacity by what
- * the device holds of the world's kernel (GGRS_E_CAPACITY at seal beyond: 256 slots per workgroup x the workgroups resident per CU -- bounded by the kernel's VGPRs and SGPRs, 6 for the
- * splitting-cells world of the tests = 393 216 slots -- x 256 CUs); no depth-parallel roles, no branch steps. */
+ * Every launch of such a world covers its whole capacity.  Where the device holds the world's kernel as one resident grid (256 slots per workgroup x the workgroups
+ * resident per CU x the CUs), it is a COOPERATIVE launch (grid barriers inside); beyond that -- or with GGRS_TICK_JIT=2 -- seal takes the STREAMED form, an
+ * ordinary launch of any size whose workgroups take their tiles by ticket and number the children by a decoupled look-back over the tiles (a workgroup only ever waits
+ * on a lower ticket).  Same results, bit for bit; no depth-parallel roles, no branch steps in either form. */
 #define GGRS_SPAWN_PAYLOAD_PARENT 0xFFFFFFFFu
 typedef struct {
     const char* name;                               /* for error messages and traces; may be NULL                                  */

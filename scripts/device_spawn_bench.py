@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """What a tick costs a world whose systems SPAWN ON THE DEVICE (tests/test_gpu_device_spawn.py's splitting cells, e.spawn(n) + GGRS_SPAWN_PAYLOAD_PARENT): SyncTest
-depth 8, one cooperative launch per tick with a grid barrier per simulated frame (two in frames that spawn).  Timing only -- parity with the oracle is the test's job.
+depth 8, one launch per tick: the resident form (cooperative, a grid barrier per simulated frame, two in frames that spawn) where the device holds the
+world's grid, the streamed form (tiles by ticket, a look-back per frame) beyond it or under GGRS_TICK_JIT=2.  Timing only -- parity with the oracle is the test's job.
 Cells are re-seeded with long fuses so that the population splits throughout the run.  usage: device_spawn_bench.py [entities ...]"""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,7 +30,8 @@ def run(n, D=8, ticks=150):
     w.profile_enable(True)
     for _ in range(20): drv.tick((0,))
     prof = w.profile_read(); w.profile_enable(False)
-    return {"entities_start": n, "capacity": 4 * n + 256, "depth": D, "ticks": ticks, "us_per_tick_blocking_api": round(secs / ticks * 1e6, 1), "len_start": len0, "len_end": w.len,
+    form = "streamed" if w.kernel_info()["device_spawn"].startswith("one streamed") else "resident"      # (GGRS_TICK_JIT=2 forces the streamed form)
+    return {"entities_start": n, "form": form, "capacity": 4 * n + 256, "depth": D, "ticks": ticks, "us_per_tick_blocking_api": round(secs / ticks * 1e6, 1), "len_start": len0, "len_end": w.len,
             "kernel_us_mean": round(prof["tick"][0] / max(prof["tick"][1], 1) * 1e3, 2), "launches_per_tick": prof["tick"][1] / 20,
             "entity_frames_per_s": round((len0 + w.len) / 2 * (D + 1) * ticks / secs / 1e9, 2), "unit": "G entity-frames/s (mean len x 9 AdvanceWorlds per tick)"}
 
