@@ -810,6 +810,8 @@ int ggrs_hip_world_kernel_info(ggrs_world* w, char* buf, uint64_t cap, uint64_t*
                                    : cover <= JIT_NT_MIN_SLOTS ? "off (the world fits the caches: the live block's bytes are not what bounds the launch)"
                                    : "on after " + std::to_string(LAZY_LIVE_STREAK) + " lists in a row that open with a LoadGameState: " + std::to_string(w->lazy_skips) + " lists left it unwritten, " +
                                      std::to_string(w->lazy_materialised) + " materialised on demand");
+        add("deferred_saves", std::string(lazy_live_possible(w) && !w->has_strategy && defer_saves_on(w) ? "on" : "off") + " (rollback groups of the same sessions store their first Save only): " +
+                              std::to_string(w->saves_deferred) + " Saves deferred, " + std::to_string(w->slots_materialised) + " ring slots materialised on demand");
         add("group_caps", std::to_string(w->cap_saves) + " saves / " + std::to_string(w->cap_steps) + " steps");
         bool any_spawn = false;
         for (auto& sd : w->systems) any_spawn |= sd.kind == GGRS_SYS_PARTICLES_SPAWN || sd.kind == GGRS_SYS_SPAWN_CUSTOM;

@@ -322,6 +322,7 @@ int ggrs_hip_fanout_adopt(ggrs_fanout* f, uint32_t branch, int32_t frame, uint32
     ggrs_world* w = f->w;
     DeviceGuard dg(w);
     if (n_checksums_out) *n_checksums_out = 0;
+    { const int mrc = materialise_slots(w); if (mrc) return f->fail(mrc, "%s", ggrs_hip_last_error(w)); }   // the ring is edited below without the request runner
     if (f->head != f->tail || f->slot[f->tail % FANOUT_MAX_INFLIGHT].n_steps || !w->pending.empty())
         return f->fail(GGRS_E_INVALID, "adopt while steps are in flight: collect them first");
     if (!f->last_branches) return f->fail(GGRS_E_INVALID, "adopt without a preceding ggrs_hip_fanout_step_branches");

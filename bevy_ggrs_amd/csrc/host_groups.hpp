@@ -42,6 +42,10 @@ struct GroupState {
     uint64_t live_rows = 0;                           // columns the group's live write handles
     // (the versions Save k's slot holds once the group has run live in w->group_save_ver, [k][column]: no allocation per group)
 };
+// deferred Saves (below)
+inline bool slot_is_stale(const ggrs_world* w, const Block* b);
+int materialise_slots(ggrs_world* w);
+inline int slot_stale_on_store(ggrs_world* w, Block* d);
 // LoadGameState opens a group: the ring slot becomes the source (schedule_systems.rs:238-250)
 int group_open(ggrs_world* w, const ggrs_request* reqs, uint32_t& i, GroupState& g) {
     g.src = &w->live; g.cover = w->live.dirty_len; g.src_is_live = 1;
@@ -49,6 +53,10 @@ int group_open(ggrs_world* w, const ggrs_request* reqs, uint32_t& i, GroupState&
     trace_request(w, reqs[i]);
     apply_synctest_confirmed(w);
     w->frame = reqs[i].frame;
+    if ((int64_t)reqs[i].frame > w->defer_first && (int64_t)reqs[i].frame <= w->defer_last) w->defer_streak = 0; else ++w->defer_streak;
+    w->defer_first = w->defer_last = 0;
+    for (size_t k = 0; k < w->ring_frame.size(); ++k)                     // a deferred Save is loaded: its bytes first
+        if (w->ring_frame[k] == reqs[i].frame && slot_is_stale(w, &w->slots[w->ring_slot[k]])) { const int mrc = materialise_slots(w); if (mrc) return mrc; break; }
     if (!ring_rollback(w, reqs[i].frame))
         return w->fail(GGRS_E_NO_SNAPSHOT, "Could not rollback to %d: no snapshot at that moment could be found.", reqs[i].frame);
     g.src = &w->slots[w->ring_slot.front()];
@@ -91,6 +99,7 @@ int group_save(ggrs_world* w, GroupState& g, uint32_t k, uint8_t** save_dst, int
     int sl = -1;
     int rc = ring_push(w, w->frame, &sl); if (rc) return rc;
     Block* d = sl >= 0 ? &w->slots[sl] : nullptr;
+    rc = slot_stale_on_store(w, d); if (rc) return rc;
     g.dsts[k] = d;
     save_dst[k] = d ? d->ptr : nullptr;
     save_frame[k] = w->frame;
@@ -265,8 +274,10 @@ int launch_jit(ggrs_world* w, hipFunction_t fn, uint32_t gx, uint32_t gy, uint32
 hipFunction_t jit_spec_for(ggrs_world* w, const GgrsJitArgs& j, bool members = false) {
     if (!w->knobs.jit_specialise_after || w->jit_src.empty() || !j.n_saves || !j.n_ops) return nullptr;
     if (w->dev_spawn) return nullptr;              // (a cooperative launch must be resident as a whole: the world was sized against the GENERAL kernel's occupancy at seal)
-    for (uint32_t k = 0; k < j.n_saves && !members; ++k)
-        if (!j.save_dst[k] || j.save_rows[k] != j.save_rows[0] || j.save_pmask[k] != j.save_pmask[0]) return nullptr;
+    // (a Save without a destination stores nothing -- the copy tests the destination at run time -- so only the stored ones must agree: deferred Saves)
+    if (!members && !j.save_dst[0]) return nullptr;
+    for (uint32_t k = 1; k < j.n_saves && !members; ++k)
+        if (j.save_dst[k] && (j.save_rows[k] != j.save_rows[0] || j.save_pmask[k] != j.save_pmask[0])) return nullptr;
     JitSig g; g.members = members ? 1u : 0u; g.vtags = j.vtags; g.op_bits = j.op_bits; g.save_rows = j.save_rows[0]; g.live_rows = j.live_rows; g.load_rows = j.load_rows; g.n_ops = j.n_ops; g.n_saves = j.n_saves;
     g.n_steps = j.n_steps; g.src_is_live = j.src_is_live; g.skip_live = j.skip_live; g.nt = j.nt; g.cached_saves = j.cached_saves; g.save_pmask = j.save_pmask[0]; g.live_pmask = j.live_pmask; g.dp_s = j.dp_s; g.nt_loads = j.nt_loads;
     auto building = [](const JitSpecSlot& s) { return s.spec && s.spec->state.load(std::memory_order_acquire) == 1; };
@@ -387,9 +398,101 @@ inline bool lazy_live_allowed(const ggrs_world* w) {                 // (what a 
     return true;
 }
 inline bool lazy_live_possible(const ggrs_world* w) { return w->gen_ok && !w->jit_marks && lazy_live_allowed(w); }
+
+// ---- deferred Saves ---------------------------------------------------------------------------------------------------------
+// The same rule for the ring.  Of the Saves of a steady tick  [Load(F - 8), Advance, (Save, Advance) x 8]  only the FIRST (F - 7) is ever read: the next tick opens
+// with Load(F - 7), which pops F - 6 .. F before anything could load them, and saves them again.  Only while the session's Loads keep landing on such a first Save
+// (defer_streak): a P2P session whose rollback length changes from tick to tick would load a deferred slot, and its replay costs more than the stores it saved.  A group of such a session (same streak, size and exclusions as the
+// lazy live block; no spawn, no Strategy -- a replay from the base would step from load(store(x))) therefore stores only its first Save: Save k of the group is DEFINED
+// as the base advanced by the group's recorded steps up to it (ggrs_world::SlotStale).  Its checksum is computed as before; only the store is left out (a null destination,
+// as in a checksum-only group).  Whoever needs a stale slot's bytes -- a Load of it (a P2P rollback of another length), the lazy live block whose source it is, a Save that
+// would overwrite the base, the fan-out -- gets every stale slot of the chain from ONE launch first: Load(base), (Advance, Save) up to the last stale one.
+inline bool defer_saves_on(const ggrs_world* w) { return w->lazy_live_on != 0 && w->lazy_live_on != 4; }
+// a stale entry whose slot no longer holds its frame in the ring (popped by a rollback, a confirm or an eviction) is needed by nobody
+inline void slot_stale_prune(ggrs_world* w) {
+    ggrs_world::SlotStale& c = w->slot_stale;
+    if (!c.valid) return;
+    bool any = false;
+    for (uint32_t k = 1; k < c.n; ++k) if (c.stale[k]) {
+        bool held = false;
+        for (size_t i = 0; i < w->ring_slot.size() && !held; ++i) held = &w->slots[w->ring_slot[i]] == c.dst[k] && w->ring_frame[i] == c.frame[k];
+        c.stale[k] = held; any |= held;
+    }
+    if (!any) c.valid = false;
+}
+inline bool slot_is_stale(const ggrs_world* w, const Block* b) {
+    const ggrs_world::SlotStale& c = w->slot_stale;
+    if (c.valid) for (uint32_t k = 1; k < c.n; ++k) if (c.stale[k] && c.dst[k] == b) return true;
+    return false;
+}
+int materialise_slots(ggrs_world* w) {
+    ggrs_world::SlotStale& c = w->slot_stale;
+    if (!c.valid) return GGRS_OK;
+    uint32_t last = 0;
+    for (uint32_t k = 1; k < c.n; ++k) if (c.stale[k]) last = k;
+    if (!last) { c.valid = false; return GGRS_OK; }
+    GgrsJitArgs j; memset(&j, 0, offsetof(GgrsJitArgs, inputs));
+    j.src = c.base->ptr; j.live = w->live.ptr; j.len = c.len[0]; j.src_is_live = 0; j.skip_live = 1;
+    j.load_rows = jit_static_reads(w);
+    const size_t nc = w->cur_ver.size();
+    const size_t in_row = std::min(sizeof c.inputs[0], sizeof j.inputs[0]);
+    uint64_t cover = std::max(c.base->dirty_len, c.len[0]), bytes = 0;
+    for (uint32_t k = 1; k <= last; ++k) {
+        for (uint32_t q = c.at[k - 1]; q < c.at[k]; ++q) {                // the steps between Save k - 1 and Save k, as the group ran them
+            const uint32_t s = j.n_steps++;
+            j.dt_bits[s] = c.dt_bits[q]; j.aux_bits[s] = c.aux_bits[q]; j.step_frame[s] = c.step_frame[q]; j.step_confirmed[s] = c.step_confirmed[q]; j.n_inputs[s] = c.n_inputs[q];
+            memcpy(j.inputs[s], c.inputs[q], in_row);
+            j.op_bits |= 1ull << j.n_ops; ++j.n_ops;
+        }
+        const uint32_t si = j.n_saves++; ++j.n_ops;
+        j.save_frame[si] = c.frame[k]; j.save_len[si] = c.len[k];
+        if (!c.stale[k]) continue;                                         // (superseded, or no longer in the ring: checksum only)
+        const Block& d = *c.dst[k];
+        const std::vector<ver_t> want(c.ver.begin() + (size_t)k * nc, c.ver.begin() + (size_t)(k + 1) * nc);
+        uint64_t m = 0;
+        for (uint32_t col = 0; col < w->n_tcols && col < 64; ++col) if (w->col_rb[col] && ver_differs(w, d, want, col)) m |= 1ull << col;
+        j.save_dst[si] = d.ptr; j.save_rows[si] = m; j.save_pmask[si] = pmask_differs(w, d, want);
+        j.load_rows |= m;
+        bytes += rows_bytes_per_slot(w, m, true) * c.len[k];
+        cover = std::max(cover, std::max(d.dirty_len, c.dirty[k]));
+    }
+    bytes += rows_bytes_per_slot(w, j.load_rows, true) * c.len[0];
+    j.vtags = w->vtags ? 1u : 0u;
+    if (j.vtags) {
+        const int trc = vtags_reserve(w, j.n_steps, 1, &j.tag_base); if (trc) return trc;
+        j.src_tagok = block_tagok(w, *c.base);
+        for (uint32_t k = 1, si = 0; k <= last; ++k, ++si) if (j.save_dst[si]) j.save_tagok[si] = block_tagok(w, *c.dst[k]);
+    }
+    j.parts = reinterpret_cast<ggrs_u64*>(w->d_gen_parts); j.part_stride = w->gen_part_stride; j.part_tstride = 1;   // (the checksums were returned by the group: these rows are dropped)
+    j.n_units = std::max<uint32_t>(1, (uint32_t)((cover + 63) / 64));
+    const uint32_t g = std::max<uint32_t>(1, (uint32_t)((cover + 255) / 256));
+    j.nt = cover > JIT_NT_MIN_SLOTS ? 1u : 0u; j.nt_loads = j.nt;
+    const int rc = launch_jit(w, w->jit_fn, jit_grid(g), 1, 1, jit_lane_fold_bytes(w, w->cks_args.n_cks, j.n_saves), j, bytes);
+    if (rc) return rc;
+    for (uint32_t k = 1, si = 0; k <= last; ++k, ++si) if (j.save_dst[si]) {
+        Block& d = *c.dst[k];
+        std::copy(c.ver.begin() + (size_t)k * nc, c.ver.begin() + (size_t)(k + 1) * nc, d.ver.begin());
+        d.dirty_len = c.dirty[k];
+        if (w->vtags) d.tag_ok |= j.save_rows[si] & w->tag_cols; else d.tag_ok &= ~j.save_rows[si];
+        c.stale[k] = false; ++w->slots_materialised;
+    }
+    c.valid = false;
+    return GGRS_OK;
+}
+// a Save of the group being assembled lands in `d`: a stale record of that slot is superseded; the base is materialised from before it is overwritten
+inline int slot_stale_on_store(ggrs_world* w, Block* d) {
+    ggrs_world::SlotStale& c = w->slot_stale;
+    if (!c.valid || !d) return GGRS_OK;
+    for (uint32_t k = 1; k < c.n; ++k) if (c.dst[k] == d) c.stale[k] = false;
+    if (d != c.base) return GGRS_OK;
+    slot_stale_prune(w);
+    return materialise_slots(w);
+}
+
 int materialise_live(ggrs_world* w) {
     ggrs_world::LiveStale& st = w->live_stale;
     if (!st.valid) return GGRS_OK;
+    if (slot_is_stale(w, st.src)) { const int src = materialise_slots(w); if (src) return src; }
     GgrsJitArgs j; memset(&j, 0, offsetof(GgrsJitArgs, inputs));
     j.src = st.src->ptr; j.live = w->live.ptr; j.len = st.len; j.src_is_live = 0;
     j.n_ops = 1; j.op_bits = 1; j.n_steps = 1;
@@ -434,6 +537,7 @@ int run_request_groups_gen(ggrs_world* w, const ggrs_request* reqs, uint32_t n, 
         w->batch_ev_attached = false;                                   // only the list's LAST launch may carry the batch event
         GgrsJitArgs j; memset(&j, 0, offsetof(GgrsJitArgs, inputs));
         GroupState gs;
+        uint32_t save_at[MAX_TICK_SAVES] = {};                          // steps the group had run at each Save
         const ggrs_request* spawn_req = nullptr;
         rc = group_open(w, reqs, i, gs); if (rc) return rc;
         j.src_is_live = gs.src_is_live;
@@ -444,7 +548,7 @@ int run_request_groups_gen(ggrs_world* w, const ggrs_request* reqs, uint32_t n, 
             if (r.kind == GGRS_REQ_SAVE) {
                 if (j.n_saves == w->cap_saves || (wait && ns + j.n_saves == w->max_results)) break;
                 rc = group_save(w, gs, j.n_saves, j.save_dst, j.save_frame); if (rc) return rc;
-                j.save_len[j.n_saves] = w->len;
+                j.save_len[j.n_saves] = w->len; save_at[j.n_saves] = j.n_steps;
                 ++j.n_ops; ++j.n_saves;
             } else if (r.kind == GGRS_REQ_ADVANCE) {
                 if (j.n_steps == w->cap_steps) break;
@@ -523,7 +627,7 @@ int run_request_groups_gen(ggrs_world* w, const ggrs_request* reqs, uint32_t n, 
         if (dead) { for (uint32_t k = 0; k < j.n_saves; ++k) j.save_dst[k] = nullptr; j.skip_live = 1; }
         const uint64_t cover = w->dev_spawn ? w->capacity : std::max(gs.cover, w->len);      // (device-decided spawns: the host only knows a bound of len)
         // lazy live block: the LAST group of a list that ends [.., Save(F), Advance] in a session whose lists keep opening with a Load
-        if (!dead && !spawn_req && i >= n && ((w->load_open_streak >= LAZY_LIVE_STREAK && cover > JIT_NT_MIN_SLOTS) || w->lazy_live_on == 2) && j.n_ops >= 2 && j.n_saves && j.n_steps &&
+        if (!dead && !spawn_req && i >= n && ((w->load_open_streak >= LAZY_LIVE_STREAK && cover > JIT_NT_MIN_SLOTS) || w->lazy_live_on == 2 || w->lazy_live_on == 3) && j.n_ops >= 2 && j.n_saves && j.n_steps &&
             ((j.op_bits >> (j.n_ops - 1)) & 1ull) && !((j.op_bits >> (j.n_ops - 2)) & 1ull) && gs.dsts[j.n_saves - 1] && !j.spawn_count[j.n_steps - 1] &&
             gs.dsts[j.n_saves - 1] != gs.src && lazy_live_possible(w)) {
             j.skip_live = 1;
@@ -533,6 +637,41 @@ int run_request_groups_gen(ggrs_world* w, const ggrs_request* reqs, uint32_t n, 
             st.dt_bits = j.dt_bits[q]; st.aux_bits = j.aux_bits[q]; st.step_frame = j.step_frame[q]; st.step_confirmed = j.step_confirmed[q]; st.n_inputs = j.n_inputs[q];
             if (w->jit_reads_inputs) memcpy(st.inputs, j.inputs[q], sizeof st.inputs); else memset(st.inputs, 0, sizeof st.inputs);
             ++w->lazy_skips;
+        }
+        // deferred Saves: a rollback group of the same steady session stores its first Save only (ggrs_world::SlotStale).  Every destination a slot of its own, none
+        // the source (the replay reads the base while it writes the others), one step at least between two Saves, no spawn anywhere in the group
+        if (!j.src_is_live && j.n_saves >= 2) { w->defer_first = j.save_frame[0]; w->defer_last = j.save_frame[j.n_saves - 1]; }
+        if (!dead && !spawn_req && !j.src_is_live && j.n_saves >= 2 && defer_saves_on(w) &&
+            ((w->load_open_streak >= LAZY_LIVE_STREAK && w->defer_streak >= LAZY_LIVE_STREAK && cover > JIT_NT_MIN_SLOTS) || w->lazy_live_on == 3) && lazy_live_possible(w) && !w->has_strategy) {
+            bool ok = true;
+            for (uint32_t k = 0; k < j.n_saves && ok; ++k) {
+                ok = gs.dsts[k] && gs.dsts[k] != gs.src && (k == 0 || save_at[k] > save_at[k - 1]);
+                for (uint32_t q = 0; q < k && ok; ++q) ok = gs.dsts[k] != gs.dsts[q];
+            }
+            for (uint32_t q = 0; q < j.n_steps && ok; ++q) ok = !j.spawn_count[q];
+            if (ok) {
+                slot_stale_prune(w);                                        // what the previous chain still owes the ring is filled before its record is replaced
+                rc = materialise_slots(w); if (rc) return rc;
+                ggrs_world::SlotStale& c = w->slot_stale;
+                const size_t nc = w->cur_ver.size();
+                const uint64_t new_dirty = std::max(gs.src->dirty_len, w->len);      // (what group_close gives a stored destination)
+                c.valid = true; c.base = gs.dsts[0]; c.n = j.n_saves;
+                if (c.ver.size() < (size_t)MAX_TICK_SAVES * nc) c.ver.resize((size_t)MAX_TICK_SAVES * nc);
+                const uint32_t s0 = save_at[0];
+                c.len[0] = j.save_len[0]; c.at[0] = 0;
+                for (uint32_t k = 1; k < j.n_saves; ++k) {
+                    c.dst[k] = gs.dsts[k]; c.stale[k] = true; c.at[k] = save_at[k] - s0;
+                    c.frame[k] = j.save_frame[k]; c.len[k] = j.save_len[k]; c.dirty[k] = new_dirty;
+                    std::copy(w->group_save_ver.begin() + (size_t)k * nc, w->group_save_ver.begin() + (size_t)(k + 1) * nc, c.ver.begin() + (size_t)k * nc);
+                    gs.dsts[k] = nullptr; j.save_dst[k] = nullptr;             // group_close leaves the slot's versions, extent and tags as they are: they describe its bytes
+                    ++w->saves_deferred;
+                }
+                for (uint32_t q = s0; q < save_at[j.n_saves - 1]; ++q) {
+                    const uint32_t r = q - s0;
+                    c.dt_bits[r] = j.dt_bits[q]; c.aux_bits[r] = j.aux_bits[q]; c.step_frame[r] = j.step_frame[q]; c.step_confirmed[r] = j.step_confirmed[q]; c.n_inputs[r] = j.n_inputs[q];
+                    if (w->jit_reads_inputs) memcpy(c.inputs[r], j.inputs[q], std::min(sizeof c.inputs[r], sizeof j.inputs[q])); else memset(c.inputs[r], 0, sizeof c.inputs[r]);
+                }
+            }
         }
         const bool wrote_live = (!j.src_is_live || j.n_steps) && !j.skip_live;
         // ---- row versions -> store masks; what must be in registers = everything stored + everything a step or checksum reads
@@ -770,7 +909,8 @@ int run_branch_step(ggrs_world* w, const ggrs_branch_step& st, uint32_t res_firs
     if (w->ring_frame.empty() || w->ring_frame.front() != w->frame)
         return w->fail(GGRS_E_NO_SNAPSHOT, "a branch step starts from the snapshot of the current frame %d, and the ring's newest snapshot is %s (end the prefix with SaveGameState)", w->frame,
                        w->ring_frame.empty() ? "none" : std::to_string(w->ring_frame.front()).c_str());
-    int rc = materialise_live(w); if (rc) return rc;
+    int rc = materialise_slots(w); if (rc) return rc;
+    rc = materialise_live(w); if (rc) return rc;
     Block& src = w->slots[w->ring_slot.front()];
     const int32_t F = w->frame;
     const uint32_t n_cks = w->cks_args.n_cks, ib = w->input_bytes;

@@ -46,7 +46,7 @@ int seal(ggrs_world* w) {
     if (w->h_rows) { (void)hipHostFree(w->h_rows); w->h_rows = nullptr; w->d_rows = nullptr; }
     arena_release(w);
     (void)hipGetLastError();
-    w->slots.clear(); w->free_slots.clear(); w->live = Block{};
+    w->slots.clear(); w->free_slots.clear(); w->live = Block{}; w->slot_stale.valid = false;
     w->sealed = false; w->seal_error = rc;
     w->err = "world could not be sealed (permanent): " + why;
     return rc;

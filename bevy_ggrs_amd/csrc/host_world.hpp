@@ -282,10 +282,26 @@ struct ggrs_world {
     // session, a P2P session in steady rollback), everything else materialises it first (materialise_live: one small launch)
     struct LiveStale { bool valid = false; Block* src = nullptr; uint64_t len = 0; uint32_t dt_bits = 0, aux_bits = 0; int step_frame = 0, step_confirmed = 0;
                        unsigned char n_inputs = 0; unsigned char inputs[GGRS_MAX_PLAYERS * (GGRS_MAX_INPUT_BYTES + 1)] = {}; } live_stale;
-    int lazy_live_on = 1;                // (ggrs_dbg_set_lazy_live: 0 = the A/B of profiles/r05h; 2 = every eligible list whatever its size and streak: the fuzzer)
+    // DEFERRED SAVES (host_groups.hpp): a group of the same steady session stored only its FIRST Save (the base); ring slot dst[k] (k >= 1) IS the base advanced by
+    // the recorded steps [0, at[k]) until somebody needs its bytes (materialise_slots: one launch fills every slot still stale).  A stale slot's Block::ver, dirty_len and
+    // tag_ok keep describing the bytes it really holds; ver[k] / dirty[k] are what it holds once materialised.  stale[k] is cleared when a Save lands in the slot.
+    struct SlotStale {
+        bool valid = false; Block* base = nullptr; uint32_t n = 0;                 // entries 1 .. n - 1 (entry 0 is the base itself)
+        Block* dst[MAX_TICK_SAVES] = {}; bool stale[MAX_TICK_SAVES] = {}; uint32_t at[MAX_TICK_SAVES] = {};
+        int32_t frame[MAX_TICK_SAVES] = {}; uint64_t len[MAX_TICK_SAVES] = {}, dirty[MAX_TICK_SAVES] = {};
+        std::vector<ver_t> ver;                                                   // [k][column]
+        uint32_t dt_bits[MAX_TICK_STEPS] = {}, aux_bits[MAX_TICK_STEPS] = {}; int step_frame[MAX_TICK_STEPS] = {}, step_confirmed[MAX_TICK_STEPS] = {};
+        unsigned char n_inputs[MAX_TICK_STEPS] = {}; unsigned char inputs[MAX_TICK_STEPS][GGRS_MAX_PLAYERS * (GGRS_MAX_INPUT_BYTES + 1)] = {};
+    } slot_stale;
+    int lazy_live_on = 1;                // (ggrs_dbg_set_lazy_live: 0 = the A/B of profiles/r05h, no deferred Saves either; 2 = every eligible list whatever its size and streak: the fuzzer;
+                                         //  3 = as 2, and every eligible group defers its Saves; 4 = as 1 without deferred Saves)
     bool live_handed_out = false;        // ggrs_hip_live_state_ptr gave the block away: it is kept current from then on
     uint32_t load_open_streak = 0;       // consecutive request lists that opened with a LoadGameState
     uint64_t lazy_skips = 0, lazy_materialised = 0;
+    uint64_t saves_deferred = 0, slots_materialised = 0;
+    // the later Saves of the last rollback group, frames (defer_first, defer_last]: a Load of one of them would have had to materialise it had they been deferred.
+    // defer_streak counts the Load-opening lists since the last such Load (a P2P session whose rollback length changes from tick to tick keeps it low)
+    int64_t defer_first = 0, defer_last = 0; uint32_t defer_streak = 0;
 
     // pending partials produced by the last advance (valid for the live state as-is)
     bool pending_valid = false; uint32_t pending_parts = 0;
