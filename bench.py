@@ -12,16 +12,22 @@ needs.  Default host API: ggrs_hip_enqueue_requests / ggrs_hip_collect_checksums
 flight (a shim collects right before the next advance_frame()); `--sync` blocks on every tick.
 
   value     = entities x 9 advances x steps / seconds      (whole job, all ranks)
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets the world up, warms up, times the K steps, writes --dump-outputs and prints the
+line: `value`, `ms_per_step` and the SyncTest consistency of the timed ticks' own checksums.  Everything that takes a run of its own is
+behind `--full` (any configuration; `full` in the line says which it was):
+
   roofline  = dominant kernel ggrs_jit_tick (the fused request group: read one snapshot, write D snapshots,
               write live once): the bytes the library counts per launch / its mean duration
               from HIP events riding on the dispatch inside libggrs_hip.so; `traffic` = HBM
               bytes per launch from the FETCH_SIZE / WRITE_SIZE passes (profiles/roofline_traffic.json).
-  extra_configs = (default N = 1 headline run only) BASELINE configs 2 / 4 / 5 (+ its spawning variant) and the all-columns-hot
+  extra_configs = (--full N = 1 headline run only) BASELINE configs 2 / 4 / 5 (+ its spawning variant) and the all-columns-hot
               world, each measured in this process AFTER the headline's clock has stopped, each with its own in-run oracle
               parity; configs 2 / 4 also through a C loop (benches/tick_loop.c) next to this file's Python loop.
               SURVEY 8d's one-kernel-per-request figure (1656 B/entity-tick) is reported as
               per_request_equiv_*; `--no-groups` measures that path itself.
   cpu_baseline = the oracle's REFERENCE-SHAPED variant (kind "port"), 1 thread, bounded sample.
+  parity    = the first timed ticks' Checksum(u128)s against the CPU oracle replaying the same frames (N > 1: the gathered table against a serial walk).
 
 N > 1 (one process per GPU, launched by torch.distributed.run): speculative fan-out -- rank 0's
 confirmed snapshot is broadcast ONCE over RCCL/xGMI; per step every rank runs ONE request list of the
@@ -304,7 +310,7 @@ def measure_traffic_now(args, budget_s=120.0):
     exe = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
     if not os.path.exists(exe): return {"error": "rocprofv3 not found"}
     t0 = time.perf_counter()
-    out = {"passes": {}, "command": "rocprofv3 --pmc <counter> -f csv -- python bench.py --steps 60 --warmup 16 --no-cpu-baseline --preheat-ms 0 --no-extra --no-traffic"}
+    out = {"passes": {}, "command": "rocprofv3 --pmc <counter> -f csv -- python bench.py --full --steps 60 --warmup 16 --no-cpu-baseline --preheat-ms 0 --no-extra --no-traffic"}
     tmp = tempfile.mkdtemp(prefix="ggrs_pmc_", dir="/tmp")
     env = dict(os.environ, TMPDIR="/tmp")
     for key in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"): env.pop(key, None)
@@ -312,7 +318,7 @@ def measure_traffic_now(args, budget_s=120.0):
         for counter in ("FETCH_SIZE", "WRITE_SIZE"):
             if time.perf_counter() - t0 > budget_s: out["passes"][counter] = {"skipped": "budget"}; continue
             d = os.path.join(tmp, counter)
-            cmd = [exe, "--pmc", counter, "-f", "csv", "-d", d, "-o", "c", "--", sys.executable, os.path.abspath(__file__), "--steps", "60", "--warmup", "16", "--no-cpu-baseline",
+            cmd = [exe, "--pmc", counter, "-f", "csv", "-d", d, "-o", "c", "--", sys.executable, os.path.abspath(__file__), "--full", "--steps", "60", "--warmup", "16", "--no-cpu-baseline",
                    "--preheat-ms", "0", "--no-extra", "--no-traffic", "--entities", str(args.entities), "--depth", str(args.depth), "--schema", args.schema]
             try:
                 r = subprocess.run(cmd, cwd="/tmp", env=env, capture_output=True, text=True, timeout=max(30.0, budget_s - (time.perf_counter() - t0)))
@@ -493,16 +499,17 @@ def spawn_ranks(args, argv):
 
 
 def measure_single(bg, cm, torch, args, contig=False, light=False):
-    """One single-GPU measurement in this process: warm-up, pre-heat, K timed ticks, then the host-timeline pass and the HIP-event pass for the
-    per-kernel roofline.  light: no telemetry, no checksum capture."""
+    """One single-GPU measurement in this process: warm-up, pre-heat, K timed ticks, then (--full) the host-timeline pass and the HIP-event pass for the
+    per-kernel roofline; a plain run stops after the timed ticks (and the dump) and reads no clocks.  light: no telemetry, no checksum capture."""
     n, D, K, W = args.entities, args.depth, args.steps, args.warmup
+    full = bool(getattr(args, "full", False))
     stream = torch.cuda.current_stream().cuda_stream
     flags = (bg.GGRS_WORLD_UNFUSED if args.unfused else 0) | (bg.GGRS_WORLD_NT_COPY if args.nt else 0) | (bg.GGRS_WORLD_NO_GROUPS if args.no_groups else 0)
     w, ids = build_world(bg, cm, n, D, stream=stream, flags=flags, checksum=not args.no_checksum, schema=args.schema)
     m = {}
     warm_ring(bg, w, D)
     run, _keep = tick_requests(bg, w, D)
-    m["clocks_start"] = None if light else read_clocks()
+    m["clocks_start"] = read_clocks() if full and not light else None
     # the interpreter's cycle collector stays out of the timed region (profiles/r03zi: one generation-2 pass inside it reads as a 35 ms
     # tick); collected HERE, before warm-up and pre-heat, so that the device is not left idle for that long right before the timed ticks
     gc.collect(); gc.disable()
@@ -560,7 +567,7 @@ def measure_single(bg, cm, torch, args, contig=False, light=False):
         secs = time.perf_counter() - t0
     gc.enable()
     m["secs"] = secs
-    m["clocks_end"] = None if light else read_clocks()
+    m["clocks_end"] = read_clocks() if full and not light else None
     m["rss_mb"] = [rss0, rss_mb()]               # resident set of this process before / after the timed region (soaks: the runtime must not grow with the tick count)
     m["live"] = w.active_count()
     m["gpu_cs"] = [[int.from_bytes(b[16 * k:16 * k + 16], "little") for k in range(D)] for b in gpu_cs]
@@ -574,6 +581,11 @@ def measure_single(bg, cm, torch, args, contig=False, light=False):
     if getattr(args, "dump_outputs", None) and gpu_cs:
         m["dump"] = dump_outputs(args.dump_outputs, w, ids, gpu_cs[-1])
         m["dump"]["frame"] = m["f_end"]
+    if not full:
+        # a plain run ends here: the two passes below are runs of their own and belong to --full
+        m["info"] = w.kernel_info()
+        w.close()
+        return m
     if not args.sync and not light:
         m["host_timeline"] = timeline_pass(w, run, min(K, 50))
     # ---- instrumented pass for the per-kernel roofline: HIP events riding on every dispatch (kernel begin / end, what rocprofv3's kernel
@@ -679,6 +691,10 @@ def measure_p2p(bg, cm, torch, args):
                  "worst5": [(i, script[first + i][1], round(gaps[i], 1)) for i in sorted(range(len(gaps)), key=lambda i: -gaps[i])[:5]],
                  "note": "host interval between consecutive collects in the timed region; worst5 = (tick, rollback length, us)"}
     advances = sum(r + 1 for _f, r, _s in script[first:])
+    if not getattr(args, "full", False):
+        # a plain run ends here: the instrumented pass, the oracle under the same script and the CPU baseline belong to --full
+        info, live = w.kernel_info(), w.active_count(); w.close()
+        return {"secs": secs, "advances": advances, "live": live, "info": info, "mean_rollback": sum(r for _f, r, _s in script[first:first + K]) / K, "settle": settle, "tick_wall_us": tick_wall}
     w.profile_enable(True)
     w.synchronize()
     tp0 = time.perf_counter()
@@ -884,12 +900,9 @@ def c_loop_p2p(bg, cm, torch, n, R, K, kernel_us=None, launches_per_tick=1.0):
     return out
 
 
-def single_line(bg, cm, torch, args, dev):
-    """One N = 1 SyncTest measurement (BASELINE configs 2 / 3 and the --schema / --entities variants) -> (JSON line, parity failed?)."""
-    n, D, K, W = args.entities, args.depth, args.steps, args.warmup
-    bps = cm.schema_bytes_per_entity(args.schema)
-    m = measure_single(bg, cm, torch, args, contig=False)
-    secs, live, gpu_cs, prof = m["secs"], m["live"], m["gpu_cs"], m["prof"]
+def single_resim_consistent(m, D):
+    """Whether the timed ticks of `m` (measure_single) agree with themselves, from the checksums the timed loop collected anyway."""
+    gpu_cs = m["gpu_cs"]
     # SyncTest's own check over ALL timed ticks (ggrs SyncTestSession: a resimulated frame's checksum must equal the first
     # one recorded for that frame, else MismatchedChecksum): timed tick k at frame F saved frames F-D+1 .. F
     first_seen, resim_ok, f_end = {}, True, m["f_end"]
@@ -897,8 +910,14 @@ def single_line(bg, cm, torch, args, dev):
         F = f_end - (len(gpu_cs) - k)
         for j, c in enumerate(tick):
             resim_ok &= first_seen.setdefault(F - D + 1 + j, c) == c
-    info = m["info"]
-    value = live * (D + 1) * K / secs
+    return bool(resim_ok)
+
+
+def single_roofline(args, m, bps):
+    """--full: the per-kernel roofline of one N = 1 SyncTest measurement, from measure_single's instrumented pass (and, for the default headline, the
+    two counter passes) -> (roofline, request groups in use?, launches per step, mean us of the group's launch)."""
+    n, D, K = args.entities, args.depth, args.steps
+    secs, live, prof, info = m["secs"], m["live"], m["prof"], m["info"]
     save_ms, save_n = prof["save"]; adv_ms, adv_n = prof["advance"]; load_ms, load_n = prof["load"]; tick_ms, tick_n = prof["tick"]; fin_ms, fin_n = prof["checksum"]
     per = lambda ms, cnt: ms / max(cnt, 1) * 1e-3
     # PMC-derived HBM bytes per launch: only valid for the exact workload the counters were collected on
@@ -959,6 +978,27 @@ def single_line(bg, cm, torch, args, dev):
                 "other_kernels": {"k_particles_step (AdvanceWorld)": {"avg_launch_us": per(adv_ms, adv_n) * 1e6, "achieved_GBps": ADV_BYTES * live / per(adv_ms, adv_n) / 1e9 if adv_n else 0.0},
                                   "k_copy_state (LoadWorld)": {"avg_launch_us": per(load_ms, load_n) * 1e6, "achieved_GBps": save_bytes * live / per(load_ms, load_n) / 1e9 if load_n else 0.0}},
                 "whole_tick_achieved_GBps": tick_bytes * live * K / secs / 1e9, "whole_tick_frac": tick_bytes * live * K / secs / 1e9 / HBM_PEAK_GBS}
+    return roof, grouped, launches_per_step, (tick_ms, tick_n)
+
+
+LEAN_NOTE = ("a plain run measures the timed steps only: roofline, latency_floor, cpu_baseline, the parity replay on the CPU oracle, the telemetry passes "
+             "and extra_configs are measured with --full")
+
+
+def single_line(bg, cm, torch, args, dev):
+    """One N = 1 SyncTest measurement (BASELINE configs 2 / 3 and the --schema / --entities variants) -> (JSON line, parity failed?).
+    Without --full the line carries the timed steps' figures and the checks that cost no run of their own."""
+    n, D, K, W = args.entities, args.depth, args.steps, args.warmup
+    full = bool(getattr(args, "full", False))
+    bps = cm.schema_bytes_per_entity(args.schema)
+    m = measure_single(bg, cm, torch, args, contig=False)
+    secs, live, gpu_cs, info = m["secs"], m["live"], m["gpu_cs"], m["info"]
+    resim_ok = single_resim_consistent(m, D)
+    value = live * (D + 1) * K / secs
+    roof, grouped = None, False
+    if full:
+        roof, grouped, launches_per_step, (tick_ms, tick_n) = single_roofline(args, m, bps)
+        per = lambda ms, cnt: ms / max(cnt, 1) * 1e-3
     headline = n == 1_000_000 and D == 8 and args.schema == "headline"
     line = {
         "metric": "rollback-resim entity-frames/sec at 1M entities, depth 8; HBM GB/s vs peak" if headline else
@@ -984,7 +1024,9 @@ def single_line(bg, cm, torch, args, dev):
     line["telemetry"] = {"clocks_start": m.get("clocks_start"), "clocks_end": m.get("clocks_end"), "tick_wall_us": m.get("tick_wall_us"), "host_timeline_us_per_tick": m.get("host_timeline"), "rss_mb": m.get("rss_mb")}
     line["parity"] = {"synctest_resim_consistent_over_timed_ticks": bool(resim_ok), "timed_ticks": len(gpu_cs)}
     parity_failed = not resim_ok
-    if not args.no_cpu_baseline:
+    line["full"] = full
+    if not full: line["not_measured"] = LEAN_NOTE
+    if full and not args.no_cpu_baseline:
         base, par = cpu_baseline_and_parity(n, D, args.cpu_ticks, m["frames_before_timed"], gpu_cs, 0 if args.no_checksum else args.parity_ticks, schema=args.schema, time_refshaped=not getattr(args, "parity_only", False))
         if base is not None: line["cpu_baseline"] = base
         line["parity"].update(par)
@@ -997,6 +1039,16 @@ def single_line(bg, cm, torch, args, dev):
 def p2p_line(bg, cm, torch, args):
     n, D, K, W = args.entities, args.depth, args.steps, args.warmup
     m4 = measure_p2p(bg, cm, torch, args)
+    if "prof" not in m4:
+        # a plain run: the timed steps' figures only
+        return {"metric": f"rollback-resim entity-frames/sec, P2P-shaped rollbacks (0..{D} frames per tick) at {n} entities; GB/s vs HBM peak",
+                "value": m4["live"] * m4["advances"] / m4["secs"], "unit": "entity-frames/s", "n_gpus": 1, "steps": K, "warmup": W,
+                "ms_per_step": m4["secs"] / K * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32+u64", "data": "synthetic",
+                "config": {"workload": f"BASELINE config 4: p2p-shaped session, {n} entities x 3 registered components, a rollback of 0..{D - 1} frames every tick "
+                                       f"(mean {m4['mean_rollback']:.2f}), ring depth {D}", "request_group_kernel": m4["info"].get("request_group_kernel"),
+                           "specialised_kernel": m4["info"].get("specialised_kernel"), "specialise_settle": m4["settle"], "checksum_fold": m4["info"].get("checksum_fold"),
+                           "arena_actual": m4["info"].get("arena"), "host_api": "enqueue/collect, 1 tick in flight"},
+                "roofline": None, "telemetry": {"tick_wall_us": m4["tick_wall_us"]}, "parity": None, "cpu_baseline": None, "full": False, "not_measured": LEAN_NOTE}, False
     t_ms, t_n = m4["prof"]["tick"]
     avg_s = t_ms / max(t_n, 1) * 1e-3
     bpl = m4["prof_bytes"]["tick"] / max(t_n, 1)
@@ -1069,7 +1121,8 @@ def fanout_line(bg, cm, torch, args, dist, rank, world_size, dev, ctl_dev):
             fan.step_pipelined(want_result=False)
         fan.drain(want_result=False)
     m = {"preheat": {"ms": (time.perf_counter() - pre_t0) * 1e3, "ticks": pre_n, "requested_ms": args.preheat_ms, "same_step_count_on_every_rank": True}}
-    P_fan = 0 if (args.no_cpu_baseline or args.no_checksum) else max(0, min(K, args.parity_steps if args.parity_steps >= 0 else max(1, 16 // max(1, world_size * args.branches))))
+    full = bool(getattr(args, "full", False))              # a plain run: the timed steps only -- no instrumented pass, no oracle walk, no CPU baseline
+    P_fan = 0 if (not full or args.no_cpu_baseline or args.no_checksum) else max(0, min(K, args.parity_steps if args.parity_steps >= 0 else max(1, 16 // max(1, world_size * args.branches))))
     c_timed = fan.confirmed
     cf = torch.tensor([c_timed, -c_timed], dtype=torch.int64, device=ctl_dev)
     dist.all_reduce(cf, op=dist.ReduceOp.MAX)                # max(C) == -max(-C): every rank enters the timed region at the same confirmed frame
@@ -1095,12 +1148,14 @@ def fanout_line(bg, cm, torch, args, dist, rank, world_size, dev, ctl_dev):
     cnt = torch.tensor([live * args.branches], dtype=torch.int64, device=ctl_dev)   # every branch resimulates the whole world
     dist.all_reduce(cnt)
     total_entities = int(cnt.item())
-    w.profile_enable(True)
-    for _ in range(min(K, 20)):
-        fan.step(want_result=False)
-    prof = w.profile_read()
-    prof_bytes = w.profile_bytes()
-    w.profile_enable(False)
+    prof, prof_bytes = {"tick": (0.0, 0)}, {"tick": 0}
+    if full:
+        w.profile_enable(True)
+        for _ in range(min(K, 20)):
+            fan.step(want_result=False)
+        prof = w.profile_read()
+        prof_bytes = w.profile_bytes()
+        w.profile_enable(False)
     info = w.kernel_info()
     # ---- adoption (--retain): the true inputs of the next D - 1 frames turn out to be what branch 0 predicted (all zero, like the confirmed inputs of this
     # bench): its retained state becomes the world on every rank -- a ring-slot swap on rank 0, a re-simulation (or nothing, at world size 1) elsewhere --, and
@@ -1161,7 +1216,11 @@ def fanout_line(bg, cm, torch, args, dist, rank, world_size, dev, ctl_dev):
                                         "branch-invariant Save(C+1) once per rank instead of once per branch (shared_prefix), so fewer are executed"}
         line["roofline_alu"].update(alu_executed(line["roofline_alu"]["frac"], D))
     parity_failed = False
-    if rank == 0 and not args.no_cpu_baseline:
+    line["full"] = full
+    if not full:
+        line["roofline"], line["not_measured"] = None, LEAN_NOTE
+        if adopt is not None: line["adopt"] = adopt
+    if rank == 0 and full and not args.no_cpu_baseline:
         if not getattr(args, "parity_only", False):
             base, _ = cpu_baseline_and_parity(n, D, args.cpu_ticks, D + 1, [], 0)
             line["cpu_baseline"] = base
@@ -1294,6 +1353,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=16)
     ap.add_argument("--entities", type=int, default=1_000_000)
     ap.add_argument("--depth", type=int, default=8)
+    ap.add_argument("--full", action="store_true", help="everything beyond the timed steps: the instrumented passes behind `roofline` / `latency_floor` / the host timeline, the "
+                    "rocprofv3 counter passes, `cpu_baseline`, the parity replay on the CPU oracle, clock telemetry and, for the default headline, `extra_configs`.  Without "
+                    "it a run sets up, warms up, times its steps, writes --dump-outputs and prints the line")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-ticks", type=int, default=3)
     ap.add_argument("--parity-ticks", type=int, default=24, help="timed ticks whose checksums the CPU oracle replays and compares (N = 1 only; 0 = off)")
@@ -1342,7 +1404,7 @@ def main():
     if args.no_lazy_live: os.environ["BENCH_NO_LAZY_LIVE"] = "1"
     default_headline = (args.config == 3 and args.entities == 1_000_000 and args.depth == 8 and args.schema == "headline" and not (args.fanout or args.sync or args.unfused or args.no_groups
                         or args.nt or args.no_checksum or args.no_cpu_baseline or args.branches != 1))
-    args.measure_traffic = default_headline and not args.no_traffic and args.gpus == 1
+    args.measure_traffic = args.full and default_headline and not args.no_traffic and args.gpus == 1
     if args.config == 2: args.entities = 10_000
     if args.config == 4: args.entities = 100_000
     if args.config == 5:
@@ -1409,7 +1471,7 @@ def main():
         line, parity_failed = p2p_line(bg, cm, torch, args)
     else:
         line, parity_failed = single_line(bg, cm, torch, args, dev)
-        if default_headline and not args.no_extra:
+        if args.full and default_headline and not args.no_extra:
             # every other BASELINE config, measured AFTER the headline's timed region (and its parity / CPU legs) in the same process
             extra, extra_failed = extra_configs(bg, cm, torch, args, dev, budget_s=args.extra_budget_s)
             line["extra_configs"] = extra

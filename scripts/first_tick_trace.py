@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Where does the FIRST timed tick's time go (86-108 us against a 45 us kernel)?  Reads a `rocprofv3 --hip-trace --kernel-trace -f csv`
-output directory of `bench.py --steps 20 --warmup 5 --no-extra --no-cpu-baseline` and lines the first timed ticks up: when the host called the launch, when
+output directory of `bench.py --full --steps 20 --warmup 5 --no-extra --no-cpu-baseline` and lines the first timed ticks up: when the host called the launch, when
 the call returned, when the kernel began and ended on the device, and what ran just before.  usage: first_tick_trace.py <dir> [out.json]"""
 import csv
 import glob

@@ -228,6 +228,22 @@ def test_bench_gpus_dry_run_builds_rank_commands():
     assert len([l for l in launched.stdout.splitlines() if l.startswith("{")]) == 1       # a rank of an existing launch: no re-spawn
 
 
+def test_bench_full_is_an_option_that_reaches_every_rank():
+    """`bench.py --full` (everything beyond the timed steps: CPU baselines, oracle replays, instrumented and counter passes, the other configurations) is off
+    by default, accepted in every form, and handed to every rank `--gpus N` starts."""
+    import json
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    for extra, want in ((["--full"], True), ([], False)):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "7", "--warmup", "2", "--dry-run"] + extra, capture_output=True, text=True, env=env, timeout=120)
+        assert out.returncode == 0, out.stderr
+        cmds = [json.loads(l)["cmd"] for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(cmds) == 2 and all(("--full" in c) is want for c in cmds), cmds
+    single = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--full", "--dry-run"], capture_output=True, text=True, env=env, timeout=120)
+    assert single.returncode == 0 and "--full" in json.loads(single.stdout.strip())["cmd"], (single.stdout, single.stderr)
+
+
 def test_kernel_info_without_a_device():
     """ggrs_hip_world_kernel_info works on a GGRS_WORLD_LAYOUT_ONLY world: the run-time compiler's state is queryable anywhere."""
     w = bg.World(1000, max_depth=4, flags=bg.GGRS_WORLD_LAYOUT_ONLY)

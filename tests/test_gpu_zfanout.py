@@ -474,7 +474,7 @@ def test_bench_two_ranks_line_carries_parity_cpu_baseline_and_roofline():
     (--oversubscribe; control plane gloo, the library's collectives over the shared-memory stand-in for RCCL), times its steps, and rank 0
     prints the line a SCALE run would record: n_gpus from ncclCommCount, the in-run parity of the gathered checksum table against the
     oracle's serial walk of every branch of both ranks, the CPU baseline and the roofline of rank 0's kernel."""
-    line = _bench_line(["--gpus", "2", "--oversubscribe", "--steps", "6", "--warmup", "2", "--preheat-ms", "20", "--entities", "300000", "--cpu-ticks", "1"],
+    line = _bench_line(["--full", "--gpus", "2", "--oversubscribe", "--steps", "6", "--warmup", "2", "--preheat-ms", "20", "--entities", "300000", "--cpu-ticks", "1"],
                        env={"GGRS_RCCL_LIB": _double_lib()})
     assert line["n_gpus"] == 2 and line["steps"] == 6 and line["scaling"] == "weak"
     par = line["parity"]
@@ -489,7 +489,7 @@ def test_bench_two_ranks_line_carries_parity_cpu_baseline_and_roofline():
 def test_bench_config5_fanout_line_on_one_gpu():
     """BASELINE config 5 through bench.py at world size 1 (the real RCCL): 256 branches, the parity gate walks every one of them on the
     oracle, and the line carries the integer-multiply roofline next to the HBM one."""
-    line = _bench_line(["--config", "5", "--steps", "4", "--warmup", "2", "--preheat-ms", "20", "--cpu-ticks", "1"])
+    line = _bench_line(["--full", "--config", "5", "--steps", "4", "--warmup", "2", "--preheat-ms", "20", "--cpu-ticks", "1"])
     assert line["n_gpus"] == 1 and line["parity"]["equal"] is True and line["parity"]["checked_branches"] == 256, line.get("parity")
     assert line["cpu_baseline"]["value"] > 0
     assert line["roofline_alu"]["achieved"] > 0
@@ -498,7 +498,7 @@ def test_bench_config5_fanout_line_on_one_gpu():
 def test_bench_dump_outputs_is_the_same_in_every_run(tmp_path):
     """`bench.py --dump-outputs DIR`: the last timed step's checksums and the world it left, as .npy files; with the same arguments two runs start their timed
     ticks at the same frame (fixed pre-heat tick count) and write the same arrays, and --steps sets the number of timed steps."""
-    args = ["--config", "2", "--steps", "9", "--warmup", "3", "--preheat-ms", "5", "--cpu-ticks", "1"]
+    args = ["--full", "--config", "2", "--steps", "9", "--warmup", "3", "--preheat-ms", "5", "--cpu-ticks", "1"]
     lines, dumps = [], []
     for rep in range(2):
         d = str(tmp_path / f"run{rep}")
@@ -515,6 +515,26 @@ def test_bench_dump_outputs_is_the_same_in_every_run(tmp_path):
         assert np.array_equal(dumps[0][k], dumps[1][k]), k
 
 
+def test_bench_plain_run_is_lean_and_keeps_the_headline_fields():
+    """`bench.py --gpus 1 --steps N --warmup W` without --full sets up, warms up, times its N steps and prints the line: the headline fields are there and mean
+    what they mean under --full, nothing that takes a run of its own is (no CPU baseline, no oracle replay, no instrumented or counter pass, no extra
+    configurations), and the whole process -- start to exit, compile or load of the kernels at the first step included -- spends at most 30 s outside its
+    N + W steps."""
+    import time
+    N, W = 20, 5
+    t0 = time.perf_counter()
+    line = _bench_line(["--gpus", "1", "--steps", str(N), "--warmup", str(W)], timeout=300)
+    wall = time.perf_counter() - t0
+    assert line["metric"] == "rollback-resim entity-frames/sec at 1M entities, depth 8; HBM GB/s vs peak" and line["unit"] == "entity-frames/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "f32+u64" and line["steps"] == N and line["warmup"] == W and line["n_gpus"] == 1
+    assert line["ms_per_step"] > 0 and line["value"] == pytest.approx(line["config"]["entities_per_gpu"] * 9 / (line["ms_per_step"] * 1e-3), rel=1e-9)
+    assert line["full"] is False and line["roofline"] is None and line["cpu_baseline"] is None and "extra_configs" not in line and "latency_floor" not in line
+    assert line["parity"] == {"synctest_resim_consistent_over_timed_ticks": True, "timed_ticks": N}, line["parity"]
+    outside = wall - (N + W) * line["ms_per_step"] * 1e-3
+    print(f"plain bench run: {wall:.1f} s in all, {outside:.1f} s outside its {N + W} steps")
+    assert outside <= 30.0, (wall, outside)
+
+
 def test_bench_two_ranks_under_torch_distributed_run():
     """The driver's launch form for N > 1 -- `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P
     bench.py --gpus N ...` -- with N = 2 on the one GPU of this box: the ranks read RANK / LOCAL_RANK / WORLD_SIZE from the launcher's
@@ -527,7 +547,7 @@ def test_bench_two_ranks_under_torch_distributed_run():
     with socket.socket() as so:
         so.bind(("127.0.0.1", 0)); port = so.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(root, "bench.py"), "--gpus", "2", "--oversubscribe", "--steps", "12", "--warmup", "3", "--preheat-ms", "30", "--entities", "300000", "--cpu-ticks", "1"]
+           os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--oversubscribe", "--steps", "12", "--warmup", "3", "--preheat-ms", "30", "--entities", "300000", "--cpu-ticks", "1"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env={**os.environ, "GGRS_RCCL_LIB": _double_lib()}, cwd=root)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stdout[-1500:], r.stderr[-3000:])
