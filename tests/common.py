@@ -3,6 +3,8 @@ built on either backend, the synthetic inputs of BASELINE.md section 3, and a ba
 SyncTest driver (run_synctest, src/schedule_systems.rs:85-118)."""
 from __future__ import annotations
 
+import re
+
 import numpy as np
 
 import bevy_ggrs_amd as bg
@@ -113,6 +115,12 @@ def assert_states_equal(a, b, ctx=""):
                 raise AssertionError(f"{ctx} state field {k} differs at {bad[:8]} ({bad.size} slots): {a[k][bad[:4]]} vs {b[k][bad[:4]]}")
         else:
             assert a[k] == b[k], (ctx, k, a[k], b[k])
+
+
+def deferred_counts(w):
+    """(Saves deferred, ring slots materialised on demand) of a library world, from kernel_info()["deferred_saves"]; None where the build reports neither."""
+    m = re.search(r"(\d+) Saves deferred, (\d+) ring slots materialised", w.kernel_info().get("deferred_saves", ""))
+    return (int(m.group(1)), int(m.group(2))) if m else None
 
 
 class SyncTestDriver:

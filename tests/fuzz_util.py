@@ -13,6 +13,7 @@ lists and at the end: every word of every component of every live entity, the li
 ring still holds."""
 from __future__ import annotations
 
+import re
 from collections import deque
 
 import numpy as np
@@ -96,7 +97,8 @@ class GenericScenario:
     despawns at zero, immediately or with a RollbackDespawned marker (tests/synctest.rs:37-44, snapshot/despawn.rs:114-143)."""
     with_spawn, spawn_budget, spawn_fn = False, 0, None
 
-    def __init__(self, seed, *, big=False, max_n=None):
+    def __init__(self, seed, *, big=False, max_n=None, plain=False):
+        self.plain = plain
         r = self.rng = np.random.default_rng([0x6E6E, seed])
         self.seed = seed
         self.n = int(r.choice([s for s in ([1, 64, 65, 257, 3000, 8193, 20_000] if not big else [300_000, 600_001]) if not max_n or s <= max_n]))
@@ -118,6 +120,9 @@ class GenericScenario:
                     if i != self.no_rollback and r.random() < 0.7]
         four = [(i, k) for i, (_, wb, nw) in enumerate(self.comps) if wb == 4 and i != self.no_rollback for k in range(nw)]
         self.adds = [four[int(r.integers(len(four)))] + (int(r.integers(1, 2**32)),) for _ in range(int(r.integers(1, 4)))]
+        # plain: every draw above is made as usual, then whatever keeps a world off the lazy live block and deferred Saves for good is taken out -- every component
+        # under rollback, Health (if any) despawning immediately, no host-side despawn_rollback (_mutate) -- while word sizes, missing components and SAT_SUB_DESPAWN stay
+        if plain: self.no_rollback, self.health_mode = -1, 0
         self.capacity = self.n + 8
 
     def describe(self):
@@ -146,7 +151,8 @@ class BoxScenario:
     rollback, Player outside it; arbitrary starting states so that every branch of move_cube_system is taken."""
     with_spawn, spawn_budget, spawn_fn = False, 0, None
 
-    def __init__(self, seed, *, big=False, max_n=None):
+    def __init__(self, seed, *, big=False, max_n=None, player_rollback=False):
+        self.player_rollback = player_rollback                 # Player under rollback too: nothing live-only is left, so this world -- whose kernel reads inputs and aux_bits -- may defer
         r = self.rng = np.random.default_rng([0xB0C5, seed])
         self.seed = seed
         self.n = int(r.choice([s for s in ([2, 64, 257, 5000, 8193] if not big else [300_000]) if not max_n or s <= max_n]))
@@ -157,11 +163,13 @@ class BoxScenario:
         self.capacity = self.n + 8
 
     def describe(self):
-        return f"box_game seed {self.seed}: n={self.n} players={self.players} depth={self.depth} checksums(T, V)={self.cks} fps={self.fps}"
+        return (f"box_game seed {self.seed}: n={self.n} players={self.players} depth={self.depth} checksums(T, V)={self.cks} fps={self.fps}"
+                + (" player_rollback" if self.player_rollback else ""))
 
     def build(self, world):
         from test_box_game import build_box
-        ids, *_ = build_box(world, self.n, self.players, seed=self.seed, spread=True, checksums=[(c, [0, 1, 2]) for c in (0, 1) if self.cks[c]])
+        ids, *_ = build_box(world, self.n, self.players, seed=self.seed, spread=True, checksums=[(c, [0, 1, 2]) for c in (0, 1) if self.cks[c]],
+                             player_rollback=self.player_rollback)
         world.set_frame_rate(self.fps)
         world.set_depth(self.depth)
         if hasattr(world, "set_synctest_check_distance"): world.set_synctest_check_distance(-1)
@@ -261,7 +269,7 @@ def _mutate(sc, st, A, B, ids):
     if x < 0.45 and alive.size:
         s = int(r.choice(alive)); A.despawn(s); B.despawn(s)
         return f"despawn({s})"
-    if x < 0.5 and alive.size and hasattr(A, "despawn_rollback") and not isinstance(sc, Scenario):
+    if x < 0.5 and alive.size and hasattr(A, "despawn_rollback") and not isinstance(sc, Scenario) and not getattr(sc, "plain", False) and not getattr(sc, "player_rollback", False):
         s = int(r.choice(alive)); A.despawn_rollback(s); B.despawn_rollback(s)
         return f"despawn_rollback({s})"
     V = ids[1] if isinstance(sc, Scenario) else ids[int(r.integers(len(ids)))]
@@ -293,8 +301,14 @@ def _extra_state(w):
     return out
 
 
-def run(seed, make_a, make_b, n_lists=30, big=False, state_every=6, generic=False, max_n=None, box=False, start_frame=None):
-    sc = (BoxScenario if box else GenericScenario if generic else Scenario)(seed, big=big, max_n=max_n)
+def run(seed, make_a, make_b, n_lists=30, big=False, state_every=6, generic=False, max_n=None, box=False, start_frame=None, variant=None, ring_sweep=False, on_end=None):
+    """variant: keywords of the scenario (GenericScenario(plain=True), BoxScenario(player_rollback=True)).
+    ring_sweep: once mid-session (after list n_lists // 2) and after the last list, every frame the ring holds at or above ConfirmedFrameCount is loaded,
+    newest first (a rollback pops what is newer), by a list [LoadGameState(f)] of its own on both backends, and the WHOLE state is compared: what a ring slot
+    holds is otherwise seen only if a later random list happens to load it.  The sweep draws nothing from sc.rng; the session goes on from the oldest swept frame,
+    so the swept slots are saved over later.  Each Load is logged as a list `L<f>   (sweep)`.
+    on_end(A, B, log): called before the worlds are closed (a test reads the library's counters there)."""
+    sc = (BoxScenario if box else GenericScenario if generic else Scenario)(seed, big=big, max_n=max_n, **(variant or {}))
     A, B = make_a(sc), make_b(sc)
     log = [sc.describe()]
     try:
@@ -314,7 +328,21 @@ def run(seed, make_a, make_b, n_lists=30, big=False, state_every=6, generic=Fals
                 got = B.collect_checksums()
                 assert want == list(got), f"checksums of the enqueued list {k0} differ:\n{ctx0}\n{want}\n{got}"
 
+        def sweep(when):
+            drain()
+            for f in [f for f in st["ring"].frames if f >= st["confirmed"]]:
+                log.append(f"L{f}   (sweep)")
+                ctx = f"ring sweep {when}, frame {f}:\n" + "\n".join(log[:1] + log[-10:]) + "\n"
+                assert A.has_snapshot(f) and B.has_snapshot(f), f"has_snapshot({f}): {A.has_snapshot(f)} vs {B.has_snapshot(f)} in the {ctx}"
+                ca, cb = A.handle_requests([bg.LoadGameState(f)]), B.handle_requests([bg.LoadGameState(f)])
+                st["ring"].rollback(f); st["F"] = f
+                assert list(ca) == list(cb) == [] and (A.frame, A.len, A.snapshot_count()) == (B.frame, B.len, B.snapshot_count()) == (f, A.len, A.snapshot_count()), \
+                    f"frame / len / snapshots differ: {(A.frame, A.len, A.snapshot_count())} vs {(B.frame, B.len, B.snapshot_count())} (model frame {f}) in the {ctx}"
+                cm.assert_states_equal(cm.snapshot_state(A, ids), cm.snapshot_state(B, ids), ctx)
+                cm.assert_states_equal(_extra_state(A), _extra_state(B), "RollbackDespawned markers, " + ctx)
+
         for k in range(n_lists):
+            if ring_sweep and k == n_lists // 2 + 1: sweep("mid-session")
             if sc.rng.random() < 0.6: drain()            # host edits with lists still in flight are part of the game (they are stream-ordered behind them)
             m = _mutate(sc, st, A, B, ids) if not pending or sc.rng.random() < 0.5 else None
             if m: log.append(m)
@@ -338,6 +366,63 @@ def run(seed, make_a, make_b, n_lists=30, big=False, state_every=6, generic=Fals
                 cm.assert_states_equal(_extra_state(A), _extra_state(B), f"RollbackDespawned markers after list {k}:\n{ctx}\n")
                 for f in (w32(st["F"] + d) for d in range(-10, 2)):
                     assert A.has_snapshot(f) == B.has_snapshot(f), f"has_snapshot({f}) differs after list {k}:\n{ctx}"
+        if ring_sweep: sweep("after the last list")
+        if on_end is not None: on_end(A, B, log)
         return log
     finally:
         A.close(); B.close()
+
+
+_TOK = re.compile(r"^(L-?\d+|S-?\d+|A\*?)$")
+
+
+def deferral_model(log, depth, cap_saves=9, cap_steps=10, on_read=None):
+    """From the log of a run alone: (groups, reads) = how many request groups the library, with deferred Saves forced on every eligible group
+    (ggrs_dbg_set_lazy_live 3), MUST have deferred, and how many Loads MUST have found a ring slot whose bytes were still owed.  A lower bound on both, never
+    an estimate: a world may defer more (a group in the middle of a list, a group this model gives up on), it must not defer less.
+
+    Counted is only the LAST group of a list -- nothing later in the list can make it a dead group -- and only if it is opened by a Load, holds no spawning
+    Advance, has two Saves at least, all of distinct frames and none of the loaded frame, with a step between two consecutive Saves, fits ONE group of the world
+    (a group ends at `cap_saves` Saves or `cap_steps` steps -- kernel_info()["group_caps"], max_depth + 1 / + 2 -- and what follows the cut reads the live
+    block, which never defers), and if, when the list ends, the model ring still holds the loaded frame (an evicted source's slot is the next Save's
+    destination: the replay would read the block it writes), the group's first Save (the base of the chain) and one later Save at least.  Those later Saves
+    that the ring still holds are owed.  A read is a later Load (the ring sweep's included) of an owed frame that the ring has held ever since and that no Save
+    has stored again; one replay fills the whole chain, so a read settles every debt.  Frames owed by an earlier group stay owed when a later group defers:
+    the library fills them before it replaces its record, which counts as materialised just the same.
+
+    The log's `depth=` and `confirmed=` lines are followed with the fuzzer's own _Ring.  on_read(index of the log line, frame) is called for every read."""
+    ring, conf, groups, reads, owed = _Ring(depth), 0, 0, 0, set()
+    for ln, line in enumerate(log[1:], 1):
+        m = re.match(r"^confirmed=(-?\d+)$", line)
+        if m:
+            conf = int(m.group(1)); ring.confirm(conf); owed &= set(ring.frames)
+            continue
+        m = re.match(r"^depth=(\d+)$", line)
+        if m:
+            ring.depth = int(m.group(1))
+            continue
+        toks = line.replace("(enqueued)", "").replace("(sweep)", "").split()
+        if not toks or not all(_TOK.match(t) for t in toks): continue
+        grp = None
+        for t in toks:
+            if t[0] == "L":
+                f = int(t[1:])
+                if f in owed:
+                    reads += 1; owed.clear()
+                    if on_read: on_read(ln, f)
+                ring.rollback(f); owed &= set(ring.frames)
+                grp = {"src": f, "saves": [], "steps": 0, "stepped": False, "ok": True}
+            elif t[0] == "S":
+                f = int(t[1:])
+                ring.push(f); ring.confirm(conf); owed.discard(f); owed &= set(ring.frames)
+                if grp is not None:
+                    if (grp["saves"] and not grp["stepped"]) or f == grp["src"] or f in grp["saves"]: grp["ok"] = False
+                    grp["saves"].append(f); grp["stepped"] = False
+            elif grp is not None:
+                grp["stepped"] = True; grp["steps"] += 1
+                if t == "A*": grp["ok"] = False
+        if grp and grp["ok"] and 2 <= len(grp["saves"]) <= cap_saves and grp["steps"] <= cap_steps and grp["src"] in ring.frames:
+            held = [f for f in grp["saves"] if f in ring.frames]
+            if grp["saves"][0] in held and len(held) >= 2:
+                groups += 1; owed |= set(held[1:])
+    return groups, reads

@@ -1,9 +1,8 @@
 """Deferred Saves (csrc/host_groups.hpp materialise_slots): in a steady rollback session a request group stores only its FIRST Save; every
 later ring slot of the group is defined as the base advanced by the recorded steps and is filled by one launch when somebody needs its bytes.
 Whatever an observer can see -- every Checksum(u128), every frame the ring holds, the live world -- must be the CPU oracle's, whether the
-slots were deferred or not, across rollbacks of every length, host edits, handed-out pointers and deferral switched on and off mid-session."""
-import re
-
+slots were deferred or not, across rollbacks of every length, host edits, handed-out pointers and deferral switched on and off mid-session -- and in a
+world whose kernel reads per-player inputs and a host-computed per-step constant, which a replay can only have from its record."""
 import numpy as np
 import pytest
 
@@ -16,9 +15,7 @@ pytestmark = pytest.mark.gpu
 DEFER_FORCED, DEFER_OFF = 3, 4          # ggrs_dbg_set_lazy_live: 3 = lazy live block and deferred Saves on every eligible list, 4 = by size without deferred Saves
 
 
-def _counts(w):
-    m = re.search(r"(\d+) Saves deferred, (\d+) ring slots materialised", w.kernel_info().get("deferred_saves", ""))
-    return (int(m.group(1)), int(m.group(2))) if m else None
+_counts = cm.deferred_counts
 
 
 def _ring_contents(w, ids, frames):
@@ -151,3 +148,113 @@ def test_deferral_switched_on_and_off_within_one_session(n):
         cm.assert_states_equal(r[1], res[2][1], "live")
         assert r[2].keys() == res[2][2].keys()
         for f in r[2]: cm.assert_states_equal(r[2][f], res[2][2][f], f"ring frame {f}")
+
+
+# ---- a world whose kernel reads what a replay has to get from its record: box_game (inputs per player, FRICTION.powf(dt) in aux_bits) with Player under rollback ----
+def _box_world(kind, n, max_depth, players, mode=None):
+    from test_box_game import build_box
+    w = bg.World(n + 8, max_depth=max_depth) if kind == "lib" else OracleWorld(n + 8, max_depth, FLAT)
+    if kind == "lib" and mode is not None: assert w._lib.ggrs_dbg_set_lazy_live(w._p, mode) == 0
+    ids, *_ = build_box(w, n, players, seed=3, spread=True, checksums=[(0, [0, 1, 2]), (1, [0, 1, 2])], player_rollback=True)
+    return w, ids
+
+
+def _box_inputs(frame, players, again=0):
+    """Four input bits per player, different for every frame and player -- and for every time the frame is advanced again (`again`: a prediction that was corrected)."""
+    return tuple(int(x) for x in np.random.default_rng([23, frame, again]).integers(0, 16, players))
+
+
+def _same(res):
+    assert res[0][0] == res[1][0]
+    cm.assert_states_equal(res[0][1], res[1][1], "live")
+    assert res[0][2].keys() == res[1][2].keys()
+    for f in res[0][2]: cm.assert_states_equal(res[0][2][f], res[1][2][f], f"ring frame {f}")
+
+
+def test_steady_synctest_of_a_world_that_reads_inputs_defers_by_the_natural_rule():
+    """No debug hook: box_game above the size where bytes bound a launch, SyncTest with check distance 7, every frame and player its own input bits.  After the Load
+    streak the ticks defer on their own; every ring frame loaded afterwards is replayed from the recorded inputs, n_inputs, dt_bits and aux_bits."""
+    n, D, players = 450_000, 7, 3
+    res = []
+    for kind in ("lib", "oracle"):
+        w, ids = _box_world(kind, n, D + 2, players)
+        drv = cm.SyncTestDriver(w, D, num_players=players)
+        for t in range(24): drv.tick(_box_inputs(t, players))
+        if kind == "lib":
+            assert w.kernel_info()["deferred_saves"].startswith("on"), w.kernel_info()["deferred_saves"]
+            d, m = _counts(w)
+            assert d >= (D - 1) * 4 and m == 0, w.kernel_info()["deferred_saves"]
+        live = cm.snapshot_state(w, ids)
+        res.append((drv.all_checksums, live, _ring_contents(w, ids, range(w.frame - D - 1, w.frame + 1))))
+        if kind == "lib":
+            assert _counts(w)[1] > 0, w.kernel_info()["deferred_saves"]
+            w.close()
+    _same(res)
+    assert len(res[0][2]) >= D
+
+
+def test_a_corrected_prediction_is_replayed_with_the_bytes_of_its_own_advance():
+    """P2P-shaped rollbacks of 0..7 frames, deferral forced: a rollback advances frames AGAIN with input bytes that differ from the first time (the prediction was
+    wrong).  The record of a deferring group must hold the inputs of the advance that produced the slot, not of an earlier or later advance of the same frame."""
+    n, players = 450_000, 4
+    res = []
+    for kind in ("lib", "oracle"):
+        w, ids = _box_world(kind, n, 9, players, mode=DEFER_FORCED)
+        times = {}
+
+        def inputs(frame, times=times):
+            times[frame] = times.get(frame, -1) + 1
+            return _box_inputs(frame, players, times[frame])
+        drv = cm.P2PShapeDriver(w, max_rollback=8, seed=29, inputs=inputs)
+        for _ in range(40): drv.tick()
+        assert max(times.values()) >= 2                                      # frames were advanced three times and more, each time with other bytes
+        if kind == "lib":
+            d, m = _counts(w)
+            assert d > 0 and m > 0, w.kernel_info()["deferred_saves"]
+        res.append((drv.all_checksums, cm.snapshot_state(w, ids), _ring_contents(w, ids, range(drv.frame - 9, drv.frame + 1))))
+        if kind == "lib": w.close()
+    _same(res)
+    assert len(res[0][2]) >= 2
+
+
+@pytest.mark.parametrize("between", ["confirmed_past_the_base", "depth_shrinks_below_the_chain", "frame_rate_changes"])
+def test_confirmation_depth_and_frame_rate_move_between_a_deferring_group_and_the_read(between):
+    """One deferring group [Load(1), (Advance, Save) x 4] -- base frame 2; frames 3, 4, 5 owed --, then, before anybody reads an owed slot:
+    ConfirmedFrameCount moves past the base (the next Saves prune the base and frame 3 and land in their blocks: the chain is filled from the base before it is
+    overwritten), the depth shrinks so that the base leaves the ring while its block still holds the bytes the chain is replayed from, or the frame rate
+    changes (the replay must step with the recorded dt_bits and FRICTION.powf(dt), not the world's current ones).  Then what remains is loaded."""
+    n, players = 100_000, 2
+    S, L, A = bg.SaveGameState, bg.LoadGameState, lambda f, again=0: bg.AdvanceFrame(_box_inputs(f, players, again))
+    res = []
+    for kind in ("lib", "oracle"):
+        w, ids = _box_world(kind, n, 9, players, mode=DEFER_FORCED)
+        w.set_depth(8)
+        if kind == "lib": w.set_synctest_check_distance(-1)
+        cks, ring = [], {}
+
+        def look(f):
+            cks.extend(w.handle_requests([L(f)]))
+            ring[f] = cm.snapshot_state(w, ids)
+        cks += w.handle_requests([S(0), A(0), S(1), A(1), S(2), A(2), S(3), A(3)])
+        cks += w.handle_requests([L(1), A(1, 1), S(2), A(2, 1), S(3), A(3, 1), S(4), A(4, 1), S(5)])        # (ends with a Save: the live block is written, nothing reads the chain yet)
+        if kind == "lib": assert _counts(w) == (3, 0), w.kernel_info()["deferred_saves"]
+        if between == "confirmed_past_the_base":
+            w.set_confirmed(4)
+            cks += w.handle_requests([A(5), S(6), A(6), S(7)])
+            assert [w.has_snapshot(f) for f in range(2, 8)] == [False, False, True, True, True, True]
+            look(5); look(4)
+        elif between == "depth_shrinks_below_the_chain":
+            w.set_depth(3)
+            cks += w.handle_requests([A(5), S(6)])
+            assert [w.has_snapshot(f) for f in range(2, 7)] == [False, False, True, True, True]
+            look(5); look(4)
+        else:
+            w.set_frame_rate(30)
+            look(4); look(3)
+            cks += w.handle_requests([A(3, 2), S(4), A(4, 2), S(5)])
+            look(5); look(2)
+        if kind == "lib": assert _counts(w)[1] > 0, w.kernel_info()["deferred_saves"]
+        cks += w.handle_requests([A(9), S(w.frame + 1), A(10), S(w.frame + 2)])
+        res.append((cks, cm.snapshot_state(w, ids), ring))
+        if kind == "lib": w.close()
+    _same(res)

@@ -2,7 +2,10 @@
 own copy; the matching branch's state is adopted).  Per seed: a world of random size / schema / spawn system, three consecutive branch steps with random branch counts'
 inputs, spawn selections and retention flags, every Checksum(u128) of the gathered table compared with the oracle walking the same branches as request lists; then a
 random branch is adopted at a random retained frame and the WHOLE live state (every column, mask and len) is compared with the oracle's replay of that branch.  One
-process runs all seeds (one RCCL communicator per world, world size 1: the collective is real, the transport trivial)."""
+process runs all seeds (one RCCL communicator per world, world size 1: the collective is real, the transport trivial).
+
+A world that drives a fan-out never defers a Save itself (its folds stay on the device: lazy_live_allowed), so no prefix of a branch step can leave a ring slot
+owed; what run_branch_step's materialise_slots can meet is a chain deferred BEFORE the fan-out was attached -- the sibling test at the end."""
 import multiprocessing as mp
 
 import pytest
@@ -146,3 +149,86 @@ def test_branch_steps_and_adoption_fuzzed_against_the_oracle(chunk):
         if p.is_alive(): p.kill()
     assert r[0] == "ok", r
     assert len(r[1]) == len(seeds)
+
+
+def _owed_rank(q, cases):
+    try:
+        import ctypes as C
+        import numpy as np
+        import bevy_ggrs_amd as bg
+        import common as cm
+        from bevy_ggrs_amd import _ffi
+        from bevy_ggrs_amd.fanout import RcclFanout
+        from oracle.binding import FLAT, OracleWorld
+        lib = _ffi.lib
+        S, L, A = bg.SaveGameState, bg.LoadGameState, lambda: bg.AdvanceFrame((0,))
+        report = []
+        for n, schema, vtags, T, B, then in cases:
+            what = dict(n=n, schema=schema, value_tags=vtags, T=T, B=B, then=then)
+            rng = np.random.default_rng([n, T, B])
+            gw, ow = bg.World(n + 64, max_depth=9), OracleWorld(n + 64, 9, FLAT)
+            assert (not vtags or lib.ggrs_dbg_set_value_tags(gw._p, 1) == 0) and lib.ggrs_dbg_set_lazy_live(gw._p, 3) == 0      # deferred Saves on every eligible group
+            for w in (gw, ow):
+                ids = cm.build_particles(w, schema=schema)
+                vel, ttl = cm.synthetic_particles(n, ttl="despawn", seed=n)
+                cm.spawn_particles(w, ids, n, vel, ttl)
+                w.set_depth(8)
+            # frames 2 .. 5 in the ring, 3 the base of a chain, 4 and 5 owed; the list ends with two Advances, so the live block (frame 7) is written
+            for reqs in ([A(), A()], [S(2)], [L(2), A(), S(3), A(), S(4), A(), S(5), A(), A()]):
+                assert list(gw.handle_requests(reqs)) == list(ow.handle_requests(reqs)), what
+            assert cm.deferred_counts(gw) == (2, 0), (what, gw.kernel_info().get("deferred_saves"))
+            native = RcclFanout(gw, 0, 1, RcclFanout.unique_id())
+            assert cm.deferred_counts(gw) == (2, 0), (what, "attaching a fan-out reads no ring slot")
+            for w in (gw, ow): w.set_confirmed(2)
+            F, prefix = 7, [S(7)]                                    # ring: 7, 5, 4, 3, 2 -- and T more per branch: nothing is evicted at depth 8
+            pred = rng.integers(0, 3, size=(B, T)).astype(np.uint8)
+            want = list(ow.handle_requests(prefix))
+            for b in range(B):
+                want += list(ow.handle_requests([L(F)] + [r for i in range(T) for r in (bg.AdvanceFrame((int(pred[b, i]),)), S(F + 1 + i))]))
+            ow.handle_requests([L(F)])
+            pre, keep, _ = gw.build_requests(prefix)
+            inputs = np.ascontiguousarray(pred.reshape(B, T, 1))
+            bs = _ffi.BranchStep()
+            bs.prefix, bs.n_prefix, bs.n_branches, bs.n_frames, bs.n_inputs, bs.flags = pre, len(prefix), B, T, 1, _ffi.BRANCH_SAVE_LAST | _ffi.BRANCH_RETAIN_ALL
+            bs.inputs = inputs.ctypes.data
+            ns = C.c_uint32(0)
+            rc = lib.ggrs_hip_fanout_step_branches(native._p, C.byref(bs), C.byref(ns))
+            assert rc == 0, (what, lib.ggrs_hip_fanout_last_error(native._p))
+            got = [int(p[0]) | (int(p[1]) << 64) for p in native.collect().reshape(-1, 2)]
+            assert got == want, (what, "the branch table")
+            assert cm.deferred_counts(gw) == (2, 2), (what, "the branch step fills what the ring is owed before it launches", gw.kernel_info().get("deferred_saves"))
+            if then == "adopt":
+                b, k = int(rng.integers(0, B)), int(rng.integers(1, T + 1))
+                native.adopt(b, F + k)
+                ow.handle_requests([L(F)] + [bg.AdvanceFrame((int(pred[b, i]),)) for i in range(k)])
+                assert gw.frame == ow.frame == F + k and gw.len == ow.len, (what, "adopt", gw.frame, ow.frame)
+                cm.assert_states_equal(cm.snapshot_state(gw, ids), cm.snapshot_state(ow, ids), f"{what} adopted branch {b} at +{k}")
+                assert gw.save() == ow.save(), (what, "SaveGameState after adoption")
+            else:
+                # (adoption confirms the adopted frame, which prunes everything older: the ring is read INSTEAD)  what the replay wrote -- the once-owed frames and
+                # the base they were replayed from --, loaded newest first
+                for f in (5, 4, 3):
+                    assert gw.has_snapshot(f) and ow.has_snapshot(f), (what, f)
+                    for w in (gw, ow): w.handle_requests([L(f)])
+                    cm.assert_states_equal(cm.snapshot_state(gw, ids), cm.snapshot_state(ow, ids), f"{what} ring frame {f}")
+            native.close()
+            report.append(what)
+        q.put(("ok", report))
+    except Exception as e:                                    # noqa: BLE001
+        import traceback
+        q.put(("error", f"{type(e).__name__}: {e}", traceback.format_exc()))
+
+
+def test_a_branch_step_on_a_world_that_still_owes_ring_slots():
+    """Deferred Saves forced, a rollback group defers two Saves, THEN the fan-out is attached: the first branch step finds a ring with slots whose bytes are owed.
+    The branch table and then either the adopted state or -- loaded one by one -- the frames that were owed equal the oracle's."""
+    cases = [c + (then,) for c in [(300, "headline", False, 2, 5), (6000, "full", True, 1, 17), (40_000, "allhot", False, 2, 2), (40_000, "headline", True, 2, 40)] for then in ("ring", "adopt")]
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    p = ctx.Process(target=_owed_rank, args=(q, cases)); p.start()
+    try: r = q.get(timeout=600)
+    finally:
+        p.join(timeout=30)
+        if p.is_alive(): p.kill()
+    assert r[0] == "ok", r
+    assert len(r[1]) == len(cases)
