@@ -126,6 +126,8 @@ void ggrs_hip_world_destroy(ggrs_world* w) {
     delete w->jl; w->jl = nullptr;
     if (w->d_gen_parts) (void)hipFree(w->d_gen_parts);
     if (w->d_branch_parts) (void)hipFree(w->d_branch_parts);
+    if (w->d_branch_marks) (void)hipFree(w->d_branch_marks);
+    if (w->d_branch_gone) (void)hipFree(w->d_branch_gone);
     if (w->d_skip) (void)hipFree(w->d_skip);
     sp_release(w);
     for (void* p : w->spec_allocs) (void)hipFree(p);
@@ -813,6 +815,8 @@ int ggrs_hip_world_kernel_info(ggrs_world* w, char* buf, uint64_t cap, uint64_t*
         add("deferred_saves", std::string(lazy_live_possible(w) && !w->has_strategy && defer_saves_on(w) ? "on" : "off") + " (rollback groups of the same sessions store their first Save only): " +
                               std::to_string(w->saves_deferred) + " Saves deferred, " + std::to_string(w->slots_materialised) + " ring slots materialised on demand");
         add("group_caps", std::to_string(w->cap_saves) + " saves / " + std::to_string(w->cap_steps) + " steps");
+        add("branch_marker_record_bytes", std::to_string(w->jit_marks ? jit_marks_rec_bytes(w) : 0));      // per retained branch of ggrs_hip_fanout_step_branches (0: the kernel keeps no markers)
+        add("branch_marker_records", std::to_string(w->branch_marks_cap));                                 // ... how many are allocated
         bool any_spawn = false;
         for (auto& sd : w->systems) any_spawn |= sd.kind == GGRS_SYS_PARTICLES_SPAWN || sd.kind == GGRS_SYS_SPAWN_CUSTOM;
         if (w->dev_spawn && jit_dev_stream(w)) { char t[256]; snprintf(t, sizeof t, "one streamed launch per request group: %u workgroups take tiles by ticket, children numbered by decoupled look-back (%d VGPRs, %d SGPRs)", w->sp_tiles, w->sp_regs, w->sp_sregs); add("device_spawn", t); }

@@ -341,6 +341,10 @@ int ggrs_hip_fanout_adopt(ggrs_fanout* f, uint32_t branch, int32_t frame, uint32
                           k.valid ? "kept other frames: GGRS_BRANCH_RETAIN_ALL keeps every one" : "kept none: GGRS_BRANCH_RETAIN_*");
         else spec_idx = k.blk[(size_t)local * k.n_out + (size_t)o];
     }
+    // a world whose kernel keeps RollbackDespawned markers: the adopted branch's marker record is merged into the live markers before the LoadWorld below.  With a
+    // broadcast every rank needs room for one record (the owner has its step's); a rank that cannot get it says so in the status agreement
+    const bool with_marks = w->jit_marks && (mine || mode == GGRS_ADOPT_BROADCAST);
+    if (with_marks && !pre && mode == GGRS_ADOPT_BROADCAST && f->size > 1) { pre = branch_marks_reserve(w, 1); if (pre) f->fail(pre, "%s", ggrs_hip_last_error(w)); }
     if (mode == GGRS_ADOPT_BROADCAST && f->size > 1) {
         // only the owner knows whether it kept that frame; the broadcast below is entered by every rank or by none (a rank that bailed out alone would leave the
         // others waiting in the collective for ever)
@@ -359,18 +363,39 @@ int ggrs_hip_fanout_adopt(ggrs_fanout* f, uint32_t branch, int32_t frame, uint32
         if (sl < 0) return f->fail(GGRS_E_INVALID, "adopt needs a ring depth of at least 1");
         Block& slot = w->slots[sl];
         if (mine) std::swap(slot, w->spec_blocks[spec_idx]);
+        // the adopted branch's marker record and how many of its words the step's launch wrote (the owner's BranchKeep; by broadcast on the other ranks)
+        const uint8_t* mrec = (mine && with_marks && f->keep.marks) ? f->keep.marks + (uint64_t)local * f->keep.rec_bytes : nullptr;
+        uint32_t munits = mrec ? f->keep.units : 0u;
         if (mode == GGRS_ADOPT_BROADCAST && f->size > 1) {
-            // the block describes itself: {len, frame, .., extent of its mask bits} in its header
+            // the block describes itself: {len, frame, words of the marker record that follows, extent of its mask bits} in its header
             Header h; memset(&h, 0, sizeof h);
-            if (mine) { h.len = slot.len; h.frame = frame; h.active = slot.dirty_len; FANCHK_HIP(f, hipMemcpyAsync(slot.ptr, &h, sizeof h, hipMemcpyHostToDevice, w->stream)); }
+            if (mine) { h.len = slot.len; h.frame = frame; h.pad0 = munits; h.active = slot.dirty_len; FANCHK_HIP(f, hipMemcpyAsync(slot.ptr, &h, sizeof h, hipMemcpyHostToDevice, w->stream)); }
             FANCHK_NCCL(f, rccl().Broadcast(slot.ptr, slot.ptr, (size_t)w->state_bytes, ncclUint8, owner, f->comm, w->stream));
             if (!mine) {
                 FANCHK_HIP(f, hipMemcpyAsync(&h, slot.ptr, sizeof h, hipMemcpyDeviceToHost, w->stream));
                 FANCHK_HIP(f, hipStreamSynchronize(w->stream));
-                if (h.len > w->capacity || h.frame != frame) return f->fail(GGRS_E_INVALID, "the broadcast block says frame %d, len %llu (expected frame %d, capacity %llu)", h.frame, (unsigned long long)h.len, frame, (unsigned long long)w->capacity);
+                if (h.len > w->capacity || h.frame != frame || (uint64_t)h.pad0 * 64u > w->cap_pad) return f->fail(GGRS_E_INVALID, "the broadcast block says frame %d, len %llu, %u marker words (expected frame %d, capacity %llu)", h.frame, (unsigned long long)h.len, h.pad0, frame, (unsigned long long)w->capacity);
                 slot.len = h.len; slot.dirty_len = std::min<uint64_t>(std::max<uint64_t>(h.active, h.len), w->cap_pad);
                 for (uint32_t c = 0; c < slot.ver.size(); ++c) slot.ver[c] = ++w->ver_counter;      // bytes from another rank: every column is new
+                munits = h.pad0;
             }
+            if (with_marks) {
+                // the marker record follows the block in ONE broadcast, bounded by the step's cover: the record from its first word to the last frame the launch could have
+                // written (the words the launch did not write, between the two parts, travel unread: at most capacity / 8 bytes).  Every rank enters it (the owner's header
+                // said how many words; a step without retained markers says 0 and nothing is sent)
+                uint8_t* rbuf = mine ? const_cast<uint8_t*>(mrec) : w->d_branch_marks;
+                if (munits) {
+                    FANCHK_NCCL(f, rccl().Broadcast(rbuf, rbuf, (size_t)(jit_marks_rec_frames_off(w) + (uint64_t)munits * 256u), ncclUint8, owner, f->comm, w->stream));
+                    mrec = rbuf;
+                }
+                FANCHK_HIP(f, hipMemsetAsync(slot.ptr + offsetof(Header, pad0), 0, sizeof h.pad0, w->stream));      // the slot's header is a snapshot's again
+            }
+        }
+        if (mrec && munits) {
+            // BEFORE the LoadWorld: its reconcile must find these entities disabled, so that they keep their non-rollback components
+            hipLaunchKernelGGL(k_merge_branch_marks, dim3((munits * 64u + TPB - 1) / TPB), dim3(TPB), 0, w->stream, w->live.ptr, w->off_alive, w->marks, mrec, jit_marks_rec_frames_off(w), munits, frame);
+            FANCHK_HIP(f, hipGetLastError());
+            w->marks_possible = true;
         }
         // LoadWorld from that slot (schedule_systems.rs:238-250): the live world IS the adopted state
         ggrs_request ld; memset(&ld, 0, sizeof ld); ld.kind = GGRS_REQ_LOAD; ld.frame = frame;

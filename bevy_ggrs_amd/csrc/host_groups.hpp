@@ -836,10 +836,16 @@ int run_request_groups_gen(ggrs_world* w, const ggrs_request* reqs, uint32_t n, 
 // PlayerInputs and spawns, in ONE launch of the generated kernel: gridDim.z = B, member z's differences in a record in device memory (kernel_gen.hpp
 // JitLayout::Member).  Branches are speculation, not history: nothing here touches the ring, the frame counters or the live block.  What a branch produces is its
 // Checksum(u128)s and -- when asked to be kept -- its frames in blocks of their own (ggrs_world::spec_blocks), under row versions like every other block.
+// LIVE-ONLY STATE (RollbackDespawned markers, non-rollback components).  Every member reads the markers and the live-only columns the prefix left, from the live block all
+// members share read-only; a branch's own markers stay in its registers and -- for a retained branch -- go to its MARKER RECORD (one per branch, not per frame: markers are
+// monotone inside a branch, so the branch's markers at frame f are the world's plus the record's slots whose frame is <= f), which ggrs_hip_fanout_adopt merges into the live
+// markers.  A DespawnConfirmed that is due runs once on the live world before the launch (what the first AdvanceFrame of the list form does).  The entities of the source
+// block that some member despawned for good lose their non-rollback components after the launch (k_clear_gone): what the next LoadGameState's reconcile does in the list form.
 // ---------------------------------------------------------------------------------------------------------------------
 struct BranchKeep {          // what the last branch step retained: output o of branch b (frame base_frame + 1 + o) lives in spec_blocks[blk[b * n_out + o]] (-1: not kept)
     bool valid = false; uint32_t n_branches = 0, n_out = 0, n_frames = 0; int32_t base_frame = 0;
     std::vector<int> blk;
+    uint8_t* marks = nullptr; uint64_t rec_bytes = 0; uint32_t units = 0;     // branch b's marker record at marks + b * rec_bytes (nullptr: the world's kernel keeps no markers); only the first `units` words of a record were written by the step's launch
 };
 constexpr uint32_t BRANCH_MAX = 4096;
 // spec_blocks[0 .. n): allocated in chunks, header + masks zeroed (the invariant every block keeps: mask words beyond its dirty_len are zero)
@@ -861,11 +867,20 @@ int spec_blocks_reserve(ggrs_world* w, size_t n) {
     }
     return GGRS_OK;
 }
+// marker records of retained branches (ggrs_world::d_branch_marks): room for n of them
+int branch_marks_reserve(ggrs_world* w, uint64_t n) {
+    if (n <= w->branch_marks_cap) return GGRS_OK;
+    const uint64_t rb = jit_marks_rec_bytes(w);
+    uint8_t* p = nullptr;
+    if (hipMalloc((void**)&p, n * rb) != hipSuccess) { (void)hipGetLastError(); return w->fail(GGRS_E_HIP, "hipMalloc of %llu branch marker records (%llu bytes each, %llu bytes in all) failed", (unsigned long long)n, (unsigned long long)rb, (unsigned long long)(n * rb)); }
+    if (w->d_branch_marks) { if (hipStreamSynchronize(w->stream) != hipSuccess) { (void)hipFree(p); return w->fail(GGRS_E_HIP, "hipStreamSynchronize failed"); } (void)hipFree(w->d_branch_marks); }
+    w->d_branch_marks = p; w->branch_marks_cap = n;
+    return GGRS_OK;
+}
 // everything that can be checked before the prefix runs
 int validate_branch_step(ggrs_world* w, const ggrs_branch_step& st) {
     if (!w->gen_ok) return w->fail(GGRS_E_INVALID, "branch steps need the generated request-group kernel, which this world does not have: %s", w->jit_status.c_str());
     if (w->dev_spawn) return w->fail(GGRS_E_INVALID, "branch steps are not available for worlds whose systems spawn on the device (every launch is one cooperative grid): use ggrs_hip_fanout_step");
-    if (w->jit_marks || w->has_nr || w->marks_possible) return w->fail(GGRS_E_INVALID, "branch steps are not available for worlds with live-only state (RollbackDespawned markers -- a system that can call despawn_rollback() --, non-rollback components): use ggrs_hip_fanout_step");
     if (st.n_branches == 0 || st.n_branches > BRANCH_MAX) return w->fail(GGRS_E_INVALID, "a branch step holds 1..%u branches, not %u", BRANCH_MAX, st.n_branches);
     const uint32_t S = (st.flags & GGRS_BRANCH_SAVE_LAST) ? st.n_frames : st.n_frames - 1;
     if (st.n_frames == 0 || st.n_frames > w->cap_steps || S > w->cap_saves) return w->fail(GGRS_E_INVALID, "a branch covers 1..%u frames (%u SaveGameStates) in this world, not %u", w->cap_steps, w->cap_saves, st.n_frames);
@@ -925,6 +940,7 @@ int run_branch_step(ggrs_world* w, const ggrs_branch_step& st, uint32_t res_firs
         j.op_bits |= 1ull << j.n_ops; ++j.n_ops;
         j.dt_bits[i] = dt_bits_for_frame(w->fps, F + 1 + (int32_t)i);
         j.step_frame[i] = F + 1 + (int32_t)i; j.step_confirmed[i] = w->confirmed;
+        if (w->jit_marks) j.step_flags[i] = w->confirmed < F + 1 + (int32_t)i ? 2u : 0u;      // bit 1: despawn_rollback() defers (group_step); bit 0 never: DespawnConfirmed runs on the live world before the launch
         if (w->jit_box_sys >= 0) { float dtf; memcpy(&dtf, &j.dt_bits[i], 4); const float fp = powf(w->systems[w->jit_box_sys].fparam[2], dtf); memcpy(&j.aux_bits[i], &fp, 4); }
         if (i < S) { j.save_frame[i] = F + 1 + (int32_t)i; ++j.n_ops; }
     }
@@ -954,6 +970,13 @@ int run_branch_step(ggrs_world* w, const ggrs_branch_step& st, uint32_t res_firs
     // ---- members: inputs, spawns, lens; with retention the blocks their frames land in and the rows each store moves (row versions)
     size_t n_keep = 0;
     if (keep_any) { n_keep = (size_t)B * (keep_all ? n_out : 1u); rc = spec_blocks_reserve(w, n_keep); if (rc) return rc; }
+    const bool keep_marks = keep_any && w->jit_marks;                  // a retained branch keeps its markers too
+    const uint64_t rec_bytes = keep_marks ? jit_marks_rec_bytes(w) : 0;
+    if (keep_marks) { rc = branch_marks_reserve(w, B); if (rc) return rc; }
+    if (w->has_nr && !w->d_branch_gone && hipMalloc((void**)&w->d_branch_gone, w->cap_pad / 8) != hipSuccess) {
+        (void)hipGetLastError(); w->d_branch_gone = nullptr;
+        return w->fail(GGRS_E_HIP, "hipMalloc of the branch step's mask of despawned entities (%llu bytes) failed", (unsigned long long)(w->cap_pad / 8));
+    }
     // value tags: the launch's ids are reserved BEFORE any block's tag_ok is read or set below (a start-over of the numbering clears them all)
     if (w->vtags && keep_any) { rc = vtags_reserve(w, T, B, &j.tag_base); if (rc) return rc; }
     if (keep) { keep->n_branches = B; keep->n_out = n_out; keep->n_frames = T; keep->base_frame = F; keep->blk.assign((size_t)B * n_out, -1); }
@@ -1024,6 +1047,7 @@ int run_branch_step(ggrs_world* w, const ggrs_branch_step& st, uint32_t res_firs
         j.live = nullptr; j.live_rows = 0; j.live_pmask = 0; j.live_tagok = 0;
         if (tail_adv) { Block* d = keep_into(n_out - 1, &j.live_rows, &j.live_pmask, &j.live_tagok); j.live = d ? d->ptr : nullptr; }
         max_len = std::max(max_len, len_b);
+        j.marks_dst = keep_marks ? w->d_branch_marks + (uint64_t)b * rec_bytes : nullptr;
         jit_pack_member(L, j, rec.data() + (size_t)b * L.m.bytes);
     }
     memcpy(w->h_stage + soff, rec.data(), rec.size());
@@ -1039,11 +1063,16 @@ int run_branch_step(ggrs_world* w, const ggrs_branch_step& st, uint32_t res_firs
         w->branch_parts_cap = parts_need;
     }
     memset(j.save_dst, 0, sizeof j.save_dst); memset(j.save_rows, 0, sizeof j.save_rows); memset(j.save_pmask, 0, sizeof j.save_pmask);
-    j.live = w->live.ptr; j.live_rows = 0; j.live_pmask = 0;           // (never used: every member's record says where its live output goes)
+    j.live = w->live.ptr; j.live_rows = 0; j.live_pmask = 0;           // no member WRITES here (its record says where its live output goes); every member READS the live-only state here --
+                                                                       // the markers (mk_dis, df_0) and live-only columns a system reads --, which is why the live block was materialised above
     j.mtab = w->d_stage + soff;
     j.load_rows = load_rows;
     j.parts = reinterpret_cast<ggrs_u64*>(w->d_branch_parts); j.part_stride = g; j.part_tstride = 1;
     j.n_units = std::max<uint32_t>(1, (uint32_t)((cover + 63) / 64));
+    // live-only state: a DespawnConfirmed that is due runs once on the live world, ahead of the launch on the stream; the members then see ConfirmedFrameCount unchanged
+    rc = step_despawn_confirmed(w); if (rc) return rc;
+    j.marks_dst = nullptr;
+    if (w->has_nr) { HIPCHK(w, hipMemsetAsync(w->d_branch_gone, 0, (size_t)j.n_units * 8, w->stream)); j.gone = reinterpret_cast<ggrs_u64*>(w->d_branch_gone); }
     // branch blocks are written once and not read before an adoption: past what the caches hold they stream around them
     j.nt = (cover > JIT_NT_MIN_SLOTS || store_bytes > (128ull << 20)) ? 1u : 0u;
     j.cached_saves = 0; j.nt_loads = 0; j.dp_s = 0;
@@ -1053,6 +1082,12 @@ int run_branch_step(ggrs_world* w, const ggrs_branch_step& st, uint32_t res_firs
     hipFunction_t fn = jit_spec_for(w, j, true);                      // the copy of the kernel built for this op sequence, once the session has sent it often enough
     if (!fn) fn = w->jit_fn;
     rc = launch_jit(w, fn, jit_grid(g), 1, B, jit_lane_fold_bytes(w, n_cks, S), j, rows_bytes_per_slot(w, load_rows, true) * src.len * B + store_bytes); if (rc) return rc;
+    if (w->has_nr) {                                                  // what the members despawned for good loses its non-rollback components, once every member is done reading them
+        MaskOffs nr; uint32_t n_nr = 0;
+        for (uint32_t c = 0; c < w->comps.size(); ++c) if (w->comps[c].no_rollback) nr.off[n_nr++] = w->off_present[c];
+        hipLaunchKernelGGL(k_clear_gone, dim3((j.n_units + TPB - 1) / TPB), dim3(TPB), 0, w->stream, w->live.ptr, (const uint64_t*)w->d_branch_gone, j.n_units, n_nr, nr);
+        HIPCHK(w, hipGetLastError());
+    }
     if (S) {
         GenFinArgs f = make_gen_fin(w, j, g, n_cks, res_first);
         f.mtab = w->d_stage + soff; f.mstride = L.m.bytes; f.moff_save_len = L.m.save_len;
@@ -1062,7 +1097,7 @@ int run_branch_step(ggrs_world* w, const ggrs_branch_step& st, uint32_t res_firs
         }
         HIPCHK(w, hipGetLastError());
     }
-    if (keep) keep->valid = keep_any;
+    if (keep) { keep->valid = keep_any; keep->marks = keep_marks ? w->d_branch_marks : nullptr; keep->rec_bytes = rec_bytes; keep->units = j.n_units; }
     return GGRS_OK;
 }
 

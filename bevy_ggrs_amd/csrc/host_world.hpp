@@ -333,6 +333,10 @@ struct ggrs_world {
     // until the world goes -- an adopted branch state trades places with a ring slot (ggrs_hip_fanout_adopt), so both sets belong to the world
     std::vector<Block> spec_blocks; std::vector<void*> spec_allocs;
     uint64_t* d_branch_parts = nullptr; uint64_t branch_parts_cap = 0;      // partial rows of a member launch: [members x saves x (n_cks + 1)][workgroups]
+    // branch steps of worlds with live-only state: one marker record per retained branch (kernel_gen.hpp jit_marks_rec_bytes each; allocated at the first retained step of a
+    // world whose kernel keeps markers), and the per-unit mask of the entities some branch despawned for good (worlds with non-rollback components); freed with the world
+    uint8_t* d_branch_marks = nullptr; uint64_t branch_marks_cap = 0;       // records allocated
+    uint64_t* d_branch_gone = nullptr;
     ggrs_world** fanout_backref = nullptr;   // the `w` field of the ggrs_fanout driving this world: cleared by world_destroy, so a fan-out object that outlives its world touches nothing
     std::deque<PendingBatch> pending; uint32_t res_head = 0; uint32_t pending_results = 0;
     std::vector<hipEvent_t> event_pool;

@@ -223,6 +223,10 @@ struct GgrsJitArgs {
     // and each parent tile writes one record per child into sp_recs (9 words: the parent's bound words, then {epoch, k}) at a place it reserves from the pool
     // cursor sp_ctl[1]; sp_desc[MAX_TICK_STEPS + step][tile] says where.  Epochs: sp_epoch + 1 + step, the cursor's sp_epoch + MAX_TICK_STEPS + 1
     ggrs_u64* sp_ctl; ggrs_u64* sp_desc; ggrs_u64* sp_recs; ggrs_u64 sp_ticket_base;
+    // BRANCH STEPS of worlds with live-only state (run_branch_step): gone = one u64 per 64-slot unit, zeroed before the launch -- every member ORs in the slots that were alive in
+    // the source block and that it despawned for good (not deferred): their non-rollback components are cleared once the launch is over (k_clear_gone).  marks_dst (host side
+    // only: it travels in the member's record) = this member's marker record -- per unit the u64 of the slots the branch newly disabled, then one i32 frame per slot
+    ggrs_u64* gone; unsigned char* marks_dst;
     ggrs_u32 cached_saves;                           // with nt: bit i = Save i is stored through the L2 all the same (the snapshot the NEXT group is expected to load)
     ggrs_u32 ff_blocks, ff_nvals, ff_g, ff_stride, ff_istride, ff_split, ff_self;   // entry e of row r: ff_rows[r * ff_stride + e * ff_istride]
     ggrs_u32 dt_bits[24], aux_bits[24]; int step_frame[24], step_confirmed[24]; ggrs_u32 spawn_count[24];
@@ -244,10 +248,10 @@ struct JitLayout {
     uint32_t cap_saves = MAX_TICK_SAVES, cap_steps = MAX_TICK_STEPS;    // a group of this world ends at this many Saves / steps
     uint32_t in_stride = 0, in_bytes = 1, max_players = GGRS_MAX_PLAYERS;   // bytes of one step's input block on the device (0: no system reads PlayerInputs)
     // one batch member's record (GgrsJitArgs::mtab): byte offsets inside it, its size (a multiple of 8); absent fields keep offset 0 and are never read
-    struct Member { uint32_t bytes = 0, save_dst = 0, save_rows = 0, save_len = 0, spawn_payload = 0, spawn_first = 0, live = 0, live_rows = 0, save_pmask = 0, live_pmask = 0,
+    struct Member { uint32_t bytes = 0, save_dst = 0, save_rows = 0, save_len = 0, spawn_payload = 0, spawn_first = 0, live = 0, live_rows = 0, marks_dst = 0, save_pmask = 0, live_pmask = 0,
                     spawn_count = 0, n_inputs = 0, inputs = 0, save_tagok = 0, live_tagok = 0; } m;
 };
-struct JitNeeds { bool spawn, inputs, marks, box, vtags, devspawn, devstream; };
+struct JitNeeds { bool spawn, inputs, marks, box, vtags, devspawn, devstream, nr; };
 JitNeeds jit_needs(const ggrs_world* w);
 // the device-side layout of this world's argument block: 8-byte fields first, then 4-byte, then bytes (no padding inside)
 JitLayout jit_layout(const ggrs_world* w) {
@@ -272,6 +276,7 @@ JitLayout jit_layout(const ggrs_world* w) {
         F1("const ggrs_u64*", ff_rows, true); F1("ggrs_u64*", ff_out, true); F1("ggrs_u64", ff_seq, true);
         F1("ggrs_u64", live_rows, true); F1("ggrs_u64", load_rows, true); F1("ggrs_u64", op_bits, true); F1("ggrs_u64", len, true);
         F1("ggrs_u64", src_tagok, need.vtags); F1("ggrs_u64", live_tagok, need.vtags); F1("ggrs_u64*", skip_count, need.vtags); FA("ggrs_u64", save_tagok, S, need.vtags);
+        F1("ggrs_u64*", gone, need.nr);
         FA("unsigned char*", save_dst, S, true); FA("ggrs_u64", save_rows, S, true); FA("ggrs_u64", save_len, S, true);
         FS("const unsigned char*", spawn_payload, need.spawn); FS("ggrs_u64", spawn_first, need.spawn);
         FA("int", save_frame, S, true); FA("ggrs_u32", save_pmask, S, true);
@@ -311,6 +316,7 @@ JitLayout jit_layout(const ggrs_world* w) {
         L.m.save_dst = o; o += 8 * S; L.m.save_rows = o; o += 8 * S; L.m.save_len = o; o += 8 * S;
         if (need.spawn) { L.m.spawn_payload = o; o += 8 * T; L.m.spawn_first = o; o += 8 * T; }
         L.m.live = o; o += 8; L.m.live_rows = o; o += 8;
+        if (need.marks) { L.m.marks_dst = o; o += 8; }
         if (need.vtags) { L.m.save_tagok = o; o += 8 * S; L.m.live_tagok = o; o += 8; }
         L.m.save_pmask = o; o += 4 * S; L.m.live_pmask = o; o += 4;
         if (need.spawn) { L.m.spawn_count = o; o += 4 * T; }
@@ -353,6 +359,7 @@ inline void jit_pack_member(const JitLayout& L, const GgrsJitArgs& j, unsigned c
     memcpy(buf + m.save_dst, j.save_dst, 8 * S); memcpy(buf + m.save_rows, j.save_rows, 8 * S); memcpy(buf + m.save_len, j.save_len, 8 * S);
     if (m.spawn_first) { memcpy(buf + m.spawn_payload, j.spawn_payload, 8 * T); memcpy(buf + m.spawn_first, j.spawn_first, 8 * T); memcpy(buf + m.spawn_count, j.spawn_count, 4 * T); }
     memcpy(buf + m.live, &j.live, 8); memcpy(buf + m.live_rows, &j.live_rows, 8);
+    if (m.marks_dst) memcpy(buf + m.marks_dst, &j.marks_dst, 8);
     if (m.live_tagok) { memcpy(buf + m.save_tagok, j.save_tagok, 8 * S); memcpy(buf + m.live_tagok, &j.live_tagok, 8); }
     memcpy(buf + m.save_pmask, j.save_pmask, 4 * S); memcpy(buf + m.live_pmask, &j.live_pmask, 4);
     if (m.inputs) { memcpy(buf + m.n_inputs, j.n_inputs, T); for (uint32_t r = 0; r < T && r < j.n_steps; ++r) memcpy(buf + m.inputs + r * L.in_stride, j.inputs[r], L.in_stride); }
@@ -475,13 +482,17 @@ bool jit_dev_spawn(const ggrs_world* w) {
 }
 // ... in the streamed form: forced (GGRS_TICK_JIT=2), or chosen at seal because the device cannot hold the resident form's grid
 bool jit_dev_stream(const ggrs_world* w) { return jit_dev_spawn(w) && (w->sp_streamed || w->knobs.dev_spawn_streamed); }
+// a retained branch's marker record (run_branch_step): one u64 per 64-slot unit, then -- at this offset -- one i32 frame per slot; sized by the padded capacity like the live block's markers
+inline uint64_t jit_marks_rec_frames_off(const ggrs_world* w) { return align_up(w->cap_pad / 8, ALIGN); }
+inline uint64_t jit_marks_rec_bytes(const ggrs_world* w) { return jit_marks_rec_frames_off(w) + align_up(w->cap_pad * 4, ALIGN); }
 // which optional parts of the argument block this world's kernel reads
 JitNeeds jit_needs(const ggrs_world* w) {
-    JitNeeds n{false, false, false, false, false, false, false};
+    JitNeeds n{false, false, false, false, false, false, false, false};
     n.vtags = vtags_policy(w);
     n.devspawn = jit_dev_spawn(w);
     n.devstream = jit_dev_stream(w);
     n.spawn = jit_fused_spawn_system(w) >= 0;
+    if (!n.devspawn) for (auto& c : w->comps) n.nr |= c.no_rollback;      // (branch steps are closed to worlds that spawn on the device: their kernel has no `gone` text)
     for (auto& d : w->systems) {
         n.inputs |= d.kind == GGRS_SYS_CUSTOM || d.kind == GGRS_SYS_BOX_MOVE || d.kind == GGRS_SYS_SPAWN_CUSTOM;
         n.marks |= (d.kind == GGRS_SYS_CUSTOM && w->customs[d.comp[0]].may_defer) || (d.kind == GGRS_SYS_SAT_SUB_DESPAWN && d.iparam[1] == GGRS_DESPAWN_ROLLBACK);
@@ -738,6 +749,9 @@ bool jit_source(const ggrs_world* w, std::string& s) {
     // ---- masks and words of the lane's slot
     sfmt(s, "    const uint64_t mk_alive = *reinterpret_cast<const uint64_t*>(a.src + %lluull + wi8);\n"
             "    bool alive_0 = (mk_alive >> sh) & 1ull;\n", OFF_ALIVE);
+    // (worlds with non-rollback components: who was alive in the source block, for the `gone` ballot of a batch member at the end of the unit.  One VGPR, made opaque
+    // so that it is not rebuilt from mk_alive there: the word, or a.src to read it again, held in SGPRs across the unit costs the marker test world a wave per SIMD)
+    if (need.nr) s += "    uint32_t src_alive_v = alive_0 ? 1u : 0u; asm volatile(\"\" : \"+v\"(src_alive_v));\n";
     for (uint32_t c = 0; c < nc; ++c) if (rb(c))
         sfmt(s, "    const uint64_t mk%u = *reinterpret_cast<const uint64_t*>(a.src + %lluull + wi8);\n"
                 "    %sbool p%u_0 = (mk%u >> sh) & 1ull;\n", c, (unsigned long long)w->off_present[c], spawn_sys >= 0 ? "" : "const ", c, c);
@@ -1391,11 +1405,29 @@ bool jit_source(const ggrs_world* w, std::string& s) {
     else if (DEV) s += "        if (gu == 0 && lane == 0) { *reinterpret_cast<uint64_t*>(live_p) = cur_len; a.sp_len[0] = cur_len; }      // the live block's header carries RollbackOrdered::len for whoever loads it next; the host reads it from pinned memory\n";
     s += "    }\n";
     if (marks) {
-        s += "    if (my_live && a.n_steps) {\n"
+        // a batch member's markers are its own: the live block is shared by all members, read-only; what the branch newly disabled goes to its marker record (retained branches)
+        s += "    if (!mb && my_live && a.n_steps) {\n"
              "        const uint64_t dis_w = __ballot(dis_0);\n";
         sfmt(s, "        if (lane == 0) *reinterpret_cast<uint64_t*>(a.live + %lluull + wi8) = dis_w;\n"
                 "        *reinterpret_cast<int*>(a.live + %lluull + e0 * 4u) = df_0;\n", OFF_DIS, OFF_DF);
         s += "    }\n";
+        sfmt(s, "    if (mb) {\n"
+                "        unsigned char* const mk_rec = (unsigned char*)mb_u64(mb, %uu);             // this member's marker record (null: the branch is not retained)\n"
+                "        if (mk_rec) {\n"
+                "            const uint64_t mk_new = __ballot(dis_0) & ~mk_dis;                      // markers are monotone inside a branch: the world's plus these\n"
+                "            if (lane == 0) *reinterpret_cast<uint64_t*>(mk_rec + wi8) = mk_new;\n"
+                "            if ((mk_new >> sh) & 1ull) *reinterpret_cast<int*>(mk_rec + %lluull + e0 * 4u) = df_0;\n"
+                "        }\n"
+                "    }\n", L.m.marks_dst, (unsigned long long)jit_marks_rec_frames_off(w));
+    }
+    if (need.nr) {
+        // an entity of the source block that a member despawned for good loses its non-rollback components (what the next LoadWorld's reconcile does in the list form):
+        // collected here, applied to the live block by one small kernel after the launch -- no member writes the live block while another may read it
+        // An entity alive in the source block is not disabled there (a deferred despawn clears `alive`), so at the end "not alive and not disabled" is "despawned for good"
+        sfmt(s, "    if (mb && a.gone) {\n"
+                "        const uint64_t gone_w = __ballot(src_alive_v && !alive_0%s);\n"
+                "        if (lane == 0 && gone_w) atomicOr((unsigned long long*)(a.gone + gu), (unsigned long long)gone_w);\n"
+                "    }\n", marks ? " && !dis_0" : "");
     }
     s += "    }   // the wave's unit\n";
     sfmt(s, "    // ---- this workgroup's partial rows (blockIdx.z: member of a batch of identical checksum-only groups)\n"

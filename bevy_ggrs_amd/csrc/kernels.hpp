@@ -562,6 +562,43 @@ __global__ __launch_bounds__(TPB) void k_despawn_confirmed(uint8_t* live, Despaw
     const uint64_t gone = __ballot(d && m <= confirmed);
     if (lane == 0 && gone) *reinterpret_cast<uint64_t*>(live + dm.off_disabled + wi8) = dis & ~gone;
 }
+// BRANCH STEPS of worlds with live-only state (host_groups.hpp run_branch_step, host_fanout.hpp ggrs_hip_fanout_adopt).
+// Adoption of a retained branch: its marker record -- per 64-slot unit the u64 of the slots the branch newly disabled, then (at frames_off) one i32 frame per
+// such slot -- joins the live markers up to the adopted frame (markers are monotone inside a branch), and those entities stop being alive.  Queued BEFORE the
+// adoption's LoadWorld: k_load_reconcile must find them disabled, so that they keep their non-rollback components.  One slot per lane; only the first n_units
+// words of the record were written by the step's launch.
+struct MaskOffs { uint64_t off[MAX_MASKS]; };
+__global__ __launch_bounds__(TPB) void k_merge_branch_marks(uint8_t* live, uint64_t off_alive, DespawnMarks dm, const uint8_t* rec, uint64_t frames_off,
+                                                            uint32_t n_units, int32_t frame) {
+    const uint64_t e = (uint64_t)blockIdx.x * TPB + threadIdx.x;
+    if ((e >> 6) >= n_units) return;                  // whole waves only
+    const uint64_t wi8 = (e >> 6) * 8;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t nw = *reinterpret_cast<const uint64_t*>(rec + wi8);
+    const bool mine = (nw >> lane) & 1ULL;
+    const int32_t m = mine ? *reinterpret_cast<const int32_t*>(rec + frames_off + e * 4) : 0;
+    const bool take = mine && m <= frame;
+    const uint64_t sel = __ballot(take);
+    if (!sel) return;
+    if (take) *reinterpret_cast<int32_t*>(live + dm.off_dframe + e * 4) = m;
+    if (lane == 0) {
+        *reinterpret_cast<uint64_t*>(live + dm.off_disabled + wi8) |= sel;
+        *reinterpret_cast<uint64_t*>(live + off_alive + wi8) &= ~sel;
+    }
+}
+// After a member launch: the entities some branch despawned for good (GgrsJitArgs::gone) lose their non-rollback components -- what the reconcile of the next
+// LoadGameState does to them in the list form.  One mask word per thread.
+__global__ __launch_bounds__(TPB) void k_clear_gone(uint8_t* live, const uint64_t* gone, uint32_t n_units, uint32_t n_nr, MaskOffs nr_present_off) {
+    const uint32_t wi = blockIdx.x * TPB + threadIdx.x;
+    if (wi >= n_units) return;
+    const uint64_t g = gone[wi];
+    if (!g) return;
+    for (uint32_t k = 0; k < n_nr; ++k) {
+        uint64_t* p = reinterpret_cast<uint64_t*>(live + nr_present_off.off[k] + (uint64_t)wi * 8);
+        const uint64_t v = *p;
+        if (v & g) *p = v & ~g;
+    }
+}
 
 // System-scope release + acquire on whatever CU / XCD the wave lands on: `buffer_wbl2 sc0 sc1` writes the XCD's dirty L2 lines back,
 // `buffer_inv sc0 sc1` drops its clean ones.  2048 single-wave workgroups cover all 8 XCDs (workgroup b lands on XCD b % 8).
@@ -572,7 +609,6 @@ __global__ void k_flush_l2() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, ""); }
 // rollback.rs:45-59) and clear the live-only masks a fresh entity does not carry (non-rollback
 // components outside its bundle, a stale RollbackDespawned marker).  One mask word per thread; each
 // word is owned by exactly one thread.
-struct MaskOffs { uint64_t off[MAX_MASKS]; };
 __global__ __launch_bounds__(TPB) void k_set_mask_range(uint8_t* state, uint64_t first, uint64_t count,
                                                         uint32_t n_masks, MaskOffs mask_off_set,
                                                         uint32_t n_clear, MaskOffs mask_off_clear) {

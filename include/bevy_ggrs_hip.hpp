@@ -443,7 +443,8 @@ public:
     SpeculativeFanout(const SpeculativeFanout&) = delete;
     void sync_confirmed(int root = 0) { check(ggrs_hip_fanout_sync_confirmed(f_, root)); }
     void set_interval(uint32_t steps_per_all_gather) { check(ggrs_hip_fanout_set_interval(f_, steps_per_all_gather)); }
-    // prefix requests, then n_branches x n_frames predicted inputs ([branch][frame][player x input bytes]); flags: GGRS_BRANCH_*; returns the step's SaveGameState count
+    // prefix requests, then n_branches x n_frames predicted inputs ([branch][frame][player x input bytes]); flags: GGRS_BRANCH_*; returns the step's SaveGameState count.
+    // Worlds with RollbackDespawned markers or non-rollback components included: a branch's markers are its own, a retained branch's are merged by adopt (ggrs_hip.h)
     uint32_t step_branches(const std::vector<ggrs_request>& prefix, uint32_t n_branches, uint32_t n_frames, uint32_t n_inputs, const std::vector<uint8_t>& inputs,
                            uint32_t flags = 0, const std::vector<ggrs_branch_spawn>& spawn_table = {}, const std::vector<uint16_t>& spawn_sel = {}) {
         ggrs_branch_step st; std::memset(&st, 0, sizeof st);

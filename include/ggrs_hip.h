@@ -175,7 +175,7 @@ int ggrs_hip_add_system(ggrs_world* w, const ggrs_system_desc* desc);
  *   e.slot                                      the entity's RollbackOrdered index (snapshot/rollback.rs:69-74)
  *   e.despawn() / e.despawn_rollback()          commands.entity(e).despawn() / .despawn_rollback() (snapshot/despawn.rs:114-143).  A world in which some system's
  *                                               source names despawn_rollback (or the `kill` field) can hold RollbackDespawned markers -- live-only state --: it
- *                                               keeps its live block written every tick and is closed to ggrs_hip_fanout_step_branches; other worlds are not
+ *                                               keeps its live block written every tick; ggrs_hip_fanout_step_branches gives each branch markers of its own
  *   e.spawn(n)                                  commands.spawn((.., Rollback)) x n, decided HERE, on the device: see GGRS_SPAWN_PAYLOAD_PARENT below
  *   f.dt  f.frame  f.n_inputs                   Time<GgrsTime>::delta_secs (time.rs), the frame being simulated, PlayerInputs::len()
  *   f.input[h]                                  first byte of player h's input (the whole input of a Config<Input = u8> session)
@@ -478,18 +478,33 @@ int  ggrs_hip_fanout_comm_info(ggrs_fanout* f, int* rank_out, int* size_out, int
  * GGRS_BRANCH_RETAIN_ALL keeps every frame a branch produces -- each SaveGameState's snapshot and, without GGRS_BRANCH_SAVE_LAST, the state after the last AdvanceFrame --
  * in private packed state blocks outside the ring (state_bytes each, allocated on first use, owned by the world); GGRS_BRANCH_RETAIN_NEWEST only the last frame (F + n_frames).
  * Row versions apply: a column no system writes reaches a branch block once.  They stay valid until the next step of this fan-out.
- * Needs the generated kernel and a world without live-only state (RollbackDespawned markers: a system that can call despawn_rollback(), or a host-issued
- * ggrs_hip_despawn_rollback on an unconfirmed frame; GGRS_COMP_NO_ROLLBACK components): GGRS_E_INVALID otherwise.
+ * Needs the generated kernel (GGRS_E_INVALID otherwise, and for worlds whose systems spawn on the device).
+ * LIVE-ONLY STATE -- RollbackDespawned markers (a system that can call despawn_rollback(), a host-issued ggrs_hip_despawn_rollback on an unconfirmed frame) and
+ * GGRS_COMP_NO_ROLLBACK components -- is outside every snapshot; for the branches of this call it means:
+ *   - the live markers after the call are what the prefix left.  One exception: when ConfirmedFrameCount has moved since the last AdvanceFrame, DespawnConfirmed
+ *     (despawn.rs:89-112) runs once on the live world before the branches start -- what the first AdvanceFrame of the list form does;
+ *   - a branch's markers are PRIVATE: it starts from the live world's, defers its own despawns (frame F+1+i defers while ConfirmedFrameCount < F+1+i) and never writes
+ *     them back.  A retained branch keeps them in one marker record (per 64 slots a u64 of the slots it newly disabled + their i32 frames: ~4.125 B per slot of
+ *     capacity per retained branch, allocated at the first retained step, owned by the world); markers only grow inside a branch, so the record serves every frame;
+ *   - an entity alive at F that some branch despawns for good (despawn(), or despawn_rollback() on a confirmed frame) loses its GGRS_COMP_NO_ROLLBACK components
+ *     once the launch is over -- what the next LoadGameState(F) does to it in the list form (entity.rs:80-90: re-created with its rollback components only).
+ *     DELIBERATE DIFFERENCE: every branch sees the live-only state the prefix left, where the list form lets branch b see what branches < b destroyed.  The two
+ *     differ only in a world where one system READS a live-only column and another despawns at once; a rank's table does not depend on how branches are dealt out.
  *
  * ggrs_hip_fanout_adopt: the true inputs of frames F .. frame-1 have arrived and equal what `branch` (GLOBAL index: rank x n_branches + local index of the LAST step)
  * predicted: that branch's retained state of `frame` becomes the world -- RollbackFrameCount = ConfirmedFrameCount = frame, a snapshot of `frame` in the ring, the live
  * world loaded from it (what LoadGameState leaves behind, schedule_systems.rs:238-250).  Collective: every rank calls it with the same arguments, no step in flight.
- *   on the OWNING rank      the retained block trades places with a ring slot (no bytes move) + one LoadWorld launch
+ *   on the OWNING rank      the retained block trades places with a ring slot (no bytes move) + one LoadWorld launch.  In a world whose kernel keeps markers, the
+ *                           branch's marker record -- its slots whose frame is <= `frame` -- is merged into the live markers first (they stop being alive, and the
+ *                           LoadWorld's reconcile lets them keep their non-rollback components): the result is what GGRS_ADOPT_RECOMPUTE's replay leaves on the other
+ *                           ranks.  ConfirmedFrameCount = frame then confirms them: the next AdvanceFrame frees them on every rank
  *   on the other ranks      GGRS_ADOPT_RECOMPUTE (default): `replay` -- the caller's request list that re-simulates F -> frame with the confirmed inputs and ends with
  *                           SaveGameState(frame), typically [AdvanceFrame x (frame - F), SaveGameState(frame)] -- runs through the ordinary path: no bytes cross xGMI, and
  *                           its Checksum(u128)s (checksums_out, {lo, hi} per SaveGameState of replay; *n_checksums_out = 0 on the owner) can be compared with the
  *                           branch's gathered ones: a free desync check.  GGRS_ADOPT_BROADCAST: ONE ncclBroadcast of the owner's packed block (state_bytes) into a ring
- *                           slot of every other rank, for worlds whose re-simulation costs more than the block's trip over one xGMI link (replay is ignored).
+ *                           slot of every other rank, for worlds whose re-simulation costs more than the block's trip over one xGMI link (replay is ignored);
+ *                           in a world whose kernel keeps markers the branch's marker record follows in a second broadcast (bounded by what the step covered) and every
+ *                           rank runs the same merge.
  * Errors: GGRS_E_NO_SNAPSHOT when the owner did not keep that frame (GGRS_BRANCH_RETAIN_*).  Only the owner can know: with GGRS_ADOPT_BROADCAST the ranks exchange one
  * status word first, so EVERY rank returns the error and none waits in the broadcast; with GGRS_ADOPT_RECOMPUTE there is no collective inside the call -- the owner
  * returns the error, the other ranks have re-simulated (they hold the right state; the owner's caller re-simulates too). */

@@ -137,7 +137,8 @@ impl Drop for HipWorld {
 /// process per GPU, RCCL inside `libggrs_hip.so`.  `step_branches` hands the library ONE compact description of a step -- a prefix request list and
 /// `n_branches x n_frames` predicted inputs -- which it runs as one launch; with `GGRS_BRANCH_RETAIN_*` every branch's frames are kept in private
 /// state blocks, and when the true inputs arrive `adopt` makes the matching branch's state the world: a ring-slot swap on the rank that ran the
-/// branch, a re-simulation with the confirmed inputs (`replay`) or one broadcast on the others.  The C++ twin (`bevy_ggrs::SpeculativeFanout`) is what
+/// branch, a re-simulation with the confirmed inputs (`replay`) or one broadcast on the others.  Worlds whose systems call `despawn_rollback()` or that hold
+/// non-rollback components take part: every branch keeps `RollbackDespawned` markers of its own, and `adopt` merges the adopted branch's into the world.  The C++ twin (`bevy_ggrs::SpeculativeFanout`) is what
 /// tests/cpp/host_test.cpp runs.
 pub struct SpeculativeFanout {
     raw: *mut ffi::ggrs_fanout,
