@@ -34,16 +34,28 @@ inline uint64_t block_tagok(const ggrs_world* w, const Block& b) {
     for (uint32_t c = 0; c < w->n_tcols && c < 64; ++c) if (w->col_ext[c]) m &= ~(1ull << c);
     return m;
 }
+// value tags: every column a launch stored into `d` now carries the tag of what it holds (stored with it, or found equal); without the feature a store leaves stale tags behind
+inline void tags_after_store(const ggrs_world* w, Block& d, uint64_t rows) { if (w->vtags) d.tag_ok |= rows & w->tag_cols; else d.tag_ok &= ~rows; }
+// A recorded step (host_world.hpp StepRec) into / out of step q of an argument block.  The record's input row and the block's are one size: no clamp.
+static_assert(sizeof(StepRec::inputs) == JIT_IN_MAX && sizeof(StepRec::inputs) == sizeof(GgrsJitArgs::inputs[0]), "StepRec::inputs is one step's input row of GgrsJitArgs");
+inline void jit_step_put(GgrsJitArgs& j, uint32_t q, const StepRec& s) {
+    j.dt_bits[q] = s.dt_bits; j.aux_bits[q] = s.aux_bits; j.step_frame[q] = s.frame; j.step_confirmed[q] = s.confirmed; j.n_inputs[q] = s.n_inputs; memcpy(j.inputs[q], s.inputs, sizeof s.inputs);
+}
+inline void jit_step_get(const GgrsJitArgs& j, uint32_t q, bool reads_inputs, StepRec& s) {   // reads_inputs (ggrs_world::jit_reads_inputs) false: nobody packed the block's row -- the record's is zero
+    s.dt_bits = j.dt_bits[q]; s.aux_bits = j.aux_bits[q]; s.frame = j.step_frame[q]; s.confirmed = j.step_confirmed[q]; s.n_inputs = j.n_inputs[q];
+    if (reads_inputs) memcpy(s.inputs, j.inputs[q], sizeof s.inputs); else memset(s.inputs, 0, sizeof s.inputs);
+}
 struct GroupState {
     Block* src; uint64_t cover; uint32_t src_is_live;
+    uint32_t save_at[MAX_TICK_SAVES] = {};            // steps the group had run at each Save
+    const ggrs_request* spawn_req = nullptr;          // a spawn the generator could not fuse fired in the group's last step: it runs as its own launches behind the group
     Block* dsts[MAX_TICK_SAVES];
     uint64_t save_rows[MAX_TICK_SAVES];               // bit c: column c is stored with Save k (row versions)
     uint32_t save_pmask[MAX_TICK_SAVES];              // bit c: component c's presence mask is stored with Save k
     uint64_t live_rows = 0;                           // columns the group's live write handles
     // (the versions Save k's slot holds once the group has run live in w->group_save_ver, [k][column]: no allocation per group)
 };
-// deferred Saves (below)
-inline bool slot_is_stale(const ggrs_world* w, const Block* b);
+inline bool slot_is_stale(const ggrs_world* w, const Block* b);      // deferred Saves (below)
 int materialise_slots(ggrs_world* w);
 inline int slot_stale_on_store(ggrs_world* w, Block* d);
 // LoadGameState opens a group: the ring slot becomes the source (schedule_systems.rs:238-250)
@@ -85,14 +97,15 @@ uint64_t rows_bytes_per_slot(const ggrs_world* w, uint64_t mask, bool ring_side)
     }
     return b;
 }
-// columns of `dst` that differ from the logical live state
-uint64_t rows_to_store(const ggrs_world* w, const Block& dst) {
+// columns of `dst` that differ from the state of versions `ver` (the logical live state: w->cur_ver)
+uint64_t rows_to_store(const ggrs_world* w, const Block& dst, const std::vector<ver_t>& ver) {
     uint64_t m = 0;
-    for (uint32_t c = 0; c < w->n_tcols && c < 64; ++c) if (w->col_rb[c] && ver_differs(w, dst, w->cur_ver, c)) m |= 1ull << c;
+    for (uint32_t c = 0; c < w->n_tcols && c < 64; ++c) if (w->col_rb[c] && ver_differs(w, dst, ver, c)) m |= 1ull << c;
     return m;
 }
 // SaveGameState inside a group: discard_old_snapshots + GgrsSnapshots::push (mod.rs:147-202); the copy itself is an op of the kernel
-int group_save(ggrs_world* w, GroupState& g, uint32_t k, uint8_t** save_dst, int32_t* save_frame) {
+int group_save(ggrs_world* w, GroupState& g, GgrsJitArgs& j) {
+    const uint32_t k = j.n_saves;
     if (tracer().on()) { ggrs_request r{}; r.kind = GGRS_REQ_SAVE; r.frame = w->frame; trace_request(w, r); }
     apply_synctest_confirmed(w);
     if (w->has_confirmed) ring_confirm(w, w->confirmed);
@@ -100,42 +113,21 @@ int group_save(ggrs_world* w, GroupState& g, uint32_t k, uint8_t** save_dst, int
     int rc = ring_push(w, w->frame, &sl); if (rc) return rc;
     Block* d = sl >= 0 ? &w->slots[sl] : nullptr;
     rc = slot_stale_on_store(w, d); if (rc) return rc;
-    g.dsts[k] = d;
-    save_dst[k] = d ? d->ptr : nullptr;
-    save_frame[k] = w->frame;
+    g.dsts[k] = d; j.save_dst[k] = d ? d->ptr : nullptr; j.save_frame[k] = w->frame;
     g.save_rows[k] = 0; g.save_pmask[k] = 0;
     if (d) {
         g.cover = std::max(g.cover, d->dirty_len); d->len = w->len;
-        g.save_rows[k] = rows_to_store(w, *d);
+        g.save_rows[k] = rows_to_store(w, *d, w->cur_ver);
         g.save_pmask[k] = pmask_differs(w, *d, w->cur_ver);
         const size_t nc = w->cur_ver.size();
         if (w->group_save_ver.size() < (size_t)MAX_TICK_SAVES * nc) w->group_save_ver.resize((size_t)MAX_TICK_SAVES * nc);
         std::copy(w->cur_ver.begin(), w->cur_ver.end(), w->group_save_ver.begin() + (size_t)k * nc);
     }
+    j.save_len[k] = w->len; g.save_at[k] = j.n_steps; ++j.n_ops; ++j.n_saves;
     return GGRS_OK;
 }
-// AdvanceFrame inside a group: RollbackFrameCount += 1 (schedule_systems.rs:254-259), DespawnConfirmed, Time<GgrsTime>.
-// DespawnConfirmed only touches the live-only marker mask, which no op inside a group reads or writes: queueing it
-// ahead of the group's launch keeps request order.
-// marks_flags != nullptr: the group kernel keeps the RollbackDespawned markers itself (generated kernel with markers);
-// it receives bit 0 = DespawnConfirmed is due before this step (its Local<ConfirmedFrameCount> changed, despawn.rs:92-99),
-// bit 1 = the step's frame is unconfirmed, i.e. despawn_rollback() defers (despawn.rs:129-137).
-int group_step(ggrs_world* w, const ggrs_request& r, uint32_t* dt_bits_out, uint8_t* marks_flags = nullptr) {
-    trace_request(w, r);
-    apply_synctest_confirmed(w);
-    w->frame += 1;
-    if (marks_flags) {
-        uint8_t f = 0;
-        if (w->confirmed != w->dc_local) { w->dc_local = w->confirmed; f |= 1; }
-        if (w->confirmed < w->frame) { f |= 2; w->marks_possible = true; }
-        *marks_flags = f;
-    } else {
-        int rc = step_despawn_confirmed(w); if (rc) return rc;
-    }
-    ver_step(w);                                                        // every system may have written its write set
-    *dt_bits_out = r.dt_bits ? r.dt_bits : dt_bits_for_frame(w->fps, w->frame);
-    return GGRS_OK;
-}
+// the aux word of a step of the box game: FRICTION.powf(dt), platform libm (box_game.rs:189-195)
+inline uint32_t box_aux_bits(const ggrs_world* w, uint32_t dt_bits) { float dtf; memcpy(&dtf, &dt_bits, 4); const float fp = powf(w->systems[w->jit_box_sys].fparam[2], dtf); uint32_t b; memcpy(&b, &fp, 4); return b; }
 // dead: the group ran checksum-only (dead-snapshot elimination) -- neither its ring slots nor the live block were written, so
 // their dirty extents and row versions still describe what they hold: lowering the extents here would leave mask bits beyond
 // the new extent that no later pass cleans (ghost entities once len grows back into those words)
@@ -147,10 +139,9 @@ void group_close(ggrs_world* w, GroupState& g, uint32_t n_saves, bool dead, bool
     for (uint32_t k = 0; k < n_saves; ++k) if (g.dsts[k]) {
         g.dsts[k]->dirty_len = new_dirty;
         std::copy(w->group_save_ver.begin() + (size_t)k * nc, w->group_save_ver.begin() + (size_t)(k + 1) * nc, g.dsts[k]->ver.begin());
-        // value tags: every column this Save handled now carries the tag of what it holds (stored with it, or found equal); without the feature a store leaves stale tags behind
-        if (w->vtags) g.dsts[k]->tag_ok |= g.save_rows[k] & w->tag_cols; else g.dsts[k]->tag_ok &= ~g.save_rows[k];
+        tags_after_store(w, *g.dsts[k], g.save_rows[k]);
     }
-    if (wrote_live) { w->live.dirty_len = new_dirty; ver_sync_live(w); if (w->vtags) w->live.tag_ok |= g.live_rows & w->tag_cols; else w->live.tag_ok &= ~g.live_rows; }
+    if (wrote_live) { w->live.dirty_len = new_dirty; ver_sync_live(w); tags_after_store(w, w->live, g.live_rows); }
 }
 
 // Dead-snapshot elimination.  A request group whose NEXT request is a LoadGameState of a frame older than everything the
@@ -181,6 +172,34 @@ constexpr uint64_t JIT_BATCH_MAX_SLOTS = 400 * 1024;   // identical checksum-onl
 // grid of the per-tile form: 8 x ceil(tiles / 8) workgroups, mapped to tiles XCD by XCD inside the kernel (kernel_gen.hpp)
 inline uint32_t jit_grid(uint32_t tiles) { return 8u * ((tiles + 7u) / 8u); }
 
+// The store / load / role policy of one launch, from the group's description alone: what run_request_groups_gen gives a group and jit_steady_sig the steady tick.
+// save0_bytes_slot: bytes per slot of the first Save's rows (ring side); aliased: a destination is the source block or another destination (group_aliases).
+struct JitPolicy { uint32_t nt = 0, cached_saves = 0, nt_loads = 0, dp_s = 0; };
+inline JitPolicy jit_group_policy(uint64_t cover, uint32_t n_saves, bool src_is_live, uint64_t save0_bytes_slot, bool aliased, bool marks, bool dev_spawn, bool nt_copy) {
+    JitPolicy p; p.nt = (nt_copy || cover > JIT_NT_MIN_SLOTS) ? 1u : 0u;
+    // A rollback group's FIRST Save is the oldest frame it produces -- what the next rollback loads (SyncTest: always; P2P with a steady
+    // rollback depth: likewise).  Storing it through the L2 instead of around it lets the next launch's loads hit there: 72.5 -> 64.6 us
+    // per depth-8 tick at 1 M in the ring-walking harness (profiles/r03n), every other row still streams past the caches.
+    // Past ~2.5 M particles the rows no longer survive in the caches until the next launch and only displace the stream (4 M: +3 %; r04c).
+    p.cached_saves = (p.nt && !src_is_live && n_saves >= 2 && save0_bytes_slot * cover <= JIT_CACHED_SAVE_MAX_BYTES) ? 1u : 0u;
+    // the source block of an HBM-sized rollback group is in the caches only if the previous group kept a Save there (the steady session: the
+    // same decision as this group's): otherwise its lines come from HBM once and are dead after the load (4 M: -3.5 %, allhot 4 M -8 %; it costs
+    // 3 % where the loads DO hit: profiles/r04o)
+    p.nt_loads = (p.nt && !p.cached_saves && !src_is_live) ? 1u : 0u;
+    // Depth-parallel roles: the group's outputs (Saves + live world) are split over grid.y roles of dp_s outputs.  Every role
+    // reads the source block while the others write theirs, so the source must be none of the destinations; below ~2 Saves
+    // there is no chain to split.  Crossovers: profiles/r02dp/ab2.txt, profiles/r02jit/jit_dp.txt.
+    const uint64_t m = JIT_DP_MAX_SLOTS;
+    if (n_saves >= 2 && !marks && !dev_spawn && !aliased) p.dp_s = cover <= m ? 1u : (cover <= 2 * m ? 2u : (cover <= 6 * m ? 3u : 0u));
+    return p;
+}
+// launch geometry of a group that covers `cover` slots: the 64-slot units to walk, one 256-slot workgroup per tile (the return value), and the rows where k_gen_finalize
+// looks for them (a fold route or a branch step points them elsewhere afterwards)
+inline uint32_t jit_geometry(const ggrs_world* w, GgrsJitArgs& j, uint64_t cover) {
+    j.parts = reinterpret_cast<ggrs_u64*>(w->d_gen_parts); j.part_stride = w->gen_part_stride; j.part_tstride = 1; j.n_units = std::max<uint32_t>(1, (uint32_t)((cover + 63) / 64));
+    return std::max<uint32_t>(1, (uint32_t)((cover + 255) / 256));
+}
+
 // FOLD-FORWARD.  Every Save of a group leaves one partial per workgroup and checksummed part (the XOR of a component's entity hashes,
 // the live count).  Up to GGRS_FOLD_FORWARD_MIN_WGS workgroups the rows go to pinned memory and the host XORs them at collect time; beyond, that
 // fold -- 94 k values = 750 KB per tick at 1 M entities, ~30 us of a host core -- sat between collect(k) and enqueue(k + 2) of a session that
@@ -198,32 +217,6 @@ inline void ff_attach(ggrs_world* w, GgrsJitArgs& j) {
     j.ff_nvals = p.nvals; j.ff_blocks = (p.nvals + 7u) & ~7u; j.ff_g = p.g; j.ff_stride = p.stride; j.ff_istride = p.istride; j.ff_split = p.split;
     w->ff_done_id = p.id; p.valid = false;
     w->ff_mark_id = p.id;                                             // launch_jit records the group's event right behind this launch
-}
-
-// The shape of a steady SyncTest tick of this world at full length -- [Load(F - D), Advance, (Save, Advance) x D] with D = max_depth - 1, every
-// slot live, the rows the systems write -- under the same store / load / role policies run_request_groups_gen applies: what
-// ggrs_hip_generated_kernel_source(GGRS_KERNEL_FORM_STEADY) specialises for and what `make aot` ships, so that a session's 16th steady tick finds its kernel
-// among the shipped objects when there is no run-time compiler.
-inline bool lazy_live_allowed(const ggrs_world* w);
-JitSig jit_steady_sig(const ggrs_world* w) {
-    // the group caps come from the world's argument-block layout -- computed here, not read from w->cap_*: a GGRS_WORLD_LAYOUT_ONLY world (`make aot` on a
-    // build machine) is never sealed, and the defaults (16 / 24) would describe a tick its device struct has no room for (ADVICE r5)
-    const JitLayout L = jit_layout(w);
-    const uint32_t d = std::min<uint32_t>(std::max<uint32_t>(w->max_depth, 2) - 1, std::min<uint32_t>(L.cap_saves, L.cap_steps - 1));
-    const uint64_t cover = w->capacity;
-    JitSig g;
-    g.n_saves = d; g.n_steps = d + 1; g.n_ops = 2 * d + 1;
-    for (uint32_t k = 0; k <= d; ++k) g.op_bits |= 1ull << (2 * k);                       // Advance, Save, Advance, ..., Save, Advance
-    g.save_rows = g.live_rows = jit_hot_cols(w); g.load_rows = g.save_rows | jit_static_reads(w);
-    g.nt = cover > JIT_NT_MIN_SLOTS ? 1u : 0u;
-    g.cached_saves = (g.nt && d >= 2 && rows_bytes_per_slot(w, g.save_rows, true) * cover <= JIT_CACHED_SAVE_MAX_BYTES) ? 1u : 0u;
-    g.nt_loads = (g.nt && !g.cached_saves) ? 1u : 0u;
-    const JitNeeds need = jit_needs(w);
-    if (d >= 2 && !need.marks) g.dp_s = cover <= JIT_DP_MAX_SLOTS ? 1u : (cover <= 2 * JIT_DP_MAX_SLOTS ? 2u : (cover <= 6 * JIT_DP_MAX_SLOTS ? 3u : 0u));
-    // an HBM-sized steady session leaves the live block unwritten (lazy live block, below): the next tick's LoadGameState never reads it
-    if (g.nt && !need.marks && lazy_live_allowed(w)) { g.skip_live = 1; g.live_rows = 0; }
-    g.vtags = vtags_policy(w) ? 1u : 0u;
-    return g;
 }
 
 // Launch of a generated kernel: the host-side argument block is packed into the world's device layout (kernel_gen.hpp jit_pack).  With
@@ -335,6 +328,69 @@ inline void arm_spin(ggrs_world* w, GenFinArgs& f, uint32_t n_wgs, bool blocking
     f.done = w->d_done; f.seq = ++w->spin_seq; w->spin_n = n_wgs;
 }
 
+inline int launch_gen_finalize(ggrs_world* w, const GenFinArgs& f, uint32_t n_wgs) {
+    { ProfScope ps(w, GGRS_KERNEL_CHECKSUM); hipLaunchKernelGGL(k_gen_finalize, dim3(n_wgs), dim3(FIN_TPB), 0, w->stream, f); }
+    HIPCHK(w, hipGetLastError()); return GGRS_OK;
+}
+// who folds this launch's partial rows: the next launch on the stream (fold-forward: enqueued lists of more than
+// GGRS_FOLD_FORWARD_MIN_WGS workgroups), the launch itself (self-fold: blocking calls of that size), the host from pinned rows (smaller groups), or k_gen_finalize (blocking calls of more than 1024
+// workgroups, results that stay on the device, no room in the pinned ring)
+enum class FoldRoute { None, Forward, Self, Host, Finalize };
+struct FoldPlan { FoldRoute route = FoldRoute::None; uint64_t rows_off = 0, id = 0, seq = 0; uint32_t split = 0, nvals = 0, rows_n = 0, buf = 0; };   // id, seq: self-fold's, handed out before the launch; split: chunks per row; buf: the fold-forward buffer
+// The route AND its room in the pinned ring, in this order: fold-forward's, else self-fold's, else the host fold's; an allocation that fails falls through to the next route
+FoldPlan fold_route_choose(ggrs_world* w, const GgrsJitArgs& j, uint32_t g, uint32_t n_cks, bool launch, bool wait, bool spawn_follows) {
+    FoldPlan p; p.split = (g + FF_CHUNK - 1u) / FF_CHUNK;                      // chunks of <= 1024 entries per row: one fold-forward workgroup each
+    p.rows_n = j.n_saves * (n_cks + 1); p.nvals = p.rows_n * p.split;
+    const bool big = launch && j.n_saves && !w->device_results_only && !w->dev_spawn && g > (uint32_t)w->knobs.fold_forward_min_wgs && w->d_ff_rows[0];
+    // a BLOCKING call of that size: the launch folds its own rows (self-fold: its fold workgroups read the tile workgroups' tagged cells as they arrive) -- no k_gen_finalize
+    // between the kernel and the caller.  Not beside a pending fold-forward (the role folds one set of rows), not with depth-parallel roles (plain grids only),
+    // and only while the fold workgroups -- resident and waiting from the launch's start -- are few beside the 2048 the device holds (8 M entities and more
+    // keep k_gen_finalize: thousands of waiting workgroups would leave the tiles no room, at 32 M none at all)
+    if (big && !wait && rows_ring_alloc(w, 2ull * p.nvals, &p.rows_off)) p.route = FoldRoute::Forward;
+    else if (big && wait && p.nvals <= SELF_FOLD_MAX_WGS && !j.dp_s && !w->ff_pending.valid && !spawn_follows && rows_ring_alloc(w, 2ull * p.nvals, &p.rows_off)) p.route = FoldRoute::Self;
+    else if (launch && host_fold_rows(w, g, j.n_saves, n_cks, 1, &p.rows_off, wait)) p.route = FoldRoute::Host;
+    else if (j.n_saves) p.route = FoldRoute::Finalize;
+    return p;
+}
+// before the launch: where its rows go
+void fold_route_setup(ggrs_world* w, GgrsJitArgs& j, FoldPlan& p, uint32_t g) {
+    switch (p.route) {
+    case FoldRoute::Forward:
+        // fold-forward rows are TILE-major: a workgroup's values of all its Saves and parts sit side by side (one coalesced store of 192 B for the
+        // stress_test; row-major they were 24 eight-byte stores into 24 different lines, and the 1 M launch took 51 us instead of 48.9: profiles/r05c)
+        p.buf = w->ff_cur; w->ff_cur ^= 1u; j.parts = reinterpret_cast<ggrs_u64*>(w->d_ff_rows[p.buf]); j.part_stride = 1; j.part_tstride = p.rows_n; break;
+    case FoldRoute::Self:
+        // (self-fold: 16-byte cells {value, tag} instead of 8-byte entries -- the two fold-forward buffers, which lie side by side and hold nothing pending, as one)
+        p.buf = 0; j.parts = reinterpret_cast<ggrs_u64*>(w->d_ff_rows[0]); j.part_stride = 1; j.part_tstride = p.rows_n;
+        p.id = w->ff_next_id++; p.seq = (0xA5ull << 56) | ++w->ff_seq; memset(w->h_rows + p.rows_off, 0, (size_t)p.nvals * 16);
+        j.ff_rows = reinterpret_cast<const ggrs_u64*>(w->d_ff_rows[p.buf]); j.ff_out = reinterpret_cast<ggrs_u64*>(w->d_rows + p.rows_off); j.ff_seq = p.seq;
+        j.ff_nvals = p.nvals; j.ff_blocks = (p.nvals + 7u) & ~7u; j.ff_g = g; j.ff_stride = 1; j.ff_istride = p.rows_n; j.ff_split = p.split; j.ff_self = 1;
+        w->ff_done_id = p.id; w->ff_mark_id = p.id; break;       // the fold is on the stream with this very launch; launch_jit records its event behind it
+    case FoldRoute::Host: j.parts = reinterpret_cast<ggrs_u64*>(w->d_rows + p.rows_off); j.part_stride = g; break;
+    case FoldRoute::Finalize: case FoldRoute::None: break;      // (jit_geometry: k_gen_finalize's buffer)
+    }
+}
+// after the launch: who is owed the fold.  res: the result slot of the (first member's) first Save; members: of a batch (Host and Finalize only)
+int fold_route_record(ggrs_world* w, const GgrsJitArgs& j, const FoldPlan& p, uint32_t g, uint32_t n_cks, uint32_t res, bool wait, uint32_t members = 1) {
+    switch (p.route) {
+    case FoldRoute::Forward: case FoldRoute::Self: {
+        ggrs_world::HostFold f = make_host_fold(j, res, p.split, n_cks, 1u, p.rows_off);   // (the host XORs / adds the row's chunks)
+        if (p.route == FoldRoute::Self) { f.ff_id = p.id; f.ff_seq = p.seq; w->folds.push_back(f); break; }
+        f.ff_id = w->ff_next_id++; f.ff_seq = (0xA5ull << 56) | ++w->ff_seq;      // (a tag no live count and -- but for 2^-64 -- no hash equals)
+        memset(w->h_rows + p.rows_off, 0, (size_t)p.nvals * 16);                    // the {value, tag} cells: whatever an earlier fold left there is gone
+        w->folds.push_back(f); ggrs_world::FfPending& pn = w->ff_pending;
+        pn.valid = true; pn.id = f.ff_id; pn.seq = f.ff_seq; pn.buf = p.buf; pn.nvals = p.nvals; pn.g = g; pn.stride = 1; pn.istride = p.rows_n; pn.split = p.split; pn.out_off = p.rows_off;
+        break; }
+    case FoldRoute::Host: w->folds.push_back(make_host_fold(j, res, g, n_cks, members, p.rows_off)); break;
+    case FoldRoute::Finalize: {
+        GenFinArgs f = make_gen_fin(w, j, g, n_cks, res);   // one row per workgroup
+        arm_spin(w, f, j.n_saves * members, wait);
+        return launch_gen_finalize(w, f, j.n_saves * members); }
+    case FoldRoute::None: break;
+    }
+    return GGRS_OK;
+}
+
 // Identical checksum-only groups off the same source block (speculative branches: same ops, same frames, same length) are
 // launched TOGETHER: one grid of tiles x K members (blockIdx.z) and one finalize of saves x K, instead of K launch pairs.
 struct JitBatch {
@@ -361,25 +417,13 @@ struct JitBatch {
     bool blocking = false;                                           // the synchronous API: see host_fold_rows
     int flush(ggrs_world* w) {
         if (!active) return GGRS_OK;
-        active = false;
-        w->batch_ev_attached = false;                                // this launch comes after whatever carried the batch event
-        bool host_fold = false; uint64_t rows_off = 0;
-        {
-            if (k > 1) j.dp_s = 0;
-            host_fold = host_fold_rows(w, g, j.n_saves, n_cks, k, &rows_off, blocking);
-            if (host_fold) { j.parts = reinterpret_cast<ggrs_u64*>(w->d_rows + rows_off); j.part_stride = g; }
-            { const int lrc = launch_jit(w, w->jit_fn, jit_grid(g), j.dp_s ? (j.n_saves + j.dp_s) / j.dp_s : 1u, k, jit_lane_fold_bytes(w, w->cks_args.n_cks, j.n_saves), j,
-                                         rows_bytes_per_slot(w, j.load_rows, !j.src_is_live) * j.len * k); if (lrc) return lrc; }
-        }
-        if (host_fold) { w->folds.push_back(make_host_fold(j, res_first, g, n_cks, k, rows_off)); return GGRS_OK; }
-        GenFinArgs f = make_gen_fin(w, j, g, n_cks, res_first);   // one row per workgroup
-        arm_spin(w, f, j.n_saves * k, blocking);
-        {
-            ProfScope ps(w, GGRS_KERNEL_CHECKSUM);
-            hipLaunchKernelGGL(k_gen_finalize, dim3(j.n_saves * k), dim3(FIN_TPB), 0, w->stream, f);
-        }
-        HIPCHK(w, hipGetLastError());
-        return GGRS_OK;
+        active = false; w->batch_ev_attached = false;                                // this launch comes after whatever carried the batch event
+        if (k > 1) j.dp_s = 0;
+        FoldPlan p; p.route = host_fold_rows(w, g, j.n_saves, n_cks, k, &p.rows_off, blocking) ? FoldRoute::Host : FoldRoute::Finalize;
+        fold_route_setup(w, j, p, g);
+        const int lrc = launch_jit(w, w->jit_fn, jit_grid(g), j.dp_s ? (j.n_saves + j.dp_s) / j.dp_s : 1u, k, jit_lane_fold_bytes(w, w->cks_args.n_cks, j.n_saves), j,
+                                   rows_bytes_per_slot(w, j.load_rows, !j.src_is_live) * j.len * k);
+        return lrc ? lrc : fold_route_record(w, j, p, g, n_cks, res_first, blocking, k);
     }
 };
 
@@ -398,6 +442,30 @@ inline bool lazy_live_allowed(const ggrs_world* w) {                 // (what a 
     return true;
 }
 inline bool lazy_live_possible(const ggrs_world* w) { return w->gen_ok && !w->jit_marks && lazy_live_allowed(w); }
+// The shape of a steady SyncTest tick of this world at full length -- [Load(F - D), Advance, (Save, Advance) x D] with D = max_depth - 1, every
+// slot live, the rows the systems write -- under the store / load / role policy run_request_groups_gen applies (jit_group_policy): what
+// ggrs_hip_generated_kernel_source(GGRS_KERNEL_FORM_STEADY) specialises for and what `make aot` ships, so that a session's 16th steady tick finds its kernel
+// among the shipped objects when there is no run-time compiler.
+JitSig jit_steady_sig(const ggrs_world* w) {
+    // the group caps come from the world's argument-block layout -- computed here, not read from w->cap_*: a GGRS_WORLD_LAYOUT_ONLY world (`make aot` on a
+    // build machine) is never sealed, and the defaults (16 / 24) would describe a tick its device struct has no room for (ADVICE r5)
+    const JitLayout L = jit_layout(w);
+    const uint32_t d = std::min<uint32_t>(std::max<uint32_t>(w->max_depth, 2) - 1, std::min<uint32_t>(L.cap_saves, L.cap_steps - 1));
+    const uint64_t cover = w->capacity;
+    JitSig g;
+    g.n_saves = d; g.n_steps = d + 1; g.n_ops = 2 * d + 1;
+    for (uint32_t k = 0; k <= d; ++k) g.op_bits |= 1ull << (2 * k);                       // Advance, Save, Advance, ..., Save, Advance
+    g.save_rows = g.live_rows = jit_hot_cols(w); g.load_rows = g.save_rows | jit_static_reads(w);
+    const JitNeeds need = jit_needs(w);
+    // Against the running group's call (run_request_groups_gen), kept as found: cover is the capacity (a full world), not the dirty extents; the source is a ring slot (the tick opens with a Load)
+    // that no destination aliases; marks come from the systems' text (a layout-only world is never sealed: no w->jit_marks); device spawn and the GGRS_WORLD_NT_COPY knob are not looked at.
+    const JitPolicy pol = jit_group_policy(cover, d, /*src_is_live*/ false, rows_bytes_per_slot(w, g.save_rows, true), /*aliased*/ false, need.marks, /*dev_spawn*/ false, /*nt_copy*/ false);
+    g.nt = pol.nt; g.cached_saves = pol.cached_saves; g.nt_loads = pol.nt_loads; g.dp_s = pol.dp_s;
+    // an HBM-sized steady session leaves the live block unwritten (lazy live block, below): the next tick's LoadGameState never reads it
+    if (g.nt && !need.marks && lazy_live_allowed(w)) { g.skip_live = 1; g.live_rows = 0; }
+    g.vtags = vtags_policy(w) ? 1u : 0u;
+    return g;
+}
 
 // ---- deferred Saves ---------------------------------------------------------------------------------------------------------
 // The same rule for the ring.  Of the Saves of a steady tick  [Load(F - 8), Advance, (Save, Advance) x 8]  only the FIRST (F - 7) is ever read: the next tick opens
@@ -435,13 +503,10 @@ int materialise_slots(ggrs_world* w) {
     j.src = c.base->ptr; j.live = w->live.ptr; j.len = c.len[0]; j.src_is_live = 0; j.skip_live = 1;
     j.load_rows = jit_static_reads(w);
     const size_t nc = w->cur_ver.size();
-    const size_t in_row = std::min(sizeof c.inputs[0], sizeof j.inputs[0]);
     uint64_t cover = std::max(c.base->dirty_len, c.len[0]), bytes = 0;
     for (uint32_t k = 1; k <= last; ++k) {
         for (uint32_t q = c.at[k - 1]; q < c.at[k]; ++q) {                // the steps between Save k - 1 and Save k, as the group ran them
-            const uint32_t s = j.n_steps++;
-            j.dt_bits[s] = c.dt_bits[q]; j.aux_bits[s] = c.aux_bits[q]; j.step_frame[s] = c.step_frame[q]; j.step_confirmed[s] = c.step_confirmed[q]; j.n_inputs[s] = c.n_inputs[q];
-            memcpy(j.inputs[s], c.inputs[q], in_row);
+            jit_step_put(j, j.n_steps++, c.steps[q]);
             j.op_bits |= 1ull << j.n_ops; ++j.n_ops;
         }
         const uint32_t si = j.n_saves++; ++j.n_ops;
@@ -449,8 +514,7 @@ int materialise_slots(ggrs_world* w) {
         if (!c.stale[k]) continue;                                         // (superseded, or no longer in the ring: checksum only)
         const Block& d = *c.dst[k];
         const std::vector<ver_t> want(c.ver.begin() + (size_t)k * nc, c.ver.begin() + (size_t)(k + 1) * nc);
-        uint64_t m = 0;
-        for (uint32_t col = 0; col < w->n_tcols && col < 64; ++col) if (w->col_rb[col] && ver_differs(w, d, want, col)) m |= 1ull << col;
+        const uint64_t m = rows_to_store(w, d, want);
         j.save_dst[si] = d.ptr; j.save_rows[si] = m; j.save_pmask[si] = pmask_differs(w, d, want);
         j.load_rows |= m;
         bytes += rows_bytes_per_slot(w, m, true) * c.len[k];
@@ -463,9 +527,7 @@ int materialise_slots(ggrs_world* w) {
         j.src_tagok = block_tagok(w, *c.base);
         for (uint32_t k = 1, si = 0; k <= last; ++k, ++si) if (j.save_dst[si]) j.save_tagok[si] = block_tagok(w, *c.dst[k]);
     }
-    j.parts = reinterpret_cast<ggrs_u64*>(w->d_gen_parts); j.part_stride = w->gen_part_stride; j.part_tstride = 1;   // (the checksums were returned by the group: these rows are dropped)
-    j.n_units = std::max<uint32_t>(1, (uint32_t)((cover + 63) / 64));
-    const uint32_t g = std::max<uint32_t>(1, (uint32_t)((cover + 255) / 256));
+    const uint32_t g = jit_geometry(w, j, cover);                      // (the checksums were returned by the group: these rows are dropped)
     j.nt = cover > JIT_NT_MIN_SLOTS ? 1u : 0u; j.nt_loads = j.nt;
     const int rc = launch_jit(w, w->jit_fn, jit_grid(g), 1, 1, jit_lane_fold_bytes(w, w->cks_args.n_cks, j.n_saves), j, bytes);
     if (rc) return rc;
@@ -473,7 +535,7 @@ int materialise_slots(ggrs_world* w) {
         Block& d = *c.dst[k];
         std::copy(c.ver.begin() + (size_t)k * nc, c.ver.begin() + (size_t)(k + 1) * nc, d.ver.begin());
         d.dirty_len = c.dirty[k];
-        if (w->vtags) d.tag_ok |= j.save_rows[si] & w->tag_cols; else d.tag_ok &= ~j.save_rows[si];
+        tags_after_store(w, d, j.save_rows[si]);
         c.stale[k] = false; ++w->slots_materialised;
     }
     c.valid = false;
@@ -496,328 +558,272 @@ int materialise_live(ggrs_world* w) {
     GgrsJitArgs j; memset(&j, 0, offsetof(GgrsJitArgs, inputs));
     j.src = st.src->ptr; j.live = w->live.ptr; j.len = st.len; j.src_is_live = 0;
     j.n_ops = 1; j.op_bits = 1; j.n_steps = 1;
-    j.dt_bits[0] = st.dt_bits; j.aux_bits[0] = st.aux_bits; j.step_frame[0] = st.step_frame; j.step_confirmed[0] = st.step_confirmed; j.n_inputs[0] = st.n_inputs;
-    memcpy(j.inputs[0], st.inputs, sizeof st.inputs);
-    j.live_rows = rows_to_store(w, w->live); j.live_pmask = pmask_differs(w, w->live, w->cur_ver);
+    jit_step_put(j, 0, st.step);
+    j.live_rows = rows_to_store(w, w->live, w->cur_ver); j.live_pmask = pmask_differs(w, w->live, w->cur_ver);
     j.load_rows = jit_static_reads(w) | j.live_rows;
     j.vtags = w->vtags ? 1u : 0u;
     if (j.vtags) { const int trc = vtags_reserve(w, 1, 1, &j.tag_base); if (trc) return trc; j.src_tagok = block_tagok(w, *st.src); j.live_tagok = block_tagok(w, w->live); }
     const uint64_t cover = std::max(std::max(st.src->dirty_len, w->live.dirty_len), w->len);
-    j.parts = reinterpret_cast<ggrs_u64*>(w->d_gen_parts); j.part_stride = w->gen_part_stride; j.part_tstride = 1;
-    j.n_units = std::max<uint32_t>(1, (uint32_t)((cover + 63) / 64));
-    const uint32_t g = std::max<uint32_t>(1, (uint32_t)((cover + 255) / 256));
+    const uint32_t g = jit_geometry(w, j, cover);
     j.nt = 0;                                                        // (the live block is read again by whoever asked for it)
     j.nt_loads = cover > JIT_NT_MIN_SLOTS ? 1u : 0u;                  // the slot was stored around the caches one launch ago
     const int rc = launch_jit(w, w->jit_fn, jit_grid(g), 1, 1, 0, j, (rows_bytes_per_slot(w, j.load_rows, true) + rows_bytes_per_slot(w, j.live_rows, false)) * w->len);
     if (rc) return rc;
     w->live.dirty_len = std::max(st.src->dirty_len, w->len);
     ver_sync_live(w);
-    if (w->vtags) w->live.tag_ok |= j.live_rows & w->tag_cols; else w->live.tag_ok &= ~j.live_rows;
+    tags_after_store(w, w->live, j.live_rows);
     st.valid = false; ++w->lazy_materialised;
     return GGRS_OK;
 }
 
+// ---- the phases of run_request_groups_gen, in the order it performs them ----------------------------------------------------
+// payloads this list has staged already (by the caller's host pointer): every branch of a fan-out step that spawns in frame f hands in the same
+// arrays.  Offsets into the ring die with the ring's generation (a reset: the ring was full and the stream was waited for; a result page was read back)
+struct StagedPayloads { struct Entry { const void* host; const void* host2; uint64_t bytes; const unsigned char* dev; }; std::vector<Entry> list; uint64_t gen; };
+// The payload of the fused spawn that fires in request r, staged now (pinned, device-mapped ring: no copy command per spawning step).  *dev: where the launch reads it
+// (nullptr: the spawner reads nothing).  *full: the ring has no room and the group already has ops -- it ends BEFORE this frame: it is launched, then the frame opens the next group
+int stage_spawn_payload(ggrs_world* w, const ggrs_request& r, StagedPayloads& staged, JitBatch& batch, bool group_has_ops, const unsigned char** dev, bool* full) {
+    const ggrs_system_desc& sd = w->systems[w->jit_spawn_sys];
+    const bool custom = sd.kind == GGRS_SYS_SPAWN_CUSTOM;
+    if (r.spawn_count > 0xFFFFFFFFull || w->len + r.spawn_count > w->capacity)
+        return w->fail(GGRS_E_CAPACITY, "spawn of %llu exceeds capacity %llu", (unsigned long long)r.spawn_count, (unsigned long long)w->capacity);
+    // what the spawner reads: particles -- count f32 of vx, then count f32 of vy; user-written -- the request's payload blob
+    const ggrs_world::SpawnSys* sp = custom ? &w->spawn_customs[sd.comp[0]] : nullptr;
+    const uint64_t pbytes = custom ? (sp->payload_stride ? (uint64_t)sp->payload_stride * r.spawn_count : r.spawn_payload_bytes) : 8 * r.spawn_count;
+    const void* key = custom ? r.spawn_payload : (const void*)r.spawn_vx; const void* key2 = custom ? nullptr : (const void*)r.spawn_vy;
+    if (staged.gen != w->stage_gen) { staged.list.clear(); staged.gen = w->stage_gen; }
+    if (!pbytes) return GGRS_OK;
+    for (auto& st : staged.list) if (st.host == key && st.host2 == key2 && st.bytes == pbytes) { *dev = st.dev; return GGRS_OK; }
+    uint64_t soff = 0;
+    if (!stage_ring_alloc(w, pbytes, &soff)) {
+        // the ring is full of payloads that launches already queued -- or the steps of THIS group -- still have to read
+        if (pbytes > w->stage_bytes) return w->fail(GGRS_E_CAPACITY, "spawn payload of %llu bytes exceeds the staging buffer (%llu bytes: GGRS_STAGE_BYTES)", (unsigned long long)pbytes, (unsigned long long)w->stage_bytes);
+        if (group_has_ops) { *full = true; return GGRS_OK; }
+        const int rc = batch.flush(w); if (rc) return rc;
+        HIPCHK(w, hipStreamSynchronize(w->stream));      // let everything queued run, then start the ring over
+        stage_ring_reset(w); staged.list.clear(); staged.gen = w->stage_gen;
+        if (!stage_ring_alloc(w, pbytes, &soff)) return w->fail(GGRS_E_CAPACITY, "spawn payload of %llu bytes does not fit the staging buffer", (unsigned long long)pbytes);
+    }
+    // (the caller's arrays are free again when the call returns; the bytes sit in the ring until this list's batch is collected)
+    if (custom) memcpy(w->h_stage + soff, r.spawn_payload, pbytes);
+    else { memcpy(w->h_stage + soff, r.spawn_vx, r.spawn_count * 4); memcpy(w->h_stage + soff + r.spawn_count * 4, r.spawn_vy, r.spawn_count * 4); }
+    *dev = w->d_hstage + soff;
+    if (staged.list.size() < 256) staged.list.push_back({key, key2, pbytes, *dev});
+    return GGRS_OK;
+}
+// One SaveGameState or AdvanceFrame into the group being assembled.  *taken stays false when the group ends BEFORE r: a cap of the argument block, the result page of a
+// blocking call (saves_room), the staging ring.  A spawn the generator could not fuse ends the group AFTER the step: gs.spawn_req
+int group_take(ggrs_world* w, const ggrs_request& r, GgrsJitArgs& j, GroupState& gs, StagedPayloads& staged, JitBatch& batch, uint32_t saves_room, bool* taken) {
+    int rc = GGRS_OK;
+    if (r.kind == GGRS_REQ_SAVE) {
+        if (j.n_saves == w->cap_saves || j.n_saves == saves_room) return GGRS_OK;
+        *taken = true; return group_save(w, gs, j);
+    }
+    if (r.kind != GGRS_REQ_ADVANCE) return w->fail(GGRS_E_INVALID, "unknown request kind %u", r.kind);
+    if (j.n_steps == w->cap_steps) return GGRS_OK;
+    // A spawn system fires in this frame.  Fused (kernel_gen.hpp): the step's launch appends the rows itself -- the payload is staged
+    // now (pinned, device-mapped ring: no copy command per spawning step), the host does in request order what run_spawn_systems does
+    // around its kernel (capacity, versions of the bundle, len) and the group goes on.  Worlds whose spawn system the generator cannot
+    // fuse end the group after the step and run the spawn as its own launches, as Bevy's Commands flush ends the schedule.
+    const bool spawns = advance_spawns(w, r);
+    const bool fused_spawn = spawns && w->jit_spawn_sys >= 0;
+    const unsigned char* payload_dev = nullptr;
+    if (fused_spawn) { bool full = false; rc = stage_spawn_payload(w, r, staged, batch, j.n_ops != 0, &payload_dev, &full); if (rc || full) return rc; }
+    auto touch_bundle = [w](const ggrs_world::SpawnSys& sp) { for (uint32_t c = 0; c < w->comps.size(); ++c) if ((sp.bundle_mask >> c) & 1ull) ver_touch_comp(w, c); };
+    const uint32_t step = j.n_steps++;
+    // AdvanceFrame inside a group: RollbackFrameCount += 1 (schedule_systems.rs:254-259), DespawnConfirmed, Time<GgrsTime>.
+    // DespawnConfirmed only touches the live-only marker mask, which no op inside a group reads or writes: queueing it
+    // ahead of the group's launch keeps request order.
+    // w->jit_marks: the group kernel keeps the RollbackDespawned markers itself (generated kernel with markers);
+    // it receives (step_flags) bit 0 = DespawnConfirmed is due before this step (its Local<ConfirmedFrameCount> changed, despawn.rs:92-99),
+    // bit 1 = the step's frame is unconfirmed, i.e. despawn_rollback() defers (despawn.rs:129-137).
+    trace_request(w, r);
+    apply_synctest_confirmed(w);
+    w->frame += 1;
+    if (w->jit_marks) {
+        uint8_t f = 0;
+        if (w->confirmed != w->dc_local) { w->dc_local = w->confirmed; f |= 1; }
+        if (w->confirmed < w->frame) { f |= 2; w->marks_possible = true; }
+        j.step_flags[step] = f;
+    } else { rc = step_despawn_confirmed(w); if (rc) return rc; }
+    ver_step(w);                                                        // every system may have written its write set
+    const uint32_t dtb = r.dt_bits ? r.dt_bits : dt_bits_for_frame(w->fps, w->frame);
+    if (w->dev_spawn) touch_bundle(w->spawn_customs[w->systems[w->jit_spawn_sys].comp[0]]);   // any frame may append rows of the bundle: its columns and presence masks are new after every step
+    j.dt_bits[step] = dtb; j.step_frame[step] = w->frame; j.step_confirmed[step] = w->confirmed;
+    if (w->jit_box_sys >= 0) j.aux_bits[step] = box_aux_bits(w, dtb);
+    j.n_inputs[step] = (uint8_t)std::min<uint32_t>(r.n_inputs, w->max_players);
+    if (w->jit_reads_inputs) pack_inputs(w, r, j.inputs[step]);      // PlayerInputs<T>: (T::Input, InputStatus) per player (src/lib.rs:98)
+    j.op_bits |= 1ULL << j.n_ops; ++j.n_ops;
+    if (fused_spawn) {
+        const ggrs_system_desc& sd = w->systems[w->jit_spawn_sys];
+        j.spawn_payload[step] = payload_dev; j.spawn_first[step] = w->len; j.spawn_count[step] = (uint32_t)r.spawn_count;
+        // new rows in every column (and the presence mask) of the bundle
+        if (sd.kind == GGRS_SYS_SPAWN_CUSTOM) touch_bundle(w->spawn_customs[sd.comp[0]]);
+        else { ver_touch_comp(w, sd.comp[0]); ver_touch_comp(w, sd.comp[1]); ver_touch_comp(w, sd.comp[2]); }
+        w->len += r.spawn_count;
+    } else if (spawns) gs.spawn_req = &r;
+    *taken = true; return GGRS_OK;
+}
+// lazy live block: the LAST group of a list that ends [.., Save(F), Advance] in a session whose lists keep opening with a Load
+inline void group_lazy_live(ggrs_world* w, GgrsJitArgs& j, const GroupState& gs, bool dead, bool list_ends, uint64_t cover) {
+    const bool applies = !dead && !gs.spawn_req && list_ends &&
+                         ((w->load_open_streak >= LAZY_LIVE_STREAK && cover > JIT_NT_MIN_SLOTS) || w->lazy_live_on == 2 || w->lazy_live_on == 3) &&
+                         j.n_ops >= 2 && j.n_saves && j.n_steps &&
+                         ((j.op_bits >> (j.n_ops - 1)) & 1ull) && !((j.op_bits >> (j.n_ops - 2)) & 1ull) &&
+                         gs.dsts[j.n_saves - 1] && !j.spawn_count[j.n_steps - 1] && gs.dsts[j.n_saves - 1] != gs.src &&
+                         lazy_live_possible(w);
+    if (!applies) return;
+    ggrs_world::LiveStale& st = w->live_stale;
+    st.valid = true; st.src = gs.dsts[j.n_saves - 1]; st.len = j.save_len[j.n_saves - 1];
+    jit_step_get(j, j.n_steps - 1, w->jit_reads_inputs, st.step);
+    j.skip_live = 1; ++w->lazy_skips;
+}
+// deferred Saves: a rollback group of the same steady session stores its first Save only (ggrs_world::SlotStale).  Every destination a slot of its own, none
+// the source (the replay reads the base while it writes the others), one step at least between two Saves, no spawn anywhere in the group
+int group_defer_saves(ggrs_world* w, GgrsJitArgs& j, GroupState& gs, bool dead, uint64_t cover) {
+    if (!j.src_is_live && j.n_saves >= 2) { w->defer_first = j.save_frame[0]; w->defer_last = j.save_frame[j.n_saves - 1]; }
+    bool ok = !dead && !gs.spawn_req && !j.src_is_live && j.n_saves >= 2 && defer_saves_on(w) &&
+              ((w->load_open_streak >= LAZY_LIVE_STREAK && w->defer_streak >= LAZY_LIVE_STREAK && cover > JIT_NT_MIN_SLOTS) || w->lazy_live_on == 3) &&
+              lazy_live_possible(w) && !w->has_strategy;
+    for (uint32_t k = 0; k < j.n_saves && ok; ++k) {
+        ok = gs.dsts[k] && gs.dsts[k] != gs.src && (k == 0 || gs.save_at[k] > gs.save_at[k - 1]);
+        for (uint32_t q = 0; q < k && ok; ++q) ok = gs.dsts[k] != gs.dsts[q];
+    }
+    for (uint32_t q = 0; q < j.n_steps && ok; ++q) ok = !j.spawn_count[q];
+    if (!ok) return GGRS_OK;
+    slot_stale_prune(w);                                        // what the previous chain still owes the ring is filled before its record is replaced
+    const int rc = materialise_slots(w); if (rc) return rc;
+    ggrs_world::SlotStale& c = w->slot_stale; const size_t nc = w->cur_ver.size();
+    const uint64_t new_dirty = std::max(gs.src->dirty_len, w->len);      // (what group_close gives a stored destination)
+    c.valid = true; c.base = gs.dsts[0]; c.n = j.n_saves;
+    if (c.ver.size() < (size_t)MAX_TICK_SAVES * nc) c.ver.resize((size_t)MAX_TICK_SAVES * nc);
+    const uint32_t s0 = gs.save_at[0]; c.len[0] = j.save_len[0]; c.at[0] = 0;
+    for (uint32_t k = 1; k < j.n_saves; ++k) {
+        c.dst[k] = gs.dsts[k]; c.stale[k] = true; c.at[k] = gs.save_at[k] - s0;
+        c.frame[k] = j.save_frame[k]; c.len[k] = j.save_len[k]; c.dirty[k] = new_dirty;
+        std::copy(w->group_save_ver.begin() + (size_t)k * nc, w->group_save_ver.begin() + (size_t)(k + 1) * nc, c.ver.begin() + (size_t)k * nc);
+        gs.dsts[k] = nullptr; j.save_dst[k] = nullptr; ++w->saves_deferred;   // group_close leaves the slot's versions, extent and tags as they are: they describe its bytes
+    }
+    for (uint32_t q = s0; q < gs.save_at[j.n_saves - 1]; ++q) jit_step_get(j, q, w->jit_reads_inputs, c.steps[q - s0]);
+    return GGRS_OK;
+}
+// ---- row versions -> store masks; what must be in registers = everything stored + everything a step or checksum reads.  Then the value tags.
+// *bytes_slot: what the launch moves per slot; *save0_bytes: the first Save's share of it (jit_group_policy)
+int group_masks(ggrs_world* w, GgrsJitArgs& j, GroupState& gs, bool dead, bool wrote_live, uint64_t static_reads, uint64_t* bytes_slot, uint64_t* save0_bytes) {
+    j.load_rows = j.n_ops ? static_reads : 0;
+    for (uint32_t k = 0; k < j.n_saves; ++k) {
+        j.save_rows[k] = j.save_dst[k] ? gs.save_rows[k] : 0;
+        j.save_pmask[k] = j.save_dst[k] ? gs.save_pmask[k] : 0;
+        j.load_rows |= j.save_rows[k];
+        const uint64_t b = rows_bytes_per_slot(w, j.save_rows[k], true); *bytes_slot += b; if (k == 0) *save0_bytes = b;
+    }
+    if (wrote_live) { j.live_rows = rows_to_store(w, w->live, w->cur_ver); j.live_pmask = pmask_differs(w, w->live, w->cur_ver); j.load_rows |= j.live_rows; *bytes_slot += rows_bytes_per_slot(w, j.live_rows, false); }
+    gs.live_rows = j.live_rows; j.vtags = (w->vtags && !dead) ? 1u : 0u;      // value tags: a group that stores nothing (a dead branch) has no use for them
+    if (j.vtags) {
+        const int rc = vtags_reserve(w, j.n_steps, 1, &j.tag_base); if (rc) return rc;
+        j.src_tagok = block_tagok(w, *gs.src); j.live_tagok = wrote_live ? block_tagok(w, w->live) : 0;
+        for (uint32_t k = 0; k < j.n_saves; ++k) j.save_tagok[k] = (j.save_dst[k] && gs.dsts[k]) ? block_tagok(w, *gs.dsts[k]) : 0;
+    }
+    *bytes_slot += rows_bytes_per_slot(w, j.load_rows, !j.src_is_live);
+    return GGRS_OK;
+}
+// spawns decided on the device: the mailboxes of the launch's rendezvous and its epochs
+int attach_dev_spawn(ggrs_world* w, GgrsJitArgs& j) {
+    const bool streamed = jit_dev_stream(w);
+    if (w->sp_epoch > 0xF0000000u) {         // epochs never repeat: long before the 32-bit counter wraps (~65 M launches) the mailboxes start over, in stream order
+        if (streamed) {                      // (the descriptors, the records' flag words and the pool cursor; never the ticket counter)
+            HIPCHK(w, hipMemsetAsync(w->d_sp_desc, 0, sp_desc_bytes(w), w->stream));
+            HIPCHK(w, hipMemsetAsync(w->d_sp_recs, 0, sp_recs_bytes(w), w->stream));
+            HIPCHK(w, hipMemsetAsync(w->d_sp_ctl + 1, 0, 8, w->stream));
+        } else HIPCHK(w, hipMemsetAsync(w->d_sp_sums, 0, (3 * (size_t)w->sp_tiles + 32) * 8, w->stream));
+        w->sp_epoch = 0;
+    }
+    j.sp_sums = reinterpret_cast<ggrs_u64*>(w->d_sp_sums); j.sp_epoch = w->sp_epoch; w->sp_epoch += streamed ? MAX_TICK_STEPS + 2u : 2u * MAX_TICK_STEPS + 2u;
+    j.sp_ctl = reinterpret_cast<ggrs_u64*>(w->d_sp_ctl); j.sp_desc = reinterpret_cast<ggrs_u64*>(w->d_sp_desc); j.sp_recs = reinterpret_cast<ggrs_u64*>(w->d_sp_recs);
+    j.sp_prec = w->d_sp_prec; j.sp_link = reinterpret_cast<ggrs_u64*>(w->d_sp_link); j.sp_len = reinterpret_cast<ggrs_u64*>(w->d_sp_len); j.sp_cap = w->capacity; j.sp_tiles = w->sp_tiles;
+    return GGRS_OK;
+}
+// a destination of the group is its source block or another destination: no depth-parallel roles (jit_group_policy)
+inline bool group_aliases(const GgrsJitArgs& j, bool wrote_live) {
+    bool ok = !(wrote_live && j.src == j.live);
+    for (uint32_t k = 0; k < j.n_saves; ++k) ok = ok && j.save_dst[k] != j.src;
+    // ... and the destinations pairwise distinct: a ring shallower than the group's Saves hands an evicted slot to a later Save, and two
+    // roles writing one block concurrently could leave the OLDER frame's rows there (in op order on one lane the newer one wins)
+    for (uint32_t k = 1; k < j.n_saves && ok; ++k) for (uint32_t q = 0; q < k; ++q) ok = ok && (!j.save_dst[k] || j.save_dst[k] != j.save_dst[q]);
+    return !ok;
+}
 int run_request_groups_gen(ggrs_world* w, const ggrs_request* reqs, uint32_t n, uint64_t* checksums_out,
                            uint32_t res_base = 0, bool wait = true, uint32_t* n_saves_out = nullptr) {
-    uint32_t i = 0, ns = 0;
-    int rc = GGRS_OK;
+    uint32_t i = 0, ns = 0; int rc = GGRS_OK;
     JitBatch batch; batch.blocking = wait;
     w->spin_n = 0;
-    // payloads this list has staged already (by the caller's host pointer): every branch of a fan-out step that spawns in frame f hands in the same
-    // arrays.  Offsets into the ring die with the ring's generation (a reset: the ring was full and the stream was waited for; a result page was read back)
-    struct Staged { const void* host; const void* host2; uint64_t bytes; const unsigned char* dev; };
-    std::vector<Staged> staged; uint64_t staged_gen = w->stage_gen;
+    StagedPayloads staged{{}, w->stage_gen};
     const uint32_t n_cks = w->cks_args.n_cks;
     const uint64_t static_reads = jit_static_reads(w);
-    if (n) {
-        // a list that opens with a LoadGameState replaces the live world: a lazily skipped live block needs no bytes; any other list reads it first
-        if (reqs[0].kind == GGRS_REQ_LOAD) ++w->load_open_streak; else { w->load_open_streak = 0; rc = materialise_live(w); if (rc) return rc; }
-    }
+    // a list that opens with a LoadGameState replaces the live world: a lazily skipped live block needs no bytes; any other list reads it first
+    if (n && reqs[0].kind == GGRS_REQ_LOAD) ++w->load_open_streak; else if (n) { w->load_open_streak = 0; rc = materialise_live(w); if (rc) return rc; }
     while (i < n) {
         w->batch_ev_attached = false;                                   // only the list's LAST launch may carry the batch event
         GgrsJitArgs j; memset(&j, 0, offsetof(GgrsJitArgs, inputs));
         GroupState gs;
-        uint32_t save_at[MAX_TICK_SAVES] = {};                          // steps the group had run at each Save
-        const ggrs_request* spawn_req = nullptr;
+        // ---- open: [Load?]; assemble: (Save | Advance)* up to the next Load, a cap, or a spawn that is not fused
         rc = group_open(w, reqs, i, gs); if (rc) return rc;
-        j.src_is_live = gs.src_is_live;
-        const uint64_t len_start = w->len;                              // the source block's len: a fused spawn grows w->len while the group is assembled
-        while (i < n && j.n_ops < (uint32_t)MAX_TICK_OPS) {
-            const ggrs_request& r = reqs[i];
-            if (r.kind == GGRS_REQ_LOAD) break;
-            if (r.kind == GGRS_REQ_SAVE) {
-                if (j.n_saves == w->cap_saves || (wait && ns + j.n_saves == w->max_results)) break;
-                rc = group_save(w, gs, j.n_saves, j.save_dst, j.save_frame); if (rc) return rc;
-                j.save_len[j.n_saves] = w->len; save_at[j.n_saves] = j.n_steps;
-                ++j.n_ops; ++j.n_saves;
-            } else if (r.kind == GGRS_REQ_ADVANCE) {
-                if (j.n_steps == w->cap_steps) break;
-                // A spawn system fires in this frame.  Fused (kernel_gen.hpp): the step's launch appends the rows itself -- the payload is staged
-                // now (pinned, device-mapped ring: no copy command per spawning step), the host does in request order what run_spawn_systems does
-                // around its kernel (capacity, versions of the bundle, len) and the group goes on.  Worlds whose spawn system the generator cannot
-                // fuse end the group after the step and run the spawn as its own launches, as Bevy's Commands flush ends the schedule.
-                const bool spawns = advance_spawns(w, r);
-                const bool fused_spawn = spawns && w->jit_spawn_sys >= 0;
-                const unsigned char* payload_dev = nullptr;
-                if (fused_spawn) {
-                    const ggrs_system_desc& sd = w->systems[w->jit_spawn_sys];
-                    const bool custom = sd.kind == GGRS_SYS_SPAWN_CUSTOM;
-                    if (r.spawn_count > 0xFFFFFFFFull || w->len + r.spawn_count > w->capacity)
-                        return w->fail(GGRS_E_CAPACITY, "spawn of %llu exceeds capacity %llu", (unsigned long long)r.spawn_count, (unsigned long long)w->capacity);
-                    // what the spawner reads: particles -- count f32 of vx, then count f32 of vy; user-written -- the request's payload blob
-                    const ggrs_world::SpawnSys* sp = custom ? &w->spawn_customs[sd.comp[0]] : nullptr;
-                    const uint64_t pbytes = custom ? (sp->payload_stride ? (uint64_t)sp->payload_stride * r.spawn_count : r.spawn_payload_bytes) : 8 * r.spawn_count;
-                    const void* key = custom ? r.spawn_payload : (const void*)r.spawn_vx;
-                    const void* key2 = custom ? nullptr : (const void*)r.spawn_vy;
-                    if (staged_gen != w->stage_gen) { staged.clear(); staged_gen = w->stage_gen; }
-                    const Staged* hit = nullptr;
-                    if (pbytes) for (auto& st : staged) if (st.host == key && st.host2 == key2 && st.bytes == pbytes) { hit = &st; break; }
-                    if (hit) payload_dev = hit->dev;
-                    else if (pbytes) {
-                        uint64_t soff = 0;
-                        if (!stage_ring_alloc(w, pbytes, &soff)) {
-                            // the ring is full of payloads that launches already queued -- or the steps of THIS group -- still have to read
-                            if (pbytes > w->stage_bytes) return w->fail(GGRS_E_CAPACITY, "spawn payload of %llu bytes exceeds the staging buffer (%llu bytes: GGRS_STAGE_BYTES)", (unsigned long long)pbytes, (unsigned long long)w->stage_bytes);
-                            if (j.n_ops) break;                              // the group ends BEFORE this frame: it is launched, then the frame opens the next group
-                            rc = batch.flush(w); if (rc) return rc;
-                            HIPCHK(w, hipStreamSynchronize(w->stream));      // let everything queued run, then start the ring over
-                            stage_ring_reset(w); staged.clear(); staged_gen = w->stage_gen;
-                            if (!stage_ring_alloc(w, pbytes, &soff)) return w->fail(GGRS_E_CAPACITY, "spawn payload of %llu bytes does not fit the staging buffer", (unsigned long long)pbytes);
-                        }
-                        // (the caller's arrays are free again when the call returns; the bytes sit in the ring until this list's batch is collected)
-                        if (custom) memcpy(w->h_stage + soff, r.spawn_payload, pbytes);
-                        else { memcpy(w->h_stage + soff, r.spawn_vx, r.spawn_count * 4); memcpy(w->h_stage + soff + r.spawn_count * 4, r.spawn_vy, r.spawn_count * 4); }
-                        payload_dev = w->d_hstage + soff;
-                        if (staged.size() < 256) staged.push_back({key, key2, pbytes, payload_dev});
-                    }
-                }
-                uint32_t dtb = 0;
-                rc = group_step(w, r, &dtb, w->jit_marks ? &j.step_flags[j.n_steps] : nullptr); if (rc) return rc;
-                if (w->dev_spawn) {                                            // any frame may append rows of the bundle: its columns and presence masks are new after every step
-                    const ggrs_world::SpawnSys& spd = w->spawn_customs[w->systems[w->jit_spawn_sys].comp[0]];
-                    for (uint32_t c = 0; c < w->comps.size(); ++c) if ((spd.bundle_mask >> c) & 1ull) ver_touch_comp(w, c);
-                }
-                j.dt_bits[j.n_steps] = dtb;
-                j.step_frame[j.n_steps] = w->frame; j.step_confirmed[j.n_steps] = w->confirmed;
-                if (w->jit_box_sys >= 0) {                                     // FRICTION.powf(dt), platform libm (box_game.rs:189-195)
-                    float dtf; memcpy(&dtf, &dtb, 4);
-                    const float fp = powf(w->systems[w->jit_box_sys].fparam[2], dtf);
-                    memcpy(&j.aux_bits[j.n_steps], &fp, 4);
-                }
-                j.n_inputs[j.n_steps] = (uint8_t)std::min<uint32_t>(r.n_inputs, w->max_players);
-                if (w->jit_reads_inputs) pack_inputs(w, r, j.inputs[j.n_steps]);      // PlayerInputs<T>: (T::Input, InputStatus) per player (src/lib.rs:98)
-                const uint32_t step = j.n_steps;
-                ++j.n_steps;
-                j.op_bits |= 1ULL << j.n_ops; ++j.n_ops;
-                if (fused_spawn) {
-                    const ggrs_system_desc& sd = w->systems[w->jit_spawn_sys];
-                    j.spawn_payload[step] = payload_dev;
-                    j.spawn_first[step] = w->len; j.spawn_count[step] = (uint32_t)r.spawn_count;
-                    // new rows in every column (and the presence mask) of the bundle
-                    if (sd.kind == GGRS_SYS_SPAWN_CUSTOM) { const ggrs_world::SpawnSys& sp = w->spawn_customs[sd.comp[0]]; for (uint32_t c = 0; c < w->comps.size(); ++c) if ((sp.bundle_mask >> c) & 1ull) ver_touch_comp(w, c); }
-                    else { ver_touch_comp(w, sd.comp[0]); ver_touch_comp(w, sd.comp[1]); ver_touch_comp(w, sd.comp[2]); }
-                    w->len += r.spawn_count;
-                } else if (spawns) { spawn_req = &r; ++i; break; }
-            } else {
-                return w->fail(GGRS_E_INVALID, "unknown request kind %u", r.kind);
-            }
-            ++i;
+        j.src_is_live = gs.src_is_live; j.src = gs.src->ptr; j.live = w->live.ptr;
+        j.len = w->len;                                                 // the source block's len: a fused spawn grows w->len while the group is assembled
+        while (i < n && j.n_ops < (uint32_t)MAX_TICK_OPS && reqs[i].kind != GGRS_REQ_LOAD) {
+            bool taken = false;
+            rc = group_take(w, reqs[i], j, gs, staged, batch, wait ? w->max_results - ns : 0xFFFFFFFFu, &taken); if (rc) return rc;
+            if (!taken) break;
+            ++i; if (gs.spawn_req) break;
         }
-        const bool dead = !w->dev_spawn && group_is_dead(w, reqs, i, n, j.save_frame, j.n_saves, spawn_req != nullptr);
+        // ---- dead / lazy / deferred: what the group need not store
+        const bool dead = !w->dev_spawn && group_is_dead(w, reqs, i, n, j.save_frame, j.n_saves, gs.spawn_req != nullptr);
         if (dead) { for (uint32_t k = 0; k < j.n_saves; ++k) j.save_dst[k] = nullptr; j.skip_live = 1; }
         const uint64_t cover = w->dev_spawn ? w->capacity : std::max(gs.cover, w->len);      // (device-decided spawns: the host only knows a bound of len)
-        // lazy live block: the LAST group of a list that ends [.., Save(F), Advance] in a session whose lists keep opening with a Load
-        if (!dead && !spawn_req && i >= n && ((w->load_open_streak >= LAZY_LIVE_STREAK && cover > JIT_NT_MIN_SLOTS) || w->lazy_live_on == 2 || w->lazy_live_on == 3) && j.n_ops >= 2 && j.n_saves && j.n_steps &&
-            ((j.op_bits >> (j.n_ops - 1)) & 1ull) && !((j.op_bits >> (j.n_ops - 2)) & 1ull) && gs.dsts[j.n_saves - 1] && !j.spawn_count[j.n_steps - 1] &&
-            gs.dsts[j.n_saves - 1] != gs.src && lazy_live_possible(w)) {
-            j.skip_live = 1;
-            ggrs_world::LiveStale& st = w->live_stale;
-            const uint32_t q = j.n_steps - 1;
-            st.valid = true; st.src = gs.dsts[j.n_saves - 1]; st.len = j.save_len[j.n_saves - 1];
-            st.dt_bits = j.dt_bits[q]; st.aux_bits = j.aux_bits[q]; st.step_frame = j.step_frame[q]; st.step_confirmed = j.step_confirmed[q]; st.n_inputs = j.n_inputs[q];
-            if (w->jit_reads_inputs) memcpy(st.inputs, j.inputs[q], sizeof st.inputs); else memset(st.inputs, 0, sizeof st.inputs);
-            ++w->lazy_skips;
-        }
-        // deferred Saves: a rollback group of the same steady session stores its first Save only (ggrs_world::SlotStale).  Every destination a slot of its own, none
-        // the source (the replay reads the base while it writes the others), one step at least between two Saves, no spawn anywhere in the group
-        if (!j.src_is_live && j.n_saves >= 2) { w->defer_first = j.save_frame[0]; w->defer_last = j.save_frame[j.n_saves - 1]; }
-        if (!dead && !spawn_req && !j.src_is_live && j.n_saves >= 2 && defer_saves_on(w) &&
-            ((w->load_open_streak >= LAZY_LIVE_STREAK && w->defer_streak >= LAZY_LIVE_STREAK && cover > JIT_NT_MIN_SLOTS) || w->lazy_live_on == 3) && lazy_live_possible(w) && !w->has_strategy) {
-            bool ok = true;
-            for (uint32_t k = 0; k < j.n_saves && ok; ++k) {
-                ok = gs.dsts[k] && gs.dsts[k] != gs.src && (k == 0 || save_at[k] > save_at[k - 1]);
-                for (uint32_t q = 0; q < k && ok; ++q) ok = gs.dsts[k] != gs.dsts[q];
-            }
-            for (uint32_t q = 0; q < j.n_steps && ok; ++q) ok = !j.spawn_count[q];
-            if (ok) {
-                slot_stale_prune(w);                                        // what the previous chain still owes the ring is filled before its record is replaced
-                rc = materialise_slots(w); if (rc) return rc;
-                ggrs_world::SlotStale& c = w->slot_stale;
-                const size_t nc = w->cur_ver.size();
-                const uint64_t new_dirty = std::max(gs.src->dirty_len, w->len);      // (what group_close gives a stored destination)
-                c.valid = true; c.base = gs.dsts[0]; c.n = j.n_saves;
-                if (c.ver.size() < (size_t)MAX_TICK_SAVES * nc) c.ver.resize((size_t)MAX_TICK_SAVES * nc);
-                const uint32_t s0 = save_at[0];
-                c.len[0] = j.save_len[0]; c.at[0] = 0;
-                for (uint32_t k = 1; k < j.n_saves; ++k) {
-                    c.dst[k] = gs.dsts[k]; c.stale[k] = true; c.at[k] = save_at[k] - s0;
-                    c.frame[k] = j.save_frame[k]; c.len[k] = j.save_len[k]; c.dirty[k] = new_dirty;
-                    std::copy(w->group_save_ver.begin() + (size_t)k * nc, w->group_save_ver.begin() + (size_t)(k + 1) * nc, c.ver.begin() + (size_t)k * nc);
-                    gs.dsts[k] = nullptr; j.save_dst[k] = nullptr;             // group_close leaves the slot's versions, extent and tags as they are: they describe its bytes
-                    ++w->saves_deferred;
-                }
-                for (uint32_t q = s0; q < save_at[j.n_saves - 1]; ++q) {
-                    const uint32_t r = q - s0;
-                    c.dt_bits[r] = j.dt_bits[q]; c.aux_bits[r] = j.aux_bits[q]; c.step_frame[r] = j.step_frame[q]; c.step_confirmed[r] = j.step_confirmed[q]; c.n_inputs[r] = j.n_inputs[q];
-                    if (w->jit_reads_inputs) memcpy(c.inputs[r], j.inputs[q], std::min(sizeof c.inputs[r], sizeof j.inputs[q])); else memset(c.inputs[r], 0, sizeof c.inputs[r]);
-                }
-            }
-        }
+        group_lazy_live(w, j, gs, dead, i >= n, cover);
+        rc = group_defer_saves(w, j, gs, dead, cover); if (rc) return rc;
         const bool wrote_live = (!j.src_is_live || j.n_steps) && !j.skip_live;
-        // ---- row versions -> store masks; what must be in registers = everything stored + everything a step or checksum reads
-        uint64_t bytes_slot = 0;
-        j.load_rows = j.n_ops ? static_reads : 0;
-        for (uint32_t k = 0; k < j.n_saves; ++k) {
-            j.save_rows[k] = j.save_dst[k] ? gs.save_rows[k] : 0;
-            j.save_pmask[k] = j.save_dst[k] ? gs.save_pmask[k] : 0;
-            j.load_rows |= j.save_rows[k];
-            bytes_slot += rows_bytes_per_slot(w, j.save_rows[k], true);
-        }
-        if (wrote_live) { j.live_rows = rows_to_store(w, w->live); j.live_pmask = pmask_differs(w, w->live, w->cur_ver); j.load_rows |= j.live_rows; bytes_slot += rows_bytes_per_slot(w, j.live_rows, false); }
-        gs.live_rows = j.live_rows;
-        // value tags: a group that stores nothing (a dead branch) has no use for them
-        j.vtags = (w->vtags && !dead) ? 1u : 0u;
-        if (j.vtags) {
-            rc = vtags_reserve(w, j.n_steps, 1, &j.tag_base); if (rc) return rc;
-            j.src_tagok = block_tagok(w, *gs.src); j.live_tagok = wrote_live ? block_tagok(w, w->live) : 0;
-            for (uint32_t k = 0; k < j.n_saves; ++k) j.save_tagok[k] = (j.save_dst[k] && gs.dsts[k]) ? block_tagok(w, *gs.dsts[k]) : 0;
-        }
-        bytes_slot += rows_bytes_per_slot(w, j.load_rows, !j.src_is_live);
-        j.src = gs.src->ptr; j.live = w->live.ptr; j.len = len_start;
-        if (w->dev_spawn) {
-            const bool streamed = jit_dev_stream(w);
-            if (w->sp_epoch > 0xF0000000u) {         // epochs never repeat: long before the 32-bit counter wraps (~65 M launches) the mailboxes start over, in stream order
-                if (streamed) {                      // (the descriptors, the records' flag words and the pool cursor; never the ticket counter)
-                    HIPCHK(w, hipMemsetAsync(w->d_sp_desc, 0, sp_desc_bytes(w), w->stream));
-                    HIPCHK(w, hipMemsetAsync(w->d_sp_recs, 0, sp_recs_bytes(w), w->stream));
-                    HIPCHK(w, hipMemsetAsync(w->d_sp_ctl + 1, 0, 8, w->stream));
-                } else HIPCHK(w, hipMemsetAsync(w->d_sp_sums, 0, (3 * (size_t)w->sp_tiles + 32) * 8, w->stream));
-                w->sp_epoch = 0;
-            }
-            j.sp_sums = reinterpret_cast<ggrs_u64*>(w->d_sp_sums); j.sp_epoch = w->sp_epoch; w->sp_epoch += streamed ? MAX_TICK_STEPS + 2u : 2u * MAX_TICK_STEPS + 2u;
-            j.sp_ctl = reinterpret_cast<ggrs_u64*>(w->d_sp_ctl); j.sp_desc = reinterpret_cast<ggrs_u64*>(w->d_sp_desc); j.sp_recs = reinterpret_cast<ggrs_u64*>(w->d_sp_recs);
-            j.sp_prec = w->d_sp_prec; j.sp_link = reinterpret_cast<ggrs_u64*>(w->d_sp_link);
-            j.sp_len = reinterpret_cast<ggrs_u64*>(w->d_sp_len); j.sp_cap = w->capacity; j.sp_tiles = w->sp_tiles;
-        }
-        j.parts = reinterpret_cast<ggrs_u64*>(w->d_gen_parts); j.part_stride = w->gen_part_stride; j.part_tstride = 1;
-        j.n_units = std::max<uint32_t>(1, (uint32_t)((cover + 63) / 64));
-        const uint32_t g = std::max<uint32_t>(1, (uint32_t)((cover + 255) / 256));
-        j.nt = (w->nt_copy || cover > JIT_NT_MIN_SLOTS) ? 1u : 0u;
-        // A rollback group's FIRST Save is the oldest frame it produces -- what the next rollback loads (SyncTest: always; P2P with a steady
-        // rollback depth: likewise).  Storing it through the L2 instead of around it lets the next launch's loads hit there: 72.5 -> 64.6 us
-        // per depth-8 tick at 1 M in the ring-walking harness (profiles/r03n), every other row still streams past the caches.
-        // Past ~2.5 M particles the rows no longer survive in the caches until the next launch and only displace the stream (4 M: +3 %; r04c).
-        j.cached_saves = (j.nt && !j.src_is_live && j.n_saves >= 2 && rows_bytes_per_slot(w, j.save_rows[0], true) * cover <= JIT_CACHED_SAVE_MAX_BYTES) ? 1u : 0u;
-        // the source block of an HBM-sized rollback group is in the caches only if the previous group kept a Save there (the steady session: the
-        // same decision as this group's): otherwise its lines come from HBM once and are dead after the load (4 M: -3.5 %, allhot 4 M -8 %; it costs
-        // 3 % where the loads DO hit: profiles/r04o)
-        j.nt_loads = (j.nt && !j.cached_saves && !j.src_is_live) ? 1u : 0u;
+        // ---- masks, tags, bytes; the device-spawn mailboxes; geometry
+        uint64_t bytes_slot = 0, save0_bytes = 0;
+        rc = group_masks(w, j, gs, dead, wrote_live, static_reads, &bytes_slot, &save0_bytes); if (rc) return rc;
+        if (w->dev_spawn) { rc = attach_dev_spawn(w, j); if (rc) return rc; }
+        const uint32_t g = jit_geometry(w, j, cover);
+        // ---- policy: per-tile grid of 256-slot workgroups, depth-parallel roles
+        const JitPolicy pol = jit_group_policy(cover, j.n_saves, j.src_is_live != 0, save0_bytes, group_aliases(j, wrote_live), w->jit_marks, w->dev_spawn, w->nt_copy);
+        j.nt = pol.nt; j.cached_saves = pol.cached_saves; j.nt_loads = pol.nt_loads; j.dp_s = pol.dp_s;
         const bool launch = j.n_ops || !j.src_is_live;
-        {
-            // ---- per-tile grid: 256-slot workgroups, depth-parallel roles, batches; the partial rows go to the host, forward, or to k_gen_finalize
-            // Depth-parallel roles: the group's outputs (Saves + live world) are split over grid.y roles of dp_s outputs.  Every role
-            // reads the source block while the others write theirs, so the source must be none of the destinations; below ~2 Saves
-            // there is no chain to split.  Crossovers: profiles/r02dp/ab2.txt, profiles/r02jit/jit_dp.txt.
-            if (j.n_saves >= 2 && !w->jit_marks && !w->dev_spawn) {
-                bool ok = !(wrote_live && j.src == j.live);
-                for (uint32_t k = 0; k < j.n_saves; ++k) ok = ok && j.save_dst[k] != j.src;
-                // ... and the destinations pairwise distinct: a ring shallower than the group's Saves hands an evicted slot to a later Save, and two
-                // roles writing one block concurrently could leave the OLDER frame's rows there (in op order on one lane the newer one wins)
-                for (uint32_t k = 1; k < j.n_saves && ok; ++k) for (uint32_t q = 0; q < k; ++q) ok = ok && (!j.save_dst[k] || j.save_dst[k] != j.save_dst[q]);
-                const uint64_t m = JIT_DP_MAX_SLOTS;
-                if (ok) j.dp_s = cover <= m ? 1u : (cover <= 2 * m ? 2u : (cover <= 6 * m ? 3u : 0u));
-            }
-            // identical checksum-only groups (speculative branches) ride in one launch; a batch already fills the chip, so no roles
-            const bool batchable = dead && j.n_saves > 0 && !w->jit_marks && cover <= JIT_BATCH_MAX_SLOTS;
-            if (batchable && batch.active) {
-                GgrsJitArgs jb = j; jb.dp_s = 0;
-                if (batch.try_add(w, jb, g, res_base + ns)) { batch.j.dp_s = 0; group_close(w, gs, j.n_saves, dead, wrote_live); ns += j.n_saves; goto group_done; }
-            }
+        // identical checksum-only groups (speculative branches) ride in one launch; a batch already fills the chip, so no roles
+        const bool batchable = dead && j.n_saves > 0 && !w->jit_marks && cover <= JIT_BATCH_MAX_SLOTS;
+        bool batched = false;
+        if (batchable && batch.active) { GgrsJitArgs jb = j; jb.dp_s = 0; batched = batch.try_add(w, jb, g, res_base + ns); if (batched) batch.j.dp_s = 0; }
+        if (!batched) {
             rc = batch.flush(w); if (rc) return rc;
-            if (batchable) { batch.start(j, g, res_base + ns, n_cks); group_close(w, gs, j.n_saves, dead, wrote_live); ns += j.n_saves; goto group_done; }
-            // who folds this launch's partial rows: the next launch on the stream (fold-forward: enqueued lists of more than
-            // GGRS_FOLD_FORWARD_MIN_WGS workgroups), the launch itself (self-fold: blocking calls of that size), the host from pinned rows (smaller groups), or k_gen_finalize (blocking calls of more than 1024
-            // workgroups, results that stay on the device, no room in the pinned ring)
-            uint64_t rows_off = 0;
-            const uint32_t ff_split = (g + FF_CHUNK - 1u) / FF_CHUNK;                      // chunks of <= 1024 entries per row: one fold-forward workgroup each
-            const uint32_t nvals = j.n_saves * (n_cks + 1) * ff_split;
-            bool ff = launch && j.n_saves && !wait && !w->device_results_only && !w->dev_spawn && g > (uint32_t)w->knobs.fold_forward_min_wgs && w->d_ff_rows[0] &&
-                      rows_ring_alloc(w, 2ull * nvals, &rows_off);
-            // a BLOCKING call of that size: the launch folds its own rows (self-fold: its fold workgroups read the tile workgroups' tagged cells as they arrive) -- no k_gen_finalize
-            // between the kernel and the caller.  Not beside a pending fold-forward (the role folds one set of rows), not with depth-parallel roles (plain grids only),
-            // and only while the fold workgroups -- resident and waiting from the launch's start -- are few beside the 2048 the device holds (8 M entities and more
-            // keep k_gen_finalize: thousands of waiting workgroups would leave the tiles no room, at 32 M none at all)
-            const bool ffs = !ff && launch && j.n_saves && wait && nvals <= SELF_FOLD_MAX_WGS && !w->device_results_only && !w->dev_spawn && !j.dp_s && !w->ff_pending.valid &&
-                             g > (uint32_t)w->knobs.fold_forward_min_wgs && w->d_ff_rows[0] && !spawn_req && rows_ring_alloc(w, 2ull * nvals, &rows_off);
-            if (ffs) ff = true;
-            const bool host_fold = !ff && launch && host_fold_rows(w, g, j.n_saves, n_cks, 1, &rows_off, wait);
-            uint32_t ff_buf = 0;
-            const uint32_t rows_n = j.n_saves * (n_cks + 1);
-            // fold-forward rows are TILE-major: a workgroup's values of all its Saves and parts sit side by side (one coalesced store of 192 B for the
-            // stress_test; row-major they were 24 eight-byte stores into 24 different lines, and the 1 M launch took 51 us instead of 48.9: profiles/r05c)
-            if (ff && !ffs) { ff_buf = w->ff_cur; w->ff_cur ^= 1u; j.parts = reinterpret_cast<ggrs_u64*>(w->d_ff_rows[ff_buf]); j.part_stride = 1; j.part_tstride = rows_n; }
-            // (self-fold: 16-byte cells {value, tag} instead of 8-byte entries -- the two fold-forward buffers, which lie side by side and hold nothing pending, as one)
-            if (ffs) { ff_buf = 0; j.parts = reinterpret_cast<ggrs_u64*>(w->d_ff_rows[0]); j.part_stride = 1; j.part_tstride = rows_n; }
-            uint64_t ffs_id = 0, ffs_seq = 0;
-            if (ffs) {
-                ffs_id = w->ff_next_id++; ffs_seq = (0xA5ull << 56) | ++w->ff_seq;
-                memset(w->h_rows + rows_off, 0, (size_t)nvals * 16);
-                j.ff_rows = reinterpret_cast<const ggrs_u64*>(w->d_ff_rows[ff_buf]); j.ff_out = reinterpret_cast<ggrs_u64*>(w->d_rows + rows_off); j.ff_seq = ffs_seq;
-                j.ff_nvals = nvals; j.ff_blocks = (nvals + 7u) & ~7u; j.ff_g = g; j.ff_stride = 1; j.ff_istride = rows_n; j.ff_split = ff_split;
-                j.ff_self = 1;
-                w->ff_done_id = ffs_id; w->ff_mark_id = ffs_id;       // the fold is on the stream with this very launch; launch_jit records its event behind it
-            }
-            if (host_fold) { j.parts = reinterpret_cast<ggrs_u64*>(w->d_rows + rows_off); j.part_stride = g; }
+            if (batchable) { batch.start(j, g, res_base + ns, n_cks); batched = true; }
+        }
+        if (batched) group_close(w, gs, j.n_saves, dead, wrote_live);
+        else {
+            // ---- fold route, launch, close, record the fold
+            FoldPlan fold = fold_route_choose(w, j, g, n_cks, launch, wait, gs.spawn_req != nullptr);
+            fold_route_setup(w, j, fold, g);
             if (launch) {
                 hipFunction_t fn = jit_spec_for(w, j);
                 if (!fn) fn = w->jit_fn;
                 // nothing is queued behind this kernel when its rows are folded later (or there is nothing to fold) and no spawn system follows:
                 // the batch event of an enqueued list then completes WITH it (no marker packet between this tick's kernel and the next one's)
-                const bool last_gpu_op = (host_fold || ff || !j.n_saves) && !spawn_req && !w->prof;
+                const bool last_gpu_op = fold.route != FoldRoute::Finalize && !gs.spawn_req && !w->prof;
                 hipEvent_t done = last_gpu_op ? w->batch_ev : nullptr;
                 rc = launch_jit(w, fn, w->dev_spawn && jit_dev_stream(w) ? g : jit_grid(g), j.dp_s ? (j.n_saves + j.dp_s) / j.dp_s : 1u, 1, jit_lane_fold_bytes(w, n_cks, j.n_saves), j, bytes_slot * w->len, done); if (rc) return rc;
                 w->batch_ev_attached = done != nullptr;
             }
             group_close(w, gs, j.n_saves, dead, wrote_live);
-            if (ff) {
-                ggrs_world::HostFold f = make_host_fold(j, res_base + ns, ff_split, n_cks, 1u, rows_off);   // (the host XORs / adds the row's chunks)
-                if (ffs) { f.ff_id = ffs_id; f.ff_seq = ffs_seq; w->folds.push_back(f); ns += j.n_saves; }
-                else {
-                f.ff_id = w->ff_next_id++; f.ff_seq = (0xA5ull << 56) | ++w->ff_seq;      // (a tag no live count and -- but for 2^-64 -- no hash equals)
-                memset(w->h_rows + rows_off, 0, (size_t)nvals * 16);                    // the {value, tag} cells: whatever an earlier fold left there is gone
-                w->folds.push_back(f);
-                ggrs_world::FfPending& p = w->ff_pending;
-                p.valid = true; p.id = f.ff_id; p.seq = f.ff_seq; p.buf = ff_buf; p.nvals = nvals; p.g = g; p.stride = 1; p.istride = rows_n; p.split = ff_split; p.out_off = rows_off;
-                ns += j.n_saves;
-                }
-            } else if (host_fold) { w->folds.push_back(make_host_fold(j, res_base + ns, g, n_cks, 1u, rows_off)); ns += j.n_saves; }
-            else if (j.n_saves) {
-                GenFinArgs f = make_gen_fin(w, j, g, n_cks, res_base + ns);   // one row per workgroup
-                arm_spin(w, f, j.n_saves, wait);
-                {
-                    ProfScope ps(w, GGRS_KERNEL_CHECKSUM);
-                    hipLaunchKernelGGL(k_gen_finalize, dim3(j.n_saves), dim3(FIN_TPB), 0, w->stream, f);
-                }
-                HIPCHK(w, hipGetLastError());
-                ns += j.n_saves;
-            }
+            rc = fold_route_record(w, j, fold, g, n_cks, res_base + ns, wait); if (rc) return rc;
         }
-        group_done:
-        if (spawn_req) {
+        ns += j.n_saves;
+        // ---- spawn follow-up, read back
+        if (gs.spawn_req) {
             rc = batch.flush(w); if (rc) return rc;
             w->spin_n = 0;
-            rc = run_spawn_systems(w, spawn_req->inputs, spawn_req->n_inputs, spawn_req->spawn_count, spawn_req->spawn_vx, spawn_req->spawn_vy);
-            if (rc) return rc;
+            rc = run_spawn_systems(w, gs.spawn_req->inputs, gs.spawn_req->n_inputs, gs.spawn_req->spawn_count, gs.spawn_req->spawn_vx, gs.spawn_req->spawn_vy); if (rc) return rc;
         }
         if (wait && ns == w->max_results) {
             rc = batch.flush(w); if (rc) return rc;
@@ -827,8 +833,7 @@ int run_request_groups_gen(ggrs_world* w, const ggrs_request* reqs, uint32_t n, 
     }
     rc = batch.flush(w); if (rc) return rc;
     if (n_saves_out) *n_saves_out = ns;
-    if (!wait) return GGRS_OK;
-    return read_back(w, ns, checksums_out);
+    return wait ? read_back(w, ns, checksums_out) : GGRS_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -940,8 +945,8 @@ int run_branch_step(ggrs_world* w, const ggrs_branch_step& st, uint32_t res_firs
         j.op_bits |= 1ull << j.n_ops; ++j.n_ops;
         j.dt_bits[i] = dt_bits_for_frame(w->fps, F + 1 + (int32_t)i);
         j.step_frame[i] = F + 1 + (int32_t)i; j.step_confirmed[i] = w->confirmed;
-        if (w->jit_marks) j.step_flags[i] = w->confirmed < F + 1 + (int32_t)i ? 2u : 0u;      // bit 1: despawn_rollback() defers (group_step); bit 0 never: DespawnConfirmed runs on the live world before the launch
-        if (w->jit_box_sys >= 0) { float dtf; memcpy(&dtf, &j.dt_bits[i], 4); const float fp = powf(w->systems[w->jit_box_sys].fparam[2], dtf); memcpy(&j.aux_bits[i], &fp, 4); }
+        if (w->jit_marks) j.step_flags[i] = w->confirmed < F + 1 + (int32_t)i ? 2u : 0u;      // bit 1: despawn_rollback() defers (group_take); bit 0 never: DespawnConfirmed runs on the live world before the launch
+        if (w->jit_box_sys >= 0) j.aux_bits[i] = box_aux_bits(w, j.dt_bits[i]);
         if (i < S) { j.save_frame[i] = F + 1 + (int32_t)i; ++j.n_ops; }
     }
     j.skip_live = (keep_any && tail_adv) ? 0u : 1u;
@@ -998,11 +1003,10 @@ int run_branch_step(ggrs_world* w, const ggrs_branch_step& st, uint32_t res_firs
             Block* d = &w->spec_blocks[next_blk];
             if (keep) keep->blk[(size_t)b * n_out + o] = (int)next_blk;
             ++next_blk;
-            uint64_t m = 0;
-            for (uint32_t c = 0; c < w->n_tcols && c < 64; ++c) if (w->col_rb[c] && ver_differs(w, *d, cv, c)) m |= 1ull << c;
+            const uint64_t m = rows_to_store(w, *d, cv);
             *rows_out = m; *pm_out = pmask_differs(w, *d, cv);
             *tagok_out = block_tagok(w, *d);
-            if (w->vtags) d->tag_ok |= m & w->tag_cols; else d->tag_ok &= ~m;
+            tags_after_store(w, *d, m);
             d->ver = cv; d->len = len_b;
             load_rows |= m; store_bytes += rows_bytes_per_slot(w, m, o < S) * len_b;
             touched.push_back(d);
@@ -1055,7 +1059,7 @@ int run_branch_step(ggrs_world* w, const ggrs_branch_step& st, uint32_t res_firs
     cover = std::max(cover, max_len);
     for (Block* d : touched) d->dirty_len = std::max(src.dirty_len, max_len);
     // ---- one launch for all members, one k_gen_finalize for all their Saves
-    const uint32_t g = std::max<uint32_t>(1, (uint32_t)((cover + 255) / 256));
+    const uint32_t g = jit_geometry(w, j, cover);
     const uint64_t parts_need = (uint64_t)B * std::max(1u, S) * (n_cks + 1) * g;
     if (parts_need > w->branch_parts_cap) {
         if (w->d_branch_parts) { HIPCHK(w, hipStreamSynchronize(w->stream)); (void)hipFree(w->d_branch_parts); w->d_branch_parts = nullptr; w->branch_parts_cap = 0; }
@@ -1067,8 +1071,7 @@ int run_branch_step(ggrs_world* w, const ggrs_branch_step& st, uint32_t res_firs
                                                                        // the markers (mk_dis, df_0) and live-only columns a system reads --, which is why the live block was materialised above
     j.mtab = w->d_stage + soff;
     j.load_rows = load_rows;
-    j.parts = reinterpret_cast<ggrs_u64*>(w->d_branch_parts); j.part_stride = g; j.part_tstride = 1;
-    j.n_units = std::max<uint32_t>(1, (uint32_t)((cover + 63) / 64));
+    j.parts = reinterpret_cast<ggrs_u64*>(w->d_branch_parts); j.part_stride = g;      // (a buffer of the step's own: B members x S Saves)
     // live-only state: a DespawnConfirmed that is due runs once on the live world, ahead of the launch on the stream; the members then see ConfirmedFrameCount unchanged
     rc = step_despawn_confirmed(w); if (rc) return rc;
     j.marks_dst = nullptr;
@@ -1091,11 +1094,7 @@ int run_branch_step(ggrs_world* w, const ggrs_branch_step& st, uint32_t res_firs
     if (S) {
         GenFinArgs f = make_gen_fin(w, j, g, n_cks, res_first);
         f.mtab = w->d_stage + soff; f.mstride = L.m.bytes; f.moff_save_len = L.m.save_len;
-        {
-            ProfScope ps(w, GGRS_KERNEL_CHECKSUM);
-            hipLaunchKernelGGL(k_gen_finalize, dim3(S * B), dim3(FIN_TPB), 0, w->stream, f);
-        }
-        HIPCHK(w, hipGetLastError());
+        rc = launch_gen_finalize(w, f, S * B); if (rc) return rc;
     }
     if (keep) { keep->valid = keep_any; keep->marks = keep_marks ? w->d_branch_marks : nullptr; keep->rec_bytes = rec_bytes; keep->units = j.n_units; }
     return GGRS_OK;

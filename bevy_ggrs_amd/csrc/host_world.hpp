@@ -143,6 +143,8 @@ inline bool source_has_token(const std::string& src, const char* tok) {
         if ((p == 0 || !idc(src[p - 1])) && (p + n >= src.size() || !idc(src[p + n]))) return true;
     return false;
 }
+// One step of a request group as it ran: what a later launch needs to run it again (LiveStale, SlotStale; host_groups.hpp jit_step_get / jit_step_put).  inputs: the step's whole input row (JIT_IN_MAX, kernel_gen.hpp)
+struct StepRec { uint32_t dt_bits = 0, aux_bits = 0; int frame = 0, confirmed = 0; unsigned char n_inputs = 0; unsigned char inputs[GGRS_MAX_PLAYERS * (GGRS_MAX_INPUT_BYTES + 1)] = {}; };
 struct ggrs_world {
     // ---- configuration
     int device = 0;
@@ -280,8 +282,7 @@ struct ggrs_world {
     // LAZY LIVE BLOCK (host_groups.hpp): the last group of the previous list ended  [.., Save(F), Advance]  and did not write the live block -- the
     // live world (frame F + 1) IS Advance(ring slot of F) until somebody needs its bytes: a list that opens with a LoadGameState never does (a SyncTest
     // session, a P2P session in steady rollback), everything else materialises it first (materialise_live: one small launch)
-    struct LiveStale { bool valid = false; Block* src = nullptr; uint64_t len = 0; uint32_t dt_bits = 0, aux_bits = 0; int step_frame = 0, step_confirmed = 0;
-                       unsigned char n_inputs = 0; unsigned char inputs[GGRS_MAX_PLAYERS * (GGRS_MAX_INPUT_BYTES + 1)] = {}; } live_stale;
+    struct LiveStale { bool valid = false; Block* src = nullptr; uint64_t len = 0; StepRec step; } live_stale;
     // DEFERRED SAVES (host_groups.hpp): a group of the same steady session stored only its FIRST Save (the base); ring slot dst[k] (k >= 1) IS the base advanced by
     // the recorded steps [0, at[k]) until somebody needs its bytes (materialise_slots: one launch fills every slot still stale).  A stale slot's Block::ver, dirty_len and
     // tag_ok keep describing the bytes it really holds; ver[k] / dirty[k] are what it holds once materialised.  stale[k] is cleared when a Save lands in the slot.
@@ -290,8 +291,7 @@ struct ggrs_world {
         Block* dst[MAX_TICK_SAVES] = {}; bool stale[MAX_TICK_SAVES] = {}; uint32_t at[MAX_TICK_SAVES] = {};
         int32_t frame[MAX_TICK_SAVES] = {}; uint64_t len[MAX_TICK_SAVES] = {}, dirty[MAX_TICK_SAVES] = {};
         std::vector<ver_t> ver;                                                   // [k][column]
-        uint32_t dt_bits[MAX_TICK_STEPS] = {}, aux_bits[MAX_TICK_STEPS] = {}; int step_frame[MAX_TICK_STEPS] = {}, step_confirmed[MAX_TICK_STEPS] = {};
-        unsigned char n_inputs[MAX_TICK_STEPS] = {}; unsigned char inputs[MAX_TICK_STEPS][GGRS_MAX_PLAYERS * (GGRS_MAX_INPUT_BYTES + 1)] = {};
+        StepRec steps[MAX_TICK_STEPS];                                            // the group's steps from its first Save on, as it ran them
     } slot_stale;
     int lazy_live_on = 1;                // (ggrs_dbg_set_lazy_live: 0 = the A/B of profiles/r05h, no deferred Saves either; 2 = every eligible list whatever its size and streak: the fuzzer;
                                          //  3 = as 2, and every eligible group defers its Saves; 4 = as 1 without deferred Saves)

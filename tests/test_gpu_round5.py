@@ -292,12 +292,15 @@ def _hiprtc_compile(src: str) -> bytes:
     return code.raw
 
 
-def test_shipped_code_objects_serve_a_world_without_the_runtime_compiler(tmp_path, monkeypatch):
+# one size per bucket of the store / load / role policy (host_groups.hpp jit_group_policy), which the steady signature and the running group must both land in:
+# one output per role, two, three, no roles with temporal stores, non-temporal stores with a cached first Save (lazy live block, deferred Saves)
+@pytest.mark.parametrize("n", [30_123, 60_321, 123_456, 300_321, 450_123])
+def test_shipped_code_objects_serve_a_world_without_the_runtime_compiler(tmp_path, monkeypatch, n):
     """`make aot` in miniature: the generic and the steady text of a world shape compiled ahead of time, put under GGRS_AOT_DIR by the
     names the library asks for, and the same world run with the run-time compiler treated as absent (GGRS_NO_HIPRTC=1): both kernels come
     from the shipped objects, the session is the oracle's bit for bit."""
     from bevy_ggrs_amd import _ffi
-    n, D = 123_456, 6                                                        # a shape no other test uses (the in-process module cache must not serve it)
+    D = 6                                                                    # (n: shapes no other test uses -- the in-process module cache must not serve them)
     dry = bg.World(n, max_depth=D + 1, flags=bg.GGRS_WORLD_LAYOUT_ONLY)
     cm.build_particles(dry)
     for steady in (False, True):
