@@ -67,6 +67,13 @@ class CustomSystemDesc(C.Structure):
                 ("iparam", C.c_int64 * 2), ("fparam", C.c_float * 4)]
 
 
+PEER_MAX_BINDINGS = 8
+
+
+class PeerBinding(C.Structure):
+    _fields_ = [("comp", C.c_uint32), ("word", C.c_uint32)]
+
+
 class SpawnSystemDesc(C.Structure):
     _fields_ = [("name", C.c_char_p), ("source", C.c_char_p), ("bundle_mask", C.c_uint64), ("payload_stride", C.c_uint32), ("n_bindings", C.c_uint32),
                 ("comp", C.c_uint32 * CUSTOM_MAX_BINDINGS), ("word", C.c_uint32 * CUSTOM_MAX_BINDINGS),
@@ -112,6 +119,7 @@ SIGNATURES = {
     "ggrs_hip_checksum_component_custom": (C.c_int, [_P, C.c_uint32, C.c_char_p]),
     "ggrs_hip_add_system": (C.c_int, [_P, C.POINTER(SystemDesc)]),
     "ggrs_hip_add_custom_system": (C.c_int, [_P, C.POINTER(CustomSystemDesc)]),
+    "ggrs_hip_add_custom_system_peers": (C.c_int, [_P, C.POINTER(CustomSystemDesc), C.POINTER(PeerBinding), C.c_uint32]),
     "ggrs_hip_register_component_strategy": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p]),
     "ggrs_hip_set_input_layout": (C.c_int, [_P, C.c_uint32, C.c_uint32]),
     "ggrs_hip_add_spawn_system": (C.c_int, [_P, C.POINTER(SpawnSystemDesc)]),

@@ -438,6 +438,7 @@ struct JitBatch {
 constexpr uint32_t LAZY_LIVE_STREAK = 8;
 inline bool lazy_live_allowed(const ggrs_world* w) {                 // (what a layout-only world -- `make aot` on a machine without a GPU -- can tell)
     if (!w->lazy_live_on || w->live_handed_out || w->has_nr || w->marks_possible || w->device_results_only || jit_dev_spawn(w)) return false;
+    if (world_has_peers(w)) return false;                            // peer bindings: the next group's publish reads what this one leaves -- every block is written (no deferred Saves either)
     for (uint8_t e : w->col_ext) if (e) return false;
     return true;
 }
@@ -752,6 +753,31 @@ inline bool group_aliases(const GgrsJitArgs& j, bool wrote_live) {
     for (uint32_t k = 1; k < j.n_saves && ok; ++k) for (uint32_t q = 0; q < k; ++q) ok = ok && (!j.save_dst[k] || j.save_dst[k] != j.save_dst[q]);
     return !ok;
 }
+// Peer bindings: the peer view is filled from the group's SOURCE block -- the ring slot the group loads, else the live block: the world at the start of the group's one
+// AdvanceWorld -- by a launch of its own on the world's stream ahead of the group's.  The kernel boundary is the only synchronisation.
+int publish_peers(ggrs_world* w, const Block& src, uint64_t len, GgrsJitArgs& j) {
+    ggrs_world::PeerView& pv = w->peer_view;
+    for (uint32_t k = 0; k < pv.n_cols; ++k) j.pv_col[k] = pv.d_col[k];
+    j.pv_vis = reinterpret_cast<const ggrs_u64*>(pv.d_vis); j.pv_len = len;
+    if (!len) return GGRS_OK;                                          // an empty world: every bounds test fails, nothing is read
+    PeerPubArgs a; memset(&a, 0, sizeof a);
+    a.src = src.ptr; a.vis = pv.d_vis; a.len = len; a.off_alive = w->off_alive;
+    a.n_pres = pv.n_pres; a.n_cols = pv.n_cols; a.n_units = (uint32_t)((len + 63) / 64);
+    uint64_t bytes_slot = 0;
+    for (uint32_t k = 0; k < pv.n_pres; ++k) a.off_present[k] = w->off_present[pv.pres_comp[k]];
+    for (uint32_t k = 0; k < pv.n_cols; ++k) {
+        const uint32_t cl = pv.col[k];
+        a.col_off[k] = w->col_off[cl]; a.ts[k] = w->col_ts[cl]; a.wb[k] = w->col_wb[cl]; a.dst[k] = pv.d_col[k];
+        bytes_slot += 2ull * w->col_wb[cl];                            // read from the block, written to the view
+    }
+    const uint64_t bytes = bytes_slot * len + (uint64_t)a.n_units * 8u * (pv.n_pres + 2u);
+    const double t0 = w->tl.on ? tl_now_us() : 0;
+    { ProfScope ps(w, GGRS_KERNEL_ADVANCE, bytes); hipLaunchKernelGGL(k_publish_peers, dim3((a.n_units + TPB / 64 - 1) / (TPB / 64)), dim3(TPB), 0, w->stream, a); }
+    HIPCHK(w, hipGetLastError());
+    if (w->tl.on) { w->tl.launch_us += tl_now_us() - t0; ++w->tl.n_launches; }
+    ++pv.publishes;
+    return GGRS_OK;
+}
 int run_request_groups_gen(ggrs_world* w, const ggrs_request* reqs, uint32_t n, uint64_t* checksums_out,
                            uint32_t res_base = 0, bool wait = true, uint32_t* n_saves_out = nullptr) {
     uint32_t i = 0, ns = 0; int rc = GGRS_OK;
@@ -793,7 +819,7 @@ int run_request_groups_gen(ggrs_world* w, const ggrs_request* reqs, uint32_t n, 
         j.nt = pol.nt; j.cached_saves = pol.cached_saves; j.nt_loads = pol.nt_loads; j.dp_s = pol.dp_s;
         const bool launch = j.n_ops || !j.src_is_live;
         // identical checksum-only groups (speculative branches) ride in one launch; a batch already fills the chip, so no roles
-        const bool batchable = dead && j.n_saves > 0 && !w->jit_marks && cover <= JIT_BATCH_MAX_SLOTS;
+        const bool batchable = dead && j.n_saves > 0 && !w->jit_marks && cover <= JIT_BATCH_MAX_SLOTS && !w->has_peers;   // (peer bindings: one view, published per launch)
         bool batched = false;
         if (batchable && batch.active) { GgrsJitArgs jb = j; jb.dp_s = 0; batched = batch.try_add(w, jb, g, res_base + ns); if (batched) batch.j.dp_s = 0; }
         if (!batched) {
@@ -805,6 +831,7 @@ int run_request_groups_gen(ggrs_world* w, const ggrs_request* reqs, uint32_t n, 
             // ---- fold route, launch, close, record the fold
             FoldPlan fold = fold_route_choose(w, j, g, n_cks, launch, wait, gs.spawn_req != nullptr);
             fold_route_setup(w, j, fold, g);
+            if (launch && w->has_peers && j.n_steps) { rc = publish_peers(w, *gs.src, j.len, j); if (rc) return rc; }
             if (launch) {
                 hipFunction_t fn = jit_spec_for(w, j);
                 if (!fn) fn = w->jit_fn;
@@ -885,6 +912,7 @@ int branch_marks_reserve(ggrs_world* w, uint64_t n) {
 // everything that can be checked before the prefix runs
 int validate_branch_step(ggrs_world* w, const ggrs_branch_step& st) {
     if (!w->gen_ok) return w->fail(GGRS_E_INVALID, "branch steps need the generated request-group kernel, which this world does not have: %s", w->jit_status.c_str());
+    if (w->has_peers) return w->fail(GGRS_E_INVALID, "branch steps are not available for worlds with peer bindings (a member runs several frames per launch, a peer read sees the start of ONE frame): use ggrs_hip_fanout_step");
     if (w->dev_spawn) return w->fail(GGRS_E_INVALID, "branch steps are not available for worlds whose systems spawn on the device (every launch is one cooperative grid): use ggrs_hip_fanout_step");
     if (st.n_branches == 0 || st.n_branches > BRANCH_MAX) return w->fail(GGRS_E_INVALID, "a branch step holds 1..%u branches, not %u", BRANCH_MAX, st.n_branches);
     const uint32_t S = (st.flags & GGRS_BRANCH_SAVE_LAST) ? st.n_frames : st.n_frames - 1;

@@ -30,6 +30,49 @@ void sp_release(ggrs_world* w) {
     if (w->d_sp_recs) (void)hipFree(w->d_sp_recs);
     w->d_sp_ctl = nullptr; w->d_sp_desc = nullptr; w->d_sp_recs = nullptr;
 }
+void peer_view_release(ggrs_world* w) {
+    if (w->peer_view.alloc) (void)hipFree(w->peer_view.alloc);
+    w->peer_view = ggrs_world::PeerView{};
+}
+// Peer bindings (ggrs_hip_add_custom_system_peers): what the first version refuses, and the registration-order rules under which the values at the START of the
+// frame are what Bevy's sequential schedule would show a second Query.  After build_layout (the systems' write sets); no device needed -- a GGRS_WORLD_LAYOUT_ONLY
+// world is checked by ggrs_hip_generated_kernel_source.
+int peers_validate(ggrs_world* w) {
+    if (!world_has_peers(w)) return GGRS_OK;
+    auto cname = [&](uint32_t c) { return w->comps[c].name.c_str(); };
+    auto can_despawn = [&](size_t k) {
+        const ggrs_system_desc& d = w->systems[k];
+        if (d.kind == GGRS_SYS_TTL_DESPAWN || d.kind == GGRS_SYS_SAT_SUB_DESPAWN) return true;
+        if (d.kind != GGRS_SYS_CUSTOM) return false;
+        const std::string& src = w->customs[d.comp[0]].source;
+        return source_has_token(src, "despawn") || source_has_token(src, "despawn_rollback") || source_has_token(src, "kill");
+    };
+    uint32_t cols[GGRS_PEER_MAX_COLUMNS];
+    const uint32_t n_cols = peer_cols(w, cols);
+    if (n_cols > GGRS_PEER_MAX_COLUMNS) return w->fail(GGRS_E_INVALID, "peer bindings: %u distinct peer-bound columns in this world, at most %d (GGRS_PEER_MAX_COLUMNS)", n_cols, GGRS_PEER_MAX_COLUMNS);
+    for (size_t i = 0; i < w->systems.size(); ++i) {
+        if (w->systems[i].kind != GGRS_SYS_CUSTOM) continue;
+        const ggrs_world::Custom& c = w->customs[w->systems[i].comp[0]];
+        for (uint32_t j = 0; j < c.n_peer; ++j) {
+            const Comp& pc = w->comps[c.pcomp[j]];
+            const uint32_t cl = pc.col_base + c.pword[j];
+            if (pc.s_n_words) return w->fail(GGRS_E_INVALID, "custom system '%s': peer binding %u reads word %u of component %u ('%s'), which has a Strategy: peer reads of such a component are not supported", c.name.c_str(), j, c.pword[j], c.pcomp[j], cname(c.pcomp[j]));
+            if (pc.no_rollback) return w->fail(GGRS_E_INVALID, "custom system '%s': peer binding %u reads word %u of component %u ('%s'), which is not registered for rollback (GGRS_COMP_NO_ROLLBACK): peer reads of such a component are not supported", c.name.c_str(), j, c.pword[j], c.pcomp[j], cname(c.pcomp[j]));
+            for (uint32_t b = 0; b < c.n_bind; ++b) if (w->comps[c.comp[b]].col_base + c.word[b] == cl)
+                return w->fail(GGRS_E_INVALID, "custom system '%s': word %u of component %u ('%s') is both its own binding %u and its peer binding %u: a system's own bindings and its peer bindings share no column", c.name.c_str(), c.pword[j], c.pcomp[j], cname(c.pcomp[j]), b, j);
+            for (size_t k = 0; k < i; ++k) for (uint32_t wc : w->sys_writes[k]) if (wc == cl)
+                return w->fail(GGRS_E_INVALID, "custom system '%s' (system %zu) peer-reads word %u of component %u ('%s'), which system %zu, registered before it, writes: every system with peer bindings is registered before every system that writes a column it peer-reads", c.name.c_str(), i, c.pword[j], c.pcomp[j], cname(c.pcomp[j]), k);
+        }
+        if (c.n_peer) for (size_t k = 0; k < i; ++k) if (can_despawn(k))
+            return w->fail(GGRS_E_INVALID, "custom system '%s' (system %zu) has peer bindings (first: word %u of component %u, '%s') and system %zu, registered before it, can despawn: every system with peer bindings is registered before every other system that can despawn", c.name.c_str(), i, c.pword[0], c.pcomp[0], cname(c.pcomp[0]), k);
+    }
+    const JitNeeds need = jit_needs(w);
+    if (need.marks) return w->fail(GGRS_E_INVALID, "peer bindings are not available in a world that keeps RollbackDespawned markers (a system that can call despawn_rollback(), or names the `kill` field)");
+    if (need.devspawn) return w->fail(GGRS_E_INVALID, "peer bindings are not available in a world that spawns on the device with e.spawn(n) (GGRS_SPAWN_PAYLOAD_PARENT)");
+    if (w->flags & (GGRS_WORLD_NO_GROUPS | GGRS_WORLD_UNFUSED)) return w->fail(GGRS_E_INVALID, "peer bindings need the generated request-group kernel, which a GGRS_WORLD_NO_GROUPS / GGRS_WORLD_UNFUSED world does not have");
+    if (!w->knobs.tick_jit) return w->fail(GGRS_E_INVALID, "peer bindings need the generated request-group kernel, which this world does not have: disabled (GGRS_TICK_JIT=0)");
+    return GGRS_OK;
+}
 int seal(ggrs_world* w) {
     if (w->layout_only) return w->fail(GGRS_E_NO_DEVICE, "GGRS_WORLD_LAYOUT_ONLY world: there is no device behind it");
     if (w->sealed) return GGRS_OK;
@@ -41,6 +84,7 @@ int seal(ggrs_world* w) {
     if (w->d_gen_parts) { (void)hipFree(w->d_gen_parts); w->d_gen_parts = nullptr; w->d_ff_rows[0] = w->d_ff_rows[1] = nullptr; }
     if (w->d_skip) { (void)hipFree(w->d_skip); w->d_skip = nullptr; }
     sp_release(w);
+    peer_view_release(w);
     if (w->h_results) { (void)hipHostFree(w->h_results); w->h_results = nullptr; w->d_results = nullptr; }
     if (w->h_stage) { (void)hipHostFree(w->h_stage); w->h_stage = nullptr; w->d_hstage = nullptr; }
     if (w->h_rows) { (void)hipHostFree(w->h_rows); w->h_rows = nullptr; w->d_rows = nullptr; }
@@ -103,6 +147,8 @@ int seal_impl(ggrs_world* w) {
     }
     HIPCHK(w, hipSetDevice(w->device));
     build_layout(w);
+    { const int prc = peers_validate(w); if (prc) return prc; }
+    w->has_peers = world_has_peers(w);
 
     // ---- checksum specs (the per-request k_checksum's view: one UnitDesc per hashed word)
     w->cks_comp.clear(); w->custom_hashers = false;
@@ -160,6 +206,8 @@ int seal_impl(ggrs_world* w) {
         return w->fail(GGRS_E_INVALID, "a user-written checksum hasher needs the generated request-group kernel, which this world does not have: %s", w->jit_status.c_str());
     if (w->has_strategy && !w->gen_ok)
         return w->fail(GGRS_E_INVALID, "a component under a Strategy (ggrs_hip_register_component_strategy) needs the generated request-group kernel, which this world does not have: %s", w->jit_status.c_str());
+    if (w->has_peers && !w->gen_ok)
+        return w->fail(GGRS_E_INVALID, "peer bindings (ggrs_hip_add_custom_system_peers) need the generated request-group kernel, which this world does not have: %s", w->jit_status.c_str());
     for (auto& sd : w->systems) if (sd.kind == GGRS_SYS_SPAWN_CUSTOM && !(w->gen_ok && w->jit_spawn_sys >= 0))
         return w->fail(GGRS_E_INVALID, "a user-written spawn system (ggrs_hip_add_spawn_system) runs inside the generated request-group kernel, which this world does not have "
                                        "(or the schedule holds a second spawn system): %s", w->jit_status.c_str());
@@ -252,6 +300,20 @@ int seal_impl(ggrs_world* w) {
         // launch that owns it has written it.  Tags count up per world, so memory recycled from an earlier world of the process could (the fuzz under
         // GGRS_FOLD_FORWARD_MIN_WGS=0 found it: stale cells of the previous test's world, same tags) -- the buffers start zeroed (no tag is 0)
         else HIPCHK(w, hipMemsetAsync(w->d_ff_rows[0], 0, 2 * ff_bytes, w->stream));
+    }
+    if (w->has_peers) {
+        // the peer view: one linear array of cap_pad words per distinct peer-bound column, then the visibility words (zeroed: nothing is visible before the first publish)
+        ggrs_world::PeerView& pv = w->peer_view;
+        pv = ggrs_world::PeerView{};
+        pv.n_cols = peer_cols(w, pv.col, &pv.n_pres, pv.pres_comp);
+        uint64_t off[GGRS_PEER_MAX_COLUMNS], bytes = 0;
+        for (uint32_t k = 0; k < pv.n_cols; ++k) { off[k] = bytes; bytes += align_up(w->cap_pad * (uint64_t)w->col_wb[pv.col[k]], ALIGN); }
+        const uint64_t vis_off = bytes, vis_bytes = align_up(w->cap_pad / 8, ALIGN); bytes += vis_bytes;
+        HIPCHK(w, hipMalloc((void**)&pv.alloc, bytes));
+        for (uint32_t k = 0; k < pv.n_cols; ++k) pv.d_col[k] = pv.alloc + off[k];
+        pv.d_vis = reinterpret_cast<uint64_t*>(pv.alloc + vis_off);
+        if (w->knobs.debug_poison) HIPCHK(w, hipMemsetAsync(pv.alloc, 0xA5, bytes, w->stream));
+        HIPCHK(w, hipMemsetAsync(pv.d_vis, 0, vis_bytes, w->stream));
     }
     if (w->vtags) { HIPCHK(w, hipMalloc((void**)&w->d_skip, 8)); HIPCHK(w, hipMemsetAsync(w->d_skip, 0, 8, w->stream)); }
     if (w->dev_spawn) {

@@ -161,8 +161,20 @@ struct ggrs_world {
         hipModule_t mod = nullptr; hipFunction_t fn = nullptr;
         uint32_t n_bind = 0, comp[GGRS_CUSTOM_MAX_BINDINGS] = {}, word[GGRS_CUSTOM_MAX_BINDINGS] = {};
         uint32_t n_pres = 0, pres_comp[GGRS_CUSTOM_MAX_BINDINGS] = {};
+        // peer bindings (ggrs_hip_add_custom_system_peers): words of OTHER entities the system reads through e.peer(slot), as they were at the start of the frame
+        uint32_t n_peer = 0, pcomp[GGRS_PEER_MAX_BINDINGS] = {}, pword[GGRS_PEER_MAX_BINDINGS] = {};
     };
     std::vector<Custom> customs;
+    // THE PEER VIEW of a world with peer bindings (allocated at seal, filled by k_publish_peers ahead of every request group that holds an AdvanceWorld): one LINEAR
+    // array of cap_pad words per distinct peer-bound column (a gather address is base + slot x word bytes; state blocks are tile-major) and one visibility bit per
+    // slot: alive AND every peer-bound component present.  The tick launch may rewrite its source block in place, so it never gathers from a block it writes
+    struct PeerView {
+        uint32_t n_cols = 0, col[GGRS_PEER_MAX_COLUMNS] = {};          // the distinct peer-bound columns, in order of first use
+        uint32_t n_pres = 0, pres_comp[GGRS_PEER_MAX_COLUMNS] = {};    // the components they belong to
+        uint8_t* d_col[GGRS_PEER_MAX_COLUMNS] = {}; uint64_t* d_vis = nullptr; uint8_t* alloc = nullptr;
+        uint64_t publishes = 0;
+    } peer_view;
+    bool has_peers = false;              // some system has peer bindings (set at seal: peer_cols)
     struct SpawnSys {                    // GGRS_SYS_SPAWN_CUSTOM: a user-written spawner (ggrs_hip_add_spawn_system; systems[i].comp[0] indexes this)
         std::string name, source;
         uint32_t n_bind = 0, comp[GGRS_CUSTOM_MAX_BINDINGS] = {}, word[GGRS_CUSTOM_MAX_BINDINGS] = {};

@@ -600,6 +600,42 @@ __global__ __launch_bounds__(TPB) void k_clear_gone(uint8_t* live, const uint64_
     }
 }
 
+// THE PEER VIEW (ggrs_hip_add_custom_system_peers; host_world.hpp ggrs_world::PeerView).  Ahead of every request group that holds an AdvanceWorld, the peer-bound
+// columns of the group's SOURCE block (tile-major) are copied into linear arrays, and the visibility words -- alive AND every peer-bound component present, cut at the
+// source's len -- are built by plain word ANDs.  One 64-slot unit per wave: a lane moves one word per column (coalesced on both sides), lane 0 writes the unit's
+// visibility word.  The tick launch that follows gathers from these arrays only: it may rewrite its source block in place.
+constexpr int PEER_MAX_COLS = GGRS_PEER_MAX_COLUMNS;
+struct PeerPubArgs {
+    const uint8_t* src; uint64_t* vis; uint64_t len, off_alive;
+    uint64_t off_present[PEER_MAX_COLS], col_off[PEER_MAX_COLS];
+    uint8_t* dst[PEER_MAX_COLS];
+    uint32_t ts[PEER_MAX_COLS], wb[PEER_MAX_COLS];
+    uint32_t n_pres, n_cols, n_units;
+};
+__global__ __launch_bounds__(TPB) void k_publish_peers(PeerPubArgs a) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t u = blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);             // this wave's 64-slot unit == its mask word
+    if (u >= a.n_units) return;
+    const uint64_t e = (uint64_t)u * 64u + lane;
+    if (lane == 0) {
+        uint64_t v = *reinterpret_cast<const uint64_t*>(a.src + a.off_alive + (uint64_t)u * 8u);
+        for (uint32_t k = 0; k < a.n_pres; ++k) v &= *reinterpret_cast<const uint64_t*>(a.src + a.off_present[k] + (uint64_t)u * 8u);
+        const uint64_t lo = (uint64_t)u * 64u;                                   // the source's len: slots at or beyond it are not entities of this frame
+        v &= a.len >= lo + 64u ? ~0ull : (a.len > lo ? (1ull << (a.len - lo)) - 1ull : 0ull);
+        a.vis[u] = v;
+    }
+    if (e >= a.len) return;
+    for (uint32_t c = 0; c < a.n_cols; ++c) {
+        const uint8_t* p = a.src + col_at(a.col_off[c], a.ts[c], a.wb[c], e);
+        switch (a.wb[c]) {
+        case 8: reinterpret_cast<uint64_t*>(a.dst[c])[e] = *reinterpret_cast<const uint64_t*>(p); break;
+        case 4: reinterpret_cast<uint32_t*>(a.dst[c])[e] = *reinterpret_cast<const uint32_t*>(p); break;
+        case 2: reinterpret_cast<uint16_t*>(a.dst[c])[e] = *reinterpret_cast<const uint16_t*>(p); break;
+        default: a.dst[c][e] = *p; break;
+        }
+    }
+}
+
 // System-scope release + acquire on whatever CU / XCD the wave lands on: `buffer_wbl2 sc0 sc1` writes the XCD's dirty L2 lines back,
 // `buffer_inv sc0 sc1` drops its clean ones.  2048 single-wave workgroups cover all 8 XCDs (workgroup b lands on XCD b % 8).
 __global__ void k_flush_l2() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, ""); }

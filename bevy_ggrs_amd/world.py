@@ -296,11 +296,13 @@ class World(WorldBase):
         self._comps = []
         self.capacity = capacity
 
-    def add_custom_system(self, source: str, bindings: Sequence[tuple], iparam=(), fparam=(), name: str = "custom"):
+    def add_custom_system(self, source: str, bindings: Sequence[tuple], iparam=(), fparam=(), name: str = "custom", peers: Sequence[tuple] = ()):
         """add_systems(GgrsSchedule, <your system>) for a per-entity system written in HIP C++ (ggrs_hip_add_custom_system):
         `source` defines `__device__ void ggrs_system(GgrsEntity& e, const GgrsFrame& f)`, `bindings` = [(comp, word), ..]
         are the words it sees as e.f32(i)/e.u32(i)/e.i32(i)/e.u64(i).  Compiled for gfx950 when added; a compile error raises
-        GgrsHipError carrying the compiler log."""
+        GgrsHipError carrying the compiler log.
+        `peers` = [(comp, word), ..] (ggrs_hip_add_custom_system_peers): the words of OTHER entities the system may read, as they were at
+        the start of the frame -- `GgrsPeer p = e.peer(slot); if (p.ok()) .. p.f32(j) ..` with j indexing this list."""
         d = _ffi.CustomSystemDesc()
         d.name, d.source, d.n_bindings = name.encode(), source.encode(), len(bindings)
         if len(bindings) > _ffi.CUSTOM_MAX_BINDINGS:
@@ -308,7 +310,14 @@ class World(WorldBase):
         for i, (c, w) in enumerate(bindings): d.comp[i], d.word[i] = c, w
         for i, v in enumerate(iparam): d.iparam[i] = v
         for i, v in enumerate(fparam): d.fparam[i] = v
-        self._check(self._lib.ggrs_hip_add_custom_system(self._p, C.byref(d)))
+        if not peers:
+            self._check(self._lib.ggrs_hip_add_custom_system(self._p, C.byref(d)))
+            return
+        if len(peers) > _ffi.PEER_MAX_BINDINGS:
+            raise ValueError(f"at most {_ffi.PEER_MAX_BINDINGS} peer bindings")
+        pb = (_ffi.PeerBinding * len(peers))()
+        for j, (c, w) in enumerate(peers): pb[j].comp, pb[j].word = c, w
+        self._check(self._lib.ggrs_hip_add_custom_system_peers(self._p, C.byref(d), pb, len(peers)))
 
     def add_spawn_system(self, source: str, bundle: Sequence[int], bindings: Sequence[tuple] = (), payload_stride: int = 0, iparam=(), fparam=(), name: str = "spawn"):
         """add_systems(GgrsSchedule, <a system that spawns Rollback entities>) (ggrs_hip_add_spawn_system): `source` defines

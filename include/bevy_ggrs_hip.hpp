@@ -323,13 +323,17 @@ struct KernelSystem {                  // one system of the GgrsSchedule, execut
 
 // A user-written per-entity system: HIP C++ source defining `__device__ void ggrs_system(GgrsEntity&, const GgrsFrame&)`,
 // compiled for gfx950 when it is added (ggrs_hip_add_custom_system).  bind<T>(word) appends the next e.f32(i)/e.u32(i)/e.u64(i).
+// peer<T>(word) appends the next PEER binding (ggrs_hip_add_custom_system_peers): a word of OTHER entities the system may read -- a second Query -- as
+// `GgrsPeer p = e.peer(slot); if (p.ok()) .. p.f32(j) ..`, the value at the start of the frame.
 struct CustomKernelSystem {
     std::string name, source;
     std::vector<std::pair<std::string, uint32_t>> bindings;      // (component name, word)
+    std::vector<std::pair<std::string, uint32_t>> peers;         // (component name, word) of other entities, read through e.peer(slot)
     int64_t iparam[2] = {0, 0};
     float fparam[4] = {0, 0, 0, 0};
     CustomKernelSystem(std::string n, std::string src) : name(std::move(n)), source(std::move(src)) {}
     template <class T> CustomKernelSystem& bind(uint32_t word) { bindings.emplace_back(HipComponent<T>::name, word); return *this; }
+    template <class T> CustomKernelSystem& peer(uint32_t word) { peers.emplace_back(HipComponent<T>::name, word); return *this; }
 };
 
 // add_systems(GgrsSchedule, <a system that spawns Rollback entities>): `commands.spawn((bundle.., Rollback))` (snapshot/rollback.rs:45-59) as HIP C++ source defining
@@ -403,6 +407,7 @@ struct HipBackend {
     int checksum_component_custom(uint32_t c, const char* source) { return ggrs_hip_checksum_component_custom(w, c, source); }
     int add_system(const ggrs_system_desc* d) { return ggrs_hip_add_system(w, d); }
     int add_custom_system(const ggrs_custom_system_desc* d) { return ggrs_hip_add_custom_system(w, d); }
+    int add_custom_system_peers(const ggrs_custom_system_desc* d, const ggrs_peer_binding* peers, uint32_t n_peers) { return ggrs_hip_add_custom_system_peers(w, d, peers, n_peers); }
     int add_spawn_system(const ggrs_spawn_system_desc* d) { return ggrs_hip_add_spawn_system(w, d); }
     int register_component_strategy(uint32_t c, uint32_t stored_word_bytes, uint32_t stored_n_words, const char* source) { return ggrs_hip_register_component_strategy(w, c, stored_word_bytes, stored_n_words, source); }
     int set_frame_rate(uint64_t fps) { return ggrs_hip_set_frame_rate(w, fps); }
@@ -541,7 +546,10 @@ class App {
         for (size_t k = 0; k < s.bindings.size(); ++k) { d.comp[k] = comp_id(s.bindings[k].first); d.word[k] = s.bindings[k].second; }
         for (int k = 0; k < 4; ++k) d.fparam[k] = s.fparam[k];
         d.iparam[0] = s.iparam[0]; d.iparam[1] = s.iparam[1];
-        check(be_.add_custom_system(&d));
+        if (s.peers.size() > GGRS_PEER_MAX_BINDINGS) throw std::invalid_argument("a custom kernel system has at most 8 peer bindings");
+        ggrs_peer_binding pb[GGRS_PEER_MAX_BINDINGS];
+        for (size_t k = 0; k < s.peers.size(); ++k) { pb[k].comp = comp_id(s.peers[k].first); pb[k].word = s.peers[k].second; }
+        check(s.peers.empty() ? be_.add_custom_system(&d) : be_.add_custom_system_peers(&d, pb, (uint32_t)s.peers.size()));
         return *this;
     }
     // host-side stand-in for the rolled-back ParticleRng resource (particles.rs:125,201): must be a

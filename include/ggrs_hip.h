@@ -186,7 +186,8 @@ int ggrs_hip_add_system(ggrs_world* w, const ggrs_system_desc* desc);
  * The system runs for every live entity that has all bound components, in registration order with the other systems;
  * despawns take effect before the next system, as with the built-in kinds.  The code is compiled with -ffp-contract=off
  * and correctly rounded fp32 divide/sqrt: what the source says is what runs, bit for bit, on every rank and every replay
- * -- determinism is the author's contract exactly as it is for a Bevy system (no atomics, no cross-entity reads).
+ * -- determinism is the author's contract exactly as it is for a Bevy system (no atomics; another entity is read only through
+ * e.peer(slot), ggrs_hip_add_custom_system_peers below).
  * The system is inlined into the request-group kernel the library generates for the world (and compiled as a kernel of its own for the
  * one-launch-per-request path).  A compile error returns GGRS_E_INVALID with the compiler log in ggrs_hip_last_error. */
 #define GGRS_SYS_CUSTOM 7u
@@ -202,6 +203,46 @@ typedef struct {
     float    fparam[4];
 } ggrs_custom_system_desc;
 int ggrs_hip_add_custom_system(ggrs_world* w, const ggrs_custom_system_desc* desc);
+
+/* CROSS-ENTITY READS (peer bindings).  In the reference any system may take a second Query and look another entity up: a child follows its
+ * ChildOf parent (tests/hierarchy.rs), a projectile homes on a target, a unit reads its squad leader.  An entity reference here is a stable slot in
+ * an 8-byte word; a system registered through this entry point may FOLLOW one.  peers[j] = {comp, word} names peer binding j (at most
+ * GGRS_PEER_MAX_BINDINGS); with n_peers == 0 the call behaves as ggrs_hip_add_custom_system.  Inside ggrs_system(GgrsEntity& e, const GgrsFrame& f):
+ *
+ *     GgrsPeer p = e.peer(slot);                              slot: any ggrs_u64, typically a link word of e
+ *     p.ok()                                                  see below
+ *     p.f32(j) / p.u32(j) / p.i32(j) / p.u64(j) / p.u16(j) / p.u8(j)   peer binding j of the entity at `slot`; 0 when !ok()
+ *
+ *   - A peer read returns the value the word had at the start of the frame, before any system of this AdvanceWorld ran.
+ *   - ok() is true when all of these hold: slot < RollbackOrdered::len at the start of the frame; the entity was alive then; it had every
+ *     peer-bound component then.
+ *   - Entities spawned in this frame are not visible.
+ *   - An entity despawned in this frame, by any system including the reader itself, is still visible this frame.  This matches Bevy's deferred
+ *     Commands within one system.
+ *
+ * Seal refuses the world (GGRS_E_INVALID, the message names the system and the column) unless the rules below hold, so that start-of-frame values
+ * equal what Bevy's sequential schedule would show:
+ *   - every system with peer bindings is registered before every system that writes a column it peer-reads;
+ *   - every system with peer bindings is registered before every other system that can despawn;
+ *   - a system's own bindings and its peer bindings share no column.
+ * This version also refuses, each with GGRS_E_INVALID and a message:
+ *   - a peer-bound component that has a Strategy (ggrs_hip_register_component_strategy);
+ *   - a peer-bound component that is non-rollback (GGRS_COMP_NO_ROLLBACK);
+ *   - a world that also keeps RollbackDespawned markers (a system that can call despawn_rollback());
+ *   - a world that also spawns on the device with e.spawn(n);
+ *   - a world without the generated kernel (GGRS_WORLD_NO_GROUPS, GGRS_WORLD_UNFUSED, or no compiler and no shipped object);
+ *   - more than GGRS_PEER_MAX_COLUMNS distinct peer-bound columns in one world;
+ *   - ggrs_hip_fanout_step_branches on such a world, since members run several frames per launch.  The request-list form ggrs_hip_fanout_step keeps working.
+ * Host-decided spawns, built-in systems, custom hashers, any input layout and 1/2/4/8-byte words are all allowed.
+ * How it runs: at seal the world gets a PEER VIEW -- one linear array per distinct peer-bound column, one visibility bit per slot (alive AND every
+ * peer-bound component present) -- which a small launch fills from the request group's source block ahead of every group that holds an AdvanceWorld;
+ * such a world's groups hold one AdvanceWorld each, and its live block and ring slots are written by every group (no lazy live block, no deferred Saves).
+ * The only synchronisation is the kernel boundary. */
+typedef struct { uint32_t comp; uint32_t word; } ggrs_peer_binding;   /* peer binding j = word `word` of component `comp` */
+#define GGRS_PEER_MAX_BINDINGS 8
+#define GGRS_PEER_MAX_COLUMNS 16
+int ggrs_hip_add_custom_system_peers(ggrs_world* w, const ggrs_custom_system_desc* desc,
+                                     const ggrs_peer_binding* peers, uint32_t n_peers);
 
 /* ComponentSnapshotPlugin<S: Strategy> (snapshot/strategy.rs:22-40, component_snapshot.rs:42-63): what a snapshot HOLDS of a component is
  * S::Stored, produced by S::store and turned back by S::load / S::update -- CopyStrategy / CloneStrategy (Stored == the component, bitwise for
@@ -566,7 +607,7 @@ int ggrs_hip_host_timeline(ggrs_world* w, int enable, double* us_out, uint64_t* 
  * Introspection: which kernel serves this world's request lists right now and why, what kind of arena
  * it lives on, whether the run-time compiler (libhiprtc.so, dlopen'ed) is available.  `key=value` lines,
  * NUL-terminated; *needed = bytes incl. the NUL, min(cap, *needed) are copied.  Keys: sealed, arena,
- * arena_bytes, hiprtc, generated_kernel, generated_kernel_origin, request_group_kernel, checksum_fold, kernarg_bytes, group_caps, specialised_kernel, slots_covered, row_versions.
+ * arena_bytes, hiprtc, generated_kernel, generated_kernel_origin, request_group_kernel, checksum_fold, kernarg_bytes, group_caps, specialised_kernel, slots_covered, row_versions, peer_view (worlds with peer bindings).
  * ------------------------------------------------------------------------------------------- */
 int ggrs_hip_world_kernel_info(ggrs_world* w, char* buf, uint64_t cap, uint64_t* needed);
 

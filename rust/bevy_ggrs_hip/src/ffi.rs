@@ -97,6 +97,16 @@ pub struct ggrs_custom_system_desc {
     pub fparam: [f32; 4],
 }
 
+/// One peer binding of `ggrs_hip_add_custom_system_peers`: a word of OTHER entities a system reads through `e.peer(slot)`.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct ggrs_peer_binding {
+    pub comp: u32,
+    pub word: u32,
+}
+pub const GGRS_PEER_MAX_BINDINGS: usize = 8;
+pub const GGRS_PEER_MAX_COLUMNS: usize = 16;
+
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct ggrs_spawn_system_desc {
@@ -179,6 +189,7 @@ unsafe extern "C" {
     pub fn ggrs_hip_checksum_component_custom(w: *mut ggrs_world, comp_id: u32, source: *const c_char) -> c_int;
     pub fn ggrs_hip_add_system(w: *mut ggrs_world, desc: *const ggrs_system_desc) -> c_int;
     pub fn ggrs_hip_add_custom_system(w: *mut ggrs_world, desc: *const ggrs_custom_system_desc) -> c_int;
+    pub fn ggrs_hip_add_custom_system_peers(w: *mut ggrs_world, desc: *const ggrs_custom_system_desc, peers: *const ggrs_peer_binding, n_peers: u32) -> c_int;
     pub fn ggrs_hip_register_component_strategy(w: *mut ggrs_world, comp_id: u32, stored_word_bytes: u32, stored_n_words: u32, source: *const c_char) -> c_int;
     pub fn ggrs_hip_set_input_layout(w: *mut ggrs_world, input_bytes: u32, max_players: u32) -> c_int;
     pub fn ggrs_hip_add_spawn_system(w: *mut ggrs_world, desc: *const ggrs_spawn_system_desc) -> c_int;

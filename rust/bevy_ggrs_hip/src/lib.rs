@@ -456,16 +456,25 @@ pub struct KernelSystem {
 /// (include/ggrs_hip.h `ggrs_hip_add_custom_system`): the open counterpart of [`KernelSystem`] for systems of the shape
 /// `Query<(&mut A, &mut B, ..), With<Rollback>>` + `Commands::despawn`.  `source` defines
 /// `__device__ void ggrs_system(GgrsEntity& e, const GgrsFrame& f)`; binding `i` is seen as `e.f32(i)` / `e.u32(i)` / `e.u64(i)`.
+/// A second `Query` over OTHER entities -- a child following its `ChildOf` parent, a projectile homing on a target -- is a list of PEER
+/// bindings (`ggrs_hip_add_custom_system_peers`): `GgrsPeer p = e.peer(slot); if (p.ok()) { .. p.f32(j) .. }` reads peer binding `j` of the
+/// entity at RollbackOrdered index `slot` as it was at the start of the frame.
 pub struct CustomKernelSystem {
     pub name: &'static str,
     pub source: String,
     pub bindings: Vec<(fn(&HipWorld) -> u32, u32)>,
+    pub peers: Vec<(fn(&HipWorld) -> u32, u32)>,
     pub iparam: [i64; 2],
     pub fparam: [f32; 4],
 }
 impl CustomKernelSystem {
     pub fn new(name: &'static str, source: impl Into<String>) -> Self {
-        CustomKernelSystem { name, source: source.into(), bindings: Vec::new(), iparam: [0; 2], fparam: [0.0; 4] }
+        CustomKernelSystem { name, source: source.into(), bindings: Vec::new(), peers: Vec::new(), iparam: [0; 2], fparam: [0.0; 4] }
+    }
+    /// Bind word `word` of component `T` of OTHER entities as the next peer binding `p.*(j)`.
+    pub fn peer<T: HipComponent>(mut self, word: u32) -> Self {
+        self.peers.push((HipWorld::comp_id::<T>, word));
+        self
     }
     /// Bind word `word` of component `T` as the next `e.*(i)`.
     pub fn bind<T: HipComponent>(mut self, word: u32) -> Self {
@@ -693,7 +702,13 @@ impl RollbackApp for App {
             desc.comp[k] = comp(&w);
             desc.word[k] = *word;
         }
-        let rc = unsafe { ffi::ggrs_hip_add_custom_system(w.raw, &desc) };
+        assert!(system.peers.len() <= ffi::GGRS_PEER_MAX_BINDINGS, "a custom kernel system has at most 8 peer bindings");
+        let peers: Vec<ffi::ggrs_peer_binding> = system.peers.iter().map(|(comp, word)| ffi::ggrs_peer_binding { comp: comp(&w), word: *word }).collect();
+        let rc = if peers.is_empty() {
+            unsafe { ffi::ggrs_hip_add_custom_system(w.raw, &desc) }
+        } else {
+            unsafe { ffi::ggrs_hip_add_custom_system_peers(w.raw, &desc, peers.as_ptr(), peers.len() as u32) }
+        };
         w.check(rc); // a compile error panics with the hiprtc log (ggrs_hip_last_error), like a system that fails to build
         self
     }
