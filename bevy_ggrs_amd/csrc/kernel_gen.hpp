@@ -199,19 +199,231 @@ int hiprtc_build(ggrs_world* w, const std::string& src, const char* what, const 
 // For every world the library WRITES the fused kernel at seal -- one
 // slot per lane, every registered word of the slot in a named register, the systems (built-in kinds and the user's sources
 // alike) inlined in registration order, every checksum spec (word lists and user-written hashers) unrolled -- and compiles
-// it with hiprtc.  A wave owns one 64-slot unit (== one 64-bit mask word); two forms of the same body:
-//   * per-tile grid (256-thread workgroups, one unit per wave): worlds that live in L2 / the Infinity Cache -- depth-parallel
-//     roles (blockIdx.y), batches of identical checksum-only groups (blockIdx.z), one row of partials per workgroup folded by
-//     the host or by k_gen_finalize;
-//   * PERSISTENT grid (1024-thread workgroups, as many as the device holds, a wave walks units u = wave id, += waves of the
-//     grid): HBM-sized worlds -- the partials stay in LDS across the walk and tick_fold (device_prelude.hpp: one row + one
-//     ticket per workgroup, the last to arrive folds) writes every Checksum(u128): ONE launch per request group.
+// it with hiprtc.  A wave owns one 64-slot unit (== one 64-bit mask word).  ONE form, per tile: 256-thread workgroups, one
+// 256-slot tile each, one unit per wave, one row of checksum partials per workgroup.  A workgroup's place in the grid says what it does:
+//   * ROLES (blockIdx.y, a.dp_s): depth-parallel -- each role writes its share of the group's Saves, the last one the live block;
+//   * BATCHES (blockIdx.z, a.mtab): request groups of one op shape off one source block -- speculative branches --, member z's
+//     differences in its record in device memory;
+//   * FOLD-FORWARD (the first a.ff_blocks workgroups own no tile): they fold the partial rows the PREVIOUS launch of the stream left
+//     (or, self-fold, this launch's own) and hand {value, tag} cells to the host, which finishes the Checksum(u128)s;
+//   * the STREAMED form of a world that spawns on the device (need.devstream): a workgroup's tile is the TICKET it takes first thing
+//     instead of a function of blockIdx.x, children are numbered by a decoupled look-back, and there is no fold-forward role.
+// The generator is JitGen below: what it derives once from the world, then one member function per section of the text, in the
+// order of the text (jit_source is the list).  jit_covers says which worlds it takes, before a byte is written.
 // The SeaHash / box_game / fold code is device_prelude.hpp, the text the static kernels are compiled from.
 static const char kJitPrelude[] =
 #define GGRS_SHARED_CODE(...) #__VA_ARGS__
 #include "device_prelude.hpp"
 #undef GGRS_SHARED_CODE
     ;
+// ---- device text of worlds that spawn on the device: no format argument, pasted as it stands ----
+static const char kJitSpMailbox[] =
+    "// SPAWNS DECIDED ON THE DEVICE: the workgroups of a COOPERATIVE launch (all resident) meet through mailbox words {epoch:32 | value:32}, written and polled\n"
+    "// as relaxed agent-scope atomics (sc1: through to where every XCD reads them).  The value travels INSIDE the word it is waited on, so no rendezvous needs a\n"
+    "// release/acquire pair -- on gfx950 those are a writeback / an invalidate of a whole L2 each (measured: ~100 us per barrier with an acquire in the poll loop).\n"
+    "// Bounded: a second of wall clock, then the launch reports an error instead of hanging the device\n"
+    "__device__ __forceinline__ void sp_post(ggrs_u64* p, ggrs_u32 ep, ggrs_u32 v) { __hip_atomic_store(p, ((ggrs_u64)ep << 32) | v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }\n"
+    "__device__ __forceinline__ bool sp_await(ggrs_u64* p, ggrs_u32 ep, ggrs_u32& v, unsigned long long t0_) {\n"
+    "    for (;;) {\n"
+    "        const ggrs_u64 x_ = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
+    "        if ((ggrs_u32)(x_ >> 32) == ep) { v = (ggrs_u32)x_; return true; }\n"
+    "        if (wall_clock64() - t0_ > 100000000ull) return false;\n"
+    "        __builtin_amdgcn_s_sleep(1);\n"
+    "    }\n"
+    "}\n";
+static const char kJitSpStreamed[] =
+    "// STREAMED device spawns: the grid need not be resident as a whole.  PROGRESS RULE: a workgroup only ever waits on a strictly lower ticket, or on its own\n"
+    "// workgroup behind a __syncthreads() that follows the writes.  A workgroup's tile IS its ticket (taken first thing), so the lowest unfinished ticket never\n"
+    "// waits on anyone that has not started; the look-back, the end-of-world tile's descriptor and a parent's child records all sit at lower or equal tiles.\n"
+    "// Every wait is bounded by the wall clock, as sp_await.  A descriptor {epoch:32 | inclusive:1 | count:31}: a tile posts its own count, looks back\n"
+    "// (64 predecessors per probe) until it meets an inclusive prefix, then posts its own inclusive prefix\n"
+    "__device__ __forceinline__ bool sp_await_inc(ggrs_u64* p, ggrs_u32 ep, ggrs_u32& v, unsigned long long t0_) {\n"
+    "    for (;;) {\n"
+    "        const ggrs_u64 x_ = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
+    "        if ((ggrs_u32)(x_ >> 32) == ep && (x_ & 0x80000000ull)) { v = (ggrs_u32)x_ & 0x7FFFFFFFu; return true; }\n"
+    "        if (wall_clock64() - t0_ > 100000000ull) return false;\n"
+    "        __builtin_amdgcn_s_sleep(1);\n"
+    "    }\n"
+    "}\n"
+    "// the grid's last tile, before it writes RollbackOrdered::len into the block every tile read its starting len from (a group run in place): every other tile\n"
+    "// has posted that it read it (one word per tile, a lower ticket each; wave-parallel, 64 per probe)\n"
+    "__device__ __forceinline__ bool sp_gate(ggrs_u64* f, uint32_t n, ggrs_u32 ep, uint32_t lane) {\n"
+    "    const unsigned long long t0_ = wall_clock64();\n"
+    "    for (uint32_t b_ = 0; b_ < n; b_ += 64u) { uint32_t v_ = 0; const bool g_ = b_ + lane >= n || sp_await(f + b_ + lane, ep, v_, t0_); if (__ballot(!g_) != 0ull) return false; }\n"
+    "    return true;\n"
+    "}\n";
+// the exclusive scan of the lanes' e.spawn(n) counts over the wave and the workgroup (LDS): how both forms begin a step's spawn section
+static const char kJitSpScan[] =
+    "                uint32_t inc_ = spn_0;                                                 // inclusive scan over the wave's 64 lanes\n"
+    "                for (int o_ = 1; o_ < 64; o_ <<= 1) { const uint32_t up_ = __shfl_up(inc_, o_, 64); if ((int)lane >= o_) inc_ += up_; }\n"
+    "                const uint32_t wtot_ = (uint32_t)__builtin_amdgcn_readlane((int)inc_, 63);\n"
+    "                __syncthreads();                                                       // (s_sp of the previous step has been read by everyone)\n"
+    "                if (lane == 0) s_sp[wave] = wtot_;\n"
+    "                __syncthreads();\n"
+    "                uint32_t wg_excl_ = 0, wg_tot_ = 0;\n"
+    "                for (uint32_t q_ = 0; q_ < 4u; ++q_) { const uint32_t v_ = (uint32_t)s_sp[q_]; wg_tot_ += v_; if (q_ < wave) wg_excl_ += v_; }\n";
+// How many, and whose -- streamed: the same exclusive scan over wave and workgroup; then, per step, a decoupled look-back over the tiles' descriptors
+// (slot order == RollbackOrdered order, as in the resident form).  A parent tile reserves one record per child from the pool and writes the parent's
+// bound words, then {epoch, k}, into each; a lane whose slot falls among the step's new rows finds its parent's tile by the inclusive prefixes (a binary
+// search over tiles at or below the end of the world) and polls its own record.  The end-of-world tile's inclusive prefix is the step's total: tiles
+// above it read that one descriptor.  Children beyond the capacity: those tiles ignore the records (nothing spawns), the end-of-world tile tells the host
+static const char kJitSpLookBack[] =
+    "                const unsigned long long tb_ = wall_clock64();\n"
+    "                const uint32_t own_ = (uint32_t)(cur_len ? (cur_len - 1u) >> 8 : 0u);   // the end of the world (exact where trk_)\n"
+    "                if (tile < own_) trk_ = false;\n"
+    "                const bool above_ = trk_ && tile > own_;                               // no live slot: waits for the total instead of posting\n"
+    "                if (wave == 0u) {\n"
+    "                    bool ok_ = true; uint64_t exc_ = 0; uint32_t tot_ = 0;\n"
+    "                    if (!above_) {\n"
+    "                        if (lane == 0) sp_post(dsc_ + tile, ep_, min(wg_tot_, 0x7FFFFFFFu));      // the aggregate: what this tile adds\n"
+    "                        for (uint32_t hi_ = tile; hi_ > 0u; hi_ = hi_ > 64u ? hi_ - 64u : 0u) {   // look back: lane l reads tile hi_ - 1 - l (all lower tickets)\n"
+    "                            const bool in_ = lane < hi_;\n"
+    "                            uint32_t v_ = 0;\n"
+    "                            const bool got_ = !in_ || sp_await(dsc_ + (hi_ - 1u - lane), ep_, v_, tb_);\n"
+    "                            if (__ballot(!got_) != 0ull) { ok_ = false; break; }\n"
+    "                            const uint64_t incm_ = __ballot(in_ && (v_ & 0x80000000u));     // the nearest inclusive prefix ends the walk\n"
+    "                            const uint32_t stop_ = incm_ ? (uint32_t)__builtin_ctzll(incm_) : 63u;\n"
+    "                            uint64_t c_ = (in_ && lane <= stop_) ? (uint64_t)(v_ & 0x7FFFFFFFu) : 0ull;\n"
+    "                            for (int o_ = 32; o_ > 0; o_ >>= 1) c_ += __shfl_xor(c_, o_, 64);\n"
+    "                            exc_ += c_;\n"
+    "                            if (incm_) break;\n"
+    "                        }\n"
+    "                        const uint32_t incl_ = exc_ + wg_tot_ < 0x7FFFFFFFull ? (uint32_t)(exc_ + wg_tot_) : 0x7FFFFFFFu;   // (saturated: beyond any capacity)\n"
+    "                        if (lane == 0 && ok_) sp_post(dsc_ + tile, ep_, 0x80000000u | incl_);\n"
+    "                        if (trk_ && tile == own_) tot_ = incl_;\n"
+    "                    } else if (lane == 0) ok_ = sp_await_inc(dsc_ + own_, ep_, tot_, tb_);   // the end-of-world tile: a lower ticket\n"
+    "                    if (lane == 0) { s_sp[4] = exc_; s_sp[5] = tot_; s_sp[6] = ok_ ? 1ull : 0ull; }\n"
+    "                }\n"
+    "                __syncthreads();\n"
+    "                const bool ok1_ = s_sp[6] != 0ull;\n"
+    "                uint64_t all_ = trk_ ? s_sp[5] : 0ull;                                  // the step's total, where known\n"
+    "                if (!ok1_) { if (tid == 0) a.sp_len[GGRS_SP_TIMEOUT] = 1ull; all_ = 0; }   // a wait that timed out: the host is told\n"
+    "                const bool over_ = trk_ && cur_len + all_ > a.sp_cap;\n"
+    "                if (over_) { if (tile == own_ && tid == 0) a.sp_len[1] = 1ull; all_ = 0; }   // children beyond the world's capacity: nothing spawns\n"
+    "                if (!above_ && !over_ && ok1_ && wg_tot_) {                            // a parent tile: its children's records\n"
+    "                    // one returning add on the pool cursor (started over by tile 0).  A tile whose inclusive prefix alone exceeds what len0_ leaves room for is in a step\n"
+    "                    // beyond the capacity: it reserves nothing, so every step spends at most capacity - len0_ records of the pool (capacity records)\n"
+    "                    if (tid == 0) {\n"
+    "                        uint32_t o_ = 0xFFFFFFFFu;\n"
+    "                        if (s_sp[4] + wg_tot_ <= a.sp_cap - len0_) {\n"
+    "                            const ggrs_u64 at_ = __hip_atomic_fetch_add(a.sp_ctl + 1, (ggrs_u64)wg_tot_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
+    "                            if (at_ + wg_tot_ <= a.sp_cap) o_ = (uint32_t)at_;\n"
+    "                        }\n"
+    "                        s_sp[7] = o_; sp_post(rof_ + tile, ep_, o_);\n"
+    "                    }\n"
+    "                    __syncthreads();\n"
+    "                    const uint32_t o_ = (uint32_t)s_sp[7];\n"
+    "                    if (o_ != 0xFFFFFFFFu && spn_0) {\n"
+    "                        GGRS_G ggrs_u64* const r_ = (GGRS_G ggrs_u64*)a.sp_recs + ((uint64_t)o_ + wg_excl_ + (inc_ - spn_0)) * 9u;\n"
+    "                        for (uint32_t k_ = 0; k_ < spn_0; ++k_)\n"
+    "                            for (int b_ = 0; b_ < 8; ++b_) __hip_atomic_store(r_ + 9u * k_ + b_, pw_[b_], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
+    "                        asm volatile(\"s_waitcnt vmcnt(0)\" ::: \"memory\");                    // the words have arrived where every XCD reads them: then the flags\n"
+    "                        for (uint32_t k_ = 0; k_ < spn_0; ++k_) __hip_atomic_store(r_ + 9u * k_ + 8u, ((ggrs_u64)ep_ << 32) | k_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
+    "                    }\n"
+    "                    asm volatile(\"s_waitcnt vmcnt(0)\" ::: \"memory\");\n"
+    "                }\n"
+    "                __syncthreads();                                                       // (this workgroup's own records are written before its children read them)\n"
+    "                if (all_ && e0 >= cur_len && e0 < cur_len + all_) {                    // a child: find its parent's tile, then poll its own record\n"
+    "                    const uint32_t r_ = (uint32_t)(e0 - cur_len);\n"
+    "                    uint32_t lo_ = 0, hi_ = own_, ex_ = 0; bool okc_ = true;\n"
+    "                    while (lo_ < hi_ && okc_) { const uint32_t m_ = (lo_ + hi_) >> 1; uint32_t v_ = 0; okc_ = sp_await_inc(dsc_ + m_, ep_, v_, tb_); if (v_ > r_) hi_ = m_; else { lo_ = m_ + 1u; ex_ = v_; } }\n"
+    "                    uint32_t o_ = 0xFFFFFFFFu;\n"
+    "                    if (okc_) okc_ = sp_await(rof_ + lo_, ep_, o_, tb_);\n"
+    "                    if (okc_ && o_ != 0xFFFFFFFFu) {\n"
+    "                        GGRS_G ggrs_u64* const rc_ = (GGRS_G ggrs_u64*)a.sp_recs + ((uint64_t)o_ + (r_ - ex_)) * 9u;\n"
+    "                        uint32_t k32_ = 0;\n"
+    "                        okc_ = sp_await((ggrs_u64*)(rc_ + 8u), ep_, k32_, tb_); kk_ = k32_;\n"
+    "                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, \"wavefront\");                 // (no instruction: the record's loads stay behind the poll)\n"
+    "                        if (okc_) for (int b_ = 0; b_ < 8; ++b_) prec_[b_] = __hip_atomic_load(rc_ + b_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
+    "                    }\n"
+    "                    if (!okc_) a.sp_len[GGRS_SP_TIMEOUT] = 1ull;\n"
+    "                    else if (o_ == 0xFFFFFFFFu) a.sp_len[1] = 1ull;                    // (the pool only runs dry after a step beyond the capacity: already reported)\n"
+    "                }\n"
+    "                sn_ = all_;\n"
+    "            }\n"
+    "            if (sn_) {                                                                 // uniform over the tile\n"
+    "                const unsigned char* const spay_ = (const unsigned char*)prec_;\n"
+    "                if (e0 >= sf_ && e0 < sf_ + sn_) {\n"
+    "                    alive_0 = true;\n";
+// How many, and whose: the entities that called e.spawn(n), in slot order (== RollbackOrdered order, so every rank and every replay numbers the children
+// alike).  Per step: an exclusive scan over the wave and the workgroup (LDS); every workgroup posts its count, workgroup 0 gathers them, scans them in
+// tile order and hands each workgroup its prefix and everyone the total; a parent then knows its children's slots and leaves {parent slot, k} where the
+// lane that OWNS each new slot will look; a second rendezvous (only in steps that spawn anything), and that lane takes the bundle.
+static const char kJitSpRendezvous[] =
+    "                const uint32_t T_ = a.sp_tiles, ep1_ = a.sp_epoch + 2u * sj + 1u, ep2_ = ep1_ + 1u;\n"
+    "                ggrs_u64* const cnt_ = a.sp_sums; ggrs_u64* const pref_ = cnt_ + T_; ggrs_u64* const done_ = cnt_ + 2u * T_; ggrs_u64* const tot_ = cnt_ + 3u * T_; ggrs_u64* const go_ = tot_ + 16;\n"
+    "                const unsigned long long tb_ = wall_clock64();\n"
+    "                if (tid == 0) sp_post(cnt_ + tile, ep1_, wg_tot_);\n"
+    "                if (tile == 0) {                                                       // workgroup 0: gather, scan in tile order (== slot order), hand back\n"
+    "                    // thread t takes the tiles [t x per, (t + 1) x per): at most 8 (8 x 256 workgroups are ever resident).  Awaited one after the other: keeping several\n"
+    "                    // loads in flight, or the counts in LDS, was tried and costs the WHOLE kernel 3..30 VGPRs -- a workgroup per CU of residency, i.e. of capacity\n"
+    "                    const uint32_t per_ = (T_ + 255u) / 256u, glo_ = tid * per_ < T_ ? tid * per_ : T_, ghi_ = glo_ + per_ < T_ ? glo_ + per_ : T_;\n"
+    "                    uint32_t mine_ = 0; bool okg_ = true;\n"
+    "                    for (uint32_t t_ = glo_; t_ < ghi_; ++t_) { uint32_t v_ = 0; okg_ = sp_await(cnt_ + t_, ep1_, v_, tb_) && okg_; mine_ += v_; }\n"
+    "                    uint32_t sc_ = mine_;\n"
+    "                    for (int o_ = 1; o_ < 64; o_ <<= 1) { const uint32_t up_ = __shfl_up(sc_, o_, 64); if ((int)lane >= o_) sc_ += up_; }\n"
+    "                    const uint32_t wt2_ = (uint32_t)__builtin_amdgcn_readlane((int)sc_, 63);\n"
+    "                    const bool wfail_ = __ballot(!okg_) != 0ull;\n"
+    "                    if (lane == 0) { s_sp[8u + wave] = wt2_; s_sp[12u + wave] = wfail_ ? 1ull : 0ull; }\n"
+    "                    __syncthreads();\n"
+    "                    uint32_t base_ = sc_ - mine_, run_ = 0;\n"
+    "                    for (uint32_t q_ = 0; q_ < 4u; ++q_) { const uint32_t v_ = (uint32_t)s_sp[8u + q_]; run_ += v_; if (q_ < wave) base_ += v_; }\n"
+    "                    const bool fail_ = (s_sp[12] | s_sp[13] | s_sp[14] | s_sp[15]) != 0ull;\n"
+    "                    if (run_ != 0u && !fail_)\n"
+    "                        for (uint32_t t_ = glo_; t_ < ghi_; ++t_) { const uint32_t v_ = (uint32_t)__hip_atomic_load(cnt_ + t_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); sp_post(pref_ + t_, ep1_, base_); base_ += v_; }\n"
+    "                    if (tid == 0) sp_post(tot_, ep1_, fail_ ? 0xFFFFFFFFu : run_);\n"
+    "                }\n"
+    "                if (tid == 0) {\n"
+    "                    uint32_t all32_ = 0xFFFFFFFFu, bef32_ = 0;\n"
+    "                    bool ok_ = sp_await(tot_, ep1_, all32_, tb_) && all32_ != 0xFFFFFFFFu;\n"
+    "                    if (ok_ && all32_ != 0u) ok_ = sp_await(pref_ + tile, ep1_, bef32_, tb_);\n"
+    "                    s_sp[4] = bef32_; s_sp[5] = ok_ ? all32_ : 1ull; s_sp[6] = ok_ ? 1ull : 0ull;\n"
+    "                }\n"
+    "                __syncthreads();\n"
+    "                const bool ok1_ = s_sp[6] != 0ull;\n"
+    "                const uint64_t bef_ = s_sp[4];\n"
+    "                uint64_t all_ = s_sp[5];\n"
+    "                if (!ok1_ || cur_len + all_ > a.sp_cap) {                               // a rendezvous that timed out, or children beyond the world's capacity: nothing spawns, the host is told\n"
+    "                    if (all_ && gu == 0 && lane == 0) a.sp_len[1] = !ok1_ ? 2ull : 1ull;\n"
+    "                    all_ = 0;\n"
+    "                }\n"
+    "                if (all_) {                                                            // uniform over the whole grid\n"
+    "                    const uint64_t first_ = cur_len + bef_ + wg_excl_ + (inc_ - spn_0);    // this parent's first child\n"
+    "                    for (uint32_t k_ = 0; k_ < spn_0; ++k_) {\n"
+    "                        GGRS_G ggrs_u64* lk_ = (GGRS_G ggrs_u64*)a.sp_link + 2u * (first_ + k_);\n"
+    "                        __hip_atomic_store(lk_, (ggrs_u64)e0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); __hip_atomic_store(lk_ + 1, (ggrs_u64)k_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
+    "                    }\n"
+    "                    asm volatile(\"s_waitcnt vmcnt(0)\" ::: \"memory\");                    // this wave's links and parent records (sc1 stores) have arrived where every XCD reads them\n"
+    "                    __syncthreads();\n"
+    "                    if (tid == 0) sp_post(done_ + tile, ep2_, 1u);\n"
+    "                    if (tile == 0) {\n"
+    "                        bool okd_ = true;\n"
+    "                        for (uint32_t t_ = tid; t_ < T_ && okd_; t_ += 256u) { uint32_t v_ = 0; okd_ = sp_await(done_ + t_, ep2_, v_, tb_); }\n"
+    "                        const bool wfail_ = __ballot(!okd_) != 0ull;\n"
+    "                        if (lane == 0) s_sp[12u + wave] = wfail_ ? 1ull : 0ull;\n"
+    "                        __syncthreads();\n"
+    "                        if (tid == 0) sp_post(go_, ep2_, (s_sp[12] | s_sp[13] | s_sp[14] | s_sp[15]) != 0ull ? 0xFFFFFFFFu : 1u);\n"
+    "                    }\n"
+    "                    if (tid == 0) { uint32_t g_ = 0; const bool ok_ = sp_await(go_, ep2_, g_, tb_) && g_ == 1u; s_sp[6] = ok_ ? 1ull : 0ull; }\n"
+    "                    __syncthreads();\n"
+    "                    if (s_sp[6] == 0ull) { if (gu == 0 && lane == 0) a.sp_len[1] = 2ull; all_ = 0; }\n"
+    "                }\n"
+    "                sn_ = all_;\n"
+    "            }\n"
+    "            if (sn_) {                                                                 // uniform over the grid\n"
+    "                unsigned long long kk_ = 0;\n"
+    "                ggrs_u64 prec_[8] = {0, 0, 0, 0, 0, 0, 0, 0};                          // the payload of a child: its parent's record, fetched past this XCD's L2 (sc1)\n"
+    "                if (e0 >= sf_ && e0 < sf_ + sn_) {\n"
+    "                    const GGRS_G ggrs_u64* lk_ = (const GGRS_G ggrs_u64*)a.sp_link + 2u * e0;\n"
+    "                    const unsigned long long par_ = __hip_atomic_load(lk_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); kk_ = __hip_atomic_load(lk_ + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
+    "                    // (this step's set: a parent that spawns again in the NEXT step writes the other one -- its workgroup may be a step ahead of this one, but not two: the next\n"
+    "                    // step's rendezvous waits for this workgroup)\n"
+    "                    const GGRS_G ggrs_u64* pp_ = (const GGRS_G ggrs_u64*)(a.sp_prec + ((uint64_t)(sj & 1u) * a.sp_tiles * 256u + par_) * 64u);\n"
+    "                    for (int b_ = 0; b_ < 8; ++b_) prec_[b_] = __hip_atomic_load(pp_ + b_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
+    "                }\n"
+    "                const unsigned char* const spay_ = (const unsigned char*)prec_;\n"
+    "                if (e0 >= sf_ && e0 < sf_ + sn_) {\n"
+    "                    alive_0 = true;\n";
 // ---- the argument block ---------------------------------------------------------------------------------------------------
 // HOST side: GgrsJitArgs below, every array at its maximum dimension -- what host_groups.hpp fills while it assembles a group.
 // DEVICE side: a struct of the same field names written FOR THE WORLD (jit_layout / jit_layout_text): only the fields this world's
@@ -574,30 +786,19 @@ JitNeeds jit_needs(const ggrs_world* w) {
     return n;
 }
 
-// Writes the kernel for this world.  Returns false when the world is outside what the generator covers (the caller falls
-// back to the per-request path): a system that touches a live-only component other than BOX_MOVE's read-only
-// Player.handle, too many words for the register file / the 64-bit row masks.
-bool jit_source(const ggrs_world* w, std::string& s) {
+// The worlds the generator covers; for every other one the caller falls back to the per-request path, or refuses the world.  EVERY refusal is here, and
+// jit_source asks before it writes a byte: a system that touches a live-only component other than BOX_MOVE's read-only Player.handle, too many words
+// for the register file / the 64-bit row masks, ...
+bool jit_covers(const ggrs_world* w) {
     const uint32_t nc = (uint32_t)w->comps.size();
-    const int spawn_sys = jit_fused_spawn_system(w);
     uint32_t units = 0, ncols = 0;
     for (auto& c : w->comps) { ncols += c.n_words; if (!c.no_rollback) units += c.n_words * std::max(1u, c.word_bytes / 4); }
     if (units == 0 || units > JIT_MAX_UNITS || ncols > JIT_MAX_COLS) return false;
     auto rb = [&](uint32_t c) { return c < nc && !w->comps[c].no_rollback; };
-    auto col = [&](uint32_t c, uint32_t k) { return w->comps[c].col_base + k; };
-    auto strat = [&](uint32_t c) { return w->comps[c].s_n_words != 0; };                     // snapshots hold Strategy::Stored, not the component (strategy.rs:22-40)
-    auto scol = [&](uint32_t c, uint32_t k) { return w->comps[c].scol_base + k; };
-    bool any_strat = false;
-    for (uint32_t c = 0; c < nc; ++c) if (rb(c) && strat(c)) any_strat = true;
-    const JitNeeds need = jit_needs(w);
-    const bool marks = need.marks;
-    const bool DEV = need.devspawn;                                  // spawns decided on the device (GGRS_SPAWN_PAYLOAD_PARENT): len lives on the device, the launch is cooperative
-    const bool STREAM = need.devstream;                              // ... or, in the streamed form, an ordinary launch of any size: tiles by ticket, children numbered by look-back
-    bool lds_inputs = false;                                         // user code indexes PlayerInputs (possibly by a handle it read from a component): the bytes go through LDS
+    uint32_t pv_cols[GGRS_PEER_MAX_COLUMNS]; const uint32_t n_pv = std::min<uint32_t>(peer_cols(w, pv_cols), GGRS_PEER_MAX_COLUMNS);
     for (auto& d : w->systems) {
         switch (d.kind) {
-        case GGRS_SYS_PARTICLES_SPAWN: break;
-        case GGRS_SYS_SPAWN_CUSTOM: lds_inputs = true; break;
+        case GGRS_SYS_PARTICLES_SPAWN: case GGRS_SYS_SPAWN_CUSTOM: break;
         case GGRS_SYS_PARTICLES_UPDATE: if (!rb(d.comp[0]) || !rb(d.comp[1])) return false; break;
         case GGRS_SYS_TTL_DESPAWN: case GGRS_SYS_ADD_U32: if (!rb(d.comp[0])) return false; break;
         case GGRS_SYS_SAT_SUB_DESPAWN: if (!rb(d.comp[0])) return false; break;
@@ -605,287 +806,301 @@ bool jit_source(const ggrs_world* w, std::string& s) {
         case GGRS_SYS_CUSTOM: {
             const ggrs_world::Custom& c = w->customs[d.comp[0]];
             for (uint32_t i = 0; i < c.n_bind; ++i) if (!rb(c.comp[i])) return false;      // may WRITE a live-only word: not replayable
-            lds_inputs = true;
+            // every peer binding finds its column in the world's peer view
+            for (uint32_t j = 0; j < c.n_peer; ++j) if (std::find(pv_cols, pv_cols + n_pv, w->comps[c.pcomp[j]].col_base + c.pword[j]) == pv_cols + n_pv) return false;
         } break;
         default: return false;
         }
     }
-    if (spawn_sys < 0) for (auto& d : w->systems) if (d.kind == GGRS_SYS_SPAWN_CUSTOM) return false;      // a user-written spawner only exists inside the generated kernel
-    std::vector<uint32_t> cks_comp;                                  // checksummed components in id order (== w->cks_comp once sealed)
-    for (uint32_t c = 0; c < nc; ++c) if (w->comps[c].checksummed) { if (!rb(c)) return false; cks_comp.push_back(c); }
-    const uint32_t n_cks = (uint32_t)cks_comp.size();
-    const bool lane_fold = jit_lane_fold(w, n_cks);
-    std::string fold_text;
-    if (lane_fold) {
-        char ft[1024];
-        snprintf(ft, sizeof ft,
-                 "    for (uint32_t r_ = wave; r_ < a.n_saves * %uu; r_ += 4u) {                  // one row per wave and trip: XOR over its 64 lanes\n"
-                 "        const uint32_t sv = r_ / %uu;\n"
-                 "        if (sv < o_first || sv >= o_last) continue;\n"
-                 "        const ggrs_u64 v_ = wave_xor(s_lane[r_ * 64u + lane]);\n"
-                 "        if (lane == 0) s_acc[sv * %uu + r_ %% %uu] = v_;\n"
-                 "    }\n"
-                 "    __syncthreads();\n", n_cks, n_cks, n_cks + 1, n_cks);
-        fold_text = ft;
-    }
+    if (jit_fused_spawn_system(w) < 0) for (auto& d : w->systems) if (d.kind == GGRS_SYS_SPAWN_CUSTOM) return false;      // a user-written spawner only exists inside the generated kernel
+    uint32_t n_cks = 0;
+    for (uint32_t c = 0; c < nc; ++c) if (w->comps[c].checksummed) { if (!rb(c)) return false; ++n_cks; }
     if (n_cks > (uint32_t)GEN_MAX_CKS) return false;
-    const unsigned long long OFF_ALIVE = w->off_alive, OFF_DIS = w->marks.off_disabled, OFF_DF = w->marks.off_dframe;
-    const JitLayout L = jit_layout(w);
-    const uint32_t IB = L.in_bytes, MAXP = L.max_players, IN_STRIDE = L.in_stride;
-
-    s.clear();
-    s += "typedef unsigned long uint64_t; typedef unsigned int uint32_t; typedef unsigned short uint16_t; typedef unsigned char uint8_t;\n"
-         "typedef long int64_t; typedef int int32_t;\n"
-         "typedef unsigned long long ggrs_u64; typedef unsigned int ggrs_u32;\n"
-         "#define GGRS_G __attribute__((address_space(1)))\n"
-         "// a wave-uniform pointer pinned into an SGPR pair: `sgpr_base(p) + lane_offset_u32` selects the saddr form of\n"
-         "// global_load / global_store (no 64-bit VALU address arithmetic, no 64-bit address registers per word)\n"
-         "__device__ __forceinline__ GGRS_G unsigned char* sgpr_base(const unsigned char* p) { unsigned long x = (unsigned long)p; asm volatile(\"\" : \"+s\"(x)); return (GGRS_G unsigned char*)x; }\n"
-         "// stores of one word to `base + lo` (base wave-uniform in an SGPR pair, lo a 32-bit lane offset), written as inline asm: the\n"
-         "// compiler otherwise materialises a 64-bit VGPR address per store -- into ONE register pair it recomputes before every store,\n"
-         "// which serialises a snapshot's store burst behind VALU address arithmetic (two extra VALU ops per stored word)\n"
-         "#define GGRS_ST(NAME, INSN, T, C) __device__ __forceinline__ void NAME(const unsigned char* base, uint32_t lo, T v) { const unsigned long b = (unsigned long)base; asm volatile(INSN \" %0, %1, %2\" : : \"v\"(lo), C(v), \"s\"(b) : \"memory\"); }\n"
-         "GGRS_ST(st1, \"global_store_byte\", uint32_t, \"v\") GGRS_ST(st2, \"global_store_short\", uint32_t, \"v\") GGRS_ST(st4, \"global_store_dword\", uint32_t, \"v\") GGRS_ST(st8, \"global_store_dwordx2\", uint64_t, \"v\")\n"
-         "#undef GGRS_ST\n"
-         "#define GGRS_ST(NAME, INSN, T, C) __device__ __forceinline__ void NAME(const unsigned char* base, uint32_t lo, T v) { const unsigned long b = (unsigned long)base; asm volatile(INSN \" %0, %1, %2 nt\" : : \"v\"(lo), C(v), \"s\"(b) : \"memory\"); }\n"
-         "GGRS_ST(st1nt, \"global_store_byte\", uint32_t, \"v\") GGRS_ST(st2nt, \"global_store_short\", uint32_t, \"v\") GGRS_ST(st4nt, \"global_store_dword\", uint32_t, \"v\") GGRS_ST(st8nt, \"global_store_dwordx2\", uint64_t, \"v\")\n"
-         "#undef GGRS_ST\n"
-         "// a batch member's record (GgrsJitArgs::mtab): written by the host before the launch, never by a kernel -- read through the constant address space,\n"
-         "// i.e. with scalar loads (the record's address is wave-uniform: blockIdx.z)\n"
-         "#define GGRS_K __attribute__((address_space(4)))\n"
-         "__device__ __forceinline__ uint64_t mb_u64(const GGRS_K unsigned char* mb, uint32_t off) { return *(const GGRS_K uint64_t*)(mb + off); }\n"
-         "__device__ __forceinline__ uint32_t mb_u32(const GGRS_K unsigned char* mb, uint32_t off) { return *(const GGRS_K uint32_t*)(mb + off); }\n"
-         "__device__ __forceinline__ uint32_t mb_u8(const GGRS_K unsigned char* mb, uint32_t off) { return *(const GGRS_K unsigned char*)(mb + off); }\n"
-         "// value tags keep one 32-bit tag per COLUMN in lane `column` of a register: a wave-uniform 64-bit column mask therefore IS the set of lanes to touch.  These\n"
-         "// run one instruction under that mask (exec narrowed, the instruction, exec restored) instead of building a per-lane condition from the mask with VALU\n"
-         "// shifts and compares -- the generated kernel is bound by its vector ALUs.  (`s_and_b64` writes SCC and the statements SAY so: without the clobber the compiler\n"
-         "// kept a condition in SCC across them -- s_bitcmp1 before the asm, s_cselect behind it -- in copies specialised for some shapes: profiles/r06ff)\n"
-         "__device__ __forceinline__ uint64_t uni64(uint64_t m) { return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(m >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)m); }   // wave-uniform by construction: say so\n"
-         "__device__ __forceinline__ void set_lanes(uint32_t& v, uint64_t lanes_, uint32_t x_) { const uint64_t lanes = uni64(lanes_); const uint32_t x = (uint32_t)__builtin_amdgcn_readfirstlane((int)x_); uint64_t sv_; asm volatile(\"s_mov_b64 %0, exec\\n\\ts_and_b64 exec, exec, %2\\n\\tv_mov_b32 %1, %3\\n\\ts_mov_b64 exec, %0\" : \"=&s\"(sv_), \"+v\"(v) : \"s\"(lanes), \"s\"(x) : \"scc\"); }\n"
-         "__device__ __forceinline__ void store_lanes(GGRS_G uint32_t* p, uint32_t v, uint64_t lanes_) { const uint64_t lanes = uni64(lanes_); uint64_t sv_; asm volatile(\"s_mov_b64 %0, exec\\n\\ts_and_b64 exec, exec, %3\\n\\tglobal_store_dword %1, %2, off\\n\\ts_mov_b64 exec, %0\" : \"=&s\"(sv_) : \"v\"(p), \"v\"(v), \"s\"(lanes) : \"memory\", \"scc\"); }\n"
-         "// SPAWNS DECIDED ON THE DEVICE: the workgroups of a COOPERATIVE launch (all resident) meet through mailbox words {epoch:32 | value:32}, written and polled\n"
-         "// as relaxed agent-scope atomics (sc1: through to where every XCD reads them).  The value travels INSIDE the word it is waited on, so no rendezvous needs a\n"
-         "// release/acquire pair -- on gfx950 those are a writeback / an invalidate of a whole L2 each (measured: ~100 us per barrier with an acquire in the poll loop).\n"
-         "// Bounded: a second of wall clock, then the launch reports an error instead of hanging the device\n"
-         "__device__ __forceinline__ void sp_post(ggrs_u64* p, ggrs_u32 ep, ggrs_u32 v) { __hip_atomic_store(p, ((ggrs_u64)ep << 32) | v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }\n"
-         "__device__ __forceinline__ bool sp_await(ggrs_u64* p, ggrs_u32 ep, ggrs_u32& v, unsigned long long t0_) {\n"
-         "    for (;;) {\n"
-         "        const ggrs_u64 x_ = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
-         "        if ((ggrs_u32)(x_ >> 32) == ep) { v = (ggrs_u32)x_; return true; }\n"
-         "        if (wall_clock64() - t0_ > 100000000ull) return false;\n"
-         "        __builtin_amdgcn_s_sleep(1);\n"
-         "    }\n"
-         "}\n"
-         "namespace ggrs {\n";
-    s += kJitPrelude;
-    s += "\n}\nusing namespace ggrs;\n";
-    if (STREAM)
-        s += "// STREAMED device spawns: the grid need not be resident as a whole.  PROGRESS RULE: a workgroup only ever waits on a strictly lower ticket, or on its own\n"
-             "// workgroup behind a __syncthreads() that follows the writes.  A workgroup's tile IS its ticket (taken first thing), so the lowest unfinished ticket never\n"
-             "// waits on anyone that has not started; the look-back, the end-of-world tile's descriptor and a parent's child records all sit at lower or equal tiles.\n"
-             "// Every wait is bounded by the wall clock, as sp_await.  A descriptor {epoch:32 | inclusive:1 | count:31}: a tile posts its own count, looks back\n"
-             "// (64 predecessors per probe) until it meets an inclusive prefix, then posts its own inclusive prefix\n"
-             "__device__ __forceinline__ bool sp_await_inc(ggrs_u64* p, ggrs_u32 ep, ggrs_u32& v, unsigned long long t0_) {\n"
-             "    for (;;) {\n"
-             "        const ggrs_u64 x_ = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
-             "        if ((ggrs_u32)(x_ >> 32) == ep && (x_ & 0x80000000ull)) { v = (ggrs_u32)x_ & 0x7FFFFFFFu; return true; }\n"
-             "        if (wall_clock64() - t0_ > 100000000ull) return false;\n"
-             "        __builtin_amdgcn_s_sleep(1);\n"
-             "    }\n"
-             "}\n"
-             "// the grid's last tile, before it writes RollbackOrdered::len into the block every tile read its starting len from (a group run in place): every other tile\n"
-             "// has posted that it read it (one word per tile, a lower ticket each; wave-parallel, 64 per probe)\n"
-             "__device__ __forceinline__ bool sp_gate(ggrs_u64* f, uint32_t n, ggrs_u32 ep, uint32_t lane) {\n"
-             "    const unsigned long long t0_ = wall_clock64();\n"
-             "    for (uint32_t b_ = 0; b_ < n; b_ += 64u) { uint32_t v_ = 0; const bool g_ = b_ + lane >= n || sp_await(f + b_ + lane, ep, v_, t0_); if (__ballot(!g_) != 0ull) return false; }\n"
-             "    return true;\n"
-             "}\n";
-    if (STREAM) sfmt(s, "#define GGRS_SP_TIMEOUT %uu                                                        // sp_len[GGRS_SP_TIMEOUT] = 1: a wait timed out (sp_len[1] = 1: children beyond the capacity)\n"
-                        "#define GGRS_SP_READ %uu                                                           // sp_desc[GGRS_SP_READ x tiles + tile]: that tile has read its starting len\n",
-                     2u + (unsigned)MAX_TICK_SAVES, 2u * (unsigned)MAX_TICK_STEPS);
-    s += GGRS_FRAME_TEXT;
-    s += need.peers ? GGRS_ENTITY_PEERS_TEXT : GGRS_ENTITY_TEXT;
-    s += GGRS_COMPONENT_TEXT;
-    s += GGRS_WORDS_TEXT;
-    s += jit_layout_text(L);
-    for (size_t i = 0; i < w->customs.size(); ++i) {
-        std::string nm = w->customs[i].name;
-        for (char& ch : nm) if (!isalnum((unsigned char)ch) && ch != '_') ch = '_';
-        sfmt(s, "namespace ggrs_sys_%zu {\n#line 1 \"%s\"\n", i, nm.c_str());
-        s += w->customs[i].source;
-        s += "\n}\n";
-    }
-    if (spawn_sys >= 0 && w->systems[spawn_sys].kind == GGRS_SYS_SPAWN_CUSTOM) {
-        const ggrs_world::SpawnSys& sp = w->spawn_customs[w->systems[spawn_sys].comp[0]];
-        std::string nm = sp.name;
-        for (char& ch : nm) if (!isalnum((unsigned char)ch) && ch != '_') ch = '_';
-        sfmt(s, "namespace ggrs_spawn_sys {\n#line 1 \"%s\"\n", nm.c_str());
-        s += sp.source;
-        s += "\n}\n";
-    }
-    for (uint32_t c : cks_comp) if (!w->comps[c].cks_source.empty()) {
-        sfmt(s, "namespace ggrs_hash_%u {\n#line 1 \"checksum_%s\"\n", c, w->comps[c].name.c_str());
-        s += w->comps[c].cks_source;
-        s += "\n}\n";
-    }
-    for (uint32_t c = 0; c < nc; ++c) if (rb(c) && strat(c)) {
-        sfmt(s, "namespace ggrs_strategy_%u {\n#line 1 \"strategy_%s\"\n", c, w->comps[c].name.c_str());
-        s += w->comps[c].strat_source;
-        s += "\n}\n";
-    }
-    s += "#line 1 \"ggrs_jit_tick\"\n";
-    s += "extern \"C\" __global__ __launch_bounds__(256) void ggrs_jit_tick(GgrsJitArgs a) {\n"
-         "    const uint32_t tid = threadIdx.x, lane = tid & 63u;\n"
-         "    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));   // wave-uniform, and the compiler knows it\n";
-    if (STREAM)
-        s += "    // STREAMED: this workgroup's tile is its ticket -- the order in which workgroups START, whatever order the dispatcher picks (no fold-forward role here)\n"
-             "    __shared__ uint32_t s_tk;\n"
-             "    if (tid == 0) s_tk = (uint32_t)(atomicAdd((unsigned long long*)a.sp_ctl, 1ull) - a.sp_ticket_base);\n"
-             "    __syncthreads();\n";
-    else sfmt(s,
-            "    // FOLD-FORWARD role: the first ff_blocks workgroups (a multiple of 8: the XCD mapping below is unchanged) do not own a tile -- each folds one row\n"
-            "    // of partials the PREVIOUS launch on this stream left in device memory and hands the value, then its tag, to the host\n"
-            "    if (blockIdx.x < a.ff_blocks) {\n"
-            "        if (blockIdx.y == 0u && blockIdx.z == 0u && blockIdx.x < a.ff_nvals) {                   // ff_nvals = rows x chunks per row (ff_split)\n"
-            "            const uint32_t row = blockIdx.x / a.ff_split, ck = blockIdx.x %% a.ff_split, per = (a.ff_g + a.ff_split - 1u) / a.ff_split;\n"
-            "            ff_fold_row((const uint64_t*)a.ff_rows + (uint64_t)row * a.ff_stride * (a.ff_self ? 2u : 1u), a.ff_istride,     // (self-fold: 16-byte cells)\n"
-            "                        ck * per, min(a.ff_g, (ck + 1u) * per), (row %% %uu) == %uu,\n"
-            "                        (uint64_t*)a.ff_out + 2u * blockIdx.x, (uint64_t)a.ff_seq, a.ff_self ? (uint64_t)a.ff_seq : 0ull);   // cell blockIdx.x: {value, tag}\n"
-            "        }\n"
-            "        return;\n"
-            "    }\n"
-            "    const uint32_t bx = blockIdx.x - a.ff_blocks, gx = gridDim.x - a.ff_blocks;\n", n_cks + 1, n_cks);
-    sfmt(s,
-            "    // batch members (blockIdx.z) with records: what differs between the launch's groups comes from member z's record, the rest from the argument block\n"
-            "    const GGRS_K unsigned char* const mb = a.mtab ? (const GGRS_K unsigned char*)(unsigned long)(a.mtab + (uint64_t)blockIdx.z * %uull) : (const GGRS_K unsigned char*)0ul;\n"
-            "    const bool writes_live = (!a.src_is_live || a.n_steps) && !a.skip_live;\n"
-            "    const uint32_t o_first = a.dp_s ? blockIdx.y * a.dp_s : 0u;          // depth-parallel roles: this workgroup's share of the outputs\n"
-            "    const uint32_t o_last = a.dp_s ? min(o_first + a.dp_s, a.n_saves + 1u) : a.n_saves + 1u;\n"
-            "    const bool my_live = o_last == a.n_saves + 1u;\n"
-            "    if (a.dp_s && o_first == a.n_saves && !writes_live) return;\n"
-            "    // per-workgroup checksum partials [Save][component .. live count]: the waves fold into LDS\n"
-            "    __shared__ ggrs_u64 s_acc[16 * %u];\n"
-            "%s"
-            "    for (uint32_t i = tid; i < 16u * %uu; i += 256u) s_acc[i] = 0;\n",
-         L.m.bytes, n_cks + 1,
-         vtags_policy(w) ? "    __shared__ ggrs_u64 s_skip;                                                // value tags, profiling: bytes this workgroup's Saves did not store\n    if (tid == 0) s_skip = 0;\n" : "",
-         n_cks + 1);
-    if (lane_fold) sfmt(s, "    extern __shared__ ggrs_u64 s_lane[];                                  // [Save][checksummed component][lane]: a.n_saves * %u * 64 cells (dynamic LDS)\n"
-                           "    for (uint32_t i = tid; i < a.n_saves * %uu; i += 256u) s_lane[i] = 0;\n", n_cks, n_cks * 64u);
-    if (lds_inputs && IN_STRIDE)
-        sfmt(s, "    __shared__ unsigned char s_in[%u * %u];                                  // PlayerInputs of every step of the group: [step][%u players x %u bytes | %u status bytes]\n"
-                "    for (uint32_t i = tid; i < a.n_steps * %uu; i += 256u) s_in[i] = mb ? (unsigned char)mb_u8(mb, %uu + i) : a.inputs[i / %uu][i %% %uu];\n", L.cap_steps, IN_STRIDE, MAXP, IB, MAXP, IN_STRIDE, L.m.inputs, IN_STRIDE, IN_STRIDE);
-    if (STREAM) s += "    __syncthreads();\n"
-                     "    const uint32_t tile = s_tk;                                               // ticket order == tile order (no XCD remap: look-back needs it)\n"
-                     "    if (tile * 4u >= a.n_units) return;\n"
-                     "    {\n"
-                     "    const uint32_t gu = tile * 4u + wave;                                     // this wave's 64-slot unit == its mask word\n";
-    else
-    s += "    __syncthreads();\n"
-         "    // XCD-aware tile mapping: workgroup b runs on XCD b % 8 (observed placement; used for speed only), and each XCD has its own\n"
-         "    // L2.  Handing XCD x the x-th CONTIGUOUS eighth of the tiles makes the workgroups that write neighbouring 1 KiB pieces of a\n"
-         "    // row share one L2, which merges them into long runs before they go to memory -- instead of every L2 seeing every 8th piece.\n"
-         "    const uint32_t g8 = gx >> 3;                                              // the grid is 8 x ceil(tiles / 8) workgroups (+ the fold-forward ones)\n"
-         "    const uint32_t tile = (bx & 7u) * g8 + (bx >> 3);\n"
-         "    if (tile * 4u >= a.n_units) return;                                       // padding workgroup of the last eighth\n"
-         "    {\n"
-         "    const uint32_t gu = tile * 4u + wave;                                     // this wave's 64-slot unit == its mask word\n";
-    sfmt(s, "    const uint64_t e0 = (uint64_t)gu * 64u + lane;                             // this lane's slot\n"
-            "%s"
-            "    %sbool in_len = (uint64_t)gu * 64u < %s;                                 // wave-uniform%s\n"
-            "    // word c of slot e lives at col_off[c] + (e >> 13) * tile_stride + (e & 8191) * word_bytes: the layout tile is the\n"
-            "    // wave's (uniform: SGPRs), the lane contributes one 32-bit offset per word size -> saddr-form accesses\n"
-            "    const uint64_t tbase = (uint64_t)(gu >> %d) * %uull;\n"
-            "    const uint32_t ei = (gu & %uu) * 64u + lane, lo1 = ei, lo2 = ei * 2u, lo4 = ei * 4u, lo8 = ei * 8u;\n"
-            "    (void)lo1; (void)lo2; (void)lo4; (void)lo8;\n"
-            "    const uint64_t wi8 = (uint64_t)gu * 8u;                                    // byte offset of this wave's mask word: bit `lane` is this slot\n"
-            "    const uint32_t sh = lane;\n",
-         DEV ? "    uint64_t cur_len = *reinterpret_cast<const uint64_t*>(a.src);                // RollbackOrdered::len as the source block's header says: with spawns decided on the device the host only knows a bound\n"
-                   "    __shared__ uint64_t s_sp[16];                                              // the workgroup's spawn bookkeeping of one step\n" : "",
-         spawn_sys >= 0 ? "" : "const ", DEV ? "cur_len" : "a.len", spawn_sys >= 0 ? " (a spawn inside the group grows len)" : "", LT_SHIFT - 6, w->ts, (unsigned)(LAYOUT_TILE / 64 - 1));
-    if (STREAM)
-        s += "    // Only tiles at or above the END of the world -- the tile of slot len - 1 -- can hold children, and only they learn each step's total (from that tile's\n"
-             "    // descriptor: a lower ticket).  A tile below it stays below it (len only grows inside a group), has parents at most, and never needs the total: its\n"
-             "    // cur_len goes stale and it writes no len anywhere.  trk_: this tile still tracks cur_len exactly; the grid's last tile always does and writes it\n"
-             "    bool trk_ = tile >= (uint32_t)(cur_len ? (cur_len - 1u) >> 8 : 0u);\n"
-             "    const bool len_wr = tile == a.sp_tiles - 1u && wave == 0u && lane == 0u;         // the one lane that writes RollbackOrdered::len (headers, sp_len)\n"
-             "    const uint64_t len0_ = cur_len;                                                  // len at the launch's start: exact in every tile\n"
-             "    bool gated_ = false;                                                             // (the last tile: every tile has read its starting len)\n"
-             "    // tile 0 starts the record-pool cursor over (before its first descriptor: every reservation of this launch follows a look-back that reaches one of\n"
-             "    // tile 0's); every tile then says it has read its starting len\n"
-             "    asm volatile(\"s_waitcnt vmcnt(0)\" ::: \"memory\");\n"
-             "    __syncthreads();\n"
-             "    if (tid == 0) {\n"
-             "        if (tile == 0u) { (void)__hip_atomic_exchange(a.sp_ctl + 1, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); asm volatile(\"s_waitcnt vmcnt(0)\" ::: \"memory\"); }\n"
-             "        sp_post(a.sp_desc + (uint64_t)GGRS_SP_READ * a.sp_tiles + tile, a.sp_epoch + 1u + GGRS_SP_READ, 1u);\n"
-             "    }\n";
-    // ---- masks and words of the lane's slot
-    sfmt(s, "    const uint64_t mk_alive = *reinterpret_cast<const uint64_t*>(a.src + %lluull + wi8);\n"
-            "    bool alive_0 = (mk_alive >> sh) & 1ull;\n", OFF_ALIVE);
-    // (worlds with non-rollback components: who was alive in the source block, for the `gone` ballot of a batch member at the end of the unit.  One VGPR, made opaque
-    // so that it is not rebuilt from mk_alive there: the word, or a.src to read it again, held in SGPRs across the unit costs the marker test world a wave per SIMD)
-    if (need.nr) s += "    uint32_t src_alive_v = alive_0 ? 1u : 0u; asm volatile(\"\" : \"+v\"(src_alive_v));\n";
-    for (uint32_t c = 0; c < nc; ++c) if (rb(c))
-        sfmt(s, "    const uint64_t mk%u = *reinterpret_cast<const uint64_t*>(a.src + %lluull + wi8);\n"
-                "    %sbool p%u_0 = (mk%u >> sh) & 1ull;\n", c, (unsigned long long)w->off_present[c], spawn_sys >= 0 ? "" : "const ", c, c);
-    auto wtype_b = [](uint32_t b) { return b == 8 ? "uint64_t" : "uint32_t"; };                                      // register type of a word of b bytes
-    auto mtype_b = [](uint32_t b) { return b == 8 ? "uint64_t" : (b == 4 ? "uint32_t" : (b == 2 ? "uint16_t" : "uint8_t")); };   // its memory type
-    auto wtype = [&](uint32_t c) { return wtype_b(w->comps[c].word_bytes); };
-    auto mtype = [&](uint32_t c) { return mtype_b(w->comps[c].word_bytes); };
+    // every rollback column shares the tile stride -- the Stored words of a component under a Strategy too
     for (uint32_t c = 0; c < nc; ++c) if (rb(c)) {
-        for (uint32_t k = 0; k < w->comps[c].n_words; ++k) {
-            const uint32_t cl = col(c, k), wb = w->comps[c].word_bytes;
-            if (w->col_ts[cl] != w->ts) return false;                    // every rollback column shares the tile stride
-            sfmt(s, "#define o%u(blk) (sgpr_base((blk) + (%lluull + tbase)) + lo%u)\n#define b%u(blk) ((blk) + (%lluull + tbase))\n    %s w%u_0 = 0;\n",
-                 cl, (unsigned long long)w->col_off[cl], wb, cl, (unsigned long long)w->col_off[cl], wtype(c), cl);
+        for (uint32_t k = 0; k < w->comps[c].n_words; ++k) if (w->col_ts[w->comps[c].col_base + k] != w->ts) return false;
+        for (uint32_t k = 0; k < w->comps[c].s_n_words; ++k) if (w->col_ts[w->comps[c].scol_base + k] != w->ts) return false;
+    }
+    return true;
+}
+
+// The generator: what jit_source derives ONCE from a world jit_covers, and one member function per section of the kernel's text.
+struct JitGen {
+    const ggrs_world* const w; std::string& s;                       // the world, the text
+    const uint32_t nc;
+    const int spawn_sys;                                             // jit_fused_spawn_system: the spawn system that runs inside the kernel, or -1
+    // need.devspawn: spawns decided on the device (GGRS_SPAWN_PAYLOAD_PARENT): len lives on the device, the launch is cooperative
+    // need.devstream: ... or, in the streamed form, an ordinary launch of any size: tiles by ticket, children numbered by look-back
+    const JitNeeds need;
+    const JitLayout L;
+    const uint32_t IB, MAXP, IN_STRIDE;
+    const unsigned long long OFF_ALIVE, OFF_DIS, OFF_DF, OFF_TAGS, TAGCOLS;
+    const uint32_t NTC, TAG_ROW;
+    // columns some system writes (a steady SaveWorld stores exactly these); those plus what steps and checksums read
+    const uint64_t HOT, LOADHOT;
+    std::vector<uint32_t> cks_comp; uint32_t n_cks = 0;              // checksummed components in id order (== w->cks_comp once sealed)
+    bool lane_fold = false;
+    bool any_strat = false;
+    bool lds_inputs = false;                                         // user code indexes PlayerInputs (possibly by a handle it read from a component): the bytes go through LDS
+    uint64_t wb_mask[4] = {0, 0, 0, 0};                              // columns by word size (1, 2, 4, 8 bytes): what a skipped column saves
+    std::vector<uint32_t> spec_bytes; std::vector<uint8_t> spec_memo;   // which word-list specs take the memoised form: 9..12 hashed bytes whose byte 8.. tail is made of whole fields
+
+    JitGen(const ggrs_world* w_, std::string& s_)
+        : w(w_), s(s_), nc((uint32_t)w_->comps.size()), spawn_sys(jit_fused_spawn_system(w_)), need(jit_needs(w_)), L(jit_layout(w_)),
+          IB(L.in_bytes), MAXP(L.max_players), IN_STRIDE(L.in_stride), OFF_ALIVE(w_->off_alive), OFF_DIS(w_->marks.off_disabled), OFF_DF(w_->marks.off_dframe),
+          OFF_TAGS(w_->off_tags), TAGCOLS(w_->tag_cols), NTC(w_->n_tcols), TAG_ROW(w_->tag_row_bytes), HOT(jit_hot_cols(w_)), LOADHOT(HOT | jit_static_reads(w_)) {
+        for (uint32_t c = 0; c < nc; ++c) if (rb(c) && strat(c)) any_strat = true;
+        for (auto& d : w->systems) lds_inputs |= d.kind == GGRS_SYS_SPAWN_CUSTOM || d.kind == GGRS_SYS_CUSTOM;
+        for (uint32_t c = 0; c < nc; ++c) if (w->comps[c].checksummed) cks_comp.push_back(c);
+        n_cks = (uint32_t)cks_comp.size();
+        lane_fold = jit_lane_fold(w, n_cks);
+        for (uint32_t c = 0; c < nc; ++c) if (rb(c) && !strat(c)) for (uint32_t k = 0; k < w->comps[c].n_words; ++k) {
+            const uint32_t wb = w->comps[c].word_bytes; wb_mask[wb == 1 ? 0 : wb == 2 ? 1 : wb == 4 ? 2 : 3] |= 1ull << col(c, k);
         }
-        // a component under a Strategy: its Stored words have columns of their own (ring slots hold them, the live block holds the component)
-        for (uint32_t k = 0; k < w->comps[c].s_n_words; ++k) {
-            const uint32_t cl = scol(c, k), wb = w->comps[c].s_word_bytes;
-            if (w->col_ts[cl] != w->ts) return false;
-            sfmt(s, "#define o%u(blk) (sgpr_base((blk) + (%lluull + tbase)) + lo%u)\n#define b%u(blk) ((blk) + (%lluull + tbase))\n",
-                 cl, (unsigned long long)w->col_off[cl], wb, cl, (unsigned long long)w->col_off[cl]);
+        spec_bytes.assign(n_cks, 0); spec_memo.assign(n_cks, 0);
+        for (uint32_t k = 0; k < n_cks; ++k) {
+            const Comp& cc = w->comps[cks_comp[k]];
+            if (!cc.cks_source.empty()) continue;
+            spec_bytes[k] = (uint32_t)cc.cks_words.size() * cc.word_bytes;
+            spec_memo[k] = spec_bytes[k] > 8 && spec_bytes[k] <= 12;
         }
     }
-    // loads / stores of the words of the lane's slot from / to a block, each guarded by its bit of a wave-uniform row mask
+
+    bool rb(uint32_t c) const { return c < nc && !w->comps[c].no_rollback; }
+    uint32_t col(uint32_t c, uint32_t k) const { return w->comps[c].col_base + k; }
+    bool strat(uint32_t c) const { return w->comps[c].s_n_words != 0; }                      // snapshots hold Strategy::Stored, not the component (strategy.rs:22-40)
+    uint32_t scol(uint32_t c, uint32_t k) const { return w->comps[c].scol_base + k; }
+    static const char* wtype_b(uint32_t b) { return b == 8 ? "uint64_t" : "uint32_t"; }                                      // register type of a word of b bytes
+    static const char* mtype_b(uint32_t b) { return b == 8 ? "uint64_t" : (b == 4 ? "uint32_t" : (b == 2 ? "uint16_t" : "uint8_t")); }   // its memory type
+    const char* wtype(uint32_t c) const { return wtype_b(w->comps[c].word_bytes); }
+    const char* mtype(uint32_t c) const { return mtype_b(w->comps[c].word_bytes); }
+    uint64_t comp_mask(uint32_t c) const { uint64_t m = 0; for (uint32_t k = 0; k < w->comps[c].n_words; ++k) m |= 1ull << col(c, k); return m; }
+    void each_col(uint64_t only, const std::function<void(uint32_t, uint32_t)>& fn) const {          // plain columns (not under a Strategy)
+        for (uint32_t c = 0; c < nc; ++c) if (rb(c) && !strat(c)) for (uint32_t k = 0; k < w->comps[c].n_words; ++k)
+            if ((only >> col(c, k)) & 1ull) fn(c, col(c, k));
+    }
+    void each_strat(uint64_t only, const std::function<void(uint32_t)>& fn) const { for (uint32_t c = 0; c < nc; ++c) if (rb(c) && strat(c) && (only & comp_mask(c))) fn(c); }
+    static std::string file_name(std::string nm) { for (char& ch : nm) if (!isalnum((unsigned char)ch) && ch != '_') ch = '_'; return nm; }   // a user's name as a #line file name
+
+    // ---- 1. the fixed preamble: types, store helpers, the mailboxes, the device prelude, what user code sees, the argument block
+    void preamble() {
+        s += "typedef unsigned long uint64_t; typedef unsigned int uint32_t; typedef unsigned short uint16_t; typedef unsigned char uint8_t;\n"
+             "typedef long int64_t; typedef int int32_t;\n"
+             "typedef unsigned long long ggrs_u64; typedef unsigned int ggrs_u32;\n"
+             "#define GGRS_G __attribute__((address_space(1)))\n"
+             "// a wave-uniform pointer pinned into an SGPR pair: `sgpr_base(p) + lane_offset_u32` selects the saddr form of\n"
+             "// global_load / global_store (no 64-bit VALU address arithmetic, no 64-bit address registers per word)\n"
+             "__device__ __forceinline__ GGRS_G unsigned char* sgpr_base(const unsigned char* p) { unsigned long x = (unsigned long)p; asm volatile(\"\" : \"+s\"(x)); return (GGRS_G unsigned char*)x; }\n"
+             "// stores of one word to `base + lo` (base wave-uniform in an SGPR pair, lo a 32-bit lane offset), written as inline asm: the\n"
+             "// compiler otherwise materialises a 64-bit VGPR address per store -- into ONE register pair it recomputes before every store,\n"
+             "// which serialises a snapshot's store burst behind VALU address arithmetic (two extra VALU ops per stored word)\n"
+             "#define GGRS_ST(NAME, INSN, T, C) __device__ __forceinline__ void NAME(const unsigned char* base, uint32_t lo, T v) { const unsigned long b = (unsigned long)base; asm volatile(INSN \" %0, %1, %2\" : : \"v\"(lo), C(v), \"s\"(b) : \"memory\"); }\n"
+             "GGRS_ST(st1, \"global_store_byte\", uint32_t, \"v\") GGRS_ST(st2, \"global_store_short\", uint32_t, \"v\") GGRS_ST(st4, \"global_store_dword\", uint32_t, \"v\") GGRS_ST(st8, \"global_store_dwordx2\", uint64_t, \"v\")\n"
+             "#undef GGRS_ST\n"
+             "#define GGRS_ST(NAME, INSN, T, C) __device__ __forceinline__ void NAME(const unsigned char* base, uint32_t lo, T v) { const unsigned long b = (unsigned long)base; asm volatile(INSN \" %0, %1, %2 nt\" : : \"v\"(lo), C(v), \"s\"(b) : \"memory\"); }\n"
+             "GGRS_ST(st1nt, \"global_store_byte\", uint32_t, \"v\") GGRS_ST(st2nt, \"global_store_short\", uint32_t, \"v\") GGRS_ST(st4nt, \"global_store_dword\", uint32_t, \"v\") GGRS_ST(st8nt, \"global_store_dwordx2\", uint64_t, \"v\")\n"
+             "#undef GGRS_ST\n"
+             "// a batch member's record (GgrsJitArgs::mtab): written by the host before the launch, never by a kernel -- read through the constant address space,\n"
+             "// i.e. with scalar loads (the record's address is wave-uniform: blockIdx.z)\n"
+             "#define GGRS_K __attribute__((address_space(4)))\n"
+             "__device__ __forceinline__ uint64_t mb_u64(const GGRS_K unsigned char* mb, uint32_t off) { return *(const GGRS_K uint64_t*)(mb + off); }\n"
+             "__device__ __forceinline__ uint32_t mb_u32(const GGRS_K unsigned char* mb, uint32_t off) { return *(const GGRS_K uint32_t*)(mb + off); }\n"
+             "__device__ __forceinline__ uint32_t mb_u8(const GGRS_K unsigned char* mb, uint32_t off) { return *(const GGRS_K unsigned char*)(mb + off); }\n"
+             "// value tags keep one 32-bit tag per COLUMN in lane `column` of a register: a wave-uniform 64-bit column mask therefore IS the set of lanes to touch.  These\n"
+             "// run one instruction under that mask (exec narrowed, the instruction, exec restored) instead of building a per-lane condition from the mask with VALU\n"
+             "// shifts and compares -- the generated kernel is bound by its vector ALUs.  (`s_and_b64` writes SCC and the statements SAY so: without the clobber the compiler\n"
+             "// kept a condition in SCC across them -- s_bitcmp1 before the asm, s_cselect behind it -- in copies specialised for some shapes: profiles/r06ff)\n"
+             "__device__ __forceinline__ uint64_t uni64(uint64_t m) { return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(m >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)m); }   // wave-uniform by construction: say so\n"
+             "__device__ __forceinline__ void set_lanes(uint32_t& v, uint64_t lanes_, uint32_t x_) { const uint64_t lanes = uni64(lanes_); const uint32_t x = (uint32_t)__builtin_amdgcn_readfirstlane((int)x_); uint64_t sv_; asm volatile(\"s_mov_b64 %0, exec\\n\\ts_and_b64 exec, exec, %2\\n\\tv_mov_b32 %1, %3\\n\\ts_mov_b64 exec, %0\" : \"=&s\"(sv_), \"+v\"(v) : \"s\"(lanes), \"s\"(x) : \"scc\"); }\n"
+             "__device__ __forceinline__ void store_lanes(GGRS_G uint32_t* p, uint32_t v, uint64_t lanes_) { const uint64_t lanes = uni64(lanes_); uint64_t sv_; asm volatile(\"s_mov_b64 %0, exec\\n\\ts_and_b64 exec, exec, %3\\n\\tglobal_store_dword %1, %2, off\\n\\ts_mov_b64 exec, %0\" : \"=&s\"(sv_) : \"v\"(p), \"v\"(v), \"s\"(lanes) : \"memory\", \"scc\"); }\n";
+        s += kJitSpMailbox;
+        s += "namespace ggrs {\n";
+        s += kJitPrelude;
+        s += "\n}\nusing namespace ggrs;\n";
+        if (need.devstream) s += kJitSpStreamed;
+        if (need.devstream) sfmt(s, "#define GGRS_SP_TIMEOUT %uu                                                        // sp_len[GGRS_SP_TIMEOUT] = 1: a wait timed out (sp_len[1] = 1: children beyond the capacity)\n"
+                                    "#define GGRS_SP_READ %uu                                                           // sp_desc[GGRS_SP_READ x tiles + tile]: that tile has read its starting len\n",
+                         2u + (unsigned)MAX_TICK_SAVES, 2u * (unsigned)MAX_TICK_STEPS);
+        s += GGRS_FRAME_TEXT;
+        s += need.peers ? GGRS_ENTITY_PEERS_TEXT : GGRS_ENTITY_TEXT;
+        s += GGRS_COMPONENT_TEXT;
+        s += GGRS_WORDS_TEXT;
+        s += jit_layout_text(L);
+    }
+    // ---- 2. user sources: systems, spawner, hashers, strategies -- each in a namespace of its own, under its own name in the compiler's messages
+    void user_sources() {
+        for (size_t i = 0; i < w->customs.size(); ++i) {
+            sfmt(s, "namespace ggrs_sys_%zu {\n#line 1 \"%s\"\n", i, file_name(w->customs[i].name).c_str());
+            s += w->customs[i].source;
+            s += "\n}\n";
+        }
+        if (spawn_sys >= 0 && w->systems[spawn_sys].kind == GGRS_SYS_SPAWN_CUSTOM) {
+            const ggrs_world::SpawnSys& sp = w->spawn_customs[w->systems[spawn_sys].comp[0]];
+            sfmt(s, "namespace ggrs_spawn_sys {\n#line 1 \"%s\"\n", file_name(sp.name).c_str());
+            s += sp.source;
+            s += "\n}\n";
+        }
+        for (uint32_t c : cks_comp) if (!w->comps[c].cks_source.empty()) {
+            sfmt(s, "namespace ggrs_hash_%u {\n#line 1 \"checksum_%s\"\n", c, w->comps[c].name.c_str());
+            s += w->comps[c].cks_source;
+            s += "\n}\n";
+        }
+        for (uint32_t c = 0; c < nc; ++c) if (rb(c) && strat(c)) {
+            sfmt(s, "namespace ggrs_strategy_%u {\n#line 1 \"strategy_%s\"\n", c, w->comps[c].name.c_str());
+            s += w->comps[c].strat_source;
+            s += "\n}\n";
+        }
+    }
+    // ---- 3. kernel head: ticket or fold-forward role, member record, LDS, inputs, tile mapping, the lane's slot
+    void kernel_head() {
+        s += "#line 1 \"ggrs_jit_tick\"\n";
+        s += "extern \"C\" __global__ __launch_bounds__(256) void ggrs_jit_tick(GgrsJitArgs a) {\n"
+             "    const uint32_t tid = threadIdx.x, lane = tid & 63u;\n"
+             "    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));   // wave-uniform, and the compiler knows it\n";
+        if (need.devstream)
+            s += "    // STREAMED: this workgroup's tile is its ticket -- the order in which workgroups START, whatever order the dispatcher picks (no fold-forward role here)\n"
+                 "    __shared__ uint32_t s_tk;\n"
+                 "    if (tid == 0) s_tk = (uint32_t)(atomicAdd((unsigned long long*)a.sp_ctl, 1ull) - a.sp_ticket_base);\n"
+                 "    __syncthreads();\n";
+        else sfmt(s,
+                "    // FOLD-FORWARD role: the first ff_blocks workgroups (a multiple of 8: the XCD mapping below is unchanged) do not own a tile -- each folds one row\n"
+                "    // of partials the PREVIOUS launch on this stream left in device memory and hands the value, then its tag, to the host\n"
+                "    if (blockIdx.x < a.ff_blocks) {\n"
+                "        if (blockIdx.y == 0u && blockIdx.z == 0u && blockIdx.x < a.ff_nvals) {                   // ff_nvals = rows x chunks per row (ff_split)\n"
+                "            const uint32_t row = blockIdx.x / a.ff_split, ck = blockIdx.x %% a.ff_split, per = (a.ff_g + a.ff_split - 1u) / a.ff_split;\n"
+                "            ff_fold_row((const uint64_t*)a.ff_rows + (uint64_t)row * a.ff_stride * (a.ff_self ? 2u : 1u), a.ff_istride,     // (self-fold: 16-byte cells)\n"
+                "                        ck * per, min(a.ff_g, (ck + 1u) * per), (row %% %uu) == %uu,\n"
+                "                        (uint64_t*)a.ff_out + 2u * blockIdx.x, (uint64_t)a.ff_seq, a.ff_self ? (uint64_t)a.ff_seq : 0ull);   // cell blockIdx.x: {value, tag}\n"
+                "        }\n"
+                "        return;\n"
+                "    }\n"
+                "    const uint32_t bx = blockIdx.x - a.ff_blocks, gx = gridDim.x - a.ff_blocks;\n", n_cks + 1, n_cks);
+        sfmt(s,
+                "    // batch members (blockIdx.z) with records: what differs between the launch's groups comes from member z's record, the rest from the argument block\n"
+                "    const GGRS_K unsigned char* const mb = a.mtab ? (const GGRS_K unsigned char*)(unsigned long)(a.mtab + (uint64_t)blockIdx.z * %uull) : (const GGRS_K unsigned char*)0ul;\n"
+                "    const bool writes_live = (!a.src_is_live || a.n_steps) && !a.skip_live;\n"
+                "    const uint32_t o_first = a.dp_s ? blockIdx.y * a.dp_s : 0u;          // depth-parallel roles: this workgroup's share of the outputs\n"
+                "    const uint32_t o_last = a.dp_s ? min(o_first + a.dp_s, a.n_saves + 1u) : a.n_saves + 1u;\n"
+                "    const bool my_live = o_last == a.n_saves + 1u;\n"
+                "    if (a.dp_s && o_first == a.n_saves && !writes_live) return;\n"
+                "    // per-workgroup checksum partials [Save][component .. live count]: the waves fold into LDS\n"
+                "    __shared__ ggrs_u64 s_acc[16 * %u];\n"
+                "%s"
+                "    for (uint32_t i = tid; i < 16u * %uu; i += 256u) s_acc[i] = 0;\n",
+             L.m.bytes, n_cks + 1,
+             need.vtags ? "    __shared__ ggrs_u64 s_skip;                                                // value tags, profiling: bytes this workgroup's Saves did not store\n    if (tid == 0) s_skip = 0;\n" : "",
+             n_cks + 1);
+        if (lane_fold) sfmt(s, "    extern __shared__ ggrs_u64 s_lane[];                                  // [Save][checksummed component][lane]: a.n_saves * %u * 64 cells (dynamic LDS)\n"
+                               "    for (uint32_t i = tid; i < a.n_saves * %uu; i += 256u) s_lane[i] = 0;\n", n_cks, n_cks * 64u);
+        if (lds_inputs && IN_STRIDE)
+            sfmt(s, "    __shared__ unsigned char s_in[%u * %u];                                  // PlayerInputs of every step of the group: [step][%u players x %u bytes | %u status bytes]\n"
+                    "    for (uint32_t i = tid; i < a.n_steps * %uu; i += 256u) s_in[i] = mb ? (unsigned char)mb_u8(mb, %uu + i) : a.inputs[i / %uu][i %% %uu];\n", L.cap_steps, IN_STRIDE, MAXP, IB, MAXP, IN_STRIDE, L.m.inputs, IN_STRIDE, IN_STRIDE);
+        if (need.devstream) s += "    __syncthreads();\n"
+                                 "    const uint32_t tile = s_tk;                                               // ticket order == tile order (no XCD remap: look-back needs it)\n"
+                                 "    if (tile * 4u >= a.n_units) return;\n"
+                                 "    {\n"
+                                 "    const uint32_t gu = tile * 4u + wave;                                     // this wave's 64-slot unit == its mask word\n";
+        else
+        s += "    __syncthreads();\n"
+             "    // XCD-aware tile mapping: workgroup b runs on XCD b % 8 (observed placement; used for speed only), and each XCD has its own\n"
+             "    // L2.  Handing XCD x the x-th CONTIGUOUS eighth of the tiles makes the workgroups that write neighbouring 1 KiB pieces of a\n"
+             "    // row share one L2, which merges them into long runs before they go to memory -- instead of every L2 seeing every 8th piece.\n"
+             "    const uint32_t g8 = gx >> 3;                                              // the grid is 8 x ceil(tiles / 8) workgroups (+ the fold-forward ones)\n"
+             "    const uint32_t tile = (bx & 7u) * g8 + (bx >> 3);\n"
+             "    if (tile * 4u >= a.n_units) return;                                       // padding workgroup of the last eighth\n"
+             "    {\n"
+             "    const uint32_t gu = tile * 4u + wave;                                     // this wave's 64-slot unit == its mask word\n";
+        sfmt(s, "    const uint64_t e0 = (uint64_t)gu * 64u + lane;                             // this lane's slot\n"
+                "%s"
+                "    %sbool in_len = (uint64_t)gu * 64u < %s;                                 // wave-uniform%s\n"
+                "    // word c of slot e lives at col_off[c] + (e >> 13) * tile_stride + (e & 8191) * word_bytes: the layout tile is the\n"
+                "    // wave's (uniform: SGPRs), the lane contributes one 32-bit offset per word size -> saddr-form accesses\n"
+                "    const uint64_t tbase = (uint64_t)(gu >> %d) * %uull;\n"
+                "    const uint32_t ei = (gu & %uu) * 64u + lane, lo1 = ei, lo2 = ei * 2u, lo4 = ei * 4u, lo8 = ei * 8u;\n"
+                "    (void)lo1; (void)lo2; (void)lo4; (void)lo8;\n"
+                "    const uint64_t wi8 = (uint64_t)gu * 8u;                                    // byte offset of this wave's mask word: bit `lane` is this slot\n"
+                "    const uint32_t sh = lane;\n",
+             need.devspawn ? "    uint64_t cur_len = *reinterpret_cast<const uint64_t*>(a.src);                // RollbackOrdered::len as the source block's header says: with spawns decided on the device the host only knows a bound\n"
+                             "    __shared__ uint64_t s_sp[16];                                              // the workgroup's spawn bookkeeping of one step\n" : "",
+             spawn_sys >= 0 ? "" : "const ", need.devspawn ? "cur_len" : "a.len", spawn_sys >= 0 ? " (a spawn inside the group grows len)" : "", LT_SHIFT - 6, w->ts, (unsigned)(LAYOUT_TILE / 64 - 1));
+        if (need.devstream)
+            s += "    // Only tiles at or above the END of the world -- the tile of slot len - 1 -- can hold children, and only they learn each step's total (from that tile's\n"
+                 "    // descriptor: a lower ticket).  A tile below it stays below it (len only grows inside a group), has parents at most, and never needs the total: its\n"
+                 "    // cur_len goes stale and it writes no len anywhere.  trk_: this tile still tracks cur_len exactly; the grid's last tile always does and writes it\n"
+                 "    bool trk_ = tile >= (uint32_t)(cur_len ? (cur_len - 1u) >> 8 : 0u);\n"
+                 "    const bool len_wr = tile == a.sp_tiles - 1u && wave == 0u && lane == 0u;         // the one lane that writes RollbackOrdered::len (headers, sp_len)\n"
+                 "    const uint64_t len0_ = cur_len;                                                  // len at the launch's start: exact in every tile\n"
+                 "    bool gated_ = false;                                                             // (the last tile: every tile has read its starting len)\n"
+                 "    // tile 0 starts the record-pool cursor over (before its first descriptor: every reservation of this launch follows a look-back that reaches one of\n"
+                 "    // tile 0's); every tile then says it has read its starting len\n"
+                 "    asm volatile(\"s_waitcnt vmcnt(0)\" ::: \"memory\");\n"
+                 "    __syncthreads();\n"
+                 "    if (tid == 0) {\n"
+                 "        if (tile == 0u) { (void)__hip_atomic_exchange(a.sp_ctl + 1, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); asm volatile(\"s_waitcnt vmcnt(0)\" ::: \"memory\"); }\n"
+                 "        sp_post(a.sp_desc + (uint64_t)GGRS_SP_READ * a.sp_tiles + tile, a.sp_epoch + 1u + GGRS_SP_READ, 1u);\n"
+                 "    }\n";
+    }
+    // ---- 4. unit head: masks and words of the lane's slot, the o/b macros of every column, the source block's words
+    void unit_head() {
+        sfmt(s, "    const uint64_t mk_alive = *reinterpret_cast<const uint64_t*>(a.src + %lluull + wi8);\n"
+                "    bool alive_0 = (mk_alive >> sh) & 1ull;\n", OFF_ALIVE);
+        // (worlds with non-rollback components: who was alive in the source block, for the `gone` ballot of a batch member at the end of the unit.  One VGPR, made opaque
+        // so that it is not rebuilt from mk_alive there: the word, or a.src to read it again, held in SGPRs across the unit costs the marker test world a wave per SIMD)
+        if (need.nr) s += "    uint32_t src_alive_v = alive_0 ? 1u : 0u; asm volatile(\"\" : \"+v\"(src_alive_v));\n";
+        for (uint32_t c = 0; c < nc; ++c) if (rb(c))
+            sfmt(s, "    const uint64_t mk%u = *reinterpret_cast<const uint64_t*>(a.src + %lluull + wi8);\n"
+                    "    %sbool p%u_0 = (mk%u >> sh) & 1ull;\n", c, (unsigned long long)w->off_present[c], spawn_sys >= 0 ? "" : "const ", c, c);
+        for (uint32_t c = 0; c < nc; ++c) if (rb(c)) {
+            for (uint32_t k = 0; k < w->comps[c].n_words; ++k) {
+                const uint32_t cl = col(c, k), wb = w->comps[c].word_bytes;
+                sfmt(s, "#define o%u(blk) (sgpr_base((blk) + (%lluull + tbase)) + lo%u)\n#define b%u(blk) ((blk) + (%lluull + tbase))\n    %s w%u_0 = 0;\n",
+                     cl, (unsigned long long)w->col_off[cl], wb, cl, (unsigned long long)w->col_off[cl], wtype(c), cl);
+            }
+            // a component under a Strategy: its Stored words have columns of their own (ring slots hold them, the live block holds the component)
+            for (uint32_t k = 0; k < w->comps[c].s_n_words; ++k) {
+                const uint32_t cl = scol(c, k), wb = w->comps[c].s_word_bytes;
+                sfmt(s, "#define o%u(blk) (sgpr_base((blk) + (%lluull + tbase)) + lo%u)\n#define b%u(blk) ((blk) + (%lluull + tbase))\n",
+                     cl, (unsigned long long)w->col_off[cl], wb, cl, (unsigned long long)w->col_off[cl]);
+            }
+        }
+        s += "    if (in_len) {\n";
+        emit_load("a.src", "a.load_rows", "        ");
+        s += "    }\n"
+             "    const uint64_t ordB_0 = sea_order_lane(e0);\n";
+    }
+    // ---- 5. loads / stores of the words of the lane's slot from / to a block, each guarded by its bit of a wave-uniform row mask
     // Row masks are wave-uniform.  The masks of a steady-state tick are known when the kernel is written -- a SaveWorld stores
     // exactly the columns some system writes (HOT), the source block is read for those plus what steps and checksums read -- so
     // each access block is emitted twice: straight-line for that mask (one scalar compare), column-by-column guards otherwise.
     // A component under a Strategy moves as a whole: any of its columns in the mask means `store` / `load` runs and all Stored words move.
-    const uint64_t HOT = jit_hot_cols(w), LOADHOT = HOT | jit_static_reads(w);
-    auto comp_mask = [&](uint32_t c) { uint64_t m = 0; for (uint32_t k = 0; k < w->comps[c].n_words; ++k) m |= 1ull << col(c, k); return m; };
-    auto each_col = [&](uint64_t only, const std::function<void(uint32_t, uint32_t)>& fn) {          // plain columns (not under a Strategy)
-        for (uint32_t c = 0; c < nc; ++c) if (rb(c) && !strat(c)) for (uint32_t k = 0; k < w->comps[c].n_words; ++k)
-            if ((only >> col(c, k)) & 1ull) fn(c, col(c, k));
-    };
-    auto each_strat = [&](uint64_t only, const std::function<void(uint32_t)>& fn) { for (uint32_t c = 0; c < nc; ++c) if (rb(c) && strat(c) && (only & comp_mask(c))) fn(c); };
+    std::string strat_guard(uint32_t c, const char* guard_mask) const {      // "if (<mask> & <the component's columns>) ", or nothing
+        char b[96] = "";
+        if (guard_mask) snprintf(b, sizeof b, "if (%s & 0x%llxull) ", guard_mask, (unsigned long long)comp_mask(c));
+        return b;
+    }
     // Strategy::load / update (strategy.rs:31-39): the Stored words of the snapshot -> the component's registers
-    auto emit_strat_load = [&](uint32_t c, const char* blk, const char* indent, bool nt, const char* guard_mask) {
+    void emit_strat_load(uint32_t c, const char* blk, const char* indent, bool nt, const char* guard_mask) {
         const Comp& cc = w->comps[c];
-        std::string g;
-        if (guard_mask) { char b[96]; snprintf(b, sizeof b, "if (%s & 0x%llxull) ", guard_mask, (unsigned long long)comp_mask(c)); g = b; }
-        sfmt(s, "%s%s{ GgrsWords st_, tg_;\n", indent, g.c_str());
+        sfmt(s, "%s%s{ GgrsWords st_, tg_;\n", indent, strat_guard(c, guard_mask).c_str());
         for (uint32_t k = 0; k < cc.s_n_words; ++k)
             sfmt(s, nt ? "%s    st_.w[%u] = __builtin_nontemporal_load((const GGRS_G %s*)o%u(%s));\n" : "%s    st_.w[%u] = *(const GGRS_G %s*)o%u(%s);\n", indent, k, mtype_b(cc.s_word_bytes), scol(c, k), blk);
         for (uint32_t k = 0; k < cc.n_words; ++k) sfmt(s, "%s    tg_.w[%u] = 0;\n", indent, k);
         sfmt(s, "%s    ggrs_strategy_%u::ggrs_load(st_, tg_);\n", indent, c);
         for (uint32_t k = 0; k < cc.n_words; ++k) sfmt(s, "%s    w%u_0 = (%s)(%s)tg_.w[%u];\n", indent, col(c, k), wtype(c), mtype(c), k);
         sfmt(s, "%s}\n", indent);
-    };
+    }
     // Strategy::store (strategy.rs:28-29): the component's registers -> the Stored words of a snapshot
-    auto emit_strat_store = [&](uint32_t c, const char* dst, const char* indent, bool nt, const char* guard_mask) {
+    void emit_strat_store(uint32_t c, const char* dst, const char* indent, bool nt, const char* guard_mask) {
         const Comp& cc = w->comps[c];
-        std::string g;
-        if (guard_mask) { char b[96]; snprintf(b, sizeof b, "if (%s & 0x%llxull) ", guard_mask, (unsigned long long)comp_mask(c)); g = b; }
-        sfmt(s, "%s%s{ GgrsWords tg_, st_;\n", indent, g.c_str());
+        sfmt(s, "%s%s{ GgrsWords tg_, st_;\n", indent, strat_guard(c, guard_mask).c_str());
         for (uint32_t k = 0; k < cc.n_words; ++k) sfmt(s, "%s    tg_.w[%u] = w%u_0;\n", indent, k, col(c, k));
         for (uint32_t k = 0; k < cc.s_n_words; ++k) sfmt(s, "%s    st_.w[%u] = 0;\n", indent, k);
         sfmt(s, "%s    ggrs_strategy_%u::ggrs_store(tg_, st_);\n", indent, c);
         for (uint32_t k = 0; k < cc.s_n_words; ++k)
             sfmt(s, "%s    st%u%s(b%u(%s), lo%u, (%s)st_.w[%u]);\n", indent, cc.s_word_bytes, nt ? "nt" : "", scol(c, k), dst, cc.s_word_bytes, wtype_b(cc.s_word_bytes), k);
         sfmt(s, "%s}\n", indent);
-    };
-    auto emit_load = [&](const char* blk, const char* mask, const char* indent) {
+    }
+    void emit_load(const char* blk, const char* mask, const char* indent) {
         const std::string in2 = std::string(indent) + "    ", in3 = in2 + "    ";
         sfmt(s, "%sif (%s == 0x%llxull) {\n", indent, mask, (unsigned long long)LOADHOT);
         sfmt(s, "%s  if (a.nt_loads) {\n", indent);
@@ -907,8 +1122,8 @@ bool jit_source(const ggrs_world* w, std::string& s) {
             each_strat(~0ull, [&](uint32_t c) { emit_strat_load(c, blk, in2.c_str(), false, mask); });
             sfmt(s, "%s}\n", indent);
         }
-    };
-    auto emit_words_out = [&](const char* dst, const char* mask, const char* indent, bool nt, bool to_ring) {
+    }
+    void emit_words_out(const char* dst, const char* mask, const char* indent, bool nt, bool to_ring) {
         auto one = [&](uint32_t c, uint32_t cl, const char* ind, bool guard) {
             char g[64] = "";
             if (guard) snprintf(g, sizeof g, "if ((%s >> %uu) & 1ull) ", mask, cl);
@@ -925,8 +1140,8 @@ bool jit_source(const ggrs_world* w, std::string& s) {
         if (to_ring) each_strat(~0ull, [&](uint32_t c) { emit_strat_store(c, dst, in2.c_str(), nt, mask); });
         else for (uint32_t c = 0; c < nc; ++c) if (rb(c) && strat(c)) for (uint32_t k = 0; k < w->comps[c].n_words; ++k) one(c, col(c, k), in2.c_str(), true);
         sfmt(s, "%s}\n", indent);
-    };
-    auto emit_store = [&](const char* dst, const char* mask, const char* pmask, const char* alive_word, const char* indent, bool nt_variant) {
+    }
+    void emit_store(const char* dst, const char* mask, const char* pmask, const char* alive_word, const char* indent, bool nt_variant) {
         std::string in2 = std::string(indent) + "    ", in3 = in2 + "    ";
         sfmt(s, "%sif (in_len) {\n", indent);
         if (nt_variant) {
@@ -947,46 +1162,44 @@ bool jit_source(const ggrs_world* w, std::string& s) {
         for (uint32_t c = 0; c < nc; ++c) if (rb(c))
             sfmt(s, "%s    if ((%s >> %uu) & 1u) *reinterpret_cast<uint64_t*>(%s + %lluull + wi8) = %s%u;\n", indent, pmask, c, dst, (unsigned long long)w->off_present[c], spawn_sys >= 0 ? "pm" : "mk", c);
         sfmt(s, "%s}\n", indent);
-    };
-    s += "    if (in_len) {\n";
-    emit_load("a.src", "a.load_rows", "        ");
-    s += "    }\n"
-         "    const uint64_t ordB_0 = sea_order_lane(e0);\n";
-    // ---- value tags (host_world.hpp ggrs_world::vtags): lane c of `tn` holds the identity of column c's 64 values in this wave's unit.  Only worlds whose
-    // policy keeps tags (vtags_policy: a steady Save bound by bytes) carry the code at all: every other world's kernels are what they were without the feature
-    const bool VT = vtags_policy(w);
-    const uint32_t NTC = w->n_tcols, TAG_ROW = w->tag_row_bytes;
-    const unsigned long long OFF_TAGS = w->off_tags, TAGCOLS = w->tag_cols;
-    uint64_t wb_mask[4] = {0, 0, 0, 0};                              // columns by word size (1, 2, 4, 8 bytes): what a skipped column saves
-    for (uint32_t c = 0; c < nc; ++c) if (rb(c) && !strat(c)) for (uint32_t k = 0; k < w->comps[c].n_words; ++k) {
-        const uint32_t wb = w->comps[c].word_bytes; wb_mask[wb == 1 ? 0 : wb == 2 ? 1 : wb == 4 ? 2 : 3] |= 1ull << col(c, k);
     }
-    if (VT)
-    sfmt(s, "    // VALUE TAGS: lane c of tn = the identity of column c's 64 values in this unit (0: none).  Loaded with the unit, renewed by the step that changes any of\n"
-            "    // the 64 values, compared with the destination's tag at every store: equal non-zero tags mean equal bytes, and the column is not stored again\n"
-            "    uint32_t tn = 0u;\n"
-            "    uint64_t chg = 0ull;                                                        // wave-uniform: bit c = column c changed in this unit since tn was last brought up to date\n"
-            "    const uint32_t tag_mine = a.tag_base + blockIdx.z * (a.n_steps + 2u);        // ids this (member of the) launch may hand out: +0 at the load, +1+j at a store after j steps (j <= n_steps)\n"
-            "    const uint32_t tag_lane = lane < %uu ? lane : 0u;\n"
-            "    if (a.vtags && lane < %uu) {\n"
-            "        if (in_len && ((a.src_tagok >> lane) & 1ull)) tn = *reinterpret_cast<const uint32_t*>(a.src + %lluull + (uint64_t)gu * %uu + tag_lane * 4u);\n"
-            "        if (tn == 0u) tn = tag_mine;\n"
-            "    }\n"
-            "#ifdef GGRS_SPEC\n"
-            "    // A copy built for one op sequence (GGRS_SPEC: the op loop is unrolled, a.n_saves a literal) loads the tags of EVERY destination up front: a load issued\n"
-            "    // inside a Save would sit behind the previous Save's stores and its latency on the wave's critical path, once per Save.  A destination written twice by\n"
-            "    // one launch (a ring shallower than the group) is then compared with the tag it held BEFORE the launch: that can only cost a redundant store, never a\n"
-            "    // wrong skip (the value in hand carries the source's identity or one this launch made).\n"
-            "    uint32_t dtv[%u]; uint32_t dtl = 0u;\n"
-            "    for (uint32_t k_ = 0; k_ < a.n_saves; ++k_) {\n"
-            "        const unsigned char* d_ = mb ? (const unsigned char*)mb_u64(mb, %uu + 8u * k_) : a.save_dst[k_];\n"
-            "        dtv[k_] = (a.vtags && in_len && d_ && lane < %uu) ? *reinterpret_cast<const uint32_t*>(d_ + %lluull + (uint64_t)gu * %uu + tag_lane * 4u) : 0u;\n"
-            "    }\n"
-            "    if (a.vtags && in_len && writes_live && lane < %uu) dtl = *reinterpret_cast<const uint32_t*>((mb ? (const unsigned char*)mb_u64(mb, %uu) : a.live) + %lluull + (uint64_t)gu * %uu + tag_lane * 4u);\n"
-            "#endif\n", NTC, NTC, OFF_TAGS, TAG_ROW, L.cap_saves, L.m.save_dst, NTC, OFF_TAGS, TAG_ROW, NTC, L.m.live, OFF_TAGS, TAG_ROW);
+    // the statement of the STREAMED form after a store into `blk`: see sp_gate (kJitSpStreamed)
+    void emit_sp_gate(const char* indent, const char* blk) {
+        sfmt(s, "%sif (tile == a.sp_tiles - 1u && wave == 0u && !gated_ && (const unsigned char*)%s == a.src) {   // a write to the block every tile read len from\n"
+                "%s    gated_ = true;\n"
+                "%s    if (!sp_gate(a.sp_desc + (uint64_t)GGRS_SP_READ * a.sp_tiles, a.sp_tiles - 1u, a.sp_epoch + 1u + GGRS_SP_READ, lane) && lane == 0) a.sp_len[GGRS_SP_TIMEOUT] = 1ull;\n"
+                "%s}\n", indent, blk, indent, indent, indent);
+    }
+    // ---- 6. value tags (host_world.hpp ggrs_world::vtags): lane c of `tn` holds the identity of column c's 64 values in this wave's unit.  Only worlds whose
+    // policy keeps tags (vtags_policy: a steady Save bound by bytes) carry the code at all: every other world's kernels are what they were without the feature
+    void tag_head() {
+        if (need.vtags)
+        sfmt(s, "    // VALUE TAGS: lane c of tn = the identity of column c's 64 values in this unit (0: none).  Loaded with the unit, renewed by the step that changes any of\n"
+                "    // the 64 values, compared with the destination's tag at every store: equal non-zero tags mean equal bytes, and the column is not stored again\n"
+                "    uint32_t tn = 0u;\n"
+                "    uint64_t chg = 0ull;                                                        // wave-uniform: bit c = column c changed in this unit since tn was last brought up to date\n"
+                "    const uint32_t tag_mine = a.tag_base + blockIdx.z * (a.n_steps + 2u);        // ids this (member of the) launch may hand out: +0 at the load, +1+j at a store after j steps (j <= n_steps)\n"
+                "    const uint32_t tag_lane = lane < %uu ? lane : 0u;\n"
+                "    if (a.vtags && lane < %uu) {\n"
+                "        if (in_len && ((a.src_tagok >> lane) & 1ull)) tn = *reinterpret_cast<const uint32_t*>(a.src + %lluull + (uint64_t)gu * %uu + tag_lane * 4u);\n"
+                "        if (tn == 0u) tn = tag_mine;\n"
+                "    }\n"
+                "#ifdef GGRS_SPEC\n"
+                "    // A copy built for one op sequence (GGRS_SPEC: the op loop is unrolled, a.n_saves a literal) loads the tags of EVERY destination up front: a load issued\n"
+                "    // inside a Save would sit behind the previous Save's stores and its latency on the wave's critical path, once per Save.  A destination written twice by\n"
+                "    // one launch (a ring shallower than the group) is then compared with the tag it held BEFORE the launch: that can only cost a redundant store, never a\n"
+                "    // wrong skip (the value in hand carries the source's identity or one this launch made).\n"
+                "    uint32_t dtv[%u]; uint32_t dtl = 0u;\n"
+                "    for (uint32_t k_ = 0; k_ < a.n_saves; ++k_) {\n"
+                "        const unsigned char* d_ = mb ? (const unsigned char*)mb_u64(mb, %uu + 8u * k_) : a.save_dst[k_];\n"
+                "        dtv[k_] = (a.vtags && in_len && d_ && lane < %uu) ? *reinterpret_cast<const uint32_t*>(d_ + %lluull + (uint64_t)gu * %uu + tag_lane * 4u) : 0u;\n"
+                "    }\n"
+                "    if (a.vtags && in_len && writes_live && lane < %uu) dtl = *reinterpret_cast<const uint32_t*>((mb ? (const unsigned char*)mb_u64(mb, %uu) : a.live) + %lluull + (uint64_t)gu * %uu + tag_lane * 4u);\n"
+                "#endif\n", NTC, NTC, OFF_TAGS, TAG_ROW, L.cap_saves, L.m.save_dst, NTC, OFF_TAGS, TAG_ROW, NTC, L.m.live, OFF_TAGS, TAG_ROW);
+    }
     // a store into `blk` under the column mask `rows` (a non-const uint64_t in scope): columns whose tag the block already holds drop out of the mask
-    auto emit_tag_filter = [&](const char* blk, const char* rows, const char* tagok_expr, const char* indent, const char* prefetched) {
-        if (!VT) return;
+    void emit_tag_filter(const char* blk, const char* rows, const char* tagok_expr, const char* indent, const char* prefetched) {
+        if (!need.vtags) return;
         std::string weight;                                          // bytes one slot saves when the columns of `same_` are not stored
         for (int k = 0; k < 4; ++k) if (wb_mask[k]) { char b[96]; snprintf(b, sizeof b, "%s%uu * __popcll(same_ & 0x%llxull)", weight.empty() ? "" : " + ", 1u << k, (unsigned long long)wb_mask[k]); weight += b; }
         sfmt(s, "%sif (a.vtags && chg) { set_lanes(tn, chg, tag_mine + 1u + sj); chg = 0ull; }      // what changed since the last store: a fresh identity (sj = steps so far)\n", indent);
@@ -1004,10 +1217,9 @@ bool jit_source(const ggrs_world* w, std::string& s) {
                 "%s}\n",
              indent, indent, blk, OFF_TAGS, TAG_ROW, indent, prefetched, indent, indent, tagok_expr, rows, TAGCOLS, indent, rows, indent, rows,
              (unsigned long long)(NTC >= 64 ? ~0ull : ((1ull << NTC) - 1ull)), indent, weight.empty() ? "0u" : weight.c_str(), indent);
-    };
-    // which word-list specs take the memoised form: 9..12 hashed bytes whose byte 8.. tail is made of whole fields
-    std::vector<uint32_t> spec_bytes(n_cks, 0); std::vector<uint8_t> spec_memo(n_cks, 0);
-    auto chunk_expr = [&](const Comp& cc, uint32_t c, uint32_t first, uint32_t nbytes) {      // bytes [first, first + nbytes) of the hashed stream as a u64 expression
+    }
+    // ---- 7. what the unit keeps across the op loop besides its words: checksum memos, markers, live-only columns a system reads
+    std::string chunk_expr(const Comp& cc, uint32_t c, uint32_t first, uint32_t nbytes) const {      // bytes [first, first + nbytes) of the hashed stream as a u64 expression
         std::string e; uint32_t pos = 0; char buf[160];
         for (uint32_t wi : cc.cks_words) {
             const uint32_t wb = cc.word_bytes, lo = std::max(pos, first), hi = std::min(pos + wb, first + nbytes);
@@ -1019,58 +1231,58 @@ bool jit_source(const ggrs_world* w, std::string& s) {
             pos += wb;
         }
         return e.empty() ? std::string("0ull") : e;
-    };
-    for (uint32_t k = 0; k < n_cks; ++k) {
-        const Comp& cc = w->comps[cks_comp[k]];
-        if (!cc.cks_source.empty()) continue;
-        spec_bytes[k] = (uint32_t)cc.cks_words.size() * cc.word_bytes;
-        spec_memo[k] = spec_bytes[k] > 8 && spec_bytes[k] <= 12;
-        if (spec_memo[k]) {
-            const std::string tail = chunk_expr(cc, cks_comp[k], 8, spec_bytes[k] - 8);
+    }
+    void unit_state() {
+        for (uint32_t k = 0; k < n_cks; ++k) if (spec_memo[k]) {
+            const std::string tail = chunk_expr(w->comps[cks_comp[k]], cks_comp[k], 8, spec_bytes[k] - 8);
             sfmt(s, "    uint32_t mt%u = (uint32_t)(%s); uint64_t ma%u = a.n_saves ? sea_diffuse(SEA_K1 ^ (uint64_t)mt%u) : 0ull;   // memoised tail of checksum spec %u\n", k, tail.c_str(), k, k, k);
         }
+        if (need.marks) {
+            sfmt(s, "    // RollbackDespawned markers (despawn.rs:45-46): live-only, never part of a snapshot\n"
+                    "    const uint64_t mk_dis = *reinterpret_cast<const uint64_t*>(a.live + %lluull + wi8);\n"
+                    "    bool dis_0 = (mk_dis >> sh) & 1ull;\n"
+                    "    int df_0 = *reinterpret_cast<const int*>(a.live + %lluull + e0 * 4u);\n", OFF_DIS, OFF_DF);
+        }
+        // live-only columns a built-in system READS (BOX_MOVE: Player.handle when Player is not registered for rollback)
+        for (size_t i = 0; i < w->systems.size(); ++i) {
+            const ggrs_system_desc& d = w->systems[i];
+            if (d.kind != GGRS_SYS_BOX_MOVE || rb(d.comp[2])) continue;
+            const uint32_t hc = col(d.comp[2], d.word[2]);
+            sfmt(s, "    const uint64_t side_mk%zu = *reinterpret_cast<const uint64_t*>(a.live + %lluull + wi8);\n"
+                    "    const bool side_p%zu_0 = (side_mk%zu >> sh) & 1ull; const uint64_t side_h%zu_0 = *reinterpret_cast<const uint64_t*>(a.live + %lluull + (e0 >> %d) * %uull + (e0 & %uull) * 8ull);\n",
+                 i, (unsigned long long)w->off_present[d.comp[2]], i, i, i, (unsigned long long)w->col_off[hc], LT_SHIFT, w->col_ts[hc], (unsigned)(LAYOUT_TILE - 1));
+        }
     }
-    if (marks) {
-        sfmt(s, "    // RollbackDespawned markers (despawn.rs:45-46): live-only, never part of a snapshot\n"
-                "    const uint64_t mk_dis = *reinterpret_cast<const uint64_t*>(a.live + %lluull + wi8);\n"
-                "    bool dis_0 = (mk_dis >> sh) & 1ull;\n"
-                "    int df_0 = *reinterpret_cast<const int*>(a.live + %lluull + e0 * 4u);\n", OFF_DIS, OFF_DF);
+    // ---- 8. the op loop and its SaveWorld arm
+    void save_arm() {
+        s += "    uint32_t si = 0, sj = 0;\n"
+             "    for (uint32_t op = 0; op < a.n_ops; ++op) {\n"
+             "        if (!((a.op_bits >> op) & 1ull)) {\n"
+             "            // ---------------- SaveWorld\n"
+             "            if (si < o_first) { ++si; continue; }                          // another role's snapshot\n"
+             "            if (si >= o_last) break;\n"
+             "            const uint64_t alive_now = __ballot(alive_0);\n";
+        sfmt(s, "            unsigned char* dst = mb ? (unsigned char*)mb_u64(mb, %uu + 8u * si) : a.save_dst[si];\n"
+                "            if (dst) {\n"
+                "                uint64_t rows = mb ? mb_u64(mb, %uu + 8u * si) : a.save_rows[si];\n"
+                "                const uint32_t pmask_s = mb ? mb_u32(mb, %uu + 4u * si) : a.save_pmask[si];\n", L.m.save_dst, L.m.save_rows, L.m.save_pmask);
+        { char te[96]; snprintf(te, sizeof te, "(mb ? mb_u64(mb, %uu + 8u * si) : a.save_tagok[si])", L.m.save_tagok); emit_tag_filter("dst", "rows", te, "                ", "dtv[si]"); }
+        emit_store("dst", "rows", "pmask_s", "alive_now", "                ", true);
+        if (need.devstream) emit_sp_gate("                ", "dst");
+        sfmt(s, "                if (%s) {\n"
+                "                    Header h; h.len = %s; h.frame = a.save_frame[si]; h.pad0 = 0; h.active = 0; h.checksum[0] = 0; h.checksum[1] = 0;\n"
+                "                    *reinterpret_cast<Header*>(dst) = h;\n"
+                "                }\n"
+                "            }\n", need.devstream ? "len_wr" : "gu == 0 && lane == 0", need.devspawn ? "cur_len" : (std::string("mb ? mb_u64(mb, ") + std::to_string(L.m.save_len) + "u + 8u * si) : a.save_len[si]").c_str());
+        if (need.devstream) s += "            if (len_wr) a.sp_len[2u + si] = cur_len;                                   // RollbackOrdered::len at this Save: k_gen_finalize's entity checksum and the host read it here\n";
+        else if (need.devspawn) s += "            if (gu == 0 && lane == 0) a.sp_len[2u + si] = cur_len;                        // RollbackOrdered::len at this Save: k_gen_finalize's entity checksum and the host read it here\n";
+        sfmt(s, "            ggrs_u64* acc = s_acc + si * %uu;                                 // this Save's partials of the workgroup (LDS)\n", n_cks + 1);
+        for (uint32_t k = 0; k < n_cks; ++k) emit_checksum(k);
+        sfmt(s, "            if (lane == 0) atomicAdd(&acc[%u], (ggrs_u64)__popcll(alive_now));\n"
+                "            ++si;\n"
+                "            if (si >= o_last) break;\n", n_cks);
     }
-    // live-only columns a built-in system READS (BOX_MOVE: Player.handle when Player is not registered for rollback)
-    for (size_t i = 0; i < w->systems.size(); ++i) {
-        const ggrs_system_desc& d = w->systems[i];
-        if (d.kind != GGRS_SYS_BOX_MOVE || rb(d.comp[2])) continue;
-        const uint32_t hc = col(d.comp[2], d.word[2]);
-        sfmt(s, "    const uint64_t side_mk%zu = *reinterpret_cast<const uint64_t*>(a.live + %lluull + wi8);\n"
-                "    const bool side_p%zu_0 = (side_mk%zu >> sh) & 1ull; const uint64_t side_h%zu_0 = *reinterpret_cast<const uint64_t*>(a.live + %lluull + (e0 >> %d) * %uull + (e0 & %uull) * 8ull);\n",
-             i, (unsigned long long)w->off_present[d.comp[2]], i, i, i, (unsigned long long)w->col_off[hc], LT_SHIFT, w->col_ts[hc], (unsigned)(LAYOUT_TILE - 1));
-    }
-    s += "    uint32_t si = 0, sj = 0;\n"
-         "    for (uint32_t op = 0; op < a.n_ops; ++op) {\n"
-         "        if (!((a.op_bits >> op) & 1ull)) {\n"
-         "            // ---------------- SaveWorld\n"
-         "            if (si < o_first) { ++si; continue; }                          // another role's snapshot\n"
-         "            if (si >= o_last) break;\n"
-         "            const uint64_t alive_now = __ballot(alive_0);\n";
-    sfmt(s, "            unsigned char* dst = mb ? (unsigned char*)mb_u64(mb, %uu + 8u * si) : a.save_dst[si];\n"
-            "            if (dst) {\n"
-            "                uint64_t rows = mb ? mb_u64(mb, %uu + 8u * si) : a.save_rows[si];\n"
-            "                const uint32_t pmask_s = mb ? mb_u32(mb, %uu + 4u * si) : a.save_pmask[si];\n", L.m.save_dst, L.m.save_rows, L.m.save_pmask);
-    { char te[96]; snprintf(te, sizeof te, "(mb ? mb_u64(mb, %uu + 8u * si) : a.save_tagok[si])", L.m.save_tagok); emit_tag_filter("dst", "rows", te, "                ", "dtv[si]"); }
-    emit_store("dst", "rows", "pmask_s", "alive_now", "                ", true);
-    if (STREAM) sfmt(s, "                if (tile == a.sp_tiles - 1u && wave == 0u && !gated_ && (const unsigned char*)%s == a.src) {   // a write to the block every tile read len from\n"
-            "                    gated_ = true;\n"
-            "                    if (!sp_gate(a.sp_desc + (uint64_t)GGRS_SP_READ * a.sp_tiles, a.sp_tiles - 1u, a.sp_epoch + 1u + GGRS_SP_READ, lane) && lane == 0) a.sp_len[GGRS_SP_TIMEOUT] = 1ull;\n"
-            "                }\n", "dst");
-    sfmt(s, "                if (%s) {\n"
-            "                    Header h; h.len = %s; h.frame = a.save_frame[si]; h.pad0 = 0; h.active = 0; h.checksum[0] = 0; h.checksum[1] = 0;\n"
-            "                    *reinterpret_cast<Header*>(dst) = h;\n"
-            "                }\n"
-            "            }\n", STREAM ? "len_wr" : "gu == 0 && lane == 0", DEV ? "cur_len" : (std::string("mb ? mb_u64(mb, ") + std::to_string(L.m.save_len) + "u + 8u * si) : a.save_len[si]").c_str());
-    if (STREAM) s += "            if (len_wr) a.sp_len[2u + si] = cur_len;                                   // RollbackOrdered::len at this Save: k_gen_finalize's entity checksum and the host read it here\n";
-    else if (DEV) s += "            if (gu == 0 && lane == 0) a.sp_len[2u + si] = cur_len;                        // RollbackOrdered::len at this Save: k_gen_finalize's entity checksum and the host read it here\n";
-    sfmt(s, "            ggrs_u64* acc = s_acc + si * %uu;                                 // this Save's partials of the workgroup (LDS)\n", n_cks + 1);
-    for (uint32_t k = 0; k < n_cks; ++k) {
+    void emit_checksum(uint32_t k) {
         const uint32_t c = cks_comp[k];
         const Comp& cc = w->comps[c];
         s += "            {   // ComponentChecksumPlugin::update (component_checksum.rs:77-90): per-entity hash, paired with the order index\n"
@@ -1101,140 +1313,147 @@ bool jit_source(const ggrs_world* w, std::string& s) {
                 "                if (lane == 0) atomicXor(&acc[%u], (ggrs_u64)hx);\n"
                 "            }\n", k);
     }
-    sfmt(s, "            if (lane == 0) atomicAdd(&acc[%u], (ggrs_u64)__popcll(alive_now));\n"
-            "            ++si;\n"
-            "            if (si >= o_last) break;\n"
-            "        } else {\n"
-            "            // ---------------- AdvanceWorld: the registered systems, in order\n"
-            "            const float dt = __uint_as_float(a.dt_bits[sj]);\n", n_cks);
-    if (DEV) s += "            uint32_t spn_0 = 0u;                                                       // children this entity's systems asked for in this frame (e.spawn(n))\n";
-    if (STREAM) s += "            ggrs_u64 pw_[8] = {0, 0, 0, 0, 0, 0, 0, 0};                               // ... and the bound words that call left: its children's payload\n";
+    // ---- 9. the AdvanceWorld arm: the registered systems, in order
     // value tags: around every system, the columns IT may write as they were before it ran -- a column whose 64 values are not all what they were carries a
     // fresh identity from here on (wave-uniform; per system, so that at most one write set of old values is alive at a time)
     // (a step only RECORDS which columns changed -- one compare per column and scalar bookkeeping; the identities are renewed where they are needed, at the next store)
-    auto sys_det = [&](size_t si) { uint64_t m = 0; for (uint32_t c : w->sys_writes[si]) if (c < 64) m |= 1ull << c; return VT ? (m & w->tag_cols) : 0ull; };
+    uint64_t sys_det(size_t si) const { uint64_t m = 0; for (uint32_t c : w->sys_writes[si]) if (c < 64) m |= 1ull << c; return need.vtags ? (m & w->tag_cols) : 0ull; }
     // detection around a piece of code that writes `cols`: old values in, comparison out
-    auto det_in = [&](uint64_t cols) { if (!cols) return; s += "            {\n"; each_col(cols, [&](uint32_t c, uint32_t cl) { sfmt(s, "            const %s o%u_ = w%u_0;\n", wtype(c), cl, cl); }); };
-    auto det_out = [&](uint64_t cols) {
+    void det_in(uint64_t cols) { if (!cols) return; s += "            {\n"; each_col(cols, [&](uint32_t c, uint32_t cl) { sfmt(s, "            const %s o%u_ = w%u_0;\n", wtype(c), cl, cl); }); }
+    void det_out(uint64_t cols) {
         if (!cols) return;
         s += "            if (a.vtags) {\n";
         each_col(cols, [&](uint32_t, uint32_t cl) { sfmt(s, "                chg |= (__ballot(w%u_0 != o%u_) != 0ull) ? 0x%llxull : 0ull;\n", cl, cl, 1ull << cl); });
         s += "            }\n            }\n";
-    };
-    if (marks) {
-        s += "            const uint32_t sflags = a.step_flags[sj];\n"
-             "            const bool defer = sflags & 2u;                                            // despawn_rollback() defers (despawn.rs:129-137)\n"
-             "            if ((sflags & 1u) && dis_0 && df_0 <= a.step_confirmed[sj]) dis_0 = false;   // DespawnConfirmed (despawn.rs:89-112)\n";
     }
     // PlayerInputs<T> of the step as user code sees it (src/lib.rs:98): bytes in LDS
-    auto emit_frame = [&](const char* name, const float* fparam, const int64_t* iparam) {
+    void emit_frame(const char* name, const float* fparam, const int64_t* iparam) {
         sfmt(s, "            GgrsFrame %s; %s.dt = dt; %s.frame = a.step_frame[sj]; %s.n_inputs = mb ? mb_u8(mb, %uu + sj) : a.n_inputs[sj]; %s.input_bytes = %uu;\n"
                 "            %s.input.p = s_in + sj * %uu; %s.input.ib = %uu; %s.status = s_in + sj * %uu + %uu;\n",
              name, name, name, name, L.m.n_inputs, name, IB, name, IN_STRIDE, name, IB, name, IN_STRIDE, MAXP * IB);
         for (int k = 0; k < 4; ++k) sfmt(s, "            %s.fparam[%d] = %s;\n", name, k, f32_lit(fparam[k]).c_str());
         sfmt(s, "            %s.iparam[0] = %lldll; %s.iparam[1] = %lldll;\n", name, (long long)iparam[0], name, (long long)iparam[1]);
-    };
-    for (size_t i = 0; i < w->systems.size(); ++i) {
-        const ggrs_system_desc& d = w->systems[i];
-        if (d.kind == GGRS_SYS_CUSTOM) { char nm[24]; snprintf(nm, sizeof nm, "fr%zu", i); emit_frame(nm, d.fparam, d.iparam); }
-        const uint64_t det = d.kind == GGRS_SYS_PARTICLES_UPDATE ? 0ull : sys_det(i);      // (update_particles: per axis, below -- two old values alive at a time instead of six)
-        det_in(det);
-        switch (d.kind) {
-        case GGRS_SYS_PARTICLES_UPDATE: {
-            if (!sys_det(i)) {
-                sfmt(s, "            if (alive_0 && p%u_0 && p%u_0) {                                     // particles.rs:272-280\n", d.comp[0], d.comp[1]);
-                for (uint32_t k = 0; k < 3; ++k) {
-                    const uint32_t x = col(d.comp[0], d.word[0] + k), v = col(d.comp[1], d.word[1] + k);
-                    sfmt(s, "                { const float nv = __uint_as_float(w%u_0) + %s * dt; w%u_0 = __float_as_uint(nv); w%u_0 = __float_as_uint(__uint_as_float(w%u_0) + nv * dt); }\n",
-                         v, f32_lit(d.fparam[k]).c_str(), v, x, x);
-                }
-                s += "            }\n";
-            } else {
-                // value tags: axis by axis, each with its detection -- two old values alive at a time instead of six (the comparison sits outside the
-                // per-lane branch: __ballot needs every lane)
-                for (uint32_t k = 0; k < 3; ++k) {
-                    const uint32_t x = col(d.comp[0], d.word[0] + k), v = col(d.comp[1], d.word[1] + k);
-                    const uint64_t m = ((1ull << x) | (1ull << v)) & sys_det(i);
-                    det_in(m);
-                    sfmt(s, "            if (alive_0 && p%u_0 && p%u_0) { const float nv = __uint_as_float(w%u_0) + %s * dt; w%u_0 = __float_as_uint(nv); w%u_0 = __float_as_uint(__uint_as_float(w%u_0) + nv * dt); }   // particles.rs:272-280\n",
-                         d.comp[0], d.comp[1], v, f32_lit(d.fparam[k]).c_str(), v, x, x);
-                    det_out(m);
-                }
-            }
-        } break;
-        case GGRS_SYS_TTL_DESPAWN: {
-            const uint32_t q = col(d.comp[0], d.word[0]);
-            sfmt(s, "            if (alive_0 && p%u_0) { w%u_0 -= 1; if (w%u_0 == 0) alive_0 = false; }      // particles.rs:282-289\n", d.comp[0], q, q);
-        } break;
-        case GGRS_SYS_ADD_U32: {
-            const uint32_t q = col(d.comp[0], d.word[0]);
-            sfmt(s, "            if (alive_0 && p%u_0) w%u_0 += %uu;                                    // benches/bench.rs:30-46\n", d.comp[0], q, (uint32_t)d.iparam[0]);
-        } break;
-        case GGRS_SYS_SAT_SUB_DESPAWN: {
-            const uint32_t q = col(d.comp[0], d.word[0]);
-            sfmt(s, "            if (alive_0 && p%u_0) {                                              // tests/synctest.rs:37-44\n"
-                    "                w%u_0 = w%u_0 >= %uu ? w%u_0 - %uu : 0u;\n"
-                    "                if (w%u_0 == 0) {\n", d.comp[0], q, q, (uint32_t)d.iparam[0], q, (uint32_t)d.iparam[0], q);
-            if (d.iparam[1] == GGRS_DESPAWN_ROLLBACK) s += "                    if (defer) { dis_0 = true; df_0 = a.step_frame[sj]; }\n";
-            s += "                    alive_0 = false;\n                }\n            }\n";
-        } break;
-        case GGRS_SYS_BOX_MOVE: {
-            const bool h_rb = rb(d.comp[2]);
-            char hp[64], hv[64];
-            if (h_rb) { snprintf(hp, sizeof hp, "p%u_0", d.comp[2]); snprintf(hv, sizeof hv, "w%u_0", col(d.comp[2], d.word[2])); }
-            else { snprintf(hp, sizeof hp, "side_p%zu_0", i); snprintf(hv, sizeof hv, "side_h%zu_0", i); }
-            const uint32_t x = col(d.comp[0], d.word[0]), v = col(d.comp[1], d.word[1]);
-            sfmt(s, "            if (alive_0 && p%u_0 && p%u_0 && %s && %s < (mb ? mb_u8(mb, %uu + sj) : (uint32_t)a.n_inputs[sj])) {               // box_game.rs:154-206\n"
-                    "                float x = __uint_as_float(w%u_0), y = __uint_as_float(w%u_0), z = __uint_as_float(w%u_0);\n"
-                    "                float vx = __uint_as_float(w%u_0), vy = __uint_as_float(w%u_0), vz = __uint_as_float(w%u_0);\n",
-                 d.comp[0], d.comp[1], hp, hv, L.m.n_inputs, x, x + 1, x + 2, v, v + 1, v + 2);
-            sfmt(s, "                box_move_math(x, y, z, vx, vy, vz, mb ? (uint8_t)mb_u8(mb, %uu + sj * %uu + (uint32_t)(%s * %uu)) : a.inputs[sj][%s * %uu], dt, __uint_as_float(a.aux_bits[sj]), %s, %s, %s);\n"
-                    "                w%u_0 = __float_as_uint(x); w%u_0 = __float_as_uint(y); w%u_0 = __float_as_uint(z);\n"
-                    "                w%u_0 = __float_as_uint(vx); w%u_0 = __float_as_uint(vy); w%u_0 = __float_as_uint(vz);\n"
-                    "            }\n",
-                 L.m.inputs, IN_STRIDE, hv, IB, hv, IB, f32_lit(d.fparam[0]).c_str(), f32_lit(d.fparam[1]).c_str(), f32_lit(d.fparam[3]).c_str(), x, x + 1, x + 2, v, v + 1, v + 2);
-        } break;
-        case GGRS_SYS_CUSTOM: {
-            const ggrs_world::Custom& c = w->customs[d.comp[0]];
-            s += "            if (alive_0";
-            for (uint32_t pz = 0; pz < c.n_pres; ++pz) sfmt(s, " && p%u_0", c.pres_comp[pz]);
-            sfmt(s, ") {                                                   // user system %u\n"
-                    "                GgrsEntity ent; ent.slot = e0; ent.kill = 0; ent.spawn_n = 0;\n", d.comp[0]);
-            for (uint32_t b = 0; b < 8; ++b) { if (b < c.n_bind) sfmt(s, "                ent.w[%u] = w%u_0;\n", b, col(c.comp[b], c.word[b])); else if (DEV) sfmt(s, "                ent.w[%u] = 0;\n", b); }
-            if (c.n_peer) {
-                // peer bindings: binding j reads its column's linear array of the world's peer view (plain loads: the view was written by an earlier launch, many
-                // lanes of a CU read the same lines -- several followers of one target, neighbours in one 64-byte line --, so the L1 is wanted)
-                uint32_t pv_cols[GGRS_PEER_MAX_COLUMNS]; const uint32_t n_pv = std::min<uint32_t>(peer_cols(w, pv_cols), GGRS_PEER_MAX_COLUMNS);
-                s += "                ent.pv_.len = a.pv_len; ent.pv_.vis = (unsigned long)a.pv_vis;\n";
-                for (uint32_t j = 0; j < c.n_peer; ++j) {
-                    const uint32_t cl = col(c.pcomp[j], c.pword[j]);
-                    uint32_t at = 0; while (at < n_pv && pv_cols[at] != cl) ++at;
-                    if (at == n_pv) return false;
-                    sfmt(s, "                ent.pv_.col[%u] = (unsigned long)a.pv_col[%u]; ent.pv_.wb[%u] = %uu;\n", j, at, j, w->comps[c.pcomp[j]].word_bytes);
-                }
-            }
-            sfmt(s, "                ggrs_sys_%u::ggrs_system(ent, fr%zu);\n", d.comp[0], i);
-            if (STREAM) s += "                if (ent.spawn_n) {                                        // e.spawn(n): the children are made after the frame's systems, from what THIS call left in e\n"
-                             "                    spn_0 = (uint32_t)ent.spawn_n;\n"
-                             "                    for (int b_ = 0; b_ < 8; ++b_) pw_[b_] = ent.w[b_];                 // (written to the children's records once their slots are known)\n"
-                             "                }\n";
-            else if (DEV) s += "                if (ent.spawn_n) {                                        // e.spawn(n): the children are made after the frame's systems, from what THIS call left in e\n"
-                          "                    spn_0 = (uint32_t)ent.spawn_n;\n"
-                          "                    GGRS_G ggrs_u64* pr_ = (GGRS_G ggrs_u64*)(a.sp_prec + ((uint64_t)(sj & 1u) * a.sp_tiles * 256u + e0) * 64u);   // two sets of records, by step parity: see the children's read\n"
-                          "                    for (int b_ = 0; b_ < 8; ++b_) __hip_atomic_store(pr_ + b_, (ggrs_u64)ent.w[b_], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // sc1: read by another workgroup, maybe another XCD, later in this launch\n"
-                          "                }\n";
-            for (uint32_t b = 0; b < c.n_bind; ++b)
-                sfmt(s, "                w%u_0 = (%s)(%s)ent.w[%u];\n", col(c.comp[b], c.word[b]), wtype(c.comp[b]), mtype(c.comp[b]), b);   // narrow words wrap as their memory type does
-            if (marks) s += "                if (ent.kill) { if (ent.kill == 2 && defer) { dis_0 = true; df_0 = a.step_frame[sj]; } alive_0 = false; }\n";
-            else       s += "                if (ent.kill) alive_0 = false;                            // (no system of this world can defer a despawn: its sources name neither despawn_rollback() nor `kill`)\n";
-            s += ""
-                 "            }\n";
-        } break;
-        default: break;
-        }
-        det_out(det);
     }
-    if (spawn_sys >= 0) {
+    void advance_arm() {
+        s += "        } else {\n"
+             "            // ---------------- AdvanceWorld: the registered systems, in order\n"
+             "            const float dt = __uint_as_float(a.dt_bits[sj]);\n";
+        if (need.devspawn) s += "            uint32_t spn_0 = 0u;                                                       // children this entity's systems asked for in this frame (e.spawn(n))\n";
+        if (need.devstream) s += "            ggrs_u64 pw_[8] = {0, 0, 0, 0, 0, 0, 0, 0};                               // ... and the bound words that call left: its children's payload\n";
+        if (need.marks) {
+            s += "            const uint32_t sflags = a.step_flags[sj];\n"
+                 "            const bool defer = sflags & 2u;                                            // despawn_rollback() defers (despawn.rs:129-137)\n"
+                 "            if ((sflags & 1u) && dis_0 && df_0 <= a.step_confirmed[sj]) dis_0 = false;   // DespawnConfirmed (despawn.rs:89-112)\n";
+        }
+        for (size_t i = 0; i < w->systems.size(); ++i) {
+            const ggrs_system_desc& d = w->systems[i];
+            if (d.kind == GGRS_SYS_CUSTOM) { char nm[24]; snprintf(nm, sizeof nm, "fr%zu", i); emit_frame(nm, d.fparam, d.iparam); }
+            const uint64_t det = d.kind == GGRS_SYS_PARTICLES_UPDATE ? 0ull : sys_det(i);      // (update_particles: per axis, below -- two old values alive at a time instead of six)
+            det_in(det);
+            switch (d.kind) {
+            case GGRS_SYS_PARTICLES_UPDATE: sys_particles_update(i, d); break;
+            case GGRS_SYS_TTL_DESPAWN: sys_ttl_despawn(d); break;
+            case GGRS_SYS_ADD_U32: sys_add_u32(d); break;
+            case GGRS_SYS_SAT_SUB_DESPAWN: sys_sat_sub_despawn(d); break;
+            case GGRS_SYS_BOX_MOVE: sys_box_move(i, d); break;
+            case GGRS_SYS_CUSTOM: sys_custom(i, d); break;
+            default: break;
+            }
+            det_out(det);
+        }
+    }
+    void sys_particles_update(size_t i, const ggrs_system_desc& d) {
+        if (!sys_det(i)) {
+            sfmt(s, "            if (alive_0 && p%u_0 && p%u_0) {                                     // particles.rs:272-280\n", d.comp[0], d.comp[1]);
+            for (uint32_t k = 0; k < 3; ++k) {
+                const uint32_t x = col(d.comp[0], d.word[0] + k), v = col(d.comp[1], d.word[1] + k);
+                sfmt(s, "                { const float nv = __uint_as_float(w%u_0) + %s * dt; w%u_0 = __float_as_uint(nv); w%u_0 = __float_as_uint(__uint_as_float(w%u_0) + nv * dt); }\n",
+                     v, f32_lit(d.fparam[k]).c_str(), v, x, x);
+            }
+            s += "            }\n";
+        } else {
+            // value tags: axis by axis, each with its detection -- two old values alive at a time instead of six (the comparison sits outside the
+            // per-lane branch: __ballot needs every lane)
+            for (uint32_t k = 0; k < 3; ++k) {
+                const uint32_t x = col(d.comp[0], d.word[0] + k), v = col(d.comp[1], d.word[1] + k);
+                const uint64_t m = ((1ull << x) | (1ull << v)) & sys_det(i);
+                det_in(m);
+                sfmt(s, "            if (alive_0 && p%u_0 && p%u_0) { const float nv = __uint_as_float(w%u_0) + %s * dt; w%u_0 = __float_as_uint(nv); w%u_0 = __float_as_uint(__uint_as_float(w%u_0) + nv * dt); }   // particles.rs:272-280\n",
+                     d.comp[0], d.comp[1], v, f32_lit(d.fparam[k]).c_str(), v, x, x);
+                det_out(m);
+            }
+        }
+    }
+    void sys_ttl_despawn(const ggrs_system_desc& d) {
+        const uint32_t q = col(d.comp[0], d.word[0]);
+        sfmt(s, "            if (alive_0 && p%u_0) { w%u_0 -= 1; if (w%u_0 == 0) alive_0 = false; }      // particles.rs:282-289\n", d.comp[0], q, q);
+    }
+    void sys_add_u32(const ggrs_system_desc& d) {
+        const uint32_t q = col(d.comp[0], d.word[0]);
+        sfmt(s, "            if (alive_0 && p%u_0) w%u_0 += %uu;                                    // benches/bench.rs:30-46\n", d.comp[0], q, (uint32_t)d.iparam[0]);
+    }
+    void sys_sat_sub_despawn(const ggrs_system_desc& d) {
+        const uint32_t q = col(d.comp[0], d.word[0]);
+        sfmt(s, "            if (alive_0 && p%u_0) {                                              // tests/synctest.rs:37-44\n"
+                "                w%u_0 = w%u_0 >= %uu ? w%u_0 - %uu : 0u;\n"
+                "                if (w%u_0 == 0) {\n", d.comp[0], q, q, (uint32_t)d.iparam[0], q, (uint32_t)d.iparam[0], q);
+        if (d.iparam[1] == GGRS_DESPAWN_ROLLBACK) s += "                    if (defer) { dis_0 = true; df_0 = a.step_frame[sj]; }\n";
+        s += "                    alive_0 = false;\n                }\n            }\n";
+    }
+    void sys_box_move(size_t i, const ggrs_system_desc& d) {
+        const bool h_rb = rb(d.comp[2]);
+        char hp[64], hv[64];
+        if (h_rb) { snprintf(hp, sizeof hp, "p%u_0", d.comp[2]); snprintf(hv, sizeof hv, "w%u_0", col(d.comp[2], d.word[2])); }
+        else { snprintf(hp, sizeof hp, "side_p%zu_0", i); snprintf(hv, sizeof hv, "side_h%zu_0", i); }
+        const uint32_t x = col(d.comp[0], d.word[0]), v = col(d.comp[1], d.word[1]);
+        sfmt(s, "            if (alive_0 && p%u_0 && p%u_0 && %s && %s < (mb ? mb_u8(mb, %uu + sj) : (uint32_t)a.n_inputs[sj])) {               // box_game.rs:154-206\n"
+                "                float x = __uint_as_float(w%u_0), y = __uint_as_float(w%u_0), z = __uint_as_float(w%u_0);\n"
+                "                float vx = __uint_as_float(w%u_0), vy = __uint_as_float(w%u_0), vz = __uint_as_float(w%u_0);\n",
+             d.comp[0], d.comp[1], hp, hv, L.m.n_inputs, x, x + 1, x + 2, v, v + 1, v + 2);
+        sfmt(s, "                box_move_math(x, y, z, vx, vy, vz, mb ? (uint8_t)mb_u8(mb, %uu + sj * %uu + (uint32_t)(%s * %uu)) : a.inputs[sj][%s * %uu], dt, __uint_as_float(a.aux_bits[sj]), %s, %s, %s);\n"
+                "                w%u_0 = __float_as_uint(x); w%u_0 = __float_as_uint(y); w%u_0 = __float_as_uint(z);\n"
+                "                w%u_0 = __float_as_uint(vx); w%u_0 = __float_as_uint(vy); w%u_0 = __float_as_uint(vz);\n"
+                "            }\n",
+             L.m.inputs, IN_STRIDE, hv, IB, hv, IB, f32_lit(d.fparam[0]).c_str(), f32_lit(d.fparam[1]).c_str(), f32_lit(d.fparam[3]).c_str(), x, x + 1, x + 2, v, v + 1, v + 2);
+    }
+    void sys_custom(size_t i, const ggrs_system_desc& d) {
+        const ggrs_world::Custom& c = w->customs[d.comp[0]];
+        s += "            if (alive_0";
+        for (uint32_t pz = 0; pz < c.n_pres; ++pz) sfmt(s, " && p%u_0", c.pres_comp[pz]);
+        sfmt(s, ") {                                                   // user system %u\n"
+                "                GgrsEntity ent; ent.slot = e0; ent.kill = 0; ent.spawn_n = 0;\n", d.comp[0]);
+        for (uint32_t b = 0; b < 8; ++b) { if (b < c.n_bind) sfmt(s, "                ent.w[%u] = w%u_0;\n", b, col(c.comp[b], c.word[b])); else if (need.devspawn) sfmt(s, "                ent.w[%u] = 0;\n", b); }
+        if (c.n_peer) {
+            // peer bindings: binding j reads its column's linear array of the world's peer view (plain loads: the view was written by an earlier launch, many
+            // lanes of a CU read the same lines -- several followers of one target, neighbours in one 64-byte line --, so the L1 is wanted)
+            uint32_t pv_cols[GGRS_PEER_MAX_COLUMNS]; const uint32_t n_pv = std::min<uint32_t>(peer_cols(w, pv_cols), GGRS_PEER_MAX_COLUMNS);
+            s += "                ent.pv_.len = a.pv_len; ent.pv_.vis = (unsigned long)a.pv_vis;\n";
+            for (uint32_t j = 0; j < c.n_peer; ++j) {
+                const uint32_t cl = col(c.pcomp[j], c.pword[j]);
+                uint32_t at = 0; while (at < n_pv && pv_cols[at] != cl) ++at;      // (jit_covers: the column is in the view)
+                sfmt(s, "                ent.pv_.col[%u] = (unsigned long)a.pv_col[%u]; ent.pv_.wb[%u] = %uu;\n", j, at, j, w->comps[c.pcomp[j]].word_bytes);
+            }
+        }
+        sfmt(s, "                ggrs_sys_%u::ggrs_system(ent, fr%zu);\n", d.comp[0], i);
+        if (need.devstream) s += "                if (ent.spawn_n) {                                        // e.spawn(n): the children are made after the frame's systems, from what THIS call left in e\n"
+                                 "                    spn_0 = (uint32_t)ent.spawn_n;\n"
+                                 "                    for (int b_ = 0; b_ < 8; ++b_) pw_[b_] = ent.w[b_];                 // (written to the children's records once their slots are known)\n"
+                                 "                }\n";
+        else if (need.devspawn) s += "                if (ent.spawn_n) {                                        // e.spawn(n): the children are made after the frame's systems, from what THIS call left in e\n"
+                                     "                    spn_0 = (uint32_t)ent.spawn_n;\n"
+                                     "                    GGRS_G ggrs_u64* pr_ = (GGRS_G ggrs_u64*)(a.sp_prec + ((uint64_t)(sj & 1u) * a.sp_tiles * 256u + e0) * 64u);   // two sets of records, by step parity: see the children's read\n"
+                                     "                    for (int b_ = 0; b_ < 8; ++b_) __hip_atomic_store(pr_ + b_, (ggrs_u64)ent.w[b_], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // sc1: read by another workgroup, maybe another XCD, later in this launch\n"
+                                     "                }\n";
+        for (uint32_t b = 0; b < c.n_bind; ++b)
+            sfmt(s, "                w%u_0 = (%s)(%s)ent.w[%u];\n", col(c.comp[b], c.word[b]), wtype(c.comp[b]), mtype(c.comp[b]), b);   // narrow words wrap as their memory type does
+        if (need.marks) s += "                if (ent.kill) { if (ent.kill == 2 && defer) { dis_0 = true; df_0 = a.step_frame[sj]; } alive_0 = false; }\n";
+        else       s += "                if (ent.kill) alive_0 = false;                            // (no system of this world can defer a despawn: its sources name neither despawn_rollback() nor `kill`)\n";
+        s += ""
+             "            }\n";
+    }
+    // ---- 10. the spawn section
+    void spawn_section() {
+        if (spawn_sys < 0) return;
         // The spawn system, applied where Bevy applies its Commands: after the step's other systems.  The new rows are RollbackOrdered's next
         // indices == the next slots; a lane whose slot falls into the range takes the bundle -- every component of it at its registered
         // default, then what the spawner writes -- and its liveness and the bundle's presence bits are set.
@@ -1243,194 +1462,9 @@ bool jit_source(const ggrs_world* w, std::string& s) {
         uint64_t bundle = 0;
         if (custom) bundle = w->spawn_customs[d.comp[0]].bundle_mask; else bundle = (1ull << d.comp[0]) | (1ull << d.comp[1]) | (1ull << d.comp[2]);
         if (custom) emit_frame("fr_spawn", d.fparam, d.iparam);
-        if (STREAM) {
-            // How many, and whose -- streamed: the same exclusive scan over wave and workgroup; then, per step, a decoupled look-back over the tiles' descriptors
-            // (slot order == RollbackOrdered order, as in the resident form).  A parent tile reserves one record per child from the pool and writes the parent's
-            // bound words, then {epoch, k}, into each; a lane whose slot falls among the step's new rows finds its parent's tile by the inclusive prefixes (a binary
-            // search over tiles at or below the end of the world) and polls its own record.  The end-of-world tile's inclusive prefix is the step's total: tiles
-            // above it read that one descriptor.  Children beyond the capacity: those tiles ignore the records (nothing spawns), the end-of-world tile tells the host
-            s += "            uint64_t sn_ = 0, sf_ = cur_len;\n"
-                    "            unsigned long long kk_ = 0;\n"
-                    "            ggrs_u64 prec_[8] = {0, 0, 0, 0, 0, 0, 0, 0};                              // the payload of a child: its parent's record, fetched past this XCD's L2 (sc1)\n"
-                    "            {\n"
-                    "                uint32_t inc_ = spn_0;                                                 // inclusive scan over the wave's 64 lanes\n"
-                    "                for (int o_ = 1; o_ < 64; o_ <<= 1) { const uint32_t up_ = __shfl_up(inc_, o_, 64); if ((int)lane >= o_) inc_ += up_; }\n"
-                    "                const uint32_t wtot_ = (uint32_t)__builtin_amdgcn_readlane((int)inc_, 63);\n"
-                    "                __syncthreads();                                                       // (s_sp of the previous step has been read by everyone)\n"
-                    "                if (lane == 0) s_sp[wave] = wtot_;\n"
-                    "                __syncthreads();\n"
-                    "                uint32_t wg_excl_ = 0, wg_tot_ = 0;\n"
-                    "                for (uint32_t q_ = 0; q_ < 4u; ++q_) { const uint32_t v_ = (uint32_t)s_sp[q_]; wg_tot_ += v_; if (q_ < wave) wg_excl_ += v_; }\n"
-                    "                const uint32_t T_ = a.sp_tiles, ep_ = a.sp_epoch + 1u + sj;\n"
-                    "                ggrs_u64* const dsc_ = a.sp_desc + (uint64_t)sj * T_;                  // this step's descriptors, one per tile\n";
-            sfmt(s, "                ggrs_u64* const rof_ = a.sp_desc + (uint64_t)(%uu + sj) * T_;          // {epoch, first record} of each parent tile of this step\n", (unsigned)MAX_TICK_STEPS);
-            s += "                const unsigned long long tb_ = wall_clock64();\n"
-                    "                const uint32_t own_ = (uint32_t)(cur_len ? (cur_len - 1u) >> 8 : 0u);   // the end of the world (exact where trk_)\n"
-                    "                if (tile < own_) trk_ = false;\n"
-                    "                const bool above_ = trk_ && tile > own_;                               // no live slot: waits for the total instead of posting\n"
-                    "                if (wave == 0u) {\n"
-                    "                    bool ok_ = true; uint64_t exc_ = 0; uint32_t tot_ = 0;\n"
-                    "                    if (!above_) {\n"
-                    "                        if (lane == 0) sp_post(dsc_ + tile, ep_, min(wg_tot_, 0x7FFFFFFFu));      // the aggregate: what this tile adds\n"
-                    "                        for (uint32_t hi_ = tile; hi_ > 0u; hi_ = hi_ > 64u ? hi_ - 64u : 0u) {   // look back: lane l reads tile hi_ - 1 - l (all lower tickets)\n"
-                    "                            const bool in_ = lane < hi_;\n"
-                    "                            uint32_t v_ = 0;\n"
-                    "                            const bool got_ = !in_ || sp_await(dsc_ + (hi_ - 1u - lane), ep_, v_, tb_);\n"
-                    "                            if (__ballot(!got_) != 0ull) { ok_ = false; break; }\n"
-                    "                            const uint64_t incm_ = __ballot(in_ && (v_ & 0x80000000u));     // the nearest inclusive prefix ends the walk\n"
-                    "                            const uint32_t stop_ = incm_ ? (uint32_t)__builtin_ctzll(incm_) : 63u;\n"
-                    "                            uint64_t c_ = (in_ && lane <= stop_) ? (uint64_t)(v_ & 0x7FFFFFFFu) : 0ull;\n"
-                    "                            for (int o_ = 32; o_ > 0; o_ >>= 1) c_ += __shfl_xor(c_, o_, 64);\n"
-                    "                            exc_ += c_;\n"
-                    "                            if (incm_) break;\n"
-                    "                        }\n"
-                    "                        const uint32_t incl_ = exc_ + wg_tot_ < 0x7FFFFFFFull ? (uint32_t)(exc_ + wg_tot_) : 0x7FFFFFFFu;   // (saturated: beyond any capacity)\n"
-                    "                        if (lane == 0 && ok_) sp_post(dsc_ + tile, ep_, 0x80000000u | incl_);\n"
-                    "                        if (trk_ && tile == own_) tot_ = incl_;\n"
-                    "                    } else if (lane == 0) ok_ = sp_await_inc(dsc_ + own_, ep_, tot_, tb_);   // the end-of-world tile: a lower ticket\n"
-                    "                    if (lane == 0) { s_sp[4] = exc_; s_sp[5] = tot_; s_sp[6] = ok_ ? 1ull : 0ull; }\n"
-                    "                }\n"
-                    "                __syncthreads();\n"
-                    "                const bool ok1_ = s_sp[6] != 0ull;\n"
-                    "                uint64_t all_ = trk_ ? s_sp[5] : 0ull;                                  // the step's total, where known\n"
-                    "                if (!ok1_) { if (tid == 0) a.sp_len[GGRS_SP_TIMEOUT] = 1ull; all_ = 0; }   // a wait that timed out: the host is told\n"
-                    "                const bool over_ = trk_ && cur_len + all_ > a.sp_cap;\n"
-                    "                if (over_) { if (tile == own_ && tid == 0) a.sp_len[1] = 1ull; all_ = 0; }   // children beyond the world's capacity: nothing spawns\n"
-                    "                if (!above_ && !over_ && ok1_ && wg_tot_) {                            // a parent tile: its children's records\n";
-            s += "                    // one returning add on the pool cursor (started over by tile 0).  A tile whose inclusive prefix alone exceeds what len0_ leaves room for is in a step\n"
-                 "                    // beyond the capacity: it reserves nothing, so every step spends at most capacity - len0_ records of the pool (capacity records)\n"
-                 "                    if (tid == 0) {\n"
-                 "                        uint32_t o_ = 0xFFFFFFFFu;\n"
-                 "                        if (s_sp[4] + wg_tot_ <= a.sp_cap - len0_) {\n"
-                 "                            const ggrs_u64 at_ = __hip_atomic_fetch_add(a.sp_ctl + 1, (ggrs_u64)wg_tot_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
-                 "                            if (at_ + wg_tot_ <= a.sp_cap) o_ = (uint32_t)at_;\n"
-                 "                        }\n"
-                 "                        s_sp[7] = o_; sp_post(rof_ + tile, ep_, o_);\n"
-                 "                    }\n";
-            s += "                    __syncthreads();\n"
-                    "                    const uint32_t o_ = (uint32_t)s_sp[7];\n"
-                    "                    if (o_ != 0xFFFFFFFFu && spn_0) {\n"
-                    "                        GGRS_G ggrs_u64* const r_ = (GGRS_G ggrs_u64*)a.sp_recs + ((uint64_t)o_ + wg_excl_ + (inc_ - spn_0)) * 9u;\n"
-                    "                        for (uint32_t k_ = 0; k_ < spn_0; ++k_)\n"
-                    "                            for (int b_ = 0; b_ < 8; ++b_) __hip_atomic_store(r_ + 9u * k_ + b_, pw_[b_], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
-                    "                        asm volatile(\"s_waitcnt vmcnt(0)\" ::: \"memory\");                    // the words have arrived where every XCD reads them: then the flags\n"
-                    "                        for (uint32_t k_ = 0; k_ < spn_0; ++k_) __hip_atomic_store(r_ + 9u * k_ + 8u, ((ggrs_u64)ep_ << 32) | k_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
-                    "                    }\n"
-                    "                    asm volatile(\"s_waitcnt vmcnt(0)\" ::: \"memory\");\n"
-                    "                }\n"
-                    "                __syncthreads();                                                       // (this workgroup's own records are written before its children read them)\n"
-                    "                if (all_ && e0 >= cur_len && e0 < cur_len + all_) {                    // a child: find its parent's tile, then poll its own record\n"
-                    "                    const uint32_t r_ = (uint32_t)(e0 - cur_len);\n"
-                    "                    uint32_t lo_ = 0, hi_ = own_, ex_ = 0; bool okc_ = true;\n"
-                    "                    while (lo_ < hi_ && okc_) { const uint32_t m_ = (lo_ + hi_) >> 1; uint32_t v_ = 0; okc_ = sp_await_inc(dsc_ + m_, ep_, v_, tb_); if (v_ > r_) hi_ = m_; else { lo_ = m_ + 1u; ex_ = v_; } }\n"
-                    "                    uint32_t o_ = 0xFFFFFFFFu;\n"
-                    "                    if (okc_) okc_ = sp_await(rof_ + lo_, ep_, o_, tb_);\n"
-                    "                    if (okc_ && o_ != 0xFFFFFFFFu) {\n"
-                    "                        GGRS_G ggrs_u64* const rc_ = (GGRS_G ggrs_u64*)a.sp_recs + ((uint64_t)o_ + (r_ - ex_)) * 9u;\n"
-                    "                        uint32_t k32_ = 0;\n"
-                    "                        okc_ = sp_await((ggrs_u64*)(rc_ + 8u), ep_, k32_, tb_); kk_ = k32_;\n"
-                    "                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, \"wavefront\");                 // (no instruction: the record's loads stay behind the poll)\n"
-                    "                        if (okc_) for (int b_ = 0; b_ < 8; ++b_) prec_[b_] = __hip_atomic_load(rc_ + b_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
-                    "                    }\n"
-                    "                    if (!okc_) a.sp_len[GGRS_SP_TIMEOUT] = 1ull;\n"
-                    "                    else if (o_ == 0xFFFFFFFFu) a.sp_len[1] = 1ull;                    // (the pool only runs dry after a step beyond the capacity: already reported)\n"
-                    "                }\n"
-                    "                sn_ = all_;\n"
-                    "            }\n"
-                    "            if (sn_) {                                                                 // uniform over the tile\n"
-                    "                const unsigned char* const spay_ = (const unsigned char*)prec_;\n"
-                    "                if (e0 >= sf_ && e0 < sf_ + sn_) {\n"
-                    "                    alive_0 = true;\n";
-        } else if (DEV) {
-            // How many, and whose: the entities that called e.spawn(n), in slot order (== RollbackOrdered order, so every rank and every replay numbers the children
-            // alike).  Per step: an exclusive scan over the wave and the workgroup (LDS); every workgroup posts its count, workgroup 0 gathers them, scans them in
-            // tile order and hands each workgroup its prefix and everyone the total; a parent then knows its children's slots and leaves {parent slot, k} where the
-            // lane that OWNS each new slot will look; a second rendezvous (only in steps that spawn anything), and that lane takes the bundle.
-            s += "            uint64_t sn_ = 0, sf_ = cur_len;\n"
-                 "            {\n"
-                 "                uint32_t inc_ = spn_0;                                                 // inclusive scan over the wave's 64 lanes\n"
-                 "                for (int o_ = 1; o_ < 64; o_ <<= 1) { const uint32_t up_ = __shfl_up(inc_, o_, 64); if ((int)lane >= o_) inc_ += up_; }\n"
-                 "                const uint32_t wtot_ = (uint32_t)__builtin_amdgcn_readlane((int)inc_, 63);\n"
-                 "                __syncthreads();                                                       // (s_sp of the previous step has been read by everyone)\n"
-                 "                if (lane == 0) s_sp[wave] = wtot_;\n"
-                 "                __syncthreads();\n"
-                 "                uint32_t wg_excl_ = 0, wg_tot_ = 0;\n"
-                 "                for (uint32_t q_ = 0; q_ < 4u; ++q_) { const uint32_t v_ = (uint32_t)s_sp[q_]; wg_tot_ += v_; if (q_ < wave) wg_excl_ += v_; }\n"
-                 "                const uint32_t T_ = a.sp_tiles, ep1_ = a.sp_epoch + 2u * sj + 1u, ep2_ = ep1_ + 1u;\n"
-                 "                ggrs_u64* const cnt_ = a.sp_sums; ggrs_u64* const pref_ = cnt_ + T_; ggrs_u64* const done_ = cnt_ + 2u * T_; ggrs_u64* const tot_ = cnt_ + 3u * T_; ggrs_u64* const go_ = tot_ + 16;\n"
-                 "                const unsigned long long tb_ = wall_clock64();\n"
-                 "                if (tid == 0) sp_post(cnt_ + tile, ep1_, wg_tot_);\n"
-                 "                if (tile == 0) {                                                       // workgroup 0: gather, scan in tile order (== slot order), hand back\n"
-                 "                    // thread t takes the tiles [t x per, (t + 1) x per): at most 8 (8 x 256 workgroups are ever resident).  Awaited one after the other: keeping several\n"
-                 "                    // loads in flight, or the counts in LDS, was tried and costs the WHOLE kernel 3..30 VGPRs -- a workgroup per CU of residency, i.e. of capacity\n"
-                 "                    const uint32_t per_ = (T_ + 255u) / 256u, glo_ = tid * per_ < T_ ? tid * per_ : T_, ghi_ = glo_ + per_ < T_ ? glo_ + per_ : T_;\n"
-                 "                    uint32_t mine_ = 0; bool okg_ = true;\n"
-                 "                    for (uint32_t t_ = glo_; t_ < ghi_; ++t_) { uint32_t v_ = 0; okg_ = sp_await(cnt_ + t_, ep1_, v_, tb_) && okg_; mine_ += v_; }\n"
-                 "                    uint32_t sc_ = mine_;\n"
-                 "                    for (int o_ = 1; o_ < 64; o_ <<= 1) { const uint32_t up_ = __shfl_up(sc_, o_, 64); if ((int)lane >= o_) sc_ += up_; }\n"
-                 "                    const uint32_t wt2_ = (uint32_t)__builtin_amdgcn_readlane((int)sc_, 63);\n"
-                 "                    const bool wfail_ = __ballot(!okg_) != 0ull;\n"
-                 "                    if (lane == 0) { s_sp[8u + wave] = wt2_; s_sp[12u + wave] = wfail_ ? 1ull : 0ull; }\n"
-                 "                    __syncthreads();\n"
-                 "                    uint32_t base_ = sc_ - mine_, run_ = 0;\n"
-                 "                    for (uint32_t q_ = 0; q_ < 4u; ++q_) { const uint32_t v_ = (uint32_t)s_sp[8u + q_]; run_ += v_; if (q_ < wave) base_ += v_; }\n"
-                 "                    const bool fail_ = (s_sp[12] | s_sp[13] | s_sp[14] | s_sp[15]) != 0ull;\n"
-                 "                    if (run_ != 0u && !fail_)\n"
-                 "                        for (uint32_t t_ = glo_; t_ < ghi_; ++t_) { const uint32_t v_ = (uint32_t)__hip_atomic_load(cnt_ + t_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); sp_post(pref_ + t_, ep1_, base_); base_ += v_; }\n"
-                 "                    if (tid == 0) sp_post(tot_, ep1_, fail_ ? 0xFFFFFFFFu : run_);\n"
-                 "                }\n"
-                 "                if (tid == 0) {\n"
-                 "                    uint32_t all32_ = 0xFFFFFFFFu, bef32_ = 0;\n"
-                 "                    bool ok_ = sp_await(tot_, ep1_, all32_, tb_) && all32_ != 0xFFFFFFFFu;\n"
-                 "                    if (ok_ && all32_ != 0u) ok_ = sp_await(pref_ + tile, ep1_, bef32_, tb_);\n"
-                 "                    s_sp[4] = bef32_; s_sp[5] = ok_ ? all32_ : 1ull; s_sp[6] = ok_ ? 1ull : 0ull;\n"
-                 "                }\n"
-                 "                __syncthreads();\n"
-                 "                const bool ok1_ = s_sp[6] != 0ull;\n"
-                 "                const uint64_t bef_ = s_sp[4];\n"
-                 "                uint64_t all_ = s_sp[5];\n"
-                 "                if (!ok1_ || cur_len + all_ > a.sp_cap) {                               // a rendezvous that timed out, or children beyond the world's capacity: nothing spawns, the host is told\n"
-                 "                    if (all_ && gu == 0 && lane == 0) a.sp_len[1] = !ok1_ ? 2ull : 1ull;\n"
-                 "                    all_ = 0;\n"
-                 "                }\n"
-                 "                if (all_) {                                                            // uniform over the whole grid\n"
-                 "                    const uint64_t first_ = cur_len + bef_ + wg_excl_ + (inc_ - spn_0);    // this parent's first child\n"
-                 "                    for (uint32_t k_ = 0; k_ < spn_0; ++k_) {\n"
-                 "                        GGRS_G ggrs_u64* lk_ = (GGRS_G ggrs_u64*)a.sp_link + 2u * (first_ + k_);\n"
-                 "                        __hip_atomic_store(lk_, (ggrs_u64)e0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); __hip_atomic_store(lk_ + 1, (ggrs_u64)k_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
-                 "                    }\n"
-                 "                    asm volatile(\"s_waitcnt vmcnt(0)\" ::: \"memory\");                    // this wave's links and parent records (sc1 stores) have arrived where every XCD reads them\n"
-                 "                    __syncthreads();\n"
-                 "                    if (tid == 0) sp_post(done_ + tile, ep2_, 1u);\n"
-                 "                    if (tile == 0) {\n"
-                 "                        bool okd_ = true;\n"
-                 "                        for (uint32_t t_ = tid; t_ < T_ && okd_; t_ += 256u) { uint32_t v_ = 0; okd_ = sp_await(done_ + t_, ep2_, v_, tb_); }\n"
-                 "                        const bool wfail_ = __ballot(!okd_) != 0ull;\n"
-                 "                        if (lane == 0) s_sp[12u + wave] = wfail_ ? 1ull : 0ull;\n"
-                 "                        __syncthreads();\n"
-                 "                        if (tid == 0) sp_post(go_, ep2_, (s_sp[12] | s_sp[13] | s_sp[14] | s_sp[15]) != 0ull ? 0xFFFFFFFFu : 1u);\n"
-                 "                    }\n"
-                 "                    if (tid == 0) { uint32_t g_ = 0; const bool ok_ = sp_await(go_, ep2_, g_, tb_) && g_ == 1u; s_sp[6] = ok_ ? 1ull : 0ull; }\n"
-                 "                    __syncthreads();\n"
-                 "                    if (s_sp[6] == 0ull) { if (gu == 0 && lane == 0) a.sp_len[1] = 2ull; all_ = 0; }\n"
-                 "                }\n"
-                 "                sn_ = all_;\n"
-                 "            }\n"
-                 "            if (sn_) {                                                                 // uniform over the grid\n"
-                 "                unsigned long long kk_ = 0;\n"
-                 "                ggrs_u64 prec_[8] = {0, 0, 0, 0, 0, 0, 0, 0};                          // the payload of a child: its parent's record, fetched past this XCD's L2 (sc1)\n"
-                 "                if (e0 >= sf_ && e0 < sf_ + sn_) {\n"
-                 "                    const GGRS_G ggrs_u64* lk_ = (const GGRS_G ggrs_u64*)a.sp_link + 2u * e0;\n"
-                 "                    const unsigned long long par_ = __hip_atomic_load(lk_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); kk_ = __hip_atomic_load(lk_ + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
-                 "                    // (this step's set: a parent that spawns again in the NEXT step writes the other one -- its workgroup may be a step ahead of this one, but not two: the next\n"
-                 "                    // step's rendezvous waits for this workgroup)\n"
-                 "                    const GGRS_G ggrs_u64* pp_ = (const GGRS_G ggrs_u64*)(a.sp_prec + ((uint64_t)(sj & 1u) * a.sp_tiles * 256u + par_) * 64u);\n"
-                 "                    for (int b_ = 0; b_ < 8; ++b_) prec_[b_] = __hip_atomic_load(pp_ + b_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
-                 "                }\n"
-                 "                const unsigned char* const spay_ = (const unsigned char*)prec_;\n"
-                 "                if (e0 >= sf_ && e0 < sf_ + sn_) {\n"
-                 "                    alive_0 = true;\n";
-        } else
+        if (need.devstream) spawn_head_streamed();
+        else if (need.devspawn) spawn_head_resident();
+        else
         sfmt(s, "            const uint64_t sn_ = mb ? mb_u32(mb, %uu + 4u * sj) : a.spawn_count[sj];\n"
                 "            if (sn_) {                                                                 // wave-uniform\n"
                 "                const uint64_t sf_ = mb ? mb_u64(mb, %uu + 8u * sj) : a.spawn_first[sj];\n"
@@ -1456,82 +1490,132 @@ bool jit_source(const ggrs_world* w, std::string& s) {
             const ggrs_world::SpawnSys& sp = w->spawn_customs[d.comp[0]];
             s += "                    GgrsEntity ent; ent.slot = e0; ent.kill = 0; ent.spawn_n = 0;\n";
             for (uint32_t b = 0; b < sp.n_bind; ++b) sfmt(s, "                    ent.w[%u] = w%u_0;\n", b, col(sp.comp[b], sp.word[b]));
-            if (DEV) s += "                    ggrs_spawn_sys::ggrs_spawn(ent, kk_, fr_spawn, spay_);                     // k = which child of its parent; payload = the parent's 8 bound words (u64 each)\n";
+            if (need.devspawn) s += "                    ggrs_spawn_sys::ggrs_spawn(ent, kk_, fr_spawn, spay_);                     // k = which child of its parent; payload = the parent's 8 bound words (u64 each)\n";
             else sfmt(s, "                    ggrs_spawn_sys::ggrs_spawn(ent, e0 - sf_, fr_spawn, spay_ + (e0 - sf_) * %uull);\n", sp.payload_stride);
             for (uint32_t b = 0; b < sp.n_bind; ++b)
                 sfmt(s, "                    w%u_0 = (%s)(%s)ent.w[%u];\n", col(sp.comp[b], sp.word[b]), wtype(sp.comp[b]), mtype(sp.comp[b]), b);
         }
-        if (marks) s += "                    dis_0 = false;\n";
+        if (need.marks) s += "                    dis_0 = false;\n";
         uint64_t bundle_cols = 0;
         for (uint32_t c = 0; c < nc; ++c) if (rb(c) && ((bundle >> c) & 1ull)) for (uint32_t k = 0; k < w->comps[c].n_words; ++k) bundle_cols |= 1ull << col(c, k);
         s += "                }\n";
-        if (VT) sfmt(s, "                // value tags: new rows in this unit -- every column of the bundle carries a fresh identity\n"
-                        "                if (a.vtags && __ballot(e0 >= sf_ && e0 < sf_ + sn_) != 0ull) chg |= 0x%llxull;\n", (unsigned long long)bundle_cols);
+        if (need.vtags) sfmt(s, "                // value tags: new rows in this unit -- every column of the bundle carries a fresh identity\n"
+                                "                if (a.vtags && __ballot(e0 >= sf_ && e0 < sf_ + sn_) != 0ull) chg |= 0x%llxull;\n", (unsigned long long)bundle_cols);
         s += "                in_len = (uint64_t)gu * 64u < sf_ + sn_;\n";
-        if (DEV) s += "                cur_len = sf_ + sn_;\n";
+        if (need.devspawn) s += "                cur_len = sf_ + sn_;\n";
         s += "            }\n";
     }
-    s += "            ++sj;\n"
-         "        }\n"
-         "    }\n"
-         "    // ---- the live world, written once\n"
-         "    if (my_live && writes_live) {\n"
-         "        const uint64_t alive_now = __ballot(alive_0);\n";
-    sfmt(s, "        unsigned char* const live_p = mb ? (unsigned char*)mb_u64(mb, %uu) : a.live;\n"
-            "        uint64_t live_rows_v = mb ? mb_u64(mb, %uu) : a.live_rows;\n"
-            "        const uint32_t live_pm_v = mb ? mb_u32(mb, %uu) : a.live_pmask;\n", L.m.live, L.m.live_rows, L.m.live_pmask);
-    { char te[96]; snprintf(te, sizeof te, "(mb ? mb_u64(mb, %uu) : a.live_tagok)", L.m.live_tagok); emit_tag_filter("live_p", "live_rows_v", te, "        ", "dtl"); }
-    emit_store("live_p", "live_rows_v", "live_pm_v", "alive_now", "        ", false);
-    if (STREAM) sfmt(s, "        if (tile == a.sp_tiles - 1u && wave == 0u && !gated_ && (const unsigned char*)%s == a.src) {   // a write to the block every tile read len from\n"
-            "            gated_ = true;\n"
-            "            if (!sp_gate(a.sp_desc + (uint64_t)GGRS_SP_READ * a.sp_tiles, a.sp_tiles - 1u, a.sp_epoch + 1u + GGRS_SP_READ, lane) && lane == 0) a.sp_len[GGRS_SP_TIMEOUT] = 1ull;\n"
-            "        }\n", "live_p");
-    if (STREAM) s += "        if (len_wr) { *reinterpret_cast<uint64_t*>(live_p) = cur_len; a.sp_len[0] = cur_len; }      // (the last tile: it tracks cur_len exactly)\n";
-    else if (DEV) s += "        if (gu == 0 && lane == 0) { *reinterpret_cast<uint64_t*>(live_p) = cur_len; a.sp_len[0] = cur_len; }      // the live block's header carries RollbackOrdered::len for whoever loads it next; the host reads it from pinned memory\n";
-    s += "    }\n";
-    if (marks) {
-        // a batch member's markers are its own: the live block is shared by all members, read-only; what the branch newly disabled goes to its marker record (retained branches)
-        s += "    if (!mb && my_live && a.n_steps) {\n"
-             "        const uint64_t dis_w = __ballot(dis_0);\n";
-        sfmt(s, "        if (lane == 0) *reinterpret_cast<uint64_t*>(a.live + %lluull + wi8) = dis_w;\n"
-                "        *reinterpret_cast<int*>(a.live + %lluull + e0 * 4u) = df_0;\n", OFF_DIS, OFF_DF);
+    void spawn_head_streamed() {
+        s += "            uint64_t sn_ = 0, sf_ = cur_len;\n"
+             "            unsigned long long kk_ = 0;\n"
+             "            ggrs_u64 prec_[8] = {0, 0, 0, 0, 0, 0, 0, 0};                              // the payload of a child: its parent's record, fetched past this XCD's L2 (sc1)\n"
+             "            {\n";
+        s += kJitSpScan;
+        s += "                const uint32_t T_ = a.sp_tiles, ep_ = a.sp_epoch + 1u + sj;\n"
+             "                ggrs_u64* const dsc_ = a.sp_desc + (uint64_t)sj * T_;                  // this step's descriptors, one per tile\n";
+        sfmt(s, "                ggrs_u64* const rof_ = a.sp_desc + (uint64_t)(%uu + sj) * T_;          // {epoch, first record} of each parent tile of this step\n", (unsigned)MAX_TICK_STEPS);
+        s += kJitSpLookBack;
+    }
+    void spawn_head_resident() {
+        s += "            uint64_t sn_ = 0, sf_ = cur_len;\n"
+             "            {\n";
+        s += kJitSpScan;
+        s += kJitSpRendezvous;
+    }
+    // ---- 11. the end of the op loop; the live world, written once
+    void live_store() {
+        s += "            ++sj;\n"
+             "        }\n"
+             "    }\n"
+             "    // ---- the live world, written once\n"
+             "    if (my_live && writes_live) {\n"
+             "        const uint64_t alive_now = __ballot(alive_0);\n";
+        sfmt(s, "        unsigned char* const live_p = mb ? (unsigned char*)mb_u64(mb, %uu) : a.live;\n"
+                "        uint64_t live_rows_v = mb ? mb_u64(mb, %uu) : a.live_rows;\n"
+                "        const uint32_t live_pm_v = mb ? mb_u32(mb, %uu) : a.live_pmask;\n", L.m.live, L.m.live_rows, L.m.live_pmask);
+        { char te[96]; snprintf(te, sizeof te, "(mb ? mb_u64(mb, %uu) : a.live_tagok)", L.m.live_tagok); emit_tag_filter("live_p", "live_rows_v", te, "        ", "dtl"); }
+        emit_store("live_p", "live_rows_v", "live_pm_v", "alive_now", "        ", false);
+        if (need.devstream) emit_sp_gate("        ", "live_p");
+        if (need.devstream) s += "        if (len_wr) { *reinterpret_cast<uint64_t*>(live_p) = cur_len; a.sp_len[0] = cur_len; }      // (the last tile: it tracks cur_len exactly)\n";
+        else if (need.devspawn) s += "        if (gu == 0 && lane == 0) { *reinterpret_cast<uint64_t*>(live_p) = cur_len; a.sp_len[0] = cur_len; }      // the live block's header carries RollbackOrdered::len for whoever loads it next; the host reads it from pinned memory\n";
         s += "    }\n";
-        sfmt(s, "    if (mb) {\n"
-                "        unsigned char* const mk_rec = (unsigned char*)mb_u64(mb, %uu);             // this member's marker record (null: the branch is not retained)\n"
-                "        if (mk_rec) {\n"
-                "            const uint64_t mk_new = __ballot(dis_0) & ~mk_dis;                      // markers are monotone inside a branch: the world's plus these\n"
-                "            if (lane == 0) *reinterpret_cast<uint64_t*>(mk_rec + wi8) = mk_new;\n"
-                "            if ((mk_new >> sh) & 1ull) *reinterpret_cast<int*>(mk_rec + %lluull + e0 * 4u) = df_0;\n"
+    }
+    // ---- 12. marker and `gone` tails, the end of the wave's unit
+    void unit_tails() {
+        if (need.marks) {
+            // a batch member's markers are its own: the live block is shared by all members, read-only; what the branch newly disabled goes to its marker record (retained branches)
+            s += "    if (!mb && my_live && a.n_steps) {\n"
+                 "        const uint64_t dis_w = __ballot(dis_0);\n";
+            sfmt(s, "        if (lane == 0) *reinterpret_cast<uint64_t*>(a.live + %lluull + wi8) = dis_w;\n"
+                    "        *reinterpret_cast<int*>(a.live + %lluull + e0 * 4u) = df_0;\n", OFF_DIS, OFF_DF);
+            s += "    }\n";
+            sfmt(s, "    if (mb) {\n"
+                    "        unsigned char* const mk_rec = (unsigned char*)mb_u64(mb, %uu);             // this member's marker record (null: the branch is not retained)\n"
+                    "        if (mk_rec) {\n"
+                    "            const uint64_t mk_new = __ballot(dis_0) & ~mk_dis;                      // markers are monotone inside a branch: the world's plus these\n"
+                    "            if (lane == 0) *reinterpret_cast<uint64_t*>(mk_rec + wi8) = mk_new;\n"
+                    "            if ((mk_new >> sh) & 1ull) *reinterpret_cast<int*>(mk_rec + %lluull + e0 * 4u) = df_0;\n"
+                    "        }\n"
+                    "    }\n", L.m.marks_dst, (unsigned long long)jit_marks_rec_frames_off(w));
+        }
+        if (need.nr) {
+            // an entity of the source block that a member despawned for good loses its non-rollback components (what the next LoadWorld's reconcile does in the list form):
+            // collected here, applied to the live block by one small kernel after the launch -- no member writes the live block while another may read it
+            // An entity alive in the source block is not disabled there (a deferred despawn clears `alive`), so at the end "not alive and not disabled" is "despawned for good"
+            sfmt(s, "    if (mb && a.gone) {\n"
+                    "        const uint64_t gone_w = __ballot(src_alive_v && !alive_0%s);\n"
+                    "        if (lane == 0 && gone_w) atomicOr((unsigned long long*)(a.gone + gu), (unsigned long long)gone_w);\n"
+                    "    }\n", need.marks ? " && !dis_0" : "");
+        }
+        s += "    }   // the wave's unit\n";
+    }
+    // ---- 13. this workgroup's partial rows
+    void partial_rows() {
+        s += "    // ---- this workgroup's partial rows (blockIdx.z: member of a batch of identical checksum-only groups)\n"
+             "    __syncthreads();\n";
+        if (lane_fold)
+            sfmt(s,
+                 "    for (uint32_t r_ = wave; r_ < a.n_saves * %uu; r_ += 4u) {                  // one row per wave and trip: XOR over its 64 lanes\n"
+                 "        const uint32_t sv = r_ / %uu;\n"
+                 "        if (sv < o_first || sv >= o_last) continue;\n"
+                 "        const ggrs_u64 v_ = wave_xor(s_lane[r_ * 64u + lane]);\n"
+                 "        if (lane == 0) s_acc[sv * %uu + r_ %% %uu] = v_;\n"
+                 "    }\n"
+                 "    __syncthreads();\n", n_cks, n_cks, n_cks + 1, n_cks);
+        sfmt(s,
+                "    for (uint32_t i = tid; i < a.n_saves * %uu; i += 256u) {\n"
+                "        const uint32_t sv = i / %uu;\n"
+                "        if (sv >= o_first && sv < o_last) {\n"
+                "            const uint64_t at_ = ((uint64_t)blockIdx.z * a.n_saves * %uu + i) * a.part_stride + (uint64_t)tile * a.part_tstride;\n"
+                "            if (a.ff_self) {                                                  // self-fold: a 16-byte cell {value, tag} in ONE sc1 store, read by a fold workgroup of THIS launch\n"
+                "                const uint64_t v_ = s_acc[i], sq_ = (uint64_t)a.ff_seq;\n"
+                "                const ff_u32x4 q_ = {(uint32_t)v_, (uint32_t)(v_ >> 32), (uint32_t)sq_, (uint32_t)(sq_ >> 32)};\n"
+                "                asm volatile(\"global_store_dwordx4 %%0, %%1, off sc1\" : : \"v\"(reinterpret_cast<ff_u32x4*>(a.parts) + at_), \"v\"(q_) : \"memory\");\n"
+                "            } else a.parts[at_] = s_acc[i];\n"
                 "        }\n"
-                "    }\n", L.m.marks_dst, (unsigned long long)jit_marks_rec_frames_off(w));
+                "    }\n", n_cks + 1, n_cks + 1, n_cks + 1);
+        if (need.vtags) s += "    if (a.skip_count && tid == 0 && s_skip) atomicAdd(a.skip_count, s_skip);      // value tags, profiled launches only: bytes this workgroup did not store\n";
+        s += "}\n";
     }
-    if (need.nr) {
-        // an entity of the source block that a member despawned for good loses its non-rollback components (what the next LoadWorld's reconcile does in the list form):
-        // collected here, applied to the live block by one small kernel after the launch -- no member writes the live block while another may read it
-        // An entity alive in the source block is not disabled there (a deferred despawn clears `alive`), so at the end "not alive and not disabled" is "despawned for good"
-        sfmt(s, "    if (mb && a.gone) {\n"
-                "        const uint64_t gone_w = __ballot(src_alive_v && !alive_0%s);\n"
-                "        if (lane == 0 && gone_w) atomicOr((unsigned long long*)(a.gone + gu), (unsigned long long)gone_w);\n"
-                "    }\n", marks ? " && !dis_0" : "");
-    }
-    s += "    }   // the wave's unit\n";
-    sfmt(s, "    // ---- this workgroup's partial rows (blockIdx.z: member of a batch of identical checksum-only groups)\n"
-            "    __syncthreads();\n"
-            "%s", fold_text.c_str());
-    sfmt(s,
-            "    for (uint32_t i = tid; i < a.n_saves * %uu; i += 256u) {\n"
-            "        const uint32_t sv = i / %uu;\n"
-            "        if (sv >= o_first && sv < o_last) {\n"
-            "            const uint64_t at_ = ((uint64_t)blockIdx.z * a.n_saves * %uu + i) * a.part_stride + (uint64_t)tile * a.part_tstride;\n"
-            "            if (a.ff_self) {                                                  // self-fold: a 16-byte cell {value, tag} in ONE sc1 store, read by a fold workgroup of THIS launch\n"
-            "                const uint64_t v_ = s_acc[i], sq_ = (uint64_t)a.ff_seq;\n"
-            "                const ff_u32x4 q_ = {(uint32_t)v_, (uint32_t)(v_ >> 32), (uint32_t)sq_, (uint32_t)(sq_ >> 32)};\n"
-            "                asm volatile(\"global_store_dwordx4 %%0, %%1, off sc1\" : : \"v\"(reinterpret_cast<ff_u32x4*>(a.parts) + at_), \"v\"(q_) : \"memory\");\n"
-            "            } else a.parts[at_] = s_acc[i];\n"
-            "        }\n"
-            "    }\n", n_cks + 1, n_cks + 1, n_cks + 1);
-    if (VT) s += "    if (a.skip_count && tid == 0 && s_skip) atomicAdd(a.skip_count, s_skip);      // value tags, profiled launches only: bytes this workgroup did not store\n";
-    s += "}\n";
+};
+
+// Writes the kernel for this world.  Returns false, and leaves `s` empty, when the world is outside what the generator covers (jit_covers).
+bool jit_source(const ggrs_world* w, std::string& s) {
+    s.clear();
+    if (!jit_covers(w)) return false;
+    JitGen g(w, s);
+    g.preamble();
+    g.user_sources();
+    g.kernel_head();
+    g.unit_head();
+    g.tag_head();
+    g.unit_state();
+    g.save_arm();
+    g.advance_arm();
+    g.spawn_section();
+    g.live_store();
+    g.unit_tails();
+    g.partial_rows();
     return true;
 }
 

@@ -201,6 +201,50 @@ def test_generator_limits_and_errors():
     assert "broken" in str(ei.value) and "nope" in str(ei.value)
 
 
+def _eight_byte_words(n_words):
+    w = dry(400)
+    for k in range(0, n_words, 8): w.register_component(f"Wide{k}", 8, min(8, n_words - k))      # two four-byte register units per word
+    w.add_system(bg.SYS_TTL_DESPAWN, comp=(0,), word=(0,))
+    return w
+
+
+def _four_byte_words(n_words):
+    w = dry(400)
+    for k in range(0, n_words, 13): w.register_component(f"Thin{k}", 4, min(13, n_words - k))
+    w.add_system(bg.SYS_ADD_U32, comp=(0,), word=(0,), iparam=(1,))
+    return w
+
+
+def _builtin_on_live_only():
+    w = dry(400)
+    w.register_component("A", 4, 1); K = w.register_component("K", 4, 1, rollback=False)
+    w.add_system(bg.SYS_ADD_U32, comp=(K,), word=(0,), iparam=(1,))
+    return w
+
+
+def _checksummed_live_only():
+    w = dry(400)
+    A = w.register_component("A", 4, 1); K = w.register_component("K", 4, 1, rollback=False)
+    w.checksum_component(K, [0])
+    w.add_system(bg.SYS_ADD_U32, comp=(A,), word=(0,), iparam=(1,))
+    return w
+
+
+@pytest.mark.parametrize("make,covered", [pytest.param(lambda: _eight_byte_words(64), True, id="units_at_the_limit"), pytest.param(lambda: _four_byte_words(65), False, id="words_over_the_limit"),
+                                          pytest.param(_builtin_on_live_only, False, id="builtin_system_on_live_only"), pytest.param(_checksummed_live_only, False, id="checksummed_live_only")])
+def test_generator_refuses_before_it_writes(make, covered):
+    """What the generator does not cover is refused as a whole, with the one message of ggrs_hip_generated_kernel_source; 128 four-byte units (JIT_MAX_UNITS) still generate."""
+    w = make()
+    if covered:
+        src = w.generated_kernel_source()
+        assert len(re.findall(r"#define o\d+\(blk\)", src)) == 64 and "#error" not in src
+        return
+    with pytest.raises(bg.GgrsHipError) as ei:
+        w.generated_kernel_source()
+    assert ei.value.code == bg.GGRS_E_INVALID
+    assert "the kernel generator does not cover this world (a system writes a live-only component, or more than 128 four-byte units / 64 words per entity)" in str(ei.value)
+
+
 def test_layout_only_world_has_no_device_behind_it():
     w = particles()
     with pytest.raises(bg.GgrsHipError) as ei:
