@@ -74,6 +74,15 @@ class PeerBinding(C.Structure):
     _fields_ = [("comp", C.c_uint32), ("word", C.c_uint32)]
 
 
+EFFECT_ADD, EFFECT_MIN_U, EFFECT_MAX_U, EFFECT_MIN_I, EFFECT_MAX_I, EFFECT_OR, EFFECT_AND, EFFECT_XOR = range(8)
+EFFECT_MAX_BINDINGS = 8
+EFFECT_MAX_COLUMNS = 8
+
+
+class EffectBinding(C.Structure):
+    _fields_ = [("comp", C.c_uint32), ("word", C.c_uint32), ("op", C.c_uint32)]
+
+
 class SpawnSystemDesc(C.Structure):
     _fields_ = [("name", C.c_char_p), ("source", C.c_char_p), ("bundle_mask", C.c_uint64), ("payload_stride", C.c_uint32), ("n_bindings", C.c_uint32),
                 ("comp", C.c_uint32 * CUSTOM_MAX_BINDINGS), ("word", C.c_uint32 * CUSTOM_MAX_BINDINGS),
@@ -120,6 +129,7 @@ SIGNATURES = {
     "ggrs_hip_add_system": (C.c_int, [_P, C.POINTER(SystemDesc)]),
     "ggrs_hip_add_custom_system": (C.c_int, [_P, C.POINTER(CustomSystemDesc)]),
     "ggrs_hip_add_custom_system_peers": (C.c_int, [_P, C.POINTER(CustomSystemDesc), C.POINTER(PeerBinding), C.c_uint32]),
+    "ggrs_hip_add_custom_system_effects": (C.c_int, [_P, C.POINTER(CustomSystemDesc), C.POINTER(PeerBinding), C.c_uint32, C.POINTER(EffectBinding), C.c_uint32]),
     "ggrs_hip_register_component_strategy": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p]),
     "ggrs_hip_set_input_layout": (C.c_int, [_P, C.c_uint32, C.c_uint32]),
     "ggrs_hip_add_spawn_system": (C.c_int, [_P, C.POINTER(SpawnSystemDesc)]),

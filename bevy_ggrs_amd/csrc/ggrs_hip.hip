@@ -131,6 +131,7 @@ void ggrs_hip_world_destroy(ggrs_world* w) {
     if (w->d_skip) (void)hipFree(w->d_skip);
     sp_release(w);
     peer_view_release(w);
+    fx_inbox_release(w);
     for (void* p : w->spec_allocs) (void)hipFree(p);
     if (w->h_results) (void)hipHostFree(w->h_results);
     if (w->h_stage) (void)hipHostFree(w->h_stage);
@@ -219,11 +220,15 @@ int ggrs_hip_add_system(ggrs_world* w, const ggrs_system_desc* d) {
 }
 int ggrs_hip_add_custom_system(ggrs_world* w, const ggrs_custom_system_desc* d) { return ggrs_hip_add_custom_system_peers(w, d, nullptr, 0); }
 // ... with peer bindings: words of OTHER entities the system reads through e.peer(slot), as they were at the start of the frame (include/ggrs_hip.h)
-int ggrs_hip_add_custom_system_peers(ggrs_world* w, const ggrs_custom_system_desc* d, const ggrs_peer_binding* peers, uint32_t n_peers) {
+int ggrs_hip_add_custom_system_peers(ggrs_world* w, const ggrs_custom_system_desc* d, const ggrs_peer_binding* peers, uint32_t n_peers) { return ggrs_hip_add_custom_system_effects(w, d, peers, n_peers, nullptr, 0); }
+// ... and with effect bindings: words of OTHER entities the system combines a value into through e.send_*(slot, j, v), landing at the end of the frame (include/ggrs_hip.h)
+int ggrs_hip_add_custom_system_effects(ggrs_world* w, const ggrs_custom_system_desc* d, const ggrs_peer_binding* peers, uint32_t n_peers, const ggrs_effect_binding* effects, uint32_t n_effects) {
     if (!w || !d || !d->source) return GGRS_E_INVALID;
     if (w->sealed) return w->fail(GGRS_E_INVALID, "add_custom_system after the world was sealed");
     if (n_peers > GGRS_PEER_MAX_BINDINGS) return w->fail(GGRS_E_INVALID, "custom system: at most %d peer bindings, not %u", GGRS_PEER_MAX_BINDINGS, n_peers);
     if (n_peers && !peers) return w->fail(GGRS_E_INVALID, "custom system: n_peers = %u but peers is NULL", n_peers);
+    if (n_effects > GGRS_EFFECT_MAX_BINDINGS) return w->fail(GGRS_E_INVALID, "custom system: at most %d effect bindings, not %u", GGRS_EFFECT_MAX_BINDINGS, n_effects);
+    if (n_effects && !effects) return w->fail(GGRS_E_INVALID, "custom system: n_effects = %u but effects is NULL", n_effects);
     if (w->systems.size() >= GGRS_MAX_SYSTEMS) return w->fail(GGRS_E_INVALID, "too many systems");
     if (d->n_bindings == 0 || d->n_bindings > GGRS_CUSTOM_MAX_BINDINGS) return w->fail(GGRS_E_INVALID, "custom system: 1..%d bindings", GGRS_CUSTOM_MAX_BINDINGS);
     ggrs_world::Custom c;
@@ -243,6 +248,13 @@ int ggrs_hip_add_custom_system_peers(ggrs_world* w, const ggrs_custom_system_des
         c.pcomp[j] = peers[j].comp; c.pword[j] = peers[j].word;
     }
     c.n_peer = n_peers;
+    for (uint32_t j = 0; j < n_effects; ++j) {
+        if (effects[j].comp >= w->comps.size() || effects[j].word >= w->comps[effects[j].comp].n_words)
+            return w->fail(GGRS_E_INVALID, "custom system '%s': effect binding %u names word %u of component %u, which is not registered", c.name.c_str(), j, effects[j].word, effects[j].comp);
+        if (effects[j].op > GGRS_EFFECT_XOR) return w->fail(GGRS_E_INVALID, "custom system '%s': effect binding %u has op %u, which is none of GGRS_EFFECT_*", c.name.c_str(), j, effects[j].op);
+        c.fcomp[j] = effects[j].comp; c.fword[j] = effects[j].word; c.fop[j] = effects[j].op;
+    }
+    c.n_fx = n_effects;
     DeviceGuard dg(w);
     c.source = d->source;
     c.may_defer = source_has_token(c.source, "despawn_rollback") || source_has_token(c.source, "kill");
@@ -317,7 +329,7 @@ int ggrs_hip_generated_kernel_source(ggrs_world* w, uint32_t form, char* buf, ui
     if (!w || (form != GGRS_KERNEL_FORM_TILES && form != GGRS_KERNEL_FORM_STEADY)) return GGRS_E_INVALID;
     if (!w->sealed) {
         if (!w->layout_only) { DeviceGuard dg(w); const int rc = seal(w); if (rc) return rc; }
-        else { build_layout(w); const int prc = peers_validate(w); if (prc) return prc; }   // host arithmetic only: offsets of every mask and column; the peer-binding rules
+        else { build_layout(w); const int prc = peers_validate(w); if (prc) return prc; const int frc = effects_validate(w); if (frc) return frc; }   // host arithmetic only: offsets of every mask and column; the peer- and effect-binding rules
     }
     std::string src;
     if (!jit_source(w, src)) return w->fail(GGRS_E_INVALID, "the kernel generator does not cover this world (a system writes a live-only component, or more than %u four-byte units / %u words per entity)", JIT_MAX_UNITS, JIT_MAX_COLS);
@@ -828,6 +840,8 @@ int ggrs_hip_world_kernel_info(ggrs_world* w, char* buf, uint64_t cap, uint64_t*
         add("group_caps", std::to_string(w->cap_saves) + " saves / " + std::to_string(w->cap_steps) + " steps");
         if (w->has_peers) add("peer_view", std::to_string(w->peer_view.n_cols) + " linear columns + visibility words, published from the group's source block ahead of every request group that holds an AdvanceWorld (" +
                                            std::to_string(w->peer_view.publishes) + " publishes so far)");
+        if (w->has_effects) add("effect_inbox", std::to_string(w->fx_inbox.n_cols) + " linear columns holding the ops' identities, applied to the live block right behind every request group that holds an AdvanceWorld (" +
+                                               std::to_string(w->fx_inbox.applies) + " applies so far)");
         add("branch_marker_record_bytes", std::to_string(w->jit_marks ? jit_marks_rec_bytes(w) : 0));      // per retained branch of ggrs_hip_fanout_step_branches (0: the kernel keeps no markers)
         add("branch_marker_records", std::to_string(w->branch_marks_cap));                                 // ... how many are allocated
         bool any_spawn = false;

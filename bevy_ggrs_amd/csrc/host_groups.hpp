@@ -439,6 +439,7 @@ constexpr uint32_t LAZY_LIVE_STREAK = 8;
 inline bool lazy_live_allowed(const ggrs_world* w) {                 // (what a layout-only world -- `make aot` on a machine without a GPU -- can tell)
     if (!w->lazy_live_on || w->live_handed_out || w->has_nr || w->marks_possible || w->device_results_only || jit_dev_spawn(w)) return false;
     if (world_has_peers(w)) return false;                            // peer bindings: the next group's publish reads what this one leaves -- every block is written (no deferred Saves either)
+    if (world_has_effects(w)) return false;                          // effect bindings: k_apply_effects combines the frame's sends into the live block -- every group writes it (no deferred Saves either)
     for (uint8_t e : w->col_ext) if (e) return false;
     return true;
 }
@@ -618,6 +619,7 @@ int group_take(ggrs_world* w, const ggrs_request& r, GgrsJitArgs& j, GroupState&
     int rc = GGRS_OK;
     if (r.kind == GGRS_REQ_SAVE) {
         if (j.n_saves == w->cap_saves || j.n_saves == saves_room) return GGRS_OK;
+        if (w->has_effects && j.n_steps) return GGRS_OK;               // effect bindings: the group ends ON its AdvanceWorld ([Load?] Save* Advance) -- this Save opens the next group and reads the live block after the apply
         *taken = true; return group_save(w, gs, j);
     }
     if (r.kind != GGRS_REQ_ADVANCE) return w->fail(GGRS_E_INVALID, "unknown request kind %u", r.kind);
@@ -778,6 +780,34 @@ int publish_peers(ggrs_world* w, const Block& src, uint64_t len, GgrsJitArgs& j)
     ++pv.publishes;
     return GGRS_OK;
 }
+// Effect bindings: the sends the group's launch left in the inbox are combined into the live block -- and the identities put back -- by a launch of its own on the
+// world's stream right BEHIND the group's, enqueued with it (never lazily): whatever follows on the stream -- a Save, a download, the next group's peer publish -- sees
+// the frame with its effects, and the inbox holds identities again.  The kernel boundary is the only synchronisation.
+inline void attach_effects(ggrs_world* w, GgrsJitArgs& j) {
+    for (uint32_t k = 0; k < w->fx_inbox.n_cols; ++k) j.fx_col[k] = w->fx_inbox.d_col[k];
+    j.fx_len = j.len;                                                  // the source block's len == RollbackOrdered::len at the start of the group's one AdvanceWorld
+}
+int apply_effects(ggrs_world* w) {
+    ggrs_world::EffectInbox& fx = w->fx_inbox;
+    const uint64_t len = w->len;                                       // the end-of-frame len (host-decided spawns only: the host knows it)
+    if (!len) return GGRS_OK;
+    FxApplyArgs a; memset(&a, 0, sizeof a);
+    a.live = w->live.ptr; a.len = len; a.off_alive = w->off_alive; a.n_cols = fx.n_cols; a.n_units = (uint32_t)((len + 63) / 64);
+    uint64_t bytes_slot = 0;
+    for (uint32_t k = 0; k < fx.n_cols; ++k) {
+        const uint32_t cl = fx.col[k];
+        a.off_present[k] = w->off_present[fx.comp[k]]; a.col_off[k] = w->col_off[cl]; a.ts[k] = w->col_ts[cl]; a.wb[k] = w->col_wb[cl]; a.op[k] = fx.op[k];
+        a.ident[k] = fx_identity(fx.op[k], w->col_wb[cl]); a.inbox[k] = fx.d_col[k];
+        bytes_slot += w->col_wb[cl];                                   // the inbox word is always read; the live word and the identity move only where something was sent
+    }
+    const double t0 = w->tl.on ? tl_now_us() : 0;
+    { ProfScope ps(w, GGRS_KERNEL_ADVANCE, bytes_slot * len); hipLaunchKernelGGL(k_apply_effects, dim3((a.n_units + TPB / 64 - 1) / (TPB / 64)), dim3(TPB), 0, w->stream, a); }
+    HIPCHK(w, hipGetLastError());
+    if (w->tl.on) { w->tl.launch_us += tl_now_us() - t0; ++w->tl.n_launches; }
+    w->spin_n = 0; w->batch_ev_attached = false;                       // this launch comes after whatever carried the batch event, and after a finalize that was the list's last GPU operation
+    ++fx.applies;
+    return GGRS_OK;
+}
 int run_request_groups_gen(ggrs_world* w, const ggrs_request* reqs, uint32_t n, uint64_t* checksums_out,
                            uint32_t res_base = 0, bool wait = true, uint32_t* n_saves_out = nullptr) {
     uint32_t i = 0, ns = 0; int rc = GGRS_OK;
@@ -803,7 +833,8 @@ int run_request_groups_gen(ggrs_world* w, const ggrs_request* reqs, uint32_t n, 
             ++i; if (gs.spawn_req) break;
         }
         // ---- dead / lazy / deferred: what the group need not store
-        const bool dead = !w->dev_spawn && group_is_dead(w, reqs, i, n, j.save_frame, j.n_saves, gs.spawn_req != nullptr);
+        // (effect bindings: every live sender's sends reach the inbox exactly once per simulated frame and are applied to a live block the group WROTE -- no group is dead)
+        const bool dead = !w->dev_spawn && !w->has_effects && group_is_dead(w, reqs, i, n, j.save_frame, j.n_saves, gs.spawn_req != nullptr);
         if (dead) { for (uint32_t k = 0; k < j.n_saves; ++k) j.save_dst[k] = nullptr; j.skip_live = 1; }
         const uint64_t cover = w->dev_spawn ? w->capacity : std::max(gs.cover, w->len);      // (device-decided spawns: the host only knows a bound of len)
         group_lazy_live(w, j, gs, dead, i >= n, cover);
@@ -817,6 +848,7 @@ int run_request_groups_gen(ggrs_world* w, const ggrs_request* reqs, uint32_t n, 
         // ---- policy: per-tile grid of 256-slot workgroups, depth-parallel roles
         const JitPolicy pol = jit_group_policy(cover, j.n_saves, j.src_is_live != 0, save0_bytes, group_aliases(j, wrote_live), w->jit_marks, w->dev_spawn, w->nt_copy);
         j.nt = pol.nt; j.cached_saves = pol.cached_saves; j.nt_loads = pol.nt_loads; j.dp_s = pol.dp_s;
+        if (w->has_effects) j.dp_s = 0;                                 // (every depth-parallel role runs the group's steps: a role more is every send once more)
         const bool launch = j.n_ops || !j.src_is_live;
         // identical checksum-only groups (speculative branches) ride in one launch; a batch already fills the chip, so no roles
         const bool batchable = dead && j.n_saves > 0 && !w->jit_marks && cover <= JIT_BATCH_MAX_SLOTS && !w->has_peers;   // (peer bindings: one view, published per launch)
@@ -832,18 +864,21 @@ int run_request_groups_gen(ggrs_world* w, const ggrs_request* reqs, uint32_t n, 
             FoldPlan fold = fold_route_choose(w, j, g, n_cks, launch, wait, gs.spawn_req != nullptr);
             fold_route_setup(w, j, fold, g);
             if (launch && w->has_peers && j.n_steps) { rc = publish_peers(w, *gs.src, j.len, j); if (rc) return rc; }
+            if (w->has_effects) attach_effects(w, j);
+            const bool applies = launch && w->has_effects && j.n_steps;
             if (launch) {
                 hipFunction_t fn = jit_spec_for(w, j);
                 if (!fn) fn = w->jit_fn;
                 // nothing is queued behind this kernel when its rows are folded later (or there is nothing to fold) and no spawn system follows:
                 // the batch event of an enqueued list then completes WITH it (no marker packet between this tick's kernel and the next one's)
-                const bool last_gpu_op = fold.route != FoldRoute::Finalize && !gs.spawn_req && !w->prof;
+                const bool last_gpu_op = fold.route != FoldRoute::Finalize && !gs.spawn_req && !w->prof && !applies;
                 hipEvent_t done = last_gpu_op ? w->batch_ev : nullptr;
                 rc = launch_jit(w, fn, w->dev_spawn && jit_dev_stream(w) ? g : jit_grid(g), j.dp_s ? (j.n_saves + j.dp_s) / j.dp_s : 1u, 1, jit_lane_fold_bytes(w, n_cks, j.n_saves), j, bytes_slot * w->len, done); if (rc) return rc;
                 w->batch_ev_attached = done != nullptr;
             }
             group_close(w, gs, j.n_saves, dead, wrote_live);
             rc = fold_route_record(w, j, fold, g, n_cks, res_base + ns, wait); if (rc) return rc;
+            if (applies) { rc = apply_effects(w); if (rc) return rc; }
         }
         ns += j.n_saves;
         // ---- spawn follow-up, read back
@@ -913,6 +948,7 @@ int branch_marks_reserve(ggrs_world* w, uint64_t n) {
 int validate_branch_step(ggrs_world* w, const ggrs_branch_step& st) {
     if (!w->gen_ok) return w->fail(GGRS_E_INVALID, "branch steps need the generated request-group kernel, which this world does not have: %s", w->jit_status.c_str());
     if (w->has_peers) return w->fail(GGRS_E_INVALID, "branch steps are not available for worlds with peer bindings (a member runs several frames per launch, a peer read sees the start of ONE frame): use ggrs_hip_fanout_step");
+    if (w->has_effects) return w->fail(GGRS_E_INVALID, "branch steps are not available for worlds with effect bindings (a member runs several frames per launch, the sends of ONE frame are applied behind a launch): use ggrs_hip_fanout_step");
     if (w->dev_spawn) return w->fail(GGRS_E_INVALID, "branch steps are not available for worlds whose systems spawn on the device (every launch is one cooperative grid): use ggrs_hip_fanout_step");
     if (st.n_branches == 0 || st.n_branches > BRANCH_MAX) return w->fail(GGRS_E_INVALID, "a branch step holds 1..%u branches, not %u", BRANCH_MAX, st.n_branches);
     const uint32_t S = (st.flags & GGRS_BRANCH_SAVE_LAST) ? st.n_frames : st.n_frames - 1;

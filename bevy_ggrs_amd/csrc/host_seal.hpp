@@ -73,6 +73,69 @@ int peers_validate(ggrs_world* w) {
     if (!w->knobs.tick_jit) return w->fail(GGRS_E_INVALID, "peer bindings need the generated request-group kernel, which this world does not have: disabled (GGRS_TICK_JIT=0)");
     return GGRS_OK;
 }
+void fx_inbox_release(ggrs_world* w) {
+    if (w->fx_inbox.alloc) (void)hipFree(w->fx_inbox.alloc);
+    w->fx_inbox = ggrs_world::EffectInbox{};
+}
+// Effect bindings (ggrs_hip_add_custom_system_effects): what the first version refuses, and the registration-order rules under which "all sends land at the END of
+// the frame" equals Bevy's immediate get_mut write under sequential order: nothing that runs at or after a column's first sender looks at the column, so nobody
+// can tell when inside the frame the write happened.  After build_layout; no device needed -- a GGRS_WORLD_LAYOUT_ONLY world is checked by
+// ggrs_hip_generated_kernel_source.  (peers_validate counts a sender as a writer of the column: build_layout puts effect columns into the system's write set.)
+int effects_validate(ggrs_world* w) {
+    if (!world_has_effects(w)) return GGRS_OK;
+    auto cname = [&](uint32_t c) { return w->comps[c].name.c_str(); };
+    auto colof = [&](uint32_t comp, uint32_t word) { return w->comps[comp].col_base + word; };
+    // does system k bind column cl: its own bindings, its peer bindings, the words of a built-in kind
+    auto binds = [&](size_t k, uint32_t cl) {
+        const ggrs_system_desc& d = w->systems[k];
+        auto span = [&](uint32_t comp, uint32_t word, uint32_t n) { return comp < w->comps.size() && cl >= colof(comp, word) && cl < colof(comp, word) + n && cl < colof(comp, 0) + w->comps[comp].n_words; };
+        switch (d.kind) {
+        case GGRS_SYS_PARTICLES_UPDATE: return span(d.comp[0], d.word[0], 3) || span(d.comp[1], d.word[1], 3);
+        case GGRS_SYS_TTL_DESPAWN: case GGRS_SYS_ADD_U32: case GGRS_SYS_SAT_SUB_DESPAWN: return span(d.comp[0], d.word[0], 1);
+        case GGRS_SYS_BOX_MOVE: return span(d.comp[0], d.word[0], 3) || span(d.comp[1], d.word[1], 3) || span(d.comp[2], d.word[2], 1);
+        case GGRS_SYS_CUSTOM: {
+            const ggrs_world::Custom& c = w->customs[d.comp[0]];
+            for (uint32_t b = 0; b < c.n_bind; ++b) if (colof(c.comp[b], c.word[b]) == cl) return true;
+            for (uint32_t j = 0; j < c.n_peer; ++j) if (colof(c.pcomp[j], c.pword[j]) == cl) return true;
+            return false;
+        }
+        default: return false;       // a spawn system appends rows: entities spawned in this frame cannot be hit
+        }
+    };
+    static const char* const op_name[] = {"ADD", "MIN_U", "MAX_U", "MIN_I", "MAX_I", "OR", "AND", "XOR"};
+    uint32_t cols[GGRS_EFFECT_MAX_COLUMNS], ops[GGRS_EFFECT_MAX_COLUMNS];
+    const uint32_t n_cols = effect_cols(w, cols, ops);
+    if (n_cols > GGRS_EFFECT_MAX_COLUMNS) return w->fail(GGRS_E_INVALID, "effect bindings: %u distinct effect columns in this world, at most %d (GGRS_EFFECT_MAX_COLUMNS)", n_cols, GGRS_EFFECT_MAX_COLUMNS);
+    uint64_t sent = 0;                                                  // the columns some earlier system sends to
+    for (size_t i = 0; i < w->systems.size(); ++i) {
+        if (w->systems[i].kind != GGRS_SYS_CUSTOM) continue;
+        const ggrs_world::Custom& c = w->customs[w->systems[i].comp[0]];
+        for (uint32_t j = 0; j < c.n_fx; ++j) {
+            const Comp& fc = w->comps[c.fcomp[j]];
+            const uint32_t cl = colof(c.fcomp[j], c.fword[j]);
+            const char* nm = c.name.c_str();
+            if (fc.s_n_words) return w->fail(GGRS_E_INVALID, "custom system '%s': effect binding %u sends to word %u of component %u ('%s'), which has a Strategy: effects on such a component are not supported", nm, j, c.fword[j], c.fcomp[j], cname(c.fcomp[j]));
+            if (fc.no_rollback) return w->fail(GGRS_E_INVALID, "custom system '%s': effect binding %u sends to word %u of component %u ('%s'), which is not registered for rollback (GGRS_COMP_NO_ROLLBACK): effects on such a component are not supported", nm, j, c.fword[j], c.fcomp[j], cname(c.fcomp[j]));
+            if (fc.word_bytes != 4 && fc.word_bytes != 8) return w->fail(GGRS_E_INVALID, "custom system '%s': effect binding %u sends to word %u of component %u ('%s'), whose words have %u bytes: effects need 4- or 8-byte words", nm, j, c.fword[j], c.fcomp[j], cname(c.fcomp[j]), fc.word_bytes);
+            for (uint32_t k = 0; k < n_cols; ++k) if (cols[k] == cl && ops[k] != c.fop[j])
+                return w->fail(GGRS_E_INVALID, "custom system '%s': effect binding %u sends to word %u of component %u ('%s') with GGRS_EFFECT_%s, another binding of this world with GGRS_EFFECT_%s: a column has one op in the whole world", nm, j, c.fword[j], c.fcomp[j], cname(c.fcomp[j]), op_name[c.fop[j] & 7u], op_name[ops[k] & 7u]);
+            if (cl < 64 && !((sent >> cl) & 1ull)) {
+                sent |= 1ull << cl;                                     // system i is the column's first sender
+                for (size_t k = i; k < w->systems.size(); ++k) if (binds(k, cl)) {
+                    const char* kn = w->systems[k].kind == GGRS_SYS_CUSTOM ? w->customs[w->systems[k].comp[0]].name.c_str() : "built-in";
+                    if (k == i) return w->fail(GGRS_E_INVALID, "custom system '%s' (system %zu) sends to word %u of component %u ('%s') and binds that column itself: a sender does not bind a column it sends to", nm, i, c.fword[j], c.fcomp[j], cname(c.fcomp[j]));
+                    return w->fail(GGRS_E_INVALID, "custom system '%s' (system %zu) sends to word %u of component %u ('%s'), which system %zu ('%s'), registered after it, binds: no system registered at or after the first sender of a column binds that column", nm, i, c.fword[j], c.fcomp[j], cname(c.fcomp[j]), k, kn);
+                }
+            }
+        }
+    }
+    const JitNeeds need = jit_needs(w);
+    if (need.marks) return w->fail(GGRS_E_INVALID, "effect bindings are not available in a world that keeps RollbackDespawned markers (a system that can call despawn_rollback(), or names the `kill` field)");
+    if (need.devspawn) return w->fail(GGRS_E_INVALID, "effect bindings are not available in a world that spawns on the device with e.spawn(n) (GGRS_SPAWN_PAYLOAD_PARENT)");
+    if (w->flags & (GGRS_WORLD_NO_GROUPS | GGRS_WORLD_UNFUSED)) return w->fail(GGRS_E_INVALID, "effect bindings need the generated request-group kernel, which a GGRS_WORLD_NO_GROUPS / GGRS_WORLD_UNFUSED world does not have");
+    if (!w->knobs.tick_jit) return w->fail(GGRS_E_INVALID, "effect bindings need the generated request-group kernel, which this world does not have: disabled (GGRS_TICK_JIT=0)");
+    return GGRS_OK;
+}
 int seal(ggrs_world* w) {
     if (w->layout_only) return w->fail(GGRS_E_NO_DEVICE, "GGRS_WORLD_LAYOUT_ONLY world: there is no device behind it");
     if (w->sealed) return GGRS_OK;
@@ -85,6 +148,7 @@ int seal(ggrs_world* w) {
     if (w->d_skip) { (void)hipFree(w->d_skip); w->d_skip = nullptr; }
     sp_release(w);
     peer_view_release(w);
+    fx_inbox_release(w);
     if (w->h_results) { (void)hipHostFree(w->h_results); w->h_results = nullptr; w->d_results = nullptr; }
     if (w->h_stage) { (void)hipHostFree(w->h_stage); w->h_stage = nullptr; w->d_hstage = nullptr; }
     if (w->h_rows) { (void)hipHostFree(w->h_rows); w->h_rows = nullptr; w->d_rows = nullptr; }
@@ -148,7 +212,9 @@ int seal_impl(ggrs_world* w) {
     HIPCHK(w, hipSetDevice(w->device));
     build_layout(w);
     { const int prc = peers_validate(w); if (prc) return prc; }
+    { const int frc = effects_validate(w); if (frc) return frc; }
     w->has_peers = world_has_peers(w);
+    w->has_effects = world_has_effects(w);
 
     // ---- checksum specs (the per-request k_checksum's view: one UnitDesc per hashed word)
     w->cks_comp.clear(); w->custom_hashers = false;
@@ -208,6 +274,8 @@ int seal_impl(ggrs_world* w) {
         return w->fail(GGRS_E_INVALID, "a component under a Strategy (ggrs_hip_register_component_strategy) needs the generated request-group kernel, which this world does not have: %s", w->jit_status.c_str());
     if (w->has_peers && !w->gen_ok)
         return w->fail(GGRS_E_INVALID, "peer bindings (ggrs_hip_add_custom_system_peers) need the generated request-group kernel, which this world does not have: %s", w->jit_status.c_str());
+    if (w->has_effects && !w->gen_ok)
+        return w->fail(GGRS_E_INVALID, "effect bindings (ggrs_hip_add_custom_system_effects) need the generated request-group kernel, which this world does not have: %s", w->jit_status.c_str());
     for (auto& sd : w->systems) if (sd.kind == GGRS_SYS_SPAWN_CUSTOM && !(w->gen_ok && w->jit_spawn_sys >= 0))
         return w->fail(GGRS_E_INVALID, "a user-written spawn system (ggrs_hip_add_spawn_system) runs inside the generated request-group kernel, which this world does not have "
                                        "(or the schedule holds a second spawn system): %s", w->jit_status.c_str());
@@ -314,6 +382,24 @@ int seal_impl(ggrs_world* w) {
         pv.d_vis = reinterpret_cast<uint64_t*>(pv.alloc + vis_off);
         if (w->knobs.debug_poison) HIPCHK(w, hipMemsetAsync(pv.alloc, 0xA5, bytes, w->stream));
         HIPCHK(w, hipMemsetAsync(pv.d_vis, 0, vis_bytes, w->stream));
+    }
+    if (w->has_effects) {
+        // the inbox: one linear array of cap_pad words per distinct effect column, filled with the op's identity -- what it holds whenever no group-and-apply pair is in flight
+        ggrs_world::EffectInbox& fx = w->fx_inbox;
+        fx = ggrs_world::EffectInbox{};
+        fx.n_cols = effect_cols(w, fx.col, fx.op, fx.comp);
+        uint64_t off[GGRS_EFFECT_MAX_COLUMNS], bytes = 0;
+        for (uint32_t k = 0; k < fx.n_cols; ++k) { off[k] = bytes; bytes += align_up(w->cap_pad * (uint64_t)w->col_wb[fx.col[k]], ALIGN); }
+        HIPCHK(w, hipMalloc((void**)&fx.alloc, bytes));
+        for (uint32_t k = 0; k < fx.n_cols; ++k) {
+            fx.d_col[k] = fx.alloc + off[k];
+            const uint32_t wb = w->col_wb[fx.col[k]];
+            const uint64_t id = fx_identity(fx.op[k], wb);
+            std::vector<uint8_t> fill((size_t)w->cap_pad * wb);
+            for (uint64_t e = 0; e < w->cap_pad; ++e) memcpy(fill.data() + e * wb, &id, wb);      // (little-endian: the low wb bytes)
+            HIPCHK(w, hipMemcpyAsync(fx.d_col[k], fill.data(), fill.size(), hipMemcpyHostToDevice, w->stream));
+            HIPCHK(w, hipStreamSynchronize(w->stream));                                             // (the host buffer dies here)
+        }
     }
     if (w->vtags) { HIPCHK(w, hipMalloc((void**)&w->d_skip, 8)); HIPCHK(w, hipMemsetAsync(w->d_skip, 0, 8, w->stream)); }
     if (w->dev_spawn) {

@@ -163,6 +163,8 @@ struct ggrs_world {
         uint32_t n_pres = 0, pres_comp[GGRS_CUSTOM_MAX_BINDINGS] = {};
         // peer bindings (ggrs_hip_add_custom_system_peers): words of OTHER entities the system reads through e.peer(slot), as they were at the start of the frame
         uint32_t n_peer = 0, pcomp[GGRS_PEER_MAX_BINDINGS] = {}, pword[GGRS_PEER_MAX_BINDINGS] = {};
+        // effect bindings (ggrs_hip_add_custom_system_effects): words of OTHER entities the system combines a value into through e.send_*(slot, j, v)
+        uint32_t n_fx = 0, fcomp[GGRS_EFFECT_MAX_BINDINGS] = {}, fword[GGRS_EFFECT_MAX_BINDINGS] = {}, fop[GGRS_EFFECT_MAX_BINDINGS] = {};
     };
     std::vector<Custom> customs;
     // THE PEER VIEW of a world with peer bindings (allocated at seal, filled by k_publish_peers ahead of every request group that holds an AdvanceWorld): one LINEAR
@@ -175,6 +177,15 @@ struct ggrs_world {
         uint64_t publishes = 0;
     } peer_view;
     bool has_peers = false;              // some system has peer bindings (set at seal: peer_cols)
+    // THE INBOX of a world with effect bindings (allocated at seal): one LINEAR array of cap_pad words per distinct effect column, holding the op's identity
+    // whenever no group-and-apply pair is in flight.  A send of the generated kernel is one relaxed atomic into it; k_apply_effects, on the world's stream right
+    // behind every request group that holds an AdvanceWorld, combines it into the live block and puts the identities back.  Not snapshot state
+    struct EffectInbox {
+        uint32_t n_cols = 0, col[GGRS_EFFECT_MAX_COLUMNS] = {}, op[GGRS_EFFECT_MAX_COLUMNS] = {}, comp[GGRS_EFFECT_MAX_COLUMNS] = {};   // the distinct effect columns in order of first use, their op and component
+        uint8_t* d_col[GGRS_EFFECT_MAX_COLUMNS] = {}; uint8_t* alloc = nullptr;
+        uint64_t applies = 0;
+    } fx_inbox;
+    bool has_effects = false;            // some system has effect bindings (set at seal: effect_cols)
     struct SpawnSys {                    // GGRS_SYS_SPAWN_CUSTOM: a user-written spawner (ggrs_hip_add_spawn_system; systems[i].comp[0] indexes this)
         std::string name, source;
         uint32_t n_bind = 0, comp[GGRS_CUSTOM_MAX_BINDINGS] = {}, word[GGRS_CUSTOM_MAX_BINDINGS] = {};
@@ -470,6 +481,7 @@ void build_layout(ggrs_world* w) {
         case GGRS_SYS_CUSTOM: {
             const ggrs_world::Custom& c = w->customs[sd.comp[0]];
             for (uint32_t b = 0; b < c.n_bind; ++b) mark(c.comp[b], c.word[b], 1, true);      // a bound word may be written
+            for (uint32_t j = 0; j < c.n_fx; ++j) mark(c.fcomp[j], c.fword[j], 1, true);     // an effect column: written (in OTHER entities) by the frame's sends -- every Save stores it, a sender counts as its writer
         } break;
         default: break;     // spawn systems append rows: whoever runs them versions the bundle (run_spawn_systems / the fused path in host_groups.hpp)
         }
@@ -559,8 +571,10 @@ inline uint64_t rows_bytes_hot(const ggrs_world* w) {
     for (size_t si = 0; si < w->sys_writes.size(); ++si) for (uint32_t c : w->sys_writes[si]) if (c < 64 && !((seen >> c) & 1ull)) { seen |= 1ull << c; b += w->col_wb[c]; }
     return b;
 }
+inline bool world_has_effects(const ggrs_world* w) { for (auto& c : w->customs) if (c.n_fx) return true; return false; }
 // does this world's kernel keep value tags?  (what a layout-only world -- `make aot` -- can tell as well)
 inline bool vtags_policy(const ggrs_world* w) {
+    if (world_has_effects(w)) return false;     // effect bindings: k_apply_effects rewrites live columns behind the group's launch, which a tag written by that launch would not know
     return w->knobs.row_versions && w->tag_cols && (w->vtags_mode == 1 || (w->vtags_mode < 0 && rows_bytes_hot(w) * w->capacity >= VTAGS_MIN_BYTES));
 }
 

@@ -118,7 +118,7 @@ Hiprtc& hiprtc_for(const ggrs_world* w) {
 // visibility word and a bit test; then one global_load per accessor, base + slot x word bytes.  !ok(): no load is issued, every accessor returns 0.
 // The view's pointers and word sizes are constants of the call site once ggrs_system is inlined: nothing of GgrsPeer lives in memory.
 // Worlds without peer bindings keep GGRS_ENTITY_TEXT: their generated text does not change.
-#define GGRS_ENTITY_PEERS_TEXT \
+#define GGRS_PEER_TYPES_TEXT \
     "#ifndef GGRS_G\n#define GGRS_G __attribute__((address_space(1)))\n#endif\n" \
     "struct GgrsPeerView { unsigned long col[8]; unsigned long vis; ggrs_u64 len; unsigned char wb[8]; };\n" \
     "struct GgrsPeer {\n" \
@@ -140,7 +140,8 @@ Hiprtc& hiprtc_for(const ggrs_world* w) {
     "    __device__ ggrs_u64 u64(int j) const { return raw(j); }\n" \
     "    __device__ unsigned short u16(int j) const { return (unsigned short)raw(j); }\n" \
     "    __device__ unsigned char u8(int j) const { return (unsigned char)raw(j); }\n" \
-    "};\n" \
+    "};\n"
+#define GGRS_ENTITY_PEERS_BODY_TEXT \
     "struct GgrsEntity {\n" \
     "    ggrs_u64 slot; ggrs_u64 w[8]; int kill; int spawn_n;\n" \
     "    GgrsPeerView pv_ = {};                                /* len 0: a system without peer bindings sees no peer */\n" \
@@ -157,8 +158,38 @@ Hiprtc& hiprtc_for(const ggrs_world* w) {
     "        GgrsPeer p; p.v_ = pv_; p.s_ = s; p.ok_ = false;\n" \
     "        if (s < pv_.len) p.ok_ = (*(const GGRS_G ggrs_u64*)(pv_.vis + (s >> 6) * 8ul) >> (s & 63ull)) & 1ull;\n" \
     "        return p;\n" \
-    "    }\n" \
-    "};\n"
+    "    }\n"
+#define GGRS_ENTITY_PEERS_TEXT GGRS_PEER_TYPES_TEXT GGRS_ENTITY_PEERS_BODY_TEXT "};\n"
+
+// ... in a world with effect bindings (ggrs_hip_add_custom_system_effects): e.send_*(slot, j, v) combines v into effect binding j of the entity at `slot` -- a bounds
+// test against the len of the frame's source block, then ONE relaxed agent-scope atomic into the column's linear INBOX array (host_world.hpp EffectInbox) whose result
+// is unused: a native no-return global_atomic_*, no compare-and-swap loop.  The ops are integer, commutative and associative: the inbox word does not depend on the
+// order in which lanes arrive.  The op and the word size are constants of the call site once ggrs_system is inlined.  Such a world's entity also carries the peer
+// view (empty unless the system has peer bindings): peer reads and effects may share a system.
+#define GGRS_FX_TYPES_TEXT \
+    "struct GgrsFxView { unsigned long col[8]; ggrs_u64 len; unsigned char wb[8]; unsigned char op[8]; };\n"
+#define GGRS_FX_SEND_TEXT(NAME, U, I, WB, SH) \
+    "    __device__ void " NAME "(ggrs_u64 s, int j, " U " v) const {   /* effect binding j of the entity at RollbackOrdered index s: dropped beyond the start-of-frame len */\n" \
+    "        if (s >= fx_.len || fx_.wb[j] != " WB ") return;\n" \
+    "        GGRS_G " U "* p = (GGRS_G " U "*)(fx_.col[j] + (s << " SH "));\n" \
+    "        switch (fx_.op[j]) {\n" \
+    "        case 0: (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break;\n" \
+    "        case 1: (void)__hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break;\n" \
+    "        case 2: (void)__hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break;\n" \
+    "        case 3: (void)__hip_atomic_fetch_min((GGRS_G " I "*)p, (" I ")v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break;\n" \
+    "        case 4: (void)__hip_atomic_fetch_max((GGRS_G " I "*)p, (" I ")v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break;\n" \
+    "        case 5: (void)__hip_atomic_fetch_or(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break;\n" \
+    "        case 6: (void)__hip_atomic_fetch_and(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break;\n" \
+    "        case 7: (void)__hip_atomic_fetch_xor(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break;\n" \
+    "        default: break;\n" \
+    "        }\n" \
+    "    }\n"
+#define GGRS_FX_MEMBERS_TEXT \
+    "    GgrsFxView fx_ = {};                                  /* len 0: a system without effect bindings sends nothing */\n" \
+    GGRS_FX_SEND_TEXT("send_u32", "ggrs_u32", "int", "4", "2") \
+    "    __device__ void send_i32(ggrs_u64 s, int j, int v) const { send_u32(s, j, (ggrs_u32)v); }   /* (signedness is the op's: MIN_I / MAX_I compare as int) */\n" \
+    GGRS_FX_SEND_TEXT("send_u64", "ggrs_u64", "long long", "8", "3")
+#define GGRS_ENTITY_EFFECTS_TEXT GGRS_PEER_TYPES_TEXT GGRS_FX_TYPES_TEXT GGRS_ENTITY_PEERS_BODY_TEXT GGRS_FX_MEMBERS_TEXT "};\n"
 
 // hiprtc: source -> code object -> module + kernel handle.  A compile error fails with the compiler log in w->err.
 // one compile at a time in this process: a world being sealed on the caller's thread and a specialised kernel being built on a worker
@@ -489,6 +520,9 @@ struct GgrsJitArgs {
     // THE PEER VIEW of a world with peer bindings (host_world.hpp PeerView; present only in such worlds): the linear arrays of the distinct peer-bound columns, the
     // visibility words and the len of the block k_publish_peers copied them from -- the group's source block, i.e. the world at the start of the group's one AdvanceWorld
     const unsigned char* pv_col[16]; const ggrs_u64* pv_vis; ggrs_u64 pv_len;
+    // THE INBOX of a world with effect bindings (host_world.hpp EffectInbox; present only in such worlds): the linear arrays of the distinct effect columns and the
+    // len of the group's source block -- RollbackOrdered::len at the start of the group's one AdvanceWorld: a send to a slot at or beyond it is dropped
+    unsigned char* fx_col[8]; ggrs_u64 fx_len;
     ggrs_u32 cached_saves;                           // with nt: bit i = Save i is stored through the L2 all the same (the snapshot the NEXT group is expected to load)
     ggrs_u32 ff_blocks, ff_nvals, ff_g, ff_stride, ff_istride, ff_split, ff_self;   // entry e of row r: ff_rows[r * ff_stride + e * ff_istride]
     ggrs_u32 dt_bits[24], aux_bits[24]; int step_frame[24], step_confirmed[24]; ggrs_u32 spawn_count[24];
@@ -497,6 +531,7 @@ struct GgrsJitArgs {
 };
 static_assert(MAX_TICK_SAVES == 16 && MAX_TICK_STEPS == 24, "GgrsJitArgs is sized for 16 Saves / 24 steps per group");
 static_assert(GGRS_PEER_MAX_COLUMNS == 16 && GGRS_PEER_MAX_BINDINGS == 8, "GgrsJitArgs::pv_col / GgrsPeerView are sized for 16 columns / 8 bindings");
+static_assert(GGRS_EFFECT_MAX_COLUMNS == 8 && GGRS_EFFECT_MAX_BINDINGS == 8, "GgrsJitArgs::fx_col / GgrsFxView are sized for 8 columns / 8 bindings");
 constexpr uint32_t JIT_MAX_UNITS = 128;      // 4-byte register units per slot the generated kernel may hold: everything 64 columns can be (64 eight-byte words).  Above ~56
                                              // units the kernel needs more than 64 VGPRs and runs fewer than 8 waves per SIMD -- still one launch per request GROUP, where rounds 2-5
                                              // sent such a world to one launch per REQUEST (4-5 x slower: VERDICT r5 missing 5)
@@ -514,7 +549,7 @@ struct JitLayout {
     struct Member { uint32_t bytes = 0, save_dst = 0, save_rows = 0, save_len = 0, spawn_payload = 0, spawn_first = 0, live = 0, live_rows = 0, marks_dst = 0, save_pmask = 0, live_pmask = 0,
                     spawn_count = 0, n_inputs = 0, inputs = 0, save_tagok = 0, live_tagok = 0; } m;
 };
-struct JitNeeds { bool spawn, inputs, marks, box, vtags, devspawn, devstream, nr, peers; };
+struct JitNeeds { bool spawn, inputs, marks, box, vtags, devspawn, devstream, nr, peers, effects; };
 // the distinct peer-bound columns of the world in order of first use (systems in registration order, peer bindings in order) and the components they belong to;
 // returns how many there are (more than GGRS_PEER_MAX_COLUMNS: only the first ones are written -- peers_validate refuses such a world)
 inline uint32_t peer_cols(const ggrs_world* w, uint32_t* cols, uint32_t* n_pres = nullptr, uint32_t* pres = nullptr) {
@@ -533,6 +568,21 @@ inline uint32_t peer_cols(const ggrs_world* w, uint32_t* cols, uint32_t* n_pres 
     return n;
 }
 inline bool world_has_peers(const ggrs_world* w) { for (auto& c : w->customs) if (c.n_peer) return true; return false; }
+// the distinct effect columns of the world in order of first use, the op of the first binding that names each and the component it belongs to; returns how many
+// there are (more than GGRS_EFFECT_MAX_COLUMNS: only the first ones are written -- effects_validate refuses such a world, as it does a column with two ops)
+inline uint32_t effect_cols(const ggrs_world* w, uint32_t* cols, uint32_t* ops = nullptr, uint32_t* comps = nullptr) {
+    uint32_t n = 0;
+    for (auto& c : w->customs) for (uint32_t j = 0; j < c.n_fx; ++j) {
+        if (c.fcomp[j] >= w->comps.size()) continue;
+        const uint32_t cl = w->comps[c.fcomp[j]].col_base + c.fword[j];
+        bool seen = false;
+        for (uint32_t k = 0; k < n && k < GGRS_EFFECT_MAX_COLUMNS; ++k) seen |= cols[k] == cl;
+        if (seen) continue;
+        if (n < GGRS_EFFECT_MAX_COLUMNS) { cols[n] = cl; if (ops) ops[n] = c.fop[j]; if (comps) comps[n] = c.fcomp[j]; }
+        ++n;
+    }
+    return n;
+}
 JitNeeds jit_needs(const ggrs_world* w);
 // the device-side layout of this world's argument block: 8-byte fields first, then 4-byte, then bytes (no padding inside)
 JitLayout jit_layout(const ggrs_world* w) {
@@ -543,6 +593,8 @@ JitLayout jit_layout(const ggrs_world* w) {
     L.cap_saves = std::min<uint32_t>(MAX_TICK_SAVES, std::max<uint32_t>(2, w->max_depth + 1));
     L.cap_steps = std::min<uint32_t>(MAX_TICK_STEPS, std::max<uint32_t>(3, w->max_depth + 2));
     if (need.peers) L.cap_steps = 1;             // peer reads see the world at the START of the frame: the view is published per group, so a group holds one AdvanceWorld
+    if (need.effects) L.cap_steps = 1;           // effects land at the END of the frame: the inbox is applied behind the group's launch, so a group ends on its one AdvanceWorld
+    uint32_t fx_cols[GGRS_EFFECT_MAX_COLUMNS]; const uint32_t n_fx = std::min<uint32_t>(effect_cols(w, fx_cols), GGRS_EFFECT_MAX_COLUMNS);
     uint32_t pv_cols[GGRS_PEER_MAX_COLUMNS]; const uint32_t n_pv = std::min<uint32_t>(peer_cols(w, pv_cols), GGRS_PEER_MAX_COLUMNS);
     auto add = [&](const char* type, const char* name, uint32_t elem, size_t off, uint32_t host_count, uint32_t dev_count, bool present) {
         L.f.push_back(JitField{type, name, elem, (uint32_t)off, host_count, dev_count, present, 0, 0, 0, 0, false});
@@ -561,6 +613,7 @@ JitLayout jit_layout(const ggrs_world* w) {
         F1("ggrs_u64", src_tagok, need.vtags); F1("ggrs_u64", live_tagok, need.vtags); F1("ggrs_u64*", skip_count, need.vtags); FA("ggrs_u64", save_tagok, S, need.vtags);
         F1("ggrs_u64*", gone, need.nr);
         FA("const unsigned char*", pv_col, n_pv, need.peers); F1("const ggrs_u64*", pv_vis, need.peers); F1("ggrs_u64", pv_len, need.peers);
+        FA("unsigned char*", fx_col, n_fx, need.effects); F1("ggrs_u64", fx_len, need.effects);
         FA("unsigned char*", save_dst, S, true); FA("ggrs_u64", save_rows, S, true); FA("ggrs_u64", save_len, S, true);
         FS("const unsigned char*", spawn_payload, need.spawn); FS("ggrs_u64", spawn_first, need.spawn);
         FA("int", save_frame, S, true); FA("ggrs_u32", save_pmask, S, true);
@@ -771,8 +824,9 @@ inline uint64_t jit_marks_rec_frames_off(const ggrs_world* w) { return align_up(
 inline uint64_t jit_marks_rec_bytes(const ggrs_world* w) { return jit_marks_rec_frames_off(w) + align_up(w->cap_pad * 4, ALIGN); }
 // which optional parts of the argument block this world's kernel reads
 JitNeeds jit_needs(const ggrs_world* w) {
-    JitNeeds n{false, false, false, false, false, false, false, false, false};
+    JitNeeds n{false, false, false, false, false, false, false, false, false, false};
     n.peers = world_has_peers(w);
+    n.effects = world_has_effects(w);
     n.vtags = vtags_policy(w);
     n.devspawn = jit_dev_spawn(w);
     n.devstream = jit_dev_stream(w);
@@ -796,6 +850,7 @@ bool jit_covers(const ggrs_world* w) {
     if (units == 0 || units > JIT_MAX_UNITS || ncols > JIT_MAX_COLS) return false;
     auto rb = [&](uint32_t c) { return c < nc && !w->comps[c].no_rollback; };
     uint32_t pv_cols[GGRS_PEER_MAX_COLUMNS]; const uint32_t n_pv = std::min<uint32_t>(peer_cols(w, pv_cols), GGRS_PEER_MAX_COLUMNS);
+    uint32_t fx_cols[GGRS_EFFECT_MAX_COLUMNS]; const uint32_t n_fx = std::min<uint32_t>(effect_cols(w, fx_cols), GGRS_EFFECT_MAX_COLUMNS);
     for (auto& d : w->systems) {
         switch (d.kind) {
         case GGRS_SYS_PARTICLES_SPAWN: case GGRS_SYS_SPAWN_CUSTOM: break;
@@ -808,6 +863,8 @@ bool jit_covers(const ggrs_world* w) {
             for (uint32_t i = 0; i < c.n_bind; ++i) if (!rb(c.comp[i])) return false;      // may WRITE a live-only word: not replayable
             // every peer binding finds its column in the world's peer view
             for (uint32_t j = 0; j < c.n_peer; ++j) if (std::find(pv_cols, pv_cols + n_pv, w->comps[c.pcomp[j]].col_base + c.pword[j]) == pv_cols + n_pv) return false;
+            // ... every effect binding its column in the world's inbox
+            for (uint32_t j = 0; j < c.n_fx; ++j) if (std::find(fx_cols, fx_cols + n_fx, w->comps[c.fcomp[j]].col_base + c.fword[j]) == fx_cols + n_fx) return false;
         } break;
         default: return false;
         }
@@ -922,7 +979,7 @@ struct JitGen {
                                     "#define GGRS_SP_READ %uu                                                           // sp_desc[GGRS_SP_READ x tiles + tile]: that tile has read its starting len\n",
                          2u + (unsigned)MAX_TICK_SAVES, 2u * (unsigned)MAX_TICK_STEPS);
         s += GGRS_FRAME_TEXT;
-        s += need.peers ? GGRS_ENTITY_PEERS_TEXT : GGRS_ENTITY_TEXT;
+        s += need.effects ? GGRS_ENTITY_EFFECTS_TEXT : (need.peers ? GGRS_ENTITY_PEERS_TEXT : GGRS_ENTITY_TEXT);
         s += GGRS_COMPONENT_TEXT;
         s += GGRS_WORDS_TEXT;
         s += jit_layout_text(L);
@@ -1432,6 +1489,16 @@ struct JitGen {
                 const uint32_t cl = col(c.pcomp[j], c.pword[j]);
                 uint32_t at = 0; while (at < n_pv && pv_cols[at] != cl) ++at;      // (jit_covers: the column is in the view)
                 sfmt(s, "                ent.pv_.col[%u] = (unsigned long)a.pv_col[%u]; ent.pv_.wb[%u] = %uu;\n", j, at, j, w->comps[c.pcomp[j]].word_bytes);
+            }
+        }
+        if (c.n_fx) {
+            // effect bindings: binding j sends into its column's linear array of the world's inbox, with the column's op; the bounds length is the source block's len
+            uint32_t fx_cols[GGRS_EFFECT_MAX_COLUMNS]; const uint32_t n_fx = std::min<uint32_t>(effect_cols(w, fx_cols), GGRS_EFFECT_MAX_COLUMNS);
+            s += "                ent.fx_.len = a.fx_len;\n";
+            for (uint32_t j = 0; j < c.n_fx; ++j) {
+                const uint32_t cl = col(c.fcomp[j], c.fword[j]);
+                uint32_t at = 0; while (at < n_fx && fx_cols[at] != cl) ++at;      // (jit_covers: the column is in the inbox)
+                sfmt(s, "                ent.fx_.col[%u] = (unsigned long)a.fx_col[%u]; ent.fx_.wb[%u] = %uu; ent.fx_.op[%u] = %uu;\n", j, at, j, w->comps[c.fcomp[j]].word_bytes, j, c.fop[j]);
             }
         }
         sfmt(s, "                ggrs_sys_%u::ggrs_system(ent, fr%zu);\n", d.comp[0], i);

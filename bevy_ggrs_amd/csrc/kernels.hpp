@@ -636,6 +636,67 @@ __global__ __launch_bounds__(TPB) void k_publish_peers(PeerPubArgs a) {
     }
 }
 
+// THE INBOX (ggrs_hip_add_custom_system_effects; host_world.hpp ggrs_world::EffectInbox).  Right behind every request group that holds an AdvanceWorld, the sends the
+// group's launch left in the inbox -- linear arrays, one word per slot and effect column, the op's identity where nothing was sent -- are combined into the LIVE block
+// (tile-major) and the identities are put back.  One 64-slot unit per wave: a lane reads its inbox word (coalesced); a word that is not the identity is combined into
+// the live column word when the slot is alive at the END of the frame and has the component, and dropped otherwise; either way the identity goes back.  Plain loads
+// and stores: the sends were atomics of an EARLIER launch, and a slot is touched by one lane.
+constexpr int FX_MAX_COLS = GGRS_EFFECT_MAX_COLUMNS;
+struct FxApplyArgs {
+    uint8_t* live; uint64_t len, off_alive;
+    uint64_t off_present[FX_MAX_COLS], col_off[FX_MAX_COLS], ident[FX_MAX_COLS];
+    uint8_t* inbox[FX_MAX_COLS];
+    uint32_t ts[FX_MAX_COLS], wb[FX_MAX_COLS], op[FX_MAX_COLS];
+    uint32_t n_cols, n_units;
+};
+// the identity of an effect op on a word of wb bytes (4 or 8): x op identity == x
+__host__ __device__ inline uint64_t fx_identity(uint32_t op, uint32_t wb) {
+    const uint64_t ones = wb == 8 ? ~0ull : 0xFFFFFFFFull;
+    switch (op) {
+    case GGRS_EFFECT_MIN_U: case GGRS_EFFECT_AND: return ones;
+    case GGRS_EFFECT_MIN_I: return ones >> 1;                 // the largest signed value
+    case GGRS_EFFECT_MAX_I: return (ones >> 1) + 1ull;        // the smallest
+    default: return 0ull;                                     // ADD, MAX_U, OR, XOR
+    }
+}
+template <typename U, typename I> __device__ __forceinline__ U fx_combine(uint32_t op, U x, U v) {
+    switch (op) {
+    case GGRS_EFFECT_ADD: return (U)(x + v);
+    case GGRS_EFFECT_MIN_U: return v < x ? v : x;
+    case GGRS_EFFECT_MAX_U: return v > x ? v : x;
+    case GGRS_EFFECT_MIN_I: return (I)v < (I)x ? v : x;
+    case GGRS_EFFECT_MAX_I: return (I)v > (I)x ? v : x;
+    case GGRS_EFFECT_OR: return x | v;
+    case GGRS_EFFECT_AND: return x & v;
+    case GGRS_EFFECT_XOR: return x ^ v;
+    default: return x;
+    }
+}
+__global__ __launch_bounds__(TPB) void k_apply_effects(FxApplyArgs a) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t u = blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);             // this wave's 64-slot unit == its mask word
+    if (u >= a.n_units) return;
+    const uint64_t e = (uint64_t)u * 64u + lane;
+    if (e >= a.len) return;                                                      // (a send never goes beyond the start-of-frame len, which the end-of-frame len is not below)
+    for (uint32_t c = 0; c < a.n_cols; ++c) {
+        if (a.wb[c] == 8) {
+            uint64_t* in = reinterpret_cast<uint64_t*>(a.inbox[c]) + e;
+            const uint64_t v = *in;
+            if (v == a.ident[c]) continue;
+            const uint64_t on = *reinterpret_cast<const uint64_t*>(a.live + a.off_alive + (uint64_t)u * 8u) & *reinterpret_cast<const uint64_t*>(a.live + a.off_present[c] + (uint64_t)u * 8u);
+            if ((on >> lane) & 1ull) { uint64_t* p = reinterpret_cast<uint64_t*>(a.live + col_at(a.col_off[c], a.ts[c], 8, e)); *p = fx_combine<uint64_t, int64_t>(a.op[c], *p, v); }
+            *in = a.ident[c];
+        } else {
+            uint32_t* in = reinterpret_cast<uint32_t*>(a.inbox[c]) + e;
+            const uint32_t v = *in;
+            if (v == (uint32_t)a.ident[c]) continue;
+            const uint64_t on = *reinterpret_cast<const uint64_t*>(a.live + a.off_alive + (uint64_t)u * 8u) & *reinterpret_cast<const uint64_t*>(a.live + a.off_present[c] + (uint64_t)u * 8u);
+            if ((on >> lane) & 1ull) { uint32_t* p = reinterpret_cast<uint32_t*>(a.live + col_at(a.col_off[c], a.ts[c], 4, e)); *p = fx_combine<uint32_t, int32_t>(a.op[c], *p, v); }
+            *in = (uint32_t)a.ident[c];
+        }
+    }
+}
+
 // System-scope release + acquire on whatever CU / XCD the wave lands on: `buffer_wbl2 sc0 sc1` writes the XCD's dirty L2 lines back,
 // `buffer_inv sc0 sc1` drops its clean ones.  2048 single-wave workgroups cover all 8 XCDs (workgroup b lands on XCD b % 8).
 __global__ void k_flush_l2() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, ""); }

@@ -329,11 +329,16 @@ struct CustomKernelSystem {
     std::string name, source;
     std::vector<std::pair<std::string, uint32_t>> bindings;      // (component name, word)
     std::vector<std::pair<std::string, uint32_t>> peers;         // (component name, word) of other entities, read through e.peer(slot)
+    struct Effect { std::string comp; uint32_t word, op; };
+    std::vector<Effect> effects;                                 // (component name, word, GGRS_EFFECT_*) of other entities, written through e.send_*(slot, j, v)
     int64_t iparam[2] = {0, 0};
     float fparam[4] = {0, 0, 0, 0};
     CustomKernelSystem(std::string n, std::string src) : name(std::move(n)), source(std::move(src)) {}
     template <class T> CustomKernelSystem& bind(uint32_t word) { bindings.emplace_back(HipComponent<T>::name, word); return *this; }
     template <class T> CustomKernelSystem& peer(uint32_t word) { peers.emplace_back(HipComponent<T>::name, word); return *this; }
+    // effect<T>(word, op) appends the next EFFECT binding (ggrs_hip_add_custom_system_effects): a second Query<&mut T> + get_mut(target) is
+    // `e.send_u32(slot, j, v)` / `e.send_i32` / `e.send_u64`, combined with op (integer, commutative, associative) at the end of the frame
+    template <class T> CustomKernelSystem& effect(uint32_t word, uint32_t op) { effects.push_back(Effect{HipComponent<T>::name, word, op}); return *this; }
 };
 
 // add_systems(GgrsSchedule, <a system that spawns Rollback entities>): `commands.spawn((bundle.., Rollback))` (snapshot/rollback.rs:45-59) as HIP C++ source defining
@@ -408,6 +413,7 @@ struct HipBackend {
     int add_system(const ggrs_system_desc* d) { return ggrs_hip_add_system(w, d); }
     int add_custom_system(const ggrs_custom_system_desc* d) { return ggrs_hip_add_custom_system(w, d); }
     int add_custom_system_peers(const ggrs_custom_system_desc* d, const ggrs_peer_binding* peers, uint32_t n_peers) { return ggrs_hip_add_custom_system_peers(w, d, peers, n_peers); }
+    int add_custom_system_effects(const ggrs_custom_system_desc* d, const ggrs_peer_binding* peers, uint32_t n_peers, const ggrs_effect_binding* effects, uint32_t n_effects) { return ggrs_hip_add_custom_system_effects(w, d, peers, n_peers, effects, n_effects); }
     int add_spawn_system(const ggrs_spawn_system_desc* d) { return ggrs_hip_add_spawn_system(w, d); }
     int register_component_strategy(uint32_t c, uint32_t stored_word_bytes, uint32_t stored_n_words, const char* source) { return ggrs_hip_register_component_strategy(w, c, stored_word_bytes, stored_n_words, source); }
     int set_frame_rate(uint64_t fps) { return ggrs_hip_set_frame_rate(w, fps); }
@@ -549,7 +555,11 @@ class App {
         if (s.peers.size() > GGRS_PEER_MAX_BINDINGS) throw std::invalid_argument("a custom kernel system has at most 8 peer bindings");
         ggrs_peer_binding pb[GGRS_PEER_MAX_BINDINGS];
         for (size_t k = 0; k < s.peers.size(); ++k) { pb[k].comp = comp_id(s.peers[k].first); pb[k].word = s.peers[k].second; }
-        check(s.peers.empty() ? be_.add_custom_system(&d) : be_.add_custom_system_peers(&d, pb, (uint32_t)s.peers.size()));
+        if (s.effects.size() > GGRS_EFFECT_MAX_BINDINGS) throw std::invalid_argument("a custom kernel system has at most 8 effect bindings");
+        ggrs_effect_binding eb[GGRS_EFFECT_MAX_BINDINGS];
+        for (size_t k = 0; k < s.effects.size(); ++k) { eb[k].comp = comp_id(s.effects[k].comp); eb[k].word = s.effects[k].word; eb[k].op = s.effects[k].op; }
+        if (!s.effects.empty()) check(be_.add_custom_system_effects(&d, pb, (uint32_t)s.peers.size(), eb, (uint32_t)s.effects.size()));
+        else check(s.peers.empty() ? be_.add_custom_system(&d) : be_.add_custom_system_peers(&d, pb, (uint32_t)s.peers.size()));
         return *this;
     }
     // host-side stand-in for the rolled-back ParticleRng resource (particles.rs:125,201): must be a

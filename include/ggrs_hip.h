@@ -186,8 +186,8 @@ int ggrs_hip_add_system(ggrs_world* w, const ggrs_system_desc* desc);
  * The system runs for every live entity that has all bound components, in registration order with the other systems;
  * despawns take effect before the next system, as with the built-in kinds.  The code is compiled with -ffp-contract=off
  * and correctly rounded fp32 divide/sqrt: what the source says is what runs, bit for bit, on every rank and every replay
- * -- determinism is the author's contract exactly as it is for a Bevy system (no atomics; another entity is read only through
- * e.peer(slot), ggrs_hip_add_custom_system_peers below).
+ * -- determinism is the author's contract exactly as it is for a Bevy system (no atomics of its own; another entity is read only through
+ * e.peer(slot), ggrs_hip_add_custom_system_peers below, and written only through e.send_*(slot, ..), ggrs_hip_add_custom_system_effects below).
  * The system is inlined into the request-group kernel the library generates for the world (and compiled as a kernel of its own for the
  * one-launch-per-request path).  A compile error returns GGRS_E_INVALID with the compiler log in ggrs_hip_last_error. */
 #define GGRS_SYS_CUSTOM 7u
@@ -243,6 +243,57 @@ typedef struct { uint32_t comp; uint32_t word; } ggrs_peer_binding;   /* peer bi
 #define GGRS_PEER_MAX_COLUMNS 16
 int ggrs_hip_add_custom_system_peers(ggrs_world* w, const ggrs_custom_system_desc* desc,
                                      const ggrs_peer_binding* peers, uint32_t n_peers);
+
+/* CROSS-ENTITY WRITES (effect bindings).  In the reference a system takes a second Query<&mut Health> and calls get_mut(target): a projectile damages
+ * what it hits, a healer tops up a squad, a unit marks a tile.  A system registered through this entry point may SEND to another entity.
+ * effects[j] = {comp, word, op} names effect binding j (at most GGRS_EFFECT_MAX_BINDINGS); peers / n_peers are as in
+ * ggrs_hip_add_custom_system_peers, and with n_effects == 0 the call behaves exactly as that one.  Inside ggrs_system(GgrsEntity& e, const GgrsFrame& f):
+ *
+ *     e.send_u32(slot, j, v) / e.send_i32(slot, j, v)         combine v into effect binding j of the entity at `slot`: a 4-byte column
+ *     e.send_u64(slot, j, v)                                  ... an 8-byte column
+ *
+ * with the binding's op.  A send whose width is not the column's is dropped.  Only the integer ops below are offered: each is commutative and
+ * associative, so the result does not depend on the order in which the lanes' sends arrive -- that is what lets bit-exact parity with the reference and
+ * determinism across ranks and replays survive atomics.  A float add has neither property and is refused for that reason: send a fixed-point integer.
+ *
+ *   - All sends of a frame land after the frame's systems and host-decided spawns, and before anything observes the frame: a SaveWorld, a checksum, a
+ *     download, the next frame, the next request group's peer publish.
+ *   - A send is dropped unless all of these hold: slot < RollbackOrdered::len at the start of the frame; the target is alive at the END of the frame;
+ *     the target has the component.
+ *   - Entities spawned in this frame cannot be hit.
+ *   - A target despawned in this frame drops the send.
+ *   - A sender that calls e.despawn() in the same call still sends.
+ *
+ * Seal refuses the world (GGRS_E_INVALID, the message names the system and the column) unless the rules below hold; together they make "lands at the
+ * end of the frame" equal to Bevy's immediate write under sequential order:
+ *   - no system registered at or after the first sender of a column binds that column: own bindings, peer bindings and built-in systems alike
+ *     (so the sender itself does not bind the column);
+ *   - a column has one op in the whole world;
+ *   - the component is registered for rollback, has no Strategy, and has 4- or 8-byte words.
+ * For the peer rules above a sender counts as a writer of the column.  A system registered BEFORE the sender (a death system on Hp, say) sees the
+ * frame's sends at the start of the next frame -- as it does in the reference with that registration order.
+ * This version also refuses, each with GGRS_E_INVALID and a message, as for peers: a world that keeps RollbackDespawned markers; a world that spawns
+ * on the device with e.spawn(n); a world without the generated kernel; more than GGRS_EFFECT_MAX_COLUMNS distinct effect columns in one world;
+ * ggrs_hip_fanout_step_branches on such a world (ggrs_hip_fanout_step keeps working).  Peer reads and effects in one world, and in one system, are
+ * allowed: read the target's position, send it damage.
+ * How it runs: at seal the world gets an INBOX -- one linear array per effect column, holding the op's identity -- into which a send is one relaxed
+ * atomic with no return value; a small launch right after every request group that holds an AdvanceWorld combines the inbox into the live block and puts
+ * the identities back.  Such a world's groups end on their one AdvanceWorld ([Load?] Save* Advance), its live block and ring slots are written by every
+ * group (no lazy live block, no deferred Saves, no value tags).  The inbox is not snapshot state.  The only synchronisation is the kernel boundary. */
+#define GGRS_EFFECT_ADD   0u   /* wrapping add                */
+#define GGRS_EFFECT_MIN_U 1u
+#define GGRS_EFFECT_MAX_U 2u
+#define GGRS_EFFECT_MIN_I 3u
+#define GGRS_EFFECT_MAX_I 4u
+#define GGRS_EFFECT_OR    5u
+#define GGRS_EFFECT_AND   6u
+#define GGRS_EFFECT_XOR   7u
+typedef struct { uint32_t comp; uint32_t word; uint32_t op; } ggrs_effect_binding;   /* effect binding j = word `word` of component `comp`, combined with `op` */
+#define GGRS_EFFECT_MAX_BINDINGS 8
+#define GGRS_EFFECT_MAX_COLUMNS  8
+int ggrs_hip_add_custom_system_effects(ggrs_world* w, const ggrs_custom_system_desc* desc,
+                                       const ggrs_peer_binding* peers, uint32_t n_peers,
+                                       const ggrs_effect_binding* effects, uint32_t n_effects);
 
 /* ComponentSnapshotPlugin<S: Strategy> (snapshot/strategy.rs:22-40, component_snapshot.rs:42-63): what a snapshot HOLDS of a component is
  * S::Stored, produced by S::store and turned back by S::load / S::update -- CopyStrategy / CloneStrategy (Stored == the component, bitwise for
@@ -607,7 +658,7 @@ int ggrs_hip_host_timeline(ggrs_world* w, int enable, double* us_out, uint64_t* 
  * Introspection: which kernel serves this world's request lists right now and why, what kind of arena
  * it lives on, whether the run-time compiler (libhiprtc.so, dlopen'ed) is available.  `key=value` lines,
  * NUL-terminated; *needed = bytes incl. the NUL, min(cap, *needed) are copied.  Keys: sealed, arena,
- * arena_bytes, hiprtc, generated_kernel, generated_kernel_origin, request_group_kernel, checksum_fold, kernarg_bytes, group_caps, specialised_kernel, slots_covered, row_versions, peer_view (worlds with peer bindings).
+ * arena_bytes, hiprtc, generated_kernel, generated_kernel_origin, request_group_kernel, checksum_fold, kernarg_bytes, group_caps, specialised_kernel, slots_covered, row_versions, peer_view (worlds with peer bindings), effect_inbox (worlds with effect bindings).
  * ------------------------------------------------------------------------------------------- */
 int ggrs_hip_world_kernel_info(ggrs_world* w, char* buf, uint64_t cap, uint64_t* needed);
 

@@ -107,6 +107,25 @@ pub struct ggrs_peer_binding {
 pub const GGRS_PEER_MAX_BINDINGS: usize = 8;
 pub const GGRS_PEER_MAX_COLUMNS: usize = 16;
 
+/// One effect binding of `ggrs_hip_add_custom_system_effects`: a word of OTHER entities a system writes through `e.send_*(slot, j, v)`, combined with `op`.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct ggrs_effect_binding {
+    pub comp: u32,
+    pub word: u32,
+    pub op: u32,
+}
+pub const GGRS_EFFECT_ADD: u32 = 0;
+pub const GGRS_EFFECT_MIN_U: u32 = 1;
+pub const GGRS_EFFECT_MAX_U: u32 = 2;
+pub const GGRS_EFFECT_MIN_I: u32 = 3;
+pub const GGRS_EFFECT_MAX_I: u32 = 4;
+pub const GGRS_EFFECT_OR: u32 = 5;
+pub const GGRS_EFFECT_AND: u32 = 6;
+pub const GGRS_EFFECT_XOR: u32 = 7;
+pub const GGRS_EFFECT_MAX_BINDINGS: usize = 8;
+pub const GGRS_EFFECT_MAX_COLUMNS: usize = 8;
+
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct ggrs_spawn_system_desc {
@@ -190,6 +209,7 @@ unsafe extern "C" {
     pub fn ggrs_hip_add_system(w: *mut ggrs_world, desc: *const ggrs_system_desc) -> c_int;
     pub fn ggrs_hip_add_custom_system(w: *mut ggrs_world, desc: *const ggrs_custom_system_desc) -> c_int;
     pub fn ggrs_hip_add_custom_system_peers(w: *mut ggrs_world, desc: *const ggrs_custom_system_desc, peers: *const ggrs_peer_binding, n_peers: u32) -> c_int;
+    pub fn ggrs_hip_add_custom_system_effects(w: *mut ggrs_world, desc: *const ggrs_custom_system_desc, peers: *const ggrs_peer_binding, n_peers: u32, effects: *const ggrs_effect_binding, n_effects: u32) -> c_int;
     pub fn ggrs_hip_register_component_strategy(w: *mut ggrs_world, comp_id: u32, stored_word_bytes: u32, stored_n_words: u32, source: *const c_char) -> c_int;
     pub fn ggrs_hip_set_input_layout(w: *mut ggrs_world, input_bytes: u32, max_players: u32) -> c_int;
     pub fn ggrs_hip_add_spawn_system(w: *mut ggrs_world, desc: *const ggrs_spawn_system_desc) -> c_int;

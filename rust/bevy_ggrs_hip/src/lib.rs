@@ -464,16 +464,24 @@ pub struct CustomKernelSystem {
     pub source: String,
     pub bindings: Vec<(fn(&HipWorld) -> u32, u32)>,
     pub peers: Vec<(fn(&HipWorld) -> u32, u32)>,
+    pub effects: Vec<(fn(&HipWorld) -> u32, u32, u32)>,
     pub iparam: [i64; 2],
     pub fparam: [f32; 4],
 }
 impl CustomKernelSystem {
     pub fn new(name: &'static str, source: impl Into<String>) -> Self {
-        CustomKernelSystem { name, source: source.into(), bindings: Vec::new(), peers: Vec::new(), iparam: [0; 2], fparam: [0.0; 4] }
+        CustomKernelSystem { name, source: source.into(), bindings: Vec::new(), peers: Vec::new(), effects: Vec::new(), iparam: [0; 2], fparam: [0.0; 4] }
     }
     /// Bind word `word` of component `T` of OTHER entities as the next peer binding `p.*(j)`.
     pub fn peer<T: HipComponent>(mut self, word: u32) -> Self {
         self.peers.push((HipWorld::comp_id::<T>, word));
+        self
+    }
+    /// Bind word `word` of component `T` of OTHER entities as the next effect binding (`ggrs_hip_add_custom_system_effects`): a second
+    /// `Query<&mut T>` + `get_mut(target)` is `e.send_u32(slot, j, v)` / `e.send_i32` / `e.send_u64`, combined with `op` (`ffi::GGRS_EFFECT_*`:
+    /// integer, commutative, associative) at the end of the frame.
+    pub fn effect<T: HipComponent>(mut self, word: u32, op: u32) -> Self {
+        self.effects.push((HipWorld::comp_id::<T>, word, op));
         self
     }
     /// Bind word `word` of component `T` as the next `e.*(i)`.
@@ -704,7 +712,11 @@ impl RollbackApp for App {
         }
         assert!(system.peers.len() <= ffi::GGRS_PEER_MAX_BINDINGS, "a custom kernel system has at most 8 peer bindings");
         let peers: Vec<ffi::ggrs_peer_binding> = system.peers.iter().map(|(comp, word)| ffi::ggrs_peer_binding { comp: comp(&w), word: *word }).collect();
-        let rc = if peers.is_empty() {
+        assert!(system.effects.len() <= ffi::GGRS_EFFECT_MAX_BINDINGS, "a custom kernel system has at most 8 effect bindings");
+        let effects: Vec<ffi::ggrs_effect_binding> = system.effects.iter().map(|(comp, word, op)| ffi::ggrs_effect_binding { comp: comp(&w), word: *word, op: *op }).collect();
+        let rc = if !effects.is_empty() {
+            unsafe { ffi::ggrs_hip_add_custom_system_effects(w.raw, &desc, peers.as_ptr(), peers.len() as u32, effects.as_ptr(), effects.len() as u32) }
+        } else if peers.is_empty() {
             unsafe { ffi::ggrs_hip_add_custom_system(w.raw, &desc) }
         } else {
             unsafe { ffi::ggrs_hip_add_custom_system_peers(w.raw, &desc, peers.as_ptr(), peers.len() as u32) }
