@@ -16,6 +16,7 @@ import test_branch_marks_text as marks  # noqa: E402
 import test_device_spawn_streamed_text as streamed  # noqa: E402
 import test_generated_kernel as gk  # noqa: E402
 import test_gpu_round5 as r5  # noqa: E402
+import test_peer_effects_text as effects  # noqa: E402
 import test_peer_reads_text as peers  # noqa: E402
 
 
@@ -75,6 +76,8 @@ WORLDS.update({
     "split_streamed_4m": knob("2", lambda: streamed.splitting_world(4_000_256)),
     "split_resident_tags": knob(None, lambda: tags(streamed.splitting_world())), "split_streamed_tags": knob("2", lambda: tags(streamed.splitting_world())),
     "peers_follow": peers.follow_world, "peers_follow_spawn": lambda: peers.follow_world(with_spawn=True),
+    "effects_strike": effects.strike_world, "effects_strike_spawn": lambda: effects.strike_world(with_spawn=True),
+    "peers_effects_strike": lambda: effects.strike_world(order="first"),
     "narrow_words_custom_hasher": narrow, "deferring_spawner": deferring_spawner, "deferring_spawner_tags": lambda: tags(deferring_spawner()),
 })
 

@@ -1,6 +1,6 @@
 // kernel_gen_host.cpp -- the kernel generator's host code (csrc/kernel_gen.hpp) in a stand-alone program, for the host sanitizers.  The generator sits in the
-// library's one translation unit, so that unit is compiled INTO this program with the sanitizer on its host side; the two worlds are GGRS_WORLD_LAYOUT_ONLY
-// (no device) and both forms of their kernel text are asked for.  Exit status 0 and no sanitizer report: the run is clean.  Host only, never on a GPU:
+// library's one translation unit, so that unit is compiled INTO this program with the sanitizer on its host side; the worlds are GGRS_WORLD_LAYOUT_ONLY
+// (no device): both forms of the kernel text of three are asked for, and a fourth is one the binding rules (csrc/host_seal.hpp) refuse.  Exit status 0 and no sanitizer report: the run is clean.  Host only, never on a GPU:
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off -fno-fast-math -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-omit-frame-pointer \
 //         -Iinclude tests/cpp/kernel_gen_host.cpp -o tests/cpp/_build/kernel_gen_host && tests/cpp/_build/kernel_gen_host
 #include "../../bevy_ggrs_amd/csrc/ggrs_hip.hip"
@@ -69,6 +69,37 @@ int main() {
     check(m, ggrs_hip_add_custom_system(m, &c), "decrease_health");
     const size_t nm = texts(m);
     ggrs_hip_world_destroy(m);
-    printf("kernel_gen_host: ok (%zu + %zu bytes of kernel text)\n", np, nm);
+
+    // peer and effect bindings in one system, next to every built-in kind the rules walk over: the striker (registered first: the peer rules) reads Pos.x of its
+    // target and sends to Hp; then a countdown that despawns, a mover over Pos / Vel with a read-only Player.handle outside every snapshot
+    const char* strike = "__device__ void ggrs_system(GgrsEntity& e, const GgrsFrame&) {\n"
+                         "    const GgrsPeer p = e.peer(e.u64(0));\n"
+                         "    e.send_u32(e.u64(0), 0, p.ok() ? (__float_as_uint(p.f32(0)) & 3u) : 7u);\n"
+                         "}\n";
+    auto strike_world = [&](bool hp_bound_later) {
+        ggrs_world* s = layout_world(20000, 8);
+        const uint32_t P = component(s, "Pos", 4, 3), Vv = component(s, "Vel", 4, 3), Pl = component(s, "Player", 8, 1, GGRS_COMP_NO_ROLLBACK);
+        const uint32_t Tg = component(s, "Target", 8, 1), F = component(s, "Fuse", 4, 1), Hp = component(s, "Hp", 4, 1);
+        check(s, ggrs_hip_checksum_component(s, Hp, w0, 1), "checksum Hp");
+        ggrs_custom_system_desc k = {};
+        k.name = "striker"; k.n_bindings = 1; k.comp[0] = Tg; k.word[0] = 0; k.source = strike;
+        const ggrs_peer_binding peer = {P, 0};
+        const ggrs_effect_binding fx = {Hp, 0, GGRS_EFFECT_ADD};
+        check(s, ggrs_hip_add_custom_system_effects(s, &k, &peer, 1, &fx, 1), "striker");
+        ggrs_system_desc cd = {}; cd.kind = GGRS_SYS_SAT_SUB_DESPAWN; cd.comp[0] = hp_bound_later ? Hp : F; cd.iparam[0] = 1;
+        ggrs_system_desc mv = {}; mv.kind = GGRS_SYS_BOX_MOVE; mv.comp[0] = P; mv.comp[1] = Vv; mv.comp[2] = Pl;
+        check(s, ggrs_hip_add_system(s, &cd), "countdown"); check(s, ggrs_hip_add_system(s, &mv), "move_cube");
+        return s;
+    };
+    ggrs_world* s = strike_world(false);
+    const size_t ns = texts(s);
+    ggrs_hip_world_destroy(s);
+    // ... and the same world with the countdown over the effect column: refused, naming system 1
+    ggrs_world* r = strike_world(true);
+    uint64_t need = 0;
+    const int rc = ggrs_hip_generated_kernel_source(r, GGRS_KERNEL_FORM_TILES, nullptr, 0, &need, 0);
+    if (rc != GGRS_E_INVALID || !strstr(ggrs_hip_last_error(r), "which system 1 ('built-in'), registered after it, binds")) { fprintf(stderr, "not refused: %d %s\n", rc, ggrs_hip_last_error(r)); return 1; }
+    ggrs_hip_world_destroy(r);
+    printf("kernel_gen_host: ok (%zu + %zu + %zu bytes of kernel text, one world refused)\n", np, nm, ns);
     return 0;
 }
