@@ -49,6 +49,15 @@ __host__ __device__ __forceinline__ uint64_t sea_pair_pre(uint64_t B, uint64_t i
     uint64_t C = sea_diffuse(SEA_K1 ^ inner);
     return sea_diffuse(SEA_K2 ^ SEA_K3 ^ B ^ C ^ 16ULL);
 }
+// PRE-FOLDED forms for the generated kernel, which is bound by its vector ALUs: a finish xors K2 ^ K3 ^ <bytes written> into its last
+// diffuse's argument, next to a value the kernel keeps across Saves anyway -- the memoised tail of a 9..12-byte spec, the order lane of the
+// slot.  Kept values carry the constant from where they are (re)computed, so a finish is one xor and one diffuse.  Same arithmetic, same
+// results: sea_inner_folded(full, sea_tail_folded(z, n)) == SeaStream{full word, n - 8 tail bytes}.finish(),
+// sea_pair_folded(sea_order_lane_folded(o), i) == sea_pair(o, i)  (tests/cpp/sea_fold_host.cpp)
+__host__ __device__ __forceinline__ uint64_t sea_tail_folded(uint64_t tail, uint64_t nbytes) { return sea_diffuse(SEA_K1 ^ tail) ^ SEA_K2 ^ SEA_K3 ^ nbytes; }
+__host__ __device__ __forceinline__ uint64_t sea_inner_folded(uint64_t full, uint64_t tail_folded) { return sea_diffuse(tail_folded ^ sea_diffuse(SEA_K0 ^ full)); }
+__host__ __device__ __forceinline__ uint64_t sea_order_lane_folded(uint64_t order) { return sea_diffuse(SEA_K0 ^ order) ^ SEA_K2 ^ SEA_K3 ^ 16ULL; }
+__host__ __device__ __forceinline__ uint64_t sea_pair_folded(uint64_t B_folded, uint64_t inner) { return sea_diffuse(B_folded ^ sea_diffuse(SEA_K1 ^ inner)); }
 // SeaHasher::new(); write_u64(x); finish()  -- component_checksum.rs:92-95
 __host__ __device__ __forceinline__ uint64_t sea_one(uint64_t x) {
     uint64_t A = sea_diffuse(SEA_K0 ^ x);

@@ -1123,7 +1123,10 @@ struct JitGen {
         s += "    if (in_len) {\n";
         emit_load("a.src", "a.load_rows", "        ");
         s += "    }\n"
-             "    const uint64_t ordB_0 = sea_order_lane(e0);\n";
+             "    const uint64_t ordB_0 = sea_order_lane_folded(e0);                        // carries the pair finish's K2 ^ K3 ^ 16 (device_prelude.hpp)\n";
+        // the lane's cell of s_lane row 0, as an LDS address held in ONE register (made opaque: the compiler otherwise rebuilds base + lane * 8 in front of every
+        // conditional xor -- two VALU ops each); a row is 64 cells further
+        if (lane_fold) s += "    __attribute__((address_space(3))) ggrs_u64* lc_ = (__attribute__((address_space(3))) ggrs_u64*)&s_lane[lane]; asm volatile(\"\" : \"+v\"(lc_));\n";
     }
     // ---- 5. loads / stores of the words of the lane's slot from / to a block, each guarded by its bit of a wave-uniform row mask
     // Row masks are wave-uniform.  The masks of a steady-state tick are known when the kernel is written -- a SaveWorld stores
@@ -1292,7 +1295,7 @@ struct JitGen {
     void unit_state() {
         for (uint32_t k = 0; k < n_cks; ++k) if (spec_memo[k]) {
             const std::string tail = chunk_expr(w->comps[cks_comp[k]], cks_comp[k], 8, spec_bytes[k] - 8);
-            sfmt(s, "    uint32_t mt%u = (uint32_t)(%s); uint64_t ma%u = a.n_saves ? sea_diffuse(SEA_K1 ^ (uint64_t)mt%u) : 0ull;   // memoised tail of checksum spec %u\n", k, tail.c_str(), k, k, k);
+            sfmt(s, "    uint32_t mt%u = (uint32_t)(%s); uint64_t ma%u = a.n_saves ? sea_tail_folded(mt%u, %uull) : 0ull;   // memoised tail of checksum spec %u, with the finish's K2 ^ K3 ^ bytes folded in\n", k, tail.c_str(), k, k, spec_bytes[k], k);
         }
         if (need.marks) {
             sfmt(s, "    // RollbackDespawned markers (despawn.rs:45-46): live-only, never part of a snapshot\n"
@@ -1342,29 +1345,31 @@ struct JitGen {
     void emit_checksum(uint32_t k) {
         const uint32_t c = cks_comp[k];
         const Comp& cc = w->comps[c];
-        s += "            {   // ComponentChecksumPlugin::update (component_checksum.rs:77-90): per-entity hash, paired with the order index\n"
-             "                uint64_t hx = 0;\n";
+        // A lane has a hash when its entity is alive and has the component.  lane_fold: only those lanes touch their LDS cell (xor of a zero
+        // from every other lane is the same result and a select pair + an LDS op more); the wave_xor form needs every lane's value, zero included.
+        s += "            {   // ComponentChecksumPlugin::update (component_checksum.rs:77-90): per-entity hash, paired with the order index\n";
+        char sink[2][160];
+        if (lane_fold) { snprintf(sink[0], sizeof sink[0], "if (alive_0 && p%u_0) atomicXor((ggrs_u64*)(lc_ + (si * %uu + %uu) * 64u), (ggrs_u64)", c, n_cks, k); snprintf(sink[1], sizeof sink[1], ");"); }
+        else { snprintf(sink[0], sizeof sink[0], "hx = (alive_0 && p%u_0) ? ", c); snprintf(sink[1], sizeof sink[1], " : 0ull;"); s += "                uint64_t hx = 0;\n"; }
         if (!cc.cks_source.empty()) {
             s += "                { GgrsComponent cv; cv.slot = e0;\n";
             for (uint32_t wi = 0; wi < cc.n_words; ++wi) sfmt(s, "                  cv.w[%u] = w%u_0;\n", wi, col(c, wi));
-            sfmt(s, "                  hx = (alive_0 && p%u_0) ? sea_pair_pre(ordB_0, ggrs_hash_%u::ggrs_hash(cv)) : 0ull; }\n", c, c);
+            sfmt(s, "                  %ssea_pair_folded(ordB_0, ggrs_hash_%u::ggrs_hash(cv))%s }\n", sink[0], c, sink[1]);
         } else if (spec_memo[k]) {
             // 8 < bytes <= 12 (one full word + a tail of <= 4 bytes, the stress_test's three f32): SeaHasher spelled out, with the
             // tail's diffuse memoised -- a word no step changed since the last SaveWorld (translation.z, velocity.z of a 2-D
             // simulation) hashes to what it hashed to then.  Value-keyed and wave-uniform: any lane that changed recomputes all.
             const std::string full = chunk_expr(cc, c, 0, 8), tail = chunk_expr(cc, c, 8, spec_bytes[k] - 8);
             sfmt(s, "                { const uint32_t tv = (uint32_t)(%s);\n"
-                    "                  if (__ballot(tv != mt%u) != 0ull) { mt%u = tv; ma%u = sea_diffuse(SEA_K1 ^ (uint64_t)tv); }\n"
-                    "                  const uint64_t A = sea_diffuse(SEA_K0 ^ (%s));\n"
-                    "                  const uint64_t inner = sea_diffuse(ma%u ^ SEA_K2 ^ SEA_K3 ^ A ^ %uull);\n"
-                    "                  hx = (alive_0 && p%u_0) ? sea_pair_pre(ordB_0, inner) : 0ull; }\n",
-                 tail.c_str(), k, k, k, full.c_str(), k, spec_bytes[k], c);
+                    "                  if (__ballot(tv != mt%u) != 0ull) { mt%u = tv; ma%u = sea_tail_folded(tv, %uull); }\n"
+                    "                  %ssea_pair_folded(ordB_0, sea_inner_folded(%s, ma%u))%s }\n",
+                 tail.c_str(), k, k, k, spec_bytes[k], sink[0], full.c_str(), k, sink[1]);
         } else {
             s += "                { SeaStream st;";
             for (uint32_t wi : cc.cks_words) sfmt(s, " st.write(w%u_0, %uu);", col(c, wi), cc.word_bytes);
-            sfmt(s, " hx = (alive_0 && p%u_0) ? sea_pair_pre(ordB_0, st.finish()) : 0ull; }\n", c);
+            sfmt(s, " %ssea_pair_folded(ordB_0, st.finish())%s }\n", sink[0], sink[1]);
         }
-        if (lane_fold) sfmt(s, "                atomicXor(&s_lane[(si * %uu + %uu) * 64u + lane], (ggrs_u64)hx);\n            }\n", n_cks, k);
+        if (lane_fold) s += "            }\n";
         else
         sfmt(s, "                hx = wave_xor(hx);\n"
                 "                if (lane == 0) atomicXor(&acc[%u], (ggrs_u64)hx);\n"
@@ -1443,7 +1448,8 @@ struct JitGen {
     }
     void sys_ttl_despawn(const ggrs_system_desc& d) {
         const uint32_t q = col(d.comp[0], d.word[0]);
-        sfmt(s, "            if (alive_0 && p%u_0) { w%u_0 -= 1; if (w%u_0 == 0) alive_0 = false; }      // particles.rs:282-289\n", d.comp[0], q, q);
+        // (no assignment under a divergent branch: candidate, select, predicate -- the liveness mask then stays a lane mask in SGPRs instead of a 0/1 VGPR that is compared again)
+        sfmt(s, "            { const bool t_ = alive_0 && p%u_0; const %s n_ = w%u_0 - 1; w%u_0 = t_ ? n_ : w%u_0; alive_0 = alive_0 && !(t_ && n_ == 0); }      // particles.rs:282-289\n", d.comp[0], wtype(d.comp[0]), q, q, q);
     }
     void sys_add_u32(const ggrs_system_desc& d) {
         const uint32_t q = col(d.comp[0], d.word[0]);
@@ -1451,11 +1457,16 @@ struct JitGen {
     }
     void sys_sat_sub_despawn(const ggrs_system_desc& d) {
         const uint32_t q = col(d.comp[0], d.word[0]);
+        if (d.iparam[1] != GGRS_DESPAWN_ROLLBACK) {             // an immediate despawn keeps no marker: branch-free, as sys_ttl_despawn
+            sfmt(s, "            { const bool t_ = alive_0 && p%u_0; const %s n_ = w%u_0 >= %uu ? w%u_0 - %uu : 0u; w%u_0 = t_ ? n_ : w%u_0; alive_0 = alive_0 && !(t_ && n_ == 0u); }      // tests/synctest.rs:37-44\n",
+                 d.comp[0], wtype(d.comp[0]), q, (uint32_t)d.iparam[0], q, (uint32_t)d.iparam[0], q, q);
+            return;
+        }
         sfmt(s, "            if (alive_0 && p%u_0) {                                              // tests/synctest.rs:37-44\n"
                 "                w%u_0 = w%u_0 >= %uu ? w%u_0 - %uu : 0u;\n"
                 "                if (w%u_0 == 0) {\n", d.comp[0], q, q, (uint32_t)d.iparam[0], q, (uint32_t)d.iparam[0], q);
-        if (d.iparam[1] == GGRS_DESPAWN_ROLLBACK) s += "                    if (defer) { dis_0 = true; df_0 = a.step_frame[sj]; }\n";
-        s += "                    alive_0 = false;\n                }\n            }\n";
+        s += "                    if (defer) { dis_0 = true; df_0 = a.step_frame[sj]; }\n"
+             "                    alive_0 = false;\n                }\n            }\n";
     }
     void sys_box_move(size_t i, const ggrs_system_desc& d) {
         const bool h_rb = rb(d.comp[2]);

@@ -1,5 +1,5 @@
 // ubench_alu.hip -- the chip's ceiling for the checksum arithmetic: SeaHash `diffuse` (two 64-bit multiplies by a constant +
-// a variable shift-xor) per second over all CUs, and the instruction mix behind it (v_mul_lo_u32 / v_mad_u64_u32 rates).
+// a variable shift-xor) per second over all CUs, and the instruction mix behind it (v_mul_lo_u32 / v_mad_u64_u32 / v_fma_f32 chains).
 // Used to state a roofline for the checksum-only paths (BASELINE config 5 after dead-snapshot elimination) and to judge how
 // far the hash ALU of a fused tick is from its floor.   build: hipcc --offload-arch=gfx950 -O3 ubench_alu.hip -o ubench_alu
 #include <hip/hip_runtime.h>
@@ -11,19 +11,51 @@ constexpr uint64_t P = 0x6eed0e9da4d94a4fULL;
 // (v_lshrrev_b64 per diffuse: rounds 4-5) was one the kernels could exceed (config 5 read 1.02 of it in profiles/r06final)
 __device__ __forceinline__ uint64_t diffuse(uint64_t x) { x *= P; const uint32_t hi = (uint32_t)(x >> 32); x ^= (uint64_t)(hi >> (hi >> 28)); x *= P; return x; }
 
-template <int CH>
+// EXPERIMENT (profiles/valu_trim): the multiply by P as three v_mad_u64_u32 and one add instead of what the compiler makes of `x *= P`
+// (2 v_mul_lo_u32 + v_mad_u64_u32 + v_add3_u32).  The cross terms xh*Pl + xl*Ph go through a chain of two of them of which only the low half is
+// used; the third is the full xl*Pl.  gfx950's VOP3 takes no literal: the halves of P sit in SGPRs.  v_mad_u64_u32 writes a carry-out: vcc, declared.
+__device__ __forceinline__ uint64_t mad64_0(uint32_t a, uint32_t b) { uint64_t d; asm("v_mad_u64_u32 %0, vcc, %1, %2, 0" : "=v"(d) : "v"(a), "s"(b) : "vcc"); return d; }
+__device__ __forceinline__ uint64_t mad64(uint32_t a, uint32_t b, uint64_t c) { uint64_t d; asm("v_mad_u64_u32 %0, vcc, %1, %2, %3" : "=v"(d) : "v"(a), "s"(b), "v"(c) : "vcc"); return d; }
+__device__ __forceinline__ uint64_t mul_p_mad3(uint64_t x) {
+    const uint32_t xl = (uint32_t)x, xh = (uint32_t)(x >> 32), pl = (uint32_t)P, ph = (uint32_t)(P >> 32);
+    const uint64_t cross = mad64(xl, ph, mad64_0(xh, pl));         // low half: (xh*Pl + xl*Ph) mod 2^32; the high half is never read
+    const uint64_t r = mad64_0(xl, pl);
+    return r + ((uint64_t)(uint32_t)cross << 32);                    // one v_add_u32 on the high half
+}
+__device__ __forceinline__ uint64_t diffuse_mad3(uint64_t x) { x = mul_p_mad3(x); const uint32_t hi = (uint32_t)(x >> 32); x ^= (uint64_t)(hi >> (hi >> 28)); x = mul_p_mad3(x); return x; }
+
+template <int CH, bool MAD3 = false>
 __global__ __launch_bounds__(256) void k_diffuse(uint64_t* out, int iters) {
     uint64_t x[CH];
 #pragma unroll
     for (int c = 0; c < CH; ++c) x[c] = (uint64_t)(blockIdx.x * 256 + threadIdx.x) * 0x9e3779b97f4a7c15ull + c;
     for (int i = 0; i < iters; ++i) {
 #pragma unroll
-        for (int c = 0; c < CH; ++c) x[c] = diffuse(x[c] ^ (uint64_t)i);
+        for (int c = 0; c < CH; ++c) x[c] = MAD3 ? diffuse_mad3(x[c] ^ (uint64_t)i) : diffuse(x[c] ^ (uint64_t)i);
     }
     uint64_t r = 0;
 #pragma unroll
     for (int c = 0; c < CH; ++c) r ^= x[c];
     if (r == 0x1234567) out[0] = r;          // never true: keeps the chains alive
+}
+// the two spellings agree: one diffuse of each per thread, compared on the host
+__global__ void k_diffuse_check(const uint64_t* in, uint64_t* a, uint64_t* b, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) { a[i] = diffuse(in[i]); b[i] = diffuse_mad3(in[i]); }
+}
+template <int CH>
+__global__ __launch_bounds__(256) void k_mad64(uint64_t* out, int iters) {           // v_mad_u64_u32 chains: x = lo(x) * K + x
+    uint64_t x[CH];
+#pragma unroll
+    for (int c = 0; c < CH; ++c) x[c] = (uint64_t)(blockIdx.x * 256 + threadIdx.x) * 0x9e3779b97f4a7c15ull + c;
+    for (int i = 0; i < iters; ++i) {
+#pragma unroll
+        for (int c = 0; c < CH; ++c) x[c] = mad64((uint32_t)x[c], 0xa4d94a4fu, x[c]);
+    }
+    uint64_t r = 0;
+#pragma unroll
+    for (int c = 0; c < CH; ++c) r ^= x[c];
+    if (r == 0x1234567) out[0] = r;
 }
 template <int CH>
 __global__ __launch_bounds__(256) void k_mul32(uint32_t* out, int iters) {           // v_mul_lo_u32 chains
@@ -67,6 +99,20 @@ int main() {
     int clk = 0; hipDeviceGetAttribute(&clk, hipDeviceAttributeClockRate, 0);
     void* out; hipMalloc(&out, 4096);
     const int iters = 4096;
+    {   // the experiment's spelling against the kernels' own, on edge values and a few thousand others
+        const int n = 4096; std::vector<uint64_t> h(n), ha(n), hb(n);
+        uint64_t z = 0x243f6a8885a308d3ull;
+        for (int i = 0; i < n; ++i) { z = z * 6364136223846793005ull + 1442695040888963407ull; h[i] = z; }
+        h[0] = 0; h[1] = ~0ull; h[2] = 1ull << 31; h[3] = 1ull << 63; h[4] = 0x80000000ull; h[5] = 0xffffffffull; h[6] = 0xffffffff00000000ull;
+        uint64_t *di, *da, *db; hipMalloc(&di, n * 8); hipMalloc(&da, n * 8); hipMalloc(&db, n * 8);
+        hipMemcpy(di, h.data(), n * 8, hipMemcpyHostToDevice);
+        hipLaunchKernelGGL(k_diffuse_check, dim3(n / 256), dim3(256), 0, 0, di, da, db, n);
+        hipMemcpy(ha.data(), da, n * 8, hipMemcpyDeviceToHost); hipMemcpy(hb.data(), db, n * 8, hipMemcpyDeviceToHost);
+        int bad = 0; for (int i = 0; i < n; ++i) bad += ha[i] != hb[i];
+        printf("mad3 spelling == own spelling on %d inputs: %s\n", n, bad ? "NO" : "yes");
+        hipFree(di); hipFree(da); hipFree(db);
+        if (bad) return 1;
+    }
     printf("CUs %d, clock attr %d kHz\n", n_cu, clk);
     printf("%-28s %8s %12s %14s %14s\n", "kernel", "waves/SIMD", "ms", "G ops/s", "cyc/op/SIMD@2.4GHz");
     for (int wps : {1, 2, 4, 8}) {
@@ -80,6 +126,13 @@ int main() {
         report("diffuse x4 chains", time_ms([&] { hipLaunchKernelGGL(k_diffuse<4>, dim3(blocks), dim3(256), 0, 0, (uint64_t*)out, iters); }), iters * 4.0);
         report("diffuse x8 chains", time_ms([&] { hipLaunchKernelGGL(k_diffuse<8>, dim3(blocks), dim3(256), 0, 0, (uint64_t*)out, iters); }), iters * 8.0);
         report("v_mul_lo_u32 x8 chains", time_ms([&] { hipLaunchKernelGGL(k_mul32<8>, dim3(blocks), dim3(256), 0, 0, (uint32_t*)out, iters); }), iters * 8.0);
+        report("v_mad_u64_u32 x8 chains", time_ms([&] { hipLaunchKernelGGL(k_mad64<8>, dim3(blocks), dim3(256), 0, 0, (uint64_t*)out, iters); }), iters * 8.0);
+        // the experiment, in the same process: the own spelling three more times (its spread is the bar), the mad3 spelling three times, interleaved
+        for (int rep = 0; rep < 3; ++rep) {
+            report("diffuse x8 chains (rep)", time_ms([&] { hipLaunchKernelGGL((k_diffuse<8, false>), dim3(blocks), dim3(256), 0, 0, (uint64_t*)out, iters); }), iters * 8.0);
+            report("mad3 diffuse x8 chains", time_ms([&] { hipLaunchKernelGGL((k_diffuse<8, true>), dim3(blocks), dim3(256), 0, 0, (uint64_t*)out, iters); }), iters * 8.0);
+        }
+        report("mad3 diffuse x4 chains", time_ms([&] { hipLaunchKernelGGL((k_diffuse<4, true>), dim3(blocks), dim3(256), 0, 0, (uint64_t*)out, iters); }), iters * 4.0);
         report("v_fma_f32 x8 chains", time_ms([&] { hipLaunchKernelGGL(k_fma32<8>, dim3(blocks), dim3(256), 0, 0, (float*)out, iters); }), iters * 8.0);
     }
     return 0;
