@@ -2,6 +2,19 @@
 // and by the kernels generated at run time (ggrs_hip.hip includes it as a string and hands it to hiprtc): one text, so the
 // SeaHash arithmetic and the box_game step cannot drift between the two.  The whole body is the argument of
 // GGRS_SHARED_CODE(...): comments are fine (they are gone before macro expansion), preprocessor directives are not.
+// The SeaHash multiply of the HOT path has two spellings, and which one a translation unit gets is settled here, in front of the shared text (a directive
+// cannot sit inside the macro argument).  Device code: x * SEA_P as three v_mad_u64_u32 (sea_mul_p_mad3 below) -- the compiler's own lowering is two
+// v_mul_lo_u32, one v_mad_u64_u32 and a v_add3_u32, and v_mul_lo_u32 is the dearer multiply (profiles/mad3_multiply).  Host code keeps x * SEA_P.  A generated
+// text brings these two macros itself and chooses per text (kernel_gen.hpp kJitSeaSpelling): the static kernels call none of the hot helpers.
+#ifndef GGRS_SEA_MUL_HOT
+#if defined(__HIP_DEVICE_COMPILE__) && __HIP_DEVICE_COMPILE__
+#define GGRS_VGPR_OPAQUE(c) asm("" : "+v"(c))
+#define GGRS_SEA_MUL_HOT(x) sea_mul_p_mad3(x)
+#else
+#define GGRS_VGPR_OPAQUE(c) ((void)0)
+#define GGRS_SEA_MUL_HOT(x) ((x) * SEA_P)
+#endif
+#endif
 GGRS_SHARED_CODE(
 constexpr int LT_SHIFT = 13;   // log2 of the slots of a LAYOUT tile (8 workgroup tiles)
 constexpr int LAYOUT_TILE = 1 << LT_SHIFT;
@@ -21,6 +34,24 @@ __host__ __device__ __forceinline__ uint64_t sea_diffuse(uint64_t x) {
     x ^= (uint64_t)(hi >> (hi >> 28));
     x *= SEA_P;
     return x;
+}
+// x * SEA_P from 32-bit halves: xl * Pl in full, and the low half of the cross sum xh * Pl + xl * Ph shifted up -- the sum may wrap modulo 2^64, only its low
+// 32 bits are used.  Exact (tests/cpp/sea_mad3_host.cpp).  On the device each product is one v_mad_u64_u32; GGRS_VGPR_OPAQUE (nothing on the host) keeps the
+// compiler from narrowing the cross sum back to v_mul_lo_u32.  No instruction sits inside an asm, so constants still fold through it.
+__host__ __device__ __forceinline__ uint64_t sea_mul_p_mad3(uint64_t x) {
+    const uint32_t xl = (uint32_t)x, xh = (uint32_t)(x >> 32);
+    uint64_t c = (uint64_t)xh * (uint32_t)SEA_P;
+    c = (uint64_t)xl * (uint32_t)(SEA_P >> 32) + c;
+    GGRS_VGPR_OPAQUE(c);
+    return (uint64_t)xl * (uint32_t)SEA_P + (c << 32);
+}
+// sea_diffuse for the generated kernel's hot path (sea_inner_folded, sea_pair_folded: both multiplicands are run-time values).  Everything whose multiplicand
+// has a constant half -- the memoised tails, the order lane -- and every other caller keeps sea_diffuse: the compiler folds a product away there.
+__host__ __device__ __forceinline__ uint64_t sea_diffuse_hot(uint64_t x) {
+    x = GGRS_SEA_MUL_HOT(x);
+    const uint32_t hi = (uint32_t)(x >> 32);
+    x ^= (uint64_t)(hi >> (hi >> 28));
+    return GGRS_SEA_MUL_HOT(x);
 }
 // SeaHasher::new(); write_u32(x); write_u32(y); write_u32(z); finish()  (12 bytes: one full
 // word + a 4-byte tail) -- particles.rs:107-120 / 207-222.
@@ -55,9 +86,9 @@ __host__ __device__ __forceinline__ uint64_t sea_pair_pre(uint64_t B, uint64_t i
 // results: sea_inner_folded(full, sea_tail_folded(z, n)) == SeaStream{full word, n - 8 tail bytes}.finish(),
 // sea_pair_folded(sea_order_lane_folded(o), i) == sea_pair(o, i)  (tests/cpp/sea_fold_host.cpp)
 __host__ __device__ __forceinline__ uint64_t sea_tail_folded(uint64_t tail, uint64_t nbytes) { return sea_diffuse(SEA_K1 ^ tail) ^ SEA_K2 ^ SEA_K3 ^ nbytes; }
-__host__ __device__ __forceinline__ uint64_t sea_inner_folded(uint64_t full, uint64_t tail_folded) { return sea_diffuse(tail_folded ^ sea_diffuse(SEA_K0 ^ full)); }
+__host__ __device__ __forceinline__ uint64_t sea_inner_folded(uint64_t full, uint64_t tail_folded) { return sea_diffuse_hot(tail_folded ^ sea_diffuse_hot(SEA_K0 ^ full)); }
 __host__ __device__ __forceinline__ uint64_t sea_order_lane_folded(uint64_t order) { return sea_diffuse(SEA_K0 ^ order) ^ SEA_K2 ^ SEA_K3 ^ 16ULL; }
-__host__ __device__ __forceinline__ uint64_t sea_pair_folded(uint64_t B_folded, uint64_t inner) { return sea_diffuse(B_folded ^ sea_diffuse(SEA_K1 ^ inner)); }
+__host__ __device__ __forceinline__ uint64_t sea_pair_folded(uint64_t B_folded, uint64_t inner) { return sea_diffuse_hot(B_folded ^ sea_diffuse_hot(SEA_K1 ^ inner)); }
 // SeaHasher::new(); write_u64(x); finish()  -- component_checksum.rs:92-95
 __host__ __device__ __forceinline__ uint64_t sea_one(uint64_t x) {
     uint64_t A = sea_diffuse(SEA_K0 ^ x);

@@ -247,6 +247,17 @@ static const char kJitPrelude[] =
 #include "device_prelude.hpp"
 #undef GGRS_SHARED_CODE
     ;
+// ... and the lines in front of it in device_prelude.hpp, which choose the hot path's multiply.  The generator decides per text, with what it knows when it
+// writes one: a copy specialised for one op sequence (GGRS_SPEC, jit_specialise) takes the three-mad multiply -- that is where a session's ticks run --, the
+// generic copy keeps x * SEA_P.  Generic copies sit at 56..90 VGPRs and the spelling costs up to 16 more there: 3 of the 32 known worlds' generic copies went
+// into the next 8-register granule above 64 with it (a wave per SIMD or more); of the specialised copies none did (profiles/mad3_multiply/resources_64.md).
+static const char kJitSeaSpelling[] =
+    "#define GGRS_VGPR_OPAQUE(c) asm(\"\" : \"+v\"(c))\n"
+    "#ifdef GGRS_SPEC\n"
+    "#define GGRS_SEA_MUL_HOT(x) sea_mul_p_mad3(x)                                  // three v_mad_u64_u32 (device_prelude.hpp)\n"
+    "#else\n"
+    "#define GGRS_SEA_MUL_HOT(x) ((x) * SEA_P)\n"
+    "#endif\n";
 // ---- device text of worlds that spawn on the device: no format argument, pasted as it stands ----
 static const char kJitSpMailbox[] =
     "// SPAWNS DECIDED ON THE DEVICE: the workgroups of a COOPERATIVE launch (all resident) meet through mailbox words {epoch:32 | value:32}, written and polled\n"
@@ -971,6 +982,7 @@ struct JitGen {
              "__device__ __forceinline__ void set_lanes(uint32_t& v, uint64_t lanes_, uint32_t x_) { const uint64_t lanes = uni64(lanes_); const uint32_t x = (uint32_t)__builtin_amdgcn_readfirstlane((int)x_); uint64_t sv_; asm volatile(\"s_mov_b64 %0, exec\\n\\ts_and_b64 exec, exec, %2\\n\\tv_mov_b32 %1, %3\\n\\ts_mov_b64 exec, %0\" : \"=&s\"(sv_), \"+v\"(v) : \"s\"(lanes), \"s\"(x) : \"scc\"); }\n"
              "__device__ __forceinline__ void store_lanes(GGRS_G uint32_t* p, uint32_t v, uint64_t lanes_) { const uint64_t lanes = uni64(lanes_); uint64_t sv_; asm volatile(\"s_mov_b64 %0, exec\\n\\ts_and_b64 exec, exec, %3\\n\\tglobal_store_dword %1, %2, off\\n\\ts_mov_b64 exec, %0\" : \"=&s\"(sv_) : \"v\"(p), \"v\"(v), \"s\"(lanes) : \"memory\", \"scc\"); }\n";
         s += kJitSpMailbox;
+        s += kJitSeaSpelling;
         s += "namespace ggrs {\n";
         s += kJitPrelude;
         s += "\n}\nusing namespace ggrs;\n";
@@ -1315,8 +1327,17 @@ struct JitGen {
     }
     // ---- 8. the op loop and its SaveWorld arm
     void save_arm() {
+        // The loop head is written twice.  A specialised copy (GGRS_SPEC: a.n_ops a literal) compiles the second, whose pragma carries the trip count: past some body
+        // size a bare `#pragma unroll` is silently not honoured ("loop not unrolled") and the copy falls back to a rolled walk of the op list (418 vector instructions,
+        // 46 VGPRs for the headline) -- with the count the compiler unrolls fully whatever the body weighs.  jit_specialise's own bare pragma goes in front of the
+        // FIRST head, as tests/test_generated_kernel.py pins it byte for byte; two unroll pragmas on one loop do not compile, so the counted one cannot sit there
         s += "    uint32_t si = 0, sj = 0;\n"
+             "#ifndef GGRS_SPEC\n"
              "    for (uint32_t op = 0; op < a.n_ops; ++op) {\n"
+             "#else\n"
+             "#pragma unroll a.n_ops\n"
+             "    for (uint32_t op = 0; op < a.n_ops; ++op) {\n"
+             "#endif\n"
              "        if (!((a.op_bits >> op) & 1ull)) {\n"
              "            // ---------------- SaveWorld\n"
              "            if (si < o_first) { ++si; continue; }                          // another role's snapshot\n"
@@ -1889,7 +1910,7 @@ std::string jit_specialise(const std::string& generic, const JitSig& g) {
     const std::string loop = "    for (uint32_t op = 0; op < " + lit32(g.n_ops) + "; ++op) {";
     const size_t lp = body.find(loop);
     if (lp == std::string::npos) return "";
-    body.insert(lp, "#pragma unroll\n");
+    body.insert(lp, "#pragma unroll\n");                                // (lands on the generic copy's loop head, which a specialised copy does not compile: save_arm)
     char note[360];
     snprintf(note, sizeof note, "// specialised: %u ops (bits %llx), %u Saves, rows %llx / live %llx / load %llx, masks %x / %x, nt %u, cached %x, nt loads %u, roles of %u, live block %s, value tags %u%s\n", g.n_ops,
              (unsigned long long)g.op_bits, g.n_saves, (unsigned long long)g.save_rows, (unsigned long long)g.live_rows, (unsigned long long)g.load_rows, g.save_pmask, g.live_pmask, g.nt, g.cached_saves, g.nt_loads, g.dp_s,

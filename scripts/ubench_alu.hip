@@ -24,24 +24,37 @@ __device__ __forceinline__ uint64_t mul_p_mad3(uint64_t x) {
 }
 __device__ __forceinline__ uint64_t diffuse_mad3(uint64_t x) { x = mul_p_mad3(x); const uint32_t hi = (uint32_t)(x >> 32); x ^= (uint64_t)(hi >> (hi >> 28)); x = mul_p_mad3(x); return x; }
 
-template <int CH, bool MAD3 = false>
+// ADOPTED (profiles/mad3_multiply): the same three products in plain C, as bevy_ggrs_amd/csrc/device_prelude.hpp sea_mul_p_mad3 spells them -- no instruction inside
+// an asm statement (the compiler folds constants through it and allocates the temporaries itself); the empty asm only keeps it from narrowing the cross sum,
+// of which the low half alone is used, back to v_mul_lo_u32
+__device__ __forceinline__ uint64_t mul_p_c3(uint64_t x) {
+    const uint32_t xl = (uint32_t)x, xh = (uint32_t)(x >> 32);
+    uint64_t c = (uint64_t)xh * (uint32_t)P;
+    c = (uint64_t)xl * (uint32_t)(P >> 32) + c;
+    asm("" : "+v"(c));
+    return (uint64_t)xl * (uint32_t)P + (c << 32);
+}
+__device__ __forceinline__ uint64_t diffuse_c3(uint64_t x) { x = mul_p_c3(x); const uint32_t hi = (uint32_t)(x >> 32); x ^= (uint64_t)(hi >> (hi >> 28)); x = mul_p_c3(x); return x; }
+
+// MAD3: 0 = the compiler's lowering of x *= P, 1 = three mads through inline asm, 2 = three mads in plain C
+template <int CH, int MAD3 = 0>
 __global__ __launch_bounds__(256) void k_diffuse(uint64_t* out, int iters) {
     uint64_t x[CH];
 #pragma unroll
     for (int c = 0; c < CH; ++c) x[c] = (uint64_t)(blockIdx.x * 256 + threadIdx.x) * 0x9e3779b97f4a7c15ull + c;
     for (int i = 0; i < iters; ++i) {
 #pragma unroll
-        for (int c = 0; c < CH; ++c) x[c] = MAD3 ? diffuse_mad3(x[c] ^ (uint64_t)i) : diffuse(x[c] ^ (uint64_t)i);
+        for (int c = 0; c < CH; ++c) x[c] = MAD3 == 2 ? diffuse_c3(x[c] ^ (uint64_t)i) : MAD3 == 1 ? diffuse_mad3(x[c] ^ (uint64_t)i) : diffuse(x[c] ^ (uint64_t)i);
     }
     uint64_t r = 0;
 #pragma unroll
     for (int c = 0; c < CH; ++c) r ^= x[c];
     if (r == 0x1234567) out[0] = r;          // never true: keeps the chains alive
 }
-// the two spellings agree: one diffuse of each per thread, compared on the host
-__global__ void k_diffuse_check(const uint64_t* in, uint64_t* a, uint64_t* b, int n) {
+// the three spellings agree: one diffuse of each per thread, compared on the host
+__global__ void k_diffuse_check(const uint64_t* in, uint64_t* a, uint64_t* b, uint64_t* c, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) { a[i] = diffuse(in[i]); b[i] = diffuse_mad3(in[i]); }
+    if (i < n) { a[i] = diffuse(in[i]); b[i] = diffuse_mad3(in[i]); c[i] = diffuse_c3(in[i]); }
 }
 template <int CH>
 __global__ __launch_bounds__(256) void k_mad64(uint64_t* out, int iters) {           // v_mad_u64_u32 chains: x = lo(x) * K + x
@@ -100,17 +113,17 @@ int main() {
     void* out; hipMalloc(&out, 4096);
     const int iters = 4096;
     {   // the experiment's spelling against the kernels' own, on edge values and a few thousand others
-        const int n = 4096; std::vector<uint64_t> h(n), ha(n), hb(n);
+        const int n = 4096; std::vector<uint64_t> h(n), ha(n), hb(n), hc(n);
         uint64_t z = 0x243f6a8885a308d3ull;
         for (int i = 0; i < n; ++i) { z = z * 6364136223846793005ull + 1442695040888963407ull; h[i] = z; }
-        h[0] = 0; h[1] = ~0ull; h[2] = 1ull << 31; h[3] = 1ull << 63; h[4] = 0x80000000ull; h[5] = 0xffffffffull; h[6] = 0xffffffff00000000ull;
-        uint64_t *di, *da, *db; hipMalloc(&di, n * 8); hipMalloc(&da, n * 8); hipMalloc(&db, n * 8);
+        h[0] = 0; h[1] = ~0ull; h[2] = 1ull << 31; h[3] = 1ull << 63; h[4] = 0x80000000ull; h[5] = 0xffffffffull; h[6] = 0xffffffff00000000ull; h[7] = 1ull; h[8] = 1ull << 32;
+        uint64_t *di, *da, *db, *dc; hipMalloc(&di, n * 8); hipMalloc(&da, n * 8); hipMalloc(&db, n * 8); hipMalloc(&dc, n * 8);
         hipMemcpy(di, h.data(), n * 8, hipMemcpyHostToDevice);
-        hipLaunchKernelGGL(k_diffuse_check, dim3(n / 256), dim3(256), 0, 0, di, da, db, n);
-        hipMemcpy(ha.data(), da, n * 8, hipMemcpyDeviceToHost); hipMemcpy(hb.data(), db, n * 8, hipMemcpyDeviceToHost);
-        int bad = 0; for (int i = 0; i < n; ++i) bad += ha[i] != hb[i];
-        printf("mad3 spelling == own spelling on %d inputs: %s\n", n, bad ? "NO" : "yes");
-        hipFree(di); hipFree(da); hipFree(db);
+        hipLaunchKernelGGL(k_diffuse_check, dim3(n / 256), dim3(256), 0, 0, di, da, db, dc, n);
+        hipMemcpy(ha.data(), da, n * 8, hipMemcpyDeviceToHost); hipMemcpy(hb.data(), db, n * 8, hipMemcpyDeviceToHost); hipMemcpy(hc.data(), dc, n * 8, hipMemcpyDeviceToHost);
+        int bad = 0; for (int i = 0; i < n; ++i) bad += ha[i] != hb[i] || ha[i] != hc[i];
+        printf("mad3 spellings (asm, C) == own spelling on %d inputs: %s\n", n, bad ? "NO" : "yes");
+        hipFree(di); hipFree(da); hipFree(db); hipFree(dc);
         if (bad) return 1;
     }
     printf("CUs %d, clock attr %d kHz\n", n_cu, clk);
@@ -129,10 +142,12 @@ int main() {
         report("v_mad_u64_u32 x8 chains", time_ms([&] { hipLaunchKernelGGL(k_mad64<8>, dim3(blocks), dim3(256), 0, 0, (uint64_t*)out, iters); }), iters * 8.0);
         // the experiment, in the same process: the own spelling three more times (its spread is the bar), the mad3 spelling three times, interleaved
         for (int rep = 0; rep < 3; ++rep) {
-            report("diffuse x8 chains (rep)", time_ms([&] { hipLaunchKernelGGL((k_diffuse<8, false>), dim3(blocks), dim3(256), 0, 0, (uint64_t*)out, iters); }), iters * 8.0);
-            report("mad3 diffuse x8 chains", time_ms([&] { hipLaunchKernelGGL((k_diffuse<8, true>), dim3(blocks), dim3(256), 0, 0, (uint64_t*)out, iters); }), iters * 8.0);
+            report("diffuse x8 chains (rep)", time_ms([&] { hipLaunchKernelGGL((k_diffuse<8, 0>), dim3(blocks), dim3(256), 0, 0, (uint64_t*)out, iters); }), iters * 8.0);
+            report("mad3 diffuse x8 chains", time_ms([&] { hipLaunchKernelGGL((k_diffuse<8, 1>), dim3(blocks), dim3(256), 0, 0, (uint64_t*)out, iters); }), iters * 8.0);
+            report("mad3-C diffuse x8 chains", time_ms([&] { hipLaunchKernelGGL((k_diffuse<8, 2>), dim3(blocks), dim3(256), 0, 0, (uint64_t*)out, iters); }), iters * 8.0);
         }
-        report("mad3 diffuse x4 chains", time_ms([&] { hipLaunchKernelGGL((k_diffuse<4, true>), dim3(blocks), dim3(256), 0, 0, (uint64_t*)out, iters); }), iters * 4.0);
+        report("mad3 diffuse x4 chains", time_ms([&] { hipLaunchKernelGGL((k_diffuse<4, 1>), dim3(blocks), dim3(256), 0, 0, (uint64_t*)out, iters); }), iters * 4.0);
+        report("mad3-C diffuse x4 chains", time_ms([&] { hipLaunchKernelGGL((k_diffuse<4, 2>), dim3(blocks), dim3(256), 0, 0, (uint64_t*)out, iters); }), iters * 4.0);
         report("v_fma_f32 x8 chains", time_ms([&] { hipLaunchKernelGGL(k_fma32<8>, dim3(blocks), dim3(256), 0, 0, (float*)out, iters); }), iters * 8.0);
     }
     return 0;
