@@ -83,6 +83,15 @@ class EffectBinding(C.Structure):
     _fields_ = [("comp", C.c_uint32), ("word", C.c_uint32), ("op", C.c_uint32)]
 
 
+CMD_INSERT, CMD_REMOVE = 1, 2
+COMMAND_MAX_BINDINGS = 4
+COMMAND_MAX_WORDS = 8
+
+
+class CommandBinding(C.Structure):
+    _fields_ = [("comp", C.c_uint32), ("flags", C.c_uint32)]
+
+
 class SpawnSystemDesc(C.Structure):
     _fields_ = [("name", C.c_char_p), ("source", C.c_char_p), ("bundle_mask", C.c_uint64), ("payload_stride", C.c_uint32), ("n_bindings", C.c_uint32),
                 ("comp", C.c_uint32 * CUSTOM_MAX_BINDINGS), ("word", C.c_uint32 * CUSTOM_MAX_BINDINGS),
@@ -130,6 +139,8 @@ SIGNATURES = {
     "ggrs_hip_add_custom_system": (C.c_int, [_P, C.POINTER(CustomSystemDesc)]),
     "ggrs_hip_add_custom_system_peers": (C.c_int, [_P, C.POINTER(CustomSystemDesc), C.POINTER(PeerBinding), C.c_uint32]),
     "ggrs_hip_add_custom_system_effects": (C.c_int, [_P, C.POINTER(CustomSystemDesc), C.POINTER(PeerBinding), C.c_uint32, C.POINTER(EffectBinding), C.c_uint32]),
+    "ggrs_hip_add_custom_system_commands": (C.c_int, [_P, C.POINTER(CustomSystemDesc), C.POINTER(PeerBinding), C.c_uint32, C.POINTER(EffectBinding), C.c_uint32,
+                                                      C.POINTER(CommandBinding), C.c_uint32]),
     "ggrs_hip_register_component_strategy": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p]),
     "ggrs_hip_set_input_layout": (C.c_int, [_P, C.c_uint32, C.c_uint32]),
     "ggrs_hip_add_spawn_system": (C.c_int, [_P, C.POINTER(SpawnSystemDesc)]),

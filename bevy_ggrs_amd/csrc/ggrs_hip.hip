@@ -223,7 +223,14 @@ int ggrs_hip_add_custom_system(ggrs_world* w, const ggrs_custom_system_desc* d) 
 int ggrs_hip_add_custom_system_peers(ggrs_world* w, const ggrs_custom_system_desc* d, const ggrs_peer_binding* peers, uint32_t n_peers) { return ggrs_hip_add_custom_system_effects(w, d, peers, n_peers, nullptr, 0); }
 // ... and with effect bindings: words of OTHER entities the system combines a value into through e.send_*(slot, j, v), landing at the end of the frame (include/ggrs_hip.h)
 int ggrs_hip_add_custom_system_effects(ggrs_world* w, const ggrs_custom_system_desc* d, const ggrs_peer_binding* peers, uint32_t n_peers, const ggrs_effect_binding* effects, uint32_t n_effects) {
+    return ggrs_hip_add_custom_system_commands(w, d, peers, n_peers, effects, n_effects, nullptr, 0);
+}
+// ... and with command bindings: whole components of its OWN entity the system sees as Option<&mut C> (e.has, e.opt_*) and may insert or remove (include/ggrs_hip.h)
+int ggrs_hip_add_custom_system_commands(ggrs_world* w, const ggrs_custom_system_desc* d, const ggrs_peer_binding* peers, uint32_t n_peers, const ggrs_effect_binding* effects, uint32_t n_effects,
+                                        const ggrs_command_binding* cmds, uint32_t n_cmds) {
     if (!w || !d || !d->source) return GGRS_E_INVALID;
+    if (n_cmds > GGRS_COMMAND_MAX_BINDINGS) return w->fail(GGRS_E_INVALID, "custom system '%s': at most %d command bindings (GGRS_COMMAND_MAX_BINDINGS), not %u", d->name ? d->name : "custom", GGRS_COMMAND_MAX_BINDINGS, n_cmds);
+    if (n_cmds && !cmds) return w->fail(GGRS_E_INVALID, "custom system: n_cmds = %u but cmds is NULL", n_cmds);
     if (w->sealed) return w->fail(GGRS_E_INVALID, "add_custom_system after the world was sealed");
     if (n_peers > GGRS_PEER_MAX_BINDINGS) return w->fail(GGRS_E_INVALID, "custom system: at most %d peer bindings, not %u", GGRS_PEER_MAX_BINDINGS, n_peers);
     if (n_peers && !peers) return w->fail(GGRS_E_INVALID, "custom system: n_peers = %u but peers is NULL", n_peers);
@@ -255,6 +262,16 @@ int ggrs_hip_add_custom_system_effects(ggrs_world* w, const ggrs_custom_system_d
         c.fcomp[j] = effects[j].comp; c.fword[j] = effects[j].word; c.fop[j] = effects[j].op;
     }
     c.n_fx = n_effects;
+    uint32_t cmd_words = 0;
+    for (uint32_t j = 0; j < n_cmds; ++j) {
+        if (cmds[j].comp >= w->comps.size()) return w->fail(GGRS_E_INVALID, "custom system '%s': command binding %u names component %u, which is not registered", c.name.c_str(), j, cmds[j].comp);
+        if (cmds[j].flags & ~(GGRS_CMD_INSERT | GGRS_CMD_REMOVE)) return w->fail(GGRS_E_INVALID, "custom system '%s': command binding %u has flags %x, which are none of GGRS_CMD_*", c.name.c_str(), j, cmds[j].flags);
+        c.ccomp[j] = cmds[j].comp; c.cflags[j] = cmds[j].flags;
+        cmd_words += w->comps[cmds[j].comp].n_words;
+    }
+    if (cmd_words > GGRS_COMMAND_MAX_WORDS)
+        return w->fail(GGRS_E_INVALID, "custom system '%s': its command-bound components have %u words together, at most %d (GGRS_COMMAND_MAX_WORDS)", c.name.c_str(), cmd_words, GGRS_COMMAND_MAX_WORDS);
+    c.n_cmd = n_cmds;
     DeviceGuard dg(w);
     c.source = d->source;
     c.may_defer = source_has_token(c.source, "despawn_rollback") || source_has_token(c.source, "kill");
@@ -329,7 +346,7 @@ int ggrs_hip_generated_kernel_source(ggrs_world* w, uint32_t form, char* buf, ui
     if (!w || (form != GGRS_KERNEL_FORM_TILES && form != GGRS_KERNEL_FORM_STEADY)) return GGRS_E_INVALID;
     if (!w->sealed) {
         if (!w->layout_only) { DeviceGuard dg(w); const int rc = seal(w); if (rc) return rc; }
-        else { build_layout(w); const int prc = peers_validate(w); if (prc) return prc; const int frc = effects_validate(w); if (frc) return frc; }   // host arithmetic only: offsets of every mask and column; the peer- and effect-binding rules
+        else { build_layout(w); const int prc = peers_validate(w); if (prc) return prc; const int frc = effects_validate(w); if (frc) return frc; const int crc = commands_validate(w); if (crc) return crc; }   // host arithmetic only: offsets of every mask and column; the peer-, effect- and command-binding rules
     }
     std::string src;
     if (!jit_source(w, src)) return w->fail(GGRS_E_INVALID, "the kernel generator does not cover this world (a system writes a live-only component, or more than %u four-byte units / %u words per entity)", JIT_MAX_UNITS, JIT_MAX_COLS);
@@ -840,6 +857,8 @@ int ggrs_hip_world_kernel_info(ggrs_world* w, char* buf, uint64_t cap, uint64_t*
         add("group_caps", std::to_string(w->cap_saves) + " saves / " + std::to_string(w->cap_steps) + " steps");
         if (w->has_peers) add("peer_view", std::to_string(w->peer_view.n_cols) + " linear columns + visibility words, published from the group's source block ahead of every request group that holds an AdvanceWorld (" +
                                            std::to_string(w->peer_view.publishes) + " publishes so far)");
+        if (w->has_commands) add("command_bindings", std::to_string(__builtin_popcountll(w->cmd_mut_comps)) + " components a system may insert or remove: their presence bits are registers of the generated kernel, "
+                                                     "their mask words are rebuilt per Save, and every AdvanceWorld gives their masks and columns fresh row versions");
         if (w->has_effects) add("effect_inbox", std::to_string(w->fx_inbox.n_cols) + " linear columns holding the ops' identities, applied to the live block right behind every request group that holds an AdvanceWorld (" +
                                                std::to_string(w->fx_inbox.applies) + " applies so far)");
         add("branch_marker_record_bytes", std::to_string(w->jit_marks ? jit_marks_rec_bytes(w) : 0));      // per retained branch of ggrs_hip_fanout_step_branches (0: the kernel keeps no markers)

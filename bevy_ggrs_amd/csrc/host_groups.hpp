@@ -652,6 +652,7 @@ int group_take(ggrs_world* w, const ggrs_request& r, GgrsJitArgs& j, GroupState&
     ver_step(w);                                                        // every system may have written its write set
     const uint32_t dtb = r.dt_bits ? r.dt_bits : dt_bits_for_frame(w->fps, w->frame);
     if (w->dev_spawn) touch_bundle(w->spawn_customs[w->systems[w->jit_spawn_sys].comp[0]]);   // any frame may append rows of the bundle: its columns and presence masks are new after every step
+    for (uint32_t c = 0; w->cmd_mut_comps >> c; ++c) if ((w->cmd_mut_comps >> c) & 1ull) ver_touch_comp(w, c);   // command bindings: any frame may insert or remove the component -- its mask (and its columns) are new after every step
     j.dt_bits[step] = dtb; j.step_frame[step] = w->frame; j.step_confirmed[step] = w->confirmed;
     if (w->jit_box_sys >= 0) j.aux_bits[step] = box_aux_bits(w, dtb);
     j.n_inputs[step] = (uint8_t)std::min<uint32_t>(r.n_inputs, w->max_players);
@@ -949,6 +950,9 @@ int validate_branch_step(ggrs_world* w, const ggrs_branch_step& st) {
     if (!w->gen_ok) return w->fail(GGRS_E_INVALID, "branch steps need the generated request-group kernel, which this world does not have: %s", w->jit_status.c_str());
     if (w->has_peers) return w->fail(GGRS_E_INVALID, "branch steps are not available for worlds with peer bindings (a member runs several frames per launch, a peer read sees the start of ONE frame): use ggrs_hip_fanout_step");
     if (w->has_effects) return w->fail(GGRS_E_INVALID, "branch steps are not available for worlds with effect bindings (a member runs several frames per launch, the sends of ONE frame are applied behind a launch): use ggrs_hip_fanout_step");
+    // a retained block's presence masks are decided by the branch's own versions, which say nothing of what the systems inserted or removed: not offered in this version
+    if (w->has_commands && (st.flags & (GGRS_BRANCH_RETAIN_NEWEST | GGRS_BRANCH_RETAIN_ALL)))
+        return w->fail(GGRS_E_INVALID, "GGRS_BRANCH_RETAIN_* is not available for worlds with command bindings (ggrs_hip_add_custom_system_commands): run the branch step without retention, or use ggrs_hip_fanout_step");
     if (w->dev_spawn) return w->fail(GGRS_E_INVALID, "branch steps are not available for worlds whose systems spawn on the device (every launch is one cooperative grid): use ggrs_hip_fanout_step");
     if (st.n_branches == 0 || st.n_branches > BRANCH_MAX) return w->fail(GGRS_E_INVALID, "a branch step holds 1..%u branches, not %u", BRANCH_MAX, st.n_branches);
     const uint32_t S = (st.flags & GGRS_BRANCH_SAVE_LAST) ? st.n_frames : st.n_frames - 1;

@@ -329,7 +329,8 @@ std::string custom_source(const ggrs_world* w, const ggrs_world::Custom& c, cons
     snprintf(buf, sizeof buf, "static_assert(sizeof(GgrsCustomArgs) == %zu, \"host/device argument block mismatch\");\n", sizeof(GgrsCustomArgs));
     s += buf;
     s += GGRS_FRAME_TEXT;
-    s += c.n_fx ? GGRS_ENTITY_EFFECTS_TEXT : (c.n_peer ? GGRS_ENTITY_PEERS_TEXT : GGRS_ENTITY_TEXT);   // (a system with peer or effect bindings only ever RUNS inside the generated kernel: here its text is compiled against an empty view and an empty inbox)
+    s += entity_text(c.n_fx != 0, c.n_peer != 0, c.n_cmd != 0, false);   // (a system with peer, effect or command bindings only ever RUNS inside the generated kernel: here its text is compiled against an empty view, an empty inbox and unset opt words)
+    if (c.n_cmd) s += cmd_entity_typedef(w, c);
     s += "#line 1 \"ggrs_system\"\n";
     s += user;
     snprintf(buf, sizeof buf, "\n#line 1 \"ggrs_custom_kernel\"\n#define GGRS_N_BIND %u\n#define GGRS_N_PRES %u\n", c.n_bind, c.n_pres);

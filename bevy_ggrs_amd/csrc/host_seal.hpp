@@ -97,6 +97,7 @@ int effects_validate(ggrs_world* w) {
             const ggrs_world::Custom& c = w->customs[d.comp[0]];
             for (uint32_t b = 0; b < c.n_bind; ++b) if (colof(c.comp[b], c.word[b]) == cl) return true;
             for (uint32_t j = 0; j < c.n_peer; ++j) if (colof(c.pcomp[j], c.pword[j]) == cl) return true;
+            for (uint32_t j = 0; j < c.n_cmd; ++j) if (span(c.ccomp[j], 0, w->comps[c.ccomp[j]].n_words)) return true;      // a command-bound component: every column
             return false;
         }
         default: return false;       // a spawn system appends rows: entities spawned in this frame cannot be hit
@@ -134,6 +135,32 @@ int effects_validate(ggrs_world* w) {
     if (need.devspawn) return w->fail(GGRS_E_INVALID, "effect bindings are not available in a world that spawns on the device with e.spawn(n) (GGRS_SPAWN_PAYLOAD_PARENT)");
     if (w->flags & (GGRS_WORLD_NO_GROUPS | GGRS_WORLD_UNFUSED)) return w->fail(GGRS_E_INVALID, "effect bindings need the generated request-group kernel, which a GGRS_WORLD_NO_GROUPS / GGRS_WORLD_UNFUSED world does not have");
     if (!w->knobs.tick_jit) return w->fail(GGRS_E_INVALID, "effect bindings need the generated request-group kernel, which this world does not have: disabled (GGRS_TICK_JIT=0)");
+    return GGRS_OK;
+}
+// Command bindings (ggrs_hip_add_custom_system_commands): what the first version refuses.  The registration-order rules of peers and effects need nothing here: a
+// command-bound component is in the system's write set, every column of it (build_layout), and binds() above counts it.  After build_layout; no device needed -- a
+// GGRS_WORLD_LAYOUT_ONLY world is checked by ggrs_hip_generated_kernel_source.
+int commands_validate(ggrs_world* w) {
+    if (!world_has_commands(w)) return GGRS_OK;
+    for (size_t i = 0; i < w->systems.size(); ++i) {
+        if (w->systems[i].kind != GGRS_SYS_CUSTOM) continue;
+        const ggrs_world::Custom& c = w->customs[w->systems[i].comp[0]];
+        const char* nm = c.name.c_str();
+        for (uint32_t j = 0; j < c.n_cmd; ++j) {
+            const Comp& cc = w->comps[c.ccomp[j]];
+            if (cc.s_n_words) return w->fail(GGRS_E_INVALID, "custom system '%s': command binding %u names component %u ('%s'), which has a Strategy: commands on such a component are not supported", nm, j, c.ccomp[j], cc.name.c_str());
+            if (cc.no_rollback) return w->fail(GGRS_E_INVALID, "custom system '%s': command binding %u names component %u ('%s'), which is not registered for rollback (GGRS_COMP_NO_ROLLBACK): commands on such a component are not supported", nm, j, c.ccomp[j], cc.name.c_str());
+            for (uint32_t b = 0; b < c.n_bind; ++b) if (c.comp[b] == c.ccomp[j])
+                return w->fail(GGRS_E_INVALID, "custom system '%s': component %u ('%s') is both its own binding %u and its command binding %u: a system's own bindings and its command bindings share no component", nm, c.ccomp[j], cc.name.c_str(), b, j);
+            for (uint32_t q = 0; q < j; ++q) if (c.ccomp[q] == c.ccomp[j])
+                return w->fail(GGRS_E_INVALID, "custom system '%s': component %u ('%s') is its command binding %u and %u: a component has one command binding per system", nm, c.ccomp[j], cc.name.c_str(), q, j);
+        }
+    }
+    const JitNeeds need = jit_needs(w);
+    if (need.marks) return w->fail(GGRS_E_INVALID, "command bindings are not available in a world that keeps RollbackDespawned markers (a system that can call despawn_rollback(), or names the `kill` field)");
+    if (need.devspawn) return w->fail(GGRS_E_INVALID, "command bindings are not available in a world that spawns on the device with e.spawn(n) (GGRS_SPAWN_PAYLOAD_PARENT)");
+    if (w->flags & (GGRS_WORLD_NO_GROUPS | GGRS_WORLD_UNFUSED)) return w->fail(GGRS_E_INVALID, "command bindings need the generated request-group kernel, which a GGRS_WORLD_NO_GROUPS / GGRS_WORLD_UNFUSED world does not have");
+    if (!w->knobs.tick_jit) return w->fail(GGRS_E_INVALID, "command bindings need the generated request-group kernel, which this world does not have: disabled (GGRS_TICK_JIT=0)");
     return GGRS_OK;
 }
 int seal(ggrs_world* w) {
@@ -213,8 +240,11 @@ int seal_impl(ggrs_world* w) {
     build_layout(w);
     { const int prc = peers_validate(w); if (prc) return prc; }
     { const int frc = effects_validate(w); if (frc) return frc; }
+    { const int crc = commands_validate(w); if (crc) return crc; }
     w->has_peers = world_has_peers(w);
     w->has_effects = world_has_effects(w);
+    w->has_commands = world_has_commands(w);
+    w->cmd_mut_comps = world_cmd_mut_comps(w);
 
     // ---- checksum specs (the per-request k_checksum's view: one UnitDesc per hashed word)
     w->cks_comp.clear(); w->custom_hashers = false;
@@ -276,6 +306,8 @@ int seal_impl(ggrs_world* w) {
         return w->fail(GGRS_E_INVALID, "peer bindings (ggrs_hip_add_custom_system_peers) need the generated request-group kernel, which this world does not have: %s", w->jit_status.c_str());
     if (w->has_effects && !w->gen_ok)
         return w->fail(GGRS_E_INVALID, "effect bindings (ggrs_hip_add_custom_system_effects) need the generated request-group kernel, which this world does not have: %s", w->jit_status.c_str());
+    if (w->has_commands && !w->gen_ok)
+        return w->fail(GGRS_E_INVALID, "command bindings (ggrs_hip_add_custom_system_commands) need the generated request-group kernel, which this world does not have: %s", w->jit_status.c_str());
     for (auto& sd : w->systems) if (sd.kind == GGRS_SYS_SPAWN_CUSTOM && !(w->gen_ok && w->jit_spawn_sys >= 0))
         return w->fail(GGRS_E_INVALID, "a user-written spawn system (ggrs_hip_add_spawn_system) runs inside the generated request-group kernel, which this world does not have "
                                        "(or the schedule holds a second spawn system): %s", w->jit_status.c_str());

@@ -165,6 +165,9 @@ struct ggrs_world {
         uint32_t n_peer = 0, pcomp[GGRS_PEER_MAX_BINDINGS] = {}, pword[GGRS_PEER_MAX_BINDINGS] = {};
         // effect bindings (ggrs_hip_add_custom_system_effects): words of OTHER entities the system combines a value into through e.send_*(slot, j, v)
         uint32_t n_fx = 0, fcomp[GGRS_EFFECT_MAX_BINDINGS] = {}, fword[GGRS_EFFECT_MAX_BINDINGS] = {}, fop[GGRS_EFFECT_MAX_BINDINGS] = {};
+        // command bindings (ggrs_hip_add_custom_system_commands): whole components of its OWN entity the system sees as Option<&mut C> (e.has / e.opt_*) and,
+        // with GGRS_CMD_INSERT / GGRS_CMD_REMOVE in the flags, may insert or remove
+        uint32_t n_cmd = 0, ccomp[GGRS_COMMAND_MAX_BINDINGS] = {}, cflags[GGRS_COMMAND_MAX_BINDINGS] = {};
     };
     std::vector<Custom> customs;
     // THE PEER VIEW of a world with peer bindings (allocated at seal, filled by k_publish_peers ahead of every request group that holds an AdvanceWorld): one LINEAR
@@ -186,6 +189,8 @@ struct ggrs_world {
         uint64_t applies = 0;
     } fx_inbox;
     bool has_effects = false;            // some system has effect bindings (set at seal: effect_cols)
+    bool has_commands = false;           // some system has command bindings (set at seal)
+    uint64_t cmd_mut_comps = 0;          // bit c = some system may insert or remove component c: its mask and columns get fresh versions with every AdvanceWorld (set at seal)
     struct SpawnSys {                    // GGRS_SYS_SPAWN_CUSTOM: a user-written spawner (ggrs_hip_add_spawn_system; systems[i].comp[0] indexes this)
         std::string name, source;
         uint32_t n_bind = 0, comp[GGRS_CUSTOM_MAX_BINDINGS] = {}, word[GGRS_CUSTOM_MAX_BINDINGS] = {};
@@ -482,6 +487,7 @@ void build_layout(ggrs_world* w) {
             const ggrs_world::Custom& c = w->customs[sd.comp[0]];
             for (uint32_t b = 0; b < c.n_bind; ++b) mark(c.comp[b], c.word[b], 1, true);      // a bound word may be written
             for (uint32_t j = 0; j < c.n_fx; ++j) mark(c.fcomp[j], c.fword[j], 1, true);     // an effect column: written (in OTHER entities) by the frame's sends -- every Save stores it, a sender counts as its writer
+            for (uint32_t j = 0; j < c.n_cmd; ++j) if (c.ccomp[j] < w->comps.size()) mark(c.ccomp[j], 0, w->comps[c.ccomp[j]].n_words, true);   // a command-bound component: every word may be written (Option<&mut C>, insert)
         } break;
         default: break;     // spawn systems append rows: whoever runs them versions the bundle (run_spawn_systems / the fused path in host_groups.hpp)
         }
@@ -572,6 +578,13 @@ inline uint64_t rows_bytes_hot(const ggrs_world* w) {
     return b;
 }
 inline bool world_has_effects(const ggrs_world* w) { for (auto& c : w->customs) if (c.n_fx) return true; return false; }
+inline bool world_has_commands(const ggrs_world* w) { for (auto& c : w->customs) if (c.n_cmd) return true; return false; }
+// the components some system may insert or remove (a declared GGRS_CMD_INSERT / GGRS_CMD_REMOVE), one bit each: their presence bits change inside the generated kernel
+inline uint64_t world_cmd_mut_comps(const ggrs_world* w) {
+    uint64_t m = 0;
+    for (auto& c : w->customs) for (uint32_t j = 0; j < c.n_cmd; ++j) if ((c.cflags[j] & (GGRS_CMD_INSERT | GGRS_CMD_REMOVE)) && c.ccomp[j] < 64) m |= 1ull << c.ccomp[j];
+    return m;
+}
 // does this world's kernel keep value tags?  (what a layout-only world -- `make aot` -- can tell as well)
 inline bool vtags_policy(const ggrs_world* w) {
     if (world_has_effects(w)) return false;     // effect bindings: k_apply_effects rewrites live columns behind the group's launch, which a tag written by that launch would not know

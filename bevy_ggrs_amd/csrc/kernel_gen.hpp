@@ -191,6 +191,51 @@ Hiprtc& hiprtc_for(const ggrs_world* w) {
     GGRS_FX_SEND_TEXT("send_u64", "ggrs_u64", "long long", "8", "3")
 #define GGRS_ENTITY_EFFECTS_TEXT GGRS_PEER_TYPES_TEXT GGRS_FX_TYPES_TEXT GGRS_ENTITY_PEERS_BODY_TEXT GGRS_FX_MEMBERS_TEXT "};\n"
 
+// ... in a world with command bindings (ggrs_hip_add_custom_system_commands): the entity is a TEMPLATE over what one system declared -- GGRS_IM / GGRS_RM: bit j =
+// command binding j may be inserted / removed; GGRS_CB: nibble j = the first of binding j's words in opt[] -- and every system's source is compiled against its own
+// instance (a `typedef ... GgrsEntity;` in front of it).  e.insert(j) / e.remove(j) exist only where the flag was declared and j is a constant (enable_if: a call to
+// anything else finds no member and does not compile).  has_ carries the presence bits in and the commands' outcome out: the last call wins.  With literal j and k every
+// opt word is a register once ggrs_system is inlined.  The base is the text of the world's entity (plain, peers or effects); worlds without command bindings keep it as it is.
+#define GGRS_CMD_MEMBERS_TEXT \
+    "    ggrs_u64 opt[8]; ggrs_u32 has_;                       /* the words of the command-bound components; bit j = the entity has command binding j */\n" \
+    "    __device__ static constexpr int oi_(int j, int k) { return (int)((GGRS_CB >> (4 * j)) & 15u) + k; }\n" \
+    "    __device__ bool has(int j) const { return (has_ >> j) & 1u; }\n" \
+    "    __device__ float& opt_f32(int j, int k) { return *reinterpret_cast<float*>(&opt[oi_(j, k)]); }\n" \
+    "    __device__ ggrs_u32& opt_u32(int j, int k) { return *reinterpret_cast<ggrs_u32*>(&opt[oi_(j, k)]); }\n" \
+    "    __device__ int& opt_i32(int j, int k) { return *reinterpret_cast<int*>(&opt[oi_(j, k)]); }\n" \
+    "    __device__ ggrs_u64& opt_u64(int j, int k) { return opt[oi_(j, k)]; }\n" \
+    "    __device__ unsigned short& opt_u16(int j, int k) { return *reinterpret_cast<unsigned short*>(&opt[oi_(j, k)]); }\n" \
+    "    __device__ unsigned char& opt_u8(int j, int k) { return *reinterpret_cast<unsigned char*>(&opt[oi_(j, k)]); }\n" \
+    "    __device__ void insert(int j) __attribute__((enable_if(j >= 0 && j < 4 && ((GGRS_IM >> j) & 1u), \"e.insert(j): command binding j (a constant) must be declared with GGRS_CMD_INSERT\"))) { has_ |= 1u << j; }\n" \
+    "    __device__ void remove(int j) __attribute__((enable_if(j >= 0 && j < 4 && ((GGRS_RM >> j) & 1u), \"e.remove(j): command binding j (a constant) must be declared with GGRS_CMD_REMOVE\"))) { has_ &= ~(1u << j); }\n"
+inline std::string entity_text(bool effects, bool peers, bool commands, bool default_typedef = true) {
+    std::string t = effects ? GGRS_ENTITY_EFFECTS_TEXT : (peers ? GGRS_ENTITY_PEERS_TEXT : GGRS_ENTITY_TEXT);
+    if (!commands) return t;
+    const std::string head = "struct GgrsEntity {\n";
+    const size_t at = t.find(head), end = t.rfind("};\n");
+    t.insert(end, GGRS_CMD_MEMBERS_TEXT);
+    t.replace(at, head.size(), "template <unsigned GGRS_IM, unsigned GGRS_RM, unsigned GGRS_CB> struct GgrsEntityC {\n");
+    if (!default_typedef) return t;
+    return t + "typedef GgrsEntityC<0u, 0u, 0u> GgrsEntity;              // what a system without command bindings, and the spawner, see\n";
+}
+// the first of command binding j's words in GgrsEntity::opt (the words of the bindings before it)
+inline uint32_t cmd_word_base(const ggrs_world* w, const ggrs_world::Custom& c, uint32_t j) {
+    uint32_t b = 0;
+    for (uint32_t q = 0; q < j && q < c.n_cmd; ++q) if (c.ccomp[q] < w->comps.size()) b += w->comps[c.ccomp[q]].n_words;
+    return b;
+}
+// the entity type of ONE system of a world with command bindings, as the line that goes in front of its source
+inline std::string cmd_entity_typedef(const ggrs_world* w, const ggrs_world::Custom& c) {
+    uint32_t im = 0, rm = 0, cb = 0;
+    for (uint32_t j = 0; j < c.n_cmd; ++j) {
+        if (c.cflags[j] & GGRS_CMD_INSERT) im |= 1u << j;
+        if (c.cflags[j] & GGRS_CMD_REMOVE) rm |= 1u << j;
+        cb |= (cmd_word_base(w, c, j) & 15u) << (4 * j);
+    }
+    char b[160]; snprintf(b, sizeof b, "typedef ::GgrsEntityC<0x%xu, 0x%xu, 0x%xu> GgrsEntity;\n", im, rm, cb);
+    return b;
+}
+
 // hiprtc: source -> code object -> module + kernel handle.  A compile error fails with the compiler log in w->err.
 // one compile at a time in this process: a world being sealed on the caller's thread and a specialised kernel being built on a worker
 // never run the compiler concurrently
@@ -560,7 +605,7 @@ struct JitLayout {
     struct Member { uint32_t bytes = 0, save_dst = 0, save_rows = 0, save_len = 0, spawn_payload = 0, spawn_first = 0, live = 0, live_rows = 0, marks_dst = 0, save_pmask = 0, live_pmask = 0,
                     spawn_count = 0, n_inputs = 0, inputs = 0, save_tagok = 0, live_tagok = 0; } m;
 };
-struct JitNeeds { bool spawn, inputs, marks, box, vtags, devspawn, devstream, nr, peers, effects; };
+struct JitNeeds { bool spawn, inputs, marks, box, vtags, devspawn, devstream, nr, peers, effects, commands; };
 // the distinct peer-bound columns of the world in order of first use (systems in registration order, peer bindings in order) and the components they belong to;
 // returns how many there are (more than GGRS_PEER_MAX_COLUMNS: only the first ones are written -- peers_validate refuses such a world)
 inline uint32_t peer_cols(const ggrs_world* w, uint32_t* cols, uint32_t* n_pres = nullptr, uint32_t* pres = nullptr) {
@@ -774,7 +819,11 @@ uint64_t jit_static_reads(const ggrs_world* w) {
         case GGRS_SYS_PARTICLES_UPDATE: add(d.comp[0], d.word[0], 3); add(d.comp[1], d.word[1], 3); break;
         case GGRS_SYS_TTL_DESPAWN: case GGRS_SYS_ADD_U32: case GGRS_SYS_SAT_SUB_DESPAWN: add(d.comp[0], d.word[0], 1); break;
         case GGRS_SYS_BOX_MOVE: add(d.comp[0], d.word[0], 3); add(d.comp[1], d.word[1], 3); if (!w->comps[d.comp[2]].no_rollback) add(d.comp[2], d.word[2], 1); break;
-        case GGRS_SYS_CUSTOM: { const ggrs_world::Custom& c = w->customs[d.comp[0]]; for (uint32_t b = 0; b < c.n_bind; ++b) add(c.comp[b], c.word[b], 1); } break;
+        case GGRS_SYS_CUSTOM: {
+            const ggrs_world::Custom& c = w->customs[d.comp[0]];
+            for (uint32_t b = 0; b < c.n_bind; ++b) add(c.comp[b], c.word[b], 1);
+            for (uint32_t j = 0; j < c.n_cmd; ++j) if (c.ccomp[j] < w->comps.size()) add(c.ccomp[j], 0, w->comps[c.ccomp[j]].n_words);    // e.opt_*: every word of a command-bound component
+        } break;
         default: break;
     }
     for (auto& c : w->comps) if (c.checksummed && !c.no_rollback) {
@@ -835,7 +884,8 @@ inline uint64_t jit_marks_rec_frames_off(const ggrs_world* w) { return align_up(
 inline uint64_t jit_marks_rec_bytes(const ggrs_world* w) { return jit_marks_rec_frames_off(w) + align_up(w->cap_pad * 4, ALIGN); }
 // which optional parts of the argument block this world's kernel reads
 JitNeeds jit_needs(const ggrs_world* w) {
-    JitNeeds n{false, false, false, false, false, false, false, false, false, false};
+    JitNeeds n{false, false, false, false, false, false, false, false, false, false, false};
+    n.commands = world_has_commands(w);
     n.peers = world_has_peers(w);
     n.effects = world_has_effects(w);
     n.vtags = vtags_policy(w);
@@ -872,6 +922,7 @@ bool jit_covers(const ggrs_world* w) {
         case GGRS_SYS_CUSTOM: {
             const ggrs_world::Custom& c = w->customs[d.comp[0]];
             for (uint32_t i = 0; i < c.n_bind; ++i) if (!rb(c.comp[i])) return false;      // may WRITE a live-only word: not replayable
+            for (uint32_t j = 0; j < c.n_cmd; ++j) if (!rb(c.ccomp[j]) || w->comps[c.ccomp[j]].s_n_words) return false;      // (commands_validate refuses such a world with a message)
             // every peer binding finds its column in the world's peer view
             for (uint32_t j = 0; j < c.n_peer; ++j) if (std::find(pv_cols, pv_cols + n_pv, w->comps[c.pcomp[j]].col_base + c.pword[j]) == pv_cols + n_pv) return false;
             // ... every effect binding its column in the world's inbox
@@ -897,6 +948,7 @@ struct JitGen {
     const ggrs_world* const w; std::string& s;                       // the world, the text
     const uint32_t nc;
     const int spawn_sys;                                             // jit_fused_spawn_system: the spawn system that runs inside the kernel, or -1
+    const uint64_t cmd_mut;                                          // world_cmd_mut_comps: components some system may insert or remove
     // need.devspawn: spawns decided on the device (GGRS_SPAWN_PAYLOAD_PARENT): len lives on the device, the launch is cooperative
     // need.devstream: ... or, in the streamed form, an ordinary launch of any size: tiles by ticket, children numbered by look-back
     const JitNeeds need;
@@ -914,7 +966,7 @@ struct JitGen {
     std::vector<uint32_t> spec_bytes; std::vector<uint8_t> spec_memo;   // which word-list specs take the memoised form: 9..12 hashed bytes whose byte 8.. tail is made of whole fields
 
     JitGen(const ggrs_world* w_, std::string& s_)
-        : w(w_), s(s_), nc((uint32_t)w_->comps.size()), spawn_sys(jit_fused_spawn_system(w_)), need(jit_needs(w_)), L(jit_layout(w_)),
+        : w(w_), s(s_), nc((uint32_t)w_->comps.size()), spawn_sys(jit_fused_spawn_system(w_)), cmd_mut(world_cmd_mut_comps(w_)), need(jit_needs(w_)), L(jit_layout(w_)),
           IB(L.in_bytes), MAXP(L.max_players), IN_STRIDE(L.in_stride), OFF_ALIVE(w_->off_alive), OFF_DIS(w_->marks.off_disabled), OFF_DF(w_->marks.off_dframe),
           OFF_TAGS(w_->off_tags), TAGCOLS(w_->tag_cols), NTC(w_->n_tcols), TAG_ROW(w_->tag_row_bytes), HOT(jit_hot_cols(w_)), LOADHOT(HOT | jit_static_reads(w_)) {
         for (uint32_t c = 0; c < nc; ++c) if (rb(c) && strat(c)) any_strat = true;
@@ -935,6 +987,9 @@ struct JitGen {
     }
 
     bool rb(uint32_t c) const { return c < nc && !w->comps[c].no_rollback; }
+    // the lane's presence bit of component c can change inside the kernel -- a fused spawn sets its bundle's, a system inserts or removes c --: the bit is a mutable
+    // register and the mask word a Save stores is rebuilt from the lanes; every other component's word is the copy of the source's
+    bool pres_mut(uint32_t c) const { return spawn_sys >= 0 || ((cmd_mut >> c) & 1ull); }
     uint32_t col(uint32_t c, uint32_t k) const { return w->comps[c].col_base + k; }
     bool strat(uint32_t c) const { return w->comps[c].s_n_words != 0; }                      // snapshots hold Strategy::Stored, not the component (strategy.rs:22-40)
     uint32_t scol(uint32_t c, uint32_t k) const { return w->comps[c].scol_base + k; }
@@ -991,7 +1046,7 @@ struct JitGen {
                                     "#define GGRS_SP_READ %uu                                                           // sp_desc[GGRS_SP_READ x tiles + tile]: that tile has read its starting len\n",
                          2u + (unsigned)MAX_TICK_SAVES, 2u * (unsigned)MAX_TICK_STEPS);
         s += GGRS_FRAME_TEXT;
-        s += need.effects ? GGRS_ENTITY_EFFECTS_TEXT : (need.peers ? GGRS_ENTITY_PEERS_TEXT : GGRS_ENTITY_TEXT);
+        s += entity_text(need.effects, need.peers, need.commands);
         s += GGRS_COMPONENT_TEXT;
         s += GGRS_WORDS_TEXT;
         s += jit_layout_text(L);
@@ -999,6 +1054,8 @@ struct JitGen {
     // ---- 2. user sources: systems, spawner, hashers, strategies -- each in a namespace of its own, under its own name in the compiler's messages
     void user_sources() {
         for (size_t i = 0; i < w->customs.size(); ++i) {
+            if (need.commands) sfmt(s, "namespace ggrs_sys_%zu {\n%s#line 1 \"%s\"\n", i, cmd_entity_typedef(w, w->customs[i]).c_str(), file_name(w->customs[i].name).c_str());
+            else
             sfmt(s, "namespace ggrs_sys_%zu {\n#line 1 \"%s\"\n", i, file_name(w->customs[i].name).c_str());
             s += w->customs[i].source;
             s += "\n}\n";
@@ -1118,7 +1175,7 @@ struct JitGen {
         if (need.nr) s += "    uint32_t src_alive_v = alive_0 ? 1u : 0u; asm volatile(\"\" : \"+v\"(src_alive_v));\n";
         for (uint32_t c = 0; c < nc; ++c) if (rb(c))
             sfmt(s, "    const uint64_t mk%u = *reinterpret_cast<const uint64_t*>(a.src + %lluull + wi8);\n"
-                    "    %sbool p%u_0 = (mk%u >> sh) & 1ull;\n", c, (unsigned long long)w->off_present[c], spawn_sys >= 0 ? "" : "const ", c, c);
+                    "    %sbool p%u_0 = (mk%u >> sh) & 1ull;\n", c, (unsigned long long)w->off_present[c], pres_mut(c) ? "" : "const ", c, c);
         for (uint32_t c = 0; c < nc; ++c) if (rb(c)) {
             for (uint32_t k = 0; k < w->comps[c].n_words; ++k) {
                 const uint32_t cl = col(c, k), wb = w->comps[c].word_bytes;
@@ -1226,13 +1283,14 @@ struct JitGen {
         sfmt(s, "%s}\n", indent);
         // a spawn inside the group sets presence bits of its bundle: the mask words are then rebuilt from the lanes (as the liveness word
         // always is); without a fusable spawn system only the host changes them and the word read from the source is what is stored
-        if (spawn_sys >= 0) for (uint32_t c = 0; c < nc; ++c) if (rb(c)) sfmt(s, "%sconst uint64_t pm%u = __ballot(p%u_0);\n", indent, c, c);
+        // ... and so does a system that inserts or removes a component (command bindings), for that component alone
+        for (uint32_t c = 0; c < nc; ++c) if (rb(c) && pres_mut(c)) sfmt(s, "%sconst uint64_t pm%u = __ballot(p%u_0);\n", indent, c, c);
         sfmt(s, "%sif (lane == 0) {\n%s    *reinterpret_cast<uint64_t*>(%s + %lluull + wi8) = %s;\n", indent, indent, dst, OFF_ALIVE, alive_word);
         // presence masks change on the host (spawn, insert, remove, load, adopt) or through a fused spawn: they carry versions like the
         // columns, and a mask the destination already holds is not stored again (8-byte single-lane stores into lines nothing else of
         // the launch touches: 2-5 % of a depth-8 tick at 1 M, 8 % at 4 M, profiles/r03n)
         for (uint32_t c = 0; c < nc; ++c) if (rb(c))
-            sfmt(s, "%s    if ((%s >> %uu) & 1u) *reinterpret_cast<uint64_t*>(%s + %lluull + wi8) = %s%u;\n", indent, pmask, c, dst, (unsigned long long)w->off_present[c], spawn_sys >= 0 ? "pm" : "mk", c);
+            sfmt(s, "%s    if ((%s >> %uu) & 1u) *reinterpret_cast<uint64_t*>(%s + %lluull + wi8) = %s%u;\n", indent, pmask, c, dst, (unsigned long long)w->off_present[c], pres_mut(c) ? "pm" : "mk", c);
         sfmt(s, "%s}\n", indent);
     }
     // the statement of the STREAMED form after a store into `blk`: see sp_gate (kJitSpStreamed)
@@ -1509,6 +1567,10 @@ struct JitGen {
         const ggrs_world::Custom& c = w->customs[d.comp[0]];
         s += "            if (alive_0";
         for (uint32_t pz = 0; pz < c.n_pres; ++pz) sfmt(s, " && p%u_0", c.pres_comp[pz]);
+        if (need.commands)
+        sfmt(s, ") {                                                   // user system %u\n"
+                "                ggrs_sys_%u::GgrsEntity ent; ent.slot = e0; ent.kill = 0; ent.spawn_n = 0; ent.has_ = 0u;\n", d.comp[0], d.comp[0]);
+        else
         sfmt(s, ") {                                                   // user system %u\n"
                 "                GgrsEntity ent; ent.slot = e0; ent.kill = 0; ent.spawn_n = 0;\n", d.comp[0]);
         for (uint32_t b = 0; b < 8; ++b) { if (b < c.n_bind) sfmt(s, "                ent.w[%u] = w%u_0;\n", b, col(c.comp[b], c.word[b])); else if (need.devspawn) sfmt(s, "                ent.w[%u] = 0;\n", b); }
@@ -1533,6 +1595,18 @@ struct JitGen {
                 sfmt(s, "                ent.fx_.col[%u] = (unsigned long)a.fx_col[%u]; ent.fx_.wb[%u] = %uu; ent.fx_.op[%u] = %uu;\n", j, at, j, w->comps[c.fcomp[j]].word_bytes, j, c.fop[j]);
             }
         }
+        // command bindings: binding j's words go in from the registers where the lane has the component and from the literals of its registered default where it has
+        // not -- what the absent lane's registers hold is whatever the source block had at that slot, never read as a value -- and has_ carries the presence bits
+        for (uint32_t j = 0; j < c.n_cmd; ++j) {
+            const uint32_t cc = c.ccomp[j], base = cmd_word_base(w, c, j);
+            const Comp& T = w->comps[cc];
+            sfmt(s, "                if (p%u_0) ent.has_ |= %uu;\n", cc, 1u << j);
+            for (uint32_t k = 0; k < T.n_words; ++k) {
+                unsigned long long v = 0;
+                if (T.defaults.size() >= (size_t)(k + 1) * T.word_bytes) memcpy(&v, &T.defaults[(size_t)k * T.word_bytes], T.word_bytes);
+                sfmt(s, "                ent.opt[%u] = p%u_0 ? (ggrs_u64)w%u_0 : 0x%llxull;\n", base + k, cc, col(cc, k), v);
+            }
+        }
         sfmt(s, "                ggrs_sys_%u::ggrs_system(ent, fr%zu);\n", d.comp[0], i);
         if (need.devstream) s += "                if (ent.spawn_n) {                                        // e.spawn(n): the children are made after the frame's systems, from what THIS call left in e\n"
                                  "                    spn_0 = (uint32_t)ent.spawn_n;\n"
@@ -1545,6 +1619,15 @@ struct JitGen {
                                      "                }\n";
         for (uint32_t b = 0; b < c.n_bind; ++b)
             sfmt(s, "                w%u_0 = (%s)(%s)ent.w[%u];\n", col(c.comp[b], c.word[b]), wtype(c.comp[b]), mtype(c.comp[b]), b);   // narrow words wrap as their memory type does
+        // ... and out: the outcome of e.insert / e.remove (the last call won) is the lane's presence bit from here on -- the systems registered after this one see it in
+        // this frame, a Save stores it --, and a component the entity now has takes all its words from e.opt_* (also when the same call despawned the entity)
+        for (uint32_t j = 0; j < c.n_cmd; ++j) {
+            const uint32_t cc = c.ccomp[j], base = cmd_word_base(w, c, j);
+            if (c.cflags[j] & (GGRS_CMD_INSERT | GGRS_CMD_REMOVE)) sfmt(s, "                p%u_0 = (ent.has_ >> %uu) & 1u;\n", cc, j);
+            sfmt(s, "                if (p%u_0) {", cc);
+            for (uint32_t k = 0; k < w->comps[cc].n_words; ++k) sfmt(s, " w%u_0 = (%s)(%s)ent.opt[%u];", col(cc, k), wtype(cc), mtype(cc), base + k);
+            s += " }\n";
+        }
         if (need.marks) s += "                if (ent.kill) { if (ent.kill == 2 && defer) { dis_0 = true; df_0 = a.step_frame[sj]; } alive_0 = false; }\n";
         else       s += "                if (ent.kill) alive_0 = false;                            // (no system of this world can defer a despawn: its sources name neither despawn_rollback() nor `kill`)\n";
         s += ""

@@ -296,7 +296,8 @@ class World(WorldBase):
         self._comps = []
         self.capacity = capacity
 
-    def add_custom_system(self, source: str, bindings: Sequence[tuple], iparam=(), fparam=(), name: str = "custom", peers: Sequence[tuple] = (), effects: Sequence[tuple] = ()):
+    def add_custom_system(self, source: str, bindings: Sequence[tuple], iparam=(), fparam=(), name: str = "custom", peers: Sequence[tuple] = (), effects: Sequence[tuple] = (),
+                          commands: Sequence[tuple] = ()):
         """add_systems(GgrsSchedule, <your system>) for a per-entity system written in HIP C++ (ggrs_hip_add_custom_system):
         `source` defines `__device__ void ggrs_system(GgrsEntity& e, const GgrsFrame& f)`, `bindings` = [(comp, word), ..]
         are the words it sees as e.f32(i)/e.u32(i)/e.i32(i)/e.u64(i).  Compiled for gfx950 when added; a compile error raises
@@ -305,7 +306,9 @@ class World(WorldBase):
         the start of the frame -- `GgrsPeer p = e.peer(slot); if (p.ok()) .. p.f32(j) ..` with j indexing this list.
         `effects` = [(comp, word, op), ..] (ggrs_hip_add_custom_system_effects): the words of OTHER entities the system may write --
         `e.send_u32(slot, j, v)` / `e.send_i32` / `e.send_u64` combines v into effect binding j of the entity at `slot` with `op` (EFFECT_ADD,
-        EFFECT_MIN_U, ..: integer, commutative, associative); every send of a frame lands at the end of the frame."""
+        EFFECT_MIN_U, ..: integer, commutative, associative); every send of a frame lands at the end of the frame.
+        `commands` = [(comp, flags), ..] (ggrs_hip_add_custom_system_commands): whole components of its OWN entity the system sees as
+        Option<&mut C> -- `e.has(j)`, `e.opt_u32(j, k)` .. -- and, with CMD_INSERT / CMD_REMOVE in the flags, may `e.insert(j)` / `e.remove(j)`."""
         d = _ffi.CustomSystemDesc()
         d.name, d.source, d.n_bindings = name.encode(), source.encode(), len(bindings)
         if len(bindings) > _ffi.CUSTOM_MAX_BINDINGS:
@@ -313,6 +316,17 @@ class World(WorldBase):
         for i, (c, w) in enumerate(bindings): d.comp[i], d.word[i] = c, w
         for i, v in enumerate(iparam): d.iparam[i] = v
         for i, v in enumerate(fparam): d.fparam[i] = v
+        if commands:
+            if len(peers) > _ffi.PEER_MAX_BINDINGS or len(effects) > _ffi.EFFECT_MAX_BINDINGS or len(commands) > _ffi.COMMAND_MAX_BINDINGS:
+                raise ValueError(f"at most {_ffi.PEER_MAX_BINDINGS} peer, {_ffi.EFFECT_MAX_BINDINGS} effect and {_ffi.COMMAND_MAX_BINDINGS} command bindings")
+            pb = (_ffi.PeerBinding * max(1, len(peers)))()
+            for j, (c, w) in enumerate(peers): pb[j].comp, pb[j].word = c, w
+            eb = (_ffi.EffectBinding * max(1, len(effects)))()
+            for j, (c, w, op) in enumerate(effects): eb[j].comp, eb[j].word, eb[j].op = c, w, op
+            cb = (_ffi.CommandBinding * len(commands))()
+            for j, (c, fl) in enumerate(commands): cb[j].comp, cb[j].flags = c, fl
+            self._check(self._lib.ggrs_hip_add_custom_system_commands(self._p, C.byref(d), pb, len(peers), eb, len(effects), cb, len(commands)))
+            return
         if not peers and not effects:
             self._check(self._lib.ggrs_hip_add_custom_system(self._p, C.byref(d)))
             return

@@ -331,6 +331,7 @@ struct CustomKernelSystem {
     std::vector<std::pair<std::string, uint32_t>> peers;         // (component name, word) of other entities, read through e.peer(slot)
     struct Effect { std::string comp; uint32_t word, op; };
     std::vector<Effect> effects;                                 // (component name, word, GGRS_EFFECT_*) of other entities, written through e.send_*(slot, j, v)
+    std::vector<std::pair<std::string, uint32_t>> commands;      // (component name, GGRS_CMD_* flags) of its OWN entity: e.has(j), e.opt_*(j, k), e.insert(j), e.remove(j)
     int64_t iparam[2] = {0, 0};
     float fparam[4] = {0, 0, 0, 0};
     CustomKernelSystem(std::string n, std::string src) : name(std::move(n)), source(std::move(src)) {}
@@ -339,6 +340,9 @@ struct CustomKernelSystem {
     // effect<T>(word, op) appends the next EFFECT binding (ggrs_hip_add_custom_system_effects): a second Query<&mut T> + get_mut(target) is
     // `e.send_u32(slot, j, v)` / `e.send_i32` / `e.send_u64`, combined with op (integer, commutative, associative) at the end of the frame
     template <class T> CustomKernelSystem& effect(uint32_t word, uint32_t op) { effects.push_back(Effect{HipComponent<T>::name, word, op}); return *this; }
+    // command<T>(flags) appends the next COMMAND binding (ggrs_hip_add_custom_system_commands): Has<T> / Option<&mut T> as e.has(j) / e.opt_*(j, k), and with
+    // GGRS_CMD_INSERT / GGRS_CMD_REMOVE in flags commands.entity(e).insert(T) / .remove::<T>() as e.insert(j) / e.remove(j)
+    template <class T> CustomKernelSystem& command(uint32_t flags) { commands.emplace_back(HipComponent<T>::name, flags); return *this; }
 };
 
 // add_systems(GgrsSchedule, <a system that spawns Rollback entities>): `commands.spawn((bundle.., Rollback))` (snapshot/rollback.rs:45-59) as HIP C++ source defining
@@ -414,6 +418,7 @@ struct HipBackend {
     int add_custom_system(const ggrs_custom_system_desc* d) { return ggrs_hip_add_custom_system(w, d); }
     int add_custom_system_peers(const ggrs_custom_system_desc* d, const ggrs_peer_binding* peers, uint32_t n_peers) { return ggrs_hip_add_custom_system_peers(w, d, peers, n_peers); }
     int add_custom_system_effects(const ggrs_custom_system_desc* d, const ggrs_peer_binding* peers, uint32_t n_peers, const ggrs_effect_binding* effects, uint32_t n_effects) { return ggrs_hip_add_custom_system_effects(w, d, peers, n_peers, effects, n_effects); }
+    int add_custom_system_commands(const ggrs_custom_system_desc* d, const ggrs_peer_binding* peers, uint32_t n_peers, const ggrs_effect_binding* effects, uint32_t n_effects, const ggrs_command_binding* cmds, uint32_t n_cmds) { return ggrs_hip_add_custom_system_commands(w, d, peers, n_peers, effects, n_effects, cmds, n_cmds); }
     int add_spawn_system(const ggrs_spawn_system_desc* d) { return ggrs_hip_add_spawn_system(w, d); }
     int register_component_strategy(uint32_t c, uint32_t stored_word_bytes, uint32_t stored_n_words, const char* source) { return ggrs_hip_register_component_strategy(w, c, stored_word_bytes, stored_n_words, source); }
     int set_frame_rate(uint64_t fps) { return ggrs_hip_set_frame_rate(w, fps); }
@@ -558,7 +563,11 @@ class App {
         if (s.effects.size() > GGRS_EFFECT_MAX_BINDINGS) throw std::invalid_argument("a custom kernel system has at most 8 effect bindings");
         ggrs_effect_binding eb[GGRS_EFFECT_MAX_BINDINGS];
         for (size_t k = 0; k < s.effects.size(); ++k) { eb[k].comp = comp_id(s.effects[k].comp); eb[k].word = s.effects[k].word; eb[k].op = s.effects[k].op; }
-        if (!s.effects.empty()) check(be_.add_custom_system_effects(&d, pb, (uint32_t)s.peers.size(), eb, (uint32_t)s.effects.size()));
+        if (s.commands.size() > GGRS_COMMAND_MAX_BINDINGS) throw std::invalid_argument("a custom kernel system has at most 4 command bindings");
+        ggrs_command_binding cb[GGRS_COMMAND_MAX_BINDINGS];
+        for (size_t k = 0; k < s.commands.size(); ++k) { cb[k].comp = comp_id(s.commands[k].first); cb[k].flags = s.commands[k].second; }
+        if (!s.commands.empty()) check(be_.add_custom_system_commands(&d, pb, (uint32_t)s.peers.size(), eb, (uint32_t)s.effects.size(), cb, (uint32_t)s.commands.size()));
+        else if (!s.effects.empty()) check(be_.add_custom_system_effects(&d, pb, (uint32_t)s.peers.size(), eb, (uint32_t)s.effects.size()));
         else check(s.peers.empty() ? be_.add_custom_system(&d) : be_.add_custom_system_peers(&d, pb, (uint32_t)s.peers.size()));
         return *this;
     }

@@ -295,6 +295,41 @@ int ggrs_hip_add_custom_system_effects(ggrs_world* w, const ggrs_custom_system_d
                                        const ggrs_peer_binding* peers, uint32_t n_peers,
                                        const ggrs_effect_binding* effects, uint32_t n_effects);
 
+/* STRUCTURAL COMMANDS (command bindings).  In the reference a system takes Has<C> or Option<&mut C> and calls commands.entity(e).insert(C) /
+ * .remove::<C>(): an entity gains Stunned{ticks} from a hit and loses it when it runs out.  LoadWorld's (Some, None) -> remove and (None, Some) -> insert
+ * branches (component_snapshot.rs:106-115) exist because systems do this.  A system registered through this entry point may change its OWN entity's set
+ * of components.  cmds[j] = {comp, flags} names command binding j -- a WHOLE component -- (at most GGRS_COMMAND_MAX_BINDINGS, and
+ * GGRS_COMMAND_MAX_WORDS words of all of them together); peers and effects are as in ggrs_hip_add_custom_system_effects, and with n_cmds == 0 the call
+ * behaves exactly as that one.  Inside ggrs_system(GgrsEntity& e, const GgrsFrame& f), with j and k literals:
+ *
+ *     e.has(j)                                                whether the entity has the component now (an earlier insert / remove of this call included)
+ *     e.opt_f32(j, k) / opt_u32 / opt_i32 / opt_u64 /         references to word k of the component: on entry the entity's word when the component is
+ *       opt_u16 / opt_u8                                      present, its registered default (ggrs_hip_set_component_default, else 0) when it is absent
+ *     e.insert(j)                                             needs GGRS_CMD_INSERT in flags   } the last call wins; a call whose flag was not declared
+ *     e.remove(j)                                             needs GGRS_CMD_REMOVE in flags   } (or whose j is not a constant) does not compile
+ *
+ * After the call the entity has the component iff (has on entry or insert) and not a later remove; if it has it, ALL its words are written back from
+ * e.opt_* -- insert on a present component replaces its value, as Bevy's does.  Commands apply even when the same call despawns the entity.  Under
+ * one-entity-at-a-time systems this equals Bevy's deferred Commands: a system registered LATER runs for the entity in the same frame only if it now
+ * has every component that system binds; a system registered EARLIER sees the change in the next frame.  The system itself still runs only for live
+ * entities that have all of its own bound components; its own bindings and its command bindings share no component.
+ * For every registration-order rule (peer and effect bindings above) a command-bound component counts as WRITTEN by the system, in every column.
+ * This version refuses, each with GGRS_E_INVALID and a message naming the system and the component: a command-bound component under a Strategy or
+ * registered GGRS_COMP_NO_ROLLBACK; a world that keeps RollbackDespawned markers; a world that spawns on the device with e.spawn(n); a world without
+ * the generated kernel; GGRS_BRANCH_RETAIN_* in ggrs_hip_fanout_step_branches on such a world (without retention, and ggrs_hip_fanout_step, work).
+ * How it runs: everything stays inside the lane of the generated kernel -- the presence bit of such a component is a mutable register, the mask word
+ * of a component with a declared INSERT or REMOVE is rebuilt with one ballot per Save, and every AdvanceWorld gives that mask and the component's
+ * columns fresh row versions.  No extra launch, no atomics. */
+#define GGRS_CMD_INSERT 1u   /* the system may call e.insert(j) */
+#define GGRS_CMD_REMOVE 2u   /* the system may call e.remove(j) */
+typedef struct { uint32_t comp; uint32_t flags; } ggrs_command_binding;   /* command binding j = component `comp`; flags 0: Has<C> / Option<&mut C> only */
+#define GGRS_COMMAND_MAX_BINDINGS 4
+#define GGRS_COMMAND_MAX_WORDS    8   /* words of all command-bound components of one system together */
+int ggrs_hip_add_custom_system_commands(ggrs_world* w, const ggrs_custom_system_desc* desc,
+                                        const ggrs_peer_binding* peers, uint32_t n_peers,
+                                        const ggrs_effect_binding* effects, uint32_t n_effects,
+                                        const ggrs_command_binding* cmds, uint32_t n_cmds);
+
 /* ComponentSnapshotPlugin<S: Strategy> (snapshot/strategy.rs:22-40, component_snapshot.rs:42-63): what a snapshot HOLDS of a component is
  * S::Stored, produced by S::store and turned back by S::load / S::update -- CopyStrategy / CloneStrategy (Stored == the component, bitwise for
  * POD) are what ggrs_hip_register_component gives; this is the open door next to them: quantised, packed or partial snapshots.

@@ -107,6 +107,19 @@ pub struct ggrs_peer_binding {
 pub const GGRS_PEER_MAX_BINDINGS: usize = 8;
 pub const GGRS_PEER_MAX_COLUMNS: usize = 16;
 
+/// One command binding of `ggrs_hip_add_custom_system_commands`: a whole component of its OWN entity a system sees as `Option<&mut C>` (`e.has(j)`, `e.opt_*(j, k)`)
+/// and, with `GGRS_CMD_INSERT` / `GGRS_CMD_REMOVE` in `flags`, may insert or remove through `e.insert(j)` / `e.remove(j)`.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct ggrs_command_binding {
+    pub comp: u32,
+    pub flags: u32,
+}
+pub const GGRS_CMD_INSERT: u32 = 1;
+pub const GGRS_CMD_REMOVE: u32 = 2;
+pub const GGRS_COMMAND_MAX_BINDINGS: usize = 4;
+pub const GGRS_COMMAND_MAX_WORDS: usize = 8;
+
 /// One effect binding of `ggrs_hip_add_custom_system_effects`: a word of OTHER entities a system writes through `e.send_*(slot, j, v)`, combined with `op`.
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -210,6 +223,7 @@ unsafe extern "C" {
     pub fn ggrs_hip_add_custom_system(w: *mut ggrs_world, desc: *const ggrs_custom_system_desc) -> c_int;
     pub fn ggrs_hip_add_custom_system_peers(w: *mut ggrs_world, desc: *const ggrs_custom_system_desc, peers: *const ggrs_peer_binding, n_peers: u32) -> c_int;
     pub fn ggrs_hip_add_custom_system_effects(w: *mut ggrs_world, desc: *const ggrs_custom_system_desc, peers: *const ggrs_peer_binding, n_peers: u32, effects: *const ggrs_effect_binding, n_effects: u32) -> c_int;
+    pub fn ggrs_hip_add_custom_system_commands(w: *mut ggrs_world, desc: *const ggrs_custom_system_desc, peers: *const ggrs_peer_binding, n_peers: u32, effects: *const ggrs_effect_binding, n_effects: u32, cmds: *const ggrs_command_binding, n_cmds: u32) -> c_int;
     pub fn ggrs_hip_register_component_strategy(w: *mut ggrs_world, comp_id: u32, stored_word_bytes: u32, stored_n_words: u32, source: *const c_char) -> c_int;
     pub fn ggrs_hip_set_input_layout(w: *mut ggrs_world, input_bytes: u32, max_players: u32) -> c_int;
     pub fn ggrs_hip_add_spawn_system(w: *mut ggrs_world, desc: *const ggrs_spawn_system_desc) -> c_int;
