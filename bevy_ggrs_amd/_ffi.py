@@ -92,6 +92,20 @@ class CommandBinding(C.Structure):
     _fields_ = [("comp", C.c_uint32), ("flags", C.c_uint32)]
 
 
+SYS_RESOURCE = 9
+RESOURCE_MAX, RESOURCE_MAX_BYTES, RESOURCE_MAX_BINDINGS = 8, 64, 8
+
+
+class ResourceBinding(C.Structure):
+    _fields_ = [("res", C.c_uint32), ("word", C.c_uint32)]
+
+
+class ResourceSystemDesc(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("source", C.c_char_p), ("n_bindings", C.c_uint32),
+                ("res", C.c_uint32 * RESOURCE_MAX_BINDINGS), ("word", C.c_uint32 * RESOURCE_MAX_BINDINGS),
+                ("iparam", C.c_int64 * 2), ("fparam", C.c_float * 4)]
+
+
 class SpawnSystemDesc(C.Structure):
     _fields_ = [("name", C.c_char_p), ("source", C.c_char_p), ("bundle_mask", C.c_uint64), ("payload_stride", C.c_uint32), ("n_bindings", C.c_uint32),
                 ("comp", C.c_uint32 * CUSTOM_MAX_BINDINGS), ("word", C.c_uint32 * CUSTOM_MAX_BINDINGS),
@@ -141,6 +155,13 @@ SIGNATURES = {
     "ggrs_hip_add_custom_system_effects": (C.c_int, [_P, C.POINTER(CustomSystemDesc), C.POINTER(PeerBinding), C.c_uint32, C.POINTER(EffectBinding), C.c_uint32]),
     "ggrs_hip_add_custom_system_commands": (C.c_int, [_P, C.POINTER(CustomSystemDesc), C.POINTER(PeerBinding), C.c_uint32, C.POINTER(EffectBinding), C.c_uint32,
                                                       C.POINTER(CommandBinding), C.c_uint32]),
+    "ggrs_hip_add_custom_system_resources": (C.c_int, [_P, C.POINTER(CustomSystemDesc), C.POINTER(PeerBinding), C.c_uint32, C.POINTER(EffectBinding), C.c_uint32,
+                                                       C.POINTER(CommandBinding), C.c_uint32, C.POINTER(ResourceBinding), C.c_uint32]),
+    "ggrs_hip_register_resource": (C.c_int, [_P, C.c_char_p, C.c_uint32, C.c_uint32, _P, C.POINTER(C.c_uint32)]),
+    "ggrs_hip_checksum_resource": (C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32]),
+    "ggrs_hip_add_resource_system": (C.c_int, [_P, C.POINTER(ResourceSystemDesc)]),
+    "ggrs_hip_resource_read": (C.c_int, [_P, C.c_uint32, _P]),
+    "ggrs_hip_resource_write": (C.c_int, [_P, C.c_uint32, _P]),
     "ggrs_hip_register_component_strategy": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p]),
     "ggrs_hip_set_input_layout": (C.c_int, [_P, C.c_uint32, C.c_uint32]),
     "ggrs_hip_add_spawn_system": (C.c_int, [_P, C.POINTER(SpawnSystemDesc)]),

@@ -228,7 +228,14 @@ int ggrs_hip_add_custom_system_effects(ggrs_world* w, const ggrs_custom_system_d
 // ... and with command bindings: whole components of its OWN entity the system sees as Option<&mut C> (e.has, e.opt_*) and may insert or remove (include/ggrs_hip.h)
 int ggrs_hip_add_custom_system_commands(ggrs_world* w, const ggrs_custom_system_desc* d, const ggrs_peer_binding* peers, uint32_t n_peers, const ggrs_effect_binding* effects, uint32_t n_effects,
                                         const ggrs_command_binding* cmds, uint32_t n_cmds) {
+    return ggrs_hip_add_custom_system_resources(w, d, peers, n_peers, effects, n_effects, cmds, n_cmds, nullptr, 0);
+}
+// ... and with resource bindings: words of the world's device resources the system reads through e.res_*(j), as they stand at that point of the frame (include/ggrs_hip.h)
+int ggrs_hip_add_custom_system_resources(ggrs_world* w, const ggrs_custom_system_desc* d, const ggrs_peer_binding* peers, uint32_t n_peers, const ggrs_effect_binding* effects, uint32_t n_effects,
+                                         const ggrs_command_binding* cmds, uint32_t n_cmds, const ggrs_resource_binding* res, uint32_t n_res) {
     if (!w || !d || !d->source) return GGRS_E_INVALID;
+    if (n_res > GGRS_RESOURCE_MAX_BINDINGS) return w->fail(GGRS_E_INVALID, "custom system '%s': at most %d resource bindings (GGRS_RESOURCE_MAX_BINDINGS), not %u", d->name ? d->name : "custom", GGRS_RESOURCE_MAX_BINDINGS, n_res);
+    if (n_res && !res) return w->fail(GGRS_E_INVALID, "custom system: n_res = %u but res is NULL", n_res);
     if (n_cmds > GGRS_COMMAND_MAX_BINDINGS) return w->fail(GGRS_E_INVALID, "custom system '%s': at most %d command bindings (GGRS_COMMAND_MAX_BINDINGS), not %u", d->name ? d->name : "custom", GGRS_COMMAND_MAX_BINDINGS, n_cmds);
     if (n_cmds && !cmds) return w->fail(GGRS_E_INVALID, "custom system: n_cmds = %u but cmds is NULL", n_cmds);
     if (w->sealed) return w->fail(GGRS_E_INVALID, "add_custom_system after the world was sealed");
@@ -272,6 +279,12 @@ int ggrs_hip_add_custom_system_commands(ggrs_world* w, const ggrs_custom_system_
     if (cmd_words > GGRS_COMMAND_MAX_WORDS)
         return w->fail(GGRS_E_INVALID, "custom system '%s': its command-bound components have %u words together, at most %d (GGRS_COMMAND_MAX_WORDS)", c.name.c_str(), cmd_words, GGRS_COMMAND_MAX_WORDS);
     c.n_cmd = n_cmds;
+    for (uint32_t j = 0; j < n_res; ++j) {
+        if (res[j].res >= w->resources.size() || res[j].word >= w->resources[res[j].res].n_words)
+            return w->fail(GGRS_E_INVALID, "custom system '%s': resource binding %u names word %u of resource %u, which is not registered", c.name.c_str(), j, res[j].word, res[j].res);
+        c.rres[j] = res[j].res; c.rword[j] = res[j].word;
+    }
+    c.n_res = n_res;
     DeviceGuard dg(w);
     c.source = d->source;
     c.may_defer = source_has_token(c.source, "despawn_rollback") || source_has_token(c.source, "kill");
@@ -284,6 +297,75 @@ int ggrs_hip_add_custom_system_commands(ggrs_world* w, const ggrs_custom_system_
     sd.iparam[0] = d->iparam[0]; sd.iparam[1] = d->iparam[1];
     for (int k = 0; k < 4; ++k) sd.fparam[k] = d->fparam[k];
     w->customs.push_back(std::move(c));
+    w->systems.push_back(sd);
+    return GGRS_OK;
+}
+// DEVICE-RESIDENT ROLLBACK RESOURCES (include/ggrs_hip.h): init_resource + rollback_resource_with_copy, checksum_resource_with_hash, and the once-per-frame systems
+// that mutate them.  Registration only records; seal validates the world (host_seal.hpp resources_validate) and puts the initial values into the live block.
+int ggrs_hip_register_resource(ggrs_world* w, const char* name, uint32_t word_bytes, uint32_t n_words, const void* init_words, uint32_t* res_id_out) {
+    if (!w || !name) return GGRS_E_INVALID;
+    if (w->sealed) return w->fail(GGRS_E_INVALID, "register_resource '%s' after the world was sealed", name);
+    if (w->resources.size() >= GGRS_RESOURCE_MAX) return w->fail(GGRS_E_INVALID, "resource '%s': at most %d resources per world (GGRS_RESOURCE_MAX)", name, GGRS_RESOURCE_MAX);
+    if (word_bytes != 4 && word_bytes != 8) return w->fail(GGRS_E_INVALID, "resource '%s': word_bytes must be 4 or 8, not %u (1- and 2-byte words are not offered for resources)", name, word_bytes);
+    if (n_words == 0 || n_words > GGRS_RESOURCE_MAX_BYTES / word_bytes || res_total_bytes(w) + word_bytes * n_words > GGRS_RESOURCE_MAX_BYTES)
+        return w->fail(GGRS_E_INVALID, "resource '%s': %u words of %u bytes on top of %u bytes already registered: the resources of a world hold at most %d bytes together (GGRS_RESOURCE_MAX_BYTES)", name, n_words, word_bytes, res_total_bytes(w), GGRS_RESOURCE_MAX_BYTES);
+    ggrs_world::Resource r; r.name = name; r.word_bytes = word_bytes; r.n_words = n_words;
+    r.init.assign((size_t)word_bytes * n_words, 0);
+    if (init_words) memcpy(r.init.data(), init_words, r.init.size());
+    w->resources.push_back(std::move(r));
+    res_layout(w);
+    if (res_id_out) *res_id_out = (uint32_t)w->resources.size() - 1;
+    return GGRS_OK;
+}
+int ggrs_hip_checksum_resource(ggrs_world* w, uint32_t res_id, const uint32_t* word_idx, uint32_t n_words) {
+    if (!w) return GGRS_E_INVALID;
+    if (res_id >= w->resources.size()) return w->fail(GGRS_E_INVALID, "checksum_resource: resource %u is not registered", res_id);
+    ggrs_world::Resource& r = w->resources[res_id];
+    if (w->sealed) return w->fail(GGRS_E_INVALID, "checksum_resource '%s' after the world was sealed", r.name.c_str());
+    if (n_words && !word_idx) return w->fail(GGRS_E_INVALID, "checksum_resource '%s': word list is NULL", r.name.c_str());
+    if (n_words > GGRS_MAX_CKS_UNITS) return w->fail(GGRS_E_INVALID, "checksum_resource '%s': checksum spec too long", r.name.c_str());
+    for (uint32_t k = 0; k < n_words; ++k) if (word_idx[k] >= r.n_words) return w->fail(GGRS_E_INVALID, "checksum_resource '%s': word %u is not a word of the resource (%u words)", r.name.c_str(), word_idx[k], r.n_words);
+    r.cks_words.assign(word_idx, word_idx + n_words);
+    r.checksummed = true;
+    return GGRS_OK;
+}
+int ggrs_hip_add_resource_system(ggrs_world* w, const ggrs_resource_system_desc* d) {
+    if (!w || !d || !d->source) return GGRS_E_INVALID;
+    const char* nm = d->name ? d->name : "resource_system";
+    if (w->sealed) return w->fail(GGRS_E_INVALID, "add_resource_system '%s' after the world was sealed", nm);
+    if (w->systems.size() >= GGRS_MAX_SYSTEMS) return w->fail(GGRS_E_INVALID, "resource system '%s': too many systems (GGRS_MAX_SYSTEMS)", nm);
+    if (d->n_bindings == 0) return w->fail(GGRS_E_INVALID, "resource system '%s' has no binding: it could neither read nor change anything", nm);
+    if (d->n_bindings > GGRS_RESOURCE_MAX_BINDINGS) return w->fail(GGRS_E_INVALID, "resource system '%s': at most %d bindings (GGRS_RESOURCE_MAX_BINDINGS), not %u", nm, GGRS_RESOURCE_MAX_BINDINGS, d->n_bindings);
+    ggrs_world::ResSys rs; rs.name = nm; rs.source = d->source; rs.n_bind = d->n_bindings;
+    for (uint32_t b = 0; b < rs.n_bind; ++b) {
+        if (d->res[b] >= w->resources.size() || d->word[b] >= w->resources[d->res[b]].n_words)
+            return w->fail(GGRS_E_INVALID, "resource system '%s': binding %u names word %u of resource %u, which is not registered", nm, b, d->word[b], d->res[b]);
+        rs.res[b] = d->res[b]; rs.word[b] = d->word[b];
+    }
+    // a compile check against the system's own GgrsResources (a word it did not bind, or the other width, does not compile): the system itself only ever runs inside the generated kernel
+    std::string src = GGRS_CUSTOM_ABI_TEXT;
+    src += GGRS_FRAME_TEXT; src += GGRS_RESOURCES_TEXT; src += res_system_typedef(w, rs);
+    src += "#line 1 \"ggrs_resource_system\"\n"; src += d->source;
+    src += "\n#line 1 \"ggrs_resource_kernel\"\n"
+           "extern \"C\" __global__ void ggrs_resource_kernel(GgrsCustomArgs a) {\n"
+           "    GgrsFrame fr; fr.dt = a.fr.dt; fr.frame = a.fr.frame; fr.n_inputs = a.fr.n_inputs; fr.input_bytes = a.fr.input_bytes;\n"
+           "    fr.input.p = a.fr.in; fr.input.ib = a.fr.input_bytes; fr.status = a.fr.in + a.fr.status_off;\n"
+           "    for (int k = 0; k < 4; ++k) fr.fparam[k] = a.fr.fparam[k];\n"
+           "    fr.iparam[0] = a.fr.iparam[0]; fr.iparam[1] = a.fr.iparam[1];\n"
+           "    GgrsResources r; for (int k = 0; k < 8; ++k) r.w[k] = a.col_off[k];\n"
+           "    ggrs_resource_system(r, fr);\n"
+           "    for (int k = 0; k < 8; ++k) reinterpret_cast<ggrs_u64*>(a.state)[k] = r.w[k];\n"
+           "}\n";
+    DeviceGuard dg(w);
+    const std::string what = "resource system '" + rs.name + "'";
+    hipFunction_t fn = nullptr;
+    const int rc = hiprtc_build(w, src, what.c_str(), "ggrs_resource_kernel", nullptr, &fn);
+    if (rc) return rc;
+    ggrs_system_desc sd; memset(&sd, 0, sizeof sd);
+    sd.kind = GGRS_SYS_RESOURCE; sd.comp[0] = (uint32_t)w->res_systems.size();
+    sd.iparam[0] = d->iparam[0]; sd.iparam[1] = d->iparam[1];
+    for (int k = 0; k < 4; ++k) sd.fparam[k] = d->fparam[k];
+    w->res_systems.push_back(std::move(rs));
     w->systems.push_back(sd);
     return GGRS_OK;
 }
@@ -346,7 +428,7 @@ int ggrs_hip_generated_kernel_source(ggrs_world* w, uint32_t form, char* buf, ui
     if (!w || (form != GGRS_KERNEL_FORM_TILES && form != GGRS_KERNEL_FORM_STEADY)) return GGRS_E_INVALID;
     if (!w->sealed) {
         if (!w->layout_only) { DeviceGuard dg(w); const int rc = seal(w); if (rc) return rc; }
-        else { build_layout(w); const int prc = peers_validate(w); if (prc) return prc; const int frc = effects_validate(w); if (frc) return frc; const int crc = commands_validate(w); if (crc) return crc; }   // host arithmetic only: offsets of every mask and column; the peer-, effect- and command-binding rules
+        else { build_layout(w); const int prc = peers_validate(w); if (prc) return prc; const int frc = effects_validate(w); if (frc) return frc; const int crc = commands_validate(w); if (crc) return crc; const int rrc = resources_validate(w); if (rrc) return rrc; }   // host arithmetic only: offsets of every mask and column; the peer-, effect-, command- and resource rules
     }
     std::string src;
     if (!jit_source(w, src)) return w->fail(GGRS_E_INVALID, "the kernel generator does not cover this world (a system writes a live-only component, or more than %u four-byte units / %u words per entity)", JIT_MAX_UNITS, JIT_MAX_COLS);
@@ -487,6 +569,29 @@ int ggrs_hip_download_word(ggrs_world* w, uint32_t c, uint32_t word, uint64_t fi
     const Comp& cc = w->comps[c];
     rc = copy_column(w, cc.col_base + word, first, count, dst, false); if (rc) return rc;
     HIPCHK(w, hipStreamSynchronize(w->stream));
+    return GGRS_OK;
+}
+// world.resource::<R>() / world.resource_mut::<R>() of a device resource: the live block's current cell.  As for the column traffic above a lazily skipped live block is
+// materialised first (seal_live) and the copy is ordered on the world's stream; a write also ends the lazy-live streak -- the next list may read what was written.
+int ggrs_hip_resource_read(ggrs_world* w, uint32_t res_id, void* words_out) {
+    if (!w) return GGRS_E_INVALID;
+    DeviceGuard dg(w);
+    int rc = seal_live(w); if (rc) return rc;
+    if (res_id >= w->resources.size() || !words_out) return w->fail(GGRS_E_INVALID, "bad resource_read arguments (resource %u of %zu)", res_id, w->resources.size());
+    const ggrs_world::Resource& r = w->resources[res_id];
+    HIPCHK(w, hipMemcpyAsync(words_out, w->live.ptr + RES_CELL_OFF + w->live.res_cell * RES_CELL_BYTES + r.off, (size_t)r.word_bytes * r.n_words, hipMemcpyDeviceToHost, w->stream));
+    HIPCHK(w, hipStreamSynchronize(w->stream));
+    return GGRS_OK;
+}
+int ggrs_hip_resource_write(ggrs_world* w, uint32_t res_id, const void* words) {
+    if (!w) return GGRS_E_INVALID;
+    DeviceGuard dg(w);
+    int rc = seal_live(w); if (rc) return rc;
+    if (res_id >= w->resources.size() || !words) return w->fail(GGRS_E_INVALID, "bad resource_write arguments (resource %u of %zu)", res_id, w->resources.size());
+    const ggrs_world::Resource& r = w->resources[res_id];
+    HIPCHK(w, hipMemcpyAsync(w->live.ptr + RES_CELL_OFF + w->live.res_cell * RES_CELL_BYTES + r.off, words, (size_t)r.word_bytes * r.n_words, hipMemcpyHostToDevice, w->stream));
+    HIPCHK(w, hipStreamSynchronize(w->stream));                        // (the caller's buffer is free again when the call returns)
+    w->load_open_streak = 0; w->pending_valid = false;
     return GGRS_OK;
 }
 static int download_mask(ggrs_world* w, uint64_t off, uint64_t* dst, uint64_t n) {
@@ -789,9 +894,12 @@ int ggrs_hip_adopt_live_state(ggrs_world* w) {
     if (!w) return GGRS_E_INVALID;
     DeviceGuard dg(w);
     int rc = seal_live(w); if (rc) return rc;
-    Header h;
-    HIPCHK(w, hipMemcpyAsync(&h, w->live.ptr, sizeof h, hipMemcpyDeviceToHost, w->stream));
+    struct { Header h; uint32_t res_cell; } hx;                      // the u32 behind the header: which resource cell the block's producer left current (RES_CELL_IDX_OFF)
+    static_assert(offsetof(decltype(hx), res_cell) == RES_CELL_IDX_OFF, "the resource cell index sits right behind struct Header");
+    HIPCHK(w, hipMemcpyAsync(&hx, w->live.ptr, sizeof hx, hipMemcpyDeviceToHost, w->stream));
     HIPCHK(w, hipStreamSynchronize(w->stream));
+    const Header h = hx.h;
+    if (w->has_resources) w->live.res_cell = hx.res_cell & 1u;
     if (h.len > w->capacity) return w->fail(GGRS_E_INVALID, "adopted state has len %llu > capacity", (unsigned long long)h.len);
     w->len = h.len; w->frame = h.frame;
     w->live.dirty_len = std::max(w->live.dirty_len, w->len);
@@ -854,11 +962,14 @@ int ggrs_hip_world_kernel_info(ggrs_world* w, char* buf, uint64_t cap, uint64_t*
                                      std::to_string(w->lazy_materialised) + " materialised on demand");
         add("deferred_saves", std::string(lazy_live_possible(w) && !w->has_strategy && defer_saves_on(w) ? "on" : "off") + " (rollback groups of the same sessions store their first Save only): " +
                               std::to_string(w->saves_deferred) + " Saves deferred, " + std::to_string(w->slots_materialised) + " ring slots materialised on demand");
+        add("depth_parallel_roles", std::to_string(w->dp_groups) + " request groups so far split their Saves and the live block over roles (blockIdx.y)");
         add("group_caps", std::to_string(w->cap_saves) + " saves / " + std::to_string(w->cap_steps) + " steps");
         if (w->has_peers) add("peer_view", std::to_string(w->peer_view.n_cols) + " linear columns + visibility words, published from the group's source block ahead of every request group that holds an AdvanceWorld (" +
                                            std::to_string(w->peer_view.publishes) + " publishes so far)");
         if (w->has_commands) add("command_bindings", std::to_string(__builtin_popcountll(w->cmd_mut_comps)) + " components a system may insert or remove: their presence bits are registers of the generated kernel, "
                                                      "their mask words are rebuilt per Save, and every AdvanceWorld gives their masks and columns fresh row versions");
+        if (w->has_resources) add("device_resources", std::to_string(w->resources.size()) + " resources, " + std::to_string(res_total_bytes(w)) + " bytes: wave-uniform registers of the generated kernel, loaded from the source block's current cell "
+                                                      "(two cells per block; the live block's is cell " + std::to_string(w->live.res_cell) + "), stored with every snapshot's header");
         if (w->has_effects) add("effect_inbox", std::to_string(w->fx_inbox.n_cols) + " linear columns holding the ops' identities, applied to the live block right behind every request group that holds an AdvanceWorld (" +
                                                std::to_string(w->fx_inbox.applies) + " applies so far)");
         add("branch_marker_record_bytes", std::to_string(w->jit_marks ? jit_marks_rec_bytes(w) : 0));      // per retained branch of ggrs_hip_fanout_step_branches (0: the kernel keeps no markers)

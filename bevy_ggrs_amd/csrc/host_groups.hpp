@@ -219,6 +219,29 @@ inline void ff_attach(ggrs_world* w, GgrsJitArgs& j) {
     w->ff_mark_id = p.id;                                             // launch_jit records the group's event right behind this launch
 }
 
+// DEVICE RESOURCES: the two-cell rule.  A launch may write the block it reads (live -> live, a Save into the slot it loaded), workgroups of one launch start at
+// different times, and the scalar cache is not coherent with the launch's own stores: a launch therefore reads its source block's CURRENT cell and writes the OTHER
+// cell of any block that is its source (the record flips here, at enqueue); every other block it stores into takes cell 0.  No launch reads resource words from a
+// location it writes.  Every launch of the generated kernel passes through launch_jit, so this is the one place that keeps the records.
+inline Block* block_of(ggrs_world* w, const unsigned char* p) {
+    if (!p) return nullptr;
+    if (p == w->live.ptr) return &w->live;
+    for (auto& b : w->slots) if (b.ptr == p) return &b;
+    for (auto& b : w->spec_blocks) if (b.ptr == p) return &b;
+    return nullptr;
+}
+inline int res_cells_for_launch(ggrs_world* w, GgrsJitArgs& j) {
+    Block* const sb = block_of(w, j.src);
+    if (!sb) return w->fail(GGRS_E_INVALID, "device resources: the launch's source block is none of the world's blocks");
+    j.res_src = j.src + RES_CELL_OFF + sb->res_cell * RES_CELL_BYTES; j.res_alt = RES_CELL_OFF + (1u - sb->res_cell) * RES_CELL_BYTES;
+    if (j.mtab) return GGRS_OK;                                        // batch members with records: GGRS_BRANCH_RETAIN_* is refused for such a world, so no member stores anything
+    bool src_written = false;
+    auto wrote = [&](const unsigned char* p) { Block* b = block_of(w, p); if (b == sb) src_written = true; else if (b) b->res_cell = 0; };
+    for (uint32_t k = 0; k < j.n_saves; ++k) wrote(j.save_dst[k]);
+    if ((!j.src_is_live || j.n_steps) && !j.skip_live) wrote(j.live);
+    if (src_written) sb->res_cell ^= 1u;
+    return GGRS_OK;
+}
 // Launch of a generated kernel: the host-side argument block is packed into the world's device layout (kernel_gen.hpp jit_pack).  With
 // profiling on, the event pair rides on the dispatch itself (hipExtModuleLaunchKernel's start / stop events: the kernel's own begin and end,
 // what rocprofv3's kernel trace reports) instead of bracketing it with two marker packets, which read ~3 us more.
@@ -229,6 +252,7 @@ int launch_jit(ggrs_world* w, hipFunction_t fn, uint32_t gx, uint32_t gy, uint32
     const bool streamed = w->dev_spawn && jit_dev_stream(w);
     if (streamed) { j.sp_ticket_base = w->sp_ticket_base; w->sp_ticket_base += (uint64_t)(gx + j.ff_blocks) * gy * gz; }   // every workgroup takes one ticket
     j.skip_count = (w->prof && j.vtags) ? reinterpret_cast<ggrs_u64*>(w->d_skip) : nullptr;
+    if (w->has_resources) { const int rrc = res_cells_for_launch(w, j); if (rrc) return rrc; }
     jit_pack(*w->jl, j, w->jit_argbuf.data());
     void* params[] = {w->jit_argbuf.data()};
     gx += j.ff_blocks;
@@ -304,15 +328,15 @@ hipFunction_t jit_spec_for(ggrs_world* w, const GgrsJitArgs& j, bool members = f
     return s->spec->state.load(std::memory_order_acquire) == 2 ? s->spec->fn : nullptr;
 }
 
-inline ggrs_world::HostFold make_host_fold(const GgrsJitArgs& j, uint32_t res_slot, uint32_t rows, uint32_t n_cks, uint32_t members, uint64_t rows_off) {
-    ggrs_world::HostFold f{}; f.res_slot = res_slot; f.n_saves = j.n_saves; f.g = rows; f.n_cks = n_cks; f.members = members; f.rows_off = rows_off;
+inline ggrs_world::HostFold make_host_fold(const ggrs_world* w, const GgrsJitArgs& j, uint32_t res_slot, uint32_t rows, uint32_t n_cks, uint32_t members, uint64_t rows_off) {
+    ggrs_world::HostFold f{}; f.res_slot = res_slot; f.n_saves = j.n_saves; f.g = rows; f.n_cks = n_cks; f.members = members; f.rows_off = rows_off; f.n_rows = jit_part_rows(w, n_cks);
     for (uint32_t k = 0; k < j.n_saves && k < (uint32_t)MAX_TICK_SAVES; ++k) f.save_len[k] = j.save_len[k];
     return f;
 }
 // res: the result slot of the group's first Save -- the pinned ring's cell and, when a consumer asked for one (ggrs_world::dev_results_dst), the device copy's
 inline GenFinArgs make_gen_fin(const ggrs_world* w, const GgrsJitArgs& j, uint32_t rows, uint32_t n_cks, uint32_t res) {
     GenFinArgs f; memset(&f, 0, sizeof f);
-    f.parts = reinterpret_cast<uint64_t*>(j.parts); f.part_stride = j.part_stride; f.n_parts = rows; f.n_cks = n_cks; f.n_saves = std::max(1u, j.n_saves);
+    f.parts = reinterpret_cast<uint64_t*>(j.parts); f.part_stride = j.part_stride; f.n_parts = rows; f.n_cks = n_cks; f.n_rows = jit_part_rows(w, n_cks); f.n_saves = std::max(1u, j.n_saves);
     for (uint32_t k = 0; k < j.n_saves && k < (uint32_t)MAX_TICK_SAVES; ++k) f.save_len[k] = j.save_len[k];
     f.out = w->d_results + 2 * (uint64_t)res;
     if (w->dev_results_dst && res >= w->dev_results_first) f.out2 = w->dev_results_dst + 2 * (uint64_t)(res - w->dev_results_first);
@@ -340,7 +364,7 @@ struct FoldPlan { FoldRoute route = FoldRoute::None; uint64_t rows_off = 0, id =
 // The route AND its room in the pinned ring, in this order: fold-forward's, else self-fold's, else the host fold's; an allocation that fails falls through to the next route
 FoldPlan fold_route_choose(ggrs_world* w, const GgrsJitArgs& j, uint32_t g, uint32_t n_cks, bool launch, bool wait, bool spawn_follows) {
     FoldPlan p; p.split = (g + FF_CHUNK - 1u) / FF_CHUNK;                      // chunks of <= 1024 entries per row: one fold-forward workgroup each
-    p.rows_n = j.n_saves * (n_cks + 1); p.nvals = p.rows_n * p.split;
+    p.rows_n = j.n_saves * jit_part_rows(w, n_cks); p.nvals = p.rows_n * p.split;
     const bool big = launch && j.n_saves && !w->device_results_only && !w->dev_spawn && g > (uint32_t)w->knobs.fold_forward_min_wgs && w->d_ff_rows[0];
     // a BLOCKING call of that size: the launch folds its own rows (self-fold: its fold workgroups read the tile workgroups' tagged cells as they arrive) -- no k_gen_finalize
     // between the kernel and the caller.  Not beside a pending fold-forward (the role folds one set of rows), not with depth-parallel roles (plain grids only),
@@ -374,14 +398,14 @@ void fold_route_setup(ggrs_world* w, GgrsJitArgs& j, FoldPlan& p, uint32_t g) {
 int fold_route_record(ggrs_world* w, const GgrsJitArgs& j, const FoldPlan& p, uint32_t g, uint32_t n_cks, uint32_t res, bool wait, uint32_t members = 1) {
     switch (p.route) {
     case FoldRoute::Forward: case FoldRoute::Self: {
-        ggrs_world::HostFold f = make_host_fold(j, res, p.split, n_cks, 1u, p.rows_off);   // (the host XORs / adds the row's chunks)
+        ggrs_world::HostFold f = make_host_fold(w, j, res, p.split, n_cks, 1u, p.rows_off);   // (the host XORs / adds the row's chunks)
         if (p.route == FoldRoute::Self) { f.ff_id = p.id; f.ff_seq = p.seq; w->folds.push_back(f); break; }
         f.ff_id = w->ff_next_id++; f.ff_seq = (0xA5ull << 56) | ++w->ff_seq;      // (a tag no live count and -- but for 2^-64 -- no hash equals)
         memset(w->h_rows + p.rows_off, 0, (size_t)p.nvals * 16);                    // the {value, tag} cells: whatever an earlier fold left there is gone
         w->folds.push_back(f); ggrs_world::FfPending& pn = w->ff_pending;
         pn.valid = true; pn.id = f.ff_id; pn.seq = f.ff_seq; pn.buf = p.buf; pn.nvals = p.nvals; pn.g = g; pn.stride = 1; pn.istride = p.rows_n; pn.split = p.split; pn.out_off = p.rows_off;
         break; }
-    case FoldRoute::Host: w->folds.push_back(make_host_fold(j, res, g, n_cks, members, p.rows_off)); break;
+    case FoldRoute::Host: w->folds.push_back(make_host_fold(w, j, res, g, n_cks, members, p.rows_off)); break;
     case FoldRoute::Finalize: {
         GenFinArgs f = make_gen_fin(w, j, g, n_cks, res);   // one row per workgroup
         arm_spin(w, f, j.n_saves * members, wait);
@@ -868,6 +892,7 @@ int run_request_groups_gen(ggrs_world* w, const ggrs_request* reqs, uint32_t n, 
             if (w->has_effects) attach_effects(w, j);
             const bool applies = launch && w->has_effects && j.n_steps;
             if (launch) {
+                if (j.dp_s) ++w->dp_groups;
                 hipFunction_t fn = jit_spec_for(w, j);
                 if (!fn) fn = w->jit_fn;
                 // nothing is queued behind this kernel when its rows are folded later (or there is nothing to fold) and no spawn system follows:
@@ -953,6 +978,9 @@ int validate_branch_step(ggrs_world* w, const ggrs_branch_step& st) {
     // a retained block's presence masks are decided by the branch's own versions, which say nothing of what the systems inserted or removed: not offered in this version
     if (w->has_commands && (st.flags & (GGRS_BRANCH_RETAIN_NEWEST | GGRS_BRANCH_RETAIN_ALL)))
         return w->fail(GGRS_E_INVALID, "GGRS_BRANCH_RETAIN_* is not available for worlds with command bindings (ggrs_hip_add_custom_system_commands): run the branch step without retention, or use ggrs_hip_fanout_step");
+    // a retained block would need its resource cell kept per member, and an adoption the record of which cell is current: not offered in this version
+    if (w->has_resources && (st.flags & (GGRS_BRANCH_RETAIN_NEWEST | GGRS_BRANCH_RETAIN_ALL)))
+        return w->fail(GGRS_E_INVALID, "GGRS_BRANCH_RETAIN_* is not available for worlds with device resources (ggrs_hip_register_resource): run the branch step without retention, or use ggrs_hip_fanout_step");
     if (w->dev_spawn) return w->fail(GGRS_E_INVALID, "branch steps are not available for worlds whose systems spawn on the device (every launch is one cooperative grid): use ggrs_hip_fanout_step");
     if (st.n_branches == 0 || st.n_branches > BRANCH_MAX) return w->fail(GGRS_E_INVALID, "a branch step holds 1..%u branches, not %u", BRANCH_MAX, st.n_branches);
     const uint32_t S = (st.flags & GGRS_BRANCH_SAVE_LAST) ? st.n_frames : st.n_frames - 1;
@@ -1128,7 +1156,7 @@ int run_branch_step(ggrs_world* w, const ggrs_branch_step& st, uint32_t res_firs
     for (Block* d : touched) d->dirty_len = std::max(src.dirty_len, max_len);
     // ---- one launch for all members, one k_gen_finalize for all their Saves
     const uint32_t g = jit_geometry(w, j, cover);
-    const uint64_t parts_need = (uint64_t)B * std::max(1u, S) * (n_cks + 1) * g;
+    const uint64_t parts_need = (uint64_t)B * std::max(1u, S) * jit_part_rows(w, n_cks) * g;
     if (parts_need > w->branch_parts_cap) {
         if (w->d_branch_parts) { HIPCHK(w, hipStreamSynchronize(w->stream)); (void)hipFree(w->d_branch_parts); w->d_branch_parts = nullptr; w->branch_parts_cap = 0; }
         HIPCHK(w, hipMalloc((void**)&w->d_branch_parts, parts_need * 8));

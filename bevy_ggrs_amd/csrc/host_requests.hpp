@@ -329,7 +329,7 @@ std::string custom_source(const ggrs_world* w, const ggrs_world::Custom& c, cons
     snprintf(buf, sizeof buf, "static_assert(sizeof(GgrsCustomArgs) == %zu, \"host/device argument block mismatch\");\n", sizeof(GgrsCustomArgs));
     s += buf;
     s += GGRS_FRAME_TEXT;
-    s += entity_text(c.n_fx != 0, c.n_peer != 0, c.n_cmd != 0, false);   // (a system with peer, effect or command bindings only ever RUNS inside the generated kernel: here its text is compiled against an empty view, an empty inbox and unset opt words)
+    s += entity_text(c.n_fx != 0, c.n_peer != 0, c.n_cmd != 0, false, c.n_res != 0);   // (a system with peer, effect or command bindings only ever RUNS inside the generated kernel: here its text is compiled against an empty view, an empty inbox and unset opt words)
     if (c.n_cmd) s += cmd_entity_typedef(w, c);
     s += "#line 1 \"ggrs_system\"\n";
     s += user;
@@ -579,7 +579,7 @@ int ff_flush(ggrs_world* w) {
     ggrs_world::FfPending& p = w->ff_pending;
     if (!p.valid) return GGRS_OK;
     FfArgs f; memset(&f, 0, sizeof f);
-    f.rows = w->d_ff_rows[p.buf]; f.out = w->d_rows + p.out_off; f.seq = p.seq; f.nvals = p.nvals / p.split; f.g = p.g; f.stride = p.stride; f.istride = p.istride; f.nc1 = w->cks_args.n_cks + 1; f.split = p.split;
+    f.rows = w->d_ff_rows[p.buf]; f.out = w->d_rows + p.out_off; f.seq = p.seq; f.nvals = p.nvals / p.split; f.g = p.g; f.stride = p.stride; f.istride = p.istride; f.nc1 = jit_part_rows(w, w->cks_args.n_cks); f.cnt_row = w->cks_args.n_cks; f.split = p.split;
     hipLaunchKernelGGL(k_ff_fold, dim3(p.nvals), dim3(TPB), 0, w->stream, f);
     HIPCHK(w, hipGetLastError());
     w->ff_done_id = p.id; p.valid = false;
@@ -592,7 +592,7 @@ int ff_flush(ggrs_world* w) {
 int run_host_folds(ggrs_world* w, uint32_t n) {
     for (; n && !w->folds.empty(); --n) {
         const ggrs_world::HostFold f = w->folds.front(); w->folds.pop_front();
-        const uint32_t nc = f.n_cks + 1;
+        const uint32_t nc = f.n_rows;                                // the components' rows, the live count, and -- device resources -- their checksum part
         if (f.ff_id) {
             // the values arrive with the launch (or k_ff_fold) that follows this group's on the stream
             if (f.ff_id > w->ff_done_id) { const int rc = ff_flush(w); if (rc) return rc; }
@@ -612,6 +612,7 @@ int run_host_folds(ggrs_world* w, uint32_t n) {
                 for (uint32_t c = 0; c < nc; ++c) {
                     const uint64_t* row = w->h_rows + f.rows_off + ((uint64_t)(m * f.n_saves + sv) * nc + c) * f.g * vs;
                     if (c == f.n_cks) { uint64_t sum = 0; for (uint32_t t = 0; t < f.g; ++t) sum += row[(size_t)t * vs]; total ^= sea_pair(sum, f.save_len[sv]); }
+                    else if (c > f.n_cks) { uint64_t x = 0; for (uint32_t t = 0; t < f.g; ++t) x ^= row[(size_t)t * vs]; total ^= x; }      // ResourceChecksumPlugin's part(s): already hashed, XORed in as they are (checksum.rs:94)
                     else { uint64_t x = 0; for (uint32_t t = 0; t < f.g; ++t) x ^= row[(size_t)t * vs]; total ^= sea_one(x); }
                 }
                 uint64_t* out = w->h_results + 2 * (uint64_t)(f.res_slot + m * f.n_saves + sv);
@@ -642,7 +643,7 @@ bool rows_ring_alloc(ggrs_world* w, uint64_t need, uint64_t* off) {
 bool host_fold_rows(ggrs_world* w, uint32_t g, uint32_t n_saves, uint32_t n_cks, uint32_t members, uint64_t* off, bool blocking = false) {
     if (!w->h_rows || w->device_results_only || w->dev_spawn || !n_saves) return false;      // (device-decided spawns: RollbackOrdered::len at each Save is only known on the device -- k_gen_finalize)
     if (blocking ? g > HOST_FOLD_MAX_WGS_BLOCKING : g > (uint32_t)w->knobs.fold_forward_min_wgs) return false;
-    return rows_ring_alloc(w, (uint64_t)g * n_saves * (n_cks + 1) * members, off);
+    return rows_ring_alloc(w, (uint64_t)g * n_saves * jit_part_rows(w, n_cks) * members, off);
 }
 
 // Spawns decided on the device: RollbackOrdered::len of the live world as the last launch left it (pinned), and what went wrong inside a launch

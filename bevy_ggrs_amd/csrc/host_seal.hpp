@@ -163,6 +163,18 @@ int commands_validate(ggrs_world* w) {
     if (!w->knobs.tick_jit) return w->fail(GGRS_E_INVALID, "command bindings need the generated request-group kernel, which this world does not have: disabled (GGRS_TICK_JIT=0)");
     return GGRS_OK;
 }
+// Device resources (ggrs_hip_register_resource): what the first version refuses.  A resource system touches no component and an entity system only READS a resource,
+// so there is no registration-order rule.  After build_layout; no device needed -- a GGRS_WORLD_LAYOUT_ONLY world is checked by ggrs_hip_generated_kernel_source.
+int resources_validate(ggrs_world* w) {
+    if (!world_has_resources(w)) return GGRS_OK;
+    const char* nm = w->resources[0].name.c_str();
+    const JitNeeds need = jit_needs(w);
+    if (need.marks) return w->fail(GGRS_E_INVALID, "device resources ('%s', ggrs_hip_register_resource) are not available in a world that keeps RollbackDespawned markers (a system that can call despawn_rollback(), or names the `kill` field)", nm);
+    if (need.devspawn) return w->fail(GGRS_E_INVALID, "device resources ('%s', ggrs_hip_register_resource) are not available in a world that spawns on the device with e.spawn(n) (GGRS_SPAWN_PAYLOAD_PARENT)", nm);
+    if (w->flags & (GGRS_WORLD_NO_GROUPS | GGRS_WORLD_UNFUSED)) return w->fail(GGRS_E_INVALID, "device resources ('%s', ggrs_hip_register_resource) need the generated request-group kernel, which a GGRS_WORLD_NO_GROUPS / GGRS_WORLD_UNFUSED world does not have", nm);
+    if (!w->knobs.tick_jit) return w->fail(GGRS_E_INVALID, "device resources ('%s', ggrs_hip_register_resource) need the generated request-group kernel, which this world does not have: disabled (GGRS_TICK_JIT=0)", nm);
+    return GGRS_OK;
+}
 int seal(ggrs_world* w) {
     if (w->layout_only) return w->fail(GGRS_E_NO_DEVICE, "GGRS_WORLD_LAYOUT_ONLY world: there is no device behind it");
     if (w->sealed) return GGRS_OK;
@@ -241,6 +253,8 @@ int seal_impl(ggrs_world* w) {
     { const int prc = peers_validate(w); if (prc) return prc; }
     { const int frc = effects_validate(w); if (frc) return frc; }
     { const int crc = commands_validate(w); if (crc) return crc; }
+    { const int rrc = resources_validate(w); if (rrc) return rrc; }
+    w->has_resources = world_has_resources(w);
     w->has_peers = world_has_peers(w);
     w->has_effects = world_has_effects(w);
     w->has_commands = world_has_commands(w);
@@ -286,7 +300,7 @@ int seal_impl(ggrs_world* w) {
         if (w->jit_fn) {
             for (size_t i = 0; i < w->systems.size(); ++i) {
                 const ggrs_system_desc& d = w->systems[i];
-                w->jit_reads_inputs |= d.kind == GGRS_SYS_CUSTOM || d.kind == GGRS_SYS_BOX_MOVE || d.kind == GGRS_SYS_SPAWN_CUSTOM;
+                w->jit_reads_inputs |= d.kind == GGRS_SYS_CUSTOM || d.kind == GGRS_SYS_BOX_MOVE || d.kind == GGRS_SYS_SPAWN_CUSTOM || d.kind == GGRS_SYS_RESOURCE;
                 w->jit_marks |= (d.kind == GGRS_SYS_CUSTOM && w->customs[d.comp[0]].may_defer) || (d.kind == GGRS_SYS_SAT_SUB_DESPAWN && d.iparam[1] == GGRS_DESPAWN_ROLLBACK);
                 if (d.kind == GGRS_SYS_BOX_MOVE) w->jit_box_sys = (int)i;
             }
@@ -308,6 +322,8 @@ int seal_impl(ggrs_world* w) {
         return w->fail(GGRS_E_INVALID, "effect bindings (ggrs_hip_add_custom_system_effects) need the generated request-group kernel, which this world does not have: %s", w->jit_status.c_str());
     if (w->has_commands && !w->gen_ok)
         return w->fail(GGRS_E_INVALID, "command bindings (ggrs_hip_add_custom_system_commands) need the generated request-group kernel, which this world does not have: %s", w->jit_status.c_str());
+    if (w->has_resources && !w->gen_ok)
+        return w->fail(GGRS_E_INVALID, "device resources ('%s', ggrs_hip_register_resource) need the generated request-group kernel, which this world does not have: %s", w->resources[0].name.c_str(), w->jit_status.c_str());
     for (auto& sd : w->systems) if (sd.kind == GGRS_SYS_SPAWN_CUSTOM && !(w->gen_ok && w->jit_spawn_sys >= 0))
         return w->fail(GGRS_E_INVALID, "a user-written spawn system (ggrs_hip_add_spawn_system) runs inside the generated request-group kernel, which this world does not have "
                                        "(or the schedule holds a second spawn system): %s", w->jit_status.c_str());
@@ -384,12 +400,20 @@ int seal_impl(ggrs_world* w) {
         HIPCHK(w, hipMemsetAsync(w->live.ptr + w->off_tags, 0, tag_bytes, w->stream));
         for (auto& b : w->slots) HIPCHK(w, hipMemsetAsync(b.ptr + w->off_tags, 0, tag_bytes, w->stream));
     }
+    if (w->has_resources) {
+        // init_resource: the initial values go into the live block's first cell (every block's record says cell 0; the headers were zeroed above)
+        uint8_t cell[RES_CELL_BYTES] = {};
+        for (auto& r : w->resources) memcpy(cell + r.off, r.init.data(), r.init.size());
+        w->live.res_cell = 0; for (auto& b : w->slots) b.res_cell = 0;
+        HIPCHK(w, hipMemcpyAsync(w->live.ptr + RES_CELL_OFF, cell, sizeof cell, hipMemcpyHostToDevice, w->stream));
+        HIPCHK(w, hipStreamSynchronize(w->stream));                    // (the host buffer dies here)
+    }
     if (!units.empty()) HIPCHK(w, hipMemcpyAsync(w->d_units, units.data(), units.size() * sizeof(UnitDesc), hipMemcpyHostToDevice, w->stream));
     if (w->gen_ok) {
         // k_gen_finalize's row buffer [saves][n_cks + 1][one row per 256-slot workgroup]; then the two row buffers of the fold-forward path
         // ([cap_saves][n_cks + 1][one row per workgroup] each, used alternately by consecutive launches)
-        const size_t bytes = align_up((size_t)w->gen_parts_saves * (w->cks_args.n_cks + 1) * w->gen_part_stride * 8, ALIGN);
-        const size_t ff_bytes = align_up((size_t)MAX_TICK_SAVES * (w->cks_args.n_cks + 1) * w->gen_part_stride * 8, ALIGN);
+        const size_t bytes = align_up((size_t)w->gen_parts_saves * jit_part_rows(w, w->cks_args.n_cks) * w->gen_part_stride * 8, ALIGN);      // (a world with device resources: one row more per Save)
+        const size_t ff_bytes = align_up((size_t)MAX_TICK_SAVES * jit_part_rows(w, w->cks_args.n_cks) * w->gen_part_stride * 8, ALIGN);
         HIPCHK(w, hipMalloc((void**)&w->d_gen_parts, bytes + 2 * ff_bytes));
         uint8_t* const base = reinterpret_cast<uint8_t*>(w->d_gen_parts);
         w->d_ff_rows[0] = reinterpret_cast<uint64_t*>(base + bytes);

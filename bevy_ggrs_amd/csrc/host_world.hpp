@@ -42,7 +42,11 @@ struct Block {                           // one packed state block in the arena
     uint64_t len = 0;                    // host mirror of Header::len for ring slots
     std::vector<ver_t> ver;              // per column: the version of the bytes this block holds (VER_NONE: unknown)
     uint64_t tag_ok = 0;                 // bit c: the block's VALUE TAGS of column c (one per 64-slot unit, in the block's tag region) describe its bytes -- see ggrs_world::vtags
+    uint32_t res_cell = 0;               // device resources: which of the block's two cells holds its resource words (RES_CELL_OFF + res_cell * RES_CELL_BYTES; host_groups.hpp launch_jit)
 };
+// device resources (ggrs_hip_register_resource): two cells of GGRS_RESOURCE_MAX_BYTES inside the unused part of every block's 256-byte header (Header uses the first 40)
+constexpr uint32_t RES_CELL_OFF = 64, RES_CELL_BYTES = 64, RES_CELL_IDX_OFF = 40;     // RES_CELL_IDX_OFF: a u32 right behind struct Header -- the index of the block's current cell, written with the cell
+static_assert(RES_CELL_BYTES == GGRS_RESOURCE_MAX_BYTES && RES_CELL_OFF + 2 * RES_CELL_BYTES <= 256, "two resource cells fit the header behind struct Header");
 
 struct EventPair { hipEvent_t a, b; uint32_t cls; };
 struct JitEntry;                         // kernel_gen.hpp: a cached generated module
@@ -168,8 +172,16 @@ struct ggrs_world {
         // command bindings (ggrs_hip_add_custom_system_commands): whole components of its OWN entity the system sees as Option<&mut C> (e.has / e.opt_*) and,
         // with GGRS_CMD_INSERT / GGRS_CMD_REMOVE in the flags, may insert or remove
         uint32_t n_cmd = 0, ccomp[GGRS_COMMAND_MAX_BINDINGS] = {}, cflags[GGRS_COMMAND_MAX_BINDINGS] = {};
+        // resource bindings (ggrs_hip_add_custom_system_resources): words of the world's device resources the system reads through e.res_*(j)
+        uint32_t n_res = 0, rres[GGRS_RESOURCE_MAX_BINDINGS] = {}, rword[GGRS_RESOURCE_MAX_BINDINGS] = {};
     };
     std::vector<Custom> customs;
+    // DEVICE RESOURCES (ggrs_hip_register_resource): a few 4- or 8-byte words per world, carried by every wave of the generated kernel in wave-uniform registers.
+    // off: the resource's first byte inside a cell (8-byte resources first, then 4-byte ones: no padding); reg: the number of its first word among the kernel's r<k>
+    struct Resource { std::string name; uint32_t word_bytes = 4, n_words = 0, off = 0, reg = 0; std::vector<uint8_t> init; bool checksummed = false; std::vector<uint32_t> cks_words; };
+    std::vector<Resource> resources;
+    struct ResSys { std::string name, source; uint32_t n_bind = 0, res[GGRS_RESOURCE_MAX_BINDINGS] = {}, word[GGRS_RESOURCE_MAX_BINDINGS] = {}; };   // GGRS_SYS_RESOURCE: systems[i].comp[0] indexes this
+    std::vector<ResSys> res_systems;
     // THE PEER VIEW of a world with peer bindings (allocated at seal, filled by k_publish_peers ahead of every request group that holds an AdvanceWorld): one LINEAR
     // array of cap_pad words per distinct peer-bound column (a gather address is base + slot x word bytes; state blocks are tile-major) and one visibility bit per
     // slot: alive AND every peer-bound component present.  The tick launch may rewrite its source block in place, so it never gathers from a block it writes
@@ -190,6 +202,8 @@ struct ggrs_world {
     } fx_inbox;
     bool has_effects = false;            // some system has effect bindings (set at seal: effect_cols)
     bool has_commands = false;           // some system has command bindings (set at seal)
+    bool has_resources = false;          // the world has device resources (ggrs_hip_register_resource; set at seal)
+    uint64_t dp_groups = 0;              // request groups launched with depth-parallel roles so far (kernel_info "depth_parallel_roles")
     uint64_t cmd_mut_comps = 0;          // bit c = some system may insert or remove component c: its mask and columns get fresh versions with every AdvanceWorld (set at seal)
     struct SpawnSys {                    // GGRS_SYS_SPAWN_CUSTOM: a user-written spawner (ggrs_hip_add_spawn_system; systems[i].comp[0] indexes this)
         std::string name, source;
@@ -349,7 +363,7 @@ struct ggrs_world {
     // device-mapped host memory and the HOST finishes each Save (XOR of g rows + three hashes) when the batch is collected.  Fold-forward
     // groups (ff_id != 0): g == 1 -- the rows were folded on the device, the pinned ring holds one value per (Save, part) followed by one tag
     // each; collect waits for the tags (ff_seq) before it hashes.
-    struct HostFold { uint32_t res_slot, n_saves, g, n_cks, members; uint64_t rows_off; uint64_t save_len[16]; uint64_t ff_id, ff_seq; };   // save_len[k]: RollbackOrdered::len at Save k (a fused spawn grows it inside a group)
+    struct HostFold { uint32_t res_slot, n_saves, g, n_cks, members, n_rows; uint64_t rows_off; uint64_t save_len[16]; uint64_t ff_id, ff_seq; };   // save_len[k]: RollbackOrdered::len at Save k (a fused spawn grows it inside a group)
     std::deque<HostFold> folds;          // in submission order; a PendingBatch owns the next n_folds of them
     uint64_t* h_rows = nullptr; uint64_t* d_rows = nullptr; uint64_t rows_cap = 0, rows_used = 0, rows_tail = 0;   // ring of partial rows
     hipEvent_t batch_ev = nullptr; bool batch_ev_attached = false;   // enqueue: the batch's event, offered to the list's last kernel launch (launch_jit)
@@ -578,6 +592,14 @@ inline uint64_t rows_bytes_hot(const ggrs_world* w) {
     return b;
 }
 inline bool world_has_effects(const ggrs_world* w) { for (auto& c : w->customs) if (c.n_fx) return true; return false; }
+inline bool world_has_resources(const ggrs_world* w) { return !w->resources.empty(); }
+inline uint32_t res_total_bytes(const ggrs_world* w) { uint32_t b = 0; for (auto& r : w->resources) b += r.word_bytes * r.n_words; return b; }
+// where each resource sits inside a cell and which registers of the generated kernel hold it: after every registration
+inline void res_layout(ggrs_world* w) {
+    uint32_t off = 0, reg = 0;
+    for (uint32_t wb : {8u, 4u}) for (auto& r : w->resources) if (r.word_bytes == wb) { r.off = off; off += wb * r.n_words; }
+    for (auto& r : w->resources) { r.reg = reg; reg += r.n_words; }
+}
 inline bool world_has_commands(const ggrs_world* w) { for (auto& c : w->customs) if (c.n_cmd) return true; return false; }
 // the components some system may insert or remove (a declared GGRS_CMD_INSERT / GGRS_CMD_REMOVE), one bit each: their presence bits change inside the generated kernel
 inline uint64_t world_cmd_mut_comps(const ggrs_world* w) {

@@ -208,8 +208,35 @@ Hiprtc& hiprtc_for(const ggrs_world* w) {
     "    __device__ unsigned char& opt_u8(int j, int k) { return *reinterpret_cast<unsigned char*>(&opt[oi_(j, k)]); }\n" \
     "    __device__ void insert(int j) __attribute__((enable_if(j >= 0 && j < 4 && ((GGRS_IM >> j) & 1u), \"e.insert(j): command binding j (a constant) must be declared with GGRS_CMD_INSERT\"))) { has_ |= 1u << j; }\n" \
     "    __device__ void remove(int j) __attribute__((enable_if(j >= 0 && j < 4 && ((GGRS_RM >> j) & 1u), \"e.remove(j): command binding j (a constant) must be declared with GGRS_CMD_REMOVE\"))) { has_ &= ~(1u << j); }\n"
-inline std::string entity_text(bool effects, bool peers, bool commands, bool default_typedef = true) {
+// ... in a world with device resources (ggrs_hip_register_resource): e.res_*(j) returns resource binding j of the system (ggrs_hip_add_custom_system_resources) as it
+// stands at that point of the frame -- a VALUE, copied in from the kernel's wave-uniform registers in front of the call; nothing is written back.  Worlds without
+// resources keep their entity text as it is.
+#define GGRS_RES_MEMBERS_TEXT \
+    "    ggrs_u64 rs_[8] = {};                                 /* the system's resource bindings, by value (Res<R>) */\n" \
+    "    __device__ ggrs_u32 res_u32(int j) const { return (ggrs_u32)rs_[j]; }\n" \
+    "    __device__ int res_i32(int j) const { return (int)(ggrs_u32)rs_[j]; }\n" \
+    "    __device__ float res_f32(int j) const { return __uint_as_float((ggrs_u32)rs_[j]); }\n" \
+    "    __device__ ggrs_u64 res_u64(int j) const { return rs_[j]; }\n"
+// What a resource system sees (ggrs_hip_add_resource_system): references to its bound words.  A TEMPLATE over what the system declared -- GGRS_RNB bindings,
+// GGRS_RW8: bit i = binding i is an 8-byte word -- so that an index it did not bind, or the other width, finds no member and does not compile (enable_if, as
+// e.insert / e.remove); every system's source is compiled against its own instance (a `typedef ... GgrsResources;` in front of it).
+#define GGRS_RESOURCES_TEXT \
+    "template <unsigned GGRS_RNB, unsigned GGRS_RW8> struct GgrsResourcesT {\n" \
+    "    ggrs_u64 w[8];\n" \
+    "    __device__ ggrs_u32& u32(int i) __attribute__((enable_if(i >= 0 && i < (int)GGRS_RNB && !((GGRS_RW8 >> i) & 1u), \"r.u32(i): i (a constant) must be a bound 4-byte resource word\"))) { return *reinterpret_cast<ggrs_u32*>(&w[i]); }\n" \
+    "    __device__ int& i32(int i) __attribute__((enable_if(i >= 0 && i < (int)GGRS_RNB && !((GGRS_RW8 >> i) & 1u), \"r.i32(i): i (a constant) must be a bound 4-byte resource word\"))) { return *reinterpret_cast<int*>(&w[i]); }\n" \
+    "    __device__ float& f32(int i) __attribute__((enable_if(i >= 0 && i < (int)GGRS_RNB && !((GGRS_RW8 >> i) & 1u), \"r.f32(i): i (a constant) must be a bound 4-byte resource word\"))) { return *reinterpret_cast<float*>(&w[i]); }\n" \
+    "    __device__ ggrs_u64& u64(int i) __attribute__((enable_if(i >= 0 && i < (int)GGRS_RNB && ((GGRS_RW8 >> i) & 1u), \"r.u64(i): i (a constant) must be a bound 8-byte resource word\"))) { return w[i]; }\n" \
+    "};\n"
+inline std::string res_system_typedef(const ggrs_world* w, const ggrs_world::ResSys& rs) {
+    uint32_t w8 = 0;
+    for (uint32_t b = 0; b < rs.n_bind; ++b) if (rs.res[b] < w->resources.size() && w->resources[rs.res[b]].word_bytes == 8) w8 |= 1u << b;
+    char b[128]; snprintf(b, sizeof b, "typedef ::GgrsResourcesT<%uu, 0x%xu> GgrsResources;\n", rs.n_bind, w8);
+    return b;
+}
+inline std::string entity_text(bool effects, bool peers, bool commands, bool default_typedef = true, bool resources = false) {
     std::string t = effects ? GGRS_ENTITY_EFFECTS_TEXT : (peers ? GGRS_ENTITY_PEERS_TEXT : GGRS_ENTITY_TEXT);
+    if (resources) t.insert(t.rfind("};\n"), GGRS_RES_MEMBERS_TEXT);
     if (!commands) return t;
     const std::string head = "struct GgrsEntity {\n";
     const size_t at = t.find(head), end = t.rfind("};\n");
@@ -579,6 +606,9 @@ struct GgrsJitArgs {
     // THE INBOX of a world with effect bindings (host_world.hpp EffectInbox; present only in such worlds): the linear arrays of the distinct effect columns and the
     // len of the group's source block -- RollbackOrdered::len at the start of the group's one AdvanceWorld: a send to a slot at or beyond it is dropped
     unsigned char* fx_col[8]; ggrs_u64 fx_len;
+    // DEVICE RESOURCES (host_world.hpp Resource; present only in worlds that have some): res_src = the CURRENT cell of the group's source block, read with scalar loads;
+    // res_alt = the byte offset, inside a block, of the cell a store into the SOURCE block goes to -- its other cell; every other block takes RES_CELL_OFF (launch_jit)
+    const unsigned char* res_src; ggrs_u32 res_alt;
     ggrs_u32 cached_saves;                           // with nt: bit i = Save i is stored through the L2 all the same (the snapshot the NEXT group is expected to load)
     ggrs_u32 ff_blocks, ff_nvals, ff_g, ff_stride, ff_istride, ff_split, ff_self;   // entry e of row r: ff_rows[r * ff_stride + e * ff_istride]
     ggrs_u32 dt_bits[24], aux_bits[24]; int step_frame[24], step_confirmed[24]; ggrs_u32 spawn_count[24];
@@ -605,7 +635,7 @@ struct JitLayout {
     struct Member { uint32_t bytes = 0, save_dst = 0, save_rows = 0, save_len = 0, spawn_payload = 0, spawn_first = 0, live = 0, live_rows = 0, marks_dst = 0, save_pmask = 0, live_pmask = 0,
                     spawn_count = 0, n_inputs = 0, inputs = 0, save_tagok = 0, live_tagok = 0; } m;
 };
-struct JitNeeds { bool spawn, inputs, marks, box, vtags, devspawn, devstream, nr, peers, effects, commands; };
+struct JitNeeds { bool spawn, inputs, marks, box, vtags, devspawn, devstream, nr, peers, effects, commands, res; };
 // the distinct peer-bound columns of the world in order of first use (systems in registration order, peer bindings in order) and the components they belong to;
 // returns how many there are (more than GGRS_PEER_MAX_COLUMNS: only the first ones are written -- peers_validate refuses such a world)
 inline uint32_t peer_cols(const ggrs_world* w, uint32_t* cols, uint32_t* n_pres = nullptr, uint32_t* pres = nullptr) {
@@ -670,6 +700,7 @@ JitLayout jit_layout(const ggrs_world* w) {
         F1("ggrs_u64*", gone, need.nr);
         FA("const unsigned char*", pv_col, n_pv, need.peers); F1("const ggrs_u64*", pv_vis, need.peers); F1("ggrs_u64", pv_len, need.peers);
         FA("unsigned char*", fx_col, n_fx, need.effects); F1("ggrs_u64", fx_len, need.effects);
+        F1("const unsigned char*", res_src, need.res);
         FA("unsigned char*", save_dst, S, true); FA("ggrs_u64", save_rows, S, true); FA("ggrs_u64", save_len, S, true);
         FS("const unsigned char*", spawn_payload, need.spawn); FS("ggrs_u64", spawn_first, need.spawn);
         FA("int", save_frame, S, true); FA("ggrs_u32", save_pmask, S, true);
@@ -679,6 +710,7 @@ JitLayout jit_layout(const ggrs_world* w) {
         F1("ggrs_u64*", sp_sums, resident); F1("ggrs_u32", sp_epoch, need.devspawn); F1("unsigned char*", sp_prec, resident); F1("ggrs_u64*", sp_link, resident);
         F1("ggrs_u64*", sp_len, need.devspawn); F1("ggrs_u64", sp_cap, need.devspawn);
         F1("ggrs_u64*", sp_ctl, need.devstream); F1("ggrs_u64*", sp_desc, need.devstream); F1("ggrs_u64*", sp_recs, need.devstream); F1("ggrs_u64", sp_ticket_base, need.devstream);
+        F1("ggrs_u32", res_alt, need.res);
         F1("ggrs_u32", n_units, true); F1("ggrs_u32", sp_tiles, need.devspawn); F1("ggrs_u32", vtags, need.vtags); F1("ggrs_u32", tag_base, need.vtags); F1("ggrs_u32", cached_saves, true); F1("ggrs_u32", ff_blocks, true); F1("ggrs_u32", ff_nvals, true); F1("ggrs_u32", ff_g, true); F1("ggrs_u32", ff_stride, true); F1("ggrs_u32", ff_istride, true); F1("ggrs_u32", ff_split, true); F1("ggrs_u32", ff_self, true);
         FS("ggrs_u32", dt_bits, true); FS("ggrs_u32", aux_bits, need.box); FS("int", step_frame, true); FS("int", step_confirmed, need.marks);
         FS("ggrs_u32", spawn_count, need.spawn);
@@ -840,6 +872,9 @@ uint64_t jit_hot_cols(const ggrs_world* w) {
     return m;
 }
 
+// partial rows per Save of a launch: one per checksummed component (XOR of the entity hashes), the live count, and -- in a world with device resources -- one more
+// that carries the resources' checksum part: written by one lane of the launch, XORed over the tiles like a component's row, and XORed into the frame's Checksum as it is
+inline uint32_t jit_part_rows(const ggrs_world* w, uint32_t n_cks) { return n_cks + 1u + (world_has_resources(w) ? 1u : 0u); }
 // The per-tile form of a world of ~100 k slots and more folds checksum values through per-lane LDS rows: 64 cells x 8 B per Save and checksummed component
 // (dynamic LDS, sized by the launch), one ds_xor per lane and Save, the rows folded across lanes once per workgroup -- instead of a
 // 12-step DPP ladder + a single-lane atomic per Save and component.  Small worlds keep the ladder: zeroing and folding the rows costs
@@ -884,7 +919,8 @@ inline uint64_t jit_marks_rec_frames_off(const ggrs_world* w) { return align_up(
 inline uint64_t jit_marks_rec_bytes(const ggrs_world* w) { return jit_marks_rec_frames_off(w) + align_up(w->cap_pad * 4, ALIGN); }
 // which optional parts of the argument block this world's kernel reads
 JitNeeds jit_needs(const ggrs_world* w) {
-    JitNeeds n{false, false, false, false, false, false, false, false, false, false, false};
+    JitNeeds n{false, false, false, false, false, false, false, false, false, false, false, false};
+    n.res = world_has_resources(w);
     n.commands = world_has_commands(w);
     n.peers = world_has_peers(w);
     n.effects = world_has_effects(w);
@@ -894,7 +930,7 @@ JitNeeds jit_needs(const ggrs_world* w) {
     n.spawn = jit_fused_spawn_system(w) >= 0;
     if (!n.devspawn) for (auto& c : w->comps) n.nr |= c.no_rollback;      // (branch steps are closed to worlds that spawn on the device: their kernel has no `gone` text)
     for (auto& d : w->systems) {
-        n.inputs |= d.kind == GGRS_SYS_CUSTOM || d.kind == GGRS_SYS_BOX_MOVE || d.kind == GGRS_SYS_SPAWN_CUSTOM;
+        n.inputs |= d.kind == GGRS_SYS_CUSTOM || d.kind == GGRS_SYS_BOX_MOVE || d.kind == GGRS_SYS_SPAWN_CUSTOM || d.kind == GGRS_SYS_RESOURCE;
         n.marks |= (d.kind == GGRS_SYS_CUSTOM && w->customs[d.comp[0]].may_defer) || (d.kind == GGRS_SYS_SAT_SUB_DESPAWN && d.iparam[1] == GGRS_DESPAWN_ROLLBACK);
         n.box |= d.kind == GGRS_SYS_BOX_MOVE;
     }
@@ -915,6 +951,7 @@ bool jit_covers(const ggrs_world* w) {
     for (auto& d : w->systems) {
         switch (d.kind) {
         case GGRS_SYS_PARTICLES_SPAWN: case GGRS_SYS_SPAWN_CUSTOM: break;
+        case GGRS_SYS_RESOURCE: if (d.comp[0] >= w->res_systems.size()) return false; break;      // touches no component
         case GGRS_SYS_PARTICLES_UPDATE: if (!rb(d.comp[0]) || !rb(d.comp[1])) return false; break;
         case GGRS_SYS_TTL_DESPAWN: case GGRS_SYS_ADD_U32: if (!rb(d.comp[0])) return false; break;
         case GGRS_SYS_SAT_SUB_DESPAWN: if (!rb(d.comp[0])) return false; break;
@@ -959,6 +996,7 @@ struct JitGen {
     // columns some system writes (a steady SaveWorld stores exactly these); those plus what steps and checksums read
     const uint64_t HOT, LOADHOT;
     std::vector<uint32_t> cks_comp; uint32_t n_cks = 0;              // checksummed components in id order (== w->cks_comp once sealed)
+    uint32_t n_rows = 1;                                             // partial rows per Save: the components' XORs, the live count and -- in a world with device resources -- the resources' checksum part
     bool lane_fold = false;
     bool any_strat = false;
     bool lds_inputs = false;                                         // user code indexes PlayerInputs (possibly by a handle it read from a component): the bytes go through LDS
@@ -970,9 +1008,10 @@ struct JitGen {
           IB(L.in_bytes), MAXP(L.max_players), IN_STRIDE(L.in_stride), OFF_ALIVE(w_->off_alive), OFF_DIS(w_->marks.off_disabled), OFF_DF(w_->marks.off_dframe),
           OFF_TAGS(w_->off_tags), TAGCOLS(w_->tag_cols), NTC(w_->n_tcols), TAG_ROW(w_->tag_row_bytes), HOT(jit_hot_cols(w_)), LOADHOT(HOT | jit_static_reads(w_)) {
         for (uint32_t c = 0; c < nc; ++c) if (rb(c) && strat(c)) any_strat = true;
-        for (auto& d : w->systems) lds_inputs |= d.kind == GGRS_SYS_SPAWN_CUSTOM || d.kind == GGRS_SYS_CUSTOM;
+        for (auto& d : w->systems) lds_inputs |= d.kind == GGRS_SYS_SPAWN_CUSTOM || d.kind == GGRS_SYS_CUSTOM || d.kind == GGRS_SYS_RESOURCE;
         for (uint32_t c = 0; c < nc; ++c) if (w->comps[c].checksummed) cks_comp.push_back(c);
         n_cks = (uint32_t)cks_comp.size();
+        n_rows = jit_part_rows(w, n_cks);
         lane_fold = jit_lane_fold(w, n_cks);
         for (uint32_t c = 0; c < nc; ++c) if (rb(c) && !strat(c)) for (uint32_t k = 0; k < w->comps[c].n_words; ++k) {
             const uint32_t wb = w->comps[c].word_bytes; wb_mask[wb == 1 ? 0 : wb == 2 ? 1 : wb == 4 ? 2 : 3] |= 1ull << col(c, k);
@@ -1046,7 +1085,8 @@ struct JitGen {
                                     "#define GGRS_SP_READ %uu                                                           // sp_desc[GGRS_SP_READ x tiles + tile]: that tile has read its starting len\n",
                          2u + (unsigned)MAX_TICK_SAVES, 2u * (unsigned)MAX_TICK_STEPS);
         s += GGRS_FRAME_TEXT;
-        s += entity_text(need.effects, need.peers, need.commands);
+        s += entity_text(need.effects, need.peers, need.commands, true, need.res);
+        if (need.res) s += GGRS_RESOURCES_TEXT;
         s += GGRS_COMPONENT_TEXT;
         s += GGRS_WORDS_TEXT;
         s += jit_layout_text(L);
@@ -1058,6 +1098,11 @@ struct JitGen {
             else
             sfmt(s, "namespace ggrs_sys_%zu {\n#line 1 \"%s\"\n", i, file_name(w->customs[i].name).c_str());
             s += w->customs[i].source;
+            s += "\n}\n";
+        }
+        for (size_t i = 0; i < w->res_systems.size(); ++i) {
+            sfmt(s, "namespace ggrs_res_sys_%zu {\n%s#line 1 \"%s\"\n", i, res_system_typedef(w, w->res_systems[i]).c_str(), file_name(w->res_systems[i].name).c_str());
+            s += w->res_systems[i].source;
             s += "\n}\n";
         }
         if (spawn_sys >= 0 && w->systems[spawn_sys].kind == GGRS_SYS_SPAWN_CUSTOM) {
@@ -1100,7 +1145,7 @@ struct JitGen {
                 "        }\n"
                 "        return;\n"
                 "    }\n"
-                "    const uint32_t bx = blockIdx.x - a.ff_blocks, gx = gridDim.x - a.ff_blocks;\n", n_cks + 1, n_cks);
+                "    const uint32_t bx = blockIdx.x - a.ff_blocks, gx = gridDim.x - a.ff_blocks;\n", n_rows, n_cks);
         sfmt(s,
                 "    // batch members (blockIdx.z) with records: what differs between the launch's groups comes from member z's record, the rest from the argument block\n"
                 "    const GGRS_K unsigned char* const mb = a.mtab ? (const GGRS_K unsigned char*)(unsigned long)(a.mtab + (uint64_t)blockIdx.z * %uull) : (const GGRS_K unsigned char*)0ul;\n"
@@ -1113,9 +1158,9 @@ struct JitGen {
                 "    __shared__ ggrs_u64 s_acc[16 * %u];\n"
                 "%s"
                 "    for (uint32_t i = tid; i < 16u * %uu; i += 256u) s_acc[i] = 0;\n",
-             L.m.bytes, n_cks + 1,
+             L.m.bytes, n_rows,
              need.vtags ? "    __shared__ ggrs_u64 s_skip;                                                // value tags, profiling: bytes this workgroup's Saves did not store\n    if (tid == 0) s_skip = 0;\n" : "",
-             n_cks + 1);
+             n_rows);
         if (lane_fold) sfmt(s, "    extern __shared__ ggrs_u64 s_lane[];                                  // [Save][checksummed component][lane]: a.n_saves * %u * 64 cells (dynamic LDS)\n"
                                "    for (uint32_t i = tid; i < a.n_saves * %uu; i += 256u) s_lane[i] = 0;\n", n_cks, n_cks * 64u);
         if (lds_inputs && IN_STRIDE)
@@ -1362,7 +1407,60 @@ struct JitGen {
         }
         return e.empty() ? std::string("0ull") : e;
     }
+    // device resources: word k of resource r is the wave-uniform register r<reg + k>, loaded ONCE per launch from the current cell of the group's source block through the
+    // constant address space (scalar loads, as member records are read) -- never from a location this launch writes (a.res_src / a.res_alt: launch_jit)
+    const char* rtype(const ggrs_world::Resource& r) const { return r.word_bytes == 8 ? "uint64_t" : "uint32_t"; }
+    void res_state() {
+        if (!need.res) return;
+        s += "    // DEVICE RESOURCES: wave-uniform registers, loaded once with scalar loads from the source block's current cell; every wave replays the resource systems itself\n"
+             "    const GGRS_K unsigned char* const rs_ = (const GGRS_K unsigned char*)(unsigned long)a.res_src;\n";
+        for (auto& r : w->resources) for (uint32_t k = 0; k < r.n_words; ++k)
+            sfmt(s, "    %s r%u = *(const GGRS_K %s*)(rs_ + %uu);                                  // %s word %u\n", rtype(r), r.reg + k, rtype(r), r.off + k * r.word_bytes, file_name(r.name).c_str(), k);
+    }
+    // the resource words into a block's cell, by the lane that writes the block's header: the SOURCE block takes its other cell, every other block the first
+    void res_store(const char* dst, const char* indent) {
+        if (!need.res) return;
+        sfmt(s, "%s{ unsigned char* const rc_ = %s + ((const unsigned char*)%s == a.src ? a.res_alt : %uu);\n", indent, dst, dst, RES_CELL_OFF);
+        for (auto& r : w->resources) for (uint32_t k = 0; k < r.n_words; ++k)
+            sfmt(s, "%s  *reinterpret_cast<%s*>(rc_ + %uu) = r%u;\n", indent, rtype(r), r.off + k * r.word_bytes, r.reg + k);
+        sfmt(s, "%s  *reinterpret_cast<uint32_t*>(%s + %uu) = (uint32_t)(rc_ - %s - %uu) / %uu;      // which cell is current, for a block that travels (ggrs_hip_adopt_live_state)\n", indent, dst, RES_CELL_IDX_OFF, dst, RES_CELL_OFF, RES_CELL_BYTES);
+        sfmt(s, "%s}\n", indent);
+    }
+    // a resource system (ggrs_hip_add_resource_system), at its position among the frame's systems, outside any liveness test: every wave runs it on the same values.
+    // What comes back is pinned into scalar registers again (the frame's inputs come through LDS and float work sits on the vector ALU: uniform values in vector registers)
+    void sys_resource(size_t i, const ggrs_system_desc& d) {
+        const ggrs_world::ResSys& rs = w->res_systems[d.comp[0]];
+        sfmt(s, "            {                                                                          // resource system %u\n"
+                "                ggrs_res_sys_%u::GgrsResources rr_;\n", d.comp[0], d.comp[0]);
+        for (uint32_t b = 0; b < 8; ++b) {
+            if (b < rs.n_bind) sfmt(s, "                rr_.w[%u] = r%u;\n", b, w->resources[rs.res[b]].reg + rs.word[b]); else sfmt(s, "                rr_.w[%u] = 0;\n", b);
+        }
+        sfmt(s, "                ggrs_res_sys_%u::ggrs_resource_system(rr_, fr%zu);\n", d.comp[0], i);
+        for (uint32_t b = 0; b < rs.n_bind; ++b) {
+            const ggrs_world::Resource& r = w->resources[rs.res[b]];
+            bool later = false;                                      // two bindings of one word: the last one wins, as for an entity's bound words
+            for (uint32_t q = b + 1; q < rs.n_bind; ++q) later |= rs.res[q] == rs.res[b] && rs.word[q] == rs.word[b];
+            if (later) continue;
+            if (r.word_bytes == 8) sfmt(s, "                r%u = uni64(rr_.w[%u]);\n", r.reg + rs.word[b], b);
+            else sfmt(s, "                r%u = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)rr_.w[%u]);\n", r.reg + rs.word[b], b);
+        }
+        s += "            }\n";
+    }
+    // the resources' checksum part of a Save (ResourceChecksumPlugin, resource_checksum.rs:63-83): per checksummed resource checksum_hasher() fed the chosen words in
+    // order, each with its own width; the parts XORed.  One lane of the launch, once per Save, with the plain SeaStream: into the workgroup's extra partial row
+    void res_checksum() {
+        if (!need.res) return;
+        sfmt(s, "            if (gu == 0 && lane == 0) {                                                // the resources' ChecksumPart(s), XORed: one lane of the launch\n"
+                "                uint64_t rp_ = 0ull;\n");
+        for (auto& r : w->resources) if (r.checksummed) {
+            s += "                { SeaStream st;";
+            for (uint32_t wi : r.cks_words) sfmt(s, " st.write(r%u, %uu);", r.reg + wi, r.word_bytes);
+            s += " rp_ ^= st.finish(); }\n";
+        }
+        sfmt(s, "                acc[%u] = rp_;\n            }\n", n_cks + 1);
+    }
     void unit_state() {
+        res_state();
         for (uint32_t k = 0; k < n_cks; ++k) if (spec_memo[k]) {
             const std::string tail = chunk_expr(w->comps[cks_comp[k]], cks_comp[k], 8, spec_bytes[k] - 8);
             sfmt(s, "    uint32_t mt%u = (uint32_t)(%s); uint64_t ma%u = a.n_saves ? sea_tail_folded(mt%u, %uull) : 0ull;   // memoised tail of checksum spec %u, with the finish's K2 ^ K3 ^ bytes folded in\n", k, tail.c_str(), k, k, spec_bytes[k], k);
@@ -1410,13 +1508,16 @@ struct JitGen {
         if (need.devstream) emit_sp_gate("                ", "dst");
         sfmt(s, "                if (%s) {\n"
                 "                    Header h; h.len = %s; h.frame = a.save_frame[si]; h.pad0 = 0; h.active = 0; h.checksum[0] = 0; h.checksum[1] = 0;\n"
-                "                    *reinterpret_cast<Header*>(dst) = h;\n"
-                "                }\n"
-                "            }\n", need.devstream ? "len_wr" : "gu == 0 && lane == 0", need.devspawn ? "cur_len" : (std::string("mb ? mb_u64(mb, ") + std::to_string(L.m.save_len) + "u + 8u * si) : a.save_len[si]").c_str());
+                "                    *reinterpret_cast<Header*>(dst) = h;\n",
+             need.devstream ? "len_wr" : "gu == 0 && lane == 0", need.devspawn ? "cur_len" : (std::string("mb ? mb_u64(mb, ") + std::to_string(L.m.save_len) + "u + 8u * si) : a.save_len[si]").c_str());
+        res_store("dst", "                    ");                    // device resources: stored with the snapshot, by the lane that writes its header
+        s += "                }\n"
+             "            }\n";
         if (need.devstream) s += "            if (len_wr) a.sp_len[2u + si] = cur_len;                                   // RollbackOrdered::len at this Save: k_gen_finalize's entity checksum and the host read it here\n";
         else if (need.devspawn) s += "            if (gu == 0 && lane == 0) a.sp_len[2u + si] = cur_len;                        // RollbackOrdered::len at this Save: k_gen_finalize's entity checksum and the host read it here\n";
-        sfmt(s, "            ggrs_u64* acc = s_acc + si * %uu;                                 // this Save's partials of the workgroup (LDS)\n", n_cks + 1);
+        sfmt(s, "            ggrs_u64* acc = s_acc + si * %uu;                                 // this Save's partials of the workgroup (LDS)\n", n_rows);
         for (uint32_t k = 0; k < n_cks; ++k) emit_checksum(k);
+        res_checksum();
         sfmt(s, "            if (lane == 0) atomicAdd(&acc[%u], (ggrs_u64)__popcll(alive_now));\n"
                 "            ++si;\n"
                 "            if (si >= o_last) break;\n", n_cks);
@@ -1488,7 +1589,7 @@ struct JitGen {
         }
         for (size_t i = 0; i < w->systems.size(); ++i) {
             const ggrs_system_desc& d = w->systems[i];
-            if (d.kind == GGRS_SYS_CUSTOM) { char nm[24]; snprintf(nm, sizeof nm, "fr%zu", i); emit_frame(nm, d.fparam, d.iparam); }
+            if (d.kind == GGRS_SYS_CUSTOM || d.kind == GGRS_SYS_RESOURCE) { char nm[24]; snprintf(nm, sizeof nm, "fr%zu", i); emit_frame(nm, d.fparam, d.iparam); }
             const uint64_t det = d.kind == GGRS_SYS_PARTICLES_UPDATE ? 0ull : sys_det(i);      // (update_particles: per axis, below -- two old values alive at a time instead of six)
             det_in(det);
             switch (d.kind) {
@@ -1498,6 +1599,7 @@ struct JitGen {
             case GGRS_SYS_SAT_SUB_DESPAWN: sys_sat_sub_despawn(d); break;
             case GGRS_SYS_BOX_MOVE: sys_box_move(i, d); break;
             case GGRS_SYS_CUSTOM: sys_custom(i, d); break;
+            case GGRS_SYS_RESOURCE: sys_resource(i, d); break;
             default: break;
             }
             det_out(det);
@@ -1607,6 +1709,8 @@ struct JitGen {
                 sfmt(s, "                ent.opt[%u] = p%u_0 ? (ggrs_u64)w%u_0 : 0x%llxull;\n", base + k, cc, col(cc, k), v);
             }
         }
+        // resource bindings: Res<R> -- the bound words as they stand at this point of the frame, by value
+        for (uint32_t j = 0; j < c.n_res; ++j) sfmt(s, "                ent.rs_[%u] = (ggrs_u64)r%u;\n", j, w->resources[c.rres[j]].reg + c.rword[j]);
         sfmt(s, "                ggrs_sys_%u::ggrs_system(ent, fr%zu);\n", d.comp[0], i);
         if (need.devstream) s += "                if (ent.spawn_n) {                                        // e.spawn(n): the children are made after the frame's systems, from what THIS call left in e\n"
                                  "                    spn_0 = (uint32_t)ent.spawn_n;\n"
@@ -1717,6 +1821,7 @@ struct JitGen {
                 "        const uint32_t live_pm_v = mb ? mb_u32(mb, %uu) : a.live_pmask;\n", L.m.live, L.m.live_rows, L.m.live_pmask);
         { char te[96]; snprintf(te, sizeof te, "(mb ? mb_u64(mb, %uu) : a.live_tagok)", L.m.live_tagok); emit_tag_filter("live_p", "live_rows_v", te, "        ", "dtl"); }
         emit_store("live_p", "live_rows_v", "live_pm_v", "alive_now", "        ", false);
+        if (need.res) { s += "        if (gu == 0 && lane == 0) {                                                // device resources: the live world's, as the launch leaves them\n"; res_store("live_p", "            "); s += "        }\n"; }
         if (need.devstream) emit_sp_gate("        ", "live_p");
         if (need.devstream) s += "        if (len_wr) { *reinterpret_cast<uint64_t*>(live_p) = cur_len; a.sp_len[0] = cur_len; }      // (the last tile: it tracks cur_len exactly)\n";
         else if (need.devspawn) s += "        if (gu == 0 && lane == 0) { *reinterpret_cast<uint64_t*>(live_p) = cur_len; a.sp_len[0] = cur_len; }      // the live block's header carries RollbackOrdered::len for whoever loads it next; the host reads it from pinned memory\n";
@@ -1763,7 +1868,7 @@ struct JitGen {
                  "        const ggrs_u64 v_ = wave_xor(s_lane[r_ * 64u + lane]);\n"
                  "        if (lane == 0) s_acc[sv * %uu + r_ %% %uu] = v_;\n"
                  "    }\n"
-                 "    __syncthreads();\n", n_cks, n_cks, n_cks + 1, n_cks);
+                 "    __syncthreads();\n", n_cks, n_cks, n_rows, n_cks);
         sfmt(s,
                 "    for (uint32_t i = tid; i < a.n_saves * %uu; i += 256u) {\n"
                 "        const uint32_t sv = i / %uu;\n"
@@ -1775,7 +1880,7 @@ struct JitGen {
                 "                asm volatile(\"global_store_dwordx4 %%0, %%1, off sc1\" : : \"v\"(reinterpret_cast<ff_u32x4*>(a.parts) + at_), \"v\"(q_) : \"memory\");\n"
                 "            } else a.parts[at_] = s_acc[i];\n"
                 "        }\n"
-                "    }\n", n_cks + 1, n_cks + 1, n_cks + 1);
+                "    }\n", n_rows, n_rows, n_rows);
         if (need.vtags) s += "    if (a.skip_count && tid == 0 && s_skip) atomicAdd(a.skip_count, s_skip);      // value tags, profiled launches only: bytes this workgroup did not store\n";
         s += "}\n";
     }

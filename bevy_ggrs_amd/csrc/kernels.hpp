@@ -786,6 +786,7 @@ __global__ __launch_bounds__(TPB) void k_spawn_particles(SpawnArgs a) {
 // Fold of k_tick_gen's per-wave partials: one 1024-thread workgroup per Save; any number of checksummed components.
 struct GenFinArgs {
     const uint64_t* parts; uint32_t part_stride, n_parts, n_cks, n_saves;     // grid = n_saves x members (batch of identical groups)
+    uint32_t n_rows;                                                          // rows per Save: n_cks + 1, and one more in a world with device resources (their checksum part, XORed in as it is)
     uint64_t save_len[MAX_TICK_SAVES];                                        // RollbackOrdered::len at each Save of the group (a fused spawn grows it)
     uint64_t* out;
     uint64_t* done; uint64_t seq;                                             // completion tag per workgroup in pinned host memory (nullptr: none), see read_back
@@ -798,8 +799,8 @@ __global__ __launch_bounds__(FIN_TPB) void k_gen_finalize(GenFinArgs f) {
     // flight together (one latency round, not one per row)
     const uint32_t k = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     constexpr uint32_t NW = FIN_TPB / 64;
-    __shared__ uint64_t acc[GEN_MAX_CKS + 1];
-    const uint32_t nc = f.n_cks + 1u;
+    __shared__ uint64_t acc[GEN_MAX_CKS + 2];
+    const uint32_t nc = f.n_rows;
     if (tid < nc) acc[tid] = 0;
     __syncthreads();
     const uint32_t wpr = nc >= NW ? 1u : NW / nc;                     // waves per row
@@ -831,6 +832,7 @@ __global__ __launch_bounds__(FIN_TPB) void k_gen_finalize(GenFinArgs f) {
         for (uint32_t c = 0; c < f.n_cks; ++c) total ^= sea_one(acc[c]);      // component_checksum.rs:92-95
         const uint64_t len_k = f.dev_save_len ? f.dev_save_len[k % f.n_saves] : f.mtab ? *reinterpret_cast<const uint64_t*>(f.mtab + (uint64_t)(k / f.n_saves) * f.mstride + f.moff_save_len + 8u * (k % f.n_saves)) : f.save_len[k % f.n_saves];
         total ^= sea_pair(acc[f.n_cks], len_k);                               // entity_checksum.rs:29-52; XOR fold checksum.rs:88-99
+        if (nc > f.n_cks + 1u) total ^= acc[f.n_cks + 1u];                    // resource_checksum.rs:63-83: the resources' part(s), hashed by the launch
         f.out[2 * (uint64_t)k] = total; f.out[2 * (uint64_t)k + 1] = 0;
         if (f.out2) { f.out2[2 * (uint64_t)k] = total; f.out2[2 * (uint64_t)k + 1] = 0; }
         // the result first, then the tag the waiting host polls (both in the same pinned allocation; release at system scope orders them)
@@ -841,12 +843,12 @@ __global__ __launch_bounds__(FIN_TPB) void k_gen_finalize(GenFinArgs f) {
 // ------------------------------------------------------------------ k_ff_fold
 // Fold-forward without a following request-group launch (ff_flush): one 256-thread workgroup per chunk of a partial row of the LAST launch
 // (device_prelude.hpp ff_fold_row) -- {value, tag} as one 16-byte cell into pinned host memory.  Workgroup b = row b / split, chunk b % split.
-struct FfArgs { const uint64_t* rows; uint64_t* out; uint64_t seq; uint32_t nvals, g, stride, istride, nc1, split; };
+struct FfArgs { const uint64_t* rows; uint64_t* out; uint64_t seq; uint32_t nvals, g, stride, istride, nc1, split, cnt_row; };
 __global__ __launch_bounds__(TPB) void k_ff_fold(FfArgs f) {
     const uint32_t b = blockIdx.x;
     if (b >= f.nvals * f.split) return;
     const uint32_t row = b / f.split, ck = b % f.split, per = (f.g + f.split - 1u) / f.split;
-    ff_fold_row(f.rows + (uint64_t)row * f.stride, f.istride, ck * per, min(f.g, (ck + 1u) * per), (row % f.nc1) == f.nc1 - 1u, f.out + 2u * b, f.seq);
+    ff_fold_row(f.rows + (uint64_t)row * f.stride, f.istride, ck * per, min(f.g, (ck + 1u) * per), (row % f.nc1) == f.cnt_row, f.out + 2u * b, f.seq);
 }
 
 }  // namespace ggrs

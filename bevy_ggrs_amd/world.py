@@ -297,7 +297,7 @@ class World(WorldBase):
         self.capacity = capacity
 
     def add_custom_system(self, source: str, bindings: Sequence[tuple], iparam=(), fparam=(), name: str = "custom", peers: Sequence[tuple] = (), effects: Sequence[tuple] = (),
-                          commands: Sequence[tuple] = ()):
+                          commands: Sequence[tuple] = (), resources: Sequence[tuple] = ()):
         """add_systems(GgrsSchedule, <your system>) for a per-entity system written in HIP C++ (ggrs_hip_add_custom_system):
         `source` defines `__device__ void ggrs_system(GgrsEntity& e, const GgrsFrame& f)`, `bindings` = [(comp, word), ..]
         are the words it sees as e.f32(i)/e.u32(i)/e.i32(i)/e.u64(i).  Compiled for gfx950 when added; a compile error raises
@@ -308,7 +308,9 @@ class World(WorldBase):
         `e.send_u32(slot, j, v)` / `e.send_i32` / `e.send_u64` combines v into effect binding j of the entity at `slot` with `op` (EFFECT_ADD,
         EFFECT_MIN_U, ..: integer, commutative, associative); every send of a frame lands at the end of the frame.
         `commands` = [(comp, flags), ..] (ggrs_hip_add_custom_system_commands): whole components of its OWN entity the system sees as
-        Option<&mut C> -- `e.has(j)`, `e.opt_u32(j, k)` .. -- and, with CMD_INSERT / CMD_REMOVE in the flags, may `e.insert(j)` / `e.remove(j)`."""
+        Option<&mut C> -- `e.has(j)`, `e.opt_u32(j, k)` .. -- and, with CMD_INSERT / CMD_REMOVE in the flags, may `e.insert(j)` / `e.remove(j)`.
+        `resources` = [(res, word), ..] (ggrs_hip_add_custom_system_resources): words of the world's device resources the system reads as
+        Res<R> -- `e.res_u32(j)` / `e.res_i32(j)` / `e.res_f32(j)` / `e.res_u64(j)`: the value as it stands at that point of the frame."""
         d = _ffi.CustomSystemDesc()
         d.name, d.source, d.n_bindings = name.encode(), source.encode(), len(bindings)
         if len(bindings) > _ffi.CUSTOM_MAX_BINDINGS:
@@ -316,6 +318,19 @@ class World(WorldBase):
         for i, (c, w) in enumerate(bindings): d.comp[i], d.word[i] = c, w
         for i, v in enumerate(iparam): d.iparam[i] = v
         for i, v in enumerate(fparam): d.fparam[i] = v
+        if resources:
+            if len(peers) > _ffi.PEER_MAX_BINDINGS or len(effects) > _ffi.EFFECT_MAX_BINDINGS or len(commands) > _ffi.COMMAND_MAX_BINDINGS or len(resources) > _ffi.RESOURCE_MAX_BINDINGS:
+                raise ValueError(f"at most {_ffi.PEER_MAX_BINDINGS} peer, {_ffi.EFFECT_MAX_BINDINGS} effect, {_ffi.COMMAND_MAX_BINDINGS} command and {_ffi.RESOURCE_MAX_BINDINGS} resource bindings")
+            pb = (_ffi.PeerBinding * max(1, len(peers)))()
+            for j, (c, w) in enumerate(peers): pb[j].comp, pb[j].word = c, w
+            eb = (_ffi.EffectBinding * max(1, len(effects)))()
+            for j, (c, w, op) in enumerate(effects): eb[j].comp, eb[j].word, eb[j].op = c, w, op
+            cb = (_ffi.CommandBinding * max(1, len(commands)))()
+            for j, (c, fl) in enumerate(commands): cb[j].comp, cb[j].flags = c, fl
+            rb = (_ffi.ResourceBinding * len(resources))()
+            for j, (r, w) in enumerate(resources): rb[j].res, rb[j].word = r, w
+            self._check(self._lib.ggrs_hip_add_custom_system_resources(self._p, C.byref(d), pb, len(peers), eb, len(effects), cb, len(commands), rb, len(resources)))
+            return
         if commands:
             if len(peers) > _ffi.PEER_MAX_BINDINGS or len(effects) > _ffi.EFFECT_MAX_BINDINGS or len(commands) > _ffi.COMMAND_MAX_BINDINGS:
                 raise ValueError(f"at most {_ffi.PEER_MAX_BINDINGS} peer, {_ffi.EFFECT_MAX_BINDINGS} effect and {_ffi.COMMAND_MAX_BINDINGS} command bindings")
@@ -342,6 +357,55 @@ class World(WorldBase):
         eb = (_ffi.EffectBinding * len(effects))()
         for j, (c, w, op) in enumerate(effects): eb[j].comp, eb[j].word, eb[j].op = c, w, op
         self._check(self._lib.ggrs_hip_add_custom_system_effects(self._p, C.byref(d), pb, len(peers), eb, len(effects)))
+
+    def register_resource(self, name: str, word_bytes: int, n_words: int, init=None) -> int:
+        """init_resource + rollback_resource_with_copy for a device-resident resource (ggrs_hip_register_resource): n_words words of
+        word_bytes (4 or 8); `init` = the initial words (ints, or bytes of exactly that size; None: zero).  Returns the resource id."""
+        buf = None
+        if init is not None:
+            raw = bytes(init) if isinstance(init, (bytes, bytearray)) else b"".join(int(v).to_bytes(word_bytes, "little", signed=int(v) < 0) for v in init)
+            if len(raw) != word_bytes * n_words:
+                raise ValueError("init holds another number of bytes than the resource")
+            buf = (C.c_uint8 * len(raw)).from_buffer_copy(raw)
+        rid = C.c_uint32()
+        self._check(self._lib.ggrs_hip_register_resource(self._p, name.encode(), word_bytes, n_words, buf, C.byref(rid)))
+        self._resources = getattr(self, "_resources", []) + [(word_bytes, n_words)]
+        return rid.value
+
+    def checksum_resource(self, res: int, words: Sequence[int]):
+        """checksum_resource_with_hash (ggrs_hip_checksum_resource): the resource's ChecksumPart is checksum_hasher() over the listed words, in order."""
+        arr = (C.c_uint32 * max(1, len(words)))(*words)
+        self._check(self._lib.ggrs_hip_checksum_resource(self._p, res, arr, len(words)))
+
+    def add_resource_system(self, source: str, bindings: Sequence[tuple], iparam=(), fparam=(), name: str = "resource_system"):
+        """add_systems(GgrsSchedule, <a once-per-frame system over resources>) (ggrs_hip_add_resource_system): `source` defines
+        `__device__ void ggrs_resource_system(GgrsResources& r, const GgrsFrame& f)`, `bindings` = [(res, word), ..] are the words it
+        sees as r.u32(i) / r.i32(i) / r.f32(i) / r.u64(i)."""
+        if len(bindings) > _ffi.RESOURCE_MAX_BINDINGS:
+            raise ValueError(f"at most {_ffi.RESOURCE_MAX_BINDINGS} bindings")
+        d = _ffi.ResourceSystemDesc()
+        d.name, d.source, d.n_bindings = name.encode(), source.encode(), len(bindings)
+        for i, (r, w) in enumerate(bindings): d.res[i], d.word[i] = r, w
+        for i, v in enumerate(iparam): d.iparam[i] = v
+        for i, v in enumerate(fparam): d.fparam[i] = v
+        self._check(self._lib.ggrs_hip_add_resource_system(self._p, C.byref(d)))
+
+    def resource_read(self, res: int) -> list:
+        """world.resource::<R>() of the live world (ggrs_hip_resource_read): the resource's words as unsigned ints."""
+        wb, n = self._resources[res]
+        buf = (C.c_uint8 * (wb * n))()
+        self._check(self._lib.ggrs_hip_resource_read(self._p, res, buf))
+        raw = bytes(buf)
+        return [int.from_bytes(raw[k * wb:(k + 1) * wb], "little") for k in range(n)]
+
+    def resource_write(self, res: int, words: Sequence[int]):
+        """world.resource_mut::<R>() from the host (ggrs_hip_resource_write): replaces all words of the live world's resource."""
+        wb, n = self._resources[res]
+        if len(words) != n:
+            raise ValueError("one value per word of the resource")
+        raw = b"".join((int(v) & ((1 << (8 * wb)) - 1)).to_bytes(wb, "little") for v in words)
+        buf = (C.c_uint8 * len(raw)).from_buffer_copy(raw)
+        self._check(self._lib.ggrs_hip_resource_write(self._p, res, buf))
 
     def add_spawn_system(self, source: str, bundle: Sequence[int], bindings: Sequence[tuple] = (), payload_stride: int = 0, iparam=(), fparam=(), name: str = "spawn"):
         """add_systems(GgrsSchedule, <a system that spawns Rollback entities>) (ggrs_hip_add_spawn_system): `source` defines

@@ -18,6 +18,8 @@
 //   handle_requests
 //   RollbackApp::rollback_resource_with_*,   src/snapshot/rollback_app.rs:46-124     App member functions; resources are O(1)
 //   checksum_resource[_with_hash]            resource_snapshot.rs, resource_checksum.rs  bytes per frame and stay on the host
+//                                                                                    (POD resources a schedule system mutates once per frame can live on the device
+//                                                                                    instead: HipBackend::register_resource .. resource_write, include/ggrs_hip.h)
 //   GgrsSnapshots<For, As>                   src/snapshot/mod.rs:97-274              bevy_ggrs::GgrsSnapshots<As> (host ring for resources)
 //   checksum_hasher() == SeaHasher::new()    src/snapshot/mod.rs:318-320             bevy_ggrs::SeaHasher (seahash 4.1, restated)
 //   ggrs::SessionBuilder / SyncTestSession   (un-vendored `ggrs`, Cargo.toml:23; restated)  same names
@@ -420,6 +422,14 @@ struct HipBackend {
     int add_custom_system_effects(const ggrs_custom_system_desc* d, const ggrs_peer_binding* peers, uint32_t n_peers, const ggrs_effect_binding* effects, uint32_t n_effects) { return ggrs_hip_add_custom_system_effects(w, d, peers, n_peers, effects, n_effects); }
     int add_custom_system_commands(const ggrs_custom_system_desc* d, const ggrs_peer_binding* peers, uint32_t n_peers, const ggrs_effect_binding* effects, uint32_t n_effects, const ggrs_command_binding* cmds, uint32_t n_cmds) { return ggrs_hip_add_custom_system_commands(w, d, peers, n_peers, effects, n_effects, cmds, n_cmds); }
     int add_spawn_system(const ggrs_spawn_system_desc* d) { return ggrs_hip_add_spawn_system(w, d); }
+    // device-resident rollback resources (include/ggrs_hip.h): thin forwards -- init_resource + rollback_resource_with_copy, checksum_resource_with_hash, the systems over them
+    int register_resource(const char* n, uint32_t wb, uint32_t nw, const void* init, uint32_t* id) { return ggrs_hip_register_resource(w, n, wb, nw, init, id); }
+    int checksum_resource(uint32_t r, const uint32_t* idx, uint32_t n) { return ggrs_hip_checksum_resource(w, r, idx, n); }
+    int add_resource_system(const ggrs_resource_system_desc* d) { return ggrs_hip_add_resource_system(w, d); }
+    int add_custom_system_resources(const ggrs_custom_system_desc* d, const ggrs_peer_binding* peers, uint32_t n_peers, const ggrs_effect_binding* effects, uint32_t n_effects, const ggrs_command_binding* cmds, uint32_t n_cmds,
+                                    const ggrs_resource_binding* res, uint32_t n_res) { return ggrs_hip_add_custom_system_resources(w, d, peers, n_peers, effects, n_effects, cmds, n_cmds, res, n_res); }
+    int resource_read(uint32_t r, void* words_out) { return ggrs_hip_resource_read(w, r, words_out); }
+    int resource_write(uint32_t r, const void* words) { return ggrs_hip_resource_write(w, r, words); }
     int register_component_strategy(uint32_t c, uint32_t stored_word_bytes, uint32_t stored_n_words, const char* source) { return ggrs_hip_register_component_strategy(w, c, stored_word_bytes, stored_n_words, source); }
     int set_frame_rate(uint64_t fps) { return ggrs_hip_set_frame_rate(w, fps); }
     int spawn(uint64_t count, uint64_t mask, const void* const* cols, uint64_t* first) { return ggrs_hip_spawn(w, count, mask, cols, first); }

@@ -330,6 +330,72 @@ int ggrs_hip_add_custom_system_commands(ggrs_world* w, const ggrs_custom_system_
                                         const ggrs_effect_binding* effects, uint32_t n_effects,
                                         const ggrs_command_binding* cmds, uint32_t n_cmds);
 
+/* DEVICE-RESIDENT ROLLBACK RESOURCES.  In the reference a world-global value that evolves once per frame is a Resource: increase_frame_system(ResMut<FrameCount>)
+ * with rollback_resource_with_copy and checksum_resource_with_hash (examples/box_game/box_game.rs:146), ParticleRng (examples/stress_tests/particles.rs:200,258),
+ * frame_counter(ResMut<FrameCounter>) (tests/synctest.rs:13, tests/hierarchy.rs:48).  A resource registered here lives on the device: a few 4- or 8-byte words
+ * that every wave of the generated request-group kernel carries in wave-uniform registers.
+ *
+ *   ggrs_hip_register_resource     init_resource + rollback_resource_with_copy: n_words words of word_bytes (4 or 8), initial value init_words (NULL: zero).
+ *                                  At most GGRS_RESOURCE_MAX resources and GGRS_RESOURCE_MAX_BYTES bytes of all of them together per world.
+ *   ggrs_hip_checksum_resource     checksum_resource_with_hash (ResourceChecksumPlugin, snapshot/resource_checksum.rs:63-83): the part is
+ *                                  ChecksumPart(hasher(resource) as u128), the hasher checksum_hasher() fed the listed words in order, each with its own width;
+ *                                  it is XORed into the frame's Checksum next to the component parts (checksum.rs:94).
+ *   ggrs_hip_add_resource_system   a once-per-frame system such as `fn tick(mut c: ResMut<Clock>, inputs: Res<PlayerInputs>)`.  `source` is HIP C++ defining
+ *
+ *                                      __device__ void ggrs_resource_system(GgrsResources& r, const GgrsFrame& f);
+ *
+ *                                  r.u32(i) / r.i32(i) / r.f32(i) / r.u64(i) are references to bound resource word i (binding i = word `word[i]` of resource `res[i]`;
+ *                                  4-byte words as u32 / i32 / f32, 8-byte words as u64; another index, or the other width, does not compile); f is the GgrsFrame entity
+ *                                  systems get: dt, frame, inputs, status and the desc's constants.  It runs once per simulated frame, at its registration position
+ *                                  among the world's systems, under the library's floating-point contract, and counts against GGRS_MAX_SYSTEMS.
+ *   ggrs_hip_add_custom_system_resources   an entity system with resource bindings (Res<R> in a per-entity system): res[j] = {res, word} names resource binding j,
+ *                                  read inside ggrs_system as e.res_u32(j) / e.res_i32(j) / e.res_f32(j) / e.res_u64(j) -- values, not references: the value as it
+ *                                  stands at that point of the frame.  A resource system registered earlier has already run for this frame, one registered later has
+ *                                  not: what Bevy's sequential schedule shows, so there is no registration-order rule.  peers, effects and cmds are as in
+ *                                  ggrs_hip_add_custom_system_commands, and with n_res == 0 the call behaves exactly as that one.
+ *   ggrs_hip_resource_read / _write   the live world's value (world.resource::<R>()) / a host edit (world.resource_mut::<R>()): all words of the resource.
+ *
+ * Every SaveWorld stores the resources with the snapshot and every LoadWorld restores them (resource_snapshot.rs:70-98, the (Some, Some) branch); ggrs_hip_load, a
+ * fan-out step and a replay of deferred Saves follow.
+ * How it runs: every wave loads the words once per launch with scalar loads from the group's source block, replays the resource systems itself, step after step
+ * -- redundantly and identically in every wave --, and one lane of the launch stores them with each snapshot's header.  No extra launch, no atomics, no wait.
+ * A block keeps TWO cells for the words and the host knows which is current: a launch reads the current cell of its source block and writes the other cell of
+ * any block that is its source, so no launch reads resource words from a location it writes (a launch may write the block it reads: live -> live, a Save into
+ * the slot it loaded).
+ * Out of scope in this version: inserting or removing a resource at run time (a device resource exists from registration on; an app with an Option<Res<R>>
+ * lifecycle keeps that resource on the host); 1- and 2-byte words; a custom resource hasher; spawn systems with resource bindings; entity systems
+ * WRITING or reducing into a resource (ResMut inside a per-entity loop needs a kernel boundary per frame, like effects).
+ * Refused with GGRS_E_INVALID and a message naming the resource or system: a world without the generated kernel (GGRS_WORLD_NO_GROUPS, GGRS_WORLD_UNFUSED, no
+ * compiler and no shipped object); a world that spawns on the device with e.spawn(n); a world that keeps RollbackDespawned markers; GGRS_BRANCH_RETAIN_* in
+ * ggrs_hip_fanout_step_branches on such a world (without retention, and ggrs_hip_fanout_step, work); more than the limits below; a binding to an unknown resource or
+ * word; a resource system with no binding; registering after seal.  Peers, effects and commands in the same world and system, built-in systems, host-decided and
+ * fused spawns, strategies, custom component hashers and any input layout are allowed. */
+#define GGRS_SYS_RESOURCE 9u          /* a user-written resource system: ggrs_hip_add_resource_system (not a kind for ggrs_hip_add_system) */
+#define GGRS_RESOURCE_MAX        8    /* resources per world */
+#define GGRS_RESOURCE_MAX_BYTES  64   /* bytes of all resources of a world together */
+#define GGRS_RESOURCE_MAX_BINDINGS 8
+int ggrs_hip_register_resource(ggrs_world* w, const char* name, uint32_t word_bytes, uint32_t n_words,
+                               const void* init_words, uint32_t* res_id_out);
+int ggrs_hip_checksum_resource(ggrs_world* w, uint32_t res_id, const uint32_t* word_idx, uint32_t n_words);
+typedef struct { uint32_t res; uint32_t word; } ggrs_resource_binding;   /* resource binding j = word `word` of resource `res` */
+typedef struct {
+    const char* name;                               /* for error messages and traces; may be NULL               */
+    const char* source;                             /* HIP C++ defining ggrs_resource_system (NUL-terminated)   */
+    uint32_t n_bindings;
+    uint32_t res[GGRS_RESOURCE_MAX_BINDINGS];
+    uint32_t word[GGRS_RESOURCE_MAX_BINDINGS];
+    int64_t  iparam[2];
+    float    fparam[4];
+} ggrs_resource_system_desc;
+int ggrs_hip_add_resource_system(ggrs_world* w, const ggrs_resource_system_desc* desc);
+int ggrs_hip_add_custom_system_resources(ggrs_world* w, const ggrs_custom_system_desc* desc,
+                                         const ggrs_peer_binding* peers, uint32_t n_peers,
+                                         const ggrs_effect_binding* effects, uint32_t n_effects,
+                                         const ggrs_command_binding* cmds, uint32_t n_cmds,
+                                         const ggrs_resource_binding* res, uint32_t n_res);
+int ggrs_hip_resource_read(ggrs_world* w, uint32_t res_id, void* words_out);
+int ggrs_hip_resource_write(ggrs_world* w, uint32_t res_id, const void* words);
+
 /* ComponentSnapshotPlugin<S: Strategy> (snapshot/strategy.rs:22-40, component_snapshot.rs:42-63): what a snapshot HOLDS of a component is
  * S::Stored, produced by S::store and turned back by S::load / S::update -- CopyStrategy / CloneStrategy (Stored == the component, bitwise for
  * POD) are what ggrs_hip_register_component gives; this is the open door next to them: quantised, packed or partial snapshots.
@@ -693,7 +759,7 @@ int ggrs_hip_host_timeline(ggrs_world* w, int enable, double* us_out, uint64_t* 
  * Introspection: which kernel serves this world's request lists right now and why, what kind of arena
  * it lives on, whether the run-time compiler (libhiprtc.so, dlopen'ed) is available.  `key=value` lines,
  * NUL-terminated; *needed = bytes incl. the NUL, min(cap, *needed) are copied.  Keys: sealed, arena,
- * arena_bytes, hiprtc, generated_kernel, generated_kernel_origin, request_group_kernel, checksum_fold, kernarg_bytes, group_caps, specialised_kernel, slots_covered, row_versions, peer_view (worlds with peer bindings), effect_inbox (worlds with effect bindings).
+ * arena_bytes, hiprtc, generated_kernel, generated_kernel_origin, request_group_kernel, checksum_fold, kernarg_bytes, group_caps, specialised_kernel, slots_covered, row_versions, peer_view (worlds with peer bindings), effect_inbox (worlds with effect bindings), device_resources (worlds with device resources), depth_parallel_roles.
  * ------------------------------------------------------------------------------------------- */
 int ggrs_hip_world_kernel_info(ggrs_world* w, char* buf, uint64_t cap, uint64_t* needed);
 

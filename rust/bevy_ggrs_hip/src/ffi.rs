@@ -29,6 +29,7 @@ pub const GGRS_SYS_SAT_SUB_DESPAWN: u32 = 5;
 pub const GGRS_SYS_BOX_MOVE: u32 = 6;
 pub const GGRS_SYS_CUSTOM: u32 = 7;
 pub const GGRS_SYS_SPAWN_CUSTOM: u32 = 8;
+pub const GGRS_SYS_RESOURCE: u32 = 9;
 pub const GGRS_MAX_PLAYERS: usize = 16;
 pub const GGRS_MAX_INPUT_BYTES: usize = 16;
 pub const GGRS_INPUT_CONFIRMED: u8 = 0;
@@ -119,6 +120,30 @@ pub const GGRS_CMD_INSERT: u32 = 1;
 pub const GGRS_CMD_REMOVE: u32 = 2;
 pub const GGRS_COMMAND_MAX_BINDINGS: usize = 4;
 pub const GGRS_COMMAND_MAX_WORDS: usize = 8;
+
+/// One resource binding of `ggrs_hip_add_custom_system_resources`: a word of a device-resident rollback resource a system reads as `Res<R>` through `e.res_*(j)`.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct ggrs_resource_binding {
+    pub res: u32,
+    pub word: u32,
+}
+pub const GGRS_RESOURCE_MAX: usize = 8;
+pub const GGRS_RESOURCE_MAX_BYTES: usize = 64;
+pub const GGRS_RESOURCE_MAX_BINDINGS: usize = 8;
+
+/// A once-per-frame system over device resources (`ggrs_hip_add_resource_system`): `source` defines `ggrs_resource_system(GgrsResources& r, const GgrsFrame& f)`.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct ggrs_resource_system_desc {
+    pub name: *const c_char,
+    pub source: *const c_char,
+    pub n_bindings: u32,
+    pub res: [u32; GGRS_RESOURCE_MAX_BINDINGS],
+    pub word: [u32; GGRS_RESOURCE_MAX_BINDINGS],
+    pub iparam: [i64; 2],
+    pub fparam: [f32; 4],
+}
 
 /// One effect binding of `ggrs_hip_add_custom_system_effects`: a word of OTHER entities a system writes through `e.send_*(slot, j, v)`, combined with `op`.
 #[repr(C)]
@@ -224,6 +249,12 @@ unsafe extern "C" {
     pub fn ggrs_hip_add_custom_system_peers(w: *mut ggrs_world, desc: *const ggrs_custom_system_desc, peers: *const ggrs_peer_binding, n_peers: u32) -> c_int;
     pub fn ggrs_hip_add_custom_system_effects(w: *mut ggrs_world, desc: *const ggrs_custom_system_desc, peers: *const ggrs_peer_binding, n_peers: u32, effects: *const ggrs_effect_binding, n_effects: u32) -> c_int;
     pub fn ggrs_hip_add_custom_system_commands(w: *mut ggrs_world, desc: *const ggrs_custom_system_desc, peers: *const ggrs_peer_binding, n_peers: u32, effects: *const ggrs_effect_binding, n_effects: u32, cmds: *const ggrs_command_binding, n_cmds: u32) -> c_int;
+    pub fn ggrs_hip_add_custom_system_resources(w: *mut ggrs_world, desc: *const ggrs_custom_system_desc, peers: *const ggrs_peer_binding, n_peers: u32, effects: *const ggrs_effect_binding, n_effects: u32, cmds: *const ggrs_command_binding, n_cmds: u32, res: *const ggrs_resource_binding, n_res: u32) -> c_int;
+    pub fn ggrs_hip_register_resource(w: *mut ggrs_world, name: *const c_char, word_bytes: u32, n_words: u32, init_words: *const c_void, res_id_out: *mut u32) -> c_int;
+    pub fn ggrs_hip_checksum_resource(w: *mut ggrs_world, res_id: u32, word_idx: *const u32, n_words: u32) -> c_int;
+    pub fn ggrs_hip_add_resource_system(w: *mut ggrs_world, desc: *const ggrs_resource_system_desc) -> c_int;
+    pub fn ggrs_hip_resource_read(w: *mut ggrs_world, res_id: u32, words_out: *mut c_void) -> c_int;
+    pub fn ggrs_hip_resource_write(w: *mut ggrs_world, res_id: u32, words: *const c_void) -> c_int;
     pub fn ggrs_hip_register_component_strategy(w: *mut ggrs_world, comp_id: u32, stored_word_bytes: u32, stored_n_words: u32, source: *const c_char) -> c_int;
     pub fn ggrs_hip_set_input_layout(w: *mut ggrs_world, input_bytes: u32, max_players: u32) -> c_int;
     pub fn ggrs_hip_add_spawn_system(w: *mut ggrs_world, desc: *const ggrs_spawn_system_desc) -> c_int;
