@@ -132,6 +132,7 @@ void ggrs_hip_world_destroy(ggrs_world* w) {
     sp_release(w);
     peer_view_release(w);
     fx_inbox_release(w);
+    rd_inbox_release(w);
     for (void* p : w->spec_allocs) (void)hipFree(p);
     if (w->h_results) (void)hipHostFree(w->h_results);
     if (w->h_stage) (void)hipHostFree(w->h_stage);
@@ -233,7 +234,15 @@ int ggrs_hip_add_custom_system_commands(ggrs_world* w, const ggrs_custom_system_
 // ... and with resource bindings: words of the world's device resources the system reads through e.res_*(j), as they stand at that point of the frame (include/ggrs_hip.h)
 int ggrs_hip_add_custom_system_resources(ggrs_world* w, const ggrs_custom_system_desc* d, const ggrs_peer_binding* peers, uint32_t n_peers, const ggrs_effect_binding* effects, uint32_t n_effects,
                                          const ggrs_command_binding* cmds, uint32_t n_cmds, const ggrs_resource_binding* res, uint32_t n_res) {
+    return ggrs_hip_add_custom_system_reduces(w, d, peers, n_peers, effects, n_effects, cmds, n_cmds, res, n_res, nullptr, 0);
+}
+// ... and with reduce bindings: words of the world's device resources the system combines a value into through e.reduce_*(j, v), landing at the end of the frame
+// (include/ggrs_hip.h).  Which resource, word and width a binding names is checked at seal (host_seal.hpp reduces_validate), with the registration-order rule
+int ggrs_hip_add_custom_system_reduces(ggrs_world* w, const ggrs_custom_system_desc* d, const ggrs_peer_binding* peers, uint32_t n_peers, const ggrs_effect_binding* effects, uint32_t n_effects,
+                                       const ggrs_command_binding* cmds, uint32_t n_cmds, const ggrs_resource_binding* res, uint32_t n_res, const ggrs_reduce_binding* red, uint32_t n_red) {
     if (!w || !d || !d->source) return GGRS_E_INVALID;
+    if (n_red > GGRS_REDUCE_MAX_BINDINGS) return w->fail(GGRS_E_INVALID, "custom system '%s': at most %d reduce bindings (GGRS_REDUCE_MAX_BINDINGS), not %u", d->name ? d->name : "custom", GGRS_REDUCE_MAX_BINDINGS, n_red);
+    if (n_red && !red) return w->fail(GGRS_E_INVALID, "custom system: n_red = %u but red is NULL", n_red);
     if (n_res > GGRS_RESOURCE_MAX_BINDINGS) return w->fail(GGRS_E_INVALID, "custom system '%s': at most %d resource bindings (GGRS_RESOURCE_MAX_BINDINGS), not %u", d->name ? d->name : "custom", GGRS_RESOURCE_MAX_BINDINGS, n_res);
     if (n_res && !res) return w->fail(GGRS_E_INVALID, "custom system: n_res = %u but res is NULL", n_res);
     if (n_cmds > GGRS_COMMAND_MAX_BINDINGS) return w->fail(GGRS_E_INVALID, "custom system '%s': at most %d command bindings (GGRS_COMMAND_MAX_BINDINGS), not %u", d->name ? d->name : "custom", GGRS_COMMAND_MAX_BINDINGS, n_cmds);
@@ -285,6 +294,11 @@ int ggrs_hip_add_custom_system_resources(ggrs_world* w, const ggrs_custom_system
         c.rres[j] = res[j].res; c.rword[j] = res[j].word;
     }
     c.n_res = n_res;
+    for (uint32_t j = 0; j < n_red; ++j) {
+        if (red[j].op > GGRS_EFFECT_XOR) return w->fail(GGRS_E_INVALID, "custom system '%s': reduce binding %u (word %u of resource %u) has op %u, which is none of GGRS_EFFECT_*", c.name.c_str(), j, red[j].word, red[j].res, red[j].op);
+        c.dres[j] = red[j].res; c.dword[j] = red[j].word; c.dop[j] = red[j].op;
+    }
+    c.n_red = n_red;
     DeviceGuard dg(w);
     c.source = d->source;
     c.may_defer = source_has_token(c.source, "despawn_rollback") || source_has_token(c.source, "kill");
@@ -428,7 +442,7 @@ int ggrs_hip_generated_kernel_source(ggrs_world* w, uint32_t form, char* buf, ui
     if (!w || (form != GGRS_KERNEL_FORM_TILES && form != GGRS_KERNEL_FORM_STEADY)) return GGRS_E_INVALID;
     if (!w->sealed) {
         if (!w->layout_only) { DeviceGuard dg(w); const int rc = seal(w); if (rc) return rc; }
-        else { build_layout(w); const int prc = peers_validate(w); if (prc) return prc; const int frc = effects_validate(w); if (frc) return frc; const int crc = commands_validate(w); if (crc) return crc; const int rrc = resources_validate(w); if (rrc) return rrc; }   // host arithmetic only: offsets of every mask and column; the peer-, effect-, command- and resource rules
+        else { build_layout(w); const int prc = peers_validate(w); if (prc) return prc; const int frc = effects_validate(w); if (frc) return frc; const int crc = commands_validate(w); if (crc) return crc; const int rrc = resources_validate(w); if (rrc) return rrc; const int drc = reduces_validate(w); if (drc) return drc; }   // host arithmetic only: offsets of every mask and column; the peer-, effect-, command-, resource and reduce rules
     }
     std::string src;
     if (!jit_source(w, src)) return w->fail(GGRS_E_INVALID, "the kernel generator does not cover this world (a system writes a live-only component, or more than %u four-byte units / %u words per entity)", JIT_MAX_UNITS, JIT_MAX_COLS);
@@ -460,6 +474,17 @@ int ggrs_dbg_replace_token(const char* body, const char* tok, const char* val, c
 //                              before the world is sealed
 int ggrs_dbg_set_value_tags(ggrs_world* w, int mode) { if (!w || w->sealed) return -1; w->vtags_mode = mode; return 0; }
 int ggrs_dbg_set_lazy_live(ggrs_world* w, int on) { if (!w) return -1; w->lazy_live_on = on; return 0; }
+//   ggrs_dbg_set_reduce_stripes  lines of the reduce inbox (1..64, default RD_STRIPES = 64), before seal: what scripts/bench_reduces.py varies
+//   ggrs_dbg_reduce_inbox      the bytes of the reduce inbox (stripes x 64) after everything queued on the world's stream has run: returns how many bytes the inbox has
+//                              (min(cap, that) are copied), -1 for a world without one -- it must hold identities whenever a host call returns
+int ggrs_dbg_set_reduce_stripes(ggrs_world* w, int n) { if (!w || w->sealed || n < 1 || n > 64) return -1; w->rd_stripes = (uint32_t)n; return 0; }
+int64_t ggrs_dbg_reduce_inbox(ggrs_world* w, void* out, uint64_t cap) {
+    if (!w || !w->rd_inbox.d) return -1;
+    DeviceGuard dg(w);
+    const uint64_t bytes = (uint64_t)w->rd_inbox.stripes * 64u;
+    if (hipMemcpyAsync(out, w->rd_inbox.d, std::min(cap, bytes), hipMemcpyDeviceToHost, w->stream) != hipSuccess || hipStreamSynchronize(w->stream) != hipSuccess) return -1;
+    return (int64_t)bytes;
+}
 int ggrs_dbg_set_spec_shapes(ggrs_world* w, int n) { if (!w || n < 1 || n > 64) return -1; w->spec_shapes = n; return 0; }
 int ggrs_hip_set_frame_rate(ggrs_world* w, uint64_t fps) { if (!w || fps == 0) return GGRS_E_INVALID; w->fps = fps; return GGRS_OK; }
 
@@ -970,6 +995,8 @@ int ggrs_hip_world_kernel_info(ggrs_world* w, char* buf, uint64_t cap, uint64_t*
                                                      "their mask words are rebuilt per Save, and every AdvanceWorld gives their masks and columns fresh row versions");
         if (w->has_resources) add("device_resources", std::to_string(w->resources.size()) + " resources, " + std::to_string(res_total_bytes(w)) + " bytes: wave-uniform registers of the generated kernel, loaded from the source block's current cell "
                                                       "(two cells per block; the live block's is cell " + std::to_string(w->live.res_cell) + "), stored with every snapshot's header");
+        if (w->has_reduces) add("reduce_inbox", std::to_string(w->rd_inbox.stripes) + " stripes of 64 bytes laid out like a resource cell, " + std::to_string(w->rd_inbox.n_words) + " reduced words holding the ops' identities, folded into the live block's current resource cell right behind every request group that holds an AdvanceWorld (" +
+                                                std::to_string(w->rd_inbox.applies) + " applies so far)");
         if (w->has_effects) add("effect_inbox", std::to_string(w->fx_inbox.n_cols) + " linear columns holding the ops' identities, applied to the live block right behind every request group that holds an AdvanceWorld (" +
                                                std::to_string(w->fx_inbox.applies) + " applies so far)");
         add("branch_marker_record_bytes", std::to_string(w->jit_marks ? jit_marks_rec_bytes(w) : 0));      // per retained branch of ggrs_hip_fanout_step_branches (0: the kernel keeps no markers)

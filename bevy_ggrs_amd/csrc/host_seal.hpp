@@ -175,6 +175,54 @@ int resources_validate(ggrs_world* w) {
     if (!w->knobs.tick_jit) return w->fail(GGRS_E_INVALID, "device resources ('%s', ggrs_hip_register_resource) need the generated request-group kernel, which this world does not have: disabled (GGRS_TICK_JIT=0)", nm);
     return GGRS_OK;
 }
+void rd_inbox_release(ggrs_world* w) {
+    if (w->rd_inbox.d) (void)hipFree(w->rd_inbox.d);
+    w->rd_inbox = ggrs_world::ReduceInbox{};
+}
+// Reduce bindings (ggrs_hip_add_custom_system_reduces): the rules under which "all reductions of a frame land at the END of the frame" equals Bevy's sequential
+// ResMut write -- nothing that runs at or after a word's first reducer looks at the word, so nobody can tell when inside the frame the combine happened.  A resource
+// system registered BEFORE the reducer may read and reset the word; an entity system registered before it reads last frame's result.  What a world with device
+// resources refuses, resources_validate refuses for this one too.  After build_layout; no device needed.
+int reduces_validate(ggrs_world* w) {
+    if (!world_has_reduces(w)) return GGRS_OK;
+    static const char* const op_name[] = {"ADD", "MIN_U", "MAX_U", "MIN_I", "MAX_I", "OR", "AND", "XOR"};
+    struct First { uint32_t res, word, op; };
+    std::vector<First> seen;
+    for (size_t i = 0; i < w->systems.size(); ++i) {
+        if (w->systems[i].kind != GGRS_SYS_CUSTOM) continue;
+        const ggrs_world::Custom& c = w->customs[w->systems[i].comp[0]];
+        const char* nm = c.name.c_str();
+        for (uint32_t j = 0; j < c.n_red; ++j) {
+            const uint32_t rr = c.dres[j], rw = c.dword[j];
+            if (rr >= w->resources.size()) return w->fail(GGRS_E_INVALID, "custom system '%s': reduce binding %u names resource %u, which is not registered (%zu resources)", nm, j, rr, w->resources.size());
+            const ggrs_world::Resource& r = w->resources[rr];
+            if (rw >= r.n_words) return w->fail(GGRS_E_INVALID, "custom system '%s': reduce binding %u names word %u of resource %u ('%s'), which has %u words", nm, j, rw, rr, r.name.c_str(), r.n_words);
+            if (r.word_bytes != 4 && r.word_bytes != 8) return w->fail(GGRS_E_INVALID, "custom system '%s': reduce binding %u names word %u of resource %u ('%s'), whose words have %u bytes: reductions need 4- or 8-byte words", nm, j, rw, rr, r.name.c_str(), r.word_bytes);
+            bool first = true;
+            for (auto& f : seen) if (f.res == rr && f.word == rw) {
+                first = false;
+                if (f.op != c.dop[j]) return w->fail(GGRS_E_INVALID, "custom system '%s': reduce binding %u reduces into word %u of resource %u ('%s') with GGRS_EFFECT_%s, another binding of this world with GGRS_EFFECT_%s: a word has one op in the whole world", nm, j, rw, rr, r.name.c_str(), op_name[c.dop[j] & 7u], op_name[f.op & 7u]);
+            }
+            if (!first) continue;
+            seen.push_back(First{rr, rw, c.dop[j]});                     // system i is the word's first reducer
+            for (size_t k = i; k < w->systems.size(); ++k) {
+                const ggrs_system_desc& d = w->systems[k];
+                if (d.kind == GGRS_SYS_CUSTOM) {
+                    const ggrs_world::Custom& o = w->customs[d.comp[0]];
+                    for (uint32_t q = 0; q < o.n_res; ++q) if (o.rres[q] == rr && o.rword[q] == rw)
+                        return w->fail(GGRS_E_INVALID, "custom system '%s' (system %zu) reduces into word %u of resource %u ('%s'), which custom system '%s' (system %zu), registered at or after it, reads through resource binding %u: "
+                                                       "no system registered at or after the first reducer of a word reads or writes that word", nm, i, rw, rr, r.name.c_str(), o.name.c_str(), k, q);
+                } else if (d.kind == GGRS_SYS_RESOURCE) {
+                    const ggrs_world::ResSys& o = w->res_systems[d.comp[0]];
+                    for (uint32_t q = 0; q < o.n_bind; ++q) if (o.res[q] == rr && o.word[q] == rw)
+                        return w->fail(GGRS_E_INVALID, "custom system '%s' (system %zu) reduces into word %u of resource %u ('%s'), which resource system '%s' (system %zu), registered after it, binds: "
+                                                       "no system registered at or after the first reducer of a word reads or writes that word", nm, i, rw, rr, r.name.c_str(), o.name.c_str(), k);
+                }
+            }
+        }
+    }
+    return GGRS_OK;
+}
 int seal(ggrs_world* w) {
     if (w->layout_only) return w->fail(GGRS_E_NO_DEVICE, "GGRS_WORLD_LAYOUT_ONLY world: there is no device behind it");
     if (w->sealed) return GGRS_OK;
@@ -188,6 +236,7 @@ int seal(ggrs_world* w) {
     sp_release(w);
     peer_view_release(w);
     fx_inbox_release(w);
+    rd_inbox_release(w);
     if (w->h_results) { (void)hipHostFree(w->h_results); w->h_results = nullptr; w->d_results = nullptr; }
     if (w->h_stage) { (void)hipHostFree(w->h_stage); w->h_stage = nullptr; w->d_hstage = nullptr; }
     if (w->h_rows) { (void)hipHostFree(w->h_rows); w->h_rows = nullptr; w->d_rows = nullptr; }
@@ -254,6 +303,8 @@ int seal_impl(ggrs_world* w) {
     { const int frc = effects_validate(w); if (frc) return frc; }
     { const int crc = commands_validate(w); if (crc) return crc; }
     { const int rrc = resources_validate(w); if (rrc) return rrc; }
+    { const int drc = reduces_validate(w); if (drc) return drc; }
+    w->has_reduces = world_has_reduces(w);
     w->has_resources = world_has_resources(w);
     w->has_peers = world_has_peers(w);
     w->has_effects = world_has_effects(w);
@@ -456,6 +507,19 @@ int seal_impl(ggrs_world* w) {
             HIPCHK(w, hipMemcpyAsync(fx.d_col[k], fill.data(), fill.size(), hipMemcpyHostToDevice, w->stream));
             HIPCHK(w, hipStreamSynchronize(w->stream));                                             // (the host buffer dies here)
         }
+    }
+    if (w->has_reduces) {
+        // the reduce inbox: `stripes` lines of 64 bytes laid out like a resource cell, every reduced word at its op's identity -- what it holds whenever no group-and-apply pair is in flight
+        ggrs_world::ReduceInbox& rd = w->rd_inbox;
+        rd = ggrs_world::ReduceInbox{};
+        rd.stripes = w->rd_stripes;
+        ReducedWord rw[RD_MAX_WORDS];
+        rd.n_words = reduced_words(w, rw);
+        std::vector<uint8_t> fill((size_t)rd.stripes * 64u, 0);
+        for (uint32_t s = 0; s < rd.stripes; ++s) for (uint32_t k = 0; k < rd.n_words; ++k) { const uint64_t id = fx_identity(rw[k].op, rw[k].wb); memcpy(fill.data() + (size_t)s * 64u + rw[k].off, &id, rw[k].wb); }   // (little-endian: the low wb bytes)
+        HIPCHK(w, hipMalloc((void**)&rd.d, fill.size()));
+        HIPCHK(w, hipMemcpyAsync(rd.d, fill.data(), fill.size(), hipMemcpyHostToDevice, w->stream));
+        HIPCHK(w, hipStreamSynchronize(w->stream));                    // (the host buffer dies here)
     }
     if (w->vtags) { HIPCHK(w, hipMalloc((void**)&w->d_skip, 8)); HIPCHK(w, hipMemsetAsync(w->d_skip, 0, 8, w->stream)); }
     if (w->dev_spawn) {

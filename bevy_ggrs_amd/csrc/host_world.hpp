@@ -48,6 +48,7 @@ struct Block {                           // one packed state block in the arena
 constexpr uint32_t RES_CELL_OFF = 64, RES_CELL_BYTES = 64, RES_CELL_IDX_OFF = 40;     // RES_CELL_IDX_OFF: a u32 right behind struct Header -- the index of the block's current cell, written with the cell
 static_assert(RES_CELL_BYTES == GGRS_RESOURCE_MAX_BYTES && RES_CELL_OFF + 2 * RES_CELL_BYTES <= 256, "two resource cells fit the header behind struct Header");
 
+constexpr uint32_t RD_STRIPES = 64;      // reduce bindings: 64-byte lines of the reduce inbox (4 KB); a wave publishes into line `workgroup index mod RD_STRIPES`.  Not measured yet; at most 64 (k_apply_reduces is one wave, lane s loads line s)
 struct EventPair { hipEvent_t a, b; uint32_t cls; };
 struct JitEntry;                         // kernel_gen.hpp: a cached generated module
 
@@ -174,6 +175,8 @@ struct ggrs_world {
         uint32_t n_cmd = 0, ccomp[GGRS_COMMAND_MAX_BINDINGS] = {}, cflags[GGRS_COMMAND_MAX_BINDINGS] = {};
         // resource bindings (ggrs_hip_add_custom_system_resources): words of the world's device resources the system reads through e.res_*(j)
         uint32_t n_res = 0, rres[GGRS_RESOURCE_MAX_BINDINGS] = {}, rword[GGRS_RESOURCE_MAX_BINDINGS] = {};
+        // reduce bindings (ggrs_hip_add_custom_system_reduces): words of the world's device resources the system combines a value into through e.reduce_*(j, v)
+        uint32_t n_red = 0, dres[GGRS_REDUCE_MAX_BINDINGS] = {}, dword[GGRS_REDUCE_MAX_BINDINGS] = {}, dop[GGRS_REDUCE_MAX_BINDINGS] = {};
     };
     std::vector<Custom> customs;
     // DEVICE RESOURCES (ggrs_hip_register_resource): a few 4- or 8-byte words per world, carried by every wave of the generated kernel in wave-uniform registers.
@@ -201,6 +204,13 @@ struct ggrs_world {
         uint64_t applies = 0;
     } fx_inbox;
     bool has_effects = false;            // some system has effect bindings (set at seal: effect_cols)
+    // THE REDUCE INBOX of a world with reduce bindings (allocated at seal): `stripes` lines of 64 bytes, each laid out like a resource cell -- a reduced word sits at
+    // its byte offset inside the block header's cell -- holding the ops' identities whenever no group-and-apply pair is in flight.  A wave of the generated kernel
+    // publishes its value with one relaxed atomic into line `workgroup index mod stripes`; k_apply_reduces, right behind every request group that holds an
+    // AdvanceWorld, folds the lines into the live block's current resource cell and puts the identities back.  Not snapshot state
+    struct ReduceInbox { uint8_t* d = nullptr; uint32_t stripes = 0, n_words = 0; uint64_t applies = 0; } rd_inbox;
+    uint32_t rd_stripes = RD_STRIPES;    // lines of the inbox: the one constant, unless ggrs_dbg_set_reduce_stripes changed it before seal (scripts/bench_reduces.py measures the count)
+    bool has_reduces = false;            // some system has reduce bindings (set at seal)
     bool has_commands = false;           // some system has command bindings (set at seal)
     bool has_resources = false;          // the world has device resources (ggrs_hip_register_resource; set at seal)
     uint64_t dp_groups = 0;              // request groups launched with depth-parallel roles so far (kernel_info "depth_parallel_roles")
@@ -593,6 +603,23 @@ inline uint64_t rows_bytes_hot(const ggrs_world* w) {
 }
 inline bool world_has_effects(const ggrs_world* w) { for (auto& c : w->customs) if (c.n_fx) return true; return false; }
 inline bool world_has_resources(const ggrs_world* w) { return !w->resources.empty(); }
+inline bool world_has_reduces(const ggrs_world* w) { for (auto& c : w->customs) if (c.n_red) return true; return false; }
+// the distinct reduced words of the world in order of first use (systems in registration order, reduce bindings in order) with the op of the first binding that names
+// each; a binding to something that is not registered is skipped (reduces_validate refuses such a world, as it does a word with two ops)
+constexpr uint32_t RD_MAX_WORDS = GGRS_RESOURCE_MAX_BYTES / 4;
+struct ReducedWord { uint32_t res, word, op, wb, off, reg; };     // off: its byte offset inside a resource cell == inside an inbox line; reg: the r<reg> of the generated kernel that holds the word
+inline uint32_t reduced_words(const ggrs_world* w, ReducedWord* out) {
+    uint32_t n = 0;
+    for (auto& c : w->customs) for (uint32_t j = 0; j < c.n_red; ++j) {
+        if (c.dres[j] >= w->resources.size() || c.dword[j] >= w->resources[c.dres[j]].n_words) continue;
+        bool seen = false;
+        for (uint32_t k = 0; k < n; ++k) seen |= out[k].res == c.dres[j] && out[k].word == c.dword[j];
+        if (seen || n == RD_MAX_WORDS) continue;
+        const ggrs_world::Resource& r = w->resources[c.dres[j]];
+        out[n++] = ReducedWord{c.dres[j], c.dword[j], c.dop[j], r.word_bytes, r.off + c.dword[j] * r.word_bytes, r.reg + c.dword[j]};
+    }
+    return n;
+}
 inline uint32_t res_total_bytes(const ggrs_world* w) { uint32_t b = 0; for (auto& r : w->resources) b += r.word_bytes * r.n_words; return b; }
 // where each resource sits inside a cell and which registers of the generated kernel hold it: after every registration
 inline void res_layout(ggrs_world* w) {

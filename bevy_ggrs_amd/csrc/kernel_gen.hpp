@@ -234,9 +234,62 @@ inline std::string res_system_typedef(const ggrs_world* w, const ggrs_world::Res
     char b[128]; snprintf(b, sizeof b, "typedef ::GgrsResourcesT<%uu, 0x%xu> GgrsResources;\n", rs.n_bind, w8);
     return b;
 }
-inline std::string entity_text(bool effects, bool peers, bool commands, bool default_typedef = true, bool resources = false) {
+// ... in a world with reduce bindings (ggrs_hip_add_custom_system_reduces): e.reduce_*(j, v) combines v into the system's reduce binding j -- a plain register
+// combine into the lane's accumulator, which sys_custom hands in before the call and takes back after it: no memory, no atomic inside the user's code.  The op and
+// the word size are constants of the call site once ggrs_system is inlined.  Nothing is returned: a reducer cannot read the running value.  An accessor of the other
+// width, or of a binding the system does not have (rdw_ 0), does nothing -- as e.send_*.  Worlds without reduce bindings keep their entity text as it is.
+#define GGRS_RED_MEMBERS_TEXT \
+    "    ggrs_u64 rd_[8] = {}; unsigned char rdw_[8] = {}, rdo_[8] = {};   /* the system's reduce bindings: the lane's accumulator, the word's bytes (0: no such binding), the op */\n" \
+    "    template <typename U, typename I> __device__ static U rd_comb_(unsigned op, U x, U v) {\n" \
+    "        switch (op) {\n" \
+    "        case 0: return (U)(x + v);\n" \
+    "        case 1: return v < x ? v : x;\n" \
+    "        case 2: return v > x ? v : x;\n" \
+    "        case 3: return (I)v < (I)x ? v : x;\n" \
+    "        case 4: return (I)v > (I)x ? v : x;\n" \
+    "        case 5: return x | v;\n" \
+    "        case 6: return x & v;\n" \
+    "        case 7: return x ^ v;\n" \
+    "        default: return x;\n" \
+    "        }\n" \
+    "    }\n" \
+    "    __device__ void reduce_u32(int j, ggrs_u32 v) { if (rdw_[j] == 4) rd_[j] = rd_comb_<ggrs_u32, int>(rdo_[j], (ggrs_u32)rd_[j], v); }\n" \
+    "    __device__ void reduce_i32(int j, int v) { reduce_u32(j, (ggrs_u32)v); }   /* (signedness is the op's: MIN_I / MAX_I compare as int) */\n" \
+    "    __device__ void reduce_u64(int j, ggrs_u64 v) { if (rdw_[j] == 8) rd_[j] = rd_comb_<ggrs_u64, long long>(rdo_[j], rd_[j], v); }\n"
+// The wave-level reduction of such a world's accumulators at the end of the launch: the lane pattern of wave_xor32 (device_prelude.hpp) with the op as a template
+// literal -- add, umin, umax, smin, smax, or, and, xor, on 32 and on 64 bits.  `old` of every DPP move is the op's identity, so rows the row mask leaves out contribute
+// nothing; a 64-bit word moves as two halves and is combined as one 64-bit op.  Only in the text of worlds with reduce bindings.
+#define GGRS_REDUCE_WAVE_TEXT \
+    "template <unsigned OP, typename U, typename I> __device__ __forceinline__ U rd_comb(U x, U v) {\n" \
+    "    return OP == 0u ? (U)(x + v) : OP == 1u ? (v < x ? v : x) : OP == 2u ? (v > x ? v : x) : OP == 3u ? ((I)v < (I)x ? v : x) : OP == 4u ? ((I)v > (I)x ? v : x) : OP == 5u ? (x | v) : OP == 6u ? (x & v) : (x ^ v);\n" \
+    "}\n" \
+    "template <unsigned OP, int CTRL, int ROWS> __device__ __forceinline__ uint32_t rd_step32(uint32_t id, uint32_t v) {\n" \
+    "    return rd_comb<OP, uint32_t, int>(v, (uint32_t)__builtin_amdgcn_update_dpp((int)id, (int)v, CTRL, ROWS, 0xF, false));\n" \
+    "}\n" \
+    "template <unsigned OP, int CTRL, int ROWS> __device__ __forceinline__ uint64_t rd_step64(uint64_t id, uint64_t v) {\n" \
+    "    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)(id >> 32), (int)(uint32_t)(v >> 32), CTRL, ROWS, 0xF, false);\n" \
+    "    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)id, (int)(uint32_t)v, CTRL, ROWS, 0xF, false);\n" \
+    "    return rd_comb<OP, uint64_t, long long>(v, ((uint64_t)hi << 32) | lo);\n" \
+    "}\n" \
+    "#define GGRS_RD_LADDER(STEP) \\\n" \
+    "    v = STEP<OP, 0xB1, 0xF>(id, v);      /* quad_perm:[1,0,3,2] */ \\\n" \
+    "    v = STEP<OP, 0x4E, 0xF>(id, v);      /* quad_perm:[2,3,0,1] */ \\\n" \
+    "    v = STEP<OP, 0x141, 0xF>(id, v);     /* row_half_mirror */ \\\n" \
+    "    v = STEP<OP, 0x140, 0xF>(id, v);     /* row_mirror: every lane holds its row's value */ \\\n" \
+    "    v = STEP<OP, 0x142, 0xA>(id, v);     /* row_bcast:15 into rows 1 and 3 */ \\\n" \
+    "    v = STEP<OP, 0x143, 0xC>(id, v);     /* row_bcast:31 into rows 2 and 3: lane 63 holds the total */\n" \
+    "template <unsigned OP> __device__ __forceinline__ uint32_t wave_reduce32(uint32_t id, uint32_t v) {      // wave-uniform\n" \
+    "    GGRS_RD_LADDER(rd_step32)\n" \
+    "    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);\n" \
+    "}\n" \
+    "template <unsigned OP> __device__ __forceinline__ uint64_t wave_reduce64(uint64_t id, uint64_t v) {\n" \
+    "    GGRS_RD_LADDER(rd_step64)\n" \
+    "    return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), 63) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 63);\n" \
+    "}\n"
+inline std::string entity_text(bool effects, bool peers, bool commands, bool default_typedef = true, bool resources = false, bool reduces = false) {
     std::string t = effects ? GGRS_ENTITY_EFFECTS_TEXT : (peers ? GGRS_ENTITY_PEERS_TEXT : GGRS_ENTITY_TEXT);
     if (resources) t.insert(t.rfind("};\n"), GGRS_RES_MEMBERS_TEXT);
+    if (reduces) t.insert(t.rfind("};\n"), GGRS_RED_MEMBERS_TEXT);
     if (!commands) return t;
     const std::string head = "struct GgrsEntity {\n";
     const size_t at = t.find(head), end = t.rfind("};\n");
@@ -609,6 +662,8 @@ struct GgrsJitArgs {
     // DEVICE RESOURCES (host_world.hpp Resource; present only in worlds that have some): res_src = the CURRENT cell of the group's source block, read with scalar loads;
     // res_alt = the byte offset, inside a block, of the cell a store into the SOURCE block goes to -- its other cell; every other block takes RES_CELL_OFF (launch_jit)
     const unsigned char* res_src; ggrs_u32 res_alt;
+    // THE REDUCE INBOX of a world with reduce bindings (host_world.hpp ReduceInbox; present only in such worlds): lines of 64 bytes laid out like a resource cell
+    unsigned char* rd_inbox;
     ggrs_u32 cached_saves;                           // with nt: bit i = Save i is stored through the L2 all the same (the snapshot the NEXT group is expected to load)
     ggrs_u32 ff_blocks, ff_nvals, ff_g, ff_stride, ff_istride, ff_split, ff_self;   // entry e of row r: ff_rows[r * ff_stride + e * ff_istride]
     ggrs_u32 dt_bits[24], aux_bits[24]; int step_frame[24], step_confirmed[24]; ggrs_u32 spawn_count[24];
@@ -635,7 +690,7 @@ struct JitLayout {
     struct Member { uint32_t bytes = 0, save_dst = 0, save_rows = 0, save_len = 0, spawn_payload = 0, spawn_first = 0, live = 0, live_rows = 0, marks_dst = 0, save_pmask = 0, live_pmask = 0,
                     spawn_count = 0, n_inputs = 0, inputs = 0, save_tagok = 0, live_tagok = 0; } m;
 };
-struct JitNeeds { bool spawn, inputs, marks, box, vtags, devspawn, devstream, nr, peers, effects, commands, res; };
+struct JitNeeds { bool spawn, inputs, marks, box, vtags, devspawn, devstream, nr, peers, effects, commands, res, red; };
 // the distinct peer-bound columns of the world in order of first use (systems in registration order, peer bindings in order) and the components they belong to;
 // returns how many there are (more than GGRS_PEER_MAX_COLUMNS: only the first ones are written -- peers_validate refuses such a world)
 inline uint32_t peer_cols(const ggrs_world* w, uint32_t* cols, uint32_t* n_pres = nullptr, uint32_t* pres = nullptr) {
@@ -679,6 +734,7 @@ JitLayout jit_layout(const ggrs_world* w) {
     L.cap_saves = std::min<uint32_t>(MAX_TICK_SAVES, std::max<uint32_t>(2, w->max_depth + 1));
     L.cap_steps = std::min<uint32_t>(MAX_TICK_STEPS, std::max<uint32_t>(3, w->max_depth + 2));
     if (need.peers) L.cap_steps = 1;             // peer reads see the world at the START of the frame: the view is published per group, so a group holds one AdvanceWorld
+    if (need.red) L.cap_steps = 1;               // reductions land at the END of the frame too: k_apply_reduces runs behind the group's launch
     if (need.effects) L.cap_steps = 1;           // effects land at the END of the frame: the inbox is applied behind the group's launch, so a group ends on its one AdvanceWorld
     uint32_t fx_cols[GGRS_EFFECT_MAX_COLUMNS]; const uint32_t n_fx = std::min<uint32_t>(effect_cols(w, fx_cols), GGRS_EFFECT_MAX_COLUMNS);
     uint32_t pv_cols[GGRS_PEER_MAX_COLUMNS]; const uint32_t n_pv = std::min<uint32_t>(peer_cols(w, pv_cols), GGRS_PEER_MAX_COLUMNS);
@@ -700,7 +756,7 @@ JitLayout jit_layout(const ggrs_world* w) {
         F1("ggrs_u64*", gone, need.nr);
         FA("const unsigned char*", pv_col, n_pv, need.peers); F1("const ggrs_u64*", pv_vis, need.peers); F1("ggrs_u64", pv_len, need.peers);
         FA("unsigned char*", fx_col, n_fx, need.effects); F1("ggrs_u64", fx_len, need.effects);
-        F1("const unsigned char*", res_src, need.res);
+        F1("const unsigned char*", res_src, need.res); F1("unsigned char*", rd_inbox, need.red);
         FA("unsigned char*", save_dst, S, true); FA("ggrs_u64", save_rows, S, true); FA("ggrs_u64", save_len, S, true);
         FS("const unsigned char*", spawn_payload, need.spawn); FS("ggrs_u64", spawn_first, need.spawn);
         FA("int", save_frame, S, true); FA("ggrs_u32", save_pmask, S, true);
@@ -919,7 +975,8 @@ inline uint64_t jit_marks_rec_frames_off(const ggrs_world* w) { return align_up(
 inline uint64_t jit_marks_rec_bytes(const ggrs_world* w) { return jit_marks_rec_frames_off(w) + align_up(w->cap_pad * 4, ALIGN); }
 // which optional parts of the argument block this world's kernel reads
 JitNeeds jit_needs(const ggrs_world* w) {
-    JitNeeds n{false, false, false, false, false, false, false, false, false, false, false, false};
+    JitNeeds n{false, false, false, false, false, false, false, false, false, false, false, false, false};
+    n.red = world_has_reduces(w);
     n.res = world_has_resources(w);
     n.commands = world_has_commands(w);
     n.peers = world_has_peers(w);
@@ -1085,8 +1142,9 @@ struct JitGen {
                                     "#define GGRS_SP_READ %uu                                                           // sp_desc[GGRS_SP_READ x tiles + tile]: that tile has read its starting len\n",
                          2u + (unsigned)MAX_TICK_SAVES, 2u * (unsigned)MAX_TICK_STEPS);
         s += GGRS_FRAME_TEXT;
-        s += entity_text(need.effects, need.peers, need.commands, true, need.res);
+        s += entity_text(need.effects, need.peers, need.commands, true, need.res, need.red);
         if (need.res) s += GGRS_RESOURCES_TEXT;
+        if (need.red) s += GGRS_REDUCE_WAVE_TEXT;
         s += GGRS_COMPONENT_TEXT;
         s += GGRS_WORDS_TEXT;
         s += jit_layout_text(L);
@@ -1459,8 +1517,37 @@ struct JitGen {
         }
         sfmt(s, "                acc[%u] = rp_;\n            }\n", n_cks + 1);
     }
+    // reduce bindings: one per-lane accumulator register per reduced word, at the op's identity when the launch starts; sys_custom hands it to the system and takes it
+    // back, unit_tails reduces it over the wave and publishes the wave's value
+    std::string rd_lit(const ReducedWord& r) const { char b[40]; snprintf(b, sizeof b, r.wb == 8 ? "0x%llxull" : "0x%llxu", (unsigned long long)fx_identity(r.op, r.wb)); return b; }
+    void red_state() {
+        if (!need.red) return;
+        ReducedWord rw[RD_MAX_WORDS]; const uint32_t n = reduced_words(w, rw);
+        s += "    // REDUCE BINDINGS: this lane's accumulators, one per reduced resource word -- what the entity systems of this lane combined into it so far\n";
+        for (uint32_t k = 0; k < n; ++k)
+            sfmt(s, "    %s rd%u = %s;                                  // %s word %u, op %u: its identity\n", rw[k].wb == 8 ? "uint64_t" : "uint32_t", rw[k].reg, rd_lit(rw[k]).c_str(), file_name(w->resources[rw[k].res].name).c_str(), rw[k].word, rw[k].op);
+    }
+    // ... at a convergent point after the wave's unit: a DPP ladder of the op per accumulator, then ONE lane publishes the wave's value with one no-return atomic into the
+    // inbox line of its workgroup -- nothing when the value is the identity (the common case for rare events)
+    void red_publish() {
+        if (!need.red) return;
+        static const char* const fn[] = {"add", "min", "max", "min", "max", "or", "and", "xor"};
+        ReducedWord rw[RD_MAX_WORDS]; const uint32_t n = reduced_words(w, rw);
+        sfmt(s, "    {   // REDUCE BINDINGS: the wave's value of every accumulator, published by one lane into line `workgroup index mod %u` of the inbox\n"
+                "        unsigned char* const rl_ = a.rd_inbox + (tile %% %uu) * 64u;\n", (unsigned)w->rd_stripes, (unsigned)w->rd_stripes);
+        for (uint32_t k = 0; k < n; ++k) {
+            const bool sgn = rw[k].op == GGRS_EFFECT_MIN_I || rw[k].op == GGRS_EFFECT_MAX_I;
+            const char* ut = rw[k].wb == 8 ? "uint64_t" : "uint32_t";
+            const char* at = rw[k].wb == 8 ? (sgn ? "long long" : "uint64_t") : (sgn ? "int" : "uint32_t");
+            sfmt(s, "        { const %s v_ = wave_reduce%u<%uu>(%s, rd%u);\n"
+                    "          if (lane == 0u && v_ != %s) (void)__hip_atomic_fetch_%s((GGRS_G %s*)(rl_ + %uu), (%s)v_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }\n",
+                 ut, rw[k].wb * 8u, rw[k].op, rd_lit(rw[k]).c_str(), rw[k].reg, rd_lit(rw[k]).c_str(), fn[rw[k].op & 7u], at, rw[k].off, at);
+        }
+        s += "    }\n";
+    }
     void unit_state() {
         res_state();
+        red_state();
         for (uint32_t k = 0; k < n_cks; ++k) if (spec_memo[k]) {
             const std::string tail = chunk_expr(w->comps[cks_comp[k]], cks_comp[k], 8, spec_bytes[k] - 8);
             sfmt(s, "    uint32_t mt%u = (uint32_t)(%s); uint64_t ma%u = a.n_saves ? sea_tail_folded(mt%u, %uull) : 0ull;   // memoised tail of checksum spec %u, with the finish's K2 ^ K3 ^ bytes folded in\n", k, tail.c_str(), k, k, spec_bytes[k], k);
@@ -1665,6 +1752,13 @@ struct JitGen {
                 "            }\n",
              L.m.inputs, IN_STRIDE, hv, IB, hv, IB, f32_lit(d.fparam[0]).c_str(), f32_lit(d.fparam[1]).c_str(), f32_lit(d.fparam[3]).c_str(), x, x + 1, x + 2, v, v + 1, v + 2);
     }
+    // reduce binding j of a system as the world's reduced word (its register, width, offset; the WORLD's op for it -- reduces_validate: one op per word)
+    ReducedWord red_of(const ggrs_world::Custom& c, uint32_t j) const {
+        ReducedWord rw[RD_MAX_WORDS]; const uint32_t n = reduced_words(w, rw);
+        for (uint32_t k = 0; k < n; ++k) if (rw[k].res == c.dres[j] && rw[k].word == c.dword[j]) return rw[k];
+        return ReducedWord{0, 0, 0, 4, 0, 0};
+    }
+    bool red_dup(const ggrs_world::Custom& c, uint32_t j) const { for (uint32_t q = 0; q < j; ++q) if (c.dres[q] == c.dres[j] && c.dword[q] == c.dword[j]) return true; return false; }
     void sys_custom(size_t i, const ggrs_system_desc& d) {
         const ggrs_world::Custom& c = w->customs[d.comp[0]];
         s += "            if (alive_0";
@@ -1711,7 +1805,19 @@ struct JitGen {
         }
         // resource bindings: Res<R> -- the bound words as they stand at this point of the frame, by value
         for (uint32_t j = 0; j < c.n_res; ++j) sfmt(s, "                ent.rs_[%u] = (ggrs_u64)r%u;\n", j, w->resources[c.rres[j]].reg + c.rword[j]);
+        // reduce bindings: the lane's accumulator of the bound word goes in with the word's bytes and the op as literals, and comes back after the call (a second
+        // binding of the same word by the same system starts at the identity and is combined on the way out)
+        for (uint32_t j = 0; j < c.n_red; ++j) {
+            const ReducedWord r = red_of(c, j);
+            sfmt(s, "                ent.rd_[%u] = %s; ent.rdw_[%u] = %uu; ent.rdo_[%u] = %uu;\n", j, red_dup(c, j) ? rd_lit(r).c_str() : ("rd" + std::to_string(r.reg)).c_str(), j, r.wb, j, r.op);
+        }
         sfmt(s, "                ggrs_sys_%u::ggrs_system(ent, fr%zu);\n", d.comp[0], i);
+        for (uint32_t j = 0; j < c.n_red; ++j) {
+            const ReducedWord r = red_of(c, j);
+            const char* ut = r.wb == 8 ? "uint64_t" : "uint32_t";
+            if (!red_dup(c, j)) sfmt(s, "                rd%u = (%s)ent.rd_[%u];\n", r.reg, ut, j);
+            else sfmt(s, "                rd%u = rd_comb<%uu, %s, %s>(rd%u, (%s)ent.rd_[%u]);\n", r.reg, r.op, ut, r.wb == 8 ? "long long" : "int", r.reg, ut, j);
+        }
         if (need.devstream) s += "                if (ent.spawn_n) {                                        // e.spawn(n): the children are made after the frame's systems, from what THIS call left in e\n"
                                  "                    spn_0 = (uint32_t)ent.spawn_n;\n"
                                  "                    for (int b_ = 0; b_ < 8; ++b_) pw_[b_] = ent.w[b_];                 // (written to the children's records once their slots are known)\n"
@@ -1854,6 +1960,7 @@ struct JitGen {
                     "        if (lane == 0 && gone_w) atomicOr((unsigned long long*)(a.gone + gu), (unsigned long long)gone_w);\n"
                     "    }\n", need.marks ? " && !dis_0" : "");
         }
+        red_publish();
         s += "    }   // the wave's unit\n";
     }
     // ---- 13. this workgroup's partial rows

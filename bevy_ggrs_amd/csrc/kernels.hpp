@@ -697,6 +697,46 @@ __global__ __launch_bounds__(TPB) void k_apply_effects(FxApplyArgs a) {
     }
 }
 
+// THE REDUCE INBOX (ggrs_hip_add_custom_system_reduces; host_world.hpp ggrs_world::ReduceInbox).  Right behind every request group that holds an AdvanceWorld: ONE
+// wave; lane s loads line s of the inbox (the op's identity beyond the last line), the lane pattern of wave_xor32 folds the lines per word -- `old` is the identity,
+// so masked rows contribute nothing; a word moves as two halves and is combined as one op of its width --, one lane combines the result into the live block's current
+// resource cell, and every lane puts the identities back.  Plain loads and stores: the waves' atomics belong to an EARLIER launch; the kernel boundary is the
+// only synchronisation.
+struct RdApplyArgs {
+    uint8_t* inbox; uint8_t* cell;                          // cell: the live block's current resource cell, as the group's launch left it
+    uint32_t stripes, n_words;
+    uint32_t off[GGRS_RESOURCE_MAX_BYTES / 4], wb[GGRS_RESOURCE_MAX_BYTES / 4], op[GGRS_RESOURCE_MAX_BYTES / 4];
+};
+template <int CTRL, int ROWS> __device__ __forceinline__ uint64_t rd_fold_step(uint32_t op, uint32_t wb, uint64_t id, uint64_t v) {
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)(id >> 32), (int)(uint32_t)(v >> 32), CTRL, ROWS, 0xF, false);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)id, (int)(uint32_t)v, CTRL, ROWS, 0xF, false);
+    return wb == 8 ? fx_combine<uint64_t, int64_t>(op, v, ((uint64_t)hi << 32) | lo) : (uint64_t)fx_combine<uint32_t, int32_t>(op, (uint32_t)v, lo);
+}
+__global__ __launch_bounds__(64) void k_apply_reduces(RdApplyArgs a) {
+    const uint32_t lane = threadIdx.x;
+    for (uint32_t k = 0; k < a.n_words; ++k) {
+        const uint32_t op = a.op[k], wb = a.wb[k];
+        const uint64_t id = fx_identity(op, wb);
+        uint64_t v = id;
+        if (lane < a.stripes) {
+            uint8_t* const p = a.inbox + (uint64_t)lane * 64u + a.off[k];
+            if (wb == 8) { v = *reinterpret_cast<const uint64_t*>(p); *reinterpret_cast<uint64_t*>(p) = id; }
+            else { v = *reinterpret_cast<const uint32_t*>(p); *reinterpret_cast<uint32_t*>(p) = (uint32_t)id; }
+        }
+        v = rd_fold_step<0xB1, 0xF>(op, wb, id, v);          // quad_perm:[1,0,3,2]
+        v = rd_fold_step<0x4E, 0xF>(op, wb, id, v);          // quad_perm:[2,3,0,1]
+        v = rd_fold_step<0x141, 0xF>(op, wb, id, v);         // row_half_mirror
+        v = rd_fold_step<0x140, 0xF>(op, wb, id, v);         // row_mirror: every lane holds its row's value
+        v = rd_fold_step<0x142, 0xA>(op, wb, id, v);         // row_bcast:15 into rows 1 and 3
+        v = rd_fold_step<0x143, 0xC>(op, wb, id, v);         // row_bcast:31 into rows 2 and 3: lane 63 holds the total
+        if (lane == 63u && v != id) {
+            uint8_t* const c = a.cell + a.off[k];
+            if (wb == 8) *reinterpret_cast<uint64_t*>(c) = fx_combine<uint64_t, int64_t>(op, *reinterpret_cast<const uint64_t*>(c), v);
+            else *reinterpret_cast<uint32_t*>(c) = fx_combine<uint32_t, int32_t>(op, *reinterpret_cast<const uint32_t*>(c), (uint32_t)v);
+        }
+    }
+}
+
 // System-scope release + acquire on whatever CU / XCD the wave lands on: `buffer_wbl2 sc0 sc1` writes the XCD's dirty L2 lines back,
 // `buffer_inv sc0 sc1` drops its clean ones.  2048 single-wave workgroups cover all 8 XCDs (workgroup b lands on XCD b % 8).
 __global__ void k_flush_l2() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, ""); }

@@ -297,7 +297,7 @@ class World(WorldBase):
         self.capacity = capacity
 
     def add_custom_system(self, source: str, bindings: Sequence[tuple], iparam=(), fparam=(), name: str = "custom", peers: Sequence[tuple] = (), effects: Sequence[tuple] = (),
-                          commands: Sequence[tuple] = (), resources: Sequence[tuple] = ()):
+                          commands: Sequence[tuple] = (), resources: Sequence[tuple] = (), reduces: Sequence[tuple] = ()):
         """add_systems(GgrsSchedule, <your system>) for a per-entity system written in HIP C++ (ggrs_hip_add_custom_system):
         `source` defines `__device__ void ggrs_system(GgrsEntity& e, const GgrsFrame& f)`, `bindings` = [(comp, word), ..]
         are the words it sees as e.f32(i)/e.u32(i)/e.i32(i)/e.u64(i).  Compiled for gfx950 when added; a compile error raises
@@ -310,7 +310,10 @@ class World(WorldBase):
         `commands` = [(comp, flags), ..] (ggrs_hip_add_custom_system_commands): whole components of its OWN entity the system sees as
         Option<&mut C> -- `e.has(j)`, `e.opt_u32(j, k)` .. -- and, with CMD_INSERT / CMD_REMOVE in the flags, may `e.insert(j)` / `e.remove(j)`.
         `resources` = [(res, word), ..] (ggrs_hip_add_custom_system_resources): words of the world's device resources the system reads as
-        Res<R> -- `e.res_u32(j)` / `e.res_i32(j)` / `e.res_f32(j)` / `e.res_u64(j)`: the value as it stands at that point of the frame."""
+        Res<R> -- `e.res_u32(j)` / `e.res_i32(j)` / `e.res_f32(j)` / `e.res_u64(j)`: the value as it stands at that point of the frame.
+        `reduces` = [(res, word, op), ..] (ggrs_hip_add_custom_system_reduces): words of the world's device resources the system reduces into --
+        `e.reduce_u32(j, v)` / `e.reduce_i32(j, v)` / `e.reduce_u64(j, v)` combines v into reduce binding j with `op` (EFFECT_ADD, EFFECT_MIN_U, ..);
+        nothing is returned, and every reduction of a frame lands at the end of the frame."""
         d = _ffi.CustomSystemDesc()
         d.name, d.source, d.n_bindings = name.encode(), source.encode(), len(bindings)
         if len(bindings) > _ffi.CUSTOM_MAX_BINDINGS:
@@ -318,6 +321,23 @@ class World(WorldBase):
         for i, (c, w) in enumerate(bindings): d.comp[i], d.word[i] = c, w
         for i, v in enumerate(iparam): d.iparam[i] = v
         for i, v in enumerate(fparam): d.fparam[i] = v
+        if reduces:
+            if (len(peers) > _ffi.PEER_MAX_BINDINGS or len(effects) > _ffi.EFFECT_MAX_BINDINGS or len(commands) > _ffi.COMMAND_MAX_BINDINGS or len(resources) > _ffi.RESOURCE_MAX_BINDINGS
+                    or len(reduces) > _ffi.REDUCE_MAX_BINDINGS):
+                raise ValueError(f"at most {_ffi.PEER_MAX_BINDINGS} peer, {_ffi.EFFECT_MAX_BINDINGS} effect, {_ffi.COMMAND_MAX_BINDINGS} command, {_ffi.RESOURCE_MAX_BINDINGS} resource and "
+                                 f"{_ffi.REDUCE_MAX_BINDINGS} reduce bindings")
+            pb = (_ffi.PeerBinding * max(1, len(peers)))()
+            for j, (c, w) in enumerate(peers): pb[j].comp, pb[j].word = c, w
+            eb = (_ffi.EffectBinding * max(1, len(effects)))()
+            for j, (c, w, op) in enumerate(effects): eb[j].comp, eb[j].word, eb[j].op = c, w, op
+            cb = (_ffi.CommandBinding * max(1, len(commands)))()
+            for j, (c, fl) in enumerate(commands): cb[j].comp, cb[j].flags = c, fl
+            rb = (_ffi.ResourceBinding * max(1, len(resources)))()
+            for j, (r, w) in enumerate(resources): rb[j].res, rb[j].word = r, w
+            db = (_ffi.ReduceBinding * len(reduces))()
+            for j, (r, w, op) in enumerate(reduces): db[j].res, db[j].word, db[j].op = r, w, op
+            self._check(self._lib.ggrs_hip_add_custom_system_reduces(self._p, C.byref(d), pb, len(peers), eb, len(effects), cb, len(commands), rb, len(resources), db, len(reduces)))
+            return
         if resources:
             if len(peers) > _ffi.PEER_MAX_BINDINGS or len(effects) > _ffi.EFFECT_MAX_BINDINGS or len(commands) > _ffi.COMMAND_MAX_BINDINGS or len(resources) > _ffi.RESOURCE_MAX_BINDINGS:
                 raise ValueError(f"at most {_ffi.PEER_MAX_BINDINGS} peer, {_ffi.EFFECT_MAX_BINDINGS} effect, {_ffi.COMMAND_MAX_BINDINGS} command and {_ffi.RESOURCE_MAX_BINDINGS} resource bindings")

@@ -396,6 +396,44 @@ int ggrs_hip_add_custom_system_resources(ggrs_world* w, const ggrs_custom_system
 int ggrs_hip_resource_read(ggrs_world* w, uint32_t res_id, void* words_out);
 int ggrs_hip_resource_write(ggrs_world* w, uint32_t res_id, const void* words);
 
+/* ENTITY SYSTEMS THAT REDUCE INTO A DEVICE RESOURCE.  The sentence above narrows here: an entity system cannot WRITE a resource word, but it can REDUCE into one --
+ *
+ *     fn census(mut c: ResMut<Census>, q: Query<&Hp, With<Rollback>>) { for hp in &q { c.alive += 1; c.lowest = c.lowest.min(hp.0); } }
+ *
+ * a score, a count of living enemies, a "somebody pressed the switch" flag, the lowest health on the field, a running total.
+ *
+ *   ggrs_hip_add_custom_system_reduces   ggrs_hip_add_custom_system_resources plus REDUCE BINDINGS: red[j] = {res, word, op} names one word of a registered device
+ *                                  resource and one of the eight GGRS_EFFECT_* ops (ADD wrapping, MIN_U, MAX_U, MIN_I, MAX_I, OR, AND, XOR: integer, commutative and
+ *                                  associative, so the result does not depend on lane order -- bit-exact parity and replay determinism survive; 4- and 8-byte words;
+ *                                  float words are not offered: the result would depend on order).  With n_red == 0 the call behaves exactly as
+ *                                  ggrs_hip_add_custom_system_resources.  At most GGRS_REDUCE_MAX_BINDINGS per system.
+ *   inside ggrs_system             e.reduce_u32(j, v) / e.reduce_i32(j, v) combine v into reduce binding j, a 4-byte word; e.reduce_u64(j, v) into an 8-byte word.
+ *                                  They return nothing: a reducer cannot read the running value (Bevy's iteration order inside one system is unspecified, so a partial
+ *                                  sum is not a defined value).  An accessor of the wrong width for its word does nothing, as e.send_* does.  A system may call an
+ *                                  accessor any number of times, also under a condition, also in the call that despawns its entity.  Only entities for which the system
+ *                                  runs contribute: live entities that have every component the system binds.
+ *
+ * ALL REDUCTIONS OF A FRAME LAND AT THE END OF THE FRAME: after the frame's systems and spawns, before anything observes the frame -- a SaveWorld, its checksum part,
+ * ggrs_hip_resource_read, the next frame, the next group.  The word then holds  op(value the frame's resource systems left, every v sent in the frame).
+ * Seal makes this equal to Bevy's sequential ResMut write: no system registered AT OR AFTER a word's first reducer may read or write that word (an entity system's
+ * e.res_* binding of it, a resource system binding it), a word has one op in the whole world, the word is 4 or 8 bytes, the resource exists.  A resource system
+ * registered BEFORE the reducer may read and reset the word (the "count per frame" idiom); an entity system registered before it reads last frame's result.  Each
+ * refusal is GGRS_E_INVALID with a message naming the system and the resource.
+ * How it runs: a per-lane accumulator register per reduced word (the op's identity at launch start); e.reduce_* is a register combine, no memory and no atomic
+ * inside the user's code; at the end of the launch each wave reduces its accumulators with a DPP ladder and one lane publishes the wave's value with one no-return
+ * atomic into a striped inbox (nothing when the value is the identity); one small launch right behind the group's (k_apply_reduces) folds the stripes into the live
+ * block's current resource cell and puts the identities back.  Such a world runs one AdvanceWorld per launch, as a world with effect bindings does.
+ * Refused with a message: ggrs_hip_fanout_step_branches, and everything device resources already refuse (ggrs_hip_fanout_step works).  Peers, effects, commands and
+ * read bindings in the same world and the same system are allowed.  Out of scope: float reductions, a reducer that reads the running value. */
+typedef struct { uint32_t res; uint32_t word; uint32_t op; } ggrs_reduce_binding;   /* reduce binding j = word `word` of resource `res`, combined with GGRS_EFFECT_* `op` */
+#define GGRS_REDUCE_MAX_BINDINGS 8
+int ggrs_hip_add_custom_system_reduces(ggrs_world* w, const ggrs_custom_system_desc* desc,
+                                       const ggrs_peer_binding* peers, uint32_t n_peers,
+                                       const ggrs_effect_binding* effects, uint32_t n_effects,
+                                       const ggrs_command_binding* cmds, uint32_t n_cmds,
+                                       const ggrs_resource_binding* res, uint32_t n_res,
+                                       const ggrs_reduce_binding* red, uint32_t n_red);
+
 /* ComponentSnapshotPlugin<S: Strategy> (snapshot/strategy.rs:22-40, component_snapshot.rs:42-63): what a snapshot HOLDS of a component is
  * S::Stored, produced by S::store and turned back by S::load / S::update -- CopyStrategy / CloneStrategy (Stored == the component, bitwise for
  * POD) are what ggrs_hip_register_component gives; this is the open door next to them: quantised, packed or partial snapshots.
@@ -759,7 +797,7 @@ int ggrs_hip_host_timeline(ggrs_world* w, int enable, double* us_out, uint64_t* 
  * Introspection: which kernel serves this world's request lists right now and why, what kind of arena
  * it lives on, whether the run-time compiler (libhiprtc.so, dlopen'ed) is available.  `key=value` lines,
  * NUL-terminated; *needed = bytes incl. the NUL, min(cap, *needed) are copied.  Keys: sealed, arena,
- * arena_bytes, hiprtc, generated_kernel, generated_kernel_origin, request_group_kernel, checksum_fold, kernarg_bytes, group_caps, specialised_kernel, slots_covered, row_versions, peer_view (worlds with peer bindings), effect_inbox (worlds with effect bindings), device_resources (worlds with device resources), depth_parallel_roles.
+ * arena_bytes, hiprtc, generated_kernel, generated_kernel_origin, request_group_kernel, checksum_fold, kernarg_bytes, group_caps, specialised_kernel, slots_covered, row_versions, peer_view (worlds with peer bindings), effect_inbox (worlds with effect bindings), device_resources (worlds with device resources), depth_parallel_roles, reduce_inbox (worlds with reduce bindings: stripes, words, applies so far).
  * ------------------------------------------------------------------------------------------- */
 int ggrs_hip_world_kernel_info(ggrs_world* w, char* buf, uint64_t cap, uint64_t* needed);
 

@@ -132,6 +132,17 @@ pub const GGRS_RESOURCE_MAX: usize = 8;
 pub const GGRS_RESOURCE_MAX_BYTES: usize = 64;
 pub const GGRS_RESOURCE_MAX_BINDINGS: usize = 8;
 
+/// One reduce binding of `ggrs_hip_add_custom_system_reduces`: a word of a device-resident rollback resource an entity system reduces into through
+/// `e.reduce_*(j, v)`, combined with `op` (one of `GGRS_EFFECT_*`); every reduction of a frame lands at the end of the frame.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct ggrs_reduce_binding {
+    pub res: u32,
+    pub word: u32,
+    pub op: u32,
+}
+pub const GGRS_REDUCE_MAX_BINDINGS: usize = 8;
+
 /// A once-per-frame system over device resources (`ggrs_hip_add_resource_system`): `source` defines `ggrs_resource_system(GgrsResources& r, const GgrsFrame& f)`.
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -250,6 +261,7 @@ unsafe extern "C" {
     pub fn ggrs_hip_add_custom_system_effects(w: *mut ggrs_world, desc: *const ggrs_custom_system_desc, peers: *const ggrs_peer_binding, n_peers: u32, effects: *const ggrs_effect_binding, n_effects: u32) -> c_int;
     pub fn ggrs_hip_add_custom_system_commands(w: *mut ggrs_world, desc: *const ggrs_custom_system_desc, peers: *const ggrs_peer_binding, n_peers: u32, effects: *const ggrs_effect_binding, n_effects: u32, cmds: *const ggrs_command_binding, n_cmds: u32) -> c_int;
     pub fn ggrs_hip_add_custom_system_resources(w: *mut ggrs_world, desc: *const ggrs_custom_system_desc, peers: *const ggrs_peer_binding, n_peers: u32, effects: *const ggrs_effect_binding, n_effects: u32, cmds: *const ggrs_command_binding, n_cmds: u32, res: *const ggrs_resource_binding, n_res: u32) -> c_int;
+    pub fn ggrs_hip_add_custom_system_reduces(w: *mut ggrs_world, desc: *const ggrs_custom_system_desc, peers: *const ggrs_peer_binding, n_peers: u32, effects: *const ggrs_effect_binding, n_effects: u32, cmds: *const ggrs_command_binding, n_cmds: u32, res: *const ggrs_resource_binding, n_res: u32, red: *const ggrs_reduce_binding, n_red: u32) -> c_int;
     pub fn ggrs_hip_register_resource(w: *mut ggrs_world, name: *const c_char, word_bytes: u32, n_words: u32, init_words: *const c_void, res_id_out: *mut u32) -> c_int;
     pub fn ggrs_hip_checksum_resource(w: *mut ggrs_world, res_id: u32, word_idx: *const u32, n_words: u32) -> c_int;
     pub fn ggrs_hip_add_resource_system(w: *mut ggrs_world, desc: *const ggrs_resource_system_desc) -> c_int;
