@@ -133,6 +133,7 @@ void ggrs_hip_world_destroy(ggrs_world* w) {
     peer_view_release(w);
     fx_inbox_release(w);
     rd_inbox_release(w);
+    rx_inbox_release(w);
     for (void* p : w->spec_allocs) (void)hipFree(p);
     if (w->h_results) (void)hipHostFree(w->h_results);
     if (w->h_stage) (void)hipHostFree(w->h_stage);
@@ -240,7 +241,16 @@ int ggrs_hip_add_custom_system_resources(ggrs_world* w, const ggrs_custom_system
 // (include/ggrs_hip.h).  Which resource, word and width a binding names is checked at seal (host_seal.hpp reduces_validate), with the registration-order rule
 int ggrs_hip_add_custom_system_reduces(ggrs_world* w, const ggrs_custom_system_desc* d, const ggrs_peer_binding* peers, uint32_t n_peers, const ggrs_effect_binding* effects, uint32_t n_effects,
                                        const ggrs_command_binding* cmds, uint32_t n_cmds, const ggrs_resource_binding* res, uint32_t n_res, const ggrs_reduce_binding* red, uint32_t n_red) {
+    return ggrs_hip_add_custom_system_remote(w, d, peers, n_peers, effects, n_effects, cmds, n_cmds, res, n_res, red, n_red, nullptr, 0);
+}
+// ... and with remote bindings: components of OTHER entities the system inserts or removes through e.send_insert / e.send_remove(slot, j), and e.send_despawn(slot),
+// landing at the end of the frame (include/ggrs_hip.h).  The registration-order rules and what a component must be are checked at seal (host_seal.hpp remote_validate)
+int ggrs_hip_add_custom_system_remote(ggrs_world* w, const ggrs_custom_system_desc* d, const ggrs_peer_binding* peers, uint32_t n_peers, const ggrs_effect_binding* effects, uint32_t n_effects,
+                                      const ggrs_command_binding* cmds, uint32_t n_cmds, const ggrs_resource_binding* res, uint32_t n_res, const ggrs_reduce_binding* red, uint32_t n_red,
+                                      const ggrs_remote_binding* rem, uint32_t n_rem) {
     if (!w || !d || !d->source) return GGRS_E_INVALID;
+    if (n_rem > GGRS_REMOTE_MAX_BINDINGS) return w->fail(GGRS_E_INVALID, "custom system '%s': at most %d remote bindings (GGRS_REMOTE_MAX_BINDINGS), not %u", d->name ? d->name : "custom", GGRS_REMOTE_MAX_BINDINGS, n_rem);
+    if (n_rem && !rem) return w->fail(GGRS_E_INVALID, "custom system: n_rem = %u but rem is NULL", n_rem);
     if (n_red > GGRS_REDUCE_MAX_BINDINGS) return w->fail(GGRS_E_INVALID, "custom system '%s': at most %d reduce bindings (GGRS_REDUCE_MAX_BINDINGS), not %u", d->name ? d->name : "custom", GGRS_REDUCE_MAX_BINDINGS, n_red);
     if (n_red && !red) return w->fail(GGRS_E_INVALID, "custom system: n_red = %u but red is NULL", n_red);
     if (n_res > GGRS_RESOURCE_MAX_BINDINGS) return w->fail(GGRS_E_INVALID, "custom system '%s': at most %d resource bindings (GGRS_RESOURCE_MAX_BINDINGS), not %u", d->name ? d->name : "custom", GGRS_RESOURCE_MAX_BINDINGS, n_res);
@@ -299,6 +309,18 @@ int ggrs_hip_add_custom_system_reduces(ggrs_world* w, const ggrs_custom_system_d
         c.dres[j] = red[j].res; c.dword[j] = red[j].word; c.dop[j] = red[j].op;
     }
     c.n_red = n_red;
+    for (uint32_t j = 0; j < n_rem; ++j) {
+        const uint32_t fl = rem[j].flags;
+        if (!fl || (fl & ~(GGRS_REMOTE_INSERT | GGRS_REMOTE_REMOVE | GGRS_REMOTE_DESPAWN))) return w->fail(GGRS_E_INVALID, "custom system '%s': remote binding %u has flags %x, which are none of GGRS_REMOTE_*", c.name.c_str(), j, fl);
+        if (fl & GGRS_REMOTE_DESPAWN) {
+            if (fl != GGRS_REMOTE_DESPAWN || rem[j].comp != GGRS_REMOTE_ENTITY)
+                return w->fail(GGRS_E_INVALID, "custom system '%s': remote binding %u has GGRS_REMOTE_DESPAWN: such a binding names no component (comp = GGRS_REMOTE_ENTITY) and carries no other flag", c.name.c_str(), j);
+        } else if (rem[j].comp >= w->comps.size()) return w->fail(GGRS_E_INVALID, "custom system '%s': remote binding %u names component %u, which is not registered", c.name.c_str(), j, rem[j].comp);
+        for (uint32_t q = 0; q < j; ++q) if (c.xcomp[q] == rem[j].comp)
+            return w->fail(GGRS_E_INVALID, "custom system '%s': remote bindings %u and %u name the same component %u: a component has one remote binding per system", c.name.c_str(), q, j, rem[j].comp);
+        c.xcomp[j] = rem[j].comp; c.xflags[j] = fl;
+    }
+    c.n_rem = n_rem;
     DeviceGuard dg(w);
     c.source = d->source;
     c.may_defer = source_has_token(c.source, "despawn_rollback") || source_has_token(c.source, "kill");
@@ -442,7 +464,7 @@ int ggrs_hip_generated_kernel_source(ggrs_world* w, uint32_t form, char* buf, ui
     if (!w || (form != GGRS_KERNEL_FORM_TILES && form != GGRS_KERNEL_FORM_STEADY)) return GGRS_E_INVALID;
     if (!w->sealed) {
         if (!w->layout_only) { DeviceGuard dg(w); const int rc = seal(w); if (rc) return rc; }
-        else { build_layout(w); const int prc = peers_validate(w); if (prc) return prc; const int frc = effects_validate(w); if (frc) return frc; const int crc = commands_validate(w); if (crc) return crc; const int rrc = resources_validate(w); if (rrc) return rrc; const int drc = reduces_validate(w); if (drc) return drc; }   // host arithmetic only: offsets of every mask and column; the peer-, effect-, command-, resource and reduce rules
+        else { build_layout(w); const int prc = peers_validate(w); if (prc) return prc; const int frc = effects_validate(w); if (frc) return frc; const int crc = commands_validate(w); if (crc) return crc; const int rrc = resources_validate(w); if (rrc) return rrc; const int drc = reduces_validate(w); if (drc) return drc; const int xrc = remote_validate(w); if (xrc) return xrc; }   // host arithmetic only: offsets of every mask and column; the peer-, effect-, command-, resource, reduce and remote rules
     }
     std::string src;
     if (!jit_source(w, src)) return w->fail(GGRS_E_INVALID, "the kernel generator does not cover this world (a system writes a live-only component, or more than %u four-byte units / %u words per entity)", JIT_MAX_UNITS, JIT_MAX_COLS);
@@ -483,6 +505,15 @@ int64_t ggrs_dbg_reduce_inbox(ggrs_world* w, void* out, uint64_t cap) {
     DeviceGuard dg(w);
     const uint64_t bytes = (uint64_t)w->rd_inbox.stripes * 64u;
     if (hipMemcpyAsync(out, w->rd_inbox.d, std::min(cap, bytes), hipMemcpyDeviceToHost, w->stream) != hipSuccess || hipStreamSynchronize(w->stream) != hipSuccess) return -1;
+    return (int64_t)bytes;
+}
+//   ggrs_dbg_remote_inbox      the words of the remote inbox (one u32 per slot of the padded capacity) after everything queued on the world's stream has run: returns
+//                              how many bytes the inbox has (min(cap, that) are copied), -1 for a world without one -- it must hold zeros whenever a host call returns
+int64_t ggrs_dbg_remote_inbox(ggrs_world* w, void* out, uint64_t cap) {
+    if (!w || !w->rx_inbox.d) return -1;
+    DeviceGuard dg(w);
+    const uint64_t bytes = w->cap_pad * 4u;
+    if (hipMemcpyAsync(out, w->rx_inbox.d, std::min(cap, bytes), hipMemcpyDeviceToHost, w->stream) != hipSuccess || hipStreamSynchronize(w->stream) != hipSuccess) return -1;
     return (int64_t)bytes;
 }
 int ggrs_dbg_set_spec_shapes(ggrs_world* w, int n) { if (!w || n < 1 || n > 64) return -1; w->spec_shapes = n; return 0; }
@@ -997,6 +1028,8 @@ int ggrs_hip_world_kernel_info(ggrs_world* w, char* buf, uint64_t cap, uint64_t*
                                                       "(two cells per block; the live block's is cell " + std::to_string(w->live.res_cell) + "), stored with every snapshot's header");
         if (w->has_reduces) add("reduce_inbox", std::to_string(w->rd_inbox.stripes) + " stripes of 64 bytes laid out like a resource cell, " + std::to_string(w->rd_inbox.n_words) + " reduced words holding the ops' identities, folded into the live block's current resource cell right behind every request group that holds an AdvanceWorld (" +
                                                 std::to_string(w->rd_inbox.applies) + " applies so far)");
+        if (w->has_remote) add("remote_inbox", "one u32 per slot, " + std::to_string(w->rx_inbox.n_comps) + " remotely commanded components (bit 0 despawn, bits 1 + 2k / 2 + 2k insert / remove of component k), zeros whenever no group-and-apply pair is in flight, "
+                                               "applied to the live block's masks and columns right behind every request group that holds an AdvanceWorld and ahead of the effects (" + std::to_string(w->rx_inbox.applies) + " applies so far)");
         if (w->has_effects) add("effect_inbox", std::to_string(w->fx_inbox.n_cols) + " linear columns holding the ops' identities, applied to the live block right behind every request group that holds an AdvanceWorld (" +
                                                std::to_string(w->fx_inbox.applies) + " applies so far)");
         add("branch_marker_record_bytes", std::to_string(w->jit_marks ? jit_marks_rec_bytes(w) : 0));      // per retained branch of ggrs_hip_fanout_step_branches (0: the kernel keeps no markers)

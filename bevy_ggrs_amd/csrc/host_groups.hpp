@@ -253,6 +253,7 @@ int launch_jit(ggrs_world* w, hipFunction_t fn, uint32_t gx, uint32_t gy, uint32
     if (streamed) { j.sp_ticket_base = w->sp_ticket_base; w->sp_ticket_base += (uint64_t)(gx + j.ff_blocks) * gy * gz; }   // every workgroup takes one ticket
     j.skip_count = (w->prof && j.vtags) ? reinterpret_cast<ggrs_u64*>(w->d_skip) : nullptr;
     if (w->has_resources) { const int rrc = res_cells_for_launch(w, j); if (rrc) return rrc; }
+    if (w->has_remote) { j.rx_inbox = w->rx_inbox.d; j.rx_len = j.len; }   // remote bindings: the inbox, and the source block's len == RollbackOrdered::len at the start of the group's one AdvanceWorld (in a world with effects the kernel reads fx_len, the same value)
     if (w->has_reduces) j.rd_inbox = w->rd_inbox.d;                    // reduce bindings: every launch of the kernel knows the inbox (only one that runs an AdvanceWorld publishes into it)
     jit_pack(*w->jl, j, w->jit_argbuf.data());
     void* params[] = {w->jit_argbuf.data()};
@@ -465,6 +466,7 @@ inline bool lazy_live_allowed(const ggrs_world* w) {                 // (what a 
     if (!w->lazy_live_on || w->live_handed_out || w->has_nr || w->marks_possible || w->device_results_only || jit_dev_spawn(w)) return false;
     if (world_has_peers(w)) return false;                            // peer bindings: the next group's publish reads what this one leaves -- every block is written (no deferred Saves either)
     if (world_has_effects(w)) return false;                          // effect bindings: k_apply_effects combines the frame's sends into the live block -- every group writes it (no deferred Saves either)
+    if (world_has_remote(w)) return false;                           // remote bindings: k_apply_remote edits the live block's masks and columns behind the group's launch -- every group writes it (no deferred Saves either)
     if (world_has_reduces(w)) return false;                          // reduce bindings: k_apply_reduces combines the frame's reductions into the live block's resource cell -- every group writes it (no deferred Saves either)
     for (uint8_t e : w->col_ext) if (e) return false;
     return true;
@@ -646,6 +648,7 @@ int group_take(ggrs_world* w, const ggrs_request& r, GgrsJitArgs& j, GroupState&
     if (r.kind == GGRS_REQ_SAVE) {
         if (j.n_saves == w->cap_saves || j.n_saves == saves_room) return GGRS_OK;
         if (w->has_effects && j.n_steps) return GGRS_OK;               // effect bindings: the group ends ON its AdvanceWorld ([Load?] Save* Advance) -- this Save opens the next group and reads the live block after the apply
+        if (w->has_remote && j.n_steps) return GGRS_OK;                // remote bindings: the same shape -- the Save reads the masks and columns k_apply_remote left
         if (w->has_reduces && j.n_steps) return GGRS_OK;               // reduce bindings: the same shape -- the Save stores the resource words k_apply_reduces left
         *taken = true; return group_save(w, gs, j);
     }
@@ -680,6 +683,7 @@ int group_take(ggrs_world* w, const ggrs_request& r, GgrsJitArgs& j, GroupState&
     const uint32_t dtb = r.dt_bits ? r.dt_bits : dt_bits_for_frame(w->fps, w->frame);
     if (w->dev_spawn) touch_bundle(w->spawn_customs[w->systems[w->jit_spawn_sys].comp[0]]);   // any frame may append rows of the bundle: its columns and presence masks are new after every step
     for (uint32_t c = 0; w->cmd_mut_comps >> c; ++c) if ((w->cmd_mut_comps >> c) & 1ull) ver_touch_comp(w, c);   // command bindings: any frame may insert or remove the component -- its mask (and its columns) are new after every step
+    for (uint32_t c = 0; w->rem_comps >> c; ++c) if ((w->rem_comps >> c) & 1ull) ver_touch_comp(w, c);   // remote bindings: any frame may insert or remove the component in any entity, behind the launch (k_apply_remote) -- the host never learns which slots were hit, so its mask and columns are new after every step
     j.dt_bits[step] = dtb; j.step_frame[step] = w->frame; j.step_confirmed[step] = w->confirmed;
     if (w->jit_box_sys >= 0) j.aux_bits[step] = box_aux_bits(w, dtb);
     j.n_inputs[step] = (uint8_t)std::min<uint32_t>(r.n_inputs, w->max_players);
@@ -836,6 +840,33 @@ int apply_effects(ggrs_world* w) {
     ++fx.applies;
     return GGRS_OK;
 }
+// Remote bindings: the commands the group's launch ORed into the inbox are applied to the live block's alive word, presence words and columns -- and the inbox zeroed
+// -- by a launch of its own right BEHIND the group's and AHEAD of apply_effects (effects then see the alive and presence bits the commands left), enqueued with the
+// group (never lazily): no host entry point ever sees a pending inbox.  The kernel boundary is the only synchronisation.
+int apply_remote(ggrs_world* w) {
+    ggrs_world::RemoteInbox& rx = w->rx_inbox;
+    ++rx.applies;
+    const uint64_t len = w->len;                                       // the end-of-frame len (host-decided spawns only: the host knows it)
+    if (!len) return GGRS_OK;
+    RxApplyArgs a; memset(&a, 0, sizeof a);
+    a.live = w->live.ptr; a.inbox = rx.d; a.len = len; a.off_alive = w->off_alive; a.n_comps = rx.n_comps; a.n_units = (uint32_t)((len + 63) / 64);
+    uint32_t nw = 0;
+    for (uint32_t k = 0; k < rx.n_comps; ++k) {
+        const Comp& T = w->comps[rx.comp[k]];
+        a.off_present[k] = w->off_present[rx.comp[k]]; a.w_base[k] = nw; a.wb[k] = T.word_bytes; a.ts[k] = w->col_ts[T.col_base];
+        a.n_words[k] = (rx.flags[k] & GGRS_REMOTE_INSERT) ? T.n_words : 0u;     // (a component that is only ever removed writes no word)
+        for (uint32_t q = 0; q < a.n_words[k] && nw < (uint32_t)RX_MAX_WORDS; ++q, ++nw) {
+            a.col_off[nw] = w->col_off[T.col_base + q];
+            if (T.defaults.size() >= (size_t)(q + 1) * T.word_bytes) memcpy(&a.dflt[nw], &T.defaults[(size_t)q * T.word_bytes], T.word_bytes);      // (little-endian: the low bytes; else zeros)
+        }
+    }
+    const double t0 = w->tl.on ? tl_now_us() : 0;
+    { ProfScope ps(w, GGRS_KERNEL_ADVANCE, 4ull * len); hipLaunchKernelGGL(k_apply_remote, dim3((a.n_units + TPB / 64 - 1) / (TPB / 64)), dim3(TPB), 0, w->stream, a); }
+    HIPCHK(w, hipGetLastError());
+    if (w->tl.on) { w->tl.launch_us += tl_now_us() - t0; ++w->tl.n_launches; }
+    w->spin_n = 0; w->batch_ev_attached = false;                       // this launch comes after whatever carried the batch event, and after a finalize that was the list's last GPU operation
+    return GGRS_OK;
+}
 // Reduce bindings: what the waves of the group's launch left in the striped inbox is folded into the live block's CURRENT resource cell -- the one that launch just
 // made current (launch_jit flipped the record at enqueue) -- and the identities are put back, by a one-wave launch right BEHIND the group's, enqueued with it (never
 // lazily): no host entry point ever sees a pending inbox.  The kernel boundary is the only synchronisation.
@@ -879,7 +910,7 @@ int run_request_groups_gen(ggrs_world* w, const ggrs_request* reqs, uint32_t n, 
         }
         // ---- dead / lazy / deferred: what the group need not store
         // (effect bindings: every live sender's sends reach the inbox exactly once per simulated frame and are applied to a live block the group WROTE -- no group is dead)
-        const bool dead = !w->dev_spawn && !w->has_effects && !w->has_reduces && group_is_dead(w, reqs, i, n, j.save_frame, j.n_saves, gs.spawn_req != nullptr);
+        const bool dead = !w->dev_spawn && !w->has_effects && !w->has_reduces && !w->has_remote && group_is_dead(w, reqs, i, n, j.save_frame, j.n_saves, gs.spawn_req != nullptr);
         if (dead) { for (uint32_t k = 0; k < j.n_saves; ++k) j.save_dst[k] = nullptr; j.skip_live = 1; }
         const uint64_t cover = w->dev_spawn ? w->capacity : std::max(gs.cover, w->len);      // (device-decided spawns: the host only knows a bound of len)
         group_lazy_live(w, j, gs, dead, i >= n, cover);
@@ -893,7 +924,7 @@ int run_request_groups_gen(ggrs_world* w, const ggrs_request* reqs, uint32_t n, 
         // ---- policy: per-tile grid of 256-slot workgroups, depth-parallel roles
         const JitPolicy pol = jit_group_policy(cover, j.n_saves, j.src_is_live != 0, save0_bytes, group_aliases(j, wrote_live), w->jit_marks, w->dev_spawn, w->nt_copy);
         j.nt = pol.nt; j.cached_saves = pol.cached_saves; j.nt_loads = pol.nt_loads; j.dp_s = pol.dp_s;
-        if (w->has_effects || w->has_reduces) j.dp_s = 0;               // (every depth-parallel role runs the group's steps: a role more is every send, and every reduction, once more)
+        if (w->has_effects || w->has_reduces || w->has_remote) j.dp_s = 0;   // (every depth-parallel role runs the group's steps: a role more is every send, every reduction and every remote command once more)
         const bool launch = j.n_ops || !j.src_is_live;
         // identical checksum-only groups (speculative branches) ride in one launch; a batch already fills the chip, so no roles
         const bool batchable = dead && j.n_saves > 0 && !w->jit_marks && cover <= JIT_BATCH_MAX_SLOTS && !w->has_peers;   // (peer bindings: one view, published per launch)
@@ -912,19 +943,21 @@ int run_request_groups_gen(ggrs_world* w, const ggrs_request* reqs, uint32_t n, 
             if (w->has_effects) attach_effects(w, j);
             const bool applies = launch && w->has_effects && j.n_steps;
             const bool reduces = launch && w->has_reduces && j.n_steps;
+            const bool remotes = launch && w->has_remote && j.n_steps;
             if (launch) {
                 if (j.dp_s) ++w->dp_groups;
                 hipFunction_t fn = jit_spec_for(w, j);
                 if (!fn) fn = w->jit_fn;
                 // nothing is queued behind this kernel when its rows are folded later (or there is nothing to fold) and no spawn system follows:
                 // the batch event of an enqueued list then completes WITH it (no marker packet between this tick's kernel and the next one's)
-                const bool last_gpu_op = fold.route != FoldRoute::Finalize && !gs.spawn_req && !w->prof && !applies && !reduces;
+                const bool last_gpu_op = fold.route != FoldRoute::Finalize && !gs.spawn_req && !w->prof && !applies && !reduces && !remotes;
                 hipEvent_t done = last_gpu_op ? w->batch_ev : nullptr;
                 rc = launch_jit(w, fn, w->dev_spawn && jit_dev_stream(w) ? g : jit_grid(g), j.dp_s ? (j.n_saves + j.dp_s) / j.dp_s : 1u, 1, jit_lane_fold_bytes(w, n_cks, j.n_saves), j, bytes_slot * w->len, done); if (rc) return rc;
                 w->batch_ev_attached = done != nullptr;
             }
             group_close(w, gs, j.n_saves, dead, wrote_live);
             rc = fold_route_record(w, j, fold, g, n_cks, res_base + ns, wait); if (rc) return rc;
+            if (remotes) { rc = apply_remote(w); if (rc) return rc; }     // ahead of the effects: they apply to the alive and presence bits the remote commands left
             if (applies) { rc = apply_effects(w); if (rc) return rc; }
             if (reduces) { rc = apply_reduces(w); if (rc) return rc; }
         }
@@ -996,6 +1029,7 @@ int branch_marks_reserve(ggrs_world* w, uint64_t n) {
 int validate_branch_step(ggrs_world* w, const ggrs_branch_step& st) {
     if (!w->gen_ok) return w->fail(GGRS_E_INVALID, "branch steps need the generated request-group kernel, which this world does not have: %s", w->jit_status.c_str());
     if (w->has_peers) return w->fail(GGRS_E_INVALID, "branch steps are not available for worlds with peer bindings (a member runs several frames per launch, a peer read sees the start of ONE frame): use ggrs_hip_fanout_step");
+    if (w->has_remote) return w->fail(GGRS_E_INVALID, "branch steps (ggrs_hip_fanout_step_branches) are not available for worlds with remote bindings (ggrs_hip_add_custom_system_remote: a member runs several frames per launch, the remote commands of ONE frame are applied behind a launch): use ggrs_hip_fanout_step");
     if (w->has_reduces) return w->fail(GGRS_E_INVALID, "branch steps (ggrs_hip_fanout_step_branches) are not available for worlds with reduce bindings (ggrs_hip_add_custom_system_reduces: a member runs several frames per launch, the reductions of ONE frame are applied behind a launch): use ggrs_hip_fanout_step");
     if (w->has_effects) return w->fail(GGRS_E_INVALID, "branch steps are not available for worlds with effect bindings (a member runs several frames per launch, the sends of ONE frame are applied behind a launch): use ggrs_hip_fanout_step");
     // a retained block's presence masks are decided by the branch's own versions, which say nothing of what the systems inserted or removed: not offered in this version

@@ -45,6 +45,7 @@ int peers_validate(ggrs_world* w) {
         if (d.kind == GGRS_SYS_TTL_DESPAWN || d.kind == GGRS_SYS_SAT_SUB_DESPAWN) return true;
         if (d.kind != GGRS_SYS_CUSTOM) return false;
         const std::string& src = w->customs[d.comp[0]].source;
+        for (uint32_t j = 0; j < w->customs[d.comp[0]].n_rem; ++j) if (w->customs[d.comp[0]].xflags[j] & GGRS_REMOTE_DESPAWN) return true;      // a remote despawner (e.send_despawn)
         return source_has_token(src, "despawn") || source_has_token(src, "despawn_rollback") || source_has_token(src, "kill");
     };
     uint32_t cols[GGRS_PEER_MAX_COLUMNS];
@@ -223,6 +224,75 @@ int reduces_validate(ggrs_world* w) {
     }
     return GGRS_OK;
 }
+void rx_inbox_release(ggrs_world* w) {
+    if (w->rx_inbox.d) (void)hipFree(w->rx_inbox.d);
+    w->rx_inbox = ggrs_world::RemoteInbox{};
+}
+// Remote bindings (ggrs_hip_add_custom_system_remote): the rules under which "all remote commands of a frame land at the END of the frame" equals Bevy's deferred
+// Commands under a chained schedule -- nothing that runs at or after a component's first remote commander looks at the component, and nothing that would not have run
+// for a despawned entity has side effects on others --, and what the first version refuses (everything effects_validate refuses).  After build_layout; no device needed
+int remote_validate(ggrs_world* w) {
+    if (!world_has_remote(w)) return GGRS_OK;
+    auto cname = [&](uint32_t c) { return w->comps[c].name.c_str(); };
+    // does system k bind component cc: own, peer and command bindings, effect columns, the words of a built-in kind
+    auto binds = [&](size_t k, uint32_t cc) {
+        const ggrs_system_desc& d = w->systems[k];
+        switch (d.kind) {
+        case GGRS_SYS_PARTICLES_UPDATE: return d.comp[0] == cc || d.comp[1] == cc;
+        case GGRS_SYS_TTL_DESPAWN: case GGRS_SYS_ADD_U32: case GGRS_SYS_SAT_SUB_DESPAWN: return d.comp[0] == cc;
+        case GGRS_SYS_BOX_MOVE: return d.comp[0] == cc || d.comp[1] == cc || d.comp[2] == cc;
+        case GGRS_SYS_CUSTOM: {
+            const ggrs_world::Custom& c = w->customs[d.comp[0]];
+            for (uint32_t b = 0; b < c.n_bind; ++b) if (c.comp[b] == cc) return true;
+            for (uint32_t j = 0; j < c.n_peer; ++j) if (c.pcomp[j] == cc) return true;
+            for (uint32_t j = 0; j < c.n_cmd; ++j) if (c.ccomp[j] == cc) return true;
+            for (uint32_t j = 0; j < c.n_fx; ++j) if (c.fcomp[j] == cc) return true;
+            return false;
+        }
+        default: return false;       // a spawn system appends rows: entities spawned in this frame cannot be hit
+        }
+    };
+    uint32_t comps[GGRS_REMOTE_MAX_COMPONENTS];
+    const uint32_t n_comps = remote_comps(w, comps);
+    if (n_comps > GGRS_REMOTE_MAX_COMPONENTS) return w->fail(GGRS_E_INVALID, "remote bindings: %u distinct remotely commanded components in this world, at most %d (GGRS_REMOTE_MAX_COMPONENTS)", n_comps, GGRS_REMOTE_MAX_COMPONENTS);
+    uint64_t seen = 0;                                                  // the components some earlier system commands remotely
+    long despawner = -1;                                                // the first system with GGRS_REMOTE_DESPAWN
+    for (size_t i = 0; i < w->systems.size(); ++i) {
+        if (w->systems[i].kind != GGRS_SYS_CUSTOM) continue;
+        const ggrs_world::Custom& c = w->customs[w->systems[i].comp[0]];
+        const char* nm = c.name.c_str();
+        if (despawner >= 0 && (c.n_peer || c.n_fx || c.n_red || c.n_rem)) {
+            const ggrs_world::Custom& dc = w->customs[w->systems[(size_t)despawner].comp[0]];
+            const char* what = c.n_peer ? "peer" : (c.n_fx ? "effect" : (c.n_red ? "reduce" : "remote"));
+            return w->fail(GGRS_E_INVALID, "custom system '%s' (system %zu) has %s bindings and is registered after custom system '%s' (system %ld), which can despawn other entities (GGRS_REMOTE_DESPAWN on GGRS_REMOTE_ENTITY): "
+                                           "no system registered after a remote despawner has peer, effect, reduce or remote bindings -- in Bevy it would not run for the despawned entity", nm, i, what, dc.name.c_str(), despawner);
+        }
+        for (uint32_t j = 0; j < c.n_rem; ++j) {
+            if (c.xflags[j] & GGRS_REMOTE_DESPAWN) { if (despawner < 0) despawner = (long)i; continue; }
+            const uint32_t cc = c.xcomp[j];
+            const Comp& T = w->comps[cc];
+            if (T.s_n_words) return w->fail(GGRS_E_INVALID, "custom system '%s': remote binding %u names component %u ('%s'), which has a Strategy: remote commands on such a component are not supported", nm, j, cc, cname(cc));
+            if (T.no_rollback) return w->fail(GGRS_E_INVALID, "custom system '%s': remote binding %u names component %u ('%s'), which is not registered for rollback (GGRS_COMP_NO_ROLLBACK): remote commands on such a component are not supported", nm, j, cc, cname(cc));
+            for (auto& o : w->customs) for (uint32_t q = 0; q < o.n_fx; ++q) if (o.fcomp[q] == cc)
+                return w->fail(GGRS_E_INVALID, "custom system '%s': remote binding %u names component %u ('%s'), word %u of which is an effect column of custom system '%s': remote commands and effects on the same component are not supported in this version "
+                                               "(the order of \"insert replaces\" against \"effect lands\" would depend on registration order)", nm, j, cc, cname(cc), o.fword[q], o.name.c_str());
+            if (cc < 64 && !((seen >> cc) & 1ull)) {
+                seen |= 1ull << cc;                                     // system i is the component's first remote commander
+                for (size_t k = i; k < w->systems.size(); ++k) if (binds(k, cc)) {
+                    const char* kn = w->systems[k].kind == GGRS_SYS_CUSTOM ? w->customs[w->systems[k].comp[0]].name.c_str() : "built-in";
+                    if (k == i) return w->fail(GGRS_E_INVALID, "custom system '%s' (system %zu) remotely commands component %u ('%s') and binds that component itself: a remote commander does not bind a component it commands", nm, i, cc, cname(cc));
+                    return w->fail(GGRS_E_INVALID, "custom system '%s' (system %zu) remotely commands component %u ('%s'), which system %zu ('%s'), registered after it, binds: no system registered at or after the first remote commander of a component binds that component", nm, i, cc, cname(cc), k, kn);
+                }
+            }
+        }
+    }
+    const JitNeeds need = jit_needs(w);
+    if (need.marks) return w->fail(GGRS_E_INVALID, "remote bindings are not available in a world that keeps RollbackDespawned markers (a system that can call despawn_rollback(), or names the `kill` field)");
+    if (need.devspawn) return w->fail(GGRS_E_INVALID, "remote bindings are not available in a world that spawns on the device with e.spawn(n) (GGRS_SPAWN_PAYLOAD_PARENT)");
+    if (w->flags & (GGRS_WORLD_NO_GROUPS | GGRS_WORLD_UNFUSED)) return w->fail(GGRS_E_INVALID, "remote bindings need the generated request-group kernel, which a GGRS_WORLD_NO_GROUPS / GGRS_WORLD_UNFUSED world does not have");
+    if (!w->knobs.tick_jit) return w->fail(GGRS_E_INVALID, "remote bindings need the generated request-group kernel, which this world does not have: disabled (GGRS_TICK_JIT=0)");
+    return GGRS_OK;
+}
 int seal(ggrs_world* w) {
     if (w->layout_only) return w->fail(GGRS_E_NO_DEVICE, "GGRS_WORLD_LAYOUT_ONLY world: there is no device behind it");
     if (w->sealed) return GGRS_OK;
@@ -237,6 +307,7 @@ int seal(ggrs_world* w) {
     peer_view_release(w);
     fx_inbox_release(w);
     rd_inbox_release(w);
+    rx_inbox_release(w);
     if (w->h_results) { (void)hipHostFree(w->h_results); w->h_results = nullptr; w->d_results = nullptr; }
     if (w->h_stage) { (void)hipHostFree(w->h_stage); w->h_stage = nullptr; w->d_hstage = nullptr; }
     if (w->h_rows) { (void)hipHostFree(w->h_rows); w->h_rows = nullptr; w->d_rows = nullptr; }
@@ -304,6 +375,9 @@ int seal_impl(ggrs_world* w) {
     { const int crc = commands_validate(w); if (crc) return crc; }
     { const int rrc = resources_validate(w); if (rrc) return rrc; }
     { const int drc = reduces_validate(w); if (drc) return drc; }
+    { const int xrc = remote_validate(w); if (xrc) return xrc; }
+    w->has_remote = world_has_remote(w);
+    w->rem_comps = world_rem_comps(w);
     w->has_reduces = world_has_reduces(w);
     w->has_resources = world_has_resources(w);
     w->has_peers = world_has_peers(w);
@@ -373,6 +447,8 @@ int seal_impl(ggrs_world* w) {
         return w->fail(GGRS_E_INVALID, "effect bindings (ggrs_hip_add_custom_system_effects) need the generated request-group kernel, which this world does not have: %s", w->jit_status.c_str());
     if (w->has_commands && !w->gen_ok)
         return w->fail(GGRS_E_INVALID, "command bindings (ggrs_hip_add_custom_system_commands) need the generated request-group kernel, which this world does not have: %s", w->jit_status.c_str());
+    if (w->has_remote && !w->gen_ok)
+        return w->fail(GGRS_E_INVALID, "remote bindings (ggrs_hip_add_custom_system_remote) need the generated request-group kernel, which this world does not have: %s", w->jit_status.c_str());
     if (w->has_resources && !w->gen_ok)
         return w->fail(GGRS_E_INVALID, "device resources ('%s', ggrs_hip_register_resource) need the generated request-group kernel, which this world does not have: %s", w->resources[0].name.c_str(), w->jit_status.c_str());
     for (auto& sd : w->systems) if (sd.kind == GGRS_SYS_SPAWN_CUSTOM && !(w->gen_ok && w->jit_spawn_sys >= 0))
@@ -520,6 +596,14 @@ int seal_impl(ggrs_world* w) {
         HIPCHK(w, hipMalloc((void**)&rd.d, fill.size()));
         HIPCHK(w, hipMemcpyAsync(rd.d, fill.data(), fill.size(), hipMemcpyHostToDevice, w->stream));
         HIPCHK(w, hipStreamSynchronize(w->stream));                    // (the host buffer dies here)
+    }
+    if (w->has_remote) {
+        // the remote inbox: one u32 per slot of the padded capacity, zeroed -- what it holds whenever no group-and-apply pair is in flight
+        ggrs_world::RemoteInbox& rx = w->rx_inbox;
+        rx = ggrs_world::RemoteInbox{};
+        rx.n_comps = remote_comps(w, rx.comp, rx.flags);
+        HIPCHK(w, hipMalloc((void**)&rx.d, w->cap_pad * 4u));
+        HIPCHK(w, hipMemsetAsync(rx.d, 0, w->cap_pad * 4u, w->stream));
     }
     if (w->vtags) { HIPCHK(w, hipMalloc((void**)&w->d_skip, 8)); HIPCHK(w, hipMemsetAsync(w->d_skip, 0, 8, w->stream)); }
     if (w->dev_spawn) {

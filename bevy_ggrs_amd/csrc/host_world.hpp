@@ -177,6 +177,9 @@ struct ggrs_world {
         uint32_t n_res = 0, rres[GGRS_RESOURCE_MAX_BINDINGS] = {}, rword[GGRS_RESOURCE_MAX_BINDINGS] = {};
         // reduce bindings (ggrs_hip_add_custom_system_reduces): words of the world's device resources the system combines a value into through e.reduce_*(j, v)
         uint32_t n_red = 0, dres[GGRS_REDUCE_MAX_BINDINGS] = {}, dword[GGRS_REDUCE_MAX_BINDINGS] = {}, dop[GGRS_REDUCE_MAX_BINDINGS] = {};
+        // remote bindings (ggrs_hip_add_custom_system_remote): components of OTHER entities the system may insert / remove through e.send_insert / e.send_remove(slot, j);
+        // a binding with GGRS_REMOTE_DESPAWN names no component (xcomp = GGRS_REMOTE_ENTITY): e.send_despawn(slot)
+        uint32_t n_rem = 0, xcomp[GGRS_REMOTE_MAX_BINDINGS] = {}, xflags[GGRS_REMOTE_MAX_BINDINGS] = {};
     };
     std::vector<Custom> customs;
     // DEVICE RESOURCES (ggrs_hip_register_resource): a few 4- or 8-byte words per world, carried by every wave of the generated kernel in wave-uniform registers.
@@ -211,6 +214,13 @@ struct ggrs_world {
     struct ReduceInbox { uint8_t* d = nullptr; uint32_t stripes = 0, n_words = 0; uint64_t applies = 0; } rd_inbox;
     uint32_t rd_stripes = RD_STRIPES;    // lines of the inbox: the one constant, unless ggrs_dbg_set_reduce_stripes changed it before seal (scripts/bench_reduces.py measures the count)
     bool has_reduces = false;            // some system has reduce bindings (set at seal)
+    // THE REMOTE INBOX of a world with remote bindings (allocated at seal): ONE linear array of cap_pad u32, one word per slot -- bit 0 = despawn, bits 1 + 2k and
+    // 2 + 2k = insert and remove of the world's k-th remotely commanded component (remote_comps) -- all zeros whenever no group-and-apply pair is in flight.  The
+    // generated kernel ORs into it with relaxed atomics; k_apply_remote, right behind every request group that holds an AdvanceWorld and ahead of k_apply_effects,
+    // edits the live block's masks and columns and zeroes it again.  Not snapshot state
+    struct RemoteInbox { uint32_t* d = nullptr; uint32_t n_comps = 0, comp[GGRS_REMOTE_MAX_COMPONENTS] = {}, flags[GGRS_REMOTE_MAX_COMPONENTS] = {}; uint64_t applies = 0; } rx_inbox;
+    bool has_remote = false;             // some system has remote bindings (set at seal)
+    uint64_t rem_comps = 0;              // bit c = some system may remotely insert or remove component c: its mask and columns get fresh versions with every AdvanceWorld (set at seal)
     bool has_commands = false;           // some system has command bindings (set at seal)
     bool has_resources = false;          // the world has device resources (ggrs_hip_register_resource; set at seal)
     uint64_t dp_groups = 0;              // request groups launched with depth-parallel roles so far (kernel_info "depth_parallel_roles")
@@ -512,6 +522,7 @@ void build_layout(ggrs_world* w) {
             for (uint32_t b = 0; b < c.n_bind; ++b) mark(c.comp[b], c.word[b], 1, true);      // a bound word may be written
             for (uint32_t j = 0; j < c.n_fx; ++j) mark(c.fcomp[j], c.fword[j], 1, true);     // an effect column: written (in OTHER entities) by the frame's sends -- every Save stores it, a sender counts as its writer
             for (uint32_t j = 0; j < c.n_cmd; ++j) if (c.ccomp[j] < w->comps.size()) mark(c.ccomp[j], 0, w->comps[c.ccomp[j]].n_words, true);   // a command-bound component: every word may be written (Option<&mut C>, insert)
+            for (uint32_t j = 0; j < c.n_rem; ++j) if (c.xcomp[j] < w->comps.size()) mark(c.xcomp[j], 0, w->comps[c.xcomp[j]].n_words, true);   // a remotely commanded component: a remote insert writes every word (in OTHER entities) -- every Save stores them, the commander counts as their writer
         } break;
         default: break;     // spawn systems append rows: whoever runs them versions the bundle (run_spawn_systems / the fused path in host_groups.hpp)
         }
@@ -603,6 +614,28 @@ inline uint64_t rows_bytes_hot(const ggrs_world* w) {
 }
 inline bool world_has_effects(const ggrs_world* w) { for (auto& c : w->customs) if (c.n_fx) return true; return false; }
 inline bool world_has_resources(const ggrs_world* w) { return !w->resources.empty(); }
+inline bool world_has_remote(const ggrs_world* w) { for (auto& c : w->customs) if (c.n_rem) return true; return false; }
+// the distinct remotely commanded components of the world in order of first use (systems in registration order, remote bindings in order) and the GGRS_REMOTE_* flags
+// some binding declares for each; returns how many there are (more than GGRS_REMOTE_MAX_COMPONENTS: only the first ones are written -- remote_validate refuses such a
+// world).  Component k owns bits 1 + 2k (insert) and 2 + 2k (remove) of an inbox word.  A despawn binding names no component
+inline uint32_t remote_comps(const ggrs_world* w, uint32_t* comps, uint32_t* flags = nullptr) {
+    uint32_t n = 0;
+    for (auto& c : w->customs) for (uint32_t j = 0; j < c.n_rem; ++j) {
+        if (c.xcomp[j] >= w->comps.size()) continue;
+        uint32_t k = 0;
+        while (k < n && k < GGRS_REMOTE_MAX_COMPONENTS && comps[k] != c.xcomp[j]) ++k;
+        if (k < n && k < GGRS_REMOTE_MAX_COMPONENTS) { if (flags) flags[k] |= c.xflags[j]; continue; }
+        if (n < GGRS_REMOTE_MAX_COMPONENTS) { comps[n] = c.xcomp[j]; if (flags) flags[n] = c.xflags[j]; }
+        ++n;
+    }
+    return n;
+}
+inline uint64_t world_rem_comps(const ggrs_world* w) {
+    uint32_t comps[GGRS_REMOTE_MAX_COMPONENTS]; const uint32_t n = std::min<uint32_t>(remote_comps(w, comps), GGRS_REMOTE_MAX_COMPONENTS);
+    uint64_t m = 0;
+    for (uint32_t k = 0; k < n; ++k) if (comps[k] < 64) m |= 1ull << comps[k];
+    return m;
+}
 inline bool world_has_reduces(const ggrs_world* w) { for (auto& c : w->customs) if (c.n_red) return true; return false; }
 // the distinct reduced words of the world in order of first use (systems in registration order, reduce bindings in order) with the op of the first binding that names
 // each; a binding to something that is not registered is skipped (reduces_validate refuses such a world, as it does a word with two ops)
@@ -637,6 +670,7 @@ inline uint64_t world_cmd_mut_comps(const ggrs_world* w) {
 // does this world's kernel keep value tags?  (what a layout-only world -- `make aot` -- can tell as well)
 inline bool vtags_policy(const ggrs_world* w) {
     if (world_has_effects(w)) return false;     // effect bindings: k_apply_effects rewrites live columns behind the group's launch, which a tag written by that launch would not know
+    if (world_has_remote(w)) return false;      // remote bindings: k_apply_remote writes defaults into live columns behind the group's launch, likewise
     return w->knobs.row_versions && w->tag_cols && (w->vtags_mode == 1 || (w->vtags_mode < 0 && rows_bytes_hot(w) * w->capacity >= VTAGS_MIN_BYTES));
 }
 

@@ -286,16 +286,36 @@ inline std::string res_system_typedef(const ggrs_world* w, const ggrs_world::Res
     "    GGRS_RD_LADDER(rd_step64)\n" \
     "    return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), 63) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 63);\n" \
     "}\n"
-inline std::string entity_text(bool effects, bool peers, bool commands, bool default_typedef = true, bool resources = false, bool reduces = false) {
+// ... in a world with remote bindings (ggrs_hip_add_custom_system_remote): e.send_insert(slot, j) / e.send_remove(slot, j) / e.send_despawn(slot) command ANOTHER
+// entity -- a bounds test against the len of the frame's source block, then ONE relaxed agent-scope atomic OR into the slot's word of the world's linear REMOTE INBOX
+// (host_world.hpp RemoteInbox) whose result is unused: a native no-return global_atomic_or, no compare-and-swap loop.  OR is commutative, associative and idempotent:
+// the word does not depend on which lanes arrive, in which order, or how often.  rxb_[j] = the bit of the inbox word that means "insert the component of remote
+// binding j" (remove is the next bit; despawn is bit 0).  The entity is the TEMPLATE of GGRS_CMD_MEMBERS_TEXT with three more parameters -- GGRS_XI / GGRS_XR: bit j =
+// remote binding j may be inserted / removed; GGRS_XD: the system may despawn -- and the accessors carry enable_if: a call whose flag was not declared, or whose j is
+// not a constant, finds no member and does not compile.  Worlds without remote bindings keep their entity text as it is.
+#define GGRS_REMOTE_MEMBERS_TEXT \
+    "    unsigned long rx_ = 0ul; ggrs_u64 rxn_ = 0ull; unsigned char rxb_[4] = {};   /* the remote inbox, the len of the frame's source block (0: a system without remote bindings sends nothing), the insert bit of remote binding j */\n" \
+    "    __device__ void rx_or_(ggrs_u64 s, ggrs_u32 m) const {    /* dropped beyond the start-of-frame len */\n" \
+    "        if (s < rxn_) (void)__hip_atomic_fetch_or((GGRS_G ggrs_u32*)(rx_ + (s << 2)), m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n" \
+    "    }\n" \
+    "    __device__ void send_insert(ggrs_u64 s, int j) const __attribute__((enable_if(j >= 0 && j < 4 && ((GGRS_XI >> j) & 1u), \"e.send_insert(slot, j): remote binding j (a constant) must be declared with GGRS_REMOTE_INSERT\"))) { rx_or_(s, 1u << rxb_[j]); }\n" \
+    "    __device__ void send_remove(ggrs_u64 s, int j) const __attribute__((enable_if(j >= 0 && j < 4 && ((GGRS_XR >> j) & 1u), \"e.send_remove(slot, j): remote binding j (a constant) must be declared with GGRS_REMOTE_REMOVE\"))) { rx_or_(s, 2u << rxb_[j]); }\n" \
+    "    __device__ void send_despawn(ggrs_u64 s) const __attribute__((enable_if(GGRS_XD != 0u, \"e.send_despawn(slot): the system must have a remote binding with GGRS_REMOTE_DESPAWN\"))) { rx_or_(s, 1u); }\n"
+inline std::string entity_text(bool effects, bool peers, bool commands, bool default_typedef = true, bool resources = false, bool reduces = false, bool remote = false) {
     std::string t = effects ? GGRS_ENTITY_EFFECTS_TEXT : (peers ? GGRS_ENTITY_PEERS_TEXT : GGRS_ENTITY_TEXT);
     if (resources) t.insert(t.rfind("};\n"), GGRS_RES_MEMBERS_TEXT);
     if (reduces) t.insert(t.rfind("};\n"), GGRS_RED_MEMBERS_TEXT);
-    if (!commands) return t;
+    if (!commands && !remote) return t;
     const std::string head = "struct GgrsEntity {\n";
+    if (remote && !effects && !peers) t.insert(0, "#ifndef GGRS_G\n#define GGRS_G __attribute__((address_space(1)))\n#endif\n");
+    if (remote) t.insert(t.rfind("};\n"), GGRS_REMOTE_MEMBERS_TEXT);
     const size_t at = t.find(head), end = t.rfind("};\n");
-    t.insert(end, GGRS_CMD_MEMBERS_TEXT);
+    if (commands) t.insert(end, GGRS_CMD_MEMBERS_TEXT);
+    if (remote) t.replace(at, head.size(), "template <unsigned GGRS_IM, unsigned GGRS_RM, unsigned GGRS_CB, unsigned GGRS_XI, unsigned GGRS_XR, unsigned GGRS_XD> struct GgrsEntityC {\n");
+    else
     t.replace(at, head.size(), "template <unsigned GGRS_IM, unsigned GGRS_RM, unsigned GGRS_CB> struct GgrsEntityC {\n");
     if (!default_typedef) return t;
+    if (remote) return t + "typedef GgrsEntityC<0u, 0u, 0u, 0u, 0u, 0u> GgrsEntity;  // what a system without command or remote bindings, and the spawner, see\n";
     return t + "typedef GgrsEntityC<0u, 0u, 0u> GgrsEntity;              // what a system without command bindings, and the spawner, see\n";
 }
 // the first of command binding j's words in GgrsEntity::opt (the words of the bindings before it)
@@ -305,14 +325,25 @@ inline uint32_t cmd_word_base(const ggrs_world* w, const ggrs_world::Custom& c, 
     return b;
 }
 // the entity type of ONE system of a world with command bindings, as the line that goes in front of its source
-inline std::string cmd_entity_typedef(const ggrs_world* w, const ggrs_world::Custom& c) {
+inline std::string cmd_entity_typedef(const ggrs_world* w, const ggrs_world::Custom& c, bool remote = false) {
     uint32_t im = 0, rm = 0, cb = 0;
     for (uint32_t j = 0; j < c.n_cmd; ++j) {
         if (c.cflags[j] & GGRS_CMD_INSERT) im |= 1u << j;
         if (c.cflags[j] & GGRS_CMD_REMOVE) rm |= 1u << j;
         cb |= (cmd_word_base(w, c, j) & 15u) << (4 * j);
     }
-    char b[160]; snprintf(b, sizeof b, "typedef ::GgrsEntityC<0x%xu, 0x%xu, 0x%xu> GgrsEntity;\n", im, rm, cb);
+    char b[200];
+    if (remote) {                                                      // the text has the three remote parameters (entity_text): what THIS system declared
+        uint32_t xi = 0, xr = 0, xd = 0;
+        for (uint32_t j = 0; j < c.n_rem; ++j) {
+            if (c.xflags[j] & GGRS_REMOTE_INSERT) xi |= 1u << j;
+            if (c.xflags[j] & GGRS_REMOTE_REMOVE) xr |= 1u << j;
+            if (c.xflags[j] & GGRS_REMOTE_DESPAWN) xd = 1u;
+        }
+        snprintf(b, sizeof b, "typedef ::GgrsEntityC<0x%xu, 0x%xu, 0x%xu, 0x%xu, 0x%xu, %uu> GgrsEntity;\n", im, rm, cb, xi, xr, xd);
+        return b;
+    }
+    snprintf(b, sizeof b, "typedef ::GgrsEntityC<0x%xu, 0x%xu, 0x%xu> GgrsEntity;\n", im, rm, cb);
     return b;
 }
 
@@ -664,6 +695,9 @@ struct GgrsJitArgs {
     const unsigned char* res_src; ggrs_u32 res_alt;
     // THE REDUCE INBOX of a world with reduce bindings (host_world.hpp ReduceInbox; present only in such worlds): lines of 64 bytes laid out like a resource cell
     unsigned char* rd_inbox;
+    // THE REMOTE INBOX of a world with remote bindings (host_world.hpp RemoteInbox; present only in such worlds): one u32 per slot; rx_len = the len of the group's source
+    // block, as fx_len -- which the kernel reads instead in a world that also has effect bindings (rx_len is then absent from the device block)
+    ggrs_u32* rx_inbox; ggrs_u64 rx_len;
     ggrs_u32 cached_saves;                           // with nt: bit i = Save i is stored through the L2 all the same (the snapshot the NEXT group is expected to load)
     ggrs_u32 ff_blocks, ff_nvals, ff_g, ff_stride, ff_istride, ff_split, ff_self;   // entry e of row r: ff_rows[r * ff_stride + e * ff_istride]
     ggrs_u32 dt_bits[24], aux_bits[24]; int step_frame[24], step_confirmed[24]; ggrs_u32 spawn_count[24];
@@ -690,7 +724,7 @@ struct JitLayout {
     struct Member { uint32_t bytes = 0, save_dst = 0, save_rows = 0, save_len = 0, spawn_payload = 0, spawn_first = 0, live = 0, live_rows = 0, marks_dst = 0, save_pmask = 0, live_pmask = 0,
                     spawn_count = 0, n_inputs = 0, inputs = 0, save_tagok = 0, live_tagok = 0; } m;
 };
-struct JitNeeds { bool spawn, inputs, marks, box, vtags, devspawn, devstream, nr, peers, effects, commands, res, red; };
+struct JitNeeds { bool spawn, inputs, marks, box, vtags, devspawn, devstream, nr, peers, effects, commands, res, red, rem; };
 // the distinct peer-bound columns of the world in order of first use (systems in registration order, peer bindings in order) and the components they belong to;
 // returns how many there are (more than GGRS_PEER_MAX_COLUMNS: only the first ones are written -- peers_validate refuses such a world)
 inline uint32_t peer_cols(const ggrs_world* w, uint32_t* cols, uint32_t* n_pres = nullptr, uint32_t* pres = nullptr) {
@@ -734,6 +768,7 @@ JitLayout jit_layout(const ggrs_world* w) {
     L.cap_saves = std::min<uint32_t>(MAX_TICK_SAVES, std::max<uint32_t>(2, w->max_depth + 1));
     L.cap_steps = std::min<uint32_t>(MAX_TICK_STEPS, std::max<uint32_t>(3, w->max_depth + 2));
     if (need.peers) L.cap_steps = 1;             // peer reads see the world at the START of the frame: the view is published per group, so a group holds one AdvanceWorld
+    if (need.rem) L.cap_steps = 1;               // remote commands land at the END of the frame too: k_apply_remote runs behind the group's launch
     if (need.red) L.cap_steps = 1;               // reductions land at the END of the frame too: k_apply_reduces runs behind the group's launch
     if (need.effects) L.cap_steps = 1;           // effects land at the END of the frame: the inbox is applied behind the group's launch, so a group ends on its one AdvanceWorld
     uint32_t fx_cols[GGRS_EFFECT_MAX_COLUMNS]; const uint32_t n_fx = std::min<uint32_t>(effect_cols(w, fx_cols), GGRS_EFFECT_MAX_COLUMNS);
@@ -757,6 +792,7 @@ JitLayout jit_layout(const ggrs_world* w) {
         FA("const unsigned char*", pv_col, n_pv, need.peers); F1("const ggrs_u64*", pv_vis, need.peers); F1("ggrs_u64", pv_len, need.peers);
         FA("unsigned char*", fx_col, n_fx, need.effects); F1("ggrs_u64", fx_len, need.effects);
         F1("const unsigned char*", res_src, need.res); F1("unsigned char*", rd_inbox, need.red);
+        F1("ggrs_u32*", rx_inbox, need.rem); F1("ggrs_u64", rx_len, need.rem && !need.effects);
         FA("unsigned char*", save_dst, S, true); FA("ggrs_u64", save_rows, S, true); FA("ggrs_u64", save_len, S, true);
         FS("const unsigned char*", spawn_payload, need.spawn); FS("ggrs_u64", spawn_first, need.spawn);
         FA("int", save_frame, S, true); FA("ggrs_u32", save_pmask, S, true);
@@ -975,7 +1011,8 @@ inline uint64_t jit_marks_rec_frames_off(const ggrs_world* w) { return align_up(
 inline uint64_t jit_marks_rec_bytes(const ggrs_world* w) { return jit_marks_rec_frames_off(w) + align_up(w->cap_pad * 4, ALIGN); }
 // which optional parts of the argument block this world's kernel reads
 JitNeeds jit_needs(const ggrs_world* w) {
-    JitNeeds n{false, false, false, false, false, false, false, false, false, false, false, false, false};
+    JitNeeds n{false, false, false, false, false, false, false, false, false, false, false, false, false, false};
+    n.rem = world_has_remote(w);
     n.red = world_has_reduces(w);
     n.res = world_has_resources(w);
     n.commands = world_has_commands(w);
@@ -1142,7 +1179,7 @@ struct JitGen {
                                     "#define GGRS_SP_READ %uu                                                           // sp_desc[GGRS_SP_READ x tiles + tile]: that tile has read its starting len\n",
                          2u + (unsigned)MAX_TICK_SAVES, 2u * (unsigned)MAX_TICK_STEPS);
         s += GGRS_FRAME_TEXT;
-        s += entity_text(need.effects, need.peers, need.commands, true, need.res, need.red);
+        s += entity_text(need.effects, need.peers, need.commands, true, need.res, need.red, need.rem);
         if (need.res) s += GGRS_RESOURCES_TEXT;
         if (need.red) s += GGRS_REDUCE_WAVE_TEXT;
         s += GGRS_COMPONENT_TEXT;
@@ -1152,7 +1189,7 @@ struct JitGen {
     // ---- 2. user sources: systems, spawner, hashers, strategies -- each in a namespace of its own, under its own name in the compiler's messages
     void user_sources() {
         for (size_t i = 0; i < w->customs.size(); ++i) {
-            if (need.commands) sfmt(s, "namespace ggrs_sys_%zu {\n%s#line 1 \"%s\"\n", i, cmd_entity_typedef(w, w->customs[i]).c_str(), file_name(w->customs[i].name).c_str());
+            if (need.commands || need.rem) sfmt(s, "namespace ggrs_sys_%zu {\n%s#line 1 \"%s\"\n", i, cmd_entity_typedef(w, w->customs[i], need.rem).c_str(), file_name(w->customs[i].name).c_str());
             else
             sfmt(s, "namespace ggrs_sys_%zu {\n#line 1 \"%s\"\n", i, file_name(w->customs[i].name).c_str());
             s += w->customs[i].source;
@@ -1766,6 +1803,9 @@ struct JitGen {
         if (need.commands)
         sfmt(s, ") {                                                   // user system %u\n"
                 "                ggrs_sys_%u::GgrsEntity ent; ent.slot = e0; ent.kill = 0; ent.spawn_n = 0; ent.has_ = 0u;\n", d.comp[0], d.comp[0]);
+        else if (need.rem)
+        sfmt(s, ") {                                                   // user system %u\n"
+                "                ggrs_sys_%u::GgrsEntity ent; ent.slot = e0; ent.kill = 0; ent.spawn_n = 0;\n", d.comp[0], d.comp[0]);
         else
         sfmt(s, ") {                                                   // user system %u\n"
                 "                GgrsEntity ent; ent.slot = e0; ent.kill = 0; ent.spawn_n = 0;\n", d.comp[0]);
@@ -1789,6 +1829,17 @@ struct JitGen {
                 const uint32_t cl = col(c.fcomp[j], c.fword[j]);
                 uint32_t at = 0; while (at < n_fx && fx_cols[at] != cl) ++at;      // (jit_covers: the column is in the inbox)
                 sfmt(s, "                ent.fx_.col[%u] = (unsigned long)a.fx_col[%u]; ent.fx_.wb[%u] = %uu; ent.fx_.op[%u] = %uu;\n", j, at, j, w->comps[c.fcomp[j]].word_bytes, j, c.fop[j]);
+            }
+        }
+        if (c.n_rem) {
+            // remote bindings: every send ORs into the slot's word of the world's one inbox; binding j's insert bit is 1 + 2k, k = the component's place among the
+            // world's remotely commanded components (remove: the next bit).  The bounds length is the source block's len
+            uint32_t rx_comps[GGRS_REMOTE_MAX_COMPONENTS]; const uint32_t n_rx = std::min<uint32_t>(remote_comps(w, rx_comps), GGRS_REMOTE_MAX_COMPONENTS);
+            sfmt(s, "                ent.rx_ = (unsigned long)a.rx_inbox; ent.rxn_ = a.%s;\n", need.effects ? "fx_len" : "rx_len");
+            for (uint32_t j = 0; j < c.n_rem; ++j) {
+                if (c.xflags[j] & GGRS_REMOTE_DESPAWN) continue;
+                uint32_t at = 0; while (at < n_rx && rx_comps[at] != c.xcomp[j]) ++at;
+                sfmt(s, "                ent.rxb_[%u] = %uu;\n", j, 1u + 2u * at);
             }
         }
         // command bindings: binding j's words go in from the registers where the lane has the component and from the literals of its registered default where it has

@@ -697,6 +697,59 @@ __global__ __launch_bounds__(TPB) void k_apply_effects(FxApplyArgs a) {
     }
 }
 
+// THE REMOTE INBOX (ggrs_hip_add_custom_system_remote; host_world.hpp ggrs_world::RemoteInbox).  Right behind every request group that holds an AdvanceWorld and AHEAD of
+// k_apply_effects: the commands the group's launch ORed into the inbox -- one u32 per slot: bit 0 despawn, bits 1 + 2k / 2 + 2k insert / remove of remotely commanded
+// component k -- are applied to the LIVE block.  One 64-slot unit per wave == one mask word; for slots below the end-of-frame len a lane reads its inbox word
+// (coalesced).  A unit whose 64 words are all zero touches nothing else.  Otherwise the wave rebuilds the unit's alive word and each touched component's presence word
+// with one __ballot each (lane 0 stores the 8-byte word), lanes whose slot gains a component write its registered default into the live columns (tile-major), and the
+// inbox words go back to zero.  A command on a slot that is not alive once the frame's own despawns are in is dropped; DESPAWN WINS over everything, REMOVE WINS over
+// insert.  Plain loads and stores: the sends were atomics of an EARLIER launch, a slot is touched by one lane, a mask word by one wave.
+constexpr int RX_MAX_COMPS = GGRS_REMOTE_MAX_COMPONENTS;
+constexpr int RX_MAX_WORDS = 64;                            // words of all remotely commanded components together (a world has at most 64 word columns)
+struct RxApplyArgs {
+    uint8_t* live; uint32_t* inbox; uint64_t len, off_alive;
+    uint64_t off_present[RX_MAX_COMPS];
+    uint64_t col_off[RX_MAX_WORDS], dflt[RX_MAX_WORDS];     // per word of component k, from w_base[k]: its column and the default it takes on insert
+    uint32_t w_base[RX_MAX_COMPS], n_words[RX_MAX_COMPS], wb[RX_MAX_COMPS], ts[RX_MAX_COMPS];
+    uint32_t n_comps, n_units;
+};
+__global__ __launch_bounds__(TPB) void k_apply_remote(RxApplyArgs a) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t u = blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);             // this wave's 64-slot unit == its mask word (wave-uniform)
+    if (u >= a.n_units) return;
+    const uint64_t e = (uint64_t)u * 64u + lane;
+    const bool inside = e < a.len;                                               // (a send never goes beyond the start-of-frame len, which the end-of-frame len is not below)
+    const uint32_t m = inside ? a.inbox[e] : 0u;
+    if (!__ballot(m != 0u)) return;                                              // nothing was sent into this unit: nothing else is touched
+    uint64_t* const alive_p = reinterpret_cast<uint64_t*>(a.live + a.off_alive + (uint64_t)u * 8u);
+    const uint64_t alive_w = *alive_p;
+    const bool alive = (alive_w >> lane) & 1ull;                                 // alive once the frame's own despawns are in: else every command is dropped
+    const bool on = alive && !(m & 1u);                                          // despawn wins over everything
+    const uint64_t alive_n = __ballot(on);
+    if (lane == 0 && alive_n != alive_w) *alive_p = alive_n;
+    for (uint32_t k = 0; k < a.n_comps; ++k) {
+        const bool ins = (m >> (1u + 2u * k)) & 1u, rem = (m >> (2u + 2u * k)) & 1u;
+        if (!__ballot(on && (ins || rem))) continue;                            // wave-uniform
+        uint64_t* const pres_p = reinterpret_cast<uint64_t*>(a.live + a.off_present[k] + (uint64_t)u * 8u);
+        const uint64_t pres_w = *pres_p;
+        const bool has = (pres_w >> lane) & 1ull;
+        const bool gains = on && ins && !rem;                                    // remove wins over insert
+        const uint64_t pres_n = __ballot(on ? (!rem && (ins || has)) : has);
+        if (lane == 0 && pres_n != pres_w) *pres_p = pres_n;
+        if (gains) for (uint32_t q = 0; q < a.n_words[k]; ++q) {                 // Bevy's insert: a present component's value is replaced
+            const uint32_t x = a.w_base[k] + q;
+            uint8_t* const p = a.live + col_at(a.col_off[x], a.ts[k], a.wb[k], e);
+            switch (a.wb[k]) {
+            case 8: *reinterpret_cast<uint64_t*>(p) = a.dflt[x]; break;
+            case 4: *reinterpret_cast<uint32_t*>(p) = (uint32_t)a.dflt[x]; break;
+            case 2: *reinterpret_cast<uint16_t*>(p) = (uint16_t)a.dflt[x]; break;
+            default: *p = (uint8_t)a.dflt[x]; break;
+            }
+        }
+    }
+    if (m) a.inbox[e] = 0u;
+}
+
 // THE REDUCE INBOX (ggrs_hip_add_custom_system_reduces; host_world.hpp ggrs_world::ReduceInbox).  Right behind every request group that holds an AdvanceWorld: ONE
 // wave; lane s loads line s of the inbox (the op's identity beyond the last line), the lane pattern of wave_xor32 folds the lines per word -- `old` is the identity,
 // so masked rows contribute nothing; a word moves as two halves and is combined as one op of its width --, one lane combines the result into the live block's current

@@ -434,6 +434,59 @@ int ggrs_hip_add_custom_system_reduces(ggrs_world* w, const ggrs_custom_system_d
                                        const ggrs_resource_binding* res, uint32_t n_res,
                                        const ggrs_reduce_binding* red, uint32_t n_red);
 
+/* REMOTE STRUCTURAL COMMANDS: despawn, insert and remove on OTHER entities --
+ *
+ *     fn strike(mut commands: Commands, q: Query<&Target>) { for t in &q { commands.entity(t.0).insert(Stun::default()); commands.entity(t.0).remove::<Shield>(); } }
+ *     fn kill(mut commands: Commands, q: Query<&Target>) { for t in &q { commands.entity(t.0).despawn(); } }
+ *
+ * "the thing I hit dies", "the thing I hit becomes Stunned".
+ *
+ *   ggrs_hip_add_custom_system_remote   ggrs_hip_add_custom_system_reduces plus REMOTE BINDINGS: rem[j] = {comp, flags}, flags made of GGRS_REMOTE_INSERT,
+ *                                  GGRS_REMOTE_REMOVE and GGRS_REMOTE_DESPAWN.  A binding with GGRS_REMOTE_DESPAWN names no component: its comp is
+ *                                  GGRS_REMOTE_ENTITY and it carries no other flag.  With n_rem == 0 the call behaves exactly as
+ *                                  ggrs_hip_add_custom_system_reduces.  At most GGRS_REMOTE_MAX_BINDINGS per system and GGRS_REMOTE_MAX_COMPONENTS distinct remotely
+ *                                  commanded components per world.
+ *   inside ggrs_system, with j a literal
+ *     e.send_insert(slot, j)       the entity at `slot` HAS component rem[j].comp at the end of the frame, with its REGISTERED DEFAULT
+ *                                  (ggrs_hip_set_component_default, else zeros) in every word.  Bevy's insert: a present component's value is replaced.  Every
+ *                                  sender inserts the same value, so the result does not depend on lane order; a per-sender value would, and is not offered.
+ *     e.send_remove(slot, j)       the entity at `slot` does NOT have the component at the end of the frame.
+ *     e.send_despawn(slot)         the entity at `slot` is despawned at the end of the frame (the system has a GGRS_REMOTE_DESPAWN binding).
+ *                                  A call whose flag was not declared, or whose j is not a constant, finds no member and does not compile (enable_if, as e.insert).
+ *
+ * ALL REMOTE COMMANDS OF A FRAME LAND AT THE END OF THE FRAME: after the frame's systems and host-decided spawns, BEFORE the frame's effects
+ * (ggrs_hip_add_custom_system_effects) are applied, before anything observes the frame -- a SaveWorld, a checksum, a download, the next frame, the next group's peer
+ * publish.  A command is dropped unless  slot < the len at the start of the frame  and the target is alive once the frame's own despawns are in: an entity spawned in
+ * the frame cannot be hit; a sender that despawns itself in the same call still sends.
+ * CONFLICTS on one target in one frame: DESPAWN WINS OVER EVERYTHING; REMOVE WINS OVER INSERT of the same component.
+ * Effects then apply to the alive and presence bits the remote commands left: a target despawned in the frame drops the send, as before.
+ * Seal (remote_validate) makes "at the end of the frame" equal to Bevy's deferred Commands under a chained schedule, each refusal GGRS_E_INVALID with a message naming
+ * the system and the component:
+ *   - no system registered AT OR AFTER a component's first remote commander binds that component (own, peer, command bindings, effect columns, built-in kinds, the
+ *     commander itself); a system registered BEFORE may -- the own-entity countdown that removes Stun first, the striker that remotely inserts it last;
+ *   - no system registered AFTER a system with GGRS_REMOTE_DESPAWN has peer, effect, reduce or remote bindings (in Bevy it would not run for the despawned entity);
+ *   - for the peer rule a remote despawner is "a system that can despawn";
+ *   - a remotely commanded component is rollback, has no Strategy and is no effect column of the same world;
+ *   - refused as for effects: worlds that keep RollbackDespawned markers, device-decided spawns, worlds without the generated kernel,
+ *     ggrs_hip_fanout_step_branches (ggrs_hip_fanout_step works).
+ * How it runs: one inbox word per slot (bit 0 despawn, bits 1 + 2k / 2 + 2k insert / remove of the world's k-th remotely commanded component), each send one
+ * no-return atomic OR; k_apply_remote, one small launch right behind the group's and ahead of the effects', rebuilds the touched mask words with ballots, writes the
+ * defaults and zeroes the inbox.  Such a world runs one AdvanceWorld per launch, as a world with effect bindings does. */
+typedef struct { uint32_t comp; uint32_t flags; } ggrs_remote_binding;   /* remote binding j = component `comp` (GGRS_REMOTE_ENTITY with GGRS_REMOTE_DESPAWN) and GGRS_REMOTE_* flags */
+#define GGRS_REMOTE_INSERT  1u   /* the system may call e.send_insert(slot, j) */
+#define GGRS_REMOTE_REMOVE  2u   /* the system may call e.send_remove(slot, j) */
+#define GGRS_REMOTE_DESPAWN 4u   /* the system may call e.send_despawn(slot); comp = GGRS_REMOTE_ENTITY */
+#define GGRS_REMOTE_ENTITY  0xFFFFFFFFu
+#define GGRS_REMOTE_MAX_BINDINGS   4
+#define GGRS_REMOTE_MAX_COMPONENTS 8
+int ggrs_hip_add_custom_system_remote(ggrs_world* w, const ggrs_custom_system_desc* desc,
+                                      const ggrs_peer_binding* peers, uint32_t n_peers,
+                                      const ggrs_effect_binding* effects, uint32_t n_effects,
+                                      const ggrs_command_binding* cmds, uint32_t n_cmds,
+                                      const ggrs_resource_binding* res, uint32_t n_res,
+                                      const ggrs_reduce_binding* red, uint32_t n_red,
+                                      const ggrs_remote_binding* rem, uint32_t n_rem);
+
 /* ComponentSnapshotPlugin<S: Strategy> (snapshot/strategy.rs:22-40, component_snapshot.rs:42-63): what a snapshot HOLDS of a component is
  * S::Stored, produced by S::store and turned back by S::load / S::update -- CopyStrategy / CloneStrategy (Stored == the component, bitwise for
  * POD) are what ggrs_hip_register_component gives; this is the open door next to them: quantised, packed or partial snapshots.
@@ -797,7 +850,7 @@ int ggrs_hip_host_timeline(ggrs_world* w, int enable, double* us_out, uint64_t* 
  * Introspection: which kernel serves this world's request lists right now and why, what kind of arena
  * it lives on, whether the run-time compiler (libhiprtc.so, dlopen'ed) is available.  `key=value` lines,
  * NUL-terminated; *needed = bytes incl. the NUL, min(cap, *needed) are copied.  Keys: sealed, arena,
- * arena_bytes, hiprtc, generated_kernel, generated_kernel_origin, request_group_kernel, checksum_fold, kernarg_bytes, group_caps, specialised_kernel, slots_covered, row_versions, peer_view (worlds with peer bindings), effect_inbox (worlds with effect bindings), device_resources (worlds with device resources), depth_parallel_roles, reduce_inbox (worlds with reduce bindings: stripes, words, applies so far).
+ * arena_bytes, hiprtc, generated_kernel, generated_kernel_origin, request_group_kernel, checksum_fold, kernarg_bytes, group_caps, specialised_kernel, slots_covered, row_versions, peer_view (worlds with peer bindings), effect_inbox (worlds with effect bindings), device_resources (worlds with device resources), depth_parallel_roles, reduce_inbox (worlds with reduce bindings: stripes, words, applies so far), remote_inbox (worlds with remote bindings: components, applies so far).
  * ------------------------------------------------------------------------------------------- */
 int ggrs_hip_world_kernel_info(ggrs_world* w, char* buf, uint64_t cap, uint64_t* needed);
 

@@ -143,6 +143,22 @@ pub struct ggrs_reduce_binding {
 }
 pub const GGRS_REDUCE_MAX_BINDINGS: usize = 8;
 
+/// One remote binding of `ggrs_hip_add_custom_system_remote`: a component of OTHER entities an entity system may insert (`e.send_insert(slot, j)`, the registered
+/// default) or remove (`e.send_remove(slot, j)`); `comp == GGRS_REMOTE_ENTITY` with `GGRS_REMOTE_DESPAWN` is `e.send_despawn(slot)`.  Every command of a frame
+/// lands at the end of the frame: despawn wins over everything, remove wins over insert.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct ggrs_remote_binding {
+    pub comp: u32,
+    pub flags: u32,
+}
+pub const GGRS_REMOTE_INSERT: u32 = 1;
+pub const GGRS_REMOTE_REMOVE: u32 = 2;
+pub const GGRS_REMOTE_DESPAWN: u32 = 4;
+pub const GGRS_REMOTE_ENTITY: u32 = 0xFFFF_FFFF;
+pub const GGRS_REMOTE_MAX_BINDINGS: usize = 4;
+pub const GGRS_REMOTE_MAX_COMPONENTS: usize = 8;
+
 /// A once-per-frame system over device resources (`ggrs_hip_add_resource_system`): `source` defines `ggrs_resource_system(GgrsResources& r, const GgrsFrame& f)`.
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -262,6 +278,7 @@ unsafe extern "C" {
     pub fn ggrs_hip_add_custom_system_commands(w: *mut ggrs_world, desc: *const ggrs_custom_system_desc, peers: *const ggrs_peer_binding, n_peers: u32, effects: *const ggrs_effect_binding, n_effects: u32, cmds: *const ggrs_command_binding, n_cmds: u32) -> c_int;
     pub fn ggrs_hip_add_custom_system_resources(w: *mut ggrs_world, desc: *const ggrs_custom_system_desc, peers: *const ggrs_peer_binding, n_peers: u32, effects: *const ggrs_effect_binding, n_effects: u32, cmds: *const ggrs_command_binding, n_cmds: u32, res: *const ggrs_resource_binding, n_res: u32) -> c_int;
     pub fn ggrs_hip_add_custom_system_reduces(w: *mut ggrs_world, desc: *const ggrs_custom_system_desc, peers: *const ggrs_peer_binding, n_peers: u32, effects: *const ggrs_effect_binding, n_effects: u32, cmds: *const ggrs_command_binding, n_cmds: u32, res: *const ggrs_resource_binding, n_res: u32, red: *const ggrs_reduce_binding, n_red: u32) -> c_int;
+    pub fn ggrs_hip_add_custom_system_remote(w: *mut ggrs_world, desc: *const ggrs_custom_system_desc, peers: *const ggrs_peer_binding, n_peers: u32, effects: *const ggrs_effect_binding, n_effects: u32, cmds: *const ggrs_command_binding, n_cmds: u32, res: *const ggrs_resource_binding, n_res: u32, red: *const ggrs_reduce_binding, n_red: u32, rem: *const ggrs_remote_binding, n_rem: u32) -> c_int;
     pub fn ggrs_hip_register_resource(w: *mut ggrs_world, name: *const c_char, word_bytes: u32, n_words: u32, init_words: *const c_void, res_id_out: *mut u32) -> c_int;
     pub fn ggrs_hip_checksum_resource(w: *mut ggrs_world, res_id: u32, word_idx: *const u32, n_words: u32) -> c_int;
     pub fn ggrs_hip_add_resource_system(w: *mut ggrs_world, desc: *const ggrs_resource_system_desc) -> c_int;
