@@ -133,6 +133,7 @@ void ggrs_hip_world_destroy(ggrs_world* w) {
     peer_view_release(w);
     fx_inbox_release(w);
     rd_inbox_release(w);
+    sum_part_release(w);
     rx_inbox_release(w);
     for (void* p : w->spec_allocs) (void)hipFree(p);
     if (w->h_results) (void)hipHostFree(w->h_results);
@@ -248,7 +249,16 @@ int ggrs_hip_add_custom_system_reduces(ggrs_world* w, const ggrs_custom_system_d
 int ggrs_hip_add_custom_system_remote(ggrs_world* w, const ggrs_custom_system_desc* d, const ggrs_peer_binding* peers, uint32_t n_peers, const ggrs_effect_binding* effects, uint32_t n_effects,
                                       const ggrs_command_binding* cmds, uint32_t n_cmds, const ggrs_resource_binding* res, uint32_t n_res, const ggrs_reduce_binding* red, uint32_t n_red,
                                       const ggrs_remote_binding* rem, uint32_t n_rem) {
+    return ggrs_hip_add_custom_system_sums(w, d, peers, n_peers, effects, n_effects, cmds, n_cmds, res, n_res, red, n_red, rem, n_rem, nullptr, 0);
+}
+// ... and with sum bindings: float / double words of the world's device resources the system adds into through e.sum_f32 / e.sum_f64(j, v), summed in a fixed order
+// and landing at the end of the frame (include/ggrs_hip.h).  Which resource, word and width a binding names is checked at seal (host_seal.hpp sums_validate)
+int ggrs_hip_add_custom_system_sums(ggrs_world* w, const ggrs_custom_system_desc* d, const ggrs_peer_binding* peers, uint32_t n_peers, const ggrs_effect_binding* effects, uint32_t n_effects,
+                                    const ggrs_command_binding* cmds, uint32_t n_cmds, const ggrs_resource_binding* res, uint32_t n_res, const ggrs_reduce_binding* red, uint32_t n_red,
+                                    const ggrs_remote_binding* rem, uint32_t n_rem, const ggrs_sum_binding* sum, uint32_t n_sum) {
     if (!w || !d || !d->source) return GGRS_E_INVALID;
+    if (n_sum > GGRS_SUM_MAX_BINDINGS) return w->fail(GGRS_E_INVALID, "custom system '%s': at most %d sum bindings (GGRS_SUM_MAX_BINDINGS), not %u", d->name ? d->name : "custom", GGRS_SUM_MAX_BINDINGS, n_sum);
+    if (n_sum && !sum) return w->fail(GGRS_E_INVALID, "custom system: n_sum = %u but sum is NULL", n_sum);
     if (n_rem > GGRS_REMOTE_MAX_BINDINGS) return w->fail(GGRS_E_INVALID, "custom system '%s': at most %d remote bindings (GGRS_REMOTE_MAX_BINDINGS), not %u", d->name ? d->name : "custom", GGRS_REMOTE_MAX_BINDINGS, n_rem);
     if (n_rem && !rem) return w->fail(GGRS_E_INVALID, "custom system: n_rem = %u but rem is NULL", n_rem);
     if (n_red > GGRS_REDUCE_MAX_BINDINGS) return w->fail(GGRS_E_INVALID, "custom system '%s': at most %d reduce bindings (GGRS_REDUCE_MAX_BINDINGS), not %u", d->name ? d->name : "custom", GGRS_REDUCE_MAX_BINDINGS, n_red);
@@ -321,6 +331,8 @@ int ggrs_hip_add_custom_system_remote(ggrs_world* w, const ggrs_custom_system_de
         c.xcomp[j] = rem[j].comp; c.xflags[j] = fl;
     }
     c.n_rem = n_rem;
+    for (uint32_t j = 0; j < n_sum; ++j) { c.sres[j] = sum[j].res; c.sword[j] = sum[j].word; }
+    c.n_sum = n_sum;
     DeviceGuard dg(w);
     c.source = d->source;
     c.may_defer = source_has_token(c.source, "despawn_rollback") || source_has_token(c.source, "kill");
@@ -464,7 +476,7 @@ int ggrs_hip_generated_kernel_source(ggrs_world* w, uint32_t form, char* buf, ui
     if (!w || (form != GGRS_KERNEL_FORM_TILES && form != GGRS_KERNEL_FORM_STEADY)) return GGRS_E_INVALID;
     if (!w->sealed) {
         if (!w->layout_only) { DeviceGuard dg(w); const int rc = seal(w); if (rc) return rc; }
-        else { build_layout(w); const int prc = peers_validate(w); if (prc) return prc; const int frc = effects_validate(w); if (frc) return frc; const int crc = commands_validate(w); if (crc) return crc; const int rrc = resources_validate(w); if (rrc) return rrc; const int drc = reduces_validate(w); if (drc) return drc; const int xrc = remote_validate(w); if (xrc) return xrc; }   // host arithmetic only: offsets of every mask and column; the peer-, effect-, command-, resource, reduce and remote rules
+        else { build_layout(w); const int prc = peers_validate(w); if (prc) return prc; const int frc = effects_validate(w); if (frc) return frc; const int crc = commands_validate(w); if (crc) return crc; const int rrc = resources_validate(w); if (rrc) return rrc; const int drc = reduces_validate(w); if (drc) return drc; const int xrc = remote_validate(w); if (xrc) return xrc; const int src_ = sums_validate(w); if (src_) return src_; }   // host arithmetic only: offsets of every mask and column; the peer-, effect-, command-, resource, reduce, remote and sum rules
     }
     std::string src;
     if (!jit_source(w, src)) return w->fail(GGRS_E_INVALID, "the kernel generator does not cover this world (a system writes a live-only component, or more than %u four-byte units / %u words per entity)", JIT_MAX_UNITS, JIT_MAX_COLS);
@@ -514,6 +526,16 @@ int64_t ggrs_dbg_remote_inbox(ggrs_world* w, void* out, uint64_t cap) {
     DeviceGuard dg(w);
     const uint64_t bytes = w->cap_pad * 4u;
     if (hipMemcpyAsync(out, w->rx_inbox.d, std::min(cap, bytes), hipMemcpyDeviceToHost, w->stream) != hipSuccess || hipStreamSynchronize(w->stream) != hipSuccess) return -1;
+    return (int64_t)bytes;
+}
+//   ggrs_dbg_sum_partials      the sum partials of summed word `word` (8 bytes per 64-slot unit: a float in the low four bytes, or a double) after everything queued on the
+//                              world's stream has run: returns how many bytes the word's array has (min(cap, that) are copied), -1 for a world without one or a word it does
+//                              not have.  Only the entries of the units the last launch covered mean anything
+int64_t ggrs_dbg_sum_partials(ggrs_world* w, uint32_t word, void* out, uint64_t cap) {
+    if (!w || !w->sum_part.d || word >= w->sum_part.n_words) return -1;
+    DeviceGuard dg(w);
+    const uint64_t bytes = (uint64_t)w->sum_part.units * 8u;
+    if (hipMemcpyAsync(out, w->sum_part.d + (uint64_t)word * bytes, std::min(cap, bytes), hipMemcpyDeviceToHost, w->stream) != hipSuccess || hipStreamSynchronize(w->stream) != hipSuccess) return -1;
     return (int64_t)bytes;
 }
 int ggrs_dbg_set_spec_shapes(ggrs_world* w, int n) { if (!w || n < 1 || n > 64) return -1; w->spec_shapes = n; return 0; }
@@ -1030,6 +1052,8 @@ int ggrs_hip_world_kernel_info(ggrs_world* w, char* buf, uint64_t cap, uint64_t*
                                                 std::to_string(w->rd_inbox.applies) + " applies so far)");
         if (w->has_remote) add("remote_inbox", "one u32 per slot, " + std::to_string(w->rx_inbox.n_comps) + " remotely commanded components (bit 0 despawn, bits 1 + 2k / 2 + 2k insert / remove of component k), zeros whenever no group-and-apply pair is in flight, "
                                                "applied to the live block's masks and columns right behind every request group that holds an AdvanceWorld and ahead of the effects (" + std::to_string(w->rx_inbox.applies) + " applies so far)");
+        if (w->has_sums) add("sum_partials", std::to_string(w->sum_part.units) + " units of 64 slots, " + std::to_string(w->sum_part.n_words) + " summed words, one 8-byte partial per unit and word stored by the unit's wave, folded by the balanced tree "
+                                             "into the live block's current resource cell right behind every request group that holds an AdvanceWorld (" + std::to_string(w->sum_part.applies) + " applies so far)");
         if (w->has_effects) add("effect_inbox", std::to_string(w->fx_inbox.n_cols) + " linear columns holding the ops' identities, applied to the live block right behind every request group that holds an AdvanceWorld (" +
                                                std::to_string(w->fx_inbox.applies) + " applies so far)");
         add("branch_marker_record_bytes", std::to_string(w->jit_marks ? jit_marks_rec_bytes(w) : 0));      // per retained branch of ggrs_hip_fanout_step_branches (0: the kernel keeps no markers)

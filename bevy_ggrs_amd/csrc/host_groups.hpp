@@ -254,6 +254,10 @@ int launch_jit(ggrs_world* w, hipFunction_t fn, uint32_t gx, uint32_t gy, uint32
     j.skip_count = (w->prof && j.vtags) ? reinterpret_cast<ggrs_u64*>(w->d_skip) : nullptr;
     if (w->has_resources) { const int rrc = res_cells_for_launch(w, j); if (rrc) return rrc; }
     if (w->has_remote) { j.rx_inbox = w->rx_inbox.d; j.rx_len = j.len; }   // remote bindings: the inbox, and the source block's len == RollbackOrdered::len at the start of the group's one AdvanceWorld (in a world with effects the kernel reads fx_len, the same value)
+    if (w->has_sums) {                                                 // sum bindings: every launch of the kernel stores one partial per word and unit it covers (only one that runs an AdvanceWorld is folded)
+        if (((j.n_units + 3u) & ~3u) > w->sum_part.units) return w->fail(GGRS_E_INVALID, "sum bindings: the launch covers %u units, the partial arrays hold %u", j.n_units, w->sum_part.units);
+        j.sum_part = w->sum_part.d;
+    }
     if (w->has_reduces) j.rd_inbox = w->rd_inbox.d;                    // reduce bindings: every launch of the kernel knows the inbox (only one that runs an AdvanceWorld publishes into it)
     jit_pack(*w->jl, j, w->jit_argbuf.data());
     void* params[] = {w->jit_argbuf.data()};
@@ -467,6 +471,7 @@ inline bool lazy_live_allowed(const ggrs_world* w) {                 // (what a 
     if (world_has_peers(w)) return false;                            // peer bindings: the next group's publish reads what this one leaves -- every block is written (no deferred Saves either)
     if (world_has_effects(w)) return false;                          // effect bindings: k_apply_effects combines the frame's sends into the live block -- every group writes it (no deferred Saves either)
     if (world_has_remote(w)) return false;                           // remote bindings: k_apply_remote edits the live block's masks and columns behind the group's launch -- every group writes it (no deferred Saves either)
+    if (world_has_sums(w)) return false;                             // sum bindings: k_apply_sums adds the frame's totals into the live block's resource cell, likewise
     if (world_has_reduces(w)) return false;                          // reduce bindings: k_apply_reduces combines the frame's reductions into the live block's resource cell -- every group writes it (no deferred Saves either)
     for (uint8_t e : w->col_ext) if (e) return false;
     return true;
@@ -649,6 +654,7 @@ int group_take(ggrs_world* w, const ggrs_request& r, GgrsJitArgs& j, GroupState&
         if (j.n_saves == w->cap_saves || j.n_saves == saves_room) return GGRS_OK;
         if (w->has_effects && j.n_steps) return GGRS_OK;               // effect bindings: the group ends ON its AdvanceWorld ([Load?] Save* Advance) -- this Save opens the next group and reads the live block after the apply
         if (w->has_remote && j.n_steps) return GGRS_OK;                // remote bindings: the same shape -- the Save reads the masks and columns k_apply_remote left
+        if (w->has_sums && j.n_steps) return GGRS_OK;                  // sum bindings: the same shape -- the Save stores the resource words k_apply_sums left
         if (w->has_reduces && j.n_steps) return GGRS_OK;               // reduce bindings: the same shape -- the Save stores the resource words k_apply_reduces left
         *taken = true; return group_save(w, gs, j);
     }
@@ -884,6 +890,25 @@ int apply_reduces(ggrs_world* w) {
     ++w->rd_inbox.applies;
     return GGRS_OK;
 }
+// Sum bindings: the partials the waves of the group's launch stored -- one per summed word and 64-slot unit that launch covered -- are folded by the balanced tree and
+// added into the live block's CURRENT resource cell, by one launch right BEHIND the group's (and behind k_apply_reduces: another word of the same cell), enqueued with
+// it (never lazily).  n_units is what THAT launch covered: nothing beyond is read.  The kernel boundary is the only synchronisation.
+int apply_sums(ggrs_world* w, uint32_t n_units) {
+    SmApplyArgs a; memset(&a, 0, sizeof a);
+    SummedWord sw[GGRS_SUM_MAX_WORDS];
+    ggrs_world::SumPartials& sp = w->sum_part;
+    a.n_words = std::min<uint32_t>(summed_words(w, sw), GGRS_SUM_MAX_WORDS); a.units = sp.units; a.tmp_entries = sp.tmp_entries; a.n_units = std::min(n_units, sp.units);
+    a.part = sp.d; a.tmp = sp.d + (uint64_t)sp.n_words * sp.units * 8u;
+    a.cell = w->live.ptr + RES_CELL_OFF + w->live.res_cell * RES_CELL_BYTES;
+    for (uint32_t k = 0; k < a.n_words; ++k) { a.off[k] = sw[k].off; a.wb[k] = sw[k].wb; }
+    const double t0 = w->tl.on ? tl_now_us() : 0;
+    { ProfScope ps(w, GGRS_KERNEL_ADVANCE, (uint64_t)a.n_units * 8u * a.n_words); hipLaunchKernelGGL(k_apply_sums, dim3(a.n_words), dim3(SM_TPB), 0, w->stream, a); }
+    HIPCHK(w, hipGetLastError());
+    if (w->tl.on) { w->tl.launch_us += tl_now_us() - t0; ++w->tl.n_launches; }
+    w->spin_n = 0; w->batch_ev_attached = false;                       // this launch comes after whatever carried the batch event, and after a finalize that was the list's last GPU operation
+    ++sp.applies;
+    return GGRS_OK;
+}
 int run_request_groups_gen(ggrs_world* w, const ggrs_request* reqs, uint32_t n, uint64_t* checksums_out,
                            uint32_t res_base = 0, bool wait = true, uint32_t* n_saves_out = nullptr) {
     uint32_t i = 0, ns = 0; int rc = GGRS_OK;
@@ -910,7 +935,7 @@ int run_request_groups_gen(ggrs_world* w, const ggrs_request* reqs, uint32_t n, 
         }
         // ---- dead / lazy / deferred: what the group need not store
         // (effect bindings: every live sender's sends reach the inbox exactly once per simulated frame and are applied to a live block the group WROTE -- no group is dead)
-        const bool dead = !w->dev_spawn && !w->has_effects && !w->has_reduces && !w->has_remote && group_is_dead(w, reqs, i, n, j.save_frame, j.n_saves, gs.spawn_req != nullptr);
+        const bool dead = !w->dev_spawn && !w->has_effects && !w->has_reduces && !w->has_sums && !w->has_remote && group_is_dead(w, reqs, i, n, j.save_frame, j.n_saves, gs.spawn_req != nullptr);
         if (dead) { for (uint32_t k = 0; k < j.n_saves; ++k) j.save_dst[k] = nullptr; j.skip_live = 1; }
         const uint64_t cover = w->dev_spawn ? w->capacity : std::max(gs.cover, w->len);      // (device-decided spawns: the host only knows a bound of len)
         group_lazy_live(w, j, gs, dead, i >= n, cover);
@@ -924,7 +949,7 @@ int run_request_groups_gen(ggrs_world* w, const ggrs_request* reqs, uint32_t n, 
         // ---- policy: per-tile grid of 256-slot workgroups, depth-parallel roles
         const JitPolicy pol = jit_group_policy(cover, j.n_saves, j.src_is_live != 0, save0_bytes, group_aliases(j, wrote_live), w->jit_marks, w->dev_spawn, w->nt_copy);
         j.nt = pol.nt; j.cached_saves = pol.cached_saves; j.nt_loads = pol.nt_loads; j.dp_s = pol.dp_s;
-        if (w->has_effects || w->has_reduces || w->has_remote) j.dp_s = 0;   // (every depth-parallel role runs the group's steps: a role more is every send, every reduction and every remote command once more)
+        if (w->has_effects || w->has_reduces || w->has_sums || w->has_remote) j.dp_s = 0;   // (every depth-parallel role runs the group's steps: a role more is every send, every reduction and every remote command once more)
         const bool launch = j.n_ops || !j.src_is_live;
         // identical checksum-only groups (speculative branches) ride in one launch; a batch already fills the chip, so no roles
         const bool batchable = dead && j.n_saves > 0 && !w->jit_marks && cover <= JIT_BATCH_MAX_SLOTS && !w->has_peers;   // (peer bindings: one view, published per launch)
@@ -943,6 +968,7 @@ int run_request_groups_gen(ggrs_world* w, const ggrs_request* reqs, uint32_t n, 
             if (w->has_effects) attach_effects(w, j);
             const bool applies = launch && w->has_effects && j.n_steps;
             const bool reduces = launch && w->has_reduces && j.n_steps;
+            const bool sums = launch && w->has_sums && j.n_steps;
             const bool remotes = launch && w->has_remote && j.n_steps;
             if (launch) {
                 if (j.dp_s) ++w->dp_groups;
@@ -950,7 +976,7 @@ int run_request_groups_gen(ggrs_world* w, const ggrs_request* reqs, uint32_t n, 
                 if (!fn) fn = w->jit_fn;
                 // nothing is queued behind this kernel when its rows are folded later (or there is nothing to fold) and no spawn system follows:
                 // the batch event of an enqueued list then completes WITH it (no marker packet between this tick's kernel and the next one's)
-                const bool last_gpu_op = fold.route != FoldRoute::Finalize && !gs.spawn_req && !w->prof && !applies && !reduces && !remotes;
+                const bool last_gpu_op = fold.route != FoldRoute::Finalize && !gs.spawn_req && !w->prof && !applies && !reduces && !sums && !remotes;
                 hipEvent_t done = last_gpu_op ? w->batch_ev : nullptr;
                 rc = launch_jit(w, fn, w->dev_spawn && jit_dev_stream(w) ? g : jit_grid(g), j.dp_s ? (j.n_saves + j.dp_s) / j.dp_s : 1u, 1, jit_lane_fold_bytes(w, n_cks, j.n_saves), j, bytes_slot * w->len, done); if (rc) return rc;
                 w->batch_ev_attached = done != nullptr;
@@ -960,6 +986,7 @@ int run_request_groups_gen(ggrs_world* w, const ggrs_request* reqs, uint32_t n, 
             if (remotes) { rc = apply_remote(w); if (rc) return rc; }     // ahead of the effects: they apply to the alive and presence bits the remote commands left
             if (applies) { rc = apply_effects(w); if (rc) return rc; }
             if (reduces) { rc = apply_reduces(w); if (rc) return rc; }
+            if (sums) { rc = apply_sums(w, j.n_units); if (rc) return rc; }
         }
         ns += j.n_saves;
         // ---- spawn follow-up, read back
@@ -1030,6 +1057,7 @@ int validate_branch_step(ggrs_world* w, const ggrs_branch_step& st) {
     if (!w->gen_ok) return w->fail(GGRS_E_INVALID, "branch steps need the generated request-group kernel, which this world does not have: %s", w->jit_status.c_str());
     if (w->has_peers) return w->fail(GGRS_E_INVALID, "branch steps are not available for worlds with peer bindings (a member runs several frames per launch, a peer read sees the start of ONE frame): use ggrs_hip_fanout_step");
     if (w->has_remote) return w->fail(GGRS_E_INVALID, "branch steps (ggrs_hip_fanout_step_branches) are not available for worlds with remote bindings (ggrs_hip_add_custom_system_remote: a member runs several frames per launch, the remote commands of ONE frame are applied behind a launch): use ggrs_hip_fanout_step");
+    if (w->has_sums) return w->fail(GGRS_E_INVALID, "branch steps (ggrs_hip_fanout_step_branches) are not available for worlds with sum bindings (ggrs_hip_add_custom_system_sums: a member runs several frames per launch, the float sums of ONE frame are folded behind a launch): use ggrs_hip_fanout_step");
     if (w->has_reduces) return w->fail(GGRS_E_INVALID, "branch steps (ggrs_hip_fanout_step_branches) are not available for worlds with reduce bindings (ggrs_hip_add_custom_system_reduces: a member runs several frames per launch, the reductions of ONE frame are applied behind a launch): use ggrs_hip_fanout_step");
     if (w->has_effects) return w->fail(GGRS_E_INVALID, "branch steps are not available for worlds with effect bindings (a member runs several frames per launch, the sends of ONE frame are applied behind a launch): use ggrs_hip_fanout_step");
     // a retained block's presence masks are decided by the branch's own versions, which say nothing of what the systems inserted or removed: not offered in this version

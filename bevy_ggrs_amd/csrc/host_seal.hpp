@@ -293,6 +293,53 @@ int remote_validate(ggrs_world* w) {
     if (!w->knobs.tick_jit) return w->fail(GGRS_E_INVALID, "remote bindings need the generated request-group kernel, which this world does not have: disabled (GGRS_TICK_JIT=0)");
     return GGRS_OK;
 }
+void sum_part_release(ggrs_world* w) {
+    if (w->sum_part.d) (void)hipFree(w->sum_part.d);
+    w->sum_part = ggrs_world::SumPartials{};
+}
+// Sum bindings (ggrs_hip_add_custom_system_sums): the rules of reduces_validate, for the same reason -- "the frame's total lands at the END of the frame" equals Bevy's
+// sequential ResMut write only when nothing that runs at or after a word's first summer looks at the word -- plus: the word is a float or a double, it is under no
+// reduce binding (two applies would each add to the cell: which ran first would show), and the world has at most GGRS_SUM_MAX_WORDS of them.  What a world with device
+// resources refuses, resources_validate refuses for this one too.  After build_layout; no device needed.
+int sums_validate(ggrs_world* w) {
+    if (!world_has_sums(w)) return GGRS_OK;
+    struct First { uint32_t res, word; };
+    std::vector<First> seen;
+    for (size_t i = 0; i < w->systems.size(); ++i) {
+        if (w->systems[i].kind != GGRS_SYS_CUSTOM) continue;
+        const ggrs_world::Custom& c = w->customs[w->systems[i].comp[0]];
+        const char* nm = c.name.c_str();
+        for (uint32_t j = 0; j < c.n_sum; ++j) {
+            const uint32_t rr = c.sres[j], rw = c.sword[j];
+            if (rr >= w->resources.size()) return w->fail(GGRS_E_INVALID, "custom system '%s': sum binding %u names resource %u, which is not registered (%zu resources)", nm, j, rr, w->resources.size());
+            const ggrs_world::Resource& r = w->resources[rr];
+            if (rw >= r.n_words) return w->fail(GGRS_E_INVALID, "custom system '%s': sum binding %u names word %u of resource %u ('%s'), which has %u words", nm, j, rw, rr, r.name.c_str(), r.n_words);
+            if (r.word_bytes != 4 && r.word_bytes != 8) return w->fail(GGRS_E_INVALID, "custom system '%s': sum binding %u names word %u of resource %u ('%s'), whose words have %u bytes: sums need 4-byte (float) or 8-byte (double) words", nm, j, rw, rr, r.name.c_str(), r.word_bytes);
+            for (auto& o : w->customs) for (uint32_t q = 0; q < o.n_red; ++q) if (o.dres[q] == rr && o.dword[q] == rw)
+                return w->fail(GGRS_E_INVALID, "custom system '%s': sum binding %u sums into word %u of resource %u ('%s'), which custom system '%s' reduces into through reduce binding %u: a word has a sum binding or a reduce binding, not both", nm, j, rw, rr, r.name.c_str(), o.name.c_str(), q);
+            bool first = true;
+            for (auto& f : seen) first &= !(f.res == rr && f.word == rw);
+            if (!first) continue;
+            if (seen.size() == GGRS_SUM_MAX_WORDS) return w->fail(GGRS_E_INVALID, "custom system '%s': sum binding %u (word %u of resource %u, '%s') is the world's summed word number %zu: at most %d (GGRS_SUM_MAX_WORDS)", nm, j, rw, rr, r.name.c_str(), seen.size() + 1, GGRS_SUM_MAX_WORDS);
+            seen.push_back(First{rr, rw});                               // system i is the word's first summer
+            for (size_t k = i; k < w->systems.size(); ++k) {
+                const ggrs_system_desc& d = w->systems[k];
+                if (d.kind == GGRS_SYS_CUSTOM) {
+                    const ggrs_world::Custom& o = w->customs[d.comp[0]];
+                    for (uint32_t q = 0; q < o.n_res; ++q) if (o.rres[q] == rr && o.rword[q] == rw)
+                        return w->fail(GGRS_E_INVALID, "custom system '%s' (system %zu) sums into word %u of resource %u ('%s'), which custom system '%s' (system %zu), registered at or after it, reads through resource binding %u: "
+                                                       "no system registered at or after the first summer of a word reads or writes that word", nm, i, rw, rr, r.name.c_str(), o.name.c_str(), k, q);
+                } else if (d.kind == GGRS_SYS_RESOURCE) {
+                    const ggrs_world::ResSys& o = w->res_systems[d.comp[0]];
+                    for (uint32_t q = 0; q < o.n_bind; ++q) if (o.res[q] == rr && o.word[q] == rw)
+                        return w->fail(GGRS_E_INVALID, "custom system '%s' (system %zu) sums into word %u of resource %u ('%s'), which resource system '%s' (system %zu), registered after it, binds: "
+                                                       "no system registered at or after the first summer of a word reads or writes that word", nm, i, rw, rr, r.name.c_str(), o.name.c_str(), k);
+                }
+            }
+        }
+    }
+    return GGRS_OK;
+}
 int seal(ggrs_world* w) {
     if (w->layout_only) return w->fail(GGRS_E_NO_DEVICE, "GGRS_WORLD_LAYOUT_ONLY world: there is no device behind it");
     if (w->sealed) return GGRS_OK;
@@ -307,6 +354,7 @@ int seal(ggrs_world* w) {
     peer_view_release(w);
     fx_inbox_release(w);
     rd_inbox_release(w);
+    sum_part_release(w);
     rx_inbox_release(w);
     if (w->h_results) { (void)hipHostFree(w->h_results); w->h_results = nullptr; w->d_results = nullptr; }
     if (w->h_stage) { (void)hipHostFree(w->h_stage); w->h_stage = nullptr; w->d_hstage = nullptr; }
@@ -376,6 +424,8 @@ int seal_impl(ggrs_world* w) {
     { const int rrc = resources_validate(w); if (rrc) return rrc; }
     { const int drc = reduces_validate(w); if (drc) return drc; }
     { const int xrc = remote_validate(w); if (xrc) return xrc; }
+    { const int src = sums_validate(w); if (src) return src; }
+    w->has_sums = world_has_sums(w);
     w->has_remote = world_has_remote(w);
     w->rem_comps = world_rem_comps(w);
     w->has_reduces = world_has_reduces(w);
@@ -596,6 +646,19 @@ int seal_impl(ggrs_world* w) {
         HIPCHK(w, hipMalloc((void**)&rd.d, fill.size()));
         HIPCHK(w, hipMemcpyAsync(rd.d, fill.data(), fill.size(), hipMemcpyHostToDevice, w->stream));
         HIPCHK(w, hipStreamSynchronize(w->stream));                    // (the host buffer dies here)
+    }
+    if (w->has_sums) {
+        // the sum partials: per summed word one 8-byte entry per 64-slot unit of the padded capacity (a multiple of 4 units: every wave of a launch's last workgroup
+        // stores its entry), then two ping-pong buffers per word for k_apply_sums' upper levels (a pass folds 16 entries into one).  Never read before written: zeroed once
+        ggrs_world::SumPartials& sp = w->sum_part;
+        sp = ggrs_world::SumPartials{};
+        SummedWord sw[GGRS_SUM_MAX_WORDS];
+        sp.n_words = summed_words(w, sw);
+        sp.units = (uint32_t)((w->cap_pad + 63) / 64 + 3) & ~3u;
+        sp.tmp_entries = (sp.units + 15u) / 16u;
+        const size_t bytes = (size_t)sp.n_words * ((size_t)sp.units + 2u * sp.tmp_entries) * 8u;
+        HIPCHK(w, hipMalloc((void**)&sp.d, bytes));
+        HIPCHK(w, hipMemsetAsync(sp.d, 0, bytes, w->stream));
     }
     if (w->has_remote) {
         // the remote inbox: one u32 per slot of the padded capacity, zeroed -- what it holds whenever no group-and-apply pair is in flight

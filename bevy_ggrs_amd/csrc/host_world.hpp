@@ -180,6 +180,8 @@ struct ggrs_world {
         // remote bindings (ggrs_hip_add_custom_system_remote): components of OTHER entities the system may insert / remove through e.send_insert / e.send_remove(slot, j);
         // a binding with GGRS_REMOTE_DESPAWN names no component (xcomp = GGRS_REMOTE_ENTITY): e.send_despawn(slot)
         uint32_t n_rem = 0, xcomp[GGRS_REMOTE_MAX_BINDINGS] = {}, xflags[GGRS_REMOTE_MAX_BINDINGS] = {};
+        // sum bindings (ggrs_hip_add_custom_system_sums): float / double words of the world's device resources the system adds into through e.sum_f32 / e.sum_f64(j, v)
+        uint32_t n_sum = 0, sres[GGRS_SUM_MAX_BINDINGS] = {}, sword[GGRS_SUM_MAX_BINDINGS] = {};
     };
     std::vector<Custom> customs;
     // DEVICE RESOURCES (ggrs_hip_register_resource): a few 4- or 8-byte words per world, carried by every wave of the generated kernel in wave-uniform registers.
@@ -220,6 +222,12 @@ struct ggrs_world {
     // edits the live block's masks and columns and zeroes it again.  Not snapshot state
     struct RemoteInbox { uint32_t* d = nullptr; uint32_t n_comps = 0, comp[GGRS_REMOTE_MAX_COMPONENTS] = {}, flags[GGRS_REMOTE_MAX_COMPONENTS] = {}; uint64_t applies = 0; } rx_inbox;
     bool has_remote = false;             // some system has remote bindings (set at seal)
+    // THE SUM PARTIALS of a world with sum bindings (allocated at seal): per summed word one array of `units` 8-byte entries, entry u = the value of the balanced tree
+    // over the 64 slots of unit u (a float in the low four bytes, or a double), stored by that unit's wave with one plain store in every launch that covers the unit --
+    // so an entry is only ever valid for the launch that just ran, and k_apply_sums reads no entry beyond the units that launch covered.  Behind the arrays: two
+    // ping-pong buffers per word for the upper levels of the tree.  Not snapshot state
+    struct SumPartials { uint8_t* d = nullptr; uint32_t units = 0, n_words = 0, tmp_entries = 0; uint64_t applies = 0; } sum_part;
+    bool has_sums = false;               // some system has sum bindings (set at seal)
     uint64_t rem_comps = 0;              // bit c = some system may remotely insert or remove component c: its mask and columns get fresh versions with every AdvanceWorld (set at seal)
     bool has_commands = false;           // some system has command bindings (set at seal)
     bool has_resources = false;          // the world has device resources (ggrs_hip_register_resource; set at seal)
@@ -650,6 +658,23 @@ inline uint32_t reduced_words(const ggrs_world* w, ReducedWord* out) {
         if (seen || n == RD_MAX_WORDS) continue;
         const ggrs_world::Resource& r = w->resources[c.dres[j]];
         out[n++] = ReducedWord{c.dres[j], c.dword[j], c.dop[j], r.word_bytes, r.off + c.dword[j] * r.word_bytes, r.reg + c.dword[j]};
+    }
+    return n;
+}
+inline bool world_has_sums(const ggrs_world* w) { for (auto& c : w->customs) if (c.n_sum) return true; return false; }
+// the distinct summed words of the world in order of first use (systems in registration order, sum bindings in order); returns how many there are (more than
+// GGRS_SUM_MAX_WORDS: only the first ones are written -- sums_validate refuses such a world, as it does a binding to something that is not registered)
+struct SummedWord { uint32_t res, word, wb, off, reg; };          // off: its byte offset inside a resource cell; reg: the r<reg> of the generated kernel that holds the word
+inline uint32_t summed_words(const ggrs_world* w, SummedWord* out) {
+    uint32_t n = 0;
+    for (auto& c : w->customs) for (uint32_t j = 0; j < c.n_sum; ++j) {
+        if (c.sres[j] >= w->resources.size() || c.sword[j] >= w->resources[c.sres[j]].n_words) continue;
+        bool seen = false;
+        for (uint32_t k = 0; k < n && k < GGRS_SUM_MAX_WORDS; ++k) seen |= out[k].res == c.sres[j] && out[k].word == c.sword[j];
+        if (seen) continue;
+        const ggrs_world::Resource& r = w->resources[c.sres[j]];
+        if (n < GGRS_SUM_MAX_WORDS) out[n] = SummedWord{c.sres[j], c.sword[j], r.word_bytes, r.off + c.sword[j] * r.word_bytes, r.reg + c.sword[j]};
+        ++n;
     }
     return n;
 }

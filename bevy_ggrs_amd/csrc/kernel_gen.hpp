@@ -286,6 +286,44 @@ inline std::string res_system_typedef(const ggrs_world* w, const ggrs_world::Res
     "    GGRS_RD_LADDER(rd_step64)\n" \
     "    return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), 63) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 63);\n" \
     "}\n"
+// ... in a world with sum bindings (ggrs_hip_add_custom_system_sums): e.sum_f32(j, v) / e.sum_f64(j, v) add v into the system's sum binding j -- ONE register add
+// into the lane's accumulator of the bound word, which sys_custom hands in before the call and takes back after it: a_s = a_s + v in program order, no memory, no atomic.
+// smw_[j]: the word's bytes (0: no such binding -- the accessor does nothing, as one of the other width); sma_[j]: the binding whose accumulator binding j uses (j
+// itself, or the first binding of the same word by this system, so that calls through both keep their program order).  Worlds without sum bindings keep their text.
+#define GGRS_SUM_MEMBERS_TEXT \
+    "    float smf_[4] = {}; double smd_[4] = {}; unsigned char smw_[4] = {}, sma_[4] = {};   /* the system's sum bindings: the lane's accumulator (float / double), the word's bytes, the binding that owns the accumulator */\n" \
+    "    __device__ void sum_f32(int j, float v) { if ((unsigned)j < 4u && smw_[j] == 4) smf_[sma_[j]] = smf_[sma_[j]] + v; }\n" \
+    "    __device__ void sum_f64(int j, double v) { if ((unsigned)j < 4u && smw_[j] == 8) smd_[sma_[j]] = smd_[sma_[j]] + v; }\n"
+// The wave-level sum of such a world's accumulators at the end of the launch: the lane pattern of wave_xor32 (device_prelude.hpp) with an IEEE add.  Lane l holds slot
+// `unit * 64 + l`, and because the add is commutative bit for bit the ladder IS the balanced binary tree over the wave's 64 slots (include/ggrs_hip.h) -- at every step
+// a lane that is written adds exactly the two sibling sub-tree sums of the next level:
+//   quad_perm:[1,0,3,2]  lane l takes lane l ^ 1: x[2i] + x[2i+1], level 1, in both lanes of the pair (the same bits: a + b == b + a);
+//   quad_perm:[2,3,0,1]  lane l takes lane l ^ 2, which holds the sibling pair's level-1 sum: level 2, in all four lanes of the quad;
+//   row_half_mirror      lane l takes lane 7 - l of its group of 8, a lane of the OTHER quad of that group, which holds that quad's level-2 sum: level 3;
+//   row_mirror           lane l takes lane 15 - l of its row, a lane of the other half row, which holds its level-3 sum: level 4 -- every lane holds its row's sum;
+//   row_bcast:15         rows 1 and 3 take lane 15 of rows 0 and 2: row 1 = R1 + R0, row 3 = R3 + R2, level 5;
+//   row_bcast:31         rows 2 and 3 take lane 31 (R1 + R0): row 3 = (R3 + R2) + (R1 + R0), level 6 -- lane 63 holds the root.
+// `old` of every DPP move is -0.0, so a row the row mask leaves out adds the exact identity and keeps its bits.  A double moves as two halves and is added as one
+// double.  Only in the text of worlds with sum bindings.
+#define GGRS_SUM_WAVE_TEXT \
+    "template <int CTRL, int ROWS> __device__ __forceinline__ float sm_step32(float v) {\n" \
+    "    return v + __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp((int)0x80000000u, (int)__float_as_uint(v), CTRL, ROWS, 0xF, false));\n" \
+    "}\n" \
+    "template <int CTRL, int ROWS> __device__ __forceinline__ double sm_step64(double v) {\n" \
+    "    const uint64_t b_ = (uint64_t)__double_as_longlong(v);\n" \
+    "    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp((int)0x80000000u, (int)(uint32_t)(b_ >> 32), CTRL, ROWS, 0xF, false);\n" \
+    "    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)b_, CTRL, ROWS, 0xF, false);\n" \
+    "    return v + __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));\n" \
+    "}\n" \
+    "#define GGRS_SM_LADDER(STEP) \\\n" \
+    "    v = STEP<0xB1, 0xF>(v);      /* quad_perm:[1,0,3,2]: level 1 */ \\\n" \
+    "    v = STEP<0x4E, 0xF>(v);      /* quad_perm:[2,3,0,1]: level 2 */ \\\n" \
+    "    v = STEP<0x141, 0xF>(v);     /* row_half_mirror: level 3 */ \\\n" \
+    "    v = STEP<0x140, 0xF>(v);     /* row_mirror: level 4, every lane holds its row's sum */ \\\n" \
+    "    v = STEP<0x142, 0xA>(v);     /* row_bcast:15 into rows 1 and 3: level 5 */ \\\n" \
+    "    v = STEP<0x143, 0xC>(v);     /* row_bcast:31 into rows 2 and 3: level 6, lane 63 holds the root */\n" \
+    "__device__ __forceinline__ float wave_sum32(float v) { GGRS_SM_LADDER(sm_step32) return v; }        // lane 63: the tree over the wave's 64 slots\n" \
+    "__device__ __forceinline__ double wave_sum64(double v) { GGRS_SM_LADDER(sm_step64) return v; }\n"
 // ... in a world with remote bindings (ggrs_hip_add_custom_system_remote): e.send_insert(slot, j) / e.send_remove(slot, j) / e.send_despawn(slot) command ANOTHER
 // entity -- a bounds test against the len of the frame's source block, then ONE relaxed agent-scope atomic OR into the slot's word of the world's linear REMOTE INBOX
 // (host_world.hpp RemoteInbox) whose result is unused: a native no-return global_atomic_or, no compare-and-swap loop.  OR is commutative, associative and idempotent:
@@ -301,10 +339,11 @@ inline std::string res_system_typedef(const ggrs_world* w, const ggrs_world::Res
     "    __device__ void send_insert(ggrs_u64 s, int j) const __attribute__((enable_if(j >= 0 && j < 4 && ((GGRS_XI >> j) & 1u), \"e.send_insert(slot, j): remote binding j (a constant) must be declared with GGRS_REMOTE_INSERT\"))) { rx_or_(s, 1u << rxb_[j]); }\n" \
     "    __device__ void send_remove(ggrs_u64 s, int j) const __attribute__((enable_if(j >= 0 && j < 4 && ((GGRS_XR >> j) & 1u), \"e.send_remove(slot, j): remote binding j (a constant) must be declared with GGRS_REMOTE_REMOVE\"))) { rx_or_(s, 2u << rxb_[j]); }\n" \
     "    __device__ void send_despawn(ggrs_u64 s) const __attribute__((enable_if(GGRS_XD != 0u, \"e.send_despawn(slot): the system must have a remote binding with GGRS_REMOTE_DESPAWN\"))) { rx_or_(s, 1u); }\n"
-inline std::string entity_text(bool effects, bool peers, bool commands, bool default_typedef = true, bool resources = false, bool reduces = false, bool remote = false) {
+inline std::string entity_text(bool effects, bool peers, bool commands, bool default_typedef = true, bool resources = false, bool reduces = false, bool remote = false, bool sums = false) {
     std::string t = effects ? GGRS_ENTITY_EFFECTS_TEXT : (peers ? GGRS_ENTITY_PEERS_TEXT : GGRS_ENTITY_TEXT);
     if (resources) t.insert(t.rfind("};\n"), GGRS_RES_MEMBERS_TEXT);
     if (reduces) t.insert(t.rfind("};\n"), GGRS_RED_MEMBERS_TEXT);
+    if (sums) t.insert(t.rfind("};\n"), GGRS_SUM_MEMBERS_TEXT);
     if (!commands && !remote) return t;
     const std::string head = "struct GgrsEntity {\n";
     if (remote && !effects && !peers) t.insert(0, "#ifndef GGRS_G\n#define GGRS_G __attribute__((address_space(1)))\n#endif\n");
@@ -698,6 +737,8 @@ struct GgrsJitArgs {
     // THE REMOTE INBOX of a world with remote bindings (host_world.hpp RemoteInbox; present only in such worlds): one u32 per slot; rx_len = the len of the group's source
     // block, as fx_len -- which the kernel reads instead in a world that also has effect bindings (rx_len is then absent from the device block)
     ggrs_u32* rx_inbox; ggrs_u64 rx_len;
+    // THE SUM PARTIALS of a world with sum bindings (host_world.hpp SumPartials; present only in such worlds): 8 bytes per summed word and 64-slot unit
+    unsigned char* sum_part;
     ggrs_u32 cached_saves;                           // with nt: bit i = Save i is stored through the L2 all the same (the snapshot the NEXT group is expected to load)
     ggrs_u32 ff_blocks, ff_nvals, ff_g, ff_stride, ff_istride, ff_split, ff_self;   // entry e of row r: ff_rows[r * ff_stride + e * ff_istride]
     ggrs_u32 dt_bits[24], aux_bits[24]; int step_frame[24], step_confirmed[24]; ggrs_u32 spawn_count[24];
@@ -724,7 +765,7 @@ struct JitLayout {
     struct Member { uint32_t bytes = 0, save_dst = 0, save_rows = 0, save_len = 0, spawn_payload = 0, spawn_first = 0, live = 0, live_rows = 0, marks_dst = 0, save_pmask = 0, live_pmask = 0,
                     spawn_count = 0, n_inputs = 0, inputs = 0, save_tagok = 0, live_tagok = 0; } m;
 };
-struct JitNeeds { bool spawn, inputs, marks, box, vtags, devspawn, devstream, nr, peers, effects, commands, res, red, rem; };
+struct JitNeeds { bool spawn, inputs, marks, box, vtags, devspawn, devstream, nr, peers, effects, commands, res, red, rem, sum; };
 // the distinct peer-bound columns of the world in order of first use (systems in registration order, peer bindings in order) and the components they belong to;
 // returns how many there are (more than GGRS_PEER_MAX_COLUMNS: only the first ones are written -- peers_validate refuses such a world)
 inline uint32_t peer_cols(const ggrs_world* w, uint32_t* cols, uint32_t* n_pres = nullptr, uint32_t* pres = nullptr) {
@@ -769,6 +810,7 @@ JitLayout jit_layout(const ggrs_world* w) {
     L.cap_steps = std::min<uint32_t>(MAX_TICK_STEPS, std::max<uint32_t>(3, w->max_depth + 2));
     if (need.peers) L.cap_steps = 1;             // peer reads see the world at the START of the frame: the view is published per group, so a group holds one AdvanceWorld
     if (need.rem) L.cap_steps = 1;               // remote commands land at the END of the frame too: k_apply_remote runs behind the group's launch
+    if (need.sum) L.cap_steps = 1;               // ... and so do the frame's float sums: k_apply_sums runs behind the group's launch
     if (need.red) L.cap_steps = 1;               // reductions land at the END of the frame too: k_apply_reduces runs behind the group's launch
     if (need.effects) L.cap_steps = 1;           // effects land at the END of the frame: the inbox is applied behind the group's launch, so a group ends on its one AdvanceWorld
     uint32_t fx_cols[GGRS_EFFECT_MAX_COLUMNS]; const uint32_t n_fx = std::min<uint32_t>(effect_cols(w, fx_cols), GGRS_EFFECT_MAX_COLUMNS);
@@ -793,6 +835,7 @@ JitLayout jit_layout(const ggrs_world* w) {
         FA("unsigned char*", fx_col, n_fx, need.effects); F1("ggrs_u64", fx_len, need.effects);
         F1("const unsigned char*", res_src, need.res); F1("unsigned char*", rd_inbox, need.red);
         F1("ggrs_u32*", rx_inbox, need.rem); F1("ggrs_u64", rx_len, need.rem && !need.effects);
+        F1("unsigned char*", sum_part, need.sum);
         FA("unsigned char*", save_dst, S, true); FA("ggrs_u64", save_rows, S, true); FA("ggrs_u64", save_len, S, true);
         FS("const unsigned char*", spawn_payload, need.spawn); FS("ggrs_u64", spawn_first, need.spawn);
         FA("int", save_frame, S, true); FA("ggrs_u32", save_pmask, S, true);
@@ -1011,7 +1054,8 @@ inline uint64_t jit_marks_rec_frames_off(const ggrs_world* w) { return align_up(
 inline uint64_t jit_marks_rec_bytes(const ggrs_world* w) { return jit_marks_rec_frames_off(w) + align_up(w->cap_pad * 4, ALIGN); }
 // which optional parts of the argument block this world's kernel reads
 JitNeeds jit_needs(const ggrs_world* w) {
-    JitNeeds n{false, false, false, false, false, false, false, false, false, false, false, false, false, false};
+    JitNeeds n{false, false, false, false, false, false, false, false, false, false, false, false, false, false, false};
+    n.sum = world_has_sums(w);
     n.rem = world_has_remote(w);
     n.red = world_has_reduces(w);
     n.res = world_has_resources(w);
@@ -1179,9 +1223,10 @@ struct JitGen {
                                     "#define GGRS_SP_READ %uu                                                           // sp_desc[GGRS_SP_READ x tiles + tile]: that tile has read its starting len\n",
                          2u + (unsigned)MAX_TICK_SAVES, 2u * (unsigned)MAX_TICK_STEPS);
         s += GGRS_FRAME_TEXT;
-        s += entity_text(need.effects, need.peers, need.commands, true, need.res, need.red, need.rem);
+        s += entity_text(need.effects, need.peers, need.commands, true, need.res, need.red, need.rem, need.sum);
         if (need.res) s += GGRS_RESOURCES_TEXT;
         if (need.red) s += GGRS_REDUCE_WAVE_TEXT;
+        if (need.sum) s += GGRS_SUM_WAVE_TEXT;
         s += GGRS_COMPONENT_TEXT;
         s += GGRS_WORDS_TEXT;
         s += jit_layout_text(L);
@@ -1582,9 +1627,36 @@ struct JitGen {
         }
         s += "    }\n";
     }
+    // sum bindings: one per-lane accumulator register per summed word, at -0.0 (the exact identity of IEEE addition, as a bit pattern) when the launch starts; sys_custom
+    // hands it to the system and takes it back, unit_tails sums it over the wave in the fixed order of the tree and stores the wave's value
+    void sum_state() {
+        if (!need.sum) return;
+        SummedWord sw[GGRS_SUM_MAX_WORDS]; const uint32_t n = std::min<uint32_t>(summed_words(w, sw), GGRS_SUM_MAX_WORDS);
+        s += "    // SUM BINDINGS: this lane's accumulators, one per summed resource word -- a_s of this lane's slot, -0.0 until a system of this lane adds into it\n";
+        for (uint32_t k = 0; k < n; ++k)
+            sfmt(s, "    %s sm%u = %s;                // %s word %u\n", sw[k].wb == 8 ? "double" : "float", sw[k].reg,
+                 sw[k].wb == 8 ? "__longlong_as_double((long long)0x8000000000000000ull)" : "__uint_as_float(0x80000000u)", file_name(w->resources[sw[k].res].name).c_str(), sw[k].word);
+    }
+    // ... at a convergent point after the wave's unit: the DPP ladder of float adds per accumulator, then lane 63 -- which holds the root -- stores the wave's value with
+    // ONE plain store into entry `unit` of the word's partial array.  Unconditional: every unit a launch covers writes its entry in that launch, so k_apply_sums, which
+    // reads only those units, never sees an entry of an earlier launch and the array needs no reset
+    void sum_publish() {
+        if (!need.sum) return;
+        SummedWord sw[GGRS_SUM_MAX_WORDS]; const uint32_t n = std::min<uint32_t>(summed_words(w, sw), GGRS_SUM_MAX_WORDS);
+        const uint64_t units = ((w->cap_pad + 63) / 64 + 3) & ~3ull;      // == SumPartials::units (host_seal.hpp)
+        s += "    {   // SUM BINDINGS: the balanced tree over this wave's 64 slots of every accumulator, stored by lane 63 into sum_part[word][unit]\n";
+        for (uint32_t k = 0; k < n; ++k) {
+            const char* ft = sw[k].wb == 8 ? "double" : "float";
+            sfmt(s, "        { const %s v_ = wave_sum%u(sm%u);\n"
+                    "          if (lane == 63u) *(GGRS_G %s*)(a.sum_part + (%lluull + (uint64_t)gu * 8ull)) = v_; }\n",
+                 ft, sw[k].wb * 8u, sw[k].reg, ft, (unsigned long long)(k * units * 8ull));
+        }
+        s += "    }\n";
+    }
     void unit_state() {
         res_state();
         red_state();
+        sum_state();
         for (uint32_t k = 0; k < n_cks; ++k) if (spec_memo[k]) {
             const std::string tail = chunk_expr(w->comps[cks_comp[k]], cks_comp[k], 8, spec_bytes[k] - 8);
             sfmt(s, "    uint32_t mt%u = (uint32_t)(%s); uint64_t ma%u = a.n_saves ? sea_tail_folded(mt%u, %uull) : 0ull;   // memoised tail of checksum spec %u, with the finish's K2 ^ K3 ^ bytes folded in\n", k, tail.c_str(), k, k, spec_bytes[k], k);
@@ -1796,6 +1868,13 @@ struct JitGen {
         return ReducedWord{0, 0, 0, 4, 0, 0};
     }
     bool red_dup(const ggrs_world::Custom& c, uint32_t j) const { for (uint32_t q = 0; q < j; ++q) if (c.dres[q] == c.dres[j] && c.dword[q] == c.dword[j]) return true; return false; }
+    // sum binding j of a system as the world's summed word (its register, width, offset), and the first binding of the same system that names the same word
+    SummedWord sum_of(const ggrs_world::Custom& c, uint32_t j) const {
+        SummedWord sw[GGRS_SUM_MAX_WORDS]; const uint32_t n = std::min<uint32_t>(summed_words(w, sw), GGRS_SUM_MAX_WORDS);
+        for (uint32_t k = 0; k < n; ++k) if (sw[k].res == c.sres[j] && sw[k].word == c.sword[j]) return sw[k];
+        return SummedWord{0, 0, 4, 0, 0};
+    }
+    uint32_t sum_owner(const ggrs_world::Custom& c, uint32_t j) const { for (uint32_t q = 0; q < j; ++q) if (c.sres[q] == c.sres[j] && c.sword[q] == c.sword[j]) return q; return j; }
     void sys_custom(size_t i, const ggrs_system_desc& d) {
         const ggrs_world::Custom& c = w->customs[d.comp[0]];
         s += "            if (alive_0";
@@ -1862,7 +1941,18 @@ struct JitGen {
             const ReducedWord r = red_of(c, j);
             sfmt(s, "                ent.rd_[%u] = %s; ent.rdw_[%u] = %uu; ent.rdo_[%u] = %uu;\n", j, red_dup(c, j) ? rd_lit(r).c_str() : ("rd" + std::to_string(r.reg)).c_str(), j, r.wb, j, r.op);
         }
+        // sum bindings: the lane's accumulator of the bound word goes in typed, with the word's bytes, and comes back after the call; a second binding of the same word
+        // by the same system shares the first one's accumulator, so calls through both keep their program order
+        for (uint32_t j = 0; j < c.n_sum; ++j) {
+            const SummedWord r = sum_of(c, j); const uint32_t own = sum_owner(c, j);
+            if (own == j) sfmt(s, "                ent.%s[%u] = sm%u; ent.smw_[%u] = %uu; ent.sma_[%u] = %uu;\n", r.wb == 8 ? "smd_" : "smf_", j, r.reg, j, r.wb, j, j);
+            else sfmt(s, "                ent.smw_[%u] = %uu; ent.sma_[%u] = %uu;\n", j, r.wb, j, own);
+        }
         sfmt(s, "                ggrs_sys_%u::ggrs_system(ent, fr%zu);\n", d.comp[0], i);
+        for (uint32_t j = 0; j < c.n_sum; ++j) {
+            const SummedWord r = sum_of(c, j);
+            if (sum_owner(c, j) == j) sfmt(s, "                sm%u = ent.%s[%u];\n", r.reg, r.wb == 8 ? "smd_" : "smf_", j);
+        }
         for (uint32_t j = 0; j < c.n_red; ++j) {
             const ReducedWord r = red_of(c, j);
             const char* ut = r.wb == 8 ? "uint64_t" : "uint32_t";
@@ -2012,6 +2102,7 @@ struct JitGen {
                     "    }\n", need.marks ? " && !dis_0" : "");
         }
         red_publish();
+        sum_publish();
         s += "    }   // the wave's unit\n";
     }
     // ---- 13. this workgroup's partial rows

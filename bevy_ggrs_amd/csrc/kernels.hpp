@@ -790,6 +790,60 @@ __global__ __launch_bounds__(64) void k_apply_reduces(RdApplyArgs a) {
     }
 }
 
+// THE SUM PARTIALS (ggrs_hip_add_custom_system_sums; host_world.hpp ggrs_world::SumPartials).  Right behind every request group that holds an AdvanceWorld: ONE
+// launch, one workgroup per summed word.  Entry u of the word's array is the balanced tree over the 64 slots of unit u, stored by that unit's wave in the launch
+// that just ran; the units that launch covered are [0, n_units), everything beyond counts as -0.0 and is NEVER loaded (an entry there may be of an earlier, larger
+// launch).  The workgroup continues the same tree -- pair 2i with 2i + 1, level by level: while more than SM_TPB values are left, a pass in which every thread folds
+// aligned runs of 16 values (four levels in registers) from one buffer into the other, a workgroup barrier between passes; then the last ten levels in LDS, stride
+// doubling in place (x[2s i] += x[2s i + s]: the operands are the two sibling sub-tree sums, and the add is commutative bit for bit).  -0.0 pads every level: the
+// exact identity.  One lane then stores cell + T into the live block's current resource cell.  Plain loads and stores: the waves' stores belong to an EARLIER
+// launch, the kernel boundary is the only synchronisation with it; within the workgroup a barrier orders a pass's stores ahead of the next pass's loads (one CU, one L1).
+constexpr uint32_t SM_TPB = 1024, SM_FAN = 16;
+struct SmApplyArgs {
+    const uint8_t* part; uint8_t* tmp; uint8_t* cell;        // cell: the live block's current resource cell, as the group's launch (and k_apply_reduces) left it
+    uint32_t n_units, units, tmp_entries, n_words;           // n_units: what the group's launch covered; units / tmp_entries: entries per word of the arrays
+    uint32_t off[GGRS_SUM_MAX_WORDS], wb[GGRS_SUM_MAX_WORDS];
+};
+template <typename F> __device__ __forceinline__ F sm_neg_zero();
+template <> __device__ __forceinline__ float sm_neg_zero<float>() { return __uint_as_float(0x80000000u); }
+template <> __device__ __forceinline__ double sm_neg_zero<double>() { return __longlong_as_double((long long)0x8000000000000000ull); }
+template <typename F> __device__ __forceinline__ void sm_fold_word(const SmApplyArgs& a, uint32_t k, F* lds) {
+    const uint32_t t = threadIdx.x;
+    const F nz = sm_neg_zero<F>();
+    const uint8_t* src = a.part + (uint64_t)k * a.units * 8u;
+    uint32_t n = a.n_units, pp = 0;
+    while (n > SM_TPB) {
+        const uint32_t m = (n + SM_FAN - 1u) / SM_FAN;
+        uint8_t* const dst = a.tmp + ((uint64_t)k * 2u + pp) * a.tmp_entries * 8u;
+        for (uint32_t c = t; c < m; c += SM_TPB) {
+            F x[SM_FAN];
+#pragma unroll
+            for (uint32_t i = 0; i < SM_FAN; ++i) { const uint32_t at = c * SM_FAN + i; x[i] = at < n ? *reinterpret_cast<const F*>(src + (uint64_t)at * 8u) : nz; }
+#pragma unroll
+            for (uint32_t wd = SM_FAN; wd > 1u; wd >>= 1)
+#pragma unroll
+                for (uint32_t i = 0; i < wd / 2u; ++i) x[i] = x[2u * i] + x[2u * i + 1u];
+            *reinterpret_cast<F*>(dst + (uint64_t)c * 8u) = x[0];
+        }
+        __syncthreads();
+        src = dst; n = m; pp ^= 1u;
+    }
+    lds[t] = t < n ? *reinterpret_cast<const F*>(src + (uint64_t)t * 8u) : nz;
+    __syncthreads();
+    for (uint32_t st = 1; st < SM_TPB; st <<= 1) {
+        if (t < SM_TPB / (2u * st)) lds[2u * st * t] = lds[2u * st * t] + lds[2u * st * t + st];
+        __syncthreads();
+    }
+    if (t == 0) { F* const c = reinterpret_cast<F*>(a.cell + a.off[k]); *c = *c + lds[0]; }
+}
+__global__ __launch_bounds__(SM_TPB) void k_apply_sums(SmApplyArgs a) {
+    __shared__ double s_lv[SM_TPB];
+    const uint32_t k = blockIdx.x;
+    if (k >= a.n_words) return;
+    if (a.wb[k] == 8) sm_fold_word<double>(a, k, s_lv);
+    else sm_fold_word<float>(a, k, reinterpret_cast<float*>(s_lv));
+}
+
 // System-scope release + acquire on whatever CU / XCD the wave lands on: `buffer_wbl2 sc0 sc1` writes the XCD's dirty L2 lines back,
 // `buffer_inv sc0 sc1` drops its clean ones.  2048 single-wave workgroups cover all 8 XCDs (workgroup b lands on XCD b % 8).
 __global__ void k_flush_l2() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, ""); }

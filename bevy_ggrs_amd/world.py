@@ -297,7 +297,7 @@ class World(WorldBase):
         self.capacity = capacity
 
     def add_custom_system(self, source: str, bindings: Sequence[tuple], iparam=(), fparam=(), name: str = "custom", peers: Sequence[tuple] = (), effects: Sequence[tuple] = (),
-                          commands: Sequence[tuple] = (), resources: Sequence[tuple] = (), reduces: Sequence[tuple] = (), remote=None):
+                          commands: Sequence[tuple] = (), resources: Sequence[tuple] = (), reduces: Sequence[tuple] = (), remote=None, sums=None):
         """add_systems(GgrsSchedule, <your system>) for a per-entity system written in HIP C++ (ggrs_hip_add_custom_system):
         `source` defines `__device__ void ggrs_system(GgrsEntity& e, const GgrsFrame& f)`, `bindings` = [(comp, word), ..]
         are the words it sees as e.f32(i)/e.u32(i)/e.i32(i)/e.u64(i).  Compiled for gfx950 when added; a compile error raises
@@ -317,7 +317,10 @@ class World(WorldBase):
         `remote` = [(comp, flags), ..] (ggrs_hip_add_custom_system_remote): components of OTHER entities the system commands -- with REMOTE_INSERT /
         REMOTE_REMOVE in the flags `e.send_insert(slot, j)` (the component's registered default) / `e.send_remove(slot, j)`, and with
         (REMOTE_ENTITY, REMOTE_DESPAWN) `e.send_despawn(slot)`; every command of a frame lands at the end of the frame, despawn wins over everything,
-        remove wins over insert.  Any list, the empty one included, goes through that entry point; None (the default) does not."""
+        remove wins over insert.  Any list, the empty one included, goes through that entry point; None (the default) does not.
+        `sums` = [(res, word), ..] (ggrs_hip_add_custom_system_sums): float (4-byte) or double (8-byte) words of the world's device resources the system adds into --
+        `e.sum_f32(j, v)` / `e.sum_f64(j, v)`; nothing is returned.  The frame's total is the balanced binary tree over slot indices (bit-exact, independent of
+        launch geometry) and lands at the end of the frame.  Any list, the empty one included, goes through that entry point; None (the default) does not."""
         d = _ffi.CustomSystemDesc()
         d.name, d.source, d.n_bindings = name.encode(), source.encode(), len(bindings)
         if len(bindings) > _ffi.CUSTOM_MAX_BINDINGS:
@@ -325,6 +328,29 @@ class World(WorldBase):
         for i, (c, w) in enumerate(bindings): d.comp[i], d.word[i] = c, w
         for i, v in enumerate(iparam): d.iparam[i] = v
         for i, v in enumerate(fparam): d.fparam[i] = v
+        if sums is not None:
+            remote = remote or ()
+            if (len(peers) > _ffi.PEER_MAX_BINDINGS or len(effects) > _ffi.EFFECT_MAX_BINDINGS or len(commands) > _ffi.COMMAND_MAX_BINDINGS or len(resources) > _ffi.RESOURCE_MAX_BINDINGS
+                    or len(reduces) > _ffi.REDUCE_MAX_BINDINGS or len(remote) > _ffi.REMOTE_MAX_BINDINGS or len(sums) > _ffi.SUM_MAX_BINDINGS):
+                raise ValueError(f"at most {_ffi.PEER_MAX_BINDINGS} peer, {_ffi.EFFECT_MAX_BINDINGS} effect, {_ffi.COMMAND_MAX_BINDINGS} command, {_ffi.RESOURCE_MAX_BINDINGS} resource, "
+                                 f"{_ffi.REDUCE_MAX_BINDINGS} reduce, {_ffi.REMOTE_MAX_BINDINGS} remote and {_ffi.SUM_MAX_BINDINGS} sum bindings")
+            pb = (_ffi.PeerBinding * max(1, len(peers)))()
+            for j, (c, w) in enumerate(peers): pb[j].comp, pb[j].word = c, w
+            eb = (_ffi.EffectBinding * max(1, len(effects)))()
+            for j, (c, w, op) in enumerate(effects): eb[j].comp, eb[j].word, eb[j].op = c, w, op
+            cb = (_ffi.CommandBinding * max(1, len(commands)))()
+            for j, (c, fl) in enumerate(commands): cb[j].comp, cb[j].flags = c, fl
+            rb = (_ffi.ResourceBinding * max(1, len(resources)))()
+            for j, (r, w) in enumerate(resources): rb[j].res, rb[j].word = r, w
+            db = (_ffi.ReduceBinding * max(1, len(reduces)))()
+            for j, (r, w, op) in enumerate(reduces): db[j].res, db[j].word, db[j].op = r, w, op
+            xb = (_ffi.RemoteBinding * max(1, len(remote)))()
+            for j, (c, fl) in enumerate(remote): xb[j].comp, xb[j].flags = c, fl
+            sb = (_ffi.SumBinding * max(1, len(sums)))()
+            for j, (r, w) in enumerate(sums): sb[j].res, sb[j].word = r, w
+            self._check(self._lib.ggrs_hip_add_custom_system_sums(self._p, C.byref(d), pb, len(peers), eb, len(effects), cb, len(commands), rb, len(resources), db, len(reduces), xb, len(remote),
+                                                                  sb, len(sums)))
+            return
         if remote is not None:
             if (len(peers) > _ffi.PEER_MAX_BINDINGS or len(effects) > _ffi.EFFECT_MAX_BINDINGS or len(commands) > _ffi.COMMAND_MAX_BINDINGS or len(resources) > _ffi.RESOURCE_MAX_BINDINGS
                     or len(reduces) > _ffi.REDUCE_MAX_BINDINGS or len(remote) > _ffi.REMOTE_MAX_BINDINGS):

@@ -424,7 +424,8 @@ int ggrs_hip_resource_write(ggrs_world* w, uint32_t res_id, const void* words);
  * atomic into a striped inbox (nothing when the value is the identity); one small launch right behind the group's (k_apply_reduces) folds the stripes into the live
  * block's current resource cell and puts the identities back.  Such a world runs one AdvanceWorld per launch, as a world with effect bindings does.
  * Refused with a message: ggrs_hip_fanout_step_branches, and everything device resources already refuse (ggrs_hip_fanout_step works).  Peers, effects, commands and
- * read bindings in the same world and the same system are allowed.  Out of scope: float reductions, a reducer that reads the running value. */
+ * read bindings in the same world and the same system are allowed.  Out of scope: a reducer that reads the running value; float min / max (float SUMS have their
+ * own bindings: SUM BINDINGS, ggrs_hip_add_custom_system_sums, below). */
 typedef struct { uint32_t res; uint32_t word; uint32_t op; } ggrs_reduce_binding;   /* reduce binding j = word `word` of resource `res`, combined with GGRS_EFFECT_* `op` */
 #define GGRS_REDUCE_MAX_BINDINGS 8
 int ggrs_hip_add_custom_system_reduces(ggrs_world* w, const ggrs_custom_system_desc* desc,
@@ -486,6 +487,56 @@ int ggrs_hip_add_custom_system_remote(ggrs_world* w, const ggrs_custom_system_de
                                       const ggrs_resource_binding* res, uint32_t n_res,
                                       const ggrs_reduce_binding* red, uint32_t n_red,
                                       const ggrs_remote_binding* rem, uint32_t n_rem);
+
+/* DETERMINISTIC FLOAT SUMS INTO A DEVICE RESOURCE (SUM BINDINGS): the centre of mass of a flock, the camera target as the mean of the players, total kinetic energy --
+ *
+ *     fn tally(mut c: ResMut<Centre>, q: Query<&Pos, With<Rollback>>) { for p in &q { c.sx += p.x; c.sy += p.y; } }
+ *
+ * A float add is not associative, so a reduce binding (above) cannot carry it: an atomic per wave gives bits that depend on which wave arrives first.  A sum binding
+ * fixes the ORDER instead: the result is a function of the slots alone.
+ *
+ *   ggrs_hip_add_custom_system_sums   ggrs_hip_add_custom_system_remote plus SUM BINDINGS: sum[j] = {res, word} names one 4-byte (float) or 8-byte (double) word of
+ *                                  a registered device resource.  With n_sum == 0 the call behaves exactly as ggrs_hip_add_custom_system_remote.  At most
+ *                                  GGRS_SUM_MAX_BINDINGS per system and GGRS_SUM_MAX_WORDS distinct summed words per world.
+ *   inside ggrs_system             e.sum_f32(j, v) adds v into sum binding j, a 4-byte word; e.sum_f64(j, v) into an 8-byte word.  They return nothing: a summer
+ *                                  cannot read the running value.  An accessor of the other width, or of a binding the system lacks, does nothing, as e.reduce_*.
+ *                                  Any number of calls, also under a condition, also in the call that despawns its entity.
+ *
+ * THE CONTRACT, for one summed word and one simulated frame.
+ *   PER SLOT.  Slot s has a value a_s of the word's type (float / double).  a_s starts at -0.0, the exact identity of IEEE addition: x + (-0.0) is x bit for bit for
+ *   every non-NaN x, +0.0 included.  Every e.sum_*(j, v) executed for the entity at slot s does a_s = a_s + v: calls in program order within a system, systems in
+ *   registration order.  A slot for which no bound system runs keeps -0.0: dead, beyond len, lacking a bound component, or spawned in this frame.
+ *   FRAME TOTAL.  T is the root of the BALANCED BINARY TREE OVER SLOT INDICES: level 0 is a_0 .. a_{P-1} with P any power of two >= the number of slots, padded
+ *   with -0.0; level k+1 is x[2i] + x[2i+1].  Because -0.0 is an exact identity and IEEE add is commutative bit for bit for non-NaN operands, T does not depend on P,
+ *   on the grid size or how many 64-slot units a launch covers, on which copy of the kernel runs (generic / steady / specialised), or on the side of an add on which
+ *   an operand sits.
+ *   AT THE END OF THE FRAME the word becomes w + T, ONE add, where w is the value the frame's resource systems left: after the frame's systems and spawns, before
+ *   anything observes the frame (a SaveWorld, its checksum part, ggrs_hip_resource_read, the next frame, the next group) -- the point reduce bindings use.  A frame
+ *   in which nobody sums gives T = -0.0 and leaves the word's bits alone.
+ *   NaN AND THE ARITHMETIC MODE.  A NaN operand gives a NaN result whose payload is unspecified.  +-Inf follow IEEE.  Subnormals are kept: neither the library's
+ *   build nor its run-time compile flushes them, and neither allows fast-math or contraction (a user's a * b does not fuse into the add).
+ * Seal (sums_validate), each refusal GGRS_E_INVALID with a message naming the system and the resource: an unknown resource or word; a word that is neither 4 nor
+ * 8 bytes; a word with both a sum binding and a reduce binding; a system registered AT OR AFTER a word's first summer that reads or writes the word (an e.res_*
+ * binding, a resource system binding it) -- a resource system registered BEFORE the summer may reset the word (r.f32(k) = 0.f: "sum per frame"), an entity system
+ * registered before it reads last frame's result; more than GGRS_SUM_MAX_WORDS summed words; and everything device resources and reduce bindings refuse: worlds
+ * without the generated kernel, device-decided spawns, RollbackDespawned worlds, GGRS_BRANCH_RETAIN_*, ggrs_hip_fanout_step_branches (ggrs_hip_fanout_step works).
+ * Peers, effects, commands, remote bindings, read bindings and reduce bindings on OTHER words are allowed in the same world and the same system.
+ * How it runs: one per-lane accumulator register per summed word, -0.0 at launch start; e.sum_* is one register add, no memory and no atomic; at the end of the
+ * launch a DPP ladder of float adds -- which IS the balanced tree over the wave's 64 slots -- leaves the wave's value, stored with ONE plain vector store into a
+ * per-unit partial array (unit = first slot / 64); k_apply_sums, one small launch right behind the group's, folds the partials of the units that launch covered by
+ * the same tree and stores cell + T into the live block's current resource cell.  Such a world runs one AdvanceWorld per launch, as one with reduce bindings does.
+ * Out of scope: float min / max, float effects on other entities, a summer that reads the running value, branch steps and retention. */
+typedef struct { uint32_t res; uint32_t word; } ggrs_sum_binding;   /* sum binding j = word `word` of resource `res`: a float (4-byte word) or a double (8-byte word) */
+#define GGRS_SUM_MAX_BINDINGS 4
+#define GGRS_SUM_MAX_WORDS    8
+int ggrs_hip_add_custom_system_sums(ggrs_world* w, const ggrs_custom_system_desc* desc,
+                                    const ggrs_peer_binding* peers, uint32_t n_peers,
+                                    const ggrs_effect_binding* effects, uint32_t n_effects,
+                                    const ggrs_command_binding* cmds, uint32_t n_cmds,
+                                    const ggrs_resource_binding* res, uint32_t n_res,
+                                    const ggrs_reduce_binding* red, uint32_t n_red,
+                                    const ggrs_remote_binding* rem, uint32_t n_rem,
+                                    const ggrs_sum_binding* sum, uint32_t n_sum);
 
 /* ComponentSnapshotPlugin<S: Strategy> (snapshot/strategy.rs:22-40, component_snapshot.rs:42-63): what a snapshot HOLDS of a component is
  * S::Stored, produced by S::store and turned back by S::load / S::update -- CopyStrategy / CloneStrategy (Stored == the component, bitwise for
@@ -850,7 +901,7 @@ int ggrs_hip_host_timeline(ggrs_world* w, int enable, double* us_out, uint64_t* 
  * Introspection: which kernel serves this world's request lists right now and why, what kind of arena
  * it lives on, whether the run-time compiler (libhiprtc.so, dlopen'ed) is available.  `key=value` lines,
  * NUL-terminated; *needed = bytes incl. the NUL, min(cap, *needed) are copied.  Keys: sealed, arena,
- * arena_bytes, hiprtc, generated_kernel, generated_kernel_origin, request_group_kernel, checksum_fold, kernarg_bytes, group_caps, specialised_kernel, slots_covered, row_versions, peer_view (worlds with peer bindings), effect_inbox (worlds with effect bindings), device_resources (worlds with device resources), depth_parallel_roles, reduce_inbox (worlds with reduce bindings: stripes, words, applies so far), remote_inbox (worlds with remote bindings: components, applies so far).
+ * arena_bytes, hiprtc, generated_kernel, generated_kernel_origin, request_group_kernel, checksum_fold, kernarg_bytes, group_caps, specialised_kernel, slots_covered, row_versions, peer_view (worlds with peer bindings), effect_inbox (worlds with effect bindings), device_resources (worlds with device resources), depth_parallel_roles, reduce_inbox (worlds with reduce bindings: stripes, words, applies so far), remote_inbox (worlds with remote bindings: components, applies so far), sum_partials (worlds with sum bindings: units, words, applies so far).
  * ------------------------------------------------------------------------------------------- */
 int ggrs_hip_world_kernel_info(ggrs_world* w, char* buf, uint64_t cap, uint64_t* needed);
 

@@ -143,6 +143,17 @@ pub struct ggrs_reduce_binding {
 }
 pub const GGRS_REDUCE_MAX_BINDINGS: usize = 8;
 
+/// One sum binding of `ggrs_hip_add_custom_system_sums`: a float (4-byte) or double (8-byte) word of a device-resident rollback resource an entity system adds into
+/// through `e.sum_f32(j, v)` / `e.sum_f64(j, v)`; the frame's total is the balanced binary tree over slot indices and lands at the end of the frame.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct ggrs_sum_binding {
+    pub res: u32,
+    pub word: u32,
+}
+pub const GGRS_SUM_MAX_BINDINGS: usize = 4;
+pub const GGRS_SUM_MAX_WORDS: usize = 8;
+
 /// One remote binding of `ggrs_hip_add_custom_system_remote`: a component of OTHER entities an entity system may insert (`e.send_insert(slot, j)`, the registered
 /// default) or remove (`e.send_remove(slot, j)`); `comp == GGRS_REMOTE_ENTITY` with `GGRS_REMOTE_DESPAWN` is `e.send_despawn(slot)`.  Every command of a frame
 /// lands at the end of the frame: despawn wins over everything, remove wins over insert.
@@ -279,6 +290,7 @@ unsafe extern "C" {
     pub fn ggrs_hip_add_custom_system_resources(w: *mut ggrs_world, desc: *const ggrs_custom_system_desc, peers: *const ggrs_peer_binding, n_peers: u32, effects: *const ggrs_effect_binding, n_effects: u32, cmds: *const ggrs_command_binding, n_cmds: u32, res: *const ggrs_resource_binding, n_res: u32) -> c_int;
     pub fn ggrs_hip_add_custom_system_reduces(w: *mut ggrs_world, desc: *const ggrs_custom_system_desc, peers: *const ggrs_peer_binding, n_peers: u32, effects: *const ggrs_effect_binding, n_effects: u32, cmds: *const ggrs_command_binding, n_cmds: u32, res: *const ggrs_resource_binding, n_res: u32, red: *const ggrs_reduce_binding, n_red: u32) -> c_int;
     pub fn ggrs_hip_add_custom_system_remote(w: *mut ggrs_world, desc: *const ggrs_custom_system_desc, peers: *const ggrs_peer_binding, n_peers: u32, effects: *const ggrs_effect_binding, n_effects: u32, cmds: *const ggrs_command_binding, n_cmds: u32, res: *const ggrs_resource_binding, n_res: u32, red: *const ggrs_reduce_binding, n_red: u32, rem: *const ggrs_remote_binding, n_rem: u32) -> c_int;
+    pub fn ggrs_hip_add_custom_system_sums(w: *mut ggrs_world, desc: *const ggrs_custom_system_desc, peers: *const ggrs_peer_binding, n_peers: u32, effects: *const ggrs_effect_binding, n_effects: u32, cmds: *const ggrs_command_binding, n_cmds: u32, res: *const ggrs_resource_binding, n_res: u32, red: *const ggrs_reduce_binding, n_red: u32, rem: *const ggrs_remote_binding, n_rem: u32, sum: *const ggrs_sum_binding, n_sum: u32) -> c_int;
     pub fn ggrs_hip_register_resource(w: *mut ggrs_world, name: *const c_char, word_bytes: u32, n_words: u32, init_words: *const c_void, res_id_out: *mut u32) -> c_int;
     pub fn ggrs_hip_checksum_resource(w: *mut ggrs_world, res_id: u32, word_idx: *const u32, n_words: u32) -> c_int;
     pub fn ggrs_hip_add_resource_system(w: *mut ggrs_world, desc: *const ggrs_resource_system_desc) -> c_int;
