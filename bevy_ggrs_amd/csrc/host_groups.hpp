@@ -825,11 +825,10 @@ inline void attach_effects(ggrs_world* w, GgrsJitArgs& j) {
     for (uint32_t k = 0; k < w->fx_inbox.n_cols; ++k) j.fx_col[k] = w->fx_inbox.d_col[k];
     j.fx_len = j.len;                                                  // the source block's len == RollbackOrdered::len at the start of the group's one AdvanceWorld
 }
-int apply_effects(ggrs_world* w) {
+// (the argument block of k_apply_effects for the live block as it stands; returns the bytes the launch moves at least)
+uint64_t fx_apply_args(ggrs_world* w, uint64_t len, FxApplyArgs& a) {
     ggrs_world::EffectInbox& fx = w->fx_inbox;
-    const uint64_t len = w->len;                                       // the end-of-frame len (host-decided spawns only: the host knows it)
-    if (!len) return GGRS_OK;
-    FxApplyArgs a; memset(&a, 0, sizeof a);
+    memset(&a, 0, sizeof a);
     a.live = w->live.ptr; a.len = len; a.off_alive = w->off_alive; a.n_cols = fx.n_cols; a.n_units = (uint32_t)((len + 63) / 64);
     uint64_t bytes_slot = 0;
     for (uint32_t k = 0; k < fx.n_cols; ++k) {
@@ -838,23 +837,27 @@ int apply_effects(ggrs_world* w) {
         a.ident[k] = fx_identity(fx.op[k], w->col_wb[cl]); a.inbox[k] = fx.d_col[k];
         bytes_slot += w->col_wb[cl];                                   // the inbox word is always read; the live word and the identity move only where something was sent
     }
+    return bytes_slot * len;
+}
+int apply_effects(ggrs_world* w) {
+    const uint64_t len = w->len;                                       // the end-of-frame len (host-decided spawns only: the host knows it)
+    if (!len) return GGRS_OK;
+    FxApplyArgs a;
+    const uint64_t bytes = fx_apply_args(w, len, a);
     const double t0 = w->tl.on ? tl_now_us() : 0;
-    { ProfScope ps(w, GGRS_KERNEL_ADVANCE, bytes_slot * len); hipLaunchKernelGGL(k_apply_effects, dim3((a.n_units + TPB / 64 - 1) / (TPB / 64)), dim3(TPB), 0, w->stream, a); }
+    { ProfScope ps(w, GGRS_KERNEL_ADVANCE, bytes); hipLaunchKernelGGL(k_apply_effects, dim3((a.n_units + TPB / 64 - 1) / (TPB / 64)), dim3(TPB), 0, w->stream, a); }
     HIPCHK(w, hipGetLastError());
     if (w->tl.on) { w->tl.launch_us += tl_now_us() - t0; ++w->tl.n_launches; }
     w->spin_n = 0; w->batch_ev_attached = false;                       // this launch comes after whatever carried the batch event, and after a finalize that was the list's last GPU operation
-    ++fx.applies;
+    ++w->fx_inbox.applies;
     return GGRS_OK;
 }
 // Remote bindings: the commands the group's launch ORed into the inbox are applied to the live block's alive word, presence words and columns -- and the inbox zeroed
 // -- by a launch of its own right BEHIND the group's and AHEAD of apply_effects (effects then see the alive and presence bits the commands left), enqueued with the
 // group (never lazily): no host entry point ever sees a pending inbox.  The kernel boundary is the only synchronisation.
-int apply_remote(ggrs_world* w) {
+void rx_apply_args(ggrs_world* w, uint64_t len, RxApplyArgs& a) {
     ggrs_world::RemoteInbox& rx = w->rx_inbox;
-    ++rx.applies;
-    const uint64_t len = w->len;                                       // the end-of-frame len (host-decided spawns only: the host knows it)
-    if (!len) return GGRS_OK;
-    RxApplyArgs a; memset(&a, 0, sizeof a);
+    memset(&a, 0, sizeof a);
     a.live = w->live.ptr; a.inbox = rx.d; a.len = len; a.off_alive = w->off_alive; a.n_comps = rx.n_comps; a.n_units = (uint32_t)((len + 63) / 64);
     uint32_t nw = 0;
     for (uint32_t k = 0; k < rx.n_comps; ++k) {
@@ -866,11 +869,35 @@ int apply_remote(ggrs_world* w) {
             if (T.defaults.size() >= (size_t)(q + 1) * T.word_bytes) memcpy(&a.dflt[nw], &T.defaults[(size_t)q * T.word_bytes], T.word_bytes);      // (little-endian: the low bytes; else zeros)
         }
     }
+}
+int apply_remote(ggrs_world* w) {
+    ++w->rx_inbox.applies;
+    const uint64_t len = w->len;                                       // the end-of-frame len (host-decided spawns only: the host knows it)
+    if (!len) return GGRS_OK;
+    RxApplyArgs a;
+    rx_apply_args(w, len, a);
     const double t0 = w->tl.on ? tl_now_us() : 0;
     { ProfScope ps(w, GGRS_KERNEL_ADVANCE, 4ull * len); hipLaunchKernelGGL(k_apply_remote, dim3((a.n_units + TPB / 64 - 1) / (TPB / 64)), dim3(TPB), 0, w->stream, a); }
     HIPCHK(w, hipGetLastError());
     if (w->tl.on) { w->tl.launch_us += tl_now_us() - t0; ++w->tl.n_launches; }
     w->spin_n = 0; w->batch_ev_attached = false;                       // this launch comes after whatever carried the batch event, and after a finalize that was the list's last GPU operation
+    return GGRS_OK;
+}
+// A world with BOTH kinds: one launch, the remote half of every unit ahead of its effect half (kernels.hpp k_apply_remote_effects) -- the same order, one launch fewer
+// per frame.  Both applies count.
+int apply_remote_effects(ggrs_world* w) {
+    ++w->rx_inbox.applies;
+    const uint64_t len = w->len;                                       // the end-of-frame len (host-decided spawns only: the host knows it)
+    if (!len) return GGRS_OK;
+    RxApplyArgs r; FxApplyArgs f;
+    rx_apply_args(w, len, r);
+    const uint64_t bytes = 4ull * len + fx_apply_args(w, len, f);
+    const double t0 = w->tl.on ? tl_now_us() : 0;
+    { ProfScope ps(w, GGRS_KERNEL_ADVANCE, bytes); hipLaunchKernelGGL(k_apply_remote_effects, dim3((r.n_units + TPB / 64 - 1) / (TPB / 64)), dim3(TPB), 0, w->stream, r, f); }
+    HIPCHK(w, hipGetLastError());
+    if (w->tl.on) { w->tl.launch_us += tl_now_us() - t0; ++w->tl.n_launches; }
+    w->spin_n = 0; w->batch_ev_attached = false;                       // this launch comes after whatever carried the batch event, and after a finalize that was the list's last GPU operation
+    ++w->fx_inbox.applies;
     return GGRS_OK;
 }
 // Reduce bindings: what the waves of the group's launch left in the striped inbox is folded into the live block's CURRENT resource cell -- the one that launch just
@@ -983,8 +1010,11 @@ int run_request_groups_gen(ggrs_world* w, const ggrs_request* reqs, uint32_t n, 
             }
             group_close(w, gs, j.n_saves, dead, wrote_live);
             rc = fold_route_record(w, j, fold, g, n_cks, res_base + ns, wait); if (rc) return rc;
-            if (remotes) { rc = apply_remote(w); if (rc) return rc; }     // ahead of the effects: they apply to the alive and presence bits the remote commands left
-            if (applies) { rc = apply_effects(w); if (rc) return rc; }
+            if (remotes && applies) { rc = apply_remote_effects(w); if (rc) return rc; }      // one launch, unit by unit in the order of the two below
+            else {
+                if (remotes) { rc = apply_remote(w); if (rc) return rc; } // ahead of the effects: they apply to the alive and presence bits the remote commands left
+                if (applies) { rc = apply_effects(w); if (rc) return rc; }
+            }
             if (reduces) { rc = apply_reduces(w); if (rc) return rc; }
             if (sums) { rc = apply_sums(w, j.n_units); if (rc) return rc; }
         }

@@ -672,10 +672,8 @@ template <typename U, typename I> __device__ __forceinline__ U fx_combine(uint32
     default: return x;
     }
 }
-__global__ __launch_bounds__(TPB) void k_apply_effects(FxApplyArgs a) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t u = blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);             // this wave's 64-slot unit == its mask word
-    if (u >= a.n_units) return;
+// one unit of k_apply_effects.  alive_known: the caller holds the unit's alive word in a register (k_apply_remote_effects: what its remote half just decided)
+__device__ __forceinline__ void fx_apply_unit(const FxApplyArgs& a, uint32_t u, uint32_t lane, bool alive_known, uint64_t alive_w) {
     const uint64_t e = (uint64_t)u * 64u + lane;
     if (e >= a.len) return;                                                      // (a send never goes beyond the start-of-frame len, which the end-of-frame len is not below)
     for (uint32_t c = 0; c < a.n_cols; ++c) {
@@ -683,18 +681,24 @@ __global__ __launch_bounds__(TPB) void k_apply_effects(FxApplyArgs a) {
             uint64_t* in = reinterpret_cast<uint64_t*>(a.inbox[c]) + e;
             const uint64_t v = *in;
             if (v == a.ident[c]) continue;
-            const uint64_t on = *reinterpret_cast<const uint64_t*>(a.live + a.off_alive + (uint64_t)u * 8u) & *reinterpret_cast<const uint64_t*>(a.live + a.off_present[c] + (uint64_t)u * 8u);
+            const uint64_t on = (alive_known ? alive_w : *reinterpret_cast<const uint64_t*>(a.live + a.off_alive + (uint64_t)u * 8u)) & *reinterpret_cast<const uint64_t*>(a.live + a.off_present[c] + (uint64_t)u * 8u);
             if ((on >> lane) & 1ull) { uint64_t* p = reinterpret_cast<uint64_t*>(a.live + col_at(a.col_off[c], a.ts[c], 8, e)); *p = fx_combine<uint64_t, int64_t>(a.op[c], *p, v); }
             *in = a.ident[c];
         } else {
             uint32_t* in = reinterpret_cast<uint32_t*>(a.inbox[c]) + e;
             const uint32_t v = *in;
             if (v == (uint32_t)a.ident[c]) continue;
-            const uint64_t on = *reinterpret_cast<const uint64_t*>(a.live + a.off_alive + (uint64_t)u * 8u) & *reinterpret_cast<const uint64_t*>(a.live + a.off_present[c] + (uint64_t)u * 8u);
+            const uint64_t on = (alive_known ? alive_w : *reinterpret_cast<const uint64_t*>(a.live + a.off_alive + (uint64_t)u * 8u)) & *reinterpret_cast<const uint64_t*>(a.live + a.off_present[c] + (uint64_t)u * 8u);
             if ((on >> lane) & 1ull) { uint32_t* p = reinterpret_cast<uint32_t*>(a.live + col_at(a.col_off[c], a.ts[c], 4, e)); *p = fx_combine<uint32_t, int32_t>(a.op[c], *p, v); }
             *in = (uint32_t)a.ident[c];
         }
     }
+}
+__global__ __launch_bounds__(TPB) void k_apply_effects(FxApplyArgs a) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t u = blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);             // this wave's 64-slot unit == its mask word
+    if (u >= a.n_units) return;
+    fx_apply_unit(a, u, lane, false, 0ull);
 }
 
 // THE REMOTE INBOX (ggrs_hip_add_custom_system_remote; host_world.hpp ggrs_world::RemoteInbox).  Right behind every request group that holds an AdvanceWorld and AHEAD of
@@ -713,19 +717,18 @@ struct RxApplyArgs {
     uint32_t w_base[RX_MAX_COMPS], n_words[RX_MAX_COMPS], wb[RX_MAX_COMPS], ts[RX_MAX_COMPS];
     uint32_t n_comps, n_units;
 };
-__global__ __launch_bounds__(TPB) void k_apply_remote(RxApplyArgs a) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t u = blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);             // this wave's 64-slot unit == its mask word (wave-uniform)
-    if (u >= a.n_units) return;
+// one unit of k_apply_remote, by all 64 lanes of its wave.  Returns whether the unit held a command; then alive_out is the unit's alive word as it stands now
+__device__ __forceinline__ bool rx_apply_unit(const RxApplyArgs& a, uint32_t u, uint32_t lane, uint64_t& alive_out) {
     const uint64_t e = (uint64_t)u * 64u + lane;
     const bool inside = e < a.len;                                               // (a send never goes beyond the start-of-frame len, which the end-of-frame len is not below)
     const uint32_t m = inside ? a.inbox[e] : 0u;
-    if (!__ballot(m != 0u)) return;                                              // nothing was sent into this unit: nothing else is touched
+    if (!__ballot(m != 0u)) return false;                                        // nothing was sent into this unit: nothing else is touched
     uint64_t* const alive_p = reinterpret_cast<uint64_t*>(a.live + a.off_alive + (uint64_t)u * 8u);
     const uint64_t alive_w = *alive_p;
     const bool alive = (alive_w >> lane) & 1ull;                                 // alive once the frame's own despawns are in: else every command is dropped
     const bool on = alive && !(m & 1u);                                          // despawn wins over everything
     const uint64_t alive_n = __ballot(on);
+    alive_out = alive_n;
     if (lane == 0 && alive_n != alive_w) *alive_p = alive_n;
     for (uint32_t k = 0; k < a.n_comps; ++k) {
         const bool ins = (m >> (1u + 2u * k)) & 1u, rem = (m >> (2u + 2u * k)) & 1u;
@@ -748,6 +751,26 @@ __global__ __launch_bounds__(TPB) void k_apply_remote(RxApplyArgs a) {
         }
     }
     if (m) a.inbox[e] = 0u;
+    return true;
+}
+__global__ __launch_bounds__(TPB) void k_apply_remote(RxApplyArgs a) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t u = blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);             // this wave's 64-slot unit == its mask word (wave-uniform)
+    if (u >= a.n_units) return;
+    uint64_t alive_w;
+    (void)rx_apply_unit(a, u, lane, alive_w);
+}
+// A world with BOTH remote and effect bindings: k_apply_remote and k_apply_effects walk the same units of the same block, one wave per unit, and an effect looks at
+// nothing of another unit -- so one launch does both, the remote half first.  The effects apply to the alive bits the remote commands left: where the unit held a
+// command the wave carries its new alive word over in a register (lane 0's store of it is not read back), elsewhere the word in memory is unchanged.  The presence
+// words and columns the remote half writes are never an effect column's (a component under both kinds of binding is refused at seal).
+__global__ __launch_bounds__(TPB) void k_apply_remote_effects(RxApplyArgs r, FxApplyArgs f) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t u = blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);             // (wave-uniform; both halves cover the units below the end-of-frame len)
+    if (u >= r.n_units) return;
+    uint64_t alive_w = 0;
+    const bool known = rx_apply_unit(r, u, lane, alive_w);
+    fx_apply_unit(f, u, lane, known, alive_w);
 }
 
 // THE REDUCE INBOX (ggrs_hip_add_custom_system_reduces; host_world.hpp ggrs_world::ReduceInbox).  Right behind every request group that holds an AdvanceWorld: ONE

@@ -472,7 +472,8 @@ int ggrs_hip_add_custom_system_reduces(ggrs_world* w, const ggrs_custom_system_d
  *     ggrs_hip_fanout_step_branches (ggrs_hip_fanout_step works).
  * How it runs: one inbox word per slot (bit 0 despawn, bits 1 + 2k / 2 + 2k insert / remove of the world's k-th remotely commanded component), each send one
  * no-return atomic OR; k_apply_remote, one small launch right behind the group's and ahead of the effects', rebuilds the touched mask words with ballots, writes the
- * defaults and zeroes the inbox.  Such a world runs one AdvanceWorld per launch, as a world with effect bindings does. */
+ * defaults and zeroes the inbox (a world that also has effect bindings applies both in ONE launch, every 64-slot unit's remote half ahead of its effect half:
+ * the same order).  Such a world runs one AdvanceWorld per launch, as a world with effect bindings does. */
 typedef struct { uint32_t comp; uint32_t flags; } ggrs_remote_binding;   /* remote binding j = component `comp` (GGRS_REMOTE_ENTITY with GGRS_REMOTE_DESPAWN) and GGRS_REMOTE_* flags */
 #define GGRS_REMOTE_INSERT  1u   /* the system may call e.send_insert(slot, j) */
 #define GGRS_REMOTE_REMOVE  2u   /* the system may call e.send_remove(slot, j) */

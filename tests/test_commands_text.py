@@ -18,6 +18,7 @@ from commands_common import BOTH, STUN_SRC, build_shield, build_stun, build_watc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OPTS = [b"--offload-arch=gfx950", b"-O3", b"-std=c++17", b"-ffp-contract=off", b"-fno-fast-math", b"-fhip-fp32-correctly-rounded-divide-sqrt"]
+NEW_IDENTIFIERS = ("opt_u32", "has_")      # what a world without command bindings does not name
 NOP = "__device__ void ggrs_system(GgrsEntity& e, const GgrsFrame&) { e.u32(0) += 1u; }"
 OPT = "__device__ void ggrs_system(GgrsEntity& e, const GgrsFrame&) { if (e.has(0)) e.opt_u32(0, 0) += 1u; }"
 INS = "__device__ void ggrs_system(GgrsEntity& e, const GgrsFrame&) { if (!e.has(0)) { e.opt_u32(0, 0) = e.u32(0); e.insert(0); } }"
@@ -243,7 +244,8 @@ def test_worlds_without_command_bindings_keep_their_text():
     for build in (build_strike, build_follow):
         w = layout_world(); build(w)
         src = w.generated_kernel_source()
-        assert "struct GgrsEntity {" in src and "GgrsEntityC" not in src and "opt_u32" not in src and "has_" not in src and "ggrs_sys_0::GgrsEntity" not in src
+        assert "struct GgrsEntity {" in src and "GgrsEntityC" not in src and "ggrs_sys_0::GgrsEntity" not in src
+        for ident in NEW_IDENTIFIERS: assert ident not in src, ident
     assert getattr(w._lib, "ggrs_hip_add_custom_system_commands")          # (on the parent the symbol is missing: this test fails there too)
 
 
