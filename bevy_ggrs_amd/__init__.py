@@ -11,6 +11,7 @@ from ._ffi import (COMP_NO_ROLLBACK, COMP_ROLLBACK, DESPAWN_IMMEDIATE, DESPAWN_R
                    EFFECT_ADD, EFFECT_MIN_U, EFFECT_MAX_U, EFFECT_MIN_I, EFFECT_MAX_I, EFFECT_OR, EFFECT_AND, EFFECT_XOR, CMD_INSERT, CMD_REMOVE,
                    SYS_RESOURCE, RESOURCE_MAX, RESOURCE_MAX_BYTES, RESOURCE_MAX_BINDINGS, REDUCE_MAX_BINDINGS,
                    REMOTE_INSERT, REMOTE_REMOVE, REMOTE_DESPAWN, REMOTE_ENTITY, REMOTE_MAX_BINDINGS, REMOTE_MAX_COMPONENTS,
-                   SUM_MAX_BINDINGS, SUM_MAX_WORDS)
+                   SUM_MAX_BINDINGS, SUM_MAX_WORDS,
+                   VALUE_MAX_BINDINGS, VALUE_MAX_WORDS, VALUE_MAX_WORLD_BINDINGS)
 from .requests import AdvanceFrame, LoadGameState, SaveGameState  # noqa: F401
 from .world import World  # noqa: F401

@@ -123,6 +123,13 @@ class SumBinding(C.Structure):
     _fields_ = [("res", C.c_uint32), ("word", C.c_uint32)]
 
 
+VALUE_MAX_BINDINGS, VALUE_MAX_WORDS, VALUE_MAX_WORLD_BINDINGS = 4, 8, 16
+
+
+class ValueBinding(C.Structure):
+    _fields_ = [("comp", C.c_uint32), ("flags", C.c_uint32)]
+
+
 class ResourceSystemDesc(C.Structure):
     _fields_ = [("name", C.c_char_p), ("source", C.c_char_p), ("n_bindings", C.c_uint32),
                 ("res", C.c_uint32 * RESOURCE_MAX_BINDINGS), ("word", C.c_uint32 * RESOURCE_MAX_BINDINGS),
@@ -188,6 +195,9 @@ SIGNATURES = {
     "ggrs_hip_add_custom_system_sums": (C.c_int, [_P, C.POINTER(CustomSystemDesc), C.POINTER(PeerBinding), C.c_uint32, C.POINTER(EffectBinding), C.c_uint32,
                                                   C.POINTER(CommandBinding), C.c_uint32, C.POINTER(ResourceBinding), C.c_uint32, C.POINTER(ReduceBinding), C.c_uint32,
                                                   C.POINTER(RemoteBinding), C.c_uint32, C.POINTER(SumBinding), C.c_uint32]),
+    "ggrs_hip_add_custom_system_values": (C.c_int, [_P, C.POINTER(CustomSystemDesc), C.POINTER(PeerBinding), C.c_uint32, C.POINTER(EffectBinding), C.c_uint32,
+                                                    C.POINTER(CommandBinding), C.c_uint32, C.POINTER(ResourceBinding), C.c_uint32, C.POINTER(ReduceBinding), C.c_uint32,
+                                                    C.POINTER(RemoteBinding), C.c_uint32, C.POINTER(SumBinding), C.c_uint32, C.POINTER(ValueBinding), C.c_uint32]),
     "ggrs_hip_register_resource": (C.c_int, [_P, C.c_char_p, C.c_uint32, C.c_uint32, _P, C.POINTER(C.c_uint32)]),
     "ggrs_hip_checksum_resource": (C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32]),
     "ggrs_hip_add_resource_system": (C.c_int, [_P, C.POINTER(ResourceSystemDesc)]),

@@ -135,6 +135,7 @@ void ggrs_hip_world_destroy(ggrs_world* w) {
     rd_inbox_release(w);
     sum_part_release(w);
     rx_inbox_release(w);
+    rv_inbox_release(w);
     for (void* p : w->spec_allocs) (void)hipFree(p);
     if (w->h_results) (void)hipHostFree(w->h_results);
     if (w->h_stage) (void)hipHostFree(w->h_stage);
@@ -256,7 +257,16 @@ int ggrs_hip_add_custom_system_remote(ggrs_world* w, const ggrs_custom_system_de
 int ggrs_hip_add_custom_system_sums(ggrs_world* w, const ggrs_custom_system_desc* d, const ggrs_peer_binding* peers, uint32_t n_peers, const ggrs_effect_binding* effects, uint32_t n_effects,
                                     const ggrs_command_binding* cmds, uint32_t n_cmds, const ggrs_resource_binding* res, uint32_t n_res, const ggrs_reduce_binding* red, uint32_t n_red,
                                     const ggrs_remote_binding* rem, uint32_t n_rem, const ggrs_sum_binding* sum, uint32_t n_sum) {
+    return ggrs_hip_add_custom_system_values(w, d, peers, n_peers, effects, n_effects, cmds, n_cmds, res, n_res, red, n_red, rem, n_rem, sum, n_sum, nullptr, 0);
+}
+// ... and with value bindings: components of OTHER entities the system inserts with ITS OWN words through e.val_*(j, k) / e.send_value(slot, j), the last sender in
+// schedule order winning as one value, landing with the remote commands (include/ggrs_hip.h).  What a component must be is checked at seal (host_seal.hpp values_validate)
+int ggrs_hip_add_custom_system_values(ggrs_world* w, const ggrs_custom_system_desc* d, const ggrs_peer_binding* peers, uint32_t n_peers, const ggrs_effect_binding* effects, uint32_t n_effects,
+                                      const ggrs_command_binding* cmds, uint32_t n_cmds, const ggrs_resource_binding* res, uint32_t n_res, const ggrs_reduce_binding* red, uint32_t n_red,
+                                      const ggrs_remote_binding* rem, uint32_t n_rem, const ggrs_sum_binding* sum, uint32_t n_sum, const ggrs_value_binding* val, uint32_t n_val) {
     if (!w || !d || !d->source) return GGRS_E_INVALID;
+    if (n_val > GGRS_VALUE_MAX_BINDINGS) return w->fail(GGRS_E_INVALID, "custom system '%s': at most %d value bindings (GGRS_VALUE_MAX_BINDINGS), not %u", d->name ? d->name : "custom", GGRS_VALUE_MAX_BINDINGS, n_val);
+    if (n_val && !val) return w->fail(GGRS_E_INVALID, "custom system: n_val = %u but val is NULL", n_val);
     if (n_sum > GGRS_SUM_MAX_BINDINGS) return w->fail(GGRS_E_INVALID, "custom system '%s': at most %d sum bindings (GGRS_SUM_MAX_BINDINGS), not %u", d->name ? d->name : "custom", GGRS_SUM_MAX_BINDINGS, n_sum);
     if (n_sum && !sum) return w->fail(GGRS_E_INVALID, "custom system: n_sum = %u but sum is NULL", n_sum);
     if (n_rem > GGRS_REMOTE_MAX_BINDINGS) return w->fail(GGRS_E_INVALID, "custom system '%s': at most %d remote bindings (GGRS_REMOTE_MAX_BINDINGS), not %u", d->name ? d->name : "custom", GGRS_REMOTE_MAX_BINDINGS, n_rem);
@@ -333,6 +343,16 @@ int ggrs_hip_add_custom_system_sums(ggrs_world* w, const ggrs_custom_system_desc
     c.n_rem = n_rem;
     for (uint32_t j = 0; j < n_sum; ++j) { c.sres[j] = sum[j].res; c.sword[j] = sum[j].word; }
     c.n_sum = n_sum;
+    uint32_t val_words = 0;
+    for (uint32_t j = 0; j < n_val; ++j) {
+        if (val[j].comp >= w->comps.size()) return w->fail(GGRS_E_INVALID, "custom system '%s': value binding %u names component %u, which is not registered", c.name.c_str(), j, val[j].comp);
+        if (val[j].flags) return w->fail(GGRS_E_INVALID, "custom system '%s': value binding %u (component %u, '%s') has flags %x: a value binding's flags must be 0", c.name.c_str(), j, val[j].comp, w->comps[val[j].comp].name.c_str(), val[j].flags);
+        c.vcomp[j] = val[j].comp;
+        val_words += w->comps[val[j].comp].n_words;
+    }
+    if (val_words > GGRS_VALUE_MAX_WORDS)
+        return w->fail(GGRS_E_INVALID, "custom system '%s': its value bindings stage %u words together, at most %d (GGRS_VALUE_MAX_WORDS)", c.name.c_str(), val_words, GGRS_VALUE_MAX_WORDS);
+    c.n_val = n_val;
     DeviceGuard dg(w);
     c.source = d->source;
     c.may_defer = source_has_token(c.source, "despawn_rollback") || source_has_token(c.source, "kill");
@@ -476,7 +496,7 @@ int ggrs_hip_generated_kernel_source(ggrs_world* w, uint32_t form, char* buf, ui
     if (!w || (form != GGRS_KERNEL_FORM_TILES && form != GGRS_KERNEL_FORM_STEADY)) return GGRS_E_INVALID;
     if (!w->sealed) {
         if (!w->layout_only) { DeviceGuard dg(w); const int rc = seal(w); if (rc) return rc; }
-        else { build_layout(w); const int prc = peers_validate(w); if (prc) return prc; const int frc = effects_validate(w); if (frc) return frc; const int crc = commands_validate(w); if (crc) return crc; const int rrc = resources_validate(w); if (rrc) return rrc; const int drc = reduces_validate(w); if (drc) return drc; const int xrc = remote_validate(w); if (xrc) return xrc; const int src_ = sums_validate(w); if (src_) return src_; }   // host arithmetic only: offsets of every mask and column; the peer-, effect-, command-, resource, reduce, remote and sum rules
+        else { build_layout(w); const int prc = peers_validate(w); if (prc) return prc; const int frc = effects_validate(w); if (frc) return frc; const int crc = commands_validate(w); if (crc) return crc; const int rrc = resources_validate(w); if (rrc) return rrc; const int drc = reduces_validate(w); if (drc) return drc; const int xrc = remote_validate(w); if (xrc) return xrc; const int vrc = values_validate(w); if (vrc) return vrc; const int src_ = sums_validate(w); if (src_) return src_; }   // host arithmetic only: offsets of every mask and column; the peer-, effect-, command-, resource, reduce, remote, value and sum rules
     }
     std::string src;
     if (!jit_source(w, src)) return w->fail(GGRS_E_INVALID, "the kernel generator does not cover this world (a system writes a live-only component, or more than %u four-byte units / %u words per entity)", JIT_MAX_UNITS, JIT_MAX_COLS);
@@ -536,6 +556,19 @@ int64_t ggrs_dbg_sum_partials(ggrs_world* w, uint32_t word, void* out, uint64_t 
     DeviceGuard dg(w);
     const uint64_t bytes = (uint64_t)w->sum_part.units * 8u;
     if (hipMemcpyAsync(out, w->sum_part.d + (uint64_t)word * bytes, std::min(cap, bytes), hipMemcpyDeviceToHost, w->stream) != hipSuccess || hipStreamSynchronize(w->stream) != hipSuccess) return -1;
+    return (int64_t)bytes;
+}
+//   ggrs_dbg_value_winners     the winner words of value-bound component `comp` (one u64 per slot of the padded capacity) after everything queued on the world's stream
+//                              has run: returns how many bytes they have (min(cap, that) are copied), -1 for a world without value bindings or a component no value
+//                              binding names -- they must hold zeros whenever a host call returns
+int64_t ggrs_dbg_value_winners(ggrs_world* w, uint32_t comp, void* out, uint64_t cap) {
+    if (!w || !w->has_values || !w->rv_inbox.alloc) return -1;
+    const uint64_t* d = nullptr;
+    for (uint32_t k = 0; k < w->rx_inbox.n_comps; ++k) if (w->rx_inbox.comp[k] == comp) d = w->rv_inbox.d_win[k];
+    if (!d) return -1;
+    DeviceGuard dg(w);
+    const uint64_t bytes = w->cap_pad * 8u;
+    if (hipMemcpyAsync(out, d, std::min(cap, bytes), hipMemcpyDeviceToHost, w->stream) != hipSuccess || hipStreamSynchronize(w->stream) != hipSuccess) return -1;
     return (int64_t)bytes;
 }
 int ggrs_dbg_set_spec_shapes(ggrs_world* w, int n) { if (!w || n < 1 || n > 64) return -1; w->spec_shapes = n; return 0; }
@@ -1054,6 +1087,9 @@ int ggrs_hip_world_kernel_info(ggrs_world* w, char* buf, uint64_t cap, uint64_t*
                                                "applied to the live block's masks and columns right behind every request group that holds an AdvanceWorld and ahead of the effects (" + std::to_string(w->rx_inbox.applies) + " applies so far)");
         if (w->has_sums) add("sum_partials", std::to_string(w->sum_part.units) + " units of 64 slots, " + std::to_string(w->sum_part.n_words) + " summed words, one 8-byte partial per unit and word stored by the unit's wave, folded by the balanced tree "
                                              "into the live block's current resource cell right behind every request group that holds an AdvanceWorld (" + std::to_string(w->sum_part.applies) + " applies so far)");
+        if (w->has_values) add("value_inbox", std::to_string(w->rv_inbox.n_comps) + " value-bound components (one u64 winner word per slot each: the largest key (g + 1) << 40 | (sender slot + 1) of the frame, zeros whenever no group-and-apply pair is in flight), " +
+                                              std::to_string(w->rv_inbox.n_bind) + " value bindings (one payload array each: the senders' staged words at their own slots), " + std::to_string(w->rv_inbox.bytes) + " bytes allocated, applied with the remote inbox (" +
+                                              std::to_string(w->rx_inbox.applies) + " applies so far)");
         if (w->has_effects) add("effect_inbox", std::to_string(w->fx_inbox.n_cols) + " linear columns holding the ops' identities, applied to the live block right behind every request group that holds an AdvanceWorld (" +
                                                std::to_string(w->fx_inbox.applies) + " applies so far)");
         add("branch_marker_record_bytes", std::to_string(w->jit_marks ? jit_marks_rec_bytes(w) : 0));      // per retained branch of ggrs_hip_fanout_step_branches (0: the kernel keeps no markers)

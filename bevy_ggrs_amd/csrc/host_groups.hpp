@@ -253,6 +253,7 @@ int launch_jit(ggrs_world* w, hipFunction_t fn, uint32_t gx, uint32_t gy, uint32
     if (streamed) { j.sp_ticket_base = w->sp_ticket_base; w->sp_ticket_base += (uint64_t)(gx + j.ff_blocks) * gy * gz; }   // every workgroup takes one ticket
     j.skip_count = (w->prof && j.vtags) ? reinterpret_cast<ggrs_u64*>(w->d_skip) : nullptr;
     if (w->has_resources) { const int rrc = res_cells_for_launch(w, j); if (rrc) return rrc; }
+    if (w->has_values) { for (uint32_t k = 0; k < w->rx_inbox.n_comps; ++k) j.rv_win[k] = reinterpret_cast<ggrs_u64*>(w->rv_inbox.d_win[k]); for (uint32_t g = 0; g < w->rv_inbox.n_bind; ++g) j.rv_pay[g] = w->rv_inbox.d_pay[g]; }   // value bindings: the winner words and the payloads
     if (w->has_remote) { j.rx_inbox = w->rx_inbox.d; j.rx_len = j.len; }   // remote bindings: the inbox, and the source block's len == RollbackOrdered::len at the start of the group's one AdvanceWorld (in a world with effects the kernel reads fx_len, the same value)
     if (w->has_sums) {                                                 // sum bindings: every launch of the kernel stores one partial per word and unit it covers (only one that runs an AdvanceWorld is folded)
         if (((j.n_units + 3u) & ~3u) > w->sum_part.units) return w->fail(GGRS_E_INVALID, "sum bindings: the launch covers %u units, the partial arrays hold %u", j.n_units, w->sum_part.units);
@@ -863,11 +864,17 @@ void rx_apply_args(ggrs_world* w, uint64_t len, RxApplyArgs& a) {
     for (uint32_t k = 0; k < rx.n_comps; ++k) {
         const Comp& T = w->comps[rx.comp[k]];
         a.off_present[k] = w->off_present[rx.comp[k]]; a.w_base[k] = nw; a.wb[k] = T.word_bytes; a.ts[k] = w->col_ts[T.col_base];
-        a.n_words[k] = (rx.flags[k] & GGRS_REMOTE_INSERT) ? T.n_words : 0u;     // (a component that is only ever removed writes no word)
+        a.n_words[k] = (rx.flags[k] & (GGRS_REMOTE_INSERT | RX_FLAG_VALUE)) ? T.n_words : 0u;     // (a component that is only ever removed writes no word)
         for (uint32_t q = 0; q < a.n_words[k] && nw < (uint32_t)RX_MAX_WORDS; ++q, ++nw) {
             a.col_off[nw] = w->col_off[T.col_base + q];
             if (T.defaults.size() >= (size_t)(q + 1) * T.word_bytes) memcpy(&a.dflt[nw], &T.defaults[(size_t)q * T.word_bytes], T.word_bytes);      // (little-endian: the low bytes; else zeros)
         }
+    }
+    if (w->has_values) {                                               // value bindings: the winner words and payloads the group's launch wrote
+        const ggrs_world::ValueInbox& rv = w->rv_inbox;
+        for (uint32_t k = 0; k < rx.n_comps; ++k) a.win[k] = rv.d_win[k];
+        for (uint32_t g = 0; g < rv.n_bind; ++g) a.pay[g] = rv.d_pay[g];
+        a.n_pay = rv.n_bind; a.pay_stride = w->cap_pad;
     }
 }
 int apply_remote(ggrs_world* w) {
@@ -1086,6 +1093,7 @@ int branch_marks_reserve(ggrs_world* w, uint64_t n) {
 int validate_branch_step(ggrs_world* w, const ggrs_branch_step& st) {
     if (!w->gen_ok) return w->fail(GGRS_E_INVALID, "branch steps need the generated request-group kernel, which this world does not have: %s", w->jit_status.c_str());
     if (w->has_peers) return w->fail(GGRS_E_INVALID, "branch steps are not available for worlds with peer bindings (a member runs several frames per launch, a peer read sees the start of ONE frame): use ggrs_hip_fanout_step");
+    if (w->has_values) return w->fail(GGRS_E_INVALID, "branch steps (ggrs_hip_fanout_step_branches) are not available for worlds with value bindings (ggrs_hip_add_custom_system_values: a member runs several frames per launch, the values of ONE frame are applied behind a launch): use ggrs_hip_fanout_step");
     if (w->has_remote) return w->fail(GGRS_E_INVALID, "branch steps (ggrs_hip_fanout_step_branches) are not available for worlds with remote bindings (ggrs_hip_add_custom_system_remote: a member runs several frames per launch, the remote commands of ONE frame are applied behind a launch): use ggrs_hip_fanout_step");
     if (w->has_sums) return w->fail(GGRS_E_INVALID, "branch steps (ggrs_hip_fanout_step_branches) are not available for worlds with sum bindings (ggrs_hip_add_custom_system_sums: a member runs several frames per launch, the float sums of ONE frame are folded behind a launch): use ggrs_hip_fanout_step");
     if (w->has_reduces) return w->fail(GGRS_E_INVALID, "branch steps (ggrs_hip_fanout_step_branches) are not available for worlds with reduce bindings (ggrs_hip_add_custom_system_reduces: a member runs several frames per launch, the reductions of ONE frame are applied behind a launch): use ggrs_hip_fanout_step");

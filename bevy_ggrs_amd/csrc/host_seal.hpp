@@ -261,21 +261,24 @@ int remote_validate(ggrs_world* w) {
         if (w->systems[i].kind != GGRS_SYS_CUSTOM) continue;
         const ggrs_world::Custom& c = w->customs[w->systems[i].comp[0]];
         const char* nm = c.name.c_str();
-        if (despawner >= 0 && (c.n_peer || c.n_fx || c.n_red || c.n_rem)) {
+        if (despawner >= 0 && (c.n_peer || c.n_fx || c.n_red || c.n_rem || c.n_val)) {
             const ggrs_world::Custom& dc = w->customs[w->systems[(size_t)despawner].comp[0]];
-            const char* what = c.n_peer ? "peer" : (c.n_fx ? "effect" : (c.n_red ? "reduce" : "remote"));
+            const char* what = c.n_peer ? "peer" : (c.n_fx ? "effect" : (c.n_red ? "reduce" : (c.n_rem ? "remote" : "value")));
             return w->fail(GGRS_E_INVALID, "custom system '%s' (system %zu) has %s bindings and is registered after custom system '%s' (system %ld), which can despawn other entities (GGRS_REMOTE_DESPAWN on GGRS_REMOTE_ENTITY): "
                                            "no system registered after a remote despawner has peer, effect, reduce or remote bindings -- in Bevy it would not run for the despawned entity", nm, i, what, dc.name.c_str(), despawner);
         }
-        for (uint32_t j = 0; j < c.n_rem; ++j) {
-            if (c.xflags[j] & GGRS_REMOTE_DESPAWN) { if (despawner < 0) despawner = (long)i; continue; }
-            const uint32_t cc = c.xcomp[j];
+        for (uint32_t jj = 0; jj < c.n_rem + c.n_val; ++jj) {              // a value binding commands its component remotely: every rule below holds for it as well
+            const bool is_val = jj >= c.n_rem;
+            const uint32_t j = is_val ? jj - c.n_rem : jj;
+            const char* kind = is_val ? "value" : "remote";
+            if (!is_val && (c.xflags[j] & GGRS_REMOTE_DESPAWN)) { if (despawner < 0) despawner = (long)i; continue; }
+            const uint32_t cc = is_val ? c.vcomp[j] : c.xcomp[j];
             const Comp& T = w->comps[cc];
-            if (T.s_n_words) return w->fail(GGRS_E_INVALID, "custom system '%s': remote binding %u names component %u ('%s'), which has a Strategy: remote commands on such a component are not supported", nm, j, cc, cname(cc));
-            if (T.no_rollback) return w->fail(GGRS_E_INVALID, "custom system '%s': remote binding %u names component %u ('%s'), which is not registered for rollback (GGRS_COMP_NO_ROLLBACK): remote commands on such a component are not supported", nm, j, cc, cname(cc));
+            if (T.s_n_words) return w->fail(GGRS_E_INVALID, "custom system '%s': %s binding %u names component %u ('%s'), which has a Strategy: remote commands on such a component are not supported", nm, kind, j, cc, cname(cc));
+            if (T.no_rollback) return w->fail(GGRS_E_INVALID, "custom system '%s': %s binding %u names component %u ('%s'), which is not registered for rollback (GGRS_COMP_NO_ROLLBACK): remote commands on such a component are not supported", nm, kind, j, cc, cname(cc));
             for (auto& o : w->customs) for (uint32_t q = 0; q < o.n_fx; ++q) if (o.fcomp[q] == cc)
-                return w->fail(GGRS_E_INVALID, "custom system '%s': remote binding %u names component %u ('%s'), word %u of which is an effect column of custom system '%s': remote commands and effects on the same component are not supported in this version "
-                                               "(the order of \"insert replaces\" against \"effect lands\" would depend on registration order)", nm, j, cc, cname(cc), o.fword[q], o.name.c_str());
+                return w->fail(GGRS_E_INVALID, "custom system '%s': %s binding %u names component %u ('%s'), word %u of which is an effect column of custom system '%s': remote commands and effects on the same component are not supported in this version "
+                                               "(the order of \"insert replaces\" against \"effect lands\" would depend on registration order)", nm, kind, j, cc, cname(cc), o.fword[q], o.name.c_str());
             if (cc < 64 && !((seen >> cc) & 1ull)) {
                 seen |= 1ull << cc;                                     // system i is the component's first remote commander
                 for (size_t k = i; k < w->systems.size(); ++k) if (binds(k, cc)) {
@@ -291,6 +294,30 @@ int remote_validate(ggrs_world* w) {
     if (need.devspawn) return w->fail(GGRS_E_INVALID, "remote bindings are not available in a world that spawns on the device with e.spawn(n) (GGRS_SPAWN_PAYLOAD_PARENT)");
     if (w->flags & (GGRS_WORLD_NO_GROUPS | GGRS_WORLD_UNFUSED)) return w->fail(GGRS_E_INVALID, "remote bindings need the generated request-group kernel, which a GGRS_WORLD_NO_GROUPS / GGRS_WORLD_UNFUSED world does not have");
     if (!w->knobs.tick_jit) return w->fail(GGRS_E_INVALID, "remote bindings need the generated request-group kernel, which this world does not have: disabled (GGRS_TICK_JIT=0)");
+    return GGRS_OK;
+}
+void rv_inbox_release(ggrs_world* w) {
+    if (w->rv_inbox.alloc) (void)hipFree(w->rv_inbox.alloc);
+    w->rv_inbox = ggrs_world::ValueInbox{};
+}
+// Value bindings (ggrs_hip_add_custom_system_values), after remote_validate -- which holds every rule of a remotely commanded component for a value-bound one: the
+// binding order, "after a despawner", rollback, no Strategy, not an effect column, GGRS_REMOTE_MAX_COMPONENTS for both kinds together, and the worlds remote bindings
+// are refused in.  What is left: a payload word is 4 or 8 bytes, and the world's value bindings fit the kernel's argument block.  (The per-system limits and
+// flags != 0 are refused when the system is added: its text is compiled against them.)  A component bound twice by one system is allowed: several targets per call
+int values_validate(ggrs_world* w) {
+    if (!world_has_values(w)) return GGRS_OK;
+    for (auto& c : w->customs) for (uint32_t j = 0; j < c.n_val; ++j) {
+        const Comp& T = w->comps[c.vcomp[j]];
+        if (T.word_bytes != 4 && T.word_bytes != 8)
+            return w->fail(GGRS_E_INVALID, "custom system '%s': value binding %u names component %u ('%s'), whose words have %u bytes: a value binding carries words of 4 or 8 bytes", c.name.c_str(), j, c.vcomp[j], T.name.c_str(), T.word_bytes);
+    }
+    const uint32_t n = world_n_values(w);
+    if (n > GGRS_VALUE_MAX_WORLD_BINDINGS) {
+        const ggrs_world::Custom* last = nullptr;
+        for (auto& c : w->customs) if (c.n_val) last = &c;
+        return w->fail(GGRS_E_INVALID, "value bindings: %u in this world, at most %d (GGRS_VALUE_MAX_WORLD_BINDINGS); the last are custom system '%s''s, on component %u ('%s')", n, GGRS_VALUE_MAX_WORLD_BINDINGS,
+                       last->name.c_str(), last->vcomp[last->n_val - 1], w->comps[last->vcomp[last->n_val - 1]].name.c_str());
+    }
     return GGRS_OK;
 }
 void sum_part_release(ggrs_world* w) {
@@ -356,6 +383,7 @@ int seal(ggrs_world* w) {
     rd_inbox_release(w);
     sum_part_release(w);
     rx_inbox_release(w);
+    rv_inbox_release(w);
     if (w->h_results) { (void)hipHostFree(w->h_results); w->h_results = nullptr; w->d_results = nullptr; }
     if (w->h_stage) { (void)hipHostFree(w->h_stage); w->h_stage = nullptr; w->d_hstage = nullptr; }
     if (w->h_rows) { (void)hipHostFree(w->h_rows); w->h_rows = nullptr; w->d_rows = nullptr; }
@@ -424,6 +452,8 @@ int seal_impl(ggrs_world* w) {
     { const int rrc = resources_validate(w); if (rrc) return rrc; }
     { const int drc = reduces_validate(w); if (drc) return drc; }
     { const int xrc = remote_validate(w); if (xrc) return xrc; }
+    { const int vrc = values_validate(w); if (vrc) return vrc; }
+    w->has_values = world_has_values(w);
     { const int src = sums_validate(w); if (src) return src; }
     w->has_sums = world_has_sums(w);
     w->has_remote = world_has_remote(w);
@@ -667,6 +697,25 @@ int seal_impl(ggrs_world* w) {
         rx.n_comps = remote_comps(w, rx.comp, rx.flags);
         HIPCHK(w, hipMalloc((void**)&rx.d, w->cap_pad * 4u));
         HIPCHK(w, hipMemsetAsync(rx.d, 0, w->cap_pad * 4u, w->stream));
+    }
+    if (w->has_values) {
+        // the value inbox, one allocation: a winner array (u64 per slot, zeroed: its resting state) per value-bound component, then a payload array per value
+        // binding of the world (n_words x cap_pad words; zeroed once, never reset: an entry is read only through a key written in the same frame)
+        ggrs_world::ValueInbox& rv = w->rv_inbox;
+        rv = ggrs_world::ValueInbox{};
+        const ggrs_world::RemoteInbox& rx = w->rx_inbox;
+        for (auto& c : w->customs) for (uint32_t j = 0; j < c.n_val && rv.n_bind < GGRS_VALUE_MAX_WORLD_BINDINGS; ++j) rv.bind_comp[rv.n_bind++] = c.vcomp[j];
+        uint64_t bytes = 0;
+        for (uint32_t k = 0; k < rx.n_comps; ++k) if (rx.flags[k] & RX_FLAG_VALUE) { ++rv.n_comps; bytes += w->cap_pad * 8u; }
+        const uint64_t pay0 = bytes;
+        for (uint32_t g = 0; g < rv.n_bind; ++g) bytes += align_up((uint64_t)w->comps[rv.bind_comp[g]].n_words * w->comps[rv.bind_comp[g]].word_bytes * w->cap_pad, 8);
+        HIPCHK(w, hipMalloc((void**)&rv.alloc, bytes));
+        HIPCHK(w, hipMemsetAsync(rv.alloc, 0, bytes, w->stream));
+        rv.bytes = bytes;
+        uint64_t off = 0;
+        for (uint32_t k = 0; k < rx.n_comps; ++k) if (rx.flags[k] & RX_FLAG_VALUE) { rv.d_win[k] = reinterpret_cast<uint64_t*>(rv.alloc + off); off += w->cap_pad * 8u; }
+        off = pay0;
+        for (uint32_t g = 0; g < rv.n_bind; ++g) { rv.d_pay[g] = rv.alloc + off; off += align_up((uint64_t)w->comps[rv.bind_comp[g]].n_words * w->comps[rv.bind_comp[g]].word_bytes * w->cap_pad, 8); }
     }
     if (w->vtags) { HIPCHK(w, hipMalloc((void**)&w->d_skip, 8)); HIPCHK(w, hipMemsetAsync(w->d_skip, 0, 8, w->stream)); }
     if (w->dev_spawn) {

@@ -182,6 +182,8 @@ struct ggrs_world {
         uint32_t n_rem = 0, xcomp[GGRS_REMOTE_MAX_BINDINGS] = {}, xflags[GGRS_REMOTE_MAX_BINDINGS] = {};
         // sum bindings (ggrs_hip_add_custom_system_sums): float / double words of the world's device resources the system adds into through e.sum_f32 / e.sum_f64(j, v)
         uint32_t n_sum = 0, sres[GGRS_SUM_MAX_BINDINGS] = {}, sword[GGRS_SUM_MAX_BINDINGS] = {};
+        // value bindings (ggrs_hip_add_custom_system_values): components of OTHER entities the system inserts WITH ITS OWN VALUE through e.val_*(j, k) / e.send_value(slot, j)
+        uint32_t n_val = 0, vcomp[GGRS_VALUE_MAX_BINDINGS] = {};
     };
     std::vector<Custom> customs;
     // DEVICE RESOURCES (ggrs_hip_register_resource): a few 4- or 8-byte words per world, carried by every wave of the generated kernel in wave-uniform registers.
@@ -221,7 +223,18 @@ struct ggrs_world {
     // generated kernel ORs into it with relaxed atomics; k_apply_remote, right behind every request group that holds an AdvanceWorld and ahead of k_apply_effects,
     // edits the live block's masks and columns and zeroes it again.  Not snapshot state
     struct RemoteInbox { uint32_t* d = nullptr; uint32_t n_comps = 0, comp[GGRS_REMOTE_MAX_COMPONENTS] = {}, flags[GGRS_REMOTE_MAX_COMPONENTS] = {}; uint64_t applies = 0; } rx_inbox;
-    bool has_remote = false;             // some system has remote bindings (set at seal)
+    bool has_remote = false;             // some system has remote or value bindings (set at seal)
+    // THE VALUE INBOX of a world with value bindings (allocated at seal).  win[k]: per value-bound component (k = its place in rx_inbox.comp) one u64 per slot of the
+    // padded capacity, the largest key (g + 1) << 40 | (sender slot + 1) sent to that slot in the frame -- all zeros whenever no group-and-apply pair is in flight.
+    // pay[g]: per value binding of the world (g = its ordinal: systems in registration order, then binding index) the senders' staged words, word-major and linear:
+    // word q of the sender at slot s sits at (q x cap_pad + s) x word bytes.  An entry is read only through a key written in the same frame, so it is never reset.
+    // The generated kernel writes both; k_apply_remote reads them and zeroes the winner words it read.  Not snapshot state
+    struct ValueInbox {
+        uint32_t n_bind = 0, n_comps = 0, bind_comp[GGRS_VALUE_MAX_WORLD_BINDINGS] = {};
+        uint64_t* d_win[GGRS_REMOTE_MAX_COMPONENTS] = {}; uint8_t* d_pay[GGRS_VALUE_MAX_WORLD_BINDINGS] = {}; uint8_t* alloc = nullptr;
+        uint64_t bytes = 0;
+    } rv_inbox;
+    bool has_values = false;             // some system has value bindings (set at seal)
     // THE SUM PARTIALS of a world with sum bindings (allocated at seal): per summed word one array of `units` 8-byte entries, entry u = the value of the balanced tree
     // over the 64 slots of unit u (a float in the low four bytes, or a double), stored by that unit's wave with one plain store in every launch that covers the unit --
     // so an entry is only ever valid for the launch that just ran, and k_apply_sums reads no entry beyond the units that launch covered.  Behind the arrays: two
@@ -530,6 +543,7 @@ void build_layout(ggrs_world* w) {
             for (uint32_t b = 0; b < c.n_bind; ++b) mark(c.comp[b], c.word[b], 1, true);      // a bound word may be written
             for (uint32_t j = 0; j < c.n_fx; ++j) mark(c.fcomp[j], c.fword[j], 1, true);     // an effect column: written (in OTHER entities) by the frame's sends -- every Save stores it, a sender counts as its writer
             for (uint32_t j = 0; j < c.n_cmd; ++j) if (c.ccomp[j] < w->comps.size()) mark(c.ccomp[j], 0, w->comps[c.ccomp[j]].n_words, true);   // a command-bound component: every word may be written (Option<&mut C>, insert)
+            for (uint32_t j = 0; j < c.n_val; ++j) if (c.vcomp[j] < w->comps.size()) mark(c.vcomp[j], 0, w->comps[c.vcomp[j]].n_words, true);   // a value-bound component: likewise, with the sender's words
             for (uint32_t j = 0; j < c.n_rem; ++j) if (c.xcomp[j] < w->comps.size()) mark(c.xcomp[j], 0, w->comps[c.xcomp[j]].n_words, true);   // a remotely commanded component: a remote insert writes every word (in OTHER entities) -- every Save stores them, the commander counts as their writer
         } break;
         default: break;     // spawn systems append rows: whoever runs them versions the bundle (run_spawn_systems / the fused path in host_groups.hpp)
@@ -622,22 +636,36 @@ inline uint64_t rows_bytes_hot(const ggrs_world* w) {
 }
 inline bool world_has_effects(const ggrs_world* w) { for (auto& c : w->customs) if (c.n_fx) return true; return false; }
 inline bool world_has_resources(const ggrs_world* w) { return !w->resources.empty(); }
-inline bool world_has_remote(const ggrs_world* w) { for (auto& c : w->customs) if (c.n_rem) return true; return false; }
-// the distinct remotely commanded components of the world in order of first use (systems in registration order, remote bindings in order) and the GGRS_REMOTE_* flags
-// some binding declares for each; returns how many there are (more than GGRS_REMOTE_MAX_COMPONENTS: only the first ones are written -- remote_validate refuses such a
-// world).  Component k owns bits 1 + 2k (insert) and 2 + 2k (remove) of an inbox word.  A despawn binding names no component
+inline bool world_has_remote(const ggrs_world* w) { for (auto& c : w->customs) if (c.n_rem || c.n_val) return true; return false; }   // (a value binding is a remote command that carries words)
+inline bool world_has_values(const ggrs_world* w) { for (auto& c : w->customs) if (c.n_val) return true; return false; }
+constexpr uint32_t RX_FLAG_VALUE = 0x100u;     // beside the GGRS_REMOTE_* flags of remote_comps: some VALUE binding names the component
+// the distinct remotely commanded components of the world in order of first use (systems in registration order; per system its remote bindings in order, then its
+// value bindings) and the GGRS_REMOTE_* flags some binding declares for each, RX_FLAG_VALUE for a value binding; returns how many there are (more than
+// GGRS_REMOTE_MAX_COMPONENTS: only the first ones are written -- remote_validate refuses such a world).  Component k owns bits 1 + 2k (insert), 2 + 2k (remove) and
+// 17 + k (a value was sent: its key is in the component's winner word) of an inbox word.  A despawn binding names no component
 inline uint32_t remote_comps(const ggrs_world* w, uint32_t* comps, uint32_t* flags = nullptr) {
     uint32_t n = 0;
-    for (auto& c : w->customs) for (uint32_t j = 0; j < c.n_rem; ++j) {
-        if (c.xcomp[j] >= w->comps.size()) continue;
+    auto take = [&](uint32_t cc, uint32_t fl) {
+        if (cc >= w->comps.size()) return;
         uint32_t k = 0;
-        while (k < n && k < GGRS_REMOTE_MAX_COMPONENTS && comps[k] != c.xcomp[j]) ++k;
-        if (k < n && k < GGRS_REMOTE_MAX_COMPONENTS) { if (flags) flags[k] |= c.xflags[j]; continue; }
-        if (n < GGRS_REMOTE_MAX_COMPONENTS) { comps[n] = c.xcomp[j]; if (flags) flags[n] = c.xflags[j]; }
+        while (k < n && k < GGRS_REMOTE_MAX_COMPONENTS && comps[k] != cc) ++k;
+        if (k < n && k < GGRS_REMOTE_MAX_COMPONENTS) { if (flags) flags[k] |= fl; return; }
+        if (n < GGRS_REMOTE_MAX_COMPONENTS) { comps[n] = cc; if (flags) flags[n] = fl; }
         ++n;
+    };
+    for (auto& c : w->customs) {
+        for (uint32_t j = 0; j < c.n_rem; ++j) take(c.xcomp[j], c.xflags[j]);
+        for (uint32_t j = 0; j < c.n_val; ++j) take(c.vcomp[j], RX_FLAG_VALUE);
     }
     return n;
 }
+// the world-wide ordinal of value binding j of custom system ci: the value bindings of the systems registered before it, then j
+inline uint32_t value_ordinal(const ggrs_world* w, size_t ci, uint32_t j) {
+    uint32_t g = 0;
+    for (size_t q = 0; q < ci && q < w->customs.size(); ++q) g += w->customs[q].n_val;
+    return g + j;
+}
+inline uint32_t world_n_values(const ggrs_world* w) { return value_ordinal(w, w->customs.size(), 0); }
 inline uint64_t world_rem_comps(const ggrs_world* w) {
     uint32_t comps[GGRS_REMOTE_MAX_COMPONENTS]; const uint32_t n = std::min<uint32_t>(remote_comps(w, comps), GGRS_REMOTE_MAX_COMPONENTS);
     uint64_t m = 0;

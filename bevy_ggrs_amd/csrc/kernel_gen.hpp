@@ -339,7 +339,24 @@ inline std::string res_system_typedef(const ggrs_world* w, const ggrs_world::Res
     "    __device__ void send_insert(ggrs_u64 s, int j) const __attribute__((enable_if(j >= 0 && j < 4 && ((GGRS_XI >> j) & 1u), \"e.send_insert(slot, j): remote binding j (a constant) must be declared with GGRS_REMOTE_INSERT\"))) { rx_or_(s, 1u << rxb_[j]); }\n" \
     "    __device__ void send_remove(ggrs_u64 s, int j) const __attribute__((enable_if(j >= 0 && j < 4 && ((GGRS_XR >> j) & 1u), \"e.send_remove(slot, j): remote binding j (a constant) must be declared with GGRS_REMOTE_REMOVE\"))) { rx_or_(s, 2u << rxb_[j]); }\n" \
     "    __device__ void send_despawn(ggrs_u64 s) const __attribute__((enable_if(GGRS_XD != 0u, \"e.send_despawn(slot): the system must have a remote binding with GGRS_REMOTE_DESPAWN\"))) { rx_or_(s, 1u); }\n"
-inline std::string entity_text(bool effects, bool peers, bool commands, bool default_typedef = true, bool resources = false, bool reduces = false, bool remote = false, bool sums = false) {
+// ... in a world with value bindings (ggrs_hip_add_custom_system_values): e.val_*(j, k) is a reference to staged word k of the system's value binding j, and
+// e.send_value(slot, j) records the binding's target -- registers only: sys_custom fills the staged words with the component's default literals before the call and,
+// after it, stores them and sends the key for every binding whose target was set (the last call won).  The remote template takes two more parameters -- GGRS_XV: bit
+// j = value binding j is declared, bit 4 + j = its words are 8 bytes wide; GGRS_VB: nibble j = the first of binding j's words in vw_[], nibble j + 1 = one past its
+// last -- and every accessor carries enable_if: the other width, an undeclared j, a k out of range or a j / k that is no constant finds no member and does not
+// compile.  Only in the text of worlds with value bindings.
+#define GGRS_VAL_OK_(W8) "j >= 0 && j < 4 && ((GGRS_XV >> j) & 1u) && ((GGRS_XV >> (4 + j)) & 1u) == " W8 " && k >= 0 && k < 8 && (int)((GGRS_VB >> (4 * j)) & 15u) + k < (int)((GGRS_VB >> (4 * j + 4)) & 15u)"
+#define GGRS_VAL_ACC_(NAME, TYPE, W8, BYTES) \
+    "    __device__ " TYPE "& " NAME "(int j, int k) __attribute__((enable_if(" GGRS_VAL_OK_(W8) ", \"e." NAME "(j, k): value binding j (a constant) must be declared, of " BYTES "-byte words, and k (a constant) one of its words\"))) { return *reinterpret_cast<" TYPE "*>(&vw_[vi_(j, k)]); }\n"
+#define GGRS_VALUE_MEMBERS_TEXT \
+    "    ggrs_u64 vw_[8] = {}; ggrs_u64 vt_[4] = {~0ull, ~0ull, ~0ull, ~0ull};   /* the staged words of the system's value bindings; the target of value binding j (all ones: nothing was sent) */\n" \
+    "    __device__ static constexpr int vi_(int j, int k) { return (int)((GGRS_VB >> (4 * j)) & 15u) + k; }\n" \
+    GGRS_VAL_ACC_("val_u32", "ggrs_u32", "0u", "4") \
+    GGRS_VAL_ACC_("val_i32", "int", "0u", "4") \
+    GGRS_VAL_ACC_("val_f32", "float", "0u", "4") \
+    GGRS_VAL_ACC_("val_u64", "ggrs_u64", "1u", "8") \
+    "    __device__ void send_value(ggrs_u64 s, int j) __attribute__((enable_if(j >= 0 && j < 4 && ((GGRS_XV >> j) & 1u), \"e.send_value(slot, j): value binding j (a constant) must be declared\"))) { vt_[j] = s; }\n"
+inline std::string entity_text(bool effects, bool peers, bool commands, bool default_typedef = true, bool resources = false, bool reduces = false, bool remote = false, bool sums = false, bool values = false) {
     std::string t = effects ? GGRS_ENTITY_EFFECTS_TEXT : (peers ? GGRS_ENTITY_PEERS_TEXT : GGRS_ENTITY_TEXT);
     if (resources) t.insert(t.rfind("};\n"), GGRS_RES_MEMBERS_TEXT);
     if (reduces) t.insert(t.rfind("};\n"), GGRS_RED_MEMBERS_TEXT);
@@ -348,12 +365,16 @@ inline std::string entity_text(bool effects, bool peers, bool commands, bool def
     const std::string head = "struct GgrsEntity {\n";
     if (remote && !effects && !peers) t.insert(0, "#ifndef GGRS_G\n#define GGRS_G __attribute__((address_space(1)))\n#endif\n");
     if (remote) t.insert(t.rfind("};\n"), GGRS_REMOTE_MEMBERS_TEXT);
+    if (values) t.insert(t.rfind("};\n"), GGRS_VALUE_MEMBERS_TEXT);
     const size_t at = t.find(head), end = t.rfind("};\n");
     if (commands) t.insert(end, GGRS_CMD_MEMBERS_TEXT);
+    if (values) t.replace(at, head.size(), "template <unsigned GGRS_IM, unsigned GGRS_RM, unsigned GGRS_CB, unsigned GGRS_XI, unsigned GGRS_XR, unsigned GGRS_XD, unsigned GGRS_XV, unsigned GGRS_VB> struct GgrsEntityC {\n");
+    else
     if (remote) t.replace(at, head.size(), "template <unsigned GGRS_IM, unsigned GGRS_RM, unsigned GGRS_CB, unsigned GGRS_XI, unsigned GGRS_XR, unsigned GGRS_XD> struct GgrsEntityC {\n");
     else
     t.replace(at, head.size(), "template <unsigned GGRS_IM, unsigned GGRS_RM, unsigned GGRS_CB> struct GgrsEntityC {\n");
     if (!default_typedef) return t;
+    if (values) return t + "typedef GgrsEntityC<0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u> GgrsEntity;  // what a system without command, remote or value bindings, and the spawner, see\n";
     if (remote) return t + "typedef GgrsEntityC<0u, 0u, 0u, 0u, 0u, 0u> GgrsEntity;  // what a system without command or remote bindings, and the spawner, see\n";
     return t + "typedef GgrsEntityC<0u, 0u, 0u> GgrsEntity;              // what a system without command bindings, and the spawner, see\n";
 }
@@ -364,7 +385,7 @@ inline uint32_t cmd_word_base(const ggrs_world* w, const ggrs_world::Custom& c, 
     return b;
 }
 // the entity type of ONE system of a world with command bindings, as the line that goes in front of its source
-inline std::string cmd_entity_typedef(const ggrs_world* w, const ggrs_world::Custom& c, bool remote = false) {
+inline std::string cmd_entity_typedef(const ggrs_world* w, const ggrs_world::Custom& c, bool remote = false, bool values = false) {
     uint32_t im = 0, rm = 0, cb = 0;
     for (uint32_t j = 0; j < c.n_cmd; ++j) {
         if (c.cflags[j] & GGRS_CMD_INSERT) im |= 1u << j;
@@ -378,6 +399,17 @@ inline std::string cmd_entity_typedef(const ggrs_world* w, const ggrs_world::Cus
             if (c.xflags[j] & GGRS_REMOTE_INSERT) xi |= 1u << j;
             if (c.xflags[j] & GGRS_REMOTE_REMOVE) xr |= 1u << j;
             if (c.xflags[j] & GGRS_REMOTE_DESPAWN) xd = 1u;
+        }
+        if (values) {                                                  // ... and the two value parameters (GGRS_VALUE_MEMBERS_TEXT)
+            uint32_t xv = 0, vb = 0, base = 0;
+            for (uint32_t j = 0; j < c.n_val; ++j) {
+                const Comp& T = w->comps[c.vcomp[j]];
+                xv |= 1u << j; if (T.word_bytes == 8) xv |= 16u << j;
+                vb |= (base & 15u) << (4 * j); base += T.n_words;
+            }
+            vb |= (base & 15u) << (4 * c.n_val);                           // (at most GGRS_VALUE_MAX_WORDS == 8: one nibble)
+            snprintf(b, sizeof b, "typedef ::GgrsEntityC<0x%xu, 0x%xu, 0x%xu, 0x%xu, 0x%xu, %uu, 0x%xu, 0x%xu> GgrsEntity;\n", im, rm, cb, xi, xr, xd, xv, vb);
+            return b;
         }
         snprintf(b, sizeof b, "typedef ::GgrsEntityC<0x%xu, 0x%xu, 0x%xu, 0x%xu, 0x%xu, %uu> GgrsEntity;\n", im, rm, cb, xi, xr, xd);
         return b;
@@ -737,6 +769,9 @@ struct GgrsJitArgs {
     // THE REMOTE INBOX of a world with remote bindings (host_world.hpp RemoteInbox; present only in such worlds): one u32 per slot; rx_len = the len of the group's source
     // block, as fx_len -- which the kernel reads instead in a world that also has effect bindings (rx_len is then absent from the device block)
     ggrs_u32* rx_inbox; ggrs_u64 rx_len;
+    // THE VALUE INBOX of a world with value bindings (host_world.hpp ValueInbox; present only in such worlds): the winner words of every value-bound component (indexed
+    // by the component's place among the remotely commanded ones; a component without a value binding keeps a null pointer nobody reads) and every binding's payload
+    ggrs_u64* rv_win[8]; unsigned char* rv_pay[16];
     // THE SUM PARTIALS of a world with sum bindings (host_world.hpp SumPartials; present only in such worlds): 8 bytes per summed word and 64-slot unit
     unsigned char* sum_part;
     ggrs_u32 cached_saves;                           // with nt: bit i = Save i is stored through the L2 all the same (the snapshot the NEXT group is expected to load)
@@ -765,7 +800,7 @@ struct JitLayout {
     struct Member { uint32_t bytes = 0, save_dst = 0, save_rows = 0, save_len = 0, spawn_payload = 0, spawn_first = 0, live = 0, live_rows = 0, marks_dst = 0, save_pmask = 0, live_pmask = 0,
                     spawn_count = 0, n_inputs = 0, inputs = 0, save_tagok = 0, live_tagok = 0; } m;
 };
-struct JitNeeds { bool spawn, inputs, marks, box, vtags, devspawn, devstream, nr, peers, effects, commands, res, red, rem, sum; };
+struct JitNeeds { bool spawn, inputs, marks, box, vtags, devspawn, devstream, nr, peers, effects, commands, res, red, rem, sum, val; };
 // the distinct peer-bound columns of the world in order of first use (systems in registration order, peer bindings in order) and the components they belong to;
 // returns how many there are (more than GGRS_PEER_MAX_COLUMNS: only the first ones are written -- peers_validate refuses such a world)
 inline uint32_t peer_cols(const ggrs_world* w, uint32_t* cols, uint32_t* n_pres = nullptr, uint32_t* pres = nullptr) {
@@ -815,6 +850,8 @@ JitLayout jit_layout(const ggrs_world* w) {
     if (need.effects) L.cap_steps = 1;           // effects land at the END of the frame: the inbox is applied behind the group's launch, so a group ends on its one AdvanceWorld
     uint32_t fx_cols[GGRS_EFFECT_MAX_COLUMNS]; const uint32_t n_fx = std::min<uint32_t>(effect_cols(w, fx_cols), GGRS_EFFECT_MAX_COLUMNS);
     uint32_t pv_cols[GGRS_PEER_MAX_COLUMNS]; const uint32_t n_pv = std::min<uint32_t>(peer_cols(w, pv_cols), GGRS_PEER_MAX_COLUMNS);
+    uint32_t rv_comps[GGRS_REMOTE_MAX_COMPONENTS]; const uint32_t n_rvc = std::min<uint32_t>(remote_comps(w, rv_comps), GGRS_REMOTE_MAX_COMPONENTS);
+    const uint32_t n_rvb = std::min<uint32_t>(world_n_values(w), GGRS_VALUE_MAX_WORLD_BINDINGS);
     auto add = [&](const char* type, const char* name, uint32_t elem, size_t off, uint32_t host_count, uint32_t dev_count, bool present) {
         L.f.push_back(JitField{type, name, elem, (uint32_t)off, host_count, dev_count, present, 0, 0, 0, 0, false});
     };
@@ -836,6 +873,7 @@ JitLayout jit_layout(const ggrs_world* w) {
         F1("const unsigned char*", res_src, need.res); F1("unsigned char*", rd_inbox, need.red);
         F1("ggrs_u32*", rx_inbox, need.rem); F1("ggrs_u64", rx_len, need.rem && !need.effects);
         F1("unsigned char*", sum_part, need.sum);
+        FA("ggrs_u64*", rv_win, n_rvc, need.val); FA("unsigned char*", rv_pay, n_rvb, need.val);
         FA("unsigned char*", save_dst, S, true); FA("ggrs_u64", save_rows, S, true); FA("ggrs_u64", save_len, S, true);
         FS("const unsigned char*", spawn_payload, need.spawn); FS("ggrs_u64", spawn_first, need.spawn);
         FA("int", save_frame, S, true); FA("ggrs_u32", save_pmask, S, true);
@@ -1054,7 +1092,8 @@ inline uint64_t jit_marks_rec_frames_off(const ggrs_world* w) { return align_up(
 inline uint64_t jit_marks_rec_bytes(const ggrs_world* w) { return jit_marks_rec_frames_off(w) + align_up(w->cap_pad * 4, ALIGN); }
 // which optional parts of the argument block this world's kernel reads
 JitNeeds jit_needs(const ggrs_world* w) {
-    JitNeeds n{false, false, false, false, false, false, false, false, false, false, false, false, false, false, false};
+    JitNeeds n{false, false, false, false, false, false, false, false, false, false, false, false, false, false, false, false};
+    n.val = world_has_values(w);
     n.sum = world_has_sums(w);
     n.rem = world_has_remote(w);
     n.red = world_has_reduces(w);
@@ -1223,7 +1262,7 @@ struct JitGen {
                                     "#define GGRS_SP_READ %uu                                                           // sp_desc[GGRS_SP_READ x tiles + tile]: that tile has read its starting len\n",
                          2u + (unsigned)MAX_TICK_SAVES, 2u * (unsigned)MAX_TICK_STEPS);
         s += GGRS_FRAME_TEXT;
-        s += entity_text(need.effects, need.peers, need.commands, true, need.res, need.red, need.rem, need.sum);
+        s += entity_text(need.effects, need.peers, need.commands, true, need.res, need.red, need.rem, need.sum, need.val);
         if (need.res) s += GGRS_RESOURCES_TEXT;
         if (need.red) s += GGRS_REDUCE_WAVE_TEXT;
         if (need.sum) s += GGRS_SUM_WAVE_TEXT;
@@ -1234,7 +1273,7 @@ struct JitGen {
     // ---- 2. user sources: systems, spawner, hashers, strategies -- each in a namespace of its own, under its own name in the compiler's messages
     void user_sources() {
         for (size_t i = 0; i < w->customs.size(); ++i) {
-            if (need.commands || need.rem) sfmt(s, "namespace ggrs_sys_%zu {\n%s#line 1 \"%s\"\n", i, cmd_entity_typedef(w, w->customs[i], need.rem).c_str(), file_name(w->customs[i].name).c_str());
+            if (need.commands || need.rem) sfmt(s, "namespace ggrs_sys_%zu {\n%s#line 1 \"%s\"\n", i, cmd_entity_typedef(w, w->customs[i], need.rem, need.val).c_str(), file_name(w->customs[i].name).c_str());
             else
             sfmt(s, "namespace ggrs_sys_%zu {\n#line 1 \"%s\"\n", i, file_name(w->customs[i].name).c_str());
             s += w->customs[i].source;
@@ -1910,7 +1949,7 @@ struct JitGen {
                 sfmt(s, "                ent.fx_.col[%u] = (unsigned long)a.fx_col[%u]; ent.fx_.wb[%u] = %uu; ent.fx_.op[%u] = %uu;\n", j, at, j, w->comps[c.fcomp[j]].word_bytes, j, c.fop[j]);
             }
         }
-        if (c.n_rem) {
+        if (c.n_rem || c.n_val) {
             // remote bindings: every send ORs into the slot's word of the world's one inbox; binding j's insert bit is 1 + 2k, k = the component's place among the
             // world's remotely commanded components (remove: the next bit).  The bounds length is the source block's len
             uint32_t rx_comps[GGRS_REMOTE_MAX_COMPONENTS]; const uint32_t n_rx = std::min<uint32_t>(remote_comps(w, rx_comps), GGRS_REMOTE_MAX_COMPONENTS);
@@ -1948,7 +1987,38 @@ struct JitGen {
             if (own == j) sfmt(s, "                ent.%s[%u] = sm%u; ent.smw_[%u] = %uu; ent.sma_[%u] = %uu;\n", r.wb == 8 ? "smd_" : "smf_", j, r.reg, j, r.wb, j, j);
             else sfmt(s, "                ent.smw_[%u] = %uu; ent.sma_[%u] = %uu;\n", j, r.wb, j, own);
         }
+        // value bindings: the staged words start at the literals of the component's registered default (0 without one)
+        for (uint32_t j = 0, base = 0; j < c.n_val; ++j) {
+            const Comp& T = w->comps[c.vcomp[j]];
+            for (uint32_t k = 0; k < T.n_words; ++k) {
+                unsigned long long v = 0;
+                if (T.defaults.size() >= (size_t)(k + 1) * T.word_bytes) memcpy(&v, &T.defaults[(size_t)k * T.word_bytes], T.word_bytes);
+                if (v) sfmt(s, "                ent.vw_[%u] = 0x%llxull;\n", base + k, v);
+            }
+            base += T.n_words;
+        }
         sfmt(s, "                ggrs_sys_%u::ggrs_system(ent, fr%zu);\n", d.comp[0], i);
+        // ... and every binding whose target was set (the last e.send_value of the call) and lies below the start-of-frame len: the staged words as they stand now go to
+        // the binding's payload AT THE SENDER'S OWN SLOT (plain stores, word-major: lane == slot, so a wave's stores of one word are one line run), the key
+        // (g + 1) << 40 | (slot + 1) is raised into the target's winner word of the component (one no-return 64-bit atomic max: the largest key of the frame stays,
+        // whichever lane arrives first), and the "value" bit of the component goes into the target's remote inbox word.  All three are read by k_apply_remote, a LATER
+        // launch: the kernel boundary is the only synchronisation
+        if (c.n_val) {
+            uint32_t rx_comps[GGRS_REMOTE_MAX_COMPONENTS]; const uint32_t n_rx = std::min<uint32_t>(remote_comps(w, rx_comps), GGRS_REMOTE_MAX_COMPONENTS);
+            for (uint32_t j = 0, base = 0; j < c.n_val; ++j) {
+                const Comp& T = w->comps[c.vcomp[j]];
+                const uint32_t g = value_ordinal(w, d.comp[0], j);
+                uint32_t at = 0; while (at < n_rx && rx_comps[at] != c.vcomp[j]) ++at;
+                sfmt(s, "                if (ent.vt_[%u] < ent.rxn_) {                              // value binding %u: component %u, world ordinal %u\n", j, j, c.vcomp[j], g);
+                for (uint32_t k = 0; k < T.n_words; ++k)
+                    sfmt(s, "                    *(GGRS_G %s*)((unsigned long)a.rv_pay[%u] + (%lluull + e0) * %uull) = (%s)ent.vw_[%u];\n", T.word_bytes == 8 ? "ggrs_u64" : "ggrs_u32", g,
+                         (unsigned long long)k * w->cap_pad, T.word_bytes, T.word_bytes == 8 ? "ggrs_u64" : "ggrs_u32", base + k);
+                sfmt(s, "                    (void)__hip_atomic_fetch_max((GGRS_G ggrs_u64*)((unsigned long)a.rv_win[%u] + (ent.vt_[%u] << 3)), 0x%llxull | ((ggrs_u64)e0 + 1ull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
+                        "                    (void)__hip_atomic_fetch_or((GGRS_G ggrs_u32*)(ent.rx_ + (ent.vt_[%u] << 2)), 0x%xu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
+                        "                }\n", at, j, (unsigned long long)(g + 1) << 40, j, 1u << (17u + at));
+                base += T.n_words;
+            }
+        }
         for (uint32_t j = 0; j < c.n_sum; ++j) {
             const SummedWord r = sum_of(c, j);
             if (sum_owner(c, j) == j) sfmt(s, "                sm%u = ent.%s[%u];\n", r.reg, r.wb == 8 ? "smd_" : "smf_", j);

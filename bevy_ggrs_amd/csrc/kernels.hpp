@@ -708,6 +708,10 @@ __global__ __launch_bounds__(TPB) void k_apply_effects(FxApplyArgs a) {
 // with one __ballot each (lane 0 stores the 8-byte word), lanes whose slot gains a component write its registered default into the live columns (tile-major), and the
 // inbox words go back to zero.  A command on a slot that is not alive once the frame's own despawns are in is dropped; DESPAWN WINS over everything, REMOVE WINS over
 // insert.  Plain loads and stores: the sends were atomics of an EARLIER launch, a slot is touched by one lane, a mask word by one wave.
+// VALUE BINDINGS (ggrs_hip_add_custom_system_values; ggrs_world::ValueInbox): bit 17 + k of the inbox word says a value was sent for component k.  The lane then reads
+// the slot's winner word win[k][e] -- the largest key (g + 1) << 40 | (sender slot + 1) of the frame --, and where the slot gains the component it gathers the
+// component's words from pay[g][..][sender] instead of the defaults: A VALUE WINS over a default insert, the winner's words arrive together.  The winner word goes back
+// to zero whether the value landed or was dropped (a dead or despawned target, a remove); the payload needs no reset.
 constexpr int RX_MAX_COMPS = GGRS_REMOTE_MAX_COMPONENTS;
 constexpr int RX_MAX_WORDS = 64;                            // words of all remotely commanded components together (a world has at most 64 word columns)
 struct RxApplyArgs {
@@ -716,7 +720,10 @@ struct RxApplyArgs {
     uint64_t col_off[RX_MAX_WORDS], dflt[RX_MAX_WORDS];     // per word of component k, from w_base[k]: its column and the default it takes on insert
     uint32_t w_base[RX_MAX_COMPS], n_words[RX_MAX_COMPS], wb[RX_MAX_COMPS], ts[RX_MAX_COMPS];
     uint32_t n_comps, n_units;
+    // value bindings: the winner words of component k (null: no value binding names it), the payload of the world's value binding g, the entries per payload word
+    uint64_t* win[RX_MAX_COMPS]; const uint8_t* pay[GGRS_VALUE_MAX_WORLD_BINDINGS]; uint64_t pay_stride; uint32_t n_pay;
 };
+static_assert(sizeof(RxApplyArgs) + sizeof(FxApplyArgs) <= 4096, "RxApplyArgs travels by value beside FxApplyArgs (k_apply_remote_effects): both fit the 4 KiB kernel-argument segment");
 // one unit of k_apply_remote, by all 64 lanes of its wave.  Returns whether the unit held a command; then alive_out is the unit's alive word as it stands now
 __device__ __forceinline__ bool rx_apply_unit(const RxApplyArgs& a, uint32_t u, uint32_t lane, uint64_t& alive_out) {
     const uint64_t e = (uint64_t)u * 64u + lane;
@@ -732,14 +739,28 @@ __device__ __forceinline__ bool rx_apply_unit(const RxApplyArgs& a, uint32_t u, 
     if (lane == 0 && alive_n != alive_w) *alive_p = alive_n;
     for (uint32_t k = 0; k < a.n_comps; ++k) {
         const bool ins = (m >> (1u + 2u * k)) & 1u, rem = (m >> (2u + 2u * k)) & 1u;
-        if (!__ballot(on && (ins || rem))) continue;                            // wave-uniform
+        bool val = (m >> (17u + k)) & 1u;
+        uint64_t key = 0;
+        if (val) { key = a.win[k][e]; a.win[k][e] = 0ull; }                      // (the bit is only ever set beside a key, by the same sender)
+        const uint32_t vg = (uint32_t)(key >> 40) - 1u;                          // the winner's value binding and slot
+        const uint64_t vs = (key & 0xFFFFFFFFFFull) - 1ull;
+        val = val && key != 0ull && vg < a.n_pay && vs < a.pay_stride;
+        if (!__ballot(on && (ins || rem || val))) continue;                     // wave-uniform
         uint64_t* const pres_p = reinterpret_cast<uint64_t*>(a.live + a.off_present[k] + (uint64_t)u * 8u);
         const uint64_t pres_w = *pres_p;
         const bool has = (pres_w >> lane) & 1ull;
-        const bool gains = on && ins && !rem;                                    // remove wins over insert
-        const uint64_t pres_n = __ballot(on ? (!rem && (ins || has)) : has);
+        const bool gains = on && (ins || val) && !rem;                           // remove wins over any insert
+        const uint64_t pres_n = __ballot(on ? (!rem && (ins || val || has)) : has);
         if (lane == 0 && pres_n != pres_w) *pres_p = pres_n;
-        if (gains) for (uint32_t q = 0; q < a.n_words[k]; ++q) {                 // Bevy's insert: a present component's value is replaced
+        if (gains && val) for (uint32_t q = 0; q < a.n_words[k]; ++q) {          // a value wins over a default insert: the winner's words, gathered from its payload slot
+            uint8_t* const p = a.live + col_at(a.col_off[a.w_base[k] + q], a.ts[k], a.wb[k], e);
+            // (vg differs per lane: a.pay[vg] is a vector load from the kernel-argument segment, not a copy of the block into scratch -- tests/test_remote_values_text.py
+            // pins private_segment_fixed_size 0 for both apply kernels)
+            const uint8_t* const v = a.pay[vg] + ((uint64_t)q * a.pay_stride + vs) * a.wb[k];
+            if (a.wb[k] == 8) *reinterpret_cast<uint64_t*>(p) = *reinterpret_cast<const uint64_t*>(v);
+            else *reinterpret_cast<uint32_t*>(p) = *reinterpret_cast<const uint32_t*>(v);
+        }
+        else if (gains) for (uint32_t q = 0; q < a.n_words[k]; ++q) {                 // Bevy's insert: a present component's value is replaced
             const uint32_t x = a.w_base[k] + q;
             uint8_t* const p = a.live + col_at(a.col_off[x], a.ts[k], a.wb[k], e);
             switch (a.wb[k]) {

@@ -297,7 +297,7 @@ class World(WorldBase):
         self.capacity = capacity
 
     def add_custom_system(self, source: str, bindings: Sequence[tuple], iparam=(), fparam=(), name: str = "custom", peers: Sequence[tuple] = (), effects: Sequence[tuple] = (),
-                          commands: Sequence[tuple] = (), resources: Sequence[tuple] = (), reduces: Sequence[tuple] = (), remote=None, sums=None):
+                          commands: Sequence[tuple] = (), resources: Sequence[tuple] = (), reduces: Sequence[tuple] = (), remote=None, sums=None, values=None):
         """add_systems(GgrsSchedule, <your system>) for a per-entity system written in HIP C++ (ggrs_hip_add_custom_system):
         `source` defines `__device__ void ggrs_system(GgrsEntity& e, const GgrsFrame& f)`, `bindings` = [(comp, word), ..]
         are the words it sees as e.f32(i)/e.u32(i)/e.i32(i)/e.u64(i).  Compiled for gfx950 when added; a compile error raises
@@ -320,7 +320,12 @@ class World(WorldBase):
         remove wins over insert.  Any list, the empty one included, goes through that entry point; None (the default) does not.
         `sums` = [(res, word), ..] (ggrs_hip_add_custom_system_sums): float (4-byte) or double (8-byte) words of the world's device resources the system adds into --
         `e.sum_f32(j, v)` / `e.sum_f64(j, v)`; nothing is returned.  The frame's total is the balanced binary tree over slot indices (bit-exact, independent of
-        launch geometry) and lands at the end of the frame.  Any list, the empty one included, goes through that entry point; None (the default) does not."""
+        launch geometry) and lands at the end of the frame.  Any list, the empty one included, goes through that entry point; None (the default) does not.
+        `values` = [comp, ..] (ggrs_hip_add_custom_system_values): components of OTHER entities the system inserts WITH ITS OWN WORDS -- `e.val_u32(j, k)` /
+        `e.val_i32` / `e.val_f32` / `e.val_u64` is staged word k of value binding j (the component's registered default on entry), `e.send_value(slot, j)`
+        makes the entity at `slot` have the component with the staged words as they stand when ggrs_system returns.  One target per binding and call (the last
+        call wins; bind the component twice to hit two targets); the last sender in schedule order wins, as one value; a value wins over a default insert.
+        Any list, the empty one included, goes through that entry point; None (the default) does not."""
         d = _ffi.CustomSystemDesc()
         d.name, d.source, d.n_bindings = name.encode(), source.encode(), len(bindings)
         if len(bindings) > _ffi.CUSTOM_MAX_BINDINGS:
@@ -328,12 +333,17 @@ class World(WorldBase):
         for i, (c, w) in enumerate(bindings): d.comp[i], d.word[i] = c, w
         for i, v in enumerate(iparam): d.iparam[i] = v
         for i, v in enumerate(fparam): d.fparam[i] = v
-        if sums is not None:
-            remote = remote or ()
-            if (len(peers) > _ffi.PEER_MAX_BINDINGS or len(effects) > _ffi.EFFECT_MAX_BINDINGS or len(commands) > _ffi.COMMAND_MAX_BINDINGS or len(resources) > _ffi.RESOURCE_MAX_BINDINGS
-                    or len(reduces) > _ffi.REDUCE_MAX_BINDINGS or len(remote) > _ffi.REMOTE_MAX_BINDINGS or len(sums) > _ffi.SUM_MAX_BINDINGS):
-                raise ValueError(f"at most {_ffi.PEER_MAX_BINDINGS} peer, {_ffi.EFFECT_MAX_BINDINGS} effect, {_ffi.COMMAND_MAX_BINDINGS} command, {_ffi.RESOURCE_MAX_BINDINGS} resource, "
-                                 f"{_ffi.REDUCE_MAX_BINDINGS} reduce, {_ffi.REMOTE_MAX_BINDINGS} remote and {_ffi.SUM_MAX_BINDINGS} sum bindings")
+        if values is not None or sums is not None or remote is not None:
+            # the entry points that take every kind of binding: _values when `values` is a list, else _sums when `sums` is one, else _remote -- each is the one
+            # before it plus one more kind; the binding arrays are built once
+            with_sums, with_values = sums is not None or values is not None, values is not None
+            remote, sums, values = remote or (), sums or (), values or ()
+            kinds = [("peer", peers, _ffi.PEER_MAX_BINDINGS), ("effect", effects, _ffi.EFFECT_MAX_BINDINGS), ("command", commands, _ffi.COMMAND_MAX_BINDINGS),
+                     ("resource", resources, _ffi.RESOURCE_MAX_BINDINGS), ("reduce", reduces, _ffi.REDUCE_MAX_BINDINGS), ("remote", remote, _ffi.REMOTE_MAX_BINDINGS)]
+            if with_sums: kinds.append(("sum", sums, _ffi.SUM_MAX_BINDINGS))
+            if with_values: kinds.append(("value", values, _ffi.VALUE_MAX_BINDINGS))
+            if any(len(lst) > cap for _, lst, cap in kinds):
+                raise ValueError("at most " + ", ".join(f"{cap} {kind}" for kind, _, cap in kinds[:-1]) + f" and {kinds[-1][2]} {kinds[-1][0]} bindings")
             pb = (_ffi.PeerBinding * max(1, len(peers)))()
             for j, (c, w) in enumerate(peers): pb[j].comp, pb[j].word = c, w
             eb = (_ffi.EffectBinding * max(1, len(effects)))()
@@ -346,29 +356,17 @@ class World(WorldBase):
             for j, (r, w, op) in enumerate(reduces): db[j].res, db[j].word, db[j].op = r, w, op
             xb = (_ffi.RemoteBinding * max(1, len(remote)))()
             for j, (c, fl) in enumerate(remote): xb[j].comp, xb[j].flags = c, fl
-            sb = (_ffi.SumBinding * max(1, len(sums)))()
-            for j, (r, w) in enumerate(sums): sb[j].res, sb[j].word = r, w
-            self._check(self._lib.ggrs_hip_add_custom_system_sums(self._p, C.byref(d), pb, len(peers), eb, len(effects), cb, len(commands), rb, len(resources), db, len(reduces), xb, len(remote),
-                                                                  sb, len(sums)))
-            return
-        if remote is not None:
-            if (len(peers) > _ffi.PEER_MAX_BINDINGS or len(effects) > _ffi.EFFECT_MAX_BINDINGS or len(commands) > _ffi.COMMAND_MAX_BINDINGS or len(resources) > _ffi.RESOURCE_MAX_BINDINGS
-                    or len(reduces) > _ffi.REDUCE_MAX_BINDINGS or len(remote) > _ffi.REMOTE_MAX_BINDINGS):
-                raise ValueError(f"at most {_ffi.PEER_MAX_BINDINGS} peer, {_ffi.EFFECT_MAX_BINDINGS} effect, {_ffi.COMMAND_MAX_BINDINGS} command, {_ffi.RESOURCE_MAX_BINDINGS} resource, "
-                                 f"{_ffi.REDUCE_MAX_BINDINGS} reduce and {_ffi.REMOTE_MAX_BINDINGS} remote bindings")
-            pb = (_ffi.PeerBinding * max(1, len(peers)))()
-            for j, (c, w) in enumerate(peers): pb[j].comp, pb[j].word = c, w
-            eb = (_ffi.EffectBinding * max(1, len(effects)))()
-            for j, (c, w, op) in enumerate(effects): eb[j].comp, eb[j].word, eb[j].op = c, w, op
-            cb = (_ffi.CommandBinding * max(1, len(commands)))()
-            for j, (c, fl) in enumerate(commands): cb[j].comp, cb[j].flags = c, fl
-            rb = (_ffi.ResourceBinding * max(1, len(resources)))()
-            for j, (r, w) in enumerate(resources): rb[j].res, rb[j].word = r, w
-            db = (_ffi.ReduceBinding * max(1, len(reduces)))()
-            for j, (r, w, op) in enumerate(reduces): db[j].res, db[j].word, db[j].op = r, w, op
-            xb = (_ffi.RemoteBinding * max(1, len(remote)))()
-            for j, (c, fl) in enumerate(remote): xb[j].comp, xb[j].flags = c, fl
-            self._check(self._lib.ggrs_hip_add_custom_system_remote(self._p, C.byref(d), pb, len(peers), eb, len(effects), cb, len(commands), rb, len(resources), db, len(reduces), xb, len(remote)))
+            args = [self._p, C.byref(d), pb, len(peers), eb, len(effects), cb, len(commands), rb, len(resources), db, len(reduces), xb, len(remote)]
+            fn = self._lib.ggrs_hip_add_custom_system_remote
+            if with_sums:
+                sb = (_ffi.SumBinding * max(1, len(sums)))()
+                for j, (r, w) in enumerate(sums): sb[j].res, sb[j].word = r, w
+                args += [sb, len(sums)]; fn = self._lib.ggrs_hip_add_custom_system_sums
+            if with_values:
+                vb = (_ffi.ValueBinding * max(1, len(values)))()
+                for j, c in enumerate(values): vb[j].comp, vb[j].flags = (c if isinstance(c, tuple) else (c, 0))   # (a (comp, flags) pair reaches the library as it is: flags must be 0)
+                args += [vb, len(values)]; fn = self._lib.ggrs_hip_add_custom_system_values
+            self._check(fn(*args))
             return
         if reduces:
             if (len(peers) > _ffi.PEER_MAX_BINDINGS or len(effects) > _ffi.EFFECT_MAX_BINDINGS or len(commands) > _ffi.COMMAND_MAX_BINDINGS or len(resources) > _ffi.RESOURCE_MAX_BINDINGS

@@ -438,6 +438,11 @@ struct HipBackend {
                                const ggrs_resource_binding* res, uint32_t n_res, const ggrs_reduce_binding* red, uint32_t n_red, const ggrs_remote_binding* rem, uint32_t n_rem, const ggrs_sum_binding* sum, uint32_t n_sum) {
         return ggrs_hip_add_custom_system_sums(w, d, peers, n_peers, effects, n_effects, cmds, n_cmds, res, n_res, red, n_red, rem, n_rem, sum, n_sum);
     }
+    int add_custom_system_values(const ggrs_custom_system_desc* d, const ggrs_peer_binding* peers, uint32_t n_peers, const ggrs_effect_binding* effects, uint32_t n_effects, const ggrs_command_binding* cmds, uint32_t n_cmds,
+                                 const ggrs_resource_binding* res, uint32_t n_res, const ggrs_reduce_binding* red, uint32_t n_red, const ggrs_remote_binding* rem, uint32_t n_rem, const ggrs_sum_binding* sum, uint32_t n_sum,
+                                 const ggrs_value_binding* val, uint32_t n_val) {
+        return ggrs_hip_add_custom_system_values(w, d, peers, n_peers, effects, n_effects, cmds, n_cmds, res, n_res, red, n_red, rem, n_rem, sum, n_sum, val, n_val);
+    }
     int resource_read(uint32_t r, void* words_out) { return ggrs_hip_resource_read(w, r, words_out); }
     int resource_write(uint32_t r, const void* words) { return ggrs_hip_resource_write(w, r, words); }
     int register_component_strategy(uint32_t c, uint32_t stored_word_bytes, uint32_t stored_n_words, const char* source) { return ggrs_hip_register_component_strategy(w, c, stored_word_bytes, stored_n_words, source); }

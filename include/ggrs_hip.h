@@ -539,6 +539,59 @@ int ggrs_hip_add_custom_system_sums(ggrs_world* w, const ggrs_custom_system_desc
                                     const ggrs_remote_binding* rem, uint32_t n_rem,
                                     const ggrs_sum_binding* sum, uint32_t n_sum);
 
+/* REMOTE INSERTS THAT CARRY THE SENDER'S VALUE (value bindings) --
+ *
+ *     fn torch(mut commands: Commands, q: Query<(Entity, &Target, &Power)>) { for (me, t, p) in &q { commands.entity(t.0).insert(Burn { dps: p.0, ticks: 3, source: me }); } }
+ *
+ * "the thing I hit becomes Burning{dps, ticks}, and the numbers come from ME".  e.send_insert (above) can only insert the registered default.
+ *
+ *   ggrs_hip_add_custom_system_values   ggrs_hip_add_custom_system_sums plus VALUE BINDINGS: val[j] = {comp, flags}, flags must be 0.  With n_val == 0 the call
+ *                                  behaves exactly as ggrs_hip_add_custom_system_sums.  At most GGRS_VALUE_MAX_BINDINGS per system, GGRS_VALUE_MAX_WORDS staged words
+ *                                  per system (all its value bindings together; both refused when the system is added) and GGRS_VALUE_MAX_WORLD_BINDINGS value
+ *                                  bindings per world (refused at seal).  ggrs_remote_binding and its flags are unchanged.
+ *   inside ggrs_system, with j and k literals
+ *     e.val_u32(j, k) / e.val_i32 / e.val_f32 / e.val_u64
+ *                                  a reference to STAGED WORD k of value binding j.  On entry it holds word k of the component's registered default
+ *                                  (ggrs_hip_set_component_default, else 0).  An accessor of the other width, or j / k not a constant or out of range, finds no
+ *                                  member: a compile error when the system is added, with the compiler's log (enable_if, as e.insert / e.send_insert).
+ *     e.send_value(slot, j)        at the end of the frame the entity at `slot` HAS component val[j].comp, with ALL its words equal to the staged words of binding j
+ *                                  AS THEY STAND WHEN ggrs_system RETURNS (not as they stood at the call).  Bevy's insert: a present component is replaced.
+ *                                  ONE COMMAND PER BINDING AND CALL: the last e.send_value(.., j) of a call of ggrs_system sets the target, an earlier one of the
+ *                                  same call is forgotten ("the last call wins", as e.insert / e.remove).  A system that must hit SEVERAL targets in one call
+ *                                  declares several value bindings of the same component, which is allowed.  A call that never sends writes nothing.
+ *
+ * THE CONTRACT.  The value lands where the remote commands land: after the frame's systems and host-decided spawns, with the remote commands, AHEAD of effects,
+ * reductions and sums, before anything observes the frame.  The drop rules are theirs: a value is dropped unless  slot < the len at the start of the frame  and the
+ * target is alive once the frame's own despawns are in; a sender that despawns itself in the call still sends; an entity spawned in the frame cannot be hit.
+ * CONFLICTS on one target and component in one frame: DESPAWN WINS OVER EVERYTHING; REMOVE WINS OVER ANY INSERT; A VALUE WINS OVER A DEFAULT INSERT (e.send_insert);
+ * AMONG VALUES THE LARGEST KEY WINS,  key = (g + 1) << 40 | (sender slot + 1),  g = the value binding's world-wide ordinal, counted in system registration order and
+ * then binding index -- the last sender in schedule order: by system registration, then binding index, then RollbackOrdered index.  That is what a Bevy system
+ * iterating in RollbackOrdered order and applying its Commands in order leaves.  THE WINNER'S WORDS ARRIVE TOGETHER: two senders' words are never mixed.  The result
+ * depends on the SET of senders alone: replays, rollbacks, ranks and every copy of the kernel (generic, steady, specialised) agree bit for bit.
+ * Seal (values_validate, beside remote_validate), each refusal GGRS_E_INVALID with a message naming the system and the component: a value-bound component counts as a
+ * REMOTELY COMMANDED component in every rule of ggrs_hip_add_custom_system_remote -- no system registered at or after its first commander (remote or value) binds
+ * it, no cross-entity bindings after a remote despawner, rollback, no Strategy, not an effect column, and GGRS_REMOTE_MAX_COMPONENTS counts both kinds together --;
+ * its words are 4 or 8 bytes; flags != 0; more than GGRS_VALUE_MAX_WORLD_BINDINGS value bindings in the world.  A component bound twice by one system is ALLOWED.
+ * Everything remote bindings refuse stays refused: RollbackDespawned worlds, device-decided spawns, worlds without the generated kernel,
+ * ggrs_hip_fanout_step_branches (ggrs_hip_fanout_step works).
+ * How it runs: a sender stores its staged words into a payload array of its binding AT ITS OWN SLOT (plain coalesced stores), raises the target's 64-bit WINNER word
+ * of the component with one no-return atomic max of the key, and ORs bit 17 + k (k = the component's place among the remotely commanded ones) into the target's remote
+ * inbox word.  k_apply_remote decodes the winner word, gathers the winner's words from its payload slot, writes them and zeroes the winner word.  No launch is added.
+ * Out of scope: several targets per binding and call, 1- and 2-byte words, values together with effects on one component, branch steps and retention. */
+typedef struct { uint32_t comp; uint32_t flags; } ggrs_value_binding;   /* value binding j: component `comp`; flags must be 0 */
+#define GGRS_VALUE_MAX_BINDINGS        4    /* per system */
+#define GGRS_VALUE_MAX_WORDS           8    /* staged words per system, all bindings together */
+#define GGRS_VALUE_MAX_WORLD_BINDINGS 16    /* per world */
+int ggrs_hip_add_custom_system_values(ggrs_world* w, const ggrs_custom_system_desc* desc,
+                                      const ggrs_peer_binding* peers, uint32_t n_peers,
+                                      const ggrs_effect_binding* effects, uint32_t n_effects,
+                                      const ggrs_command_binding* cmds, uint32_t n_cmds,
+                                      const ggrs_resource_binding* res, uint32_t n_res,
+                                      const ggrs_reduce_binding* red, uint32_t n_red,
+                                      const ggrs_remote_binding* rem, uint32_t n_rem,
+                                      const ggrs_sum_binding* sum, uint32_t n_sum,
+                                      const ggrs_value_binding* val, uint32_t n_val);
+
 /* ComponentSnapshotPlugin<S: Strategy> (snapshot/strategy.rs:22-40, component_snapshot.rs:42-63): what a snapshot HOLDS of a component is
  * S::Stored, produced by S::store and turned back by S::load / S::update -- CopyStrategy / CloneStrategy (Stored == the component, bitwise for
  * POD) are what ggrs_hip_register_component gives; this is the open door next to them: quantised, packed or partial snapshots.
@@ -902,7 +955,7 @@ int ggrs_hip_host_timeline(ggrs_world* w, int enable, double* us_out, uint64_t* 
  * Introspection: which kernel serves this world's request lists right now and why, what kind of arena
  * it lives on, whether the run-time compiler (libhiprtc.so, dlopen'ed) is available.  `key=value` lines,
  * NUL-terminated; *needed = bytes incl. the NUL, min(cap, *needed) are copied.  Keys: sealed, arena,
- * arena_bytes, hiprtc, generated_kernel, generated_kernel_origin, request_group_kernel, checksum_fold, kernarg_bytes, group_caps, specialised_kernel, slots_covered, row_versions, peer_view (worlds with peer bindings), effect_inbox (worlds with effect bindings), device_resources (worlds with device resources), depth_parallel_roles, reduce_inbox (worlds with reduce bindings: stripes, words, applies so far), remote_inbox (worlds with remote bindings: components, applies so far), sum_partials (worlds with sum bindings: units, words, applies so far).
+ * arena_bytes, hiprtc, generated_kernel, generated_kernel_origin, request_group_kernel, checksum_fold, kernarg_bytes, group_caps, specialised_kernel, slots_covered, row_versions, peer_view (worlds with peer bindings), effect_inbox (worlds with effect bindings), device_resources (worlds with device resources), depth_parallel_roles, reduce_inbox (worlds with reduce bindings: stripes, words, applies so far), remote_inbox (worlds with remote bindings: components, applies so far), sum_partials (worlds with sum bindings: units, words, applies so far), value_inbox (worlds with value bindings: components, bindings, bytes allocated, applies so far).
  * ------------------------------------------------------------------------------------------- */
 int ggrs_hip_world_kernel_info(ggrs_world* w, char* buf, uint64_t cap, uint64_t* needed);
 

@@ -154,6 +154,18 @@ pub struct ggrs_sum_binding {
 pub const GGRS_SUM_MAX_BINDINGS: usize = 4;
 pub const GGRS_SUM_MAX_WORDS: usize = 8;
 
+/// One value binding of `ggrs_hip_add_custom_system_values`: a component of OTHER entities an entity system inserts with ITS OWN words -- `e.val_u32(j, k)` .. are the
+/// staged words, `e.send_value(slot, j)` sends them; the last sender in schedule order wins, as one value, and a value wins over a default insert.  `flags` must be 0.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct ggrs_value_binding {
+    pub comp: u32,
+    pub flags: u32,
+}
+pub const GGRS_VALUE_MAX_BINDINGS: usize = 4;
+pub const GGRS_VALUE_MAX_WORDS: usize = 8;
+pub const GGRS_VALUE_MAX_WORLD_BINDINGS: usize = 16;
+
 /// One remote binding of `ggrs_hip_add_custom_system_remote`: a component of OTHER entities an entity system may insert (`e.send_insert(slot, j)`, the registered
 /// default) or remove (`e.send_remove(slot, j)`); `comp == GGRS_REMOTE_ENTITY` with `GGRS_REMOTE_DESPAWN` is `e.send_despawn(slot)`.  Every command of a frame
 /// lands at the end of the frame: despawn wins over everything, remove wins over insert.
@@ -291,6 +303,7 @@ unsafe extern "C" {
     pub fn ggrs_hip_add_custom_system_reduces(w: *mut ggrs_world, desc: *const ggrs_custom_system_desc, peers: *const ggrs_peer_binding, n_peers: u32, effects: *const ggrs_effect_binding, n_effects: u32, cmds: *const ggrs_command_binding, n_cmds: u32, res: *const ggrs_resource_binding, n_res: u32, red: *const ggrs_reduce_binding, n_red: u32) -> c_int;
     pub fn ggrs_hip_add_custom_system_remote(w: *mut ggrs_world, desc: *const ggrs_custom_system_desc, peers: *const ggrs_peer_binding, n_peers: u32, effects: *const ggrs_effect_binding, n_effects: u32, cmds: *const ggrs_command_binding, n_cmds: u32, res: *const ggrs_resource_binding, n_res: u32, red: *const ggrs_reduce_binding, n_red: u32, rem: *const ggrs_remote_binding, n_rem: u32) -> c_int;
     pub fn ggrs_hip_add_custom_system_sums(w: *mut ggrs_world, desc: *const ggrs_custom_system_desc, peers: *const ggrs_peer_binding, n_peers: u32, effects: *const ggrs_effect_binding, n_effects: u32, cmds: *const ggrs_command_binding, n_cmds: u32, res: *const ggrs_resource_binding, n_res: u32, red: *const ggrs_reduce_binding, n_red: u32, rem: *const ggrs_remote_binding, n_rem: u32, sum: *const ggrs_sum_binding, n_sum: u32) -> c_int;
+    pub fn ggrs_hip_add_custom_system_values(w: *mut ggrs_world, desc: *const ggrs_custom_system_desc, peers: *const ggrs_peer_binding, n_peers: u32, effects: *const ggrs_effect_binding, n_effects: u32, cmds: *const ggrs_command_binding, n_cmds: u32, res: *const ggrs_resource_binding, n_res: u32, red: *const ggrs_reduce_binding, n_red: u32, rem: *const ggrs_remote_binding, n_rem: u32, sum: *const ggrs_sum_binding, n_sum: u32, val: *const ggrs_value_binding, n_val: u32) -> c_int;
     pub fn ggrs_hip_register_resource(w: *mut ggrs_world, name: *const c_char, word_bytes: u32, n_words: u32, init_words: *const c_void, res_id_out: *mut u32) -> c_int;
     pub fn ggrs_hip_checksum_resource(w: *mut ggrs_world, res_id: u32, word_idx: *const u32, n_words: u32) -> c_int;
     pub fn ggrs_hip_add_resource_system(w: *mut ggrs_world, desc: *const ggrs_resource_system_desc) -> c_int;
