@@ -1,0 +1,282 @@
+"""The skirmish world (skirmish_common.py: seven binding kinds in one system) and the brand world (remote_values_common.py: value bindings) as scenarios of the
+request fuzzer (fuzz_util.run(scenario=...)), and the oracle side of both as ONE backend object: an OracleWorld, the SumModel beside it for the skirmish, walked
+request by request the way reduces_common.run_model walks a scripted list.
+
+What the scripted sessions of these worlds never send and the fuzzer does: lists in any order, one frame loaded and advanced many times inside one list, a frame
+re-advanced with another input, Saves that evict their own source, ConfirmedFrameCount and the depth moving between lists, host edits between lists and BEHIND lists
+that are still in flight (enqueue_requests / collect_checksums).  Every AdvanceWorld of these worlds is a launch of its own with a peer-view publish ahead of it and up
+to four apply launches behind it: a Load in the middle of a list, a re-advance or an edit behind a list in flight is where yesterday's inbox or peer view would show.
+
+ANY component is removed and inserted by the host, Target and Hp included.  The oracle's apply callbacks are therefore not registered as systems here (a system runs
+only for entities that have its bound components: an entity without Target would take no remote command on the oracle and every one on the device); the adapter
+lands them by host calls behind every AdvanceFrame, for every entity alive at the end of the frame (build_skirmish / build_brand host_apply=True, w.land()).  On
+streams that never remove Target the two ways give the same bits.
+
+What the scenarios keep away from, because the ORACLE cannot say what is right there (each is a limit of the model, not of the library):
+  * despawn_rollback: these worlds do not defer despawns.
+  * Words written into Pos are finite floats of moderate size (sums_common.flock_xy), never random bits: the sum of a NaN or of +-inf is outside what the model
+    pins -- which NaN payload an add propagates differs between the host's and the device's arithmetic.  Energy is written as a finite double for the same reason.
+(A helper module, no tests of its own.)"""
+import hashlib
+
+import numpy as np
+
+import bevy_ggrs_amd as bg
+import fuzz_util
+import reduces_common as rd
+import remote_values_common as rv
+import skirmish_common as sk
+import sums_common as sums
+from oracle.binding import FLAT, REFSHAPED, OracleWorld
+
+U32, U64, F32 = np.uint32, np.uint64, np.float32
+SIZES = (1, 2, 63, 64, 65, 257, 1025)
+RUN_KW = {"n_lists": 20, "ring_sweep": True}
+EDITS = ("despawn", "insert_component", "remove_component", "upload_word", "resource_write")
+
+
+# ---- the oracle side ---------------------------------------------------------------------------------------------------------------------------------------------
+class OracleAdapter:
+    """An OracleWorld (+ the resource model of the skirmish) behind the surface fuzz_util.run drives.  Everything but handle_requests, resource_write and close is the
+    oracle's own.  handle_requests walks the list request by request (w.land() behind an AdvanceFrame, w.on_load() behind a Load): the model snapshots on Save, restores on Load, runs the resource system in front of an
+    AdvanceFrame and lands the frame's reductions and sums behind it; a Save's checksum is the oracle's XOR the model's resource parts.  begin_frame (the hook the
+    build functions hand out) is called before EVERY AdvanceFrame -- hook=False leaves it out: what the hazard tests compare with."""
+
+    def __init__(self, oracle, model=None, stats=None, hook=True, host_apply=True):
+        self.__dict__.update(oracle=oracle, model=model, stats=stats, hook=hook, host_apply=host_apply)
+
+    def __getattr__(self, k): return getattr(self.oracle, k)
+
+    def handle_requests(self, reqs):
+        o, model, out = self.oracle, self.model, []
+        for r in reqs:
+            adv = isinstance(r, bg.AdvanceFrame)
+            if model is not None:
+                if isinstance(r, bg.SaveGameState): model.save(r.frame)
+                elif isinstance(r, bg.LoadGameState): model.load(r.frame)
+                else: model.begin(int(r.inputs[0]) if len(r.inputs) else 0)
+            if adv and self.hook: o.begin_frame()
+            cs = o.handle_requests([r])
+            if adv and self.host_apply: o.land()
+            if isinstance(r, bg.LoadGameState): o.on_load()
+            if adv and model is not None: model.end()
+            if isinstance(r, bg.SaveGameState): out.append(cs[0] ^ (model.part() if model is not None else 0))
+        return out
+
+    def resource_write(self, res, words):
+        self.model.cur[res] = [int(x) for x in words]
+
+    def close(self): self.oracle.close()
+
+
+class InFlight:
+    """A backend with the library's enqueue / collect pair around an adapter: the fuzzer then draws the stream it draws for the HIP backend.  Counts the enqueued lists
+    that saw a host edit (EDITS) behind them before they were collected."""
+
+    def __init__(self, w): self.__dict__.update(_w=w, _q=[], edited_in_flight=0)
+
+    def __getattr__(self, k):
+        v = getattr(self._w, k)
+        if k not in EDITS: return v
+
+        def edit(*a, **kw):                                                     # counted when CALLED, not when looked up
+            for e in self._q:
+                if not e[1]: e[1] = True; self.__dict__["edited_in_flight"] += 1
+            return v(*a, **kw)
+        return edit
+
+    def enqueue_requests(self, reqs): self._q.append([list(self._w.handle_requests(reqs)), False])
+
+    def collect_checksums(self): return self._q.pop(0)[0]
+
+
+# ---- the scenarios -----------------------------------------------------------------------------------------------------------------------------------------------
+class _UserScenario:
+    spawn_fn, no_despawn_rollback = None, True
+
+    def _common(self, tag, seed, n):
+        r = self.rng = np.random.default_rng([tag, seed])
+        self.seed = seed
+        drawn = int(r.choice(SIZES))
+        self.n = drawn if n is None else n                                   # (a pinned size: every draw is made as usual)
+        self.depth = int(r.integers(1, 9))
+        self.capacity = self.n + 128
+
+    def _finish(self, world, ids):
+        self.ids = tuple(ids)
+        world.set_depth(self.depth)
+        if hasattr(world, "set_synctest_check_distance"): world.set_synctest_check_distance(-1)      # ConfirmedFrameCount is set explicitly on both backends
+        return self.ids
+
+    def _col(self, comp, k, m):
+        kind = self.cols[comp][k]
+        r = self.rng
+        if kind == "x": return sums.flock_xy(int(r.integers(0, 1 << 20)), m)[0].view(U32)
+        if kind == "y": return sums.flock_xy(int(r.integers(0, 1 << 20)), m)[1].view(U32)
+        if kind == "link": return r.integers(0, self.n + 16, m).astype(U64)               # mostly another entity, sometimes a child's slot or nobody's
+        if kind == "u64": return r.integers(0, 2**64, m, dtype=U64)
+        if kind == "u32": return r.integers(0, 2**32, m, dtype=np.uint64).astype(U32)
+        lo, hi = kind
+        return r.integers(lo, hi, m).astype(U32)
+
+    def words(self, comp, word, count):
+        c = self.ids.index(comp)
+        if word is not None: return self._col(c, word, count)
+        return np.array([self._col(c, k, 1)[0] for k in range(len(self.cols[c]))])
+
+    def spawns(self, q): return bool(q.spawn_count)
+
+
+class SkirmishScenario(_UserScenario):
+    """skirmish_common.build_skirmish of `kinds` under random request lists.  n from SIZES (or pinned), depth 1..8, capacity n + 128; every AdvanceFrame carries a
+    drawn input byte 0..15 and dt explicitly; fuses of 8 .. 200 frames (40 .. 232 in a world of one or two) instead of 4 .. 48, so that a session that reaches
+    frame 47 still has most of its world -- remote despawns (one sender in 61 per frame) and the strikers' own go on thinning it.  with_spawn: an `A*` AdvanceFrame
+    carries five children (skirmish_common.children with period 1: whenever the generator says so); 24 of them fit the capacity.
+    Host edits: the generator's (despawn, remove / insert, upload_word, with the words of `cols`) and two of its own: resource_write of Energy on the library and on
+    the model alike, and an upload of Armor -- the one peer column -- so that the peer view's content changes between lists.  Pos and Energy only ever get finite
+    values (the module's docstring)."""
+    #        Pos         Target     Armor     Hp        Score     Stun {ticks, seed}   Shield    Fuse
+    cols = (("x", "y"), ("link",), ("u32",), ("u32",), ("u64",), ((0, 9), "u32"), ("u64",), ((1, 200),))
+
+    def __init__(self, seed, kinds=sk.ALL, with_spawn=False, n=None):
+        self._common(0x5C1A, seed, n)
+        self.kinds, self.with_spawn = frozenset(kinds), with_spawn
+        self.spawn_budget = 24 if with_spawn else 0
+        i = np.arange(self.n)
+        self.fuse = ((40 if self.n <= 2 else 8) + (i * 7) % 193).astype(U32)
+
+    def describe(self):
+        return f"skirmish seed {self.seed}: n={self.n} kinds={sk.subset_id(self.kinds)} spawn={self.with_spawn} depth={self.depth}"
+
+    def oracle(self, mode, hook=True, host_apply=True):
+        return OracleAdapter(OracleWorld(self.capacity, 8, mode), sk.skirmish_model(self.kinds, self.capacity), sk.Stats(), hook, host_apply)
+
+    def build(self, world):
+        if hasattr(world, "oracle"): ids = sk.build_skirmish(world.oracle, self.kinds, with_spawn=self.with_spawn, model=world.model, st=world.stats, host_apply=world.host_apply)
+        else: ids = sk.build_skirmish(world, self.kinds, with_spawn=self.with_spawn)
+        sk.spawn_skirmish(world, ids, self.n, fuse=self.fuse)
+        return self._finish(world, ids)
+
+    def advance(self, frame, spawn):
+        a = bg.AdvanceFrame((int(self.rng.integers(0, 16)),), dt_bits=rd.DT_BITS)
+        if spawn: a.spawn_count, a.spawn_payload = sk.children(frame, self.n, period=1)
+        return a
+
+    def extra_edit(self, x, A, B, ids):
+        r, n = self.rng, A.len
+        if x < 0.78:
+            bits = sums.f64_bits(float(r.uniform(-1.0e6, 1.0e6)))
+            A.resource_write(sk.ENERGY, [bits]); B.resource_write(sk.ENERGY, [bits])
+            return f"Energy={bits:#x}"
+        if x < 0.88 and n:
+            first = int(r.integers(0, n)); cnt = int(r.integers(1, min(n - first, 700) + 1))
+            data = self._col(2, 0, cnt)
+            A.upload_word(ids[2], 0, first, data); B.upload_word(ids[2], 0, first, data)
+            return f"upload Armor[{first}:{first + cnt}]"
+        return None
+
+    def extra_state(self, w):
+        return {"resources": w.model.words() if hasattr(w, "model") else sums.read_resources(w, 4)}
+
+
+class BrandScenario(_UserScenario):
+    """remote_values_common.build_brand under random request lists: the same sizes, inputs 0..2; `effects` is drawn per seed -- the world with the effect binding takes
+    the fused apply (k_apply_remote_effects), the one without it the remote-only apply."""
+    with_spawn, spawn_budget = False, 0
+    #        Hp        Target     Power     Burn {dps, ticks, source}   Mark
+    cols = (("u32",), ("link",), ("u32",), ("u32", (0, 9), "u32"), ("u64",))
+
+    def __init__(self, seed, n=None):
+        self._common(0xB4A2D, seed, n)
+        self.effects = bool(self.rng.random() < 0.5)
+
+    def describe(self):
+        return f"brand seed {self.seed}: n={self.n} effects={self.effects} depth={self.depth}"
+
+    def oracle(self, mode, hook=True, host_apply=True):
+        return OracleAdapter(OracleWorld(self.capacity, 8, mode), None, rv.Stats(), hook, host_apply)
+
+    def build(self, world):
+        if hasattr(world, "oracle"): ids = rv.build_brand(world.oracle, self.n, effects=self.effects, st=world.stats, host_apply=world.host_apply)
+        else: ids = rv.build_brand(world, self.n, effects=self.effects)
+        rv.spawn_brand(world, ids, self.n)
+        return self._finish(world, ids)
+
+    def advance(self, frame, spawn):
+        return bg.AdvanceFrame((int(self.rng.integers(0, 3)),))
+
+
+
+# ---- the committed seeds: (family, seed) -> scenario; the GPU tier and the CPU tier both read these ---------------------------------------------------------------
+def _subset_cases():
+    return [(kinds, 100 + 3 * j + t) for j, kinds in enumerate(sk.GPU_SUBSETS) for t in range(3)]
+
+
+SKIRMISH_SEEDS, SPAWN_SEEDS, BRAND_SEEDS, FORCED_SEEDS = range(40), range(200, 212), range(40), range(6)
+SUBSET_CASES = _subset_cases()
+# one pinned seed per family across the 8192-slot layout tile: (seed, n, n_lists), chosen so that the session holds at most 30 AdvanceFrames, a branch-shaped list and
+# a Load in the middle of a list (test_fuzz_user_worlds.py asserts it)
+TILE = {"skirmish": (9, 8300, 5), "brand": (0, 8262, 5)}
+
+
+def factory(family, kinds=sk.ALL, n=None):
+    if family == "brand": return lambda seed, big, max_n: BrandScenario(seed, n=n)
+    return lambda seed, big, max_n: SkirmishScenario(seed, kinds, with_spawn=(family == "spawn"), n=n)
+
+
+def run(family, seed, make_b, *, kinds=sk.ALL, n=None, hook=True, after_list=None, on_end=None, **kw):
+    """fuzz_util.run of one committed case with the FLAT adapter as backend A; returns (log, scenario, A's Stats)."""
+    seen = {}
+
+    def make_a(sc): seen["sc"] = sc; seen["A"] = sc.oracle(FLAT, hook); return seen["A"]
+
+    def extra(w): return seen["sc"].extra_state(w) if hasattr(seen["sc"], "extra_state") else {}
+    log = fuzz_util.run(seed, make_a, make_b, scenario=factory(family, kinds, n), extra_state=extra, after_list=after_list, on_end=on_end, **{**RUN_KW, **kw})
+    return log, seen["sc"], seen["A"].stats
+
+
+# ---- what a log shows --------------------------------------------------------------------------------------------------------------------------------------------
+def _lists(log):
+    """The log's request lists as token lists (edits, `confirmed=` and `depth=` lines left out)."""
+    out = []
+    for line in log[1:]:
+        toks = line.replace("(enqueued)", "").replace("(sweep)", "").split()
+        if toks and all(fuzz_util._TOK.match(t) for t in toks): out.append((toks, "(sweep)" in line))
+    return out
+
+
+def advances(log):
+    return sum(t[0] == "A" for toks, _ in _lists(log) for t in toks)
+
+
+def shapes(log):
+    """(lists with a Load that is not the first request, lists in which one frame is advanced twice, branch-shaped lists: opened by a Load and loading that one frame
+    twice at least), the ring sweep's lists left out.  The session starts at frame 0."""
+    mid = twice = branch = 0
+    F = 0
+    for toks, is_sweep in _lists(log):
+        seen, again, loads = set(), False, []
+        for i, t in enumerate(toks):
+            if t[0] == "L": F = int(t[1:]); loads.append((i, F))
+            elif t[0] == "A":
+                again |= F in seen; seen.add(F); F = fuzz_util.w32(F + 1)
+        if is_sweep: continue
+        mid += any(i > 0 for i, _ in loads); twice += again
+        branch += len(loads) >= 2 and loads[0][0] == 0 and all(f == loads[0][1] for _, f in loads)
+    return mid, twice, branch
+
+
+def digest(log):
+    return hashlib.sha256("\n".join(log).encode()).hexdigest()[:16]
+
+
+def cpu_pair(family, seed, **kw):
+    """The generator guard: the FLAT adapter against the REFSHAPED one behind InFlight -- the stream the HIP backend gets.  Returns what the floors are counted from."""
+    rec = {}
+
+    def make_b(sc): rec["B"] = InFlight(sc.oracle(REFSHAPED)); return rec["B"]
+
+    def after_list(A, B, k, ctx): rec["alive"], rec["len"] = int(A.alive_mask(A.len).sum()), A.len
+    log, sc, stats = run(family, seed, make_b, after_list=after_list, **kw)
+    rec.update(log=log, n=sc.n, stats=stats, edited_in_flight=rec.pop("B").edited_in_flight)
+    return rec

@@ -181,6 +181,7 @@ class BoxScenario:
 
 
 def _adv(sc, frame, spawn):
+    if hasattr(sc, "advance"): return sc.advance(frame, spawn)          # a foreign scenario (run(scenario=...)) supplies its own AdvanceFrame
     if isinstance(sc, BoxScenario): return bg.AdvanceFrame(sc.inputs(frame))
     a = bg.AdvanceFrame((cm.INPUT_SPAWN if spawn else 0,))
     if spawn: a.spawn_vx, a.spawn_vy = sc.spawn_fn(frame)
@@ -269,9 +270,11 @@ def _mutate(sc, st, A, B, ids):
     if x < 0.45 and alive.size:
         s = int(r.choice(alive)); A.despawn(s); B.despawn(s)
         return f"despawn({s})"
-    if x < 0.5 and alive.size and hasattr(A, "despawn_rollback") and not isinstance(sc, Scenario) and not getattr(sc, "plain", False) and not getattr(sc, "player_rollback", False):
+    if (x < 0.5 and alive.size and hasattr(A, "despawn_rollback") and not isinstance(sc, Scenario) and not getattr(sc, "plain", False) and not getattr(sc, "player_rollback", False)
+            and not getattr(sc, "no_despawn_rollback", False)):
         s = int(r.choice(alive)); A.despawn_rollback(s); B.despawn_rollback(s)
         return f"despawn_rollback({s})"
+    # (a foreign scenario supplies the words -- words(comp, word, count): word None = the n_words of one entity, else `count` entities' word `word`)
     V = ids[1] if isinstance(sc, Scenario) else ids[int(r.integers(len(ids)))]
     _, wb, nw = A._comps[V]
     if x < 0.6 and alive.size:
@@ -282,6 +285,7 @@ def _mutate(sc, st, A, B, ids):
         w = r.integers(0, 2 ** (8 * wb), nw, dtype=np.uint64).astype(_DT[wb])
         if isinstance(sc, Scenario): w = cm.f32bits(np.array([r.uniform(-50, 50), r.uniform(-50, 50), 0.0], dtype=np.float32))
         if isinstance(sc, BoxScenario): w = _box_words(sc, r, wb, nw)
+        if hasattr(sc, "words"): w = sc.words(V, None, nw)
         A.insert_component(V, s, w); B.insert_component(V, s, w)
         return f"insert c{V}({s})"
     if x < 0.68:
@@ -289,26 +293,36 @@ def _mutate(sc, st, A, B, ids):
         data = r.integers(0, 2 ** (8 * wb), cnt, dtype=np.uint64).astype(_DT[wb])
         if isinstance(sc, Scenario): data = cm.f32bits(r.uniform(-100, 100, cnt).astype(np.float32))
         if isinstance(sc, BoxScenario): data = _box_words(sc, r, wb, cnt)
+        if hasattr(sc, "words"): data = sc.words(V, k, cnt)
         A.upload_word(V, k, first, data); B.upload_word(V, k, first, data)
         return f"upload c{V}w{k}[{first}:{first + cnt}]"
+    if hasattr(sc, "extra_edit"): return sc.extra_edit(x, A, B, ids)      # edits only a foreign scenario knows (a resource write); x in [0.68, 1)
     return None
 
 
-def _extra_state(w):
+def _extra_state(w, more=None):
     out = {}
     if hasattr(w, "disabled_mask"):
         out["disabled"] = w.disabled_mask(); out["despawned_frames"] = np.where(out["disabled"], w.despawned_frames(), 0)
+    if more is not None: out.update(more(w))
     return out
 
 
-def run(seed, make_a, make_b, n_lists=30, big=False, state_every=6, generic=False, max_n=None, box=False, start_frame=None, variant=None, ring_sweep=False, on_end=None):
+def run(seed, make_a, make_b, n_lists=30, big=False, state_every=6, generic=False, max_n=None, box=False, start_frame=None, variant=None, ring_sweep=False, on_end=None,
+        scenario=None, after_list=None, extra_state=None):
     """variant: keywords of the scenario (GenericScenario(plain=True), BoxScenario(player_rollback=True)).
     ring_sweep: once mid-session (after list n_lists // 2) and after the last list, every frame the ring holds at or above ConfirmedFrameCount is loaded,
     newest first (a rollback pops what is newer), by a list [LoadGameState(f)] of its own on both backends, and the WHOLE state is compared: what a ring slot
     holds is otherwise seen only if a later random list happens to load it.  The sweep draws nothing from sc.rng; the session goes on from the oldest swept frame,
     so the swept slots are saved over later.  Each Load is logged as a list `L<f>   (sweep)`.
-    on_end(A, B, log): called before the worlds are closed (a test reads the library's counters there)."""
-    sc = (BoxScenario if box else GenericScenario if generic else Scenario)(seed, big=big, max_n=max_n, **(variant or {}))
+    on_end(A, B, log): called before the worlds are closed (a test reads the library's counters there).
+    scenario: a factory (seed, big, max_n) -> scenario that replaces the three-way pick (tests/fuzz_user_worlds.py).  Such a scenario has what the three have (rng,
+    n, depth, capacity, with_spawn, spawn_budget, describe(), build(world)) and may have advance(frame, spawn), words(comp, word, count), extra_edit(x, A, B, ids), spawns(request) and no_despawn_rollback: see _adv, _mutate and the log line below.
+    after_list(A, B, k, ctx): called after a list was handled synchronously and after every drain that collected something -- never while a list is in flight.
+    extra_state(world) -> dict: merged into what is compared beside the component state, after lists and in the ring sweep.
+    With these three at their defaults the random draws are the ones made without them (test_the_streams_of_existing_seeds_did_not_move)."""
+    if scenario is not None: sc = scenario(seed, big, max_n)
+    else: sc = (BoxScenario if box else GenericScenario if generic else Scenario)(seed, big=big, max_n=max_n, **(variant or {}))
     A, B = make_a(sc), make_b(sc)
     log = [sc.describe()]
     try:
@@ -323,10 +337,12 @@ def run(seed, make_a, make_b, n_lists=30, big=False, state_every=6, generic=Fals
         pending = []
 
         def drain():
+            k0 = None
             while pending:
                 k0, want, ctx0 = pending.pop(0)
                 got = B.collect_checksums()
                 assert want == list(got), f"checksums of the enqueued list {k0} differ:\n{ctx0}\n{want}\n{got}"
+            if k0 is not None and after_list is not None: after_list(A, B, k0, "\n".join(log[:1] + log[-6:]))
 
         def sweep(when):
             drain()
@@ -339,7 +355,7 @@ def run(seed, make_a, make_b, n_lists=30, big=False, state_every=6, generic=Fals
                 assert list(ca) == list(cb) == [] and (A.frame, A.len, A.snapshot_count()) == (B.frame, B.len, B.snapshot_count()) == (f, A.len, A.snapshot_count()), \
                     f"frame / len / snapshots differ: {(A.frame, A.len, A.snapshot_count())} vs {(B.frame, B.len, B.snapshot_count())} (model frame {f}) in the {ctx}"
                 cm.assert_states_equal(cm.snapshot_state(A, ids), cm.snapshot_state(B, ids), ctx)
-                cm.assert_states_equal(_extra_state(A), _extra_state(B), "RollbackDespawned markers, " + ctx)
+                cm.assert_states_equal(_extra_state(A, extra_state), _extra_state(B, extra_state), "RollbackDespawned markers, " + ctx)
 
         for k in range(n_lists):
             if ring_sweep and k == n_lists // 2 + 1: sweep("mid-session")
@@ -348,7 +364,7 @@ def run(seed, make_a, make_b, n_lists=30, big=False, state_every=6, generic=Fals
             if m: log.append(m)
             reqs = _gen_list(sc, st)
             log.append(" ".join(("S%d" % q.frame) if isinstance(q, bg.SaveGameState) else ("L%d" % q.frame) if isinstance(q, bg.LoadGameState)
-                                else ("A*" if q.inputs[0] and not box else "A") for q in reqs))
+                                else ("A*" if (sc.spawns(q) if hasattr(sc, "spawns") else q.inputs[0] and not box) else "A") for q in reqs))
             ca = A.handle_requests(reqs)
             ctx = "\n".join(log[:1] + log[-6:])
             if use_async and sc.rng.random() < 0.4 and len(pending) < 3 and k != n_lists - 1:
@@ -361,9 +377,10 @@ def run(seed, make_a, make_b, n_lists=30, big=False, state_every=6, generic=Fals
             assert list(ca) == list(cb), f"checksums differ after list {k}:\n{ctx}\n{ca}\n{cb}"
             assert (A.frame, A.len, A.snapshot_count()) == (B.frame, B.len, B.snapshot_count()) == (st["F"], A.len, A.snapshot_count()), \
                 f"frame / len / snapshots differ after list {k}: {(A.frame, A.len, A.snapshot_count())} vs {(B.frame, B.len, B.snapshot_count())} (model frame {st['F']})\n{ctx}"
+            if after_list is not None: after_list(A, B, k, ctx)
             if k % state_every == state_every - 1 or k == n_lists - 1:
                 cm.assert_states_equal(cm.snapshot_state(A, ids), cm.snapshot_state(B, ids), f"after list {k}:\n{ctx}\n")
-                cm.assert_states_equal(_extra_state(A), _extra_state(B), f"RollbackDespawned markers after list {k}:\n{ctx}\n")
+                cm.assert_states_equal(_extra_state(A, extra_state), _extra_state(B, extra_state), f"RollbackDespawned markers after list {k}:\n{ctx}\n")
                 for f in (w32(st["F"] + d) for d in range(-10, 2)):
                     assert A.has_snapshot(f) == B.has_snapshot(f), f"has_snapshot({f}) differs after list {k}:\n{ctx}"
         if ring_sweep: sweep("after the last list")

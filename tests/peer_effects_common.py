@@ -100,6 +100,11 @@ class _Pass:
         self.slot, self.frame = slot, frame
         return new
 
+    def reset(self):
+        """The next call begins a pass whatever its slot and frame: begin() alone takes a second pass over the SAME frame that starts at a higher slot than the
+        first one ended at (`L5 A L5 A` with a host edit, or a Load, in between) for the first one's continuation."""
+        self.slot, self.frame = None, None
+
 
 class Effects:
     """What the striker's current pass sends: per effect column the combined value and the number of sends per target slot, for slots below n0 -- the len at the

@@ -138,6 +138,7 @@ def _countdown_fn(o, B):
             if c.ticks[slot] <= 1: o.remove_component(B, slot)
             else: o.upload_word(B, 1, slot, np.array([c.ticks[slot] - 1], dtype=U32))
         return [hp], 0
+    countdown.pass_ = c
     return countdown
 
 
@@ -145,9 +146,11 @@ def _f32_bits(x):
     return np.asarray(x, dtype=F32).view(U32)
 
 
-def build_brand(w, n, *, with_spawn=False, effects=False, values=True, st=None):
+def build_brand(w, n, *, with_spawn=False, effects=False, values=True, st=None, host_apply=False):
     """Registers the brand world on `w` (a library world or the oracle) for n entities at spawn; returns the component ids (Hp, Target, Power, Burn, Mark).
-    st: the oracle's Stats.  values=False (library worlds): torch and tagger use send_insert of the default only -- the parent's feature."""
+    st: the oracle's Stats.  values=False (library worlds): torch and tagger use send_insert of the default only -- the parent's feature.  host_apply (the oracle):
+    `apply` is NOT registered as a system -- it would run only for entities that have Target (and Hp) --; the driver calls w.land() behind every AdvanceFrame
+    instead, which runs it by host calls for every entity alive at the end of the frame, and lands the effect where the entity has Hp (tests/fuzz_user_worlds.py)."""
     H = w.register_component("Hp", 4, 1)
     T = w.register_component("Target", 8, 1)
     P = w.register_component("Power", 4, 1)
@@ -276,10 +279,35 @@ def build_brand(w, n, *, with_spawn=False, effects=False, values=True, st=None):
         def child(words, slot, k, f, payload):
             rec = np.frombuffer(bytes(payload[:CHILD_STRIDE]), dtype=CHILD_DT)[0]
             return [int(rec["hp"]), int(rec["target"]), int(rec["power"])]
-        w.add_custom_system(_countdown_fn(w, B), [(H, 0)])
+        countdown = _countdown_fn(w, B)
+
+        def begin_frame():
+            """For a driver that may advance one frame twice in a row, or advance a frame in which torch runs for nobody (tests/fuzz_user_worlds.py calls it before
+            every AdvanceFrame): every pass starts anew and the command record is empty -- `apply` applies nothing unless torch runs and computes this frame's."""
+            ps.reset(); countdown.pass_.reset()
+            cm_.n0 = 0
+        w.begin_frame = begin_frame
+
+        def on_load():
+            """Behind a LoadGameState: the previous pass belongs to another timeline, so what it sent out of range is not held against the next pass's len."""
+            cm_.pending = None
+        w.on_load = on_load
+
+        def land():
+            m = min(cm_.n0, w.len)
+            if not m: return                                                      # torch ran for nobody: nothing was sent
+            alive = w.alive_mask(m)
+            has_hp = w.present_mask(H, m); hp = w.download_word(H, 0, 0, m)
+            for slot in range(m):
+                if not alive[slot] or not cm_.any[slot]: continue
+                out, kill = apply([0, int(hp[slot])], slot, None)
+                if kill: w.despawn(slot)
+                elif effects and has_hp[slot]: w.upload_word(H, 0, slot, np.array([out[1]], dtype=U32))
+        w.land = land
+        w.add_custom_system(countdown, [(H, 0)])
         w.add_custom_system(torch, [(T, 0), (P, 0)], iparam=(n, 0))
         w.add_custom_system(tagger, [(T, 0), (P, 0)], iparam=(n, 0))
-        w.add_custom_system(apply, [(T, 0), (H, 0)] if effects else [(T, 0)])
+        if not host_apply: w.add_custom_system(apply, [(T, 0), (H, 0)] if effects else [(T, 0)])
         if with_spawn: w.add_spawn_system(child, bundle=(H, T, P), bindings=[(H, 0), (T, 0), (P, 0)], payload_stride=CHILD_STRIDE)
     else:
         w.add_custom_system(COUNTDOWN_SRC, [(H, 0)], name="countdown", commands=[(B, bg.CMD_REMOVE)])

@@ -178,10 +178,12 @@ class _Sent:
         self.pending = None                             # (frame, n0, out-of-range targets, one per command or effect sent there) of the previous pass
 
 
-def build_skirmish(w, kinds=ALL, *, with_spawn=False, bare_striker=False, fuse_first=False, model=None, st=None):
+def build_skirmish(w, kinds=ALL, *, with_spawn=False, bare_striker=False, fuse_first=False, model=None, st=None, host_apply=False):
     """Registers the skirmish world on `w` (a library world, or the oracle with its model); returns the component ids (Pos, Target, Armor, Hp, Score, Stun, Shield,
     Fuse).  bare_striker (a library world): the same world whose striker binds nothing but its own words -- the launch-count comparison.  fuse_first (a library world):
-    the fuse countdown registered first -- the order the peer rule refuses."""
+    the fuse countdown registered first -- the order the peer rule refuses.  host_apply (the oracle): the apply callbacks are NOT registered as systems -- a system
+    runs only for entities that have its bound component, so an entity without Target would take no remote command --; the driver calls w.land() behind every
+    AdvanceFrame instead, which runs the same callbacks by host calls for every entity alive at the end of the frame (tests/fuzz_user_worlds.py)."""
     kinds = frozenset(kinds)
     assert kinds <= ALL, kinds
     P = w.register_component("Pos", 4, 2); T = w.register_component("Target", 8, 1); A = w.register_component("Armor", 4, 1)
@@ -304,14 +306,47 @@ def build_skirmish(w, kinds=ALL, *, with_spawn=False, bare_striker=False, fuse_f
             return [(words[0] + sn.fx_val[j][slot]) & mask], 0
         return apply
 
+    def begin_frame():
+        """For a driver that may advance one frame twice in a row, or advance a frame in which the striker runs for nobody (tests/fuzz_user_worlds.py calls it
+        before every AdvanceFrame): every pass starts anew, and what the previous frame sent is forgotten -- nothing is applied unless the striker runs again."""
+        pc.reset(); ps.reset()
+        pc.removed, pc.frame_ = set(), None
+        sn.n0, sn.frame = 0, None
+    w.begin_frame = begin_frame
+
+    def on_load():
+        """Behind a LoadGameState: the previous pass belongs to another timeline, so what it sent out of range is not held against the next pass's len."""
+        sn.pending = None
+    w.on_load = on_load
+
+    def land():
+        """The applies by host calls, in the library's order: the remote apply for every entity alive at the end of the frame (whatever components it has), then one
+        effect apply per column for the entities alive after that which have the column."""
+        if sn.frame is None: return                                             # the striker ran for nobody: nothing was sent
+        class F: frame = sn.frame      # noqa: E701
+        n = min(sn.n0, w.len)
+        if "remote" in kinds:
+            alive = w.alive_mask(n)
+            for slot in range(n):
+                if alive[slot] and sn.any[slot] and apply_remote([], slot, F)[1]: w.despawn(slot)
+        if "effects" in kinds:
+            alive = w.alive_mask(n)
+            for j, (c, mask, dt) in enumerate(((H, M32, U32), (Sc, M64, U64))):
+                on = alive & w.present_mask(c, n)
+                col = w.download_word(c, 0, 0, n)
+                fn = make_apply(j, mask)
+                for slot in np.nonzero(on)[0].tolist():
+                    if sn.fx_cnt[slot]: w.upload_word(c, 0, slot, np.array([fn([int(col[slot])], slot, F)[0][0]], dtype=dt))
+    w.land = land
+
     def child(words, slot, k, f, payload):
         rec = np.frombuffer(bytes(payload[:CHILD_STRIDE]), dtype=CHILD_DT)[0]
         return [int(np.array([rec["x"]], dtype=F32).view(U32)[0]), int(np.array([rec["y"]], dtype=F32).view(U32)[0]), int(rec["target"]), int(rec["armor"]), int(rec["hp"])]
     w.add_custom_system(countdown, [(H, 0)])
     w.add_custom_system(strike, own)
     fuse()
-    if "remote" in kinds: w.add_custom_system(apply_remote, [(T, 0)])
-    if "effects" in kinds:
+    if "remote" in kinds and not host_apply: w.add_custom_system(apply_remote, [(T, 0)])
+    if "effects" in kinds and not host_apply:
         w.add_custom_system(make_apply(0, M32), [(H, 0)]); w.add_custom_system(make_apply(1, M64), [(Sc, 0)])
     if with_spawn: w.add_spawn_system(child, bundle=(P, T, A, H, Sc), bindings=child_binds, payload_stride=CHILD_STRIDE)
     return ids
@@ -323,21 +358,23 @@ def build_skirmish(w, kinds=ALL, *, with_spawn=False, bare_striker=False, fuse_f
 XY_FIRST = 13
 
 
-def spawn_skirmish(w, ids, n, *, links=None):
+def spawn_skirmish(w, ids, n, *, links=None, fuse=None):
     """n entities with everything but Stun; every fourth also has Shield (charges above 2^32).  Links: strike_links -- (i * 389 + 17) % n, every 13th at slot 0, every
-    10th out of range (n + 5: in the spawn variant that slot appears mid-session).  A fifth starts with Hp below the first damage: the ADD wraps."""
+    10th out of range (n + 5: in the spawn variant that slot appears mid-session).  A fifth starts with Hp below the first damage: the ADD wraps.
+    fuse: the n fuses, where 4 .. 48 frames (9 for a lone entity) are too short for the session."""
     P, T, A, H, Sc, S, SH, Fz = ids
     i = np.arange(n)
     x, y = sc.flock_xy(XY_FIRST, n)
-    fuse =(4 + (i * 7) % 45).astype(U32) if n > 1 else np.array([9], dtype=U32)
+    if fuse is None: fuse = (4 + (i * 7) % 45).astype(U32) if n > 1 else np.array([9], dtype=U32)
+    fuse = np.ascontiguousarray(fuse, dtype=U32)
     w.spawn(n, {P: [x.view(U32), y.view(U32)], T: [strike_links(n) if links is None else links], A: [((i * 5 + 2) % 13).astype(U32)],
                 H: [np.where(i % 5 == 1, i % 3, 300 + (i * 37 + 11) % 101).astype(U32)], Sc: [(i.astype(U64) << U64(33)) | U64(7)], Fz: [fuse]})
     for s in range(0, n, 4): w.insert_component(SH, s, np.array([0x300000000 + (s % 23)], dtype=U64))
 
 
-def children(frame, n0):
-    """The host side of the spawn system, a pure function of the frame: in every fourth frame five children that link to existing slots."""
-    if frame % 4 != 1: return 0, None
+def children(frame, n0, period=4):
+    """The host side of the spawn system, a pure function of the frame: in every fourth (`period`-th) frame five children that link to existing slots."""
+    if frame % period != 1 % period: return 0, None
     r = np.random.default_rng([6, frame])
     rec = np.zeros(5, dtype=CHILD_DT)
     xy = sc.order_values(10, 5000 + 10 * frame)
