@@ -887,6 +887,12 @@ static int enqueue_impl(ggrs_world* w, const ggrs_request* reqs, uint32_t n, con
         w->batch_ev = b.ev;
         rc = run(w, reqs, n, nullptr, b.first, false, nullptr);
         if (rc == GGRS_OK && bs) rc = run_branch_step(w, *bs, b.first + n_save_prefix, keep);
+        // a component under a Strategy: the live world the prefix left holds the component itself, the list form's closing LoadGameState(F) leaves load(store(x)),
+        // which a lossy Stored form makes another value -- the step ends with that LoadWorld (every other world: the two are the same bytes, nothing runs)
+        if (rc == GGRS_OK && bs && w->has_strategy) {
+            ggrs_request ld; memset(&ld, 0, sizeof ld); ld.kind = GGRS_REQ_LOAD; ld.frame = w->frame;
+            rc = run(w, &ld, 1, nullptr, b.first, false, nullptr);
+        }
         w->batch_ev = nullptr;
         if (rc) {
             w->event_pool.push_back(b.ev); (void)hipStreamSynchronize(w->stream);

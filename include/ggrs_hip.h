@@ -859,6 +859,7 @@ int  ggrs_hip_fanout_comm_info(ggrs_fanout* f, int* rank_out, int* size_out, int
  * without ~ 4 x n_branches x n_frames requests crossing the ABI: the library expands it, and ALL branches ride in ONE launch of the world's generated kernel whatever
  * their inputs and spawns are (one record per branch in device memory).  The branches are speculation, not history: they do not touch the world's ring or its
  * frame counters -- after the call the world is where the prefix left it (frame F, live world and newest snapshot = F), so no "settle" load is needed.
+ * (A world with a component under a Strategy ends the step with the LoadWorld of frame F: its live world is then what LoadGameState(F) leaves, load(store(x)).)
  * Checksum order of the step: the prefix's SaveGameStates, then branch 0's, branch 1's, ...  (what the request list above would have produced).
  *     inputs       [n_branches][n_frames][n_inputs x input_bytes]   predicted PlayerInputs of frame F+i of branch b
  *     status       [n_branches][n_frames][n_inputs] InputStatus bytes, or NULL (every input Confirmed, as for ggrs_request::status)

@@ -36,6 +36,26 @@ def test_full_stress_test_schema_matches_oracle(n, flags):
     if not flags: assert info["request_group_kernel"].startswith("ggrs_jit_tick"), info   # 1-byte words: never k_tick3
 
 
+def build_narrow(w, n, extra=None):
+    """The narrow-word world: u8 x 3, u16 x 2, u32, u64, every one checksummed at its own width.  extra(w, ids): further systems, before the first spawn."""
+    A = w.register_component("Bytes", 1, 3)
+    B = w.register_component("Shorts", 2, 2)
+    H = w.register_component("Health", 4, 1)
+    Q = w.register_component("Wide", 8, 1)
+    w.checksum_component(A, [2, 0, 1])                  # 3 bytes
+    w.checksum_component(B, [1, 0])                     # 4 bytes in two 2-byte writes
+    w.checksum_component(H, [0])
+    w.checksum_component(Q, [0])
+    w.add_system(bg.SYS_ADD_U32, comp=(H,), word=(0,), iparam=(7,))
+    if extra is not None: extra(w, (A, B, H, Q))
+    r = np.random.default_rng(11)
+    w.spawn(n, {A: [r.integers(0, 256, n, dtype=np.uint64).astype(np.uint8) for _ in range(3)],
+                B: [r.integers(0, 65536, n, dtype=np.uint64).astype(np.uint16) for _ in range(2)],
+                H: [r.integers(0, 2 ** 32, n, dtype=np.uint64).astype(np.uint32)],
+                Q: [r.integers(0, 2 ** 63, n, dtype=np.uint64)]})
+    return A, B, H, Q
+
+
 @pytest.mark.parametrize("flags", [0, bg.GGRS_WORLD_NO_GROUPS])
 @pytest.mark.parametrize("n", [777, 40_000, 600_000])
 def test_narrow_words_through_snapshots_and_the_hasher(n, flags):
@@ -44,20 +64,7 @@ def test_narrow_words_through_snapshots_and_the_hasher(n, flags):
     rng = np.random.default_rng(5)
     res = []
     for w in (bg.World(n, max_depth=6, flags=flags), OracleWorld(n, 6, FLAT)):
-        A = w.register_component("Bytes", 1, 3)
-        B = w.register_component("Shorts", 2, 2)
-        H = w.register_component("Health", 4, 1)
-        Q = w.register_component("Wide", 8, 1)
-        w.checksum_component(A, [2, 0, 1])                  # 3 bytes
-        w.checksum_component(B, [1, 0])                     # 4 bytes in two 2-byte writes
-        w.checksum_component(H, [0])
-        w.checksum_component(Q, [0])
-        w.add_system(bg.SYS_ADD_U32, comp=(H,), word=(0,), iparam=(7,))
-        r = np.random.default_rng(11)
-        w.spawn(n, {A: [r.integers(0, 256, n, dtype=np.uint64).astype(np.uint8) for _ in range(3)],
-                    B: [r.integers(0, 65536, n, dtype=np.uint64).astype(np.uint16) for _ in range(2)],
-                    H: [r.integers(0, 2 ** 32, n, dtype=np.uint64).astype(np.uint32)],
-                    Q: [r.integers(0, 2 ** 63, n, dtype=np.uint64)]})
+        A, B, H, Q = build_narrow(w, n)
         drv = cm.SyncTestDriver(w, 4, max_prediction=5)
         for t in range(7):
             drv.tick((0,))
@@ -103,27 +110,37 @@ def test_custom_hasher_source_equals_builtin_word_list(n):
     assert res[0] == res[1] == res[2]
 
 
+ODD_HASHER = ("__device__ ggrs_u64 ggrs_hash(const GgrsComponent& c) {\n"
+              "    GgrsHasher h; h.write_u32(c.u32(0) ^ (c.u32(1) * 3u)); h.write_u8(c.u8(3) & 1); h.write_u64((ggrs_u64)c.u16(2) << 7);\n"
+              "    return h.finish() ^ 0x55ull;\n}\n")
+
+
+def odd_hash(words: bytes, slot: int) -> int:
+    a, b, c2, d = struct.unpack("<IIII", words)        # four 4-byte words (u16 / u8 live in the low bytes of words 2 / 3)
+    h = OracleWorld.sea_hasher()
+    h.write(struct.pack("<I", (a ^ (b * 3)) & 0xFFFFFFFF)); h.write(bytes([d & 1])); h.write(struct.pack("<Q", (c2 & 0xFFFF) << 7))
+    return h.finish() ^ 0x55
+
+
+def build_odd_hasher(w, n, extra=None):
+    """One component of four u32 words under the hasher that no word list expresses.  extra(w, ids): further systems, before the first spawn."""
+    r = np.random.default_rng(3)
+    cols = [r.integers(0, 2 ** 32, n, dtype=np.uint64).astype(np.uint32) for _ in range(4)]
+    X = w.register_component("X", 4, 4)
+    w.add_system(bg.SYS_ADD_U32, comp=(X,), word=(1,), iparam=(5,))
+    if isinstance(w, bg.World): w.checksum_component_custom(X, ODD_HASHER)
+    else: w.checksum_component_custom(X, odd_hash)
+    if extra is not None: extra(w, (X,))
+    w.spawn(n, {X: cols})
+    return (X,)
+
+
 def test_custom_hasher_that_no_word_list_expresses():
     """fn(&T) -> u64 is arbitrary: fold two fields together, skip one, mix in a byte-wide flag.  Oracle side: a C-ABI callback."""
     n = 2_000
-    src = ("__device__ ggrs_u64 ggrs_hash(const GgrsComponent& c) {\n"
-           "    GgrsHasher h; h.write_u32(c.u32(0) ^ (c.u32(1) * 3u)); h.write_u8(c.u8(3) & 1); h.write_u64((ggrs_u64)c.u16(2) << 7);\n"
-           "    return h.finish() ^ 0x55ull;\n}\n")
-
-    def py_hash(words: bytes, slot: int) -> int:
-        a, b, c2, d = struct.unpack("<IIII", words)        # four 4-byte words (u16 / u8 live in the low bytes of words 2 / 3)
-        h = OracleWorld.sea_hasher()
-        h.write(struct.pack("<I", (a ^ (b * 3)) & 0xFFFFFFFF)); h.write(bytes([d & 1])); h.write(struct.pack("<Q", (c2 & 0xFFFF) << 7))
-        return h.finish() ^ 0x55
-    r = np.random.default_rng(3)
-    cols = [r.integers(0, 2 ** 32, n, dtype=np.uint64).astype(np.uint32) for _ in range(4)]
     res = []
     for w in (bg.World(n, max_depth=6), OracleWorld(n, 6, FLAT)):
-        X = w.register_component("X", 4, 4)
-        w.add_system(bg.SYS_ADD_U32, comp=(X,), word=(1,), iparam=(5,))
-        if isinstance(w, bg.World): w.checksum_component_custom(X, src)
-        else: w.checksum_component_custom(X, py_hash)
-        w.spawn(n, {X: cols})
+        build_odd_hasher(w, n)
         drv = cm.SyncTestDriver(w, 3, max_prediction=5)
         for _ in range(6): drv.tick((0,))
         res.append(drv.all_checksums)
