@@ -524,6 +524,8 @@ int ggrs_dbg_replace_token(const char* body, const char* tok, const char* val, c
 //                              streak (the fuzzer: tests/test_fuzz_requests.py), 1 = the default policy
 //   ggrs_dbg_set_spec_shapes   places in the table of group shapes / specialised kernels (default 16), so that a P2P session's eight rollback lengths
 //                              exercise the least-recently-used eviction (tests/test_gpu_gen_groups.py)
+//   ggrs_dbg_set_spec_resident 0 = a device-spawn world's resident form is told that the device does NOT hold its grid of any specialised copy (host_groups.hpp
+//                              jit_spec_fits), so the general kernel goes on running and kernel_info lists the copies under "failed"; -1 = the device is asked
 //   ggrs_dbg_set_value_tags    0 = no Save skips a column on its value tags, 1 = every world does, -1 = by size (the default: host_world.hpp VTAGS_MIN_BYTES);
 //                              before the world is sealed
 int ggrs_dbg_set_value_tags(ggrs_world* w, int mode) { if (!w || w->sealed) return -1; w->vtags_mode = mode; return 0; }
@@ -571,6 +573,7 @@ int64_t ggrs_dbg_value_winners(ggrs_world* w, uint32_t comp, void* out, uint64_t
     if (hipMemcpyAsync(out, d, std::min(cap, bytes), hipMemcpyDeviceToHost, w->stream) != hipSuccess || hipStreamSynchronize(w->stream) != hipSuccess) return -1;
     return (int64_t)bytes;
 }
+int ggrs_dbg_set_spec_resident(ggrs_world* w, int mode) { if (!w || (mode != -1 && mode != 0)) return -1; w->spec_resident = mode; return 0; }
 int ggrs_dbg_set_spec_shapes(ggrs_world* w, int n) { if (!w || n < 1 || n > 64) return -1; w->spec_shapes = n; return 0; }
 int ggrs_hip_set_frame_rate(ggrs_world* w, uint64_t fps) { if (!w || fps == 0) return GGRS_E_INVALID; w->fps = fps; return GGRS_OK; }
 
@@ -1038,8 +1041,8 @@ int ggrs_hip_world_kernel_info(ggrs_world* w, char* buf, uint64_t cap, uint64_t*
         uint32_t n_ready = 0, n_building = 0, n_failed = 0; std::string why;
         for (auto& t : w->spec_tab) {
             const int st = t.spec ? t.spec->state.load(std::memory_order_acquire) : 0;
-            n_ready += st == 2; n_building += st == 1;
-            if (st == 3) { ++n_failed; why = t.spec->why; }
+            n_ready += st == 2 && t.spec->coop != 0; n_building += st == 1;
+            if (st == 3 || (st == 2 && t.spec->coop == 0)) { ++n_failed; why = t.spec->why; }     // (coop 0: built, but the device does not hold a device-spawn world's grid of it)
         }
         std::string v = !w->knobs.jit_specialise_after ? "off (GGRS_JIT_SPECIALISE_AFTER=0)"
                       : n_ready ? "ready (" + std::to_string(n_ready) + " of " + std::to_string(w->spec_tab.size()) + " group shapes seen run on kernels compiled for them" +

@@ -273,7 +273,9 @@ int launch_jit(ggrs_world* w, hipFunction_t fn, uint32_t gx, uint32_t gy, uint32
         else HIPCHK(w, hipModuleLaunchCooperativeKernel(fn, gx, gy, gz, TPB, 1, 1, lds, w->stream, params));
         if (w->prof) { HIPCHK(w, hipEventRecord(b, w->stream)); w->prof_events.push_back({a, b, GGRS_KERNEL_TICK}); }
         if (done) HIPCHK(w, hipEventRecord(done, w->stream));
-        w->len_stale = true;
+        // (sp_len[0] is written with the live world -- the kernel's `writes_live` --: a launch that only Saves the live block leaves that word as an EARLIER launch
+        // left it, 0 before the first, while the host's len may have moved since by ggrs_hip_spawn; the host's len stands then)
+        if ((!j.src_is_live || j.n_steps) && !j.skip_live) w->len_stale = true;
     } else if (!w->prof) {
         if (done) HIPCHK(w, hipExtModuleLaunchKernel(fn, gx * TPB, gy, gz, TPB, 1, 1, lds, w->stream, params, nullptr, nullptr, done, 0));
         else HIPCHK(w, hipModuleLaunchKernel(fn, gx, gy, gz, TPB, 1, 1, lds, w->stream, params, nullptr));
@@ -295,9 +297,25 @@ int launch_jit(ggrs_world* w, hipFunction_t fn, uint32_t gx, uint32_t gy, uint32
 // session has one, a P2P session one per rollback length; the row masks right after a spawn make a few more that never reach the threshold.
 // members: the launch carries batch members with records (run_branch_step) -- where a Save lands and which rows it moves are per member, so only the op sequence,
 // the load mask and the store policies are literals of that copy.
+// A device-spawn world's RESIDENT form is a cooperative launch that must be resident as a whole, and the world was sized against the GENERAL kernel's occupancy at
+// seal: a specialised copy is used only if the device holds the world's grid of that copy too -- asked once per copy, by seal's own rule (host_seal.hpp): the
+// occupancy query with the largest LDS a group of the world takes, bounded by the register files through the counts in the copy's code-object note
+// (resident_wgs_per_cu), or one workgroup per CU less than the query where the note cannot be read.  Otherwise the general kernel goes on running and kernel_info
+// lists the copy under "failed".  The streamed form is an ordinary launch: any copy will do.
+inline bool jit_spec_fits(ggrs_world* w, JitSpec* sp) {
+    if (!w->dev_spawn || jit_dev_stream(w)) return true;
+    if (sp->coop < 0) {
+        int per_cu = 0;
+        const bool ok = hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sp->fn, TPB, jit_lane_fold_bytes(w, w->cks_args.n_cks, w->cap_saves)) == hipSuccess;
+        if (!ok) (void)hipGetLastError();
+        per_cu = (sp->vgprs && sp->sgprs) ? std::min(per_cu, resident_wgs_per_cu(sp->vgprs, sp->sgprs)) : per_cu - 1;
+        sp->coop = ok && w->spec_resident != 0 && (uint64_t)std::max(per_cu, 0) * (uint64_t)w->n_cu >= jit_grid(w->sp_tiles) ? 1 : 0;
+        if (!sp->coop) sp->why = "the device does not hold the world's cooperative grid of this copy: the general kernel runs";
+    }
+    return sp->coop == 1;
+}
 hipFunction_t jit_spec_for(ggrs_world* w, const GgrsJitArgs& j, bool members = false) {
     if (!w->knobs.jit_specialise_after || w->jit_src.empty() || !j.n_saves || !j.n_ops) return nullptr;
-    if (w->dev_spawn) return nullptr;              // (a cooperative launch must be resident as a whole: the world was sized against the GENERAL kernel's occupancy at seal)
     // (a Save without a destination stores nothing -- the copy tests the destination at run time -- so only the stored ones must agree: deferred Saves)
     if (!members && !j.save_dst[0]) return nullptr;
     for (uint32_t k = 1; k < j.n_saves && !members; ++k)
@@ -321,7 +339,7 @@ hipFunction_t jit_spec_for(ggrs_world* w, const GgrsJitArgs& j, bool members = f
     }
     s->last_use = ++w->spec_clock;
     w->spec_last_slot = (int)(s - w->spec_tab.data());
-    if (s->spec) return s->spec->state.load(std::memory_order_acquire) == 2 ? s->spec->fn : nullptr;
+    if (s->spec) return s->spec->state.load(std::memory_order_acquire) == 2 && jit_spec_fits(w, s->spec) ? s->spec->fn : nullptr;
     if (++s->seen < (uint32_t)w->knobs.jit_specialise_after) return nullptr;
     if (w->spec_builds >= JIT_SPEC_MAX_BUILDS) return nullptr;
     for (auto& t : w->spec_tab) if (building(t)) return nullptr;                 // one build at a time; this shape asks again with its next group
@@ -332,7 +350,7 @@ hipFunction_t jit_spec_for(ggrs_world* w, const GgrsJitArgs& j, bool members = f
     s->spec->state.store(1, std::memory_order_relaxed);
     if (w->knobs.jit_specialise_sync) jit_spec_build(s->spec, w->device, src, w->knobs.jit_cache_dir, w->knobs.aot_dir, w->knobs.no_hiprtc);
     else { s->spec->th = std::thread(jit_spec_build, s->spec, w->device, src, w->knobs.jit_cache_dir, w->knobs.aot_dir, w->knobs.no_hiprtc); jit_spec_worker_register(s->spec); }
-    return s->spec->state.load(std::memory_order_acquire) == 2 ? s->spec->fn : nullptr;
+    return s->spec->state.load(std::memory_order_acquire) == 2 && jit_spec_fits(w, s->spec) ? s->spec->fn : nullptr;
 }
 
 inline ggrs_world::HostFold make_host_fold(const ggrs_world* w, const GgrsJitArgs& j, uint32_t res_slot, uint32_t rows, uint32_t n_cks, uint32_t members, uint64_t rows_off) {

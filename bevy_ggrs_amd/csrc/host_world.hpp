@@ -122,6 +122,8 @@ struct JitSig {
 struct JitSpec {
     JitSig sig; std::atomic<int> state{0};                // 1 building (worker thread), 2 ready, 3 failed
     hipModule_t mod = nullptr; hipFunction_t fn = nullptr; std::thread th; std::string why;
+    uint32_t vgprs = 0, sgprs = 0;                        // the copy's register counts, from its code object's note (0: not read)
+    int coop = -1;                                        // a device-spawn world's resident form: does the device hold the world's grid of THIS copy?  -1 not asked yet, 0 no, 1 yes
 };
 // One group shape the session has sent: how often, when last, and its kernel once it earned one.  A SyncTest session has one steady
 // shape; a P2P session has one per rollback length (0 .. max prediction) -- the table holds Knobs::jit_spec_shapes (16) of them, least recently
@@ -258,6 +260,7 @@ struct ggrs_world {
     // the kernel specialised for the group shapes the session keeps sending (kernel_gen.hpp jit_specialise): its text, the
     // shapes being counted and their kernels (built on a worker thread, one at a time; used once `state` says ready)
     std::string jit_src; std::vector<JitSpecSlot> spec_tab; uint64_t spec_clock = 0; uint32_t spec_builds = 0; int spec_last_slot = -1;
+    int spec_resident = -1;              // ggrs_dbg_set_spec_resident: -1 the device is asked whether it holds a device-spawn world's grid of a copy, 0 the answer is forced to no
     int spec_shapes = JIT_SPEC_SHAPES;   // places in spec_tab (a test hook shrinks it to exercise the eviction: ggrs_dbg_set_spec_shapes)
     JitEntry* jit_entry = nullptr;       // handed back to the module cache when the world is destroyed
     JitLayout* jl = nullptr;             // device-side layout of the argument block (owned)

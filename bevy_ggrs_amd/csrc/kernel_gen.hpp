@@ -2429,7 +2429,7 @@ void jit_spec_build(JitSpec* sp, int device, std::string src, std::string cache_
     auto done = [&](int st, const std::string& why) { sp->why = why; sp->state.store(st, std::memory_order_release); };
     if (hipSetDevice(device) != hipSuccess) return done(3, "hipSetDevice failed");
     std::string origin;
-    if (jit_load_cached(cache_dir, aot_knob, src, &sp->mod, &sp->fn, &origin)) return done(2, origin);
+    if (jit_load_cached(cache_dir, aot_knob, src, &sp->mod, &sp->fn, &origin, &sp->vgprs, &sp->sgprs)) return done(2, origin);
     sp->mod = nullptr; sp->fn = nullptr;
     Hiprtc& rtc = hiprtc();
     if (no_hiprtc || !rtc.lib) return done(3, no_hiprtc ? "no shipped code object for this shape, and the run-time compiler is treated as absent (GGRS_NO_HIPRTC=1)" : rtc.why);
@@ -2457,6 +2457,7 @@ void jit_spec_build(JitSpec* sp, int device, std::string src, std::string cache_
             return done(3, "the specialised kernel's code object does not load");
         }
     }
+    sp->vgprs = hsaco_note_uint(image, ".vgpr_count"); sp->sgprs = hsaco_note_uint(image, ".sgpr_count");
     const std::string path = jit_disk_path_in(cache_dir, src);
     if (!path.empty()) {
         const std::string tmp = path + ".tmp" + std::to_string((long long)getpid()) + "s";

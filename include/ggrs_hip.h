@@ -636,7 +636,8 @@ int ggrs_hip_set_input_layout(ggrs_world* w, uint32_t input_bytes, uint32_t max_
  * seal without it). */
 /* SPAWNS DECIDED ON THE DEVICE (payload_stride = GGRS_SPAWN_PAYLOAD_PARENT).  In the reference ANY GgrsSchedule system may `commands.spawn((.., Rollback))`, as many as
  * its data says -- a particle that splits, a bullet fired when an entity's own cooldown runs out (rollback.rs:45-59).  A user-written system (ggrs_hip_add_custom_system)
- * asks for it with   e.spawn(n)   (0 <= n <= 255 children of THIS entity in this frame; a later call for the same entity in the same frame replaces it).  After the
+ * asks for it with   e.spawn(n)   (children of THIS entity in this frame; n is clamped to 0 .. 255.  Inside one system call the last e.spawn counts; a call by a system
+ * registered LATER replaces an earlier system's call for the same entity in the same frame -- the count and the record -- only when its n is not 0).  After the
  * frame's systems ran -- where Bevy applies Commands -- the children take RollbackOrdered's next indices in the slot order of their parents (an exclusive scan over
  * wave, workgroup and grid inside the group's launch), so every rank and every replay numbers them alike; child k of a parent is built by the world's spawn system:
  *     ggrs_spawn(e, k, f, payload)   with payload = the parent's record: the 8 x ggrs_u64 bound words of the system that called e.spawn(n), as that call left them.
