@@ -164,6 +164,20 @@ ADOPT_RECOMPUTE, ADOPT_BROADCAST = 0, 1
 
 KERNEL_FORM_TILES, KERNEL_FORM_STEADY = 1, 3
 
+DIFF_LIVE = -(1 << 31)            # GGRS_DIFF_LIVE: as a frame, the live world
+DIFF_TRUST_VERSIONS = 1           # GGRS_DIFF_TRUST_VERSIONS
+
+
+class DiffEntry(C.Structure):
+    _fields_ = [("slot", C.c_uint64), ("alive_a", C.c_uint32), ("alive_b", C.c_uint32), ("presence_diff", C.c_uint64), ("column_diff", C.c_uint64),
+                ("first_comp", C.c_uint32), ("first_word", C.c_uint32), ("first_a", C.c_uint64), ("first_b", C.c_uint64)]
+
+
+class DiffReport(C.Structure):
+    _fields_ = [("len_a", C.c_uint64), ("len_b", C.c_uint64), ("n_entities", C.c_uint64), ("n_alive", C.c_uint64),
+                ("n_presence", C.c_uint64 * 64), ("n_value", C.c_uint64 * 64), ("resource_diff", C.c_uint64), ("n_entries", C.c_uint32)]
+
+
 # every symbol include/ggrs_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SIGNATURES = {
@@ -243,6 +257,9 @@ SIGNATURES = {
     "ggrs_hip_state_bytes": (C.c_uint64, [_P]),
     "ggrs_hip_live_state_ptr": (C.c_int, [_P, C.POINTER(_P)]),
     "ggrs_hip_adopt_live_state": (C.c_int, [_P]),
+    "ggrs_hip_snapshot_copy": (C.c_int, [_P, C.c_int32, _P]),
+    "ggrs_hip_diff_frames": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(DiffReport), C.POINTER(DiffEntry), C.c_uint32]),
+    "ggrs_hip_diff_block": (C.c_int, [_P, C.c_int32, _P, C.c_uint32, C.POINTER(DiffReport), C.POINTER(DiffEntry), C.c_uint32]),
     "ggrs_hip_fanout_unique_id": (C.c_int, [C.POINTER(C.c_uint8)]),
     "ggrs_hip_fanout_init": (C.c_int, [_P, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.POINTER(_P)]),
     "ggrs_hip_fanout_sync_confirmed": (C.c_int, [_P, C.c_int]),

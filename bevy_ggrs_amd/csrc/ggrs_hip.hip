@@ -129,6 +129,8 @@ void ggrs_hip_world_destroy(ggrs_world* w) {
     if (w->d_branch_marks) (void)hipFree(w->d_branch_marks);
     if (w->d_branch_gone) (void)hipFree(w->d_branch_gone);
     if (w->d_skip) (void)hipFree(w->d_skip);
+    if (w->d_diff) (void)hipFree(w->d_diff);
+    if (w->h_diff) (void)hipHostFree(w->h_diff);
     sp_release(w);
     peer_view_release(w);
     fx_inbox_release(w);
@@ -1028,6 +1030,157 @@ int ggrs_hip_adopt_live_state(ggrs_world* w) {
     return GGRS_OK;
 }
 
+// ---- STATE DIFF (include/ggrs_hip.h; the kernels: kernels.hpp k_diff_count / k_diff_scan / k_diff_emit) ------------------------------------------------------
+// Nothing here is on the tick's path: the generated kernel, its arguments and the request runner are untouched.  A side of the comparison is a packed block, the
+// len that cuts its masks, the row versions it holds (none for a foreign block) and which of its two resource cells is current.
+namespace {
+constexpr uint64_t DIFF_HOST_BYTES = 64u << 10;           // the pinned page a report comes back into: the counters and up to ~1150 entries
+struct DiffSide { const uint8_t* ptr = nullptr; uint64_t len = 0; const std::vector<ver_t>* ver = nullptr; uint32_t res_cell = 0; bool live_form = false; };
+// what every diff call does first: no uncollected batches, a sealed world with a device, RollbackOrdered::len known, every deferred Save in its slot
+int diff_ready(ggrs_world* w) {
+    if (!w->pending.empty()) return w->fail(GGRS_E_INVALID, "synchronous request while %zu enqueued batches are uncollected", w->pending.size());
+    int rc = seal(w); if (rc) return rc;
+    if (w->layout_only) return w->fail(GGRS_E_NO_DEVICE, "a layout-only world has no state to compare");
+    rc = len_sync(w); if (rc) return rc;
+    return materialise_slots(w);
+}
+int diff_side(ggrs_world* w, int32_t frame, DiffSide* s) {
+    if (frame == GGRS_DIFF_LIVE) {
+        const int rc = materialise_live(w); if (rc) return rc;
+        s->ptr = w->live.ptr; s->len = w->len; s->ver = &w->live.ver; s->res_cell = w->live.res_cell; s->live_form = true;
+        return GGRS_OK;
+    }
+    for (size_t k = 0; k < w->ring_frame.size(); ++k) if (w->ring_frame[k] == frame) {
+        const Block& b = w->slots[w->ring_slot[k]];
+        s->ptr = b.ptr; s->len = b.len; s->ver = &b.ver; s->res_cell = b.res_cell; s->live_form = false;
+        if (w->dev_spawn) {                                            // spawns decided on the device: the slot's len is what its Save wrote into the header
+            HIPCHK(w, hipMemcpyAsync(&s->len, b.ptr, 8, hipMemcpyDeviceToHost, w->stream));
+            HIPCHK(w, hipStreamSynchronize(w->stream));
+            if (s->len > w->capacity) s->len = w->capacity;
+        }
+        return GGRS_OK;
+    }
+    return w->fail(GGRS_E_NO_SNAPSHOT, "no snapshot of frame %d in the ring", frame);
+}
+int diff_run(ggrs_world* w, const DiffSide& A, const DiffSide& B, uint32_t flags, ggrs_diff_report* rep, ggrs_diff_entry* entries, uint32_t max_entries) {
+    if (!rep || (max_entries && !entries)) return w->fail(GGRS_E_INVALID, "bad diff arguments (no report, or max_entries without entries)");
+    if (flags & ~GGRS_DIFF_TRUST_VERSIONS) return w->fail(GGRS_E_INVALID, "unknown diff flags 0x%x", flags);
+    if (w->has_strategy && A.live_form != B.live_form)
+        return w->fail(GGRS_E_INVALID, "the live world against a snapshot in a world with a component under a Strategy: live form and Stored form are not comparable");
+    const bool trust = (flags & GGRS_DIFF_TRUST_VERSIONS) && A.ver && B.ver && w->knobs.row_versions;
+    DiffArgs a; memset(&a, 0, sizeof a);
+    a.a = A.ptr; a.b = B.ptr; a.len_a = A.len; a.len_b = B.len; a.off_alive = w->off_alive; a.ts = w->ts;
+    uint32_t nq = 0; uint64_t bytes_per_slot_cmp = 0;
+    for (uint32_t c = 0; c < w->comps.size(); ++c) {
+        const Comp& cc = w->comps[c];
+        if (cc.no_rollback) continue;                                  // outside every snapshot
+        const uint32_t j = a.n_comps++;
+        a.off_present[j] = w->off_present[c]; a.comp_id[j] = (uint8_t)c; a.comp_col0[j] = (uint8_t)nq;
+        const bool stored = cc.s_n_words && !A.live_form;              // ring-slot form holds Strategy::Stored
+        const uint32_t base = stored ? cc.scol_base : cc.col_base, nw = stored ? cc.s_n_words : cc.n_words, wb = stored ? cc.s_word_bytes : cc.word_bytes;
+        for (uint32_t k = 0; k < nw; ++k) {
+            const uint32_t col = base + k;
+            if (col >= (uint32_t)DIFF_MAX_COLS) return w->fail(GGRS_E_INVALID, "state diff serves worlds of at most %d columns (column_diff is one 64-bit word); component %s reaches column %u", DIFF_MAX_COLS, cc.name.c_str(), col);
+            if (trust && !stored && !w->col_ext[col] && (*A.ver)[col] != VER_NONE && (*A.ver)[col] == (*B.ver)[col]) continue;   // the same version of the column on both sides: the same bytes
+            a.col_off[nq] = w->col_off[col]; a.col_wb[nq] = (uint8_t)wb; a.col_k[nq] = (uint8_t)col; a.col_word[nq] = (uint8_t)k;
+            bytes_per_slot_cmp += wb; ++nq;
+        }
+        a.comp_ncols[j] = (uint8_t)(nq - a.comp_col0[j]);
+    }
+    a.n_res = (uint32_t)w->resources.size();
+    a.res_off_a = RES_CELL_OFF + A.res_cell * RES_CELL_BYTES; a.res_off_b = RES_CELL_OFF + B.res_cell * RES_CELL_BYTES;
+    for (uint32_t r = 0; r < a.n_res && r < GGRS_RESOURCE_MAX; ++r) {
+        const ggrs_world::Resource& rr = w->resources[r];
+        for (uint32_t i = rr.off / 4; i < (rr.off + rr.word_bytes * rr.n_words + 3) / 4 && i < 16; ++i) a.res_lanes[r] |= (uint16_t)(1u << i);
+    }
+    const uint64_t span = std::min<uint64_t>(std::max(A.len, B.len), w->cap_pad);
+    a.n_units = (uint32_t)((span + 63) / 64);
+    const uint64_t cap_e = std::min<uint64_t>(max_entries, (uint64_t)a.n_units * 64u);
+    a.max_entries = (uint32_t)cap_e;
+    // scratch: counters | entries | any word per unit | entry offset per unit  (counters and entries side by side: a short report comes back in ONE copy)
+    const uint64_t o_ent = (uint64_t)DIFF_CNT_WORDS * 8, o_any = align_up(o_ent + cap_e * sizeof(ggrs_diff_entry), ALIGN), o_off = o_any + align_up((uint64_t)a.n_units * 8, ALIGN);
+    const uint64_t need = o_off + align_up((uint64_t)a.n_units * 8, ALIGN);
+    static_assert((DIFF_CNT_WORDS * 8) % alignof(ggrs_diff_entry) == 0, "the entries sit right behind the counters");
+    if (!w->h_diff) HIPCHK(w, hipHostMalloc((void**)&w->h_diff, DIFF_HOST_BYTES, hipHostMallocDefault));      // pinned: the copy back is one DMA, no staging by the runtime
+    if (need > w->diff_bytes) {
+        HIPCHK(w, hipStreamSynchronize(w->stream));
+        if (w->d_diff) { (void)hipFree(w->d_diff); w->d_diff = nullptr; w->diff_bytes = 0; }
+        const uint64_t want = align_up(need + need / 2, 4096);
+        HIPCHK(w, hipMalloc((void**)&w->d_diff, want));
+        w->diff_bytes = want;
+    }
+    a.cnt = (uint64_t*)w->d_diff; a.unit_any = (uint64_t*)(w->d_diff + o_any); a.unit_off = (uint64_t*)(w->d_diff + o_off); a.entries = (ggrs_diff_entry*)(w->d_diff + o_ent);
+    const uint32_t by_size = std::max<uint32_t>(1, (a.n_units + TPB / 64 - 1) / (TPB / 64));
+    const uint32_t g = std::min<uint32_t>(by_size, w->diff_max_wgs ? w->diff_max_wgs : 4096u);
+    HIPCHK(w, hipMemsetAsync(a.cnt, 0, (size_t)DIFF_CNT_WORDS * 8, w->stream));
+    hipLaunchKernelGGL(k_diff_count, dim3(g), dim3(TPB), 0, w->stream, a);
+    HIPCHK(w, hipGetLastError());
+    if (cap_e) {
+        hipLaunchKernelGGL(k_diff_scan, dim3(1), dim3(TPB), 0, w->stream, (const uint64_t*)a.unit_any, a.unit_off, a.n_units);
+        HIPCHK(w, hipGetLastError());
+        hipLaunchKernelGGL(k_diff_emit, dim3(g), dim3(TPB), 0, w->stream, a);
+        HIPCHK(w, hipGetLastError());
+    }
+    // counters and, where they fit the pinned page, the entries' whole room in one copy; a longer list is fetched once its length is known
+    const bool one_copy = o_ent + cap_e * sizeof(ggrs_diff_entry) <= DIFF_HOST_BYTES;
+    HIPCHK(w, hipMemcpyAsync(w->h_diff, a.cnt, one_copy ? o_ent + cap_e * sizeof(ggrs_diff_entry) : o_ent, hipMemcpyDeviceToHost, w->stream));
+    HIPCHK(w, hipStreamSynchronize(w->stream));
+    const uint64_t* cnt = (const uint64_t*)w->h_diff;
+    memset(rep, 0, sizeof *rep);
+    rep->len_a = A.len; rep->len_b = B.len; rep->n_entities = cnt[DIFF_CNT_ENT]; rep->n_alive = cnt[DIFF_CNT_ALIVE];
+    for (uint32_t c = 0; c < 64; ++c) { rep->n_presence[c] = cnt[DIFF_CNT_PRES + c]; rep->n_value[c] = cnt[DIFF_CNT_VAL + c]; }
+    rep->resource_diff = cnt[DIFF_CNT_RES];
+    rep->n_entries = (uint32_t)std::min<uint64_t>(rep->n_entities, cap_e);
+    if (rep->n_entries && one_copy) memcpy(entries, w->h_diff + o_ent, (size_t)rep->n_entries * sizeof(ggrs_diff_entry));
+    else if (rep->n_entries) {
+        HIPCHK(w, hipMemcpyAsync(entries, a.entries, (size_t)rep->n_entries * sizeof(ggrs_diff_entry), hipMemcpyDeviceToHost, w->stream));
+        HIPCHK(w, hipStreamSynchronize(w->stream));
+    }
+    ++w->diff_calls; w->diff_last_cols = nq; w->diff_last_bps = (uint32_t)bytes_per_slot_cmp; w->diff_last_units = a.n_units;
+    return GGRS_OK;
+}
+}  // namespace
+//   ggrs_dbg_set_diff_grid     at most n workgroups per state-diff launch (0: by size): the report must not depend on it
+int ggrs_dbg_set_diff_grid(ggrs_world* w, int n) { if (!w || n < 0 || n > 65535) return -1; w->diff_max_wgs = (uint32_t)n; return 0; }
+int ggrs_hip_snapshot_copy(ggrs_world* w, int32_t frame, void* dst_dev) {
+    if (!w || !dst_dev) return GGRS_E_INVALID;
+    DeviceGuard dg(w);
+    int rc = diff_ready(w); if (rc) return rc;
+    if (frame == GGRS_DIFF_LIVE) return w->fail(GGRS_E_INVALID, "snapshot_copy copies a ring frame (the live block: ggrs_hip_live_state_ptr)");
+    DiffSide s; rc = diff_side(w, frame, &s); if (rc) return rc;
+    HIPCHK(w, hipMemcpyAsync(dst_dev, s.ptr, w->state_bytes, hipMemcpyDeviceToDevice, w->stream));
+    // the copy describes itself: RollbackOrdered::len and the current resource cell as the host knows them (what the Save's launch wrote)
+    const uint64_t len = s.len; const uint32_t cell = s.res_cell;
+    HIPCHK(w, hipMemcpyAsync(dst_dev, &len, 8, hipMemcpyHostToDevice, w->stream));
+    if (w->has_resources) HIPCHK(w, hipMemcpyAsync((uint8_t*)dst_dev + RES_CELL_IDX_OFF, &cell, 4, hipMemcpyHostToDevice, w->stream));
+    HIPCHK(w, hipStreamSynchronize(w->stream));
+    return GGRS_OK;
+}
+int ggrs_hip_diff_frames(ggrs_world* w, int32_t frame_a, int32_t frame_b, uint32_t flags, ggrs_diff_report* report, ggrs_diff_entry* entries, uint32_t max_entries) {
+    if (!w) return GGRS_E_INVALID;
+    DeviceGuard dg(w);
+    int rc = diff_ready(w); if (rc) return rc;
+    DiffSide A, B;
+    rc = diff_side(w, frame_a, &A); if (rc) return rc;
+    rc = diff_side(w, frame_b, &B); if (rc) return rc;
+    return diff_run(w, A, B, flags, report, entries, max_entries);
+}
+int ggrs_hip_diff_block(ggrs_world* w, int32_t frame_a, const void* block_b_dev, uint32_t flags, ggrs_diff_report* report, ggrs_diff_entry* entries, uint32_t max_entries) {
+    if (!w) return GGRS_E_INVALID;
+    if (!block_b_dev) return w->fail(GGRS_E_INVALID, "diff_block without a block");
+    if (flags & GGRS_DIFF_TRUST_VERSIONS) return w->fail(GGRS_E_INVALID, "GGRS_DIFF_TRUST_VERSIONS with a foreign block: it carries no row versions");
+    DeviceGuard dg(w);
+    int rc = diff_ready(w); if (rc) return rc;
+    DiffSide A, B;
+    rc = diff_side(w, frame_a, &A); if (rc) return rc;
+    struct { Header h; uint32_t res_cell; } hx;
+    HIPCHK(w, hipMemcpyAsync(&hx, block_b_dev, sizeof hx, hipMemcpyDeviceToHost, w->stream));
+    HIPCHK(w, hipStreamSynchronize(w->stream));
+    if (hx.h.len > w->capacity) return w->fail(GGRS_E_INVALID, "the block's header has len %llu > capacity %llu: not a block of this world", (unsigned long long)hx.h.len, (unsigned long long)w->capacity);
+    B.ptr = (const uint8_t*)block_b_dev; B.len = hx.h.len; B.ver = nullptr; B.res_cell = w->has_resources ? (hx.res_cell & 1u) : 0u; B.live_form = false;
+    return diff_run(w, A, B, flags, report, entries, max_entries);
+}
+
 // Which kernel serves this world's request lists right now, on what kind of arena, and the state of the run-time
 // compiler -- `key=value` lines (NUL-terminated, truncated to cap).  Nothing here is needed to USE the library: it is what an
 // operator reads when a world is slower than expected (e.g. libhiprtc.so missing from a deployment image).
@@ -1113,6 +1266,8 @@ int ggrs_hip_world_kernel_info(ggrs_world* w, char* buf, uint64_t cap, uint64_t*
                                                       std::to_string(w->spin_misses) + " fell back to the stream wait), else hipStreamSynchronize"
                                                     : "hipStreamSynchronize (GGRS_SPIN_WAIT_US=0)");
     add("slots_covered", std::to_string(cover));
+    if (w->diff_calls) add("state_diff", std::to_string(w->diff_calls) + " calls; the last one compared " + std::to_string(w->diff_last_cols) + " columns (" + std::to_string(w->diff_last_bps) +
+                                         " bytes per slot and side) and " + std::to_string(w->plan.n_masks) + " masks over " + std::to_string(w->diff_last_units) + " units of 64 slots");
     add("row_versions", w->knobs.row_versions ? "on" : "off (GGRS_ROW_VERSIONS=0)");
     add("value_tags", !w->sealed ? "unknown (not sealed)" : w->vtags ? "on: a Save skips the columns whose 64 values per unit the destination already holds (" + std::to_string(w->prof_skipped) + " bytes not stored in profiled launches; the ids' numbering has started over " + std::to_string(w->tag_wraps) + " times)"
                                  : "off (the world's steady Save moves less than " + std::to_string(VTAGS_MIN_BYTES >> 20) + " MB, or row versions are off)");

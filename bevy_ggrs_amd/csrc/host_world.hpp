@@ -427,6 +427,11 @@ struct ggrs_world {
     std::deque<PendingBatch> pending; uint32_t res_head = 0; uint32_t pending_results = 0;
     std::vector<hipEvent_t> event_pool;
 
+    // ---- state diff (ggrs_hip_diff_frames / ggrs_hip_diff_block): the scratch of its three launches -- per 64-slot unit an "any difference" word and an entry
+    // offset, the counters, the entries -- allocated at the first call, grown on demand, freed with the world.  diff_max_wgs: ggrs_dbg_set_diff_grid (0: by size)
+    uint8_t* d_diff = nullptr; uint8_t* h_diff = nullptr; uint64_t diff_bytes = 0; uint32_t diff_max_wgs = 0; uint64_t diff_calls = 0;
+    uint32_t diff_last_cols = 0, diff_last_bps = 0, diff_last_units = 0;      // what the last call compared (kernel_info "state_diff")
+
     // ---- profiling
     bool nt_copy = false;               // non-temporal loads/stores in k_copy_state (A/B knob)
     bool prof = false;

@@ -1042,4 +1042,155 @@ __global__ __launch_bounds__(TPB) void k_ff_fold(FfArgs f) {
     ff_fold_row(f.rows + (uint64_t)row * f.stride, f.istride, ck * per, min(f.g, (ck + 1u) * per), (row % f.nc1) == f.cnt_row, f.out + 2u * b, f.seq);
 }
 
+// ------------------------------------------------------------------ STATE DIFF (ggrs_hip_diff_frames / ggrs_hip_diff_block)
+// Where do two packed state blocks differ, under the world's own rules: a slot at or beyond a side's len is dead there, a slot dead on both sides holds no state, a
+// component absent on both sides holds no state, where the alive bits differ only that is said, words are compared as bits.  Three launches, ordered by their
+// boundaries alone (no compare-and-swap, no wait between workgroups):
+//   k_diff_count   one 64-slot unit per wave-iteration, one slot per lane.  The unit's alive word and presence words of both sides are wave-uniform loads; every
+//                  compared column is one coalesced tile-major load per side (col_at, the 8192-slot layout tiles), the inequality a __ballot masked by
+//                  "alive and present on both sides".  Per-component counts are popcounts of those ballots, summed per workgroup in LDS, one 64-bit atomic add
+//                  per non-zero counter and workgroup into the report (integer adds: order-free).  One u64 "any difference" ballot per unit is stored.
+//   k_diff_scan    one workgroup: the exclusive prefix sum of the units' popcounts = every unit's first entry.
+//   k_diff_emit    the non-zero units whose first entry is below max_entries are read again; a differing lane writes its entry at offset + (differing lanes
+//                  below it).  Units are in slot order and so are the lanes of one: the entries are the lowest differing slots, ascending, whatever the grid is.
+constexpr int DIFF_MAX_COLS = 64;                          // column_diff is one u64
+constexpr uint32_t DIFF_BATCH = 4;                         // columns of one component whose loads are issued together
+constexpr uint32_t DIFF_CNT_ENT = 0, DIFF_CNT_ALIVE = 1, DIFF_CNT_PRES = 2, DIFF_CNT_VAL = 2 + 64, DIFF_CNT_RES = 2 + 128, DIFF_CNT_WORDS = 2 + 128 + 1;
+struct DiffArgs {
+    const uint8_t* a; const uint8_t* b;
+    uint64_t len_a, len_b, off_alive;
+    uint64_t off_present[MAX_COMPS];                       // per COMPARED component j (rollback components, in id order)
+    uint64_t col_off[DIFF_MAX_COLS];                       // per compared column q (grouped by component, ascending column number)
+    uint64_t* unit_any; uint64_t* unit_off; uint64_t* cnt; ggrs_diff_entry* entries;
+    uint32_t ts, n_comps, n_units, max_entries;
+    uint32_t res_off_a, res_off_b, n_res;                  // the current resource cell of each side (byte offset inside the block)
+    uint16_t res_lanes[GGRS_RESOURCE_MAX];                 // bit i: the i-th u32 of a cell belongs to resource r
+    uint8_t comp_id[MAX_COMPS], comp_col0[MAX_COMPS], comp_ncols[MAX_COMPS];   // the world's component index; its first compared column q and how many
+    uint8_t col_wb[DIFF_MAX_COLS], col_k[DIFF_MAX_COLS], col_word[DIFF_MAX_COLS];   // word bytes; the world's column number (the bit of column_diff); the word inside its component
+};
+__device__ __forceinline__ uint64_t diff_len_mask(uint64_t len, uint64_t lo) { return len >= lo + 64u ? ~0ull : (len > lo ? (1ull << (len - lo)) - 1ull : 0ull); }
+__device__ __forceinline__ uint64_t diff_load(const uint8_t* p, uint32_t wb) {
+    switch (wb) {
+    case 8: return *reinterpret_cast<const uint64_t*>(p);
+    case 4: return *reinterpret_cast<const uint32_t*>(p);
+    case 2: return *reinterpret_cast<const uint16_t*>(p);
+    default: return *p;
+    }
+}
+struct DiffLane { uint64_t pres = 0, cols = 0, first_a = 0, first_b = 0; uint32_t first_comp = 0xFFFFFFFFu, first_word = 0xFFFFFFFFu; };
+// one unit.  Returns the unit's "any difference" ballot and its alive-differs ballot; EMIT: also this lane's entry fields; else the per-component counts go to s_cnt (LDS)
+template <bool EMIT> __device__ __forceinline__ uint64_t diff_unit(const DiffArgs& a, uint32_t u, uint32_t lane, unsigned long long* s_cnt, uint64_t* alive_x, uint64_t* alive_a, DiffLane* dl) {
+    const uint64_t lo = (uint64_t)u * 64u, e = lo + lane;
+    const uint64_t aa = *reinterpret_cast<const uint64_t*>(a.a + a.off_alive + (uint64_t)u * 8u) & diff_len_mask(a.len_a, lo);
+    const uint64_t ab = *reinterpret_cast<const uint64_t*>(a.b + a.off_alive + (uint64_t)u * 8u) & diff_len_mask(a.len_b, lo);
+    const uint64_t both = aa & ab;
+    uint64_t any = aa ^ ab;
+    *alive_x = any; *alive_a = aa;
+    for (uint32_t j = 0; j < a.n_comps; ++j) {
+        const uint64_t pa = *reinterpret_cast<const uint64_t*>(a.a + a.off_present[j] + (uint64_t)u * 8u);
+        const uint64_t pb = *reinterpret_cast<const uint64_t*>(a.b + a.off_present[j] + (uint64_t)u * 8u);
+        const uint64_t pd = (pa ^ pb) & both, common = pa & pb & both;
+        uint64_t vd = 0;
+        if (common) {                                                            // (wave-uniform: nobody has the component on both sides -> its columns are not read)
+            const uint32_t q1 = (uint32_t)a.comp_col0[j] + a.comp_ncols[j];
+            for (uint32_t q0 = a.comp_col0[j]; q0 < q1; q0 += DIFF_BATCH) {      // DIFF_BATCH columns' loads of both sides in flight before the first compare
+                uint64_t va[DIFF_BATCH], vb[DIFF_BATCH];
+#pragma unroll
+                for (uint32_t i = 0; i < DIFF_BATCH; ++i) {
+                    va[i] = 0; vb[i] = 0;
+                    if (q0 + i < q1) {                                           // (wave-uniform)
+                        const uint32_t wb = a.col_wb[q0 + i];
+                        const uint64_t off = col_at(a.col_off[q0 + i], a.ts, wb, e);   // e < the padded capacity: inside the column for every lane
+                        va[i] = diff_load(a.a + off, wb); vb[i] = diff_load(a.b + off, wb);
+                    }
+                }
+#pragma unroll
+                for (uint32_t i = 0; i < DIFF_BATCH; ++i) {
+                    const uint64_t ne = __ballot(va[i] != vb[i]) & common;       // (a column beyond the component's last: 0 != 0 for nobody)
+                    vd |= ne;
+                    if (EMIT && ((ne >> lane) & 1ull)) {
+                        if (!dl->cols) { dl->first_comp = a.comp_id[j]; dl->first_word = a.col_word[q0 + i]; dl->first_a = va[i]; dl->first_b = vb[i]; }
+                        dl->cols |= 1ull << a.col_k[q0 + i];
+                    }
+                }
+            }
+        }
+        if (EMIT) { if ((pd >> lane) & 1ull) dl->pres |= 1ull << a.comp_id[j]; }
+        else if (lane == 0) {
+            if (pd) atomicAdd(&s_cnt[DIFF_CNT_PRES + a.comp_id[j]], (unsigned long long)__popcll(pd));
+            if (vd) atomicAdd(&s_cnt[DIFF_CNT_VAL + a.comp_id[j]], (unsigned long long)__popcll(vd));
+        }
+        any |= pd | vd;
+    }
+    return any;
+}
+__global__ __launch_bounds__(TPB) void k_diff_count(DiffArgs a) {
+    __shared__ unsigned long long s_cnt[DIFF_CNT_RES];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
+    for (uint32_t i = tid; i < DIFF_CNT_RES; i += TPB) s_cnt[i] = 0;
+    __syncthreads();
+    for (uint32_t u = blockIdx.x * (TPB / 64) + wave; u < a.n_units; u += gridDim.x * (TPB / 64)) {
+        uint64_t ax, aa;
+        const uint64_t any = diff_unit<false>(a, u, lane, s_cnt, &ax, &aa, nullptr);
+        if (lane == 0) {
+            a.unit_any[u] = any;
+            if (any) atomicAdd(&s_cnt[DIFF_CNT_ENT], (unsigned long long)__popcll(any));
+            if (ax) atomicAdd(&s_cnt[DIFF_CNT_ALIVE], (unsigned long long)__popcll(ax));
+        }
+    }
+    // device resources: the current cell of each side, u32 by u32 (one wave of the launch; the word is zero before it and nobody else writes it)
+    if (blockIdx.x == 0 && wave == 0 && a.n_res) {
+        const uint32_t ra = lane < GGRS_RESOURCE_MAX_BYTES / 4 ? reinterpret_cast<const uint32_t*>(a.a + a.res_off_a)[lane] : 0u;
+        const uint32_t rb = lane < GGRS_RESOURCE_MAX_BYTES / 4 ? reinterpret_cast<const uint32_t*>(a.b + a.res_off_b)[lane] : 0u;
+        const uint64_t ne = __ballot(ra != rb);
+        if (lane == 0) {
+            uint64_t m = 0;
+            for (uint32_t r = 0; r < a.n_res; ++r) if (ne & a.res_lanes[r]) m |= 1ull << r;
+            a.cnt[DIFF_CNT_RES] = m;
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = tid; i < DIFF_CNT_RES; i += TPB) { const unsigned long long v = s_cnt[i]; if (v) atomicAdd(reinterpret_cast<unsigned long long*>(a.cnt) + i, v); }
+}
+__global__ __launch_bounds__(TPB) void k_diff_scan(const uint64_t* __restrict__ unit_any, uint64_t* __restrict__ unit_off, uint32_t n_units) {
+    __shared__ uint64_t s[TPB];
+    const uint32_t tid = threadIdx.x, per = (n_units + TPB - 1u) / TPB;
+    const uint32_t lo = min(n_units, tid * per), hi = min(n_units, lo + per);
+    uint64_t sum = 0;
+#pragma unroll 8
+    for (uint32_t i = lo; i < hi; ++i) sum += (uint64_t)__popcll(unit_any[i]);      // (a lane's words are consecutive: its loads are independent, eight in flight)
+    s[tid] = sum;
+    __syncthreads();
+    for (uint32_t o = 1; o < TPB; o <<= 1) {
+        const uint64_t v = tid >= o ? s[tid - o] : 0ull;
+        __syncthreads();
+        s[tid] += v;
+        __syncthreads();
+    }
+    uint64_t run = s[tid] - sum;
+#pragma unroll 8
+    for (uint32_t i = lo; i < hi; ++i) { unit_off[i] = run; run += (uint64_t)__popcll(unit_any[i]); }
+}
+__global__ __launch_bounds__(TPB) void k_diff_emit(DiffArgs a) {
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
+    for (uint32_t u = blockIdx.x * (TPB / 64) + wave; u < a.n_units; u += gridDim.x * (TPB / 64)) {
+        const uint64_t any = a.unit_any[u], off = a.unit_off[u];
+        if (!any || off >= a.max_entries) continue;                              // (wave-uniform)
+        DiffLane dl; uint64_t ax, aa;
+        (void)diff_unit<true>(a, u, lane, nullptr, &ax, &aa, &dl);
+        const uint64_t idx = off + (uint64_t)__popcll(any & ((1ull << lane) - 1ull));
+        if (((any >> lane) & 1ull) && idx < a.max_entries) {                     // (the lanes meet again before the next unit's ballots)
+            ggrs_diff_entry* o = a.entries + idx;
+            const uint32_t xa = (uint32_t)((aa >> lane) & 1ull);
+            o->slot = (uint64_t)u * 64u + lane;
+            o->alive_a = xa; o->alive_b = xa ^ (uint32_t)((ax >> lane) & 1ull);
+            o->presence_diff = dl.pres; o->column_diff = dl.cols;
+            o->first_comp = dl.first_comp; o->first_word = dl.first_word;
+            o->first_a = dl.first_a; o->first_b = dl.first_b;
+        }
+    }
+}
+
 }  // namespace ggrs

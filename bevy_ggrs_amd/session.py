@@ -11,6 +11,9 @@ Per tick at current frame F with check distance d (after warm-up, F > d):
     [Load(F-d), Adv, (Save(F-d+i), Adv) for i in 1..d-1, Save(F), Adv]
 i.e. 1 load, d saves, d+1 advances.  The first recorded checksum of each frame is kept and
 every later re-save of that frame must reproduce it, otherwise MismatchedChecksum.
+With localise=True the session also keeps the block of each frame's first Save and a
+mismatch carries, per mismatched frame, where the re-simulated frame differs from it
+(MismatchedChecksum.diffs: World.diff of the kept copy against the ring's frame).
 """
 from __future__ import annotations
 
@@ -24,11 +27,14 @@ class MismatchedChecksum(Exception):
     """GgrsError::MismatchedChecksum { current_frame, mismatched_frames } ->
     SyncTestMismatch event (src/lib.rs:133-139, schedule_systems.rs:104-115)."""
 
-    def __init__(self, current_frame: int, mismatched_frames: List[int]):
+    def __init__(self, current_frame: int, mismatched_frames: List[int], diffs: Optional[dict] = None):
         super().__init__(f"Detected checksum mismatch during rollback on frame {current_frame}, "
                          f"mismatched frames: {mismatched_frames}")
         self.current_frame = current_frame
         self.mismatched_frames = mismatched_frames
+        # SyncTestSession(localise=True) only: frame -> StateDiff of (the copy kept of the frame's first Save, the re-simulated frame in the ring)
+        if diffs is not None:
+            self.diffs = diffs
 
 
 @dataclass
@@ -41,7 +47,7 @@ class SyncTestSession:
     """SessionBuilder::start_synctest_session equivalent."""
 
     def __init__(self, num_players: int = 1, check_distance: int = 2, max_prediction: int = 8,
-                 input_delay: int = 0, allow_deep_check: bool = False):
+                 input_delay: int = 0, allow_deep_check: bool = False, localise: bool = False):
         # ggrs rejects check_distance >= max_prediction; the bench harness may lift that to
         # run BASELINE's "depth 8" directly (SURVEY.md section 8d).
         if check_distance >= max_prediction and not allow_deep_check:
@@ -57,6 +63,12 @@ class SyncTestSession:
         self._cells = [_Cell() for _ in range(max(max_prediction, check_distance) + 2)]
         self._checksum_history: Dict[int, Optional[int]] = {}
         self._last_saves: List[SaveGameState] = []
+        # localise: the first Save of each frame is also kept as a block (World.snapshot_copy) in a pool of check_distance + 1 buffers, and a mismatch
+        # says WHERE the re-simulated frame differs from it (MismatchedChecksum.diffs).  Off: no allocation, no extra call.
+        self.localise = localise
+        self._world = None
+        self._kept: Dict[int, object] = {}                  # frame -> block tensor of its first Save
+        self._pool: list = []                               # buffers not in use
 
     # -- API used by run_synctest (schedule_systems.rs:85-118)
     def max_prediction(self) -> int:
@@ -97,6 +109,9 @@ class SyncTestSession:
         if d > 0 and cur > d:
             mismatched = [f for f in range(cur - d, cur + 1) if not self._checksums_consistent(f)]
             if mismatched:
+                if self.localise and self._world is not None:
+                    raise MismatchedChecksum(cur, mismatched, {f: self._world.diff(self._kept[f], f) for f in mismatched
+                                                               if f in self._kept and self._world.has_snapshot(f)})
                 raise MismatchedChecksum(cur, mismatched)
             # adjust_gamestate: roll back d frames and resimulate
             frame_to = cur - d
@@ -124,10 +139,23 @@ class SyncTestSession:
             self._input_history.pop(k, None); self._pending.pop(k, None)
         return requests
 
-    def record_checksums(self, checksums: Sequence[int]):
+    def record_checksums(self, checksums: Sequence[int], world=None):
         """cell.save(frame, None, Some(checksum)) for each SaveGameState of the last
-        advance_frame(), in order (schedule_systems.rs:231-236)."""
+        advance_frame(), in order (schedule_systems.rs:231-236).  A session with localise=True also takes the `world` that ran the requests: the
+        frame saved for the first time is still the newest of its ring, and its block is kept."""
         assert len(checksums) == len(self._last_saves)
         for r, cs in zip(self._last_saves, checksums):
             c = self._cells[r.frame % len(self._cells)]
             c.frame, c.checksum = r.frame, cs
+        if self.localise:
+            if world is None:
+                raise ValueError("a session with localise=True records checksums with the world that ran the requests")
+            self._world = world
+            for r in self._last_saves:
+                if r.frame in self._kept or not world.has_snapshot(r.frame):
+                    continue                                # a re-save; or a frame the ring no longer holds
+                for f in [f for f in self._kept if f < self.current_frame - self.check_distance - 1]:
+                    self._pool.append(self._kept.pop(f))    # no longer compared: its buffer is free
+                if not self._pool and len(self._kept) >= self.check_distance + 1:
+                    self._pool.append(self._kept.pop(min(self._kept)))    # the pool never grows beyond check_distance + 1 buffers
+                self._kept[r.frame] = world.snapshot_copy(r.frame, out=self._pool.pop() if self._pool else None)

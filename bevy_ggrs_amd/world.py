@@ -6,7 +6,8 @@ HIP kernel launch inside libggrs_hip.so.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Iterable, Mapping, Optional, Sequence
+from dataclasses import dataclass, field, replace
+from typing import Dict, Iterable, List, Mapping, Optional, Sequence
 
 import numpy as np
 
@@ -17,6 +18,69 @@ from .requests import AdvanceFrame, LoadGameState, SaveGameState
 
 def _as_c(arr: np.ndarray):
     return arr.ctypes.data_as(C.c_void_p)
+
+
+LIVE = _ffi.DIFF_LIVE      # World.diff: as a frame, the live world
+_NO_WORD = 0xFFFFFFFF
+
+
+@dataclass
+class DiffEntry:
+    """One differing entity (ggrs_diff_entry) with the names of what differs."""
+    slot: int
+    alive_a: bool
+    alive_b: bool
+    presence_diff: List[int]            # component ids present on one side only
+    column_diff: List[int]              # the world's column numbers that differ bitwise
+    first_comp: Optional[int]           # the lowest differing column as (component, word), None when no word differs
+    first_word: Optional[int]
+    first_a: int
+    first_b: int
+    presence_names: List[str] = field(default_factory=list)
+    first_name: Optional[str] = None
+
+
+@dataclass
+class StateDiff:
+    """World.diff: where two world states differ (ggrs_diff_report + its entries).  Counts are exact whatever max_entries was; `entries` are the
+    differing entities with the lowest slots, ascending.  n_presence / n_value map a component id to the number of entities whose presence /
+    whose words differ (components that do not differ are left out); `names` maps a component id to its name."""
+    len_a: int
+    len_b: int
+    n_entities: int
+    n_alive: int
+    n_presence: Dict[int, int]
+    n_value: Dict[int, int]
+    resource_diff: List[int]
+    entries: List[DiffEntry]
+    names: Dict[int, str] = field(default_factory=dict)
+
+    def __bool__(self):
+        return bool(self.n_entities or self.resource_diff or self.len_a != self.len_b)
+
+    def swapped(self) -> "StateDiff":
+        """The same diff with sides A and B exchanged."""
+        es = [replace(e, alive_a=e.alive_b, alive_b=e.alive_a, first_a=e.first_b, first_b=e.first_a) for e in self.entries]
+        return replace(self, len_a=self.len_b, len_b=self.len_a, entries=es)
+
+    def __str__(self):
+        if not self:
+            return f"states equal (len {self.len_a})"
+        out = [f"{self.n_entities} entities differ (len {self.len_a} / {self.len_b}; {self.n_alive} alive on one side only)"]
+        for c in sorted(set(self.n_presence) | set(self.n_value)):
+            out.append(f"  {self.names.get(c, c)}: presence {self.n_presence.get(c, 0)}, value {self.n_value.get(c, 0)}")
+        if self.resource_diff:
+            out.append(f"  resources that differ: {self.resource_diff}")
+        for e in self.entries:
+            if e.alive_a != e.alive_b:
+                what = f"alive {int(e.alive_a)} / {int(e.alive_b)}"
+            else:
+                what = ", ".join(([f"presence {e.presence_names}"] if e.presence_diff else []) +
+                                 ([f"{e.first_name}[{e.first_word}] {e.first_a:#x} / {e.first_b:#x} (columns {e.column_diff})"] if e.column_diff else []))
+            out.append(f"  slot {e.slot}: {what}")
+        if self.n_entities > len(self.entries):
+            out.append(f"  ... {self.n_entities - len(self.entries)} more")
+        return "\n".join(out)
 
 
 class WorldBase:
@@ -295,6 +359,7 @@ class World(WorldBase):
         self._p = p
         self._comps = []
         self.capacity = capacity
+        self.device = device
 
     def add_custom_system(self, source: str, bindings: Sequence[tuple], iparam=(), fparam=(), name: str = "custom", peers: Sequence[tuple] = (), effects: Sequence[tuple] = (),
                           commands: Sequence[tuple] = (), resources: Sequence[tuple] = (), reduces: Sequence[tuple] = (), remote=None, sums=None, values=None):
@@ -556,6 +621,53 @@ class World(WorldBase):
 
     def state_bytes(self) -> int:
         return int(self._lib.ggrs_hip_state_bytes(self._p))
+
+    # ---- state diff (include/ggrs_hip.h: ggrs_hip_snapshot_copy / ggrs_hip_diff_frames / ggrs_hip_diff_block)
+    def snapshot_copy(self, frame: int, out=None):
+        """The complete packed block of ring frame `frame` as a torch.uint8 tensor of state_bytes() bytes on the world's device (ring-slot form: what
+        World.diff takes as `b`).  `out`: a tensor of that size to copy into instead of a new one."""
+        import torch
+        n = self.state_bytes()
+        if out is None:
+            out = torch.empty(n, dtype=torch.uint8, device=f"cuda:{self.device}")
+        elif out.dtype != torch.uint8 or out.numel() != n or not out.is_cuda or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous torch.uint8 device tensor of {n} bytes")
+        torch.cuda.current_stream(out.device).synchronize()       # (the copy runs on the world's stream)
+        self._check(self._lib.ggrs_hip_snapshot_copy(self._p, frame, out.data_ptr()))
+        return out
+
+    def diff(self, a, b, *, max_entries: int = 64, trust_versions: bool = False) -> StateDiff:
+        """Where do two world states differ?  `a`, `b`: a ring frame, LIVE, or (one of them) a block tensor from snapshot_copy.  Dead slots and absent
+        components hold no state; words are compared as bits; only rollback components and device resources count.  trust_versions skips the columns
+        whose row versions agree (not with a tensor).  Returns a StateDiff: exact counts and the max_entries lowest differing entities."""
+        a_is_block, b_is_block = hasattr(a, "data_ptr"), hasattr(b, "data_ptr")
+        if a_is_block and b_is_block:
+            raise ValueError("at most one side of a diff is a block tensor")
+        if a_is_block:
+            return self.diff(b, a, max_entries=max_entries, trust_versions=trust_versions).swapped()
+        rep = _ffi.DiffReport()
+        ents = (_ffi.DiffEntry * max(1, max_entries))()
+        flags = _ffi.DIFF_TRUST_VERSIONS if trust_versions else 0
+        if b_is_block:
+            import torch
+            if b.dtype != torch.uint8 or b.numel() != self.state_bytes() or not b.is_cuda or not b.is_contiguous():
+                raise ValueError(f"a block is a contiguous torch.uint8 device tensor of {self.state_bytes()} bytes")
+            torch.cuda.current_stream(b.device).synchronize()
+            self._check(self._lib.ggrs_hip_diff_block(self._p, int(a), b.data_ptr(), flags, C.byref(rep), ents if max_entries else None, max_entries))
+        else:
+            self._check(self._lib.ggrs_hip_diff_frames(self._p, int(a), int(b), flags, C.byref(rep), ents if max_entries else None, max_entries))
+        names = {c: nm for c, (nm, _, _) in enumerate(self._comps)}
+        bits = lambda m: [i for i in range(64) if (m >> i) & 1]
+        entries = []
+        for i in range(rep.n_entries):
+            e = ents[i]
+            has = e.first_comp != _NO_WORD
+            entries.append(DiffEntry(slot=int(e.slot), alive_a=bool(e.alive_a), alive_b=bool(e.alive_b), presence_diff=bits(e.presence_diff), column_diff=bits(e.column_diff),
+                                     first_comp=int(e.first_comp) if has else None, first_word=int(e.first_word) if has else None, first_a=int(e.first_a), first_b=int(e.first_b),
+                                     presence_names=[names.get(c, str(c)) for c in bits(e.presence_diff)], first_name=names.get(int(e.first_comp)) if has else None))
+        return StateDiff(len_a=int(rep.len_a), len_b=int(rep.len_b), n_entities=int(rep.n_entities), n_alive=int(rep.n_alive),
+                         n_presence={c: int(rep.n_presence[c]) for c in range(64) if rep.n_presence[c]}, n_value={c: int(rep.n_value[c]) for c in range(64) if rep.n_value[c]},
+                         resource_diff=bits(rep.resource_diff), entries=entries, names=names)
 
     def live_state_ptr(self) -> int:
         p = C.c_void_p()

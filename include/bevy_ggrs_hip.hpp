@@ -464,6 +464,22 @@ struct HipBackend {
     int download_alive(uint64_t* dst, uint64_t n) { return ggrs_hip_download_alive(w, dst, n); }
     int has_snapshot(int32_t f) { return ggrs_hip_has_snapshot(w, f); }
     uint64_t snapshot_count() { return ggrs_hip_snapshot_count(w); }
+    // state diff (include/ggrs_hip.h): where two world states differ -- what an observer of SyncTestMismatch calls to name the entities and the component.
+    // frame_a / frame_b: a ring frame or GGRS_DIFF_LIVE; block_b_dev: a block in ring-slot form (snapshot_copy, an adopt broadcast); entries may be empty (counts only)
+    uint64_t state_bytes() { return ggrs_hip_state_bytes(w); }
+    int snapshot_copy(int32_t frame, void* dst_dev) { return ggrs_hip_snapshot_copy(w, frame, dst_dev); }
+    int diff_frames(int32_t frame_a, int32_t frame_b, uint32_t flags, ggrs_diff_report* report, std::vector<ggrs_diff_entry>* entries = nullptr, uint32_t max_entries = 64) {
+        if (entries) entries->resize(max_entries);
+        const int rc = ggrs_hip_diff_frames(w, frame_a, frame_b, flags, report, entries && max_entries ? entries->data() : nullptr, entries ? max_entries : 0);
+        if (entries) entries->resize(rc == GGRS_OK ? report->n_entries : 0);
+        return rc;
+    }
+    int diff_block(int32_t frame_a, const void* block_b_dev, uint32_t flags, ggrs_diff_report* report, std::vector<ggrs_diff_entry>* entries = nullptr, uint32_t max_entries = 64) {
+        if (entries) entries->resize(max_entries);
+        const int rc = ggrs_hip_diff_block(w, frame_a, block_b_dev, flags, report, entries && max_entries ? entries->data() : nullptr, entries ? max_entries : 0);
+        if (entries) entries->resize(rc == GGRS_OK ? report->n_entries : 0);
+        return rc;
+    }
 };
 
 // ---------------------------------------------------------------- speculative fan-out (no reference analogue: SURVEY.md 8e)

@@ -929,6 +929,64 @@ int  ggrs_hip_fanout_adopt(ggrs_fanout* f, uint32_t branch, int32_t frame, uint3
                            uint64_t* checksums_out, uint32_t* n_checksums_out);
 
 /* -------------------------------------------------------------------------------------------
+ * STATE DIFF: where two world states differ.  Every check of the library ends in one Checksum(u128); when two of them disagree -- a
+ * SyncTestMismatch (src/lib.rs:133-139), a desync between peers -- these calls say which entities and which component.  Both states are
+ * complete packed blocks in device memory; three small launches compare them under the world's own rules and hand back a short, ordered report.
+ *
+ *   ggrs_hip_snapshot_copy   the complete packed block of ring frame `frame` (ggrs_hip_state_bytes bytes, ring-slot form) copied to dst_dev, device to device.
+ *   ggrs_hip_diff_frames     state A = frame_a, state B = frame_b; either may be GGRS_DIFF_LIVE, the live world.
+ *   ggrs_hip_diff_block      state A = frame_a, state B = a block in ring-slot form somewhere in device memory: what ggrs_hip_snapshot_copy or a
+ *                            GGRS_ADOPT_BROADCAST produces.  Its RollbackOrdered::len and current resource cell are read from its header.
+ *
+ * What is compared:
+ *   - slots [0, max(len_a, len_b)); a slot at or beyond a side's len is dead on that side;
+ *   - a slot dead on both sides never differs, whatever bytes lie under it; a component absent on both sides never differs;
+ *   - where the alive bits differ only alive_a / alive_b say so: no presence and no value bits for that entity;
+ *   - words are compared as bits: -0.0 != 0.0, NaN payloads count;
+ *   - rollback components only.  Value tags, row versions, header fields other than len, GGRS_COMP_NO_ROLLBACK components and RollbackDespawned
+ *     markers are not snapshot state and are never compared;
+ *   - device resources: the current cell of each side, word by word.
+ * entries (may be NULL with max_entries == 0) receives the max_entries differing entities with the lowest slots, in ascending slot order; the result
+ * does not depend on launch geometry and is the same from run to run.  The report's counts are exact whatever max_entries is.
+ * Column numbers (column_diff) are the world's: component c's word k is column (words of the components registered before c) + k; a component under a
+ * Strategy is compared in its Stored words (frame against frame), whose columns are numbered behind all component words, first_word counting Stored words.
+ * Both calls bring deferred Saves and a lazily skipped live block up to date first.  Errors: GGRS_E_INVALID while enqueued batches are uncollected (as the
+ * other synchronous calls), for GGRS_DIFF_TRUST_VERSIONS with ggrs_hip_diff_block (a foreign block has no row versions), for GGRS_DIFF_LIVE against ring-slot
+ * form in a world with a component under a Strategy (live form and Stored form are not comparable), for a world with more than 64 columns;
+ * GGRS_E_NO_SNAPSHOT for a frame the ring does not hold.
+ * Without GGRS_DIFF_TRUST_VERSIONS every rollback row of both blocks is read -- the default: the tool must stay usable when the row versions are what is
+ * under suspicion.  With it, columns whose row version is the same on both sides are skipped on the host and never reach the kernel.
+ * Out of scope: the fan-out's desync reports, an export of per-component ChecksumParts, non-rollback components. */
+#define GGRS_DIFF_LIVE            INT32_MIN   /* as a frame: the live world */
+#define GGRS_DIFF_TRUST_VERSIONS  1u          /* flags: skip rows whose row versions are equal in both blocks */
+typedef struct {                 /* one differing ENTITY */
+    uint64_t slot;
+    uint32_t alive_a;            /* 0/1 */
+    uint32_t alive_b;
+    uint64_t presence_diff;      /* bit c: rollback component c present on one side only (both alive) */
+    uint64_t column_diff;        /* bit k: column k differs bitwise; only where the component is present on both sides */
+    uint32_t first_comp;         /* lowest differing column, as (component, word); 0xFFFFFFFF when column_diff == 0 */
+    uint32_t first_word;
+    uint64_t first_a;            /* that word's bits on each side, zero-extended */
+    uint64_t first_b;
+} ggrs_diff_entry;
+typedef struct {
+    uint64_t len_a;
+    uint64_t len_b;
+    uint64_t n_entities;         /* differing entities in all, whatever max_entries is */
+    uint64_t n_alive;            /* alive on one side only */
+    uint64_t n_presence[64];     /* per component: entities whose presence differs */
+    uint64_t n_value[64];        /* per component: entities with a differing word */
+    uint64_t resource_diff;      /* bit r: device resource r differs in some word (current cells compared) */
+    uint32_t n_entries;          /* entries written = min(n_entities, max_entries) */
+} ggrs_diff_report;
+int ggrs_hip_snapshot_copy(ggrs_world* w, int32_t frame, void* dst_dev);
+int ggrs_hip_diff_frames(ggrs_world* w, int32_t frame_a, int32_t frame_b, uint32_t flags,
+                         ggrs_diff_report* report, ggrs_diff_entry* entries, uint32_t max_entries);
+int ggrs_hip_diff_block(ggrs_world* w, int32_t frame_a, const void* block_b_dev, uint32_t flags,
+                        ggrs_diff_report* report, ggrs_diff_entry* entries, uint32_t max_entries);
+
+/* -------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): per-kernel-class HIP-event timing on the world's stream.
  * ------------------------------------------------------------------------------------------- */
 #define GGRS_KERNEL_SAVE     0u
@@ -957,7 +1015,7 @@ int ggrs_hip_host_timeline(ggrs_world* w, int enable, double* us_out, uint64_t* 
  * Introspection: which kernel serves this world's request lists right now and why, what kind of arena
  * it lives on, whether the run-time compiler (libhiprtc.so, dlopen'ed) is available.  `key=value` lines,
  * NUL-terminated; *needed = bytes incl. the NUL, min(cap, *needed) are copied.  Keys: sealed, arena,
- * arena_bytes, hiprtc, generated_kernel, generated_kernel_origin, request_group_kernel, checksum_fold, kernarg_bytes, group_caps, specialised_kernel, slots_covered, row_versions, peer_view (worlds with peer bindings), effect_inbox (worlds with effect bindings), device_resources (worlds with device resources), depth_parallel_roles, reduce_inbox (worlds with reduce bindings: stripes, words, applies so far), remote_inbox (worlds with remote bindings: components, applies so far), sum_partials (worlds with sum bindings: units, words, applies so far), value_inbox (worlds with value bindings: components, bindings, bytes allocated, applies so far).
+ * arena_bytes, hiprtc, generated_kernel, generated_kernel_origin, request_group_kernel, checksum_fold, kernarg_bytes, group_caps, specialised_kernel, slots_covered, row_versions, peer_view (worlds with peer bindings), effect_inbox (worlds with effect bindings), device_resources (worlds with device resources), depth_parallel_roles, reduce_inbox (worlds with reduce bindings: stripes, words, applies so far), remote_inbox (worlds with remote bindings: components, applies so far), sum_partials (worlds with sum bindings: units, words, applies so far), value_inbox (worlds with value bindings: components, bindings, bytes allocated, applies so far), state_diff (once a state diff ran: calls, and the columns, bytes per slot and units of the last one).
  * ------------------------------------------------------------------------------------------- */
 int ggrs_hip_world_kernel_info(ggrs_world* w, char* buf, uint64_t cap, uint64_t* needed);
 

@@ -272,6 +272,40 @@ pub struct ggrs_branch_step {
     pub spawn_sel: *const u16,
 }
 
+/// As a frame of `ggrs_hip_diff_frames` / `ggrs_hip_diff_block`: the live world.
+pub const GGRS_DIFF_LIVE: i32 = -2147483648;
+/// Flag: skip the columns whose row versions are equal in both blocks.
+pub const GGRS_DIFF_TRUST_VERSIONS: u32 = 1;
+
+/// One differing entity of a state diff.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct ggrs_diff_entry {
+    pub slot: u64,
+    pub alive_a: u32,
+    pub alive_b: u32,
+    pub presence_diff: u64,
+    pub column_diff: u64,
+    pub first_comp: u32,
+    pub first_word: u32,
+    pub first_a: u64,
+    pub first_b: u64,
+}
+
+/// The counts of a state diff: exact whatever `max_entries` was.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct ggrs_diff_report {
+    pub len_a: u64,
+    pub len_b: u64,
+    pub n_entities: u64,
+    pub n_alive: u64,
+    pub n_presence: [u64; 64],
+    pub n_value: [u64; 64],
+    pub resource_diff: u64,
+    pub n_entries: u32,
+}
+
 impl ggrs_request {
     pub const fn zeroed() -> Self {
         Self { kind: 0, frame: 0, dt_bits: 0, n_inputs: 0, inputs: core::ptr::null(), status: core::ptr::null(), spawn_count: 0, spawn_vx: core::ptr::null(), spawn_vy: core::ptr::null(),
@@ -351,6 +385,10 @@ unsafe extern "C" {
     pub fn ggrs_hip_state_bytes(w: *mut ggrs_world) -> u64;
     pub fn ggrs_hip_live_state_ptr(w: *mut ggrs_world, dev_ptr: *mut *mut c_void) -> c_int;
     pub fn ggrs_hip_adopt_live_state(w: *mut ggrs_world) -> c_int;
+    // ---- state diff: where two world states differ (a SyncTestMismatch handler calls diff_block with the copy it kept of the frame's first Save)
+    pub fn ggrs_hip_snapshot_copy(w: *mut ggrs_world, frame: i32, dst_dev: *mut c_void) -> c_int;
+    pub fn ggrs_hip_diff_frames(w: *mut ggrs_world, frame_a: i32, frame_b: i32, flags: u32, report: *mut ggrs_diff_report, entries: *mut ggrs_diff_entry, max_entries: u32) -> c_int;
+    pub fn ggrs_hip_diff_block(w: *mut ggrs_world, frame_a: i32, block_b_dev: *const c_void, flags: u32, report: *mut ggrs_diff_report, entries: *mut ggrs_diff_entry, max_entries: u32) -> c_int;
     // ---- speculative fan-out across GPUs (RCCL behind the C ABI; the host carries the 128-byte ncclUniqueId between ranks)
     pub fn ggrs_hip_fanout_unique_id(id_out: *mut u8) -> c_int;
     pub fn ggrs_hip_fanout_init(w: *mut ggrs_world, id: *const u8, rank: c_int, world_size: c_int, out: *mut *mut ggrs_fanout) -> c_int;
