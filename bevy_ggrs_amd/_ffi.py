@@ -178,6 +178,19 @@ class DiffReport(C.Structure):
                 ("n_presence", C.c_uint64 * 64), ("n_value", C.c_uint64 * 64), ("resource_diff", C.c_uint64), ("n_entries", C.c_uint32)]
 
 
+PART_COMPONENT, PART_ENTITY, PART_RESOURCE = 0, 1, 2      # GGRS_PART_*: the kind of a ggrs_checksum_part
+
+
+class ChecksumPart(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("id", C.c_uint32), ("value", C.c_uint64), ("n_hashed", C.c_uint64)]
+
+
+class PartsReport(C.Structure):
+    _fields_ = [("len", C.c_uint64), ("active", C.c_uint64), ("checksum_lo", C.c_uint64), ("checksum_hi", C.c_uint64), ("n_parts", C.c_uint32)]
+
+
+MAX_PARTS = 32 + 1 + 8                                    # GGRS_MAX_COMPONENTS components, the entities, GGRS_RESOURCE_MAX resources
+
 # every symbol include/ggrs_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SIGNATURES = {
@@ -260,6 +273,8 @@ SIGNATURES = {
     "ggrs_hip_snapshot_copy": (C.c_int, [_P, C.c_int32, _P]),
     "ggrs_hip_diff_frames": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(DiffReport), C.POINTER(DiffEntry), C.c_uint32]),
     "ggrs_hip_diff_block": (C.c_int, [_P, C.c_int32, _P, C.c_uint32, C.POINTER(DiffReport), C.POINTER(DiffEntry), C.c_uint32]),
+    "ggrs_hip_checksum_parts": (C.c_int, [_P, C.c_int32, C.POINTER(PartsReport), C.POINTER(ChecksumPart), C.c_uint32]),
+    "ggrs_hip_checksum_parts_block": (C.c_int, [_P, _P, C.POINTER(PartsReport), C.POINTER(ChecksumPart), C.c_uint32]),
     "ggrs_hip_fanout_unique_id": (C.c_int, [C.POINTER(C.c_uint8)]),
     "ggrs_hip_fanout_init": (C.c_int, [_P, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.POINTER(_P)]),
     "ggrs_hip_fanout_sync_confirmed": (C.c_int, [_P, C.c_int]),
@@ -277,6 +292,14 @@ SIGNATURES = {
     "ggrs_hip_profile_read_launches": (C.c_int, [_P, C.c_uint32, C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_uint32)]),
     "ggrs_hip_world_kernel_info": (C.c_int, [_P, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "ggrs_hip_specialise_wait": (C.c_int, [_P]),
+}
+
+
+# test hooks the header does not declare (ggrs_dbg_*) that the package binds with their types
+DEBUG_SIGNATURES = {
+    "ggrs_dbg_set_parts_grid": (C.c_int, [_P, C.c_int]),
+    "ggrs_dbg_parts_launch_us": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double)]),
+    "ggrs_dbg_parts_kernel_source": (C.c_int, [_P, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_int]),
 }
 
 
@@ -309,7 +332,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
             "bevy_ggrs_amd has no CPU fallback.")
     _preload_hip_runtime()
     lib = C.CDLL(path)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(DEBUG_SIGNATURES.items()):
         fn = getattr(lib, name)       # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -131,6 +131,10 @@ void ggrs_hip_world_destroy(ggrs_world* w) {
     if (w->d_skip) (void)hipFree(w->d_skip);
     if (w->d_diff) (void)hipFree(w->d_diff);
     if (w->h_diff) (void)hipHostFree(w->h_diff);
+    if (w->d_cparts) (void)hipFree(w->d_cparts);
+    if (w->h_cparts) (void)hipHostFree(w->h_cparts);
+    for (hipEvent_t e : w->cparts_ev) if (e) (void)hipEventDestroy(e);
+    jit_release(w->cparts_entry);
     sp_release(w);
     peer_view_release(w);
     fx_inbox_release(w);
@@ -509,6 +513,20 @@ int ggrs_hip_generated_kernel_source(ggrs_world* w, uint32_t form, char* buf, ui
     if (needed) *needed = src.size() + 1;
     if (buf && cap) { const uint64_t n = std::min<uint64_t>(cap, src.size() + 1); memcpy(buf, src.c_str(), n); buf[n - 1] = 0; }
     if (compile) { hipFunction_t fn = nullptr; return hiprtc_build(w, src, "generated request-group kernel", "ggrs_jit_tick", nullptr, &fn); }
+    return GGRS_OK;
+}
+// Test hook (no ggrs_hip_ prefix, not in the header): the text of the checksum-parts kernel generated for a world with a user-written hasher (kernel_gen.hpp
+// jit_parts_source; any world gets a text); compile != 0: also built for gfx950 with hiprtc.  Works on a GGRS_WORLD_LAYOUT_ONLY world, as the call above
+int ggrs_dbg_parts_kernel_source(ggrs_world* w, char* buf, uint64_t cap, uint64_t* needed, int compile) {
+    if (!w) return GGRS_E_INVALID;
+    if (!w->sealed) {
+        if (!w->layout_only) { DeviceGuard dg(w); const int rc = seal(w); if (rc) return rc; }
+        else build_layout(w);
+    }
+    const std::string src = jit_parts_source(w);
+    if (needed) *needed = src.size() + 1;
+    if (buf && cap) { const uint64_t n = std::min<uint64_t>(cap, src.size() + 1); memcpy(buf, src.c_str(), n); buf[n - 1] = 0; }
+    if (compile) { hipFunction_t fn = nullptr; return hiprtc_build(w, src, "generated checksum-parts kernel", "ggrs_jit_parts", nullptr, &fn); }
     return GGRS_OK;
 }
 // Test hook (not part of the C ABI: no ggrs_hip_ prefix, not in include/ggrs_hip.h): the specialiser's token rule on arbitrary text --
@@ -1181,6 +1199,108 @@ int ggrs_hip_diff_block(ggrs_world* w, int32_t frame_a, const void* block_b_dev,
     return diff_run(w, A, B, flags, report, entries, max_entries);
 }
 
+// ---- CHECKSUM PARTS (include/ggrs_hip.h; the kernels: kernels.hpp k_parts_hash / k_parts_finish, kernel_gen.hpp ggrs_jit_parts) -------------------------------------
+// Nothing here is on the tick's path.  The state is one side of a state diff (diff_ready / diff_side above: no batches outstanding, deferred Saves and the lazy live
+// block brought up to date, the len of a device-spawn world read from the slot's header).
+namespace {
+uint32_t parts_count(const ggrs_world* w) { uint32_t n = (uint32_t)w->cks_comp.size() + 1u; for (auto& r : w->resources) n += r.checksummed ? 1u : 0u; return n; }
+int parts_run(ggrs_world* w, const DiffSide& S, ggrs_parts_report* rep, ggrs_checksum_part* parts, uint32_t max_parts) {
+    const uint32_t n_cks = (uint32_t)w->cks_comp.size(), n_parts = parts_count(w);
+    if (!rep || !parts) return w->fail(GGRS_E_INVALID, "bad checksum_parts arguments (no report, or no parts array)");
+    if (max_parts < n_parts) return w->fail(GGRS_E_INVALID, "max_parts %u is below the world's %u checksum parts (%u components, the entities, %u resources)", max_parts, n_parts, n_cks, n_parts - n_cks - 1u);
+    if (!S.live_form) for (uint32_t c : w->cks_comp) {
+        const Comp& cc = w->comps[c];
+        if (cc.s_n_words) return w->fail(GGRS_E_INVALID, "checksum parts of a snapshot in a world where checksummed component %s is under a Strategy: the slot holds Stored words, the checksum is over live words (GGRS_DIFF_LIVE is served)", cc.name.c_str());
+        if (cc.no_rollback) return w->fail(GGRS_E_INVALID, "checksum parts of a snapshot in a world where checksummed component %s is not registered for rollback: no snapshot holds it (GGRS_DIFF_LIVE is served)", cc.name.c_str());
+    }
+    // a world with a user-written hasher: the hashing kernel is generated at the first call and comes through the module caches
+    if (w->custom_hashers && !w->cparts_fn) {
+        const std::string keep = w->err;
+        const int rc = jit_cached(w, jit_parts_source(w), &w->cparts_fn, &w->cparts_entry, &w->cparts_origin, "ggrs_jit_parts", "generated checksum-parts kernel");
+        if (rc != GGRS_OK) {
+            const std::string why = w->err.substr(0, 300);
+            w->cparts_fn = nullptr; w->err = keep;
+            return w->fail(GGRS_E_INVALID, "checksum parts of a world with a user-written hasher need its generated kernel: %s%s", hiprtc_for(w).lib ? "" : "no run-time compiler and no cached code object -- ", why.c_str());
+        }
+        ++w->cparts_builds;
+    }
+    if (!w->h_cparts) HIPCHK(w, hipHostMalloc((void**)&w->h_cparts, PARTS_OUT_BYTES, hipHostMallocDefault));
+    if (!w->d_cparts) HIPCHK(w, hipMalloc((void**)&w->d_cparts, PARTS_SCRATCH_BYTES));
+    PartsArgs a; memset(&a, 0, sizeof a);
+    a.state = S.ptr; a.words = reinterpret_cast<const PartsWord*>(w->d_units); a.acc = reinterpret_cast<unsigned long long*>(w->d_cparts);
+    a.len = std::min<uint64_t>(S.len, w->capacity); a.off_alive = w->off_alive; a.n_cks = n_cks;
+    a.n_units = (uint32_t)((a.len + 63) / 64);
+    for (uint32_t k = 0; k < n_cks; ++k) { a.off_present[k] = w->cks_args.off_present[k]; a.n_words[k] = w->cks_args.n_units[k]; a.word_base[k] = w->cks_args.unit_base[k]; }
+    PartsFinArgs f; memset(&f, 0, sizeof f);
+    f.acc = a.acc; f.out = w->d_cparts + PARTS_OUT_OFF; f.len = a.len; f.n_cks = n_cks;
+    f.res_cell = S.ptr + RES_CELL_OFF + S.res_cell * RES_CELL_BYTES;
+    for (uint32_t k = 0; k < n_cks; ++k) f.comp_id[k] = w->cks_comp[k];
+    for (uint32_t r = 0; r < w->resources.size(); ++r) {
+        const ggrs_world::Resource& rr = w->resources[r];
+        if (!rr.checksummed) continue;
+        const uint32_t j = f.n_res++;
+        f.res_id[j] = r; f.res_wb[j] = (uint8_t)rr.word_bytes; f.res_nw[j] = (uint8_t)rr.cks_words.size();
+        for (uint32_t i = 0; i < rr.cks_words.size() && i < (uint32_t)MAX_UNITS; ++i) f.res_off[j][i] = (uint8_t)(rr.off + rr.cks_words[i] * rr.word_bytes);
+    }
+    HIPCHK(w, hipMemsetAsync(a.acc, 0, PARTS_ACC_BYTES, w->stream));
+    if (w->cparts_timed) { for (hipEvent_t& e : w->cparts_ev) if (!e) HIPCHK(w, hipEventCreate(&e)); HIPCHK(w, hipEventRecord(w->cparts_ev[0], w->stream)); }
+    if (a.n_units) {
+        const uint32_t by_size = (a.n_units + PARTS_WAVES - 1) / PARTS_WAVES;
+        const uint32_t g = std::max<uint32_t>(1, std::min<uint32_t>(by_size, w->cparts_max_wgs ? w->cparts_max_wgs : 2048u));
+        if (w->custom_hashers) {
+            void* params[] = {&a};
+            HIPCHK(w, hipModuleLaunchKernel(w->cparts_fn, g, 1, 1, TPB, 1, 1, 0, w->stream, params, nullptr));
+        } else {
+            hipLaunchKernelGGL(k_parts_hash, dim3(g), dim3(TPB), 0, w->stream, a);
+            HIPCHK(w, hipGetLastError());
+        }
+    }
+    if (w->cparts_timed) HIPCHK(w, hipEventRecord(w->cparts_ev[1], w->stream));
+    hipLaunchKernelGGL(k_parts_finish, dim3(1), dim3(TPB), 0, w->stream, f);
+    HIPCHK(w, hipGetLastError());
+    if (w->cparts_timed) HIPCHK(w, hipEventRecord(w->cparts_ev[2], w->stream));
+    // the report and the parts: one copy into pinned host memory
+    HIPCHK(w, hipMemcpyAsync(w->h_cparts, f.out, PARTS_OUT_PARTS + (size_t)n_parts * sizeof(ggrs_checksum_part), hipMemcpyDeviceToHost, w->stream));
+    HIPCHK(w, hipStreamSynchronize(w->stream));
+    if (w->cparts_timed) for (int k = 0; k < 2; ++k) { float ms = 0; HIPCHK(w, hipEventElapsedTime(&ms, w->cparts_ev[k], w->cparts_ev[k + 1])); w->cparts_us[k] = (double)ms * 1e3; }
+    memcpy(rep, w->h_cparts, sizeof *rep);
+    memcpy(parts, w->h_cparts + PARTS_OUT_PARTS, (size_t)n_parts * sizeof(ggrs_checksum_part));
+    ++w->cparts_calls;
+    return GGRS_OK;
+}
+}  // namespace
+//   ggrs_dbg_set_parts_grid    at most n workgroups for the hashing launch of a checksum-parts call (0: by size): the report must not depend on it
+int ggrs_dbg_set_parts_grid(ggrs_world* w, int n) { if (!w || n < 0 || n > 65535) return -1; w->cparts_max_wgs = (uint32_t)n; return 0; }
+//   ggrs_dbg_parts_launch_us   enable != 0: every later checksum-parts call puts HIP events around its two launches; us_out (may be NULL) receives what the hashing
+//                              launch and k_parts_finish of the last timed call took by themselves, in microseconds (scripts/bench_checksum_parts.py)
+int ggrs_dbg_parts_launch_us(ggrs_world* w, int enable, double* us_out) {
+    if (!w) return -1;
+    w->cparts_timed = enable != 0;
+    if (us_out) { us_out[0] = w->cparts_us[0]; us_out[1] = w->cparts_us[1]; }
+    return 0;
+}
+int ggrs_hip_checksum_parts(ggrs_world* w, int32_t frame, ggrs_parts_report* report, ggrs_checksum_part* parts, uint32_t max_parts) {
+    if (!w) return GGRS_E_INVALID;
+    if (w->layout_only) return w->fail(GGRS_E_INVALID, "a layout-only world has no state to take checksum parts of");
+    DeviceGuard dg(w);
+    int rc = diff_ready(w); if (rc) return rc;
+    DiffSide S; rc = diff_side(w, frame, &S); if (rc) return rc;
+    return parts_run(w, S, report, parts, max_parts);
+}
+int ggrs_hip_checksum_parts_block(ggrs_world* w, const void* block_dev, ggrs_parts_report* report, ggrs_checksum_part* parts, uint32_t max_parts) {
+    if (!w) return GGRS_E_INVALID;
+    if (w->layout_only) return w->fail(GGRS_E_INVALID, "a layout-only world has no state to take checksum parts of");
+    if (!block_dev) return w->fail(GGRS_E_INVALID, "checksum_parts_block without a block");
+    DeviceGuard dg(w);
+    int rc = diff_ready(w); if (rc) return rc;
+    struct { Header h; uint32_t res_cell; } hx;
+    HIPCHK(w, hipMemcpyAsync(&hx, block_dev, sizeof hx, hipMemcpyDeviceToHost, w->stream));
+    HIPCHK(w, hipStreamSynchronize(w->stream));
+    if (hx.h.len > w->capacity) return w->fail(GGRS_E_INVALID, "the block's header has len %llu > capacity %llu: not a block of this world", (unsigned long long)hx.h.len, (unsigned long long)w->capacity);
+    DiffSide S; S.ptr = (const uint8_t*)block_dev; S.len = hx.h.len; S.ver = nullptr; S.res_cell = w->has_resources ? (hx.res_cell & 1u) : 0u; S.live_form = false;
+    return parts_run(w, S, report, parts, max_parts);
+}
+
 // Which kernel serves this world's request lists right now, on what kind of arena, and the state of the run-time
 // compiler -- `key=value` lines (NUL-terminated, truncated to cap).  Nothing here is needed to USE the library: it is what an
 // operator reads when a world is slower than expected (e.g. libhiprtc.so missing from a deployment image).
@@ -1268,6 +1388,8 @@ int ggrs_hip_world_kernel_info(ggrs_world* w, char* buf, uint64_t cap, uint64_t*
     add("slots_covered", std::to_string(cover));
     if (w->diff_calls) add("state_diff", std::to_string(w->diff_calls) + " calls; the last one compared " + std::to_string(w->diff_last_cols) + " columns (" + std::to_string(w->diff_last_bps) +
                                          " bytes per slot and side) and " + std::to_string(w->plan.n_masks) + " masks over " + std::to_string(w->diff_last_units) + " units of 64 slots");
+    if (w->cparts_calls) add("checksum_parts", std::to_string(w->cparts_calls) + " calls; hashing kernel " + (w->custom_hashers ? "ggrs_jit_parts (generated: the world has a user-written hasher; module from " + w->cparts_origin + ", " +
+                                             std::to_string(w->cparts_builds) + " built or loaded by this world)" : std::string("k_parts_hash (static)")));
     add("row_versions", w->knobs.row_versions ? "on" : "off (GGRS_ROW_VERSIONS=0)");
     add("value_tags", !w->sealed ? "unknown (not sealed)" : w->vtags ? "on: a Save skips the columns whose 64 values per unit the destination already holds (" + std::to_string(w->prof_skipped) + " bytes not stored in profiled launches; the ids' numbering has started over " + std::to_string(w->tag_wraps) + " times)"
                                  : "off (the world's steady Save moves less than " + std::to_string(VTAGS_MIN_BYTES >> 20) + " MB, or row versions are off)");

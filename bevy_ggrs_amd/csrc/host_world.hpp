@@ -432,8 +432,15 @@ struct ggrs_world {
     uint8_t* d_diff = nullptr; uint8_t* h_diff = nullptr; uint64_t diff_bytes = 0; uint32_t diff_max_wgs = 0; uint64_t diff_calls = 0;
     uint32_t diff_last_cols = 0, diff_last_bps = 0, diff_last_units = 0;      // what the last call compared (kernel_info "state_diff")
 
+    // ---- checksum parts (ggrs_hip_checksum_parts / ggrs_hip_checksum_parts_block): the scratch of its two launches (the accumulator cells, the finished report and
+    // parts) and the pinned page they come back into, allocated at the first call, freed with the world.  cparts_max_wgs: ggrs_dbg_set_parts_grid (0: by size).
+    // cparts_fn: a world with a user-written hasher hashes with a kernel generated at its first call (kernel_gen.hpp jit_parts_source), through the module caches
+    uint8_t* d_cparts = nullptr; uint8_t* h_cparts = nullptr; uint32_t cparts_max_wgs = 0; uint64_t cparts_calls = 0;
+    hipFunction_t cparts_fn = nullptr; JitEntry* cparts_entry = nullptr; std::string cparts_origin; uint32_t cparts_builds = 0;
+    bool cparts_timed = false; hipEvent_t cparts_ev[3] = {nullptr, nullptr, nullptr}; double cparts_us[2] = {0, 0};   // ggrs_dbg_parts_launch_us: the two launches of the last call by themselves
+
     // ---- profiling
-    bool nt_copy = false;               // non-temporal loads/stores in k_copy_state (A/B knob)
+    bool nt_copy = false;              // non-temporal loads/stores in k_copy_state (A/B knob)
     bool prof = false;
     std::vector<EventPair> prof_events;
     std::vector<hipEvent_t> prof_pool;   // timing events of drained pairs, reused: creating two events per launch kept the HOST behind the device in an instrumented pass

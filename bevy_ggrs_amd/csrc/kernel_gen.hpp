@@ -1014,6 +1014,15 @@ void sfmt(std::string& s, const char* fmt, ...) {
     if (n < 0 || (size_t)n >= sizeof buf) { s += "\n#error generator line too long\n"; return; }   // never silently truncate generated code
     s += buf;
 }
+// the user-written hashers (ggrs_hip_checksum_component_custom), each in a namespace of its own: one spelling for the request-group kernel and for the
+// checksum-parts kernel of such a world (jit_parts_source)
+void jit_hash_namespaces(const ggrs_world* w, const std::vector<uint32_t>& cks_comp, std::string& s) {
+    for (uint32_t c : cks_comp) if (!w->comps[c].cks_source.empty()) {
+        sfmt(s, "namespace ggrs_hash_%u {\n#line 1 \"checksum_%s\"\n", c, w->comps[c].name.c_str());
+        s += w->comps[c].cks_source;
+        s += "\n}\n";
+    }
+}
 std::string f32_lit(float f) { uint32_t b; memcpy(&b, &f, 4); char buf[48]; snprintf(buf, sizeof buf, "__uint_as_float(0x%08xu)", b); return buf; }
 
 // columns the generated kernel's Advance steps and checksums READ: they must be in registers whatever the row masks say
@@ -1290,11 +1299,7 @@ struct JitGen {
             s += sp.source;
             s += "\n}\n";
         }
-        for (uint32_t c : cks_comp) if (!w->comps[c].cks_source.empty()) {
-            sfmt(s, "namespace ggrs_hash_%u {\n#line 1 \"checksum_%s\"\n", c, w->comps[c].name.c_str());
-            s += w->comps[c].cks_source;
-            s += "\n}\n";
-        }
+        jit_hash_namespaces(w, cks_comp, s);
         for (uint32_t c = 0; c < nc; ++c) if (rb(c) && strat(c)) {
             sfmt(s, "namespace ggrs_strategy_%u {\n#line 1 \"strategy_%s\"\n", c, w->comps[c].name.c_str());
             s += w->comps[c].strat_source;
@@ -2302,22 +2307,25 @@ bool jit_read_file(const std::string& path, std::vector<char>& image) {
     return !image.empty();
 }
 // disk cache, then the shipped objects: a module + kernel handle, or false
-bool jit_load_cached(const std::string& cache_dir, const std::string& aot_knob, const std::string& src, hipModule_t* mod, hipFunction_t* fn, std::string* origin, uint32_t* vgprs = nullptr, uint32_t* sgprs = nullptr) {
+bool jit_load_cached(const std::string& cache_dir, const std::string& aot_knob, const std::string& src, hipModule_t* mod, hipFunction_t* fn, std::string* origin, uint32_t* vgprs = nullptr, uint32_t* sgprs = nullptr,
+                     const char* kernel = "ggrs_jit_tick") {
     const std::string aot = jit_aot_dir(aot_knob);
     const std::string paths[2] = {jit_disk_path_in(cache_dir, src), aot.empty() ? std::string() : aot + "/" + jit_aot_name(src)};
     for (int k = 0; k < 2; ++k) {
         std::vector<char> image;
         if (!jit_read_file(paths[k], image)) continue;
         if (hipModuleLoadData(mod, image.data()) == hipSuccess) {
-            if (hipModuleGetFunction(fn, *mod, "ggrs_jit_tick") == hipSuccess) { if (origin) *origin = k == 0 ? "disk cache" : "shipped code object (aot)"; if (vgprs) *vgprs = hsaco_note_uint(image, ".vgpr_count"); if (sgprs) *sgprs = hsaco_note_uint(image, ".sgpr_count"); return true; }
+            if (hipModuleGetFunction(fn, *mod, kernel) == hipSuccess) { if (origin) *origin = k == 0 ? "disk cache" : "shipped code object (aot)"; if (vgprs) *vgprs = hsaco_note_uint(image, ".vgpr_count"); if (sgprs) *sgprs = hsaco_note_uint(image, ".sgpr_count"); return true; }
             (void)hipModuleUnload(*mod); *mod = nullptr;
         }
         (void)hipGetLastError();                                     // a stale / truncated file: go on as if it were not there
     }
     return false;
 }
-// *entry_out: what the world hands back to jit_release when it is destroyed
-int jit_cached(ggrs_world* w, const std::string& src, hipFunction_t* fn, JitEntry** entry_out, std::string* origin = nullptr) {
+// *entry_out: what the world hands back to jit_release when it is destroyed.  kernel / what: the module's entry point and its name in messages (the request-group
+// kernel unless said otherwise: the checksum-parts kernel of a world with a user-written hasher comes through here too)
+int jit_cached(ggrs_world* w, const std::string& src, hipFunction_t* fn, JitEntry** entry_out, std::string* origin = nullptr, const char* kernel = "ggrs_jit_tick",
+               const char* what = "generated request-group kernel") {
     JitCache& jc = jit_cache();
     std::lock_guard<std::mutex> lk(jc.mu);
     auto& cache = jc.map; uint64_t& clock_ = jc.clock;
@@ -2326,10 +2334,10 @@ int jit_cached(ggrs_world* w, const std::string& src, hipFunction_t* fn, JitEntr
     if (it != cache.end()) { it->second.last_use = ++clock_; ++it->second.refs; *fn = it->second.fn; *entry_out = &it->second; if (origin) *origin = "in-process module cache"; return GGRS_OK; }
     hipModule_t mod = nullptr;
     uint32_t vgprs = 0, sgprs = 0;
-    int rc = jit_load_cached(w->knobs.jit_cache_dir, w->knobs.aot_dir, src, &mod, fn, origin, &vgprs, &sgprs) ? GGRS_OK : GGRS_E_HIP;
+    int rc = jit_load_cached(w->knobs.jit_cache_dir, w->knobs.aot_dir, src, &mod, fn, origin, &vgprs, &sgprs, kernel) ? GGRS_OK : GGRS_E_HIP;
     if (rc != GGRS_OK) {
         std::vector<char> image;
-        rc = hiprtc_build(w, src, "generated request-group kernel", "ggrs_jit_tick", &mod, fn, &image);
+        rc = hiprtc_build(w, src, what, kernel, &mod, fn, &image);
         vgprs = hsaco_note_uint(image, ".vgpr_count"); sgprs = hsaco_note_uint(image, ".sgpr_count");
         const std::string path = jit_disk_path(w, src);
         if (rc == GGRS_OK && origin) *origin = "hiprtc";
@@ -2345,6 +2353,76 @@ int jit_cached(ggrs_world* w, const std::string& src, hipFunction_t* fn, JitEntr
     *entry_out = &e;                                                 // std::map nodes do not move
     return GGRS_OK;
 }
+// ---- the checksum-parts kernel of a world with a user-written hasher ("ggrs_jit_parts"; ggrs_hip_checksum_parts) ------------------------------------------------
+// Only generated code can run the user's source.  The text: the device prelude, parts_shared.hpp (the argument block and the accumulation of the static
+// k_parts_hash, kernels.hpp), what a hasher sees (GGRS_COMPONENT_TEXT), the ggrs_hash_<c> namespaces as the request-group kernel has them, and one arm per
+// checksum spec -- a word list as SeaStream writes, a user-written hasher through ggrs_hash_<c>::ggrs_hash(cv) with every word of the component in cv.w, as the
+// tick hands them over.  Column offsets, strides and widths are literals.  k_parts_finish is shared with every other world.
+static const char kJitPartsShared[] =
+#define GGRS_SHARED_CODE(...) #__VA_ARGS__
+#include "parts_shared.hpp"
+#undef GGRS_SHARED_CODE
+    ;
+std::string jit_parts_source(const ggrs_world* w) {
+    std::string s;
+    s += "typedef unsigned long uint64_t; typedef unsigned int uint32_t; typedef unsigned short uint16_t; typedef unsigned char uint8_t;\n"
+         "typedef long int64_t; typedef int int32_t;\n"
+         "typedef unsigned long long ggrs_u64; typedef unsigned int ggrs_u32;\n";
+    s += kJitSeaSpelling;
+    s += "namespace ggrs {\n";
+    s += kJitPrelude;
+    s += "\n";
+    s += kJitPartsShared;
+    s += "\n}\nusing namespace ggrs;\n";
+    s += GGRS_COMPONENT_TEXT;
+    std::vector<uint32_t> cks_comp;                                  // (== w->cks_comp once sealed; a layout-only world has the registrations alone)
+    for (uint32_t c = 0; c < w->comps.size(); ++c) if (w->comps[c].checksummed) cks_comp.push_back(c);
+    jit_hash_namespaces(w, cks_comp, s);
+    s += "#line 1 \"ggrs_jit_parts\"\n"
+         "extern \"C\" __global__ __launch_bounds__(256) void ggrs_jit_parts(PartsArgs a) {\n"
+         "    __shared__ unsigned long long s_rows[PARTS_WAVES * PARTS_CELLS];\n"
+         "    const uint32_t tid = threadIdx.x, lane = tid & 63u;\n"
+         "    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));\n"
+         "    parts_rows_clear(s_rows);\n"
+         "    unsigned long long* const row = s_rows + wave * PARTS_CELLS;\n"
+         "    for (uint32_t u = blockIdx.x * PARTS_WAVES + wave; u < a.n_units; u += gridDim.x * PARTS_WAVES) {\n"
+         "        const uint64_t alive = parts_alive(a, u);\n"
+         "        if (!alive) continue;\n"
+         "        const uint64_t e = (uint64_t)u * 64u + lane;\n"
+         "        if (lane == 0u) row[2u * a.n_cks] += (unsigned long long)__popcll(alive);\n";
+    auto load = [&](const Comp& cc, uint32_t wi) {
+        char b[200]; const uint32_t col = cc.col_base + wi;
+        snprintf(b, sizeof b, "parts_load(a.state + parts_col_at(%lluull, %uu, %uu, e), %uu)", (unsigned long long)w->col_off[col], w->col_ts[col], cc.word_bytes, cc.word_bytes);
+        return std::string(b);
+    };
+    for (uint32_t k = 0; k < cks_comp.size(); ++k) {
+        const uint32_t c = cks_comp[k];
+        const Comp& cc = w->comps[c];
+        sfmt(s, "        {   // spec %u: component %u\n"
+                "            const uint64_t m = alive & parts_present(a, %uu, u);\n"
+                "            if (m) {\n"
+                "                uint64_t h = 0;\n"
+                "                if ((m >> lane) & 1ull) {\n", k, c, k);
+        if (!cc.cks_source.empty()) {
+            s += "                    GgrsComponent cv; cv.slot = e;\n";
+            for (uint32_t wi = 0; wi < cc.n_words; ++wi) sfmt(s, "                    cv.w[%u] = %s;\n", wi, load(cc, wi).c_str());
+            sfmt(s, "                    h = sea_pair(e, ggrs_hash_%u::ggrs_hash(cv));\n", c);
+        } else {
+            s += "                    SeaStream st;\n";
+            for (uint32_t wi : cc.cks_words) sfmt(s, "                    st.write(%s, %uu);\n", load(cc, wi).c_str(), cc.word_bytes);
+            s += "                    h = sea_pair(e, st.finish());\n";
+        }
+        sfmt(s, "                }\n"
+                "                parts_put(row, a.n_cks, %uu, h, m, lane);\n"
+                "            }\n"
+                "        }\n", k);
+    }
+    s += "    }\n"
+         "    parts_rows_flush(a, s_rows);\n"
+         "}\n";
+    return s;
+}
+
 // A world is done with a generated kernel.  Modules stay cached for the next world of the same shape; only a process that keeps
 // creating NEW shapes ever exceeds JIT_CACHE_MAX_MODULES, and then the least recently used unreferenced modules are unloaded.
 void jit_release(JitEntry* e) {

@@ -1193,4 +1193,98 @@ __global__ __launch_bounds__(TPB) void k_diff_emit(DiffArgs a) {
     }
 }
 
+// ------------------------------------------------------------------ CHECKSUM PARTS (ggrs_hip_checksum_parts / ggrs_hip_checksum_parts_block)
+// The per-component ChecksumParts of ONE complete packed block (component_checksum.rs:67-108, entity_checksum.rs:29-52, resource_checksum.rs:63-83), the values the
+// tick folds into Checksum(u128) inside its launch and keeps none of.  A read-only pass of two launches, ordered by their boundary alone:
+//   k_parts_hash    one 64-slot unit per wave-iteration, one slot per lane, grid-stride over the units of [0, len).  The unit's alive word (cut by len) and every
+//                   spec's presence word are wave-uniform loads; a spec nobody of the unit holds reads no column.  Otherwise a lane that is alive and has the
+//                   component feeds its registered words (col_at: tile-major, 1, 2, 4 or 8 bytes each) to a SeaStream and pairs the result with its slot
+//                   (RollbackOrdered::order == slot); wave_xor makes the unit's value.  Accumulator rows per wave in LDS, one atomic per non-zero cell and workgroup
+//                   into one of PARTS_STRIPES copies of the row (parts_shared.hpp, shared with the kernel generated for worlds with a user-written hasher).
+//   k_parts_finish  one workgroup: the copies folded, sea_one per component, sea_pair(active, len), the resources' SeaStreams over the block's current cell, the XOR of all parts.
+#define GGRS_SHARED_CODE(...) __VA_ARGS__
+#include "parts_shared.hpp"
+#undef GGRS_SHARED_CODE
+static_assert(PARTS_MAX == MAX_COMPS && PARTS_WAVES * 64 == TPB, "parts_shared.hpp spells the limits of this file");
+static_assert(sizeof(PartsWord) == sizeof(UnitDesc) && offsetof(PartsWord, wb) == offsetof(UnitDesc, wb) && offsetof(PartsWord, ts) == offsetof(UnitDesc, ts), "k_parts_hash reads the world's UnitDesc table");
+constexpr uint32_t PARTS_ACC_BYTES = PARTS_STRIPES * PARTS_STRIPE_CELLS * 8;   // the scratch: the copies of the accumulator row ...
+constexpr uint32_t PARTS_OUT_OFF = 20480;                  // ... then (here) the report followed by the parts
+constexpr uint32_t PARTS_OUT_PARTS = 64;                   // ... the parts start this far behind the report
+constexpr uint32_t PARTS_OUT_BYTES = 4096;
+constexpr uint32_t PARTS_SCRATCH_BYTES = PARTS_OUT_OFF + PARTS_OUT_BYTES;
+constexpr uint32_t PARTS_MAX_PARTS = MAX_COMPS + 1 + GGRS_RESOURCE_MAX;
+static_assert(PARTS_CELLS <= PARTS_STRIPE_CELLS && PARTS_STRIPE_CELLS % 8 == 0 && PARTS_ACC_BYTES <= PARTS_OUT_OFF && PARTS_OUT_PARTS + PARTS_MAX_PARTS * sizeof(ggrs_checksum_part) <= PARTS_OUT_BYTES && sizeof(ggrs_parts_report) <= PARTS_OUT_PARTS, "the scratch holds every world's parts");
+struct PartsFinArgs {
+    const unsigned long long* acc; const uint8_t* res_cell; uint8_t* out;
+    uint64_t len;
+    uint32_t n_cks, n_res;
+    uint32_t comp_id[MAX_COMPS];
+    uint32_t res_id[GGRS_RESOURCE_MAX];
+    uint8_t res_wb[GGRS_RESOURCE_MAX], res_nw[GGRS_RESOURCE_MAX], res_off[GGRS_RESOURCE_MAX][MAX_UNITS];   // per checksummed resource: word bytes, chosen words, each one's byte offset inside a cell
+};
+__global__ __launch_bounds__(TPB) void k_parts_hash(PartsArgs a) {
+    __shared__ unsigned long long s_rows[PARTS_WAVES * PARTS_CELLS];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
+    parts_rows_clear(s_rows);
+    unsigned long long* const row = s_rows + wave * PARTS_CELLS;
+    for (uint32_t u = blockIdx.x * PARTS_WAVES + wave; u < a.n_units; u += gridDim.x * PARTS_WAVES) {
+        const uint64_t alive = parts_alive(a, u);
+        if (!alive) continue;                                                    // (wave-uniform)
+        const uint64_t e = (uint64_t)u * 64u + lane;
+        if (lane == 0u) row[2u * a.n_cks] += (unsigned long long)__popcll(alive);
+        for (uint32_t k = 0; k < a.n_cks; ++k) {
+            const uint64_t m = alive & parts_present(a, k, u);
+            if (!m) continue;                                                    // (wave-uniform: nobody of the unit holds the component -> no column is read)
+            uint64_t h = 0;
+            if ((m >> lane) & 1ull) {                                            // (a hashed lane is alive: its slot is below len, inside every column)
+                SeaStream s;
+                const uint32_t w0 = a.word_base[k], w1 = w0 + a.n_words[k];
+#pragma unroll 1
+                for (uint32_t i = w0; i < w1; ++i) {
+                    const PartsWord pw = a.words[i];
+                    s.write(parts_load(a.state + parts_col_at(pw.off, pw.ts, pw.wb, e), pw.wb), pw.wb);
+                }
+                h = sea_pair(e, s.finish());
+            }
+            parts_put(row, a.n_cks, k, h, m, lane);
+        }
+    }
+    parts_rows_flush(a, s_rows);
+}
+__global__ __launch_bounds__(TPB) void k_parts_finish(PartsFinArgs f) {
+    __shared__ uint64_t s_val[PARTS_MAX_PARTS];
+    __shared__ uint64_t s_cell[PARTS_CELLS];
+    const uint32_t t = threadIdx.x, n_parts = f.n_cks + 1u + f.n_res;
+    ggrs_checksum_part* const parts = reinterpret_cast<ggrs_checksum_part*>(f.out + PARTS_OUT_PARTS);
+    if (t <= 2u * f.n_cks) {                                                     // the copies of the row folded: XOR for the hashes, the sum for the counts
+        uint64_t v = 0;
+        for (uint32_t s = 0; s < (uint32_t)PARTS_STRIPES; ++s) { const uint64_t c = f.acc[s * (uint32_t)PARTS_STRIPE_CELLS + t]; v = t < f.n_cks ? v ^ c : v + c; }
+        s_cell[t] = v;
+    }
+    __syncthreads();
+    const uint64_t active = s_cell[2u * f.n_cks];
+    if (t < n_parts) {
+        ggrs_checksum_part p;
+        if (t < f.n_cks) { p.kind = GGRS_PART_COMPONENT; p.id = f.comp_id[t]; p.value = sea_one(s_cell[t]); p.n_hashed = s_cell[f.n_cks + t]; }      // component_checksum.rs:92-95: nobody holds it -> sea_one(0)
+        else if (t == f.n_cks) { p.kind = GGRS_PART_ENTITY; p.id = 0; p.value = sea_pair(active, f.len); p.n_hashed = active; }                       // entity_checksum.rs:29-52
+        else {
+            const uint32_t r = t - f.n_cks - 1u, wb = f.res_wb[r];
+            SeaStream s;
+            for (uint32_t i = 0; i < f.res_nw[r]; ++i) s.write(parts_load(f.res_cell + f.res_off[r][i], wb), wb);
+            p.kind = GGRS_PART_RESOURCE; p.id = f.res_id[r]; p.value = s.finish(); p.n_hashed = 0;
+        }
+        parts[t] = p;
+        s_val[t] = p.value;
+    }
+    __syncthreads();
+    if (t == 0) {
+        uint64_t total = 0;
+        for (uint32_t i = 0; i < n_parts; ++i) total ^= s_val[i];                // checksum.rs:88-99
+        ggrs_parts_report rep;
+        rep.len = f.len; rep.active = active; rep.checksum_lo = total; rep.checksum_hi = 0; rep.n_parts = n_parts;
+        *reinterpret_cast<ggrs_parts_report*>(f.out) = rep;
+    }
+}
+
 }  // namespace ggrs

@@ -13,7 +13,8 @@ i.e. 1 load, d saves, d+1 advances.  The first recorded checksum of each frame i
 every later re-save of that frame must reproduce it, otherwise MismatchedChecksum.
 With localise=True the session also keeps the block of each frame's first Save and a
 mismatch carries, per mismatched frame, where the re-simulated frame differs from it
-(MismatchedChecksum.diffs: World.diff of the kept copy against the ring's frame).
+(MismatchedChecksum.diffs: World.diff of the kept copy against the ring's frame) and which
+ChecksumParts differ (MismatchedChecksum.parts: World.checksum_parts of either).
 """
 from __future__ import annotations
 
@@ -27,7 +28,7 @@ class MismatchedChecksum(Exception):
     """GgrsError::MismatchedChecksum { current_frame, mismatched_frames } ->
     SyncTestMismatch event (src/lib.rs:133-139, schedule_systems.rs:104-115)."""
 
-    def __init__(self, current_frame: int, mismatched_frames: List[int], diffs: Optional[dict] = None):
+    def __init__(self, current_frame: int, mismatched_frames: List[int], diffs: Optional[dict] = None, parts: Optional[dict] = None):
         super().__init__(f"Detected checksum mismatch during rollback on frame {current_frame}, "
                          f"mismatched frames: {mismatched_frames}")
         self.current_frame = current_frame
@@ -35,6 +36,9 @@ class MismatchedChecksum(Exception):
         # SyncTestSession(localise=True) only: frame -> StateDiff of (the copy kept of the frame's first Save, the re-simulated frame in the ring)
         if diffs is not None:
             self.diffs = diffs
+        # ... and frame -> (ChecksumParts of the kept copy, ChecksumParts of the re-simulated frame); absent in a world where the parts of a snapshot are refused
+        if parts is not None:
+            self.parts = parts
 
 
 @dataclass
@@ -110,8 +114,8 @@ class SyncTestSession:
             mismatched = [f for f in range(cur - d, cur + 1) if not self._checksums_consistent(f)]
             if mismatched:
                 if self.localise and self._world is not None:
-                    raise MismatchedChecksum(cur, mismatched, {f: self._world.diff(self._kept[f], f) for f in mismatched
-                                                               if f in self._kept and self._world.has_snapshot(f)})
+                    both = [f for f in mismatched if f in self._kept and self._world.has_snapshot(f)]
+                    raise MismatchedChecksum(cur, mismatched, {f: self._world.diff(self._kept[f], f) for f in both}, self._parts_of(both))
                 raise MismatchedChecksum(cur, mismatched)
             # adjust_gamestate: roll back d frames and resimulate
             frame_to = cur - d
@@ -138,6 +142,17 @@ class SyncTestSession:
         for k in [k for k in self._input_history if k < self.current_frame - d - 2]:
             self._input_history.pop(k, None); self._pending.pop(k, None)
         return requests
+
+    def _parts_of(self, frames):
+        """frame -> (parts of the kept first Save: the block call; parts of the re-simulated frame: the frame call); None where the world refuses the parts of a
+        snapshot (a checksummed component under a Strategy)."""
+        from ._ffi import GGRS_E_INVALID, GgrsHipError
+        try:
+            return {f: (self._world.checksum_parts(self._kept[f]), self._world.checksum_parts(f)) for f in frames}
+        except GgrsHipError as e:
+            if e.code != GGRS_E_INVALID:
+                raise
+            return None
 
     def record_checksums(self, checksums: Sequence[int], world=None):
         """cell.save(frame, None, Some(checksum)) for each SaveGameState of the last

@@ -83,6 +83,28 @@ class StateDiff:
         return "\n".join(out)
 
 
+@dataclass
+class ChecksumParts:
+    """World.checksum_parts: the per-component ChecksumParts of one world state (ggrs_parts_report + its parts).  `parts` maps a name to the part's value, in
+    the order the parts are folded: the checksummed components by id under their registered names, "Entity", the checksummed device resources by id under
+    theirs.  `counts` maps a name to n_hashed: the entities that contributed to a component's part, the live entities for "Entity", 0 for a resource.
+    `checksum` is the XOR of all parts: for a ring frame, the Checksum its SaveGameState returned."""
+    parts: Dict[str, int]
+    counts: Dict[str, int]
+    len: int
+    active: int
+    checksum: int
+
+    def differing(self, other: "ChecksumParts") -> List[str]:
+        """The names whose values differ between the two (a name only one of them has differs)."""
+        return [k for k in list(self.parts) + [k for k in other.parts if k not in self.parts] if self.parts.get(k) != other.parts.get(k)]
+
+    def __str__(self):
+        out = [f"checksum {self.checksum:#018x} (len {self.len}, {self.active} alive)"]
+        out += [f"  {k}: {v:#018x}" + (f" over {self.counts[k]} entities" if k != "Entity" and self.counts.get(k) else "") for k, v in self.parts.items()]
+        return "\n".join(out)
+
+
 class WorldBase:
     """Backend-neutral surface.  `bevy_ggrs_amd.World` binds it to libggrs_hip.so; the CPU
     oracle (tests only) binds the same surface to oracle/_build/libggrs_oracle.so."""
@@ -502,6 +524,7 @@ class World(WorldBase):
         rid = C.c_uint32()
         self._check(self._lib.ggrs_hip_register_resource(self._p, name.encode(), word_bytes, n_words, buf, C.byref(rid)))
         self._resources = getattr(self, "_resources", []) + [(word_bytes, n_words)]
+        self._res_names = getattr(self, "_res_names", []) + [name]
         return rid.value
 
     def checksum_resource(self, res: int, words: Sequence[int]):
@@ -668,6 +691,28 @@ class World(WorldBase):
         return StateDiff(len_a=int(rep.len_a), len_b=int(rep.len_b), n_entities=int(rep.n_entities), n_alive=int(rep.n_alive),
                          n_presence={c: int(rep.n_presence[c]) for c in range(64) if rep.n_presence[c]}, n_value={c: int(rep.n_value[c]) for c in range(64) if rep.n_value[c]},
                          resource_diff=bits(rep.resource_diff), entries=entries, names=names)
+
+    # ---- checksum parts (include/ggrs_hip.h: ggrs_hip_checksum_parts / ggrs_hip_checksum_parts_block)
+    def checksum_parts(self, state) -> ChecksumParts:
+        """The per-component ChecksumParts of one world state, computed on the device: `state` is a ring frame, LIVE, or a block tensor from snapshot_copy.
+        The XOR of the parts (.checksum) of a ring frame is the Checksum that frame's SaveGameState returned; .differing(other) names the parts apart."""
+        rep = _ffi.PartsReport()
+        arr = (_ffi.ChecksumPart * _ffi.MAX_PARTS)()
+        if hasattr(state, "data_ptr"):
+            import torch
+            if state.dtype != torch.uint8 or state.numel() != self.state_bytes() or not state.is_cuda or not state.is_contiguous():
+                raise ValueError(f"a block is a contiguous torch.uint8 device tensor of {self.state_bytes()} bytes")
+            torch.cuda.current_stream(state.device).synchronize()
+            self._check(self._lib.ggrs_hip_checksum_parts_block(self._p, state.data_ptr(), C.byref(rep), arr, _ffi.MAX_PARTS))
+        else:
+            self._check(self._lib.ggrs_hip_checksum_parts(self._p, int(state), C.byref(rep), arr, _ffi.MAX_PARTS))
+        parts, counts = {}, {}
+        res_names = getattr(self, "_res_names", [])
+        for i in range(rep.n_parts):
+            p = arr[i]
+            name = "Entity" if p.kind == _ffi.PART_ENTITY else self._comps[p.id][0] if p.kind == _ffi.PART_COMPONENT else res_names[p.id]
+            parts[name] = int(p.value); counts[name] = int(p.n_hashed)
+        return ChecksumParts(parts=parts, counts=counts, len=int(rep.len), active=int(rep.active), checksum=int(rep.checksum_lo) | (int(rep.checksum_hi) << 64))
 
     def live_state_ptr(self) -> int:
         p = C.c_void_p()

@@ -480,6 +480,20 @@ struct HipBackend {
         if (entries) entries->resize(rc == GGRS_OK ? report->n_entries : 0);
         return rc;
     }
+    // checksum parts (include/ggrs_hip.h): the ChecksumParts of a ring frame, the live world (GGRS_DIFF_LIVE) or a block in ring-slot form, computed on the device --
+    // what an observer of SyncTestMismatch compares to name the part of the schema.  (The host-resident resources' parts are XORed by this mirror itself.)
+    int checksum_parts(int32_t frame, ggrs_parts_report* report, std::vector<ggrs_checksum_part>* parts) {
+        parts->resize(GGRS_MAX_COMPONENTS + 1 + GGRS_RESOURCE_MAX);
+        const int rc = ggrs_hip_checksum_parts(w, frame, report, parts->data(), (uint32_t)parts->size());
+        parts->resize(rc == GGRS_OK ? report->n_parts : 0);
+        return rc;
+    }
+    int checksum_parts_block(const void* block_dev, ggrs_parts_report* report, std::vector<ggrs_checksum_part>* parts) {
+        parts->resize(GGRS_MAX_COMPONENTS + 1 + GGRS_RESOURCE_MAX);
+        const int rc = ggrs_hip_checksum_parts_block(w, block_dev, report, parts->data(), (uint32_t)parts->size());
+        parts->resize(rc == GGRS_OK ? report->n_parts : 0);
+        return rc;
+    }
 };
 
 // ---------------------------------------------------------------- speculative fan-out (no reference analogue: SURVEY.md 8e)

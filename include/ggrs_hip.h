@@ -956,7 +956,7 @@ int  ggrs_hip_fanout_adopt(ggrs_fanout* f, uint32_t branch, int32_t frame, uint3
  * GGRS_E_NO_SNAPSHOT for a frame the ring does not hold.
  * Without GGRS_DIFF_TRUST_VERSIONS every rollback row of both blocks is read -- the default: the tool must stay usable when the row versions are what is
  * under suspicion.  With it, columns whose row version is the same on both sides are skipped on the host and never reach the kernel.
- * Out of scope: the fan-out's desync reports, an export of per-component ChecksumParts, non-rollback components. */
+ * Out of scope: the fan-out's desync reports, non-rollback components.  (Per-component ChecksumParts: CHECKSUM PARTS below.) */
 #define GGRS_DIFF_LIVE            INT32_MIN   /* as a frame: the live world */
 #define GGRS_DIFF_TRUST_VERSIONS  1u          /* flags: skip rows whose row versions are equal in both blocks */
 typedef struct {                 /* one differing ENTITY */
@@ -987,6 +987,39 @@ int ggrs_hip_diff_block(ggrs_world* w, int32_t frame_a, const void* block_b_dev,
                         ggrs_diff_report* report, ggrs_diff_entry* entries, uint32_t max_entries);
 
 /* -------------------------------------------------------------------------------------------
+ * CHECKSUM PARTS: the per-component ChecksumParts of one world state, computed on the device.  The reference keeps one ChecksumPart per checksummed
+ * component, one for the entities and one per checksummed resource (component_checksum.rs:67-108, entity_checksum.rs:29-52, resource_checksum.rs:63-83) and
+ * folds them with XOR into Checksum(u128) (checksum.rs:88-99); the tick folds them inside its launch and keeps none.  These calls compute them again from a
+ * complete packed block in device memory, in a read-only pass of two small launches: when two checksums disagree, the parts say which part of the schema to
+ * look at -- also where the difference is only in how something was hashed (a user-written hasher, word widths, a resource's chosen words, len or the live
+ * count), which the state diff cannot see.
+ *
+ *   ggrs_hip_checksum_parts         the state is ring frame `frame`, or the live world (GGRS_DIFF_LIVE).
+ *   ggrs_hip_checksum_parts_block   the state is a block in ring-slot form somewhere in device memory: what ggrs_hip_snapshot_copy or a GGRS_ADOPT_BROADCAST
+ *                                   produces.  Its RollbackOrdered::len and current resource cell are read from its header.
+ *
+ * The parts, in this order:
+ *   1. one per checksummed component, in id order: value = hash(X), X the XOR over every slot s < len that is alive and has the component of
+ *      hash(order = s, inner(s)); inner = checksum_hasher() fed the registered words in order, each with its own width, or the user-written hasher.  A component
+ *      nobody holds has the part hash(0), not 0.  n_hashed: the entities that contributed;
+ *   2. the entity part: hash(active, len), active = alive slots below len (a slot at or beyond len is dead whatever its mask bit says); n_hashed = active;
+ *   3. one per checksummed device resource, in id order: checksum_hasher() over its chosen words of the state's current cell; n_hashed = 0.
+ * The report carries len, active and the XOR of all parts: for a ring frame that XOR is the Checksum the frame's SaveGameState returned.
+ * Bytes under dead slots, under absent components, in non-rollback components and in words no checksum names move no part.
+ * Both calls bring deferred Saves and a lazily skipped live block up to date first.  Errors: GGRS_E_INVALID while enqueued batches are uncollected; for a
+ * ring frame or a block in a world where a checksummed component is under a Strategy (the slot holds Stored words, the checksum is over live words:
+ * GGRS_DIFF_LIVE is served) or is not registered for rollback; for a layout-only world; for max_parts below the world's number of parts; in a world with a
+ * user-written hasher when neither the run-time compiler nor a cached code object of the parts kernel is there.  GGRS_E_NO_SNAPSHOT for a frame the ring
+ * does not hold.  Out of scope: the host-resident resource parts of the C++ mirror (include/bevy_ggrs_hip.hpp XORs those itself), the fan-out's desync reports. */
+#define GGRS_PART_COMPONENT 0u
+#define GGRS_PART_ENTITY    1u
+#define GGRS_PART_RESOURCE  2u
+typedef struct { uint32_t kind; uint32_t id; uint64_t value; uint64_t n_hashed; } ggrs_checksum_part;   /* id: component / resource id, 0 for the entity part; upper 64 bits of a ChecksumPart are always 0 */
+typedef struct { uint64_t len; uint64_t active; uint64_t checksum_lo; uint64_t checksum_hi; uint32_t n_parts; } ggrs_parts_report;
+int ggrs_hip_checksum_parts(ggrs_world* w, int32_t frame, ggrs_parts_report* report, ggrs_checksum_part* parts, uint32_t max_parts);
+int ggrs_hip_checksum_parts_block(ggrs_world* w, const void* block_dev, ggrs_parts_report* report, ggrs_checksum_part* parts, uint32_t max_parts);
+
+/* -------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): per-kernel-class HIP-event timing on the world's stream.
  * ------------------------------------------------------------------------------------------- */
 #define GGRS_KERNEL_SAVE     0u
@@ -1015,7 +1048,7 @@ int ggrs_hip_host_timeline(ggrs_world* w, int enable, double* us_out, uint64_t* 
  * Introspection: which kernel serves this world's request lists right now and why, what kind of arena
  * it lives on, whether the run-time compiler (libhiprtc.so, dlopen'ed) is available.  `key=value` lines,
  * NUL-terminated; *needed = bytes incl. the NUL, min(cap, *needed) are copied.  Keys: sealed, arena,
- * arena_bytes, hiprtc, generated_kernel, generated_kernel_origin, request_group_kernel, checksum_fold, kernarg_bytes, group_caps, specialised_kernel, slots_covered, row_versions, peer_view (worlds with peer bindings), effect_inbox (worlds with effect bindings), device_resources (worlds with device resources), depth_parallel_roles, reduce_inbox (worlds with reduce bindings: stripes, words, applies so far), remote_inbox (worlds with remote bindings: components, applies so far), sum_partials (worlds with sum bindings: units, words, applies so far), value_inbox (worlds with value bindings: components, bindings, bytes allocated, applies so far), state_diff (once a state diff ran: calls, and the columns, bytes per slot and units of the last one).
+ * arena_bytes, hiprtc, generated_kernel, generated_kernel_origin, request_group_kernel, checksum_fold, kernarg_bytes, group_caps, specialised_kernel, slots_covered, row_versions, peer_view (worlds with peer bindings), effect_inbox (worlds with effect bindings), device_resources (worlds with device resources), depth_parallel_roles, reduce_inbox (worlds with reduce bindings: stripes, words, applies so far), remote_inbox (worlds with remote bindings: components, applies so far), sum_partials (worlds with sum bindings: units, words, applies so far), value_inbox (worlds with value bindings: components, bindings, bytes allocated, applies so far), state_diff (once a state diff ran: calls, and the columns, bytes per slot and units of the last one), checksum_parts (once a parts call ran: calls, the hashing kernel and where its module came from, builds).
  * ------------------------------------------------------------------------------------------- */
 int ggrs_hip_world_kernel_info(ggrs_world* w, char* buf, uint64_t cap, uint64_t* needed);
 

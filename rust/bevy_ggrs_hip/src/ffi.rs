@@ -306,6 +306,32 @@ pub struct ggrs_diff_report {
     pub n_entries: u32,
 }
 
+/// The kind of a `ggrs_checksum_part`.
+pub const GGRS_PART_COMPONENT: u32 = 0;
+pub const GGRS_PART_ENTITY: u32 = 1;
+pub const GGRS_PART_RESOURCE: u32 = 2;
+
+/// One ChecksumPart of a world state: `id` is the component / resource id (0 for the entity part); the upper 64 bits of a ChecksumPart are always 0.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct ggrs_checksum_part {
+    pub kind: u32,
+    pub id: u32,
+    pub value: u64,
+    pub n_hashed: u64,
+}
+
+/// What the parts belong to: `RollbackOrdered::len`, the live entities, and the XOR of all parts (for a ring frame: its Checksum).
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct ggrs_parts_report {
+    pub len: u64,
+    pub active: u64,
+    pub checksum_lo: u64,
+    pub checksum_hi: u64,
+    pub n_parts: u32,
+}
+
 impl ggrs_request {
     pub const fn zeroed() -> Self {
         Self { kind: 0, frame: 0, dt_bits: 0, n_inputs: 0, inputs: core::ptr::null(), status: core::ptr::null(), spawn_count: 0, spawn_vx: core::ptr::null(), spawn_vy: core::ptr::null(),
@@ -389,6 +415,9 @@ unsafe extern "C" {
     pub fn ggrs_hip_snapshot_copy(w: *mut ggrs_world, frame: i32, dst_dev: *mut c_void) -> c_int;
     pub fn ggrs_hip_diff_frames(w: *mut ggrs_world, frame_a: i32, frame_b: i32, flags: u32, report: *mut ggrs_diff_report, entries: *mut ggrs_diff_entry, max_entries: u32) -> c_int;
     pub fn ggrs_hip_diff_block(w: *mut ggrs_world, frame_a: i32, block_b_dev: *const c_void, flags: u32, report: *mut ggrs_diff_report, entries: *mut ggrs_diff_entry, max_entries: u32) -> c_int;
+    // ---- checksum parts: the per-component ChecksumParts of a ring frame, the live world (GGRS_DIFF_LIVE) or a block in ring-slot form
+    pub fn ggrs_hip_checksum_parts(w: *mut ggrs_world, frame: i32, report: *mut ggrs_parts_report, parts: *mut ggrs_checksum_part, max_parts: u32) -> c_int;
+    pub fn ggrs_hip_checksum_parts_block(w: *mut ggrs_world, block_dev: *const c_void, report: *mut ggrs_parts_report, parts: *mut ggrs_checksum_part, max_parts: u32) -> c_int;
     // ---- speculative fan-out across GPUs (RCCL behind the C ABI; the host carries the 128-byte ncclUniqueId between ranks)
     pub fn ggrs_hip_fanout_unique_id(id_out: *mut u8) -> c_int;
     pub fn ggrs_hip_fanout_init(w: *mut ggrs_world, id: *const u8, rank: c_int, world_size: c_int, out: *mut *mut ggrs_fanout) -> c_int;
