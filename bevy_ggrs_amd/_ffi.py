@@ -191,6 +191,26 @@ class PartsReport(C.Structure):
 
 MAX_PARTS = 32 + 1 + 8                                    # GGRS_MAX_COMPONENTS components, the entities, GGRS_RESOURCE_MAX resources
 
+QUERY_MAX_WORDS = 32                                      # GGRS_QUERY_MAX_WORDS
+QUERY_SLOTS = 1                                           # GGRS_QUERY_SLOTS: also write each row's slot (u32)
+
+
+class QueryWord(C.Structure):
+    _fields_ = [("comp", C.c_uint32), ("word", C.c_uint32)]
+
+
+class QueryDesc(C.Structure):
+    _fields_ = [("with_mask", C.c_uint64), ("without_mask", C.c_uint64), ("n_words", C.c_uint32), ("flags", C.c_uint32), ("words", QueryWord * QUERY_MAX_WORDS)]
+
+
+class QueryLayout(C.Structure):
+    _fields_ = [("total_bytes", C.c_uint64), ("slots_off", C.c_uint64), ("col_off", C.c_uint64 * QUERY_MAX_WORDS), ("word_bytes", C.c_uint32 * QUERY_MAX_WORDS)]
+
+
+class QueryReport(C.Structure):
+    _fields_ = [("len", C.c_uint64), ("n_matched", C.c_uint64), ("n_rows", C.c_uint64)]
+
+
 # every symbol include/ggrs_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SIGNATURES = {
@@ -275,6 +295,9 @@ SIGNATURES = {
     "ggrs_hip_diff_block": (C.c_int, [_P, C.c_int32, _P, C.c_uint32, C.POINTER(DiffReport), C.POINTER(DiffEntry), C.c_uint32]),
     "ggrs_hip_checksum_parts": (C.c_int, [_P, C.c_int32, C.POINTER(PartsReport), C.POINTER(ChecksumPart), C.c_uint32]),
     "ggrs_hip_checksum_parts_block": (C.c_int, [_P, _P, C.POINTER(PartsReport), C.POINTER(ChecksumPart), C.c_uint32]),
+    "ggrs_hip_query_layout": (C.c_int, [_P, C.POINTER(QueryDesc), C.c_uint64, C.POINTER(QueryLayout)]),
+    "ggrs_hip_query": (C.c_int, [_P, C.c_int32, C.POINTER(QueryDesc), _P, C.c_uint64, C.POINTER(QueryReport)]),
+    "ggrs_hip_query_block": (C.c_int, [_P, _P, C.POINTER(QueryDesc), _P, C.c_uint64, C.POINTER(QueryReport)]),
     "ggrs_hip_fanout_unique_id": (C.c_int, [C.POINTER(C.c_uint8)]),
     "ggrs_hip_fanout_init": (C.c_int, [_P, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.POINTER(_P)]),
     "ggrs_hip_fanout_sync_confirmed": (C.c_int, [_P, C.c_int]),
@@ -299,6 +322,8 @@ SIGNATURES = {
 DEBUG_SIGNATURES = {
     "ggrs_dbg_set_parts_grid": (C.c_int, [_P, C.c_int]),
     "ggrs_dbg_parts_launch_us": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double)]),
+    "ggrs_dbg_set_query_grid": (C.c_int, [_P, C.c_int]),
+    "ggrs_dbg_query_launch_us": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double)]),
     "ggrs_dbg_parts_kernel_source": (C.c_int, [_P, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_int]),
 }
 

@@ -134,6 +134,7 @@ void ggrs_hip_world_destroy(ggrs_world* w) {
     if (w->d_cparts) (void)hipFree(w->d_cparts);
     if (w->h_cparts) (void)hipHostFree(w->h_cparts);
     for (hipEvent_t e : w->cparts_ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : w->query_ev) if (e) (void)hipEventDestroy(e);
     jit_release(w->cparts_entry);
     sp_release(w);
     peer_view_release(w);
@@ -1080,6 +1081,18 @@ int diff_side(ggrs_world* w, int32_t frame, DiffSide* s) {
     }
     return w->fail(GGRS_E_NO_SNAPSHOT, "no snapshot of frame %d in the ring", frame);
 }
+// the scratch of a state diff or a query (they never overlap): at least `need` bytes of device memory, grown on demand, and the pinned page reports come back into
+int diff_scratch(ggrs_world* w, uint64_t need) {
+    if (!w->h_diff) HIPCHK(w, hipHostMalloc((void**)&w->h_diff, DIFF_HOST_BYTES, hipHostMallocDefault));      // pinned: the copy back is one DMA, no staging by the runtime
+    if (need > w->diff_bytes) {
+        HIPCHK(w, hipStreamSynchronize(w->stream));
+        if (w->d_diff) { (void)hipFree(w->d_diff); w->d_diff = nullptr; w->diff_bytes = 0; }
+        const uint64_t want = align_up(need + need / 2, 4096);
+        HIPCHK(w, hipMalloc((void**)&w->d_diff, want));
+        w->diff_bytes = want;
+    }
+    return GGRS_OK;
+}
 int diff_run(ggrs_world* w, const DiffSide& A, const DiffSide& B, uint32_t flags, ggrs_diff_report* rep, ggrs_diff_entry* entries, uint32_t max_entries) {
     if (!rep || (max_entries && !entries)) return w->fail(GGRS_E_INVALID, "bad diff arguments (no report, or max_entries without entries)");
     if (flags & ~GGRS_DIFF_TRUST_VERSIONS) return w->fail(GGRS_E_INVALID, "unknown diff flags 0x%x", flags);
@@ -1119,14 +1132,7 @@ int diff_run(ggrs_world* w, const DiffSide& A, const DiffSide& B, uint32_t flags
     const uint64_t o_ent = (uint64_t)DIFF_CNT_WORDS * 8, o_any = align_up(o_ent + cap_e * sizeof(ggrs_diff_entry), ALIGN), o_off = o_any + align_up((uint64_t)a.n_units * 8, ALIGN);
     const uint64_t need = o_off + align_up((uint64_t)a.n_units * 8, ALIGN);
     static_assert((DIFF_CNT_WORDS * 8) % alignof(ggrs_diff_entry) == 0, "the entries sit right behind the counters");
-    if (!w->h_diff) HIPCHK(w, hipHostMalloc((void**)&w->h_diff, DIFF_HOST_BYTES, hipHostMallocDefault));      // pinned: the copy back is one DMA, no staging by the runtime
-    if (need > w->diff_bytes) {
-        HIPCHK(w, hipStreamSynchronize(w->stream));
-        if (w->d_diff) { (void)hipFree(w->d_diff); w->d_diff = nullptr; w->diff_bytes = 0; }
-        const uint64_t want = align_up(need + need / 2, 4096);
-        HIPCHK(w, hipMalloc((void**)&w->d_diff, want));
-        w->diff_bytes = want;
-    }
+    { const int src = diff_scratch(w, need); if (src) return src; }
     a.cnt = (uint64_t*)w->d_diff; a.unit_any = (uint64_t*)(w->d_diff + o_any); a.unit_off = (uint64_t*)(w->d_diff + o_off); a.entries = (ggrs_diff_entry*)(w->d_diff + o_ent);
     const uint32_t by_size = std::max<uint32_t>(1, (a.n_units + TPB / 64 - 1) / (TPB / 64));
     const uint32_t g = std::min<uint32_t>(by_size, w->diff_max_wgs ? w->diff_max_wgs : 4096u);
@@ -1301,6 +1307,141 @@ int ggrs_hip_checksum_parts_block(ggrs_world* w, const void* block_dev, ggrs_par
     return parts_run(w, S, report, parts, max_parts);
 }
 
+// ---- QUERY (include/ggrs_hip.h; the kernels: kernels.hpp k_query_match / k_diff_scan / k_query_emit) ------------------------------------------------------------------
+// Nothing here is on the tick's path.  The state is one side of a state diff (diff_ready / diff_side above); the scratch is the state diff's.
+namespace {
+// what needs no state: the desc against the world's components.  *with: with_mask and the components of the fetched words
+int query_check(ggrs_world* w, const ggrs_query_desc* d, uint64_t* with) {
+    if (!d) return w->fail(GGRS_E_INVALID, "query without a desc");
+    if (d->n_words > GGRS_QUERY_MAX_WORDS) return w->fail(GGRS_E_INVALID, "a query fetches at most %d words, not %u", GGRS_QUERY_MAX_WORDS, d->n_words);
+    if (d->flags & ~GGRS_QUERY_SLOTS) return w->fail(GGRS_E_INVALID, "unknown query flags 0x%x", d->flags);
+    const uint64_t known = w->comps.size() >= 64 ? ~0ull : (1ull << w->comps.size()) - 1ull;
+    if ((d->with_mask | d->without_mask) & ~known) return w->fail(GGRS_E_INVALID, "a query filter names a component the world does not have (with 0x%llx, without 0x%llx, %zu components)", (unsigned long long)d->with_mask, (unsigned long long)d->without_mask, w->comps.size());
+    uint64_t wm = d->with_mask;
+    for (uint32_t k = 0; k < d->n_words; ++k) {
+        const ggrs_query_word& q = d->words[k];
+        if (q.comp >= w->comps.size()) return w->fail(GGRS_E_INVALID, "fetched word %u names component %u: the world has %zu", k, q.comp, w->comps.size());
+        if (q.word >= w->comps[q.comp].n_words) return w->fail(GGRS_E_INVALID, "fetched word %u names word %u of component %s, which has %u", k, q.word, w->comps[q.comp].name.c_str(), w->comps[q.comp].n_words);
+        wm |= 1ull << q.comp;
+    }
+    if (wm & d->without_mask) return w->fail(GGRS_E_INVALID, "a query names the same component With (or fetches it) and Without (0x%llx): nothing can match", (unsigned long long)(wm & d->without_mask));
+    if ((d->flags & GGRS_QUERY_SLOTS) && w->capacity > (1ull << 32)) return w->fail(GGRS_E_INVALID, "GGRS_QUERY_SLOTS writes 32-bit slots: the world's capacity %llu exceeds 2^32", (unsigned long long)w->capacity);
+    *with = wm;
+    return GGRS_OK;
+}
+void query_layout(const ggrs_world* w, const ggrs_query_desc* d, uint64_t max_rows, ggrs_query_layout* out) {
+    memset(out, 0, sizeof *out);
+    uint64_t off = 0;
+    for (uint32_t k = 0; k < d->n_words; ++k) {
+        const uint32_t wb = w->comps[d->words[k].comp].word_bytes;
+        out->col_off[k] = off; out->word_bytes[k] = wb;
+        off = align_up(off + max_rows * wb, 256);
+    }
+    if (d->flags & GGRS_QUERY_SLOTS) { out->slots_off = off; off = align_up(off + max_rows * 4u, 256); }
+    out->total_bytes = off;
+}
+int query_run(ggrs_world* w, const DiffSide& S, const ggrs_query_desc* d, void* out_dev, uint64_t max_rows, ggrs_query_report* rep) {
+    uint64_t with = 0;
+    int rc = query_check(w, d, &with); if (rc) return rc;
+    if (!rep) return w->fail(GGRS_E_INVALID, "query without a report");
+    if (!out_dev && max_rows) return w->fail(GGRS_E_INVALID, "query with max_rows %llu and no output buffer", (unsigned long long)max_rows);
+    if (!S.live_form) {
+        for (uint32_t c = 0; c < w->comps.size(); ++c) if (((with | d->without_mask) >> c) & 1ull) {
+            if (w->comps[c].no_rollback) return w->fail(GGRS_E_INVALID, "a query of a snapshot names component %s, which is not registered for rollback: no snapshot holds it (GGRS_DIFF_LIVE is served)", w->comps[c].name.c_str());
+        }
+        for (uint32_t k = 0; k < d->n_words; ++k) {
+            const Comp& cc = w->comps[d->words[k].comp];
+            if (cc.s_n_words) return w->fail(GGRS_E_INVALID, "a query of a snapshot fetches words of component %s, which is under a Strategy: the slot holds Stored words (GGRS_DIFF_LIVE is served)", cc.name.c_str());
+        }
+    }
+    ggrs_query_layout lay; query_layout(w, d, max_rows, &lay);
+    QueryArgs a; memset(&a, 0, sizeof a);
+    a.state = S.ptr; a.out = (uint8_t*)out_dev; a.len = std::min<uint64_t>(S.len, w->capacity); a.max_rows = max_rows; a.off_alive = w->off_alive; a.slots_off = lay.slots_off;
+    for (uint32_t c = 0; c < w->comps.size() && c < 64u; ++c) {
+        const bool wi = (with >> c) & 1ull, wo = (d->without_mask >> c) & 1ull;
+        if (!wi && !wo) continue;
+        if (wo) a.without |= 1u << a.n_masks;
+        a.off_mask[a.n_masks++] = w->off_present[c];
+    }
+    a.n_words = d->n_words; a.slots = (d->flags & GGRS_QUERY_SLOTS) ? 1u : 0u;
+    for (uint32_t k = 0; k < d->n_words; ++k) {
+        const uint32_t col = w->comps[d->words[k].comp].col_base + d->words[k].word;
+        a.col_off[k] = w->col_off[col]; a.col_ts[k] = w->col_ts[col]; a.col_wb[k] = (uint8_t)w->col_wb[col]; a.out_off[k] = lay.col_off[k];
+    }
+    a.n_units = (uint32_t)((a.len + 63) / 64);
+    memset(rep, 0, sizeof *rep);
+    rep->len = S.len;
+    // scratch: match word per unit + the sentinel | first row per unit + the total
+    const uint64_t words = (uint64_t)a.n_units + 1u, o_off = align_up(words * 8, ALIGN);
+    rc = diff_scratch(w, o_off + align_up(words * 8, ALIGN)); if (rc) return rc;
+    a.unit_match = (uint64_t*)w->d_diff; a.unit_off = (uint64_t*)(w->d_diff + o_off);
+    const uint32_t cap = w->query_max_wgs ? w->query_max_wgs : 4096u;
+    const uint32_t g_match = std::max<uint32_t>(1, std::min<uint32_t>((uint32_t)((words + TPB - 1) / TPB), cap));
+    const uint32_t g_emit = std::max<uint32_t>(1, std::min<uint32_t>((a.n_units + TPB / 64 - 1) / (TPB / 64), cap));
+    const bool emit = max_rows && a.n_units && (a.n_words || a.slots);
+    if (w->query_timed) { for (hipEvent_t& e : w->query_ev) if (!e) HIPCHK(w, hipEventCreate(&e)); HIPCHK(w, hipEventRecord(w->query_ev[0], w->stream)); }
+    hipLaunchKernelGGL(k_query_match, dim3(g_match), dim3(TPB), 0, w->stream, a);
+    HIPCHK(w, hipGetLastError());
+    if (w->query_timed) HIPCHK(w, hipEventRecord(w->query_ev[1], w->stream));
+    hipLaunchKernelGGL(k_diff_scan, dim3(1), dim3(TPB), 0, w->stream, (const uint64_t*)a.unit_match, a.unit_off, (uint32_t)words);
+    HIPCHK(w, hipGetLastError());
+    if (w->query_timed) HIPCHK(w, hipEventRecord(w->query_ev[2], w->stream));
+    if (emit) {
+        hipLaunchKernelGGL(k_query_emit, dim3(g_emit), dim3(TPB), 0, w->stream, a);
+        HIPCHK(w, hipGetLastError());
+    }
+    if (w->query_timed) HIPCHK(w, hipEventRecord(w->query_ev[3], w->stream));
+    // the count: the scan's word behind the last unit, one copy into the pinned page
+    HIPCHK(w, hipMemcpyAsync(w->h_diff, a.unit_off + a.n_units, 8, hipMemcpyDeviceToHost, w->stream));
+    HIPCHK(w, hipStreamSynchronize(w->stream));
+    if (w->query_timed) for (int k = 0; k < 3; ++k) { float ms = 0; HIPCHK(w, hipEventElapsedTime(&ms, w->query_ev[k], w->query_ev[k + 1])); w->query_us[k] = (double)ms * 1e3; }
+    rep->n_matched = *(const uint64_t*)w->h_diff;
+    rep->n_rows = std::min<uint64_t>(rep->n_matched, max_rows);
+    ++w->query_calls; w->query_last_words = a.n_words; w->query_last_masks = a.n_masks + 1u; w->query_last_units = a.n_units;
+    return GGRS_OK;
+}
+}  // namespace
+//   ggrs_dbg_set_query_grid    at most n workgroups per query launch (0: by size): the output must not depend on it
+int ggrs_dbg_set_query_grid(ggrs_world* w, int n) { if (!w || n < 0 || n > 65535) return -1; w->query_max_wgs = (uint32_t)n; return 0; }
+//   ggrs_dbg_query_launch_us   enable != 0: every later query call puts HIP events around its launches; us_out (may be NULL) receives what the match, scan and emit
+//                              launches of the last timed call took by themselves, in microseconds (scripts/bench_query.py)
+int ggrs_dbg_query_launch_us(ggrs_world* w, int enable, double* us_out) {
+    if (!w) return -1;
+    w->query_timed = enable != 0;
+    if (us_out) for (int k = 0; k < 3; ++k) us_out[k] = w->query_us[k];
+    return 0;
+}
+int ggrs_hip_query_layout(ggrs_world* w, const ggrs_query_desc* desc, uint64_t max_rows, ggrs_query_layout* out) {
+    if (!w) return GGRS_E_INVALID;
+    if (!out) return w->fail(GGRS_E_INVALID, "query_layout without a layout to fill");
+    uint64_t with = 0;
+    const int rc = query_check(w, desc, &with); if (rc) return rc;
+    if (max_rows > (1ull << 48)) return w->fail(GGRS_E_INVALID, "query_layout for %llu rows", (unsigned long long)max_rows);
+    query_layout(w, desc, max_rows, out);
+    return GGRS_OK;
+}
+int ggrs_hip_query(ggrs_world* w, int32_t frame, const ggrs_query_desc* desc, void* out_dev, uint64_t max_rows, ggrs_query_report* report) {
+    if (!w) return GGRS_E_INVALID;
+    if (w->layout_only) return w->fail(GGRS_E_NO_DEVICE, "a layout-only world has no state to query");
+    DeviceGuard dg(w);
+    int rc = diff_ready(w); if (rc) return rc;
+    DiffSide S; rc = diff_side(w, frame, &S); if (rc) return rc;
+    return query_run(w, S, desc, out_dev, max_rows, report);
+}
+int ggrs_hip_query_block(ggrs_world* w, const void* block_dev, const ggrs_query_desc* desc, void* out_dev, uint64_t max_rows, ggrs_query_report* report) {
+    if (!w) return GGRS_E_INVALID;
+    if (w->layout_only) return w->fail(GGRS_E_NO_DEVICE, "a layout-only world has no state to query");
+    if (!block_dev) return w->fail(GGRS_E_INVALID, "query_block without a block");
+    DeviceGuard dg(w);
+    int rc = diff_ready(w); if (rc) return rc;
+    Header h;
+    HIPCHK(w, hipMemcpyAsync(&h, block_dev, sizeof h, hipMemcpyDeviceToHost, w->stream));
+    HIPCHK(w, hipStreamSynchronize(w->stream));
+    if (h.len > w->capacity) return w->fail(GGRS_E_INVALID, "the block's header has len %llu > capacity %llu: not a block of this world", (unsigned long long)h.len, (unsigned long long)w->capacity);
+    DiffSide S; S.ptr = (const uint8_t*)block_dev; S.len = h.len; S.ver = nullptr; S.res_cell = 0; S.live_form = false;
+    return query_run(w, S, desc, out_dev, max_rows, report);
+}
+
 // Which kernel serves this world's request lists right now, on what kind of arena, and the state of the run-time
 // compiler -- `key=value` lines (NUL-terminated, truncated to cap).  Nothing here is needed to USE the library: it is what an
 // operator reads when a world is slower than expected (e.g. libhiprtc.so missing from a deployment image).
@@ -1388,6 +1529,8 @@ int ggrs_hip_world_kernel_info(ggrs_world* w, char* buf, uint64_t cap, uint64_t*
     add("slots_covered", std::to_string(cover));
     if (w->diff_calls) add("state_diff", std::to_string(w->diff_calls) + " calls; the last one compared " + std::to_string(w->diff_last_cols) + " columns (" + std::to_string(w->diff_last_bps) +
                                          " bytes per slot and side) and " + std::to_string(w->plan.n_masks) + " masks over " + std::to_string(w->diff_last_units) + " units of 64 slots");
+    if (w->query_calls) add("query", std::to_string(w->query_calls) + " calls; the last one fetched " + std::to_string(w->query_last_words) + " words and read " + std::to_string(w->query_last_masks) +
+                                     " masks over " + std::to_string(w->query_last_units) + " units of 64 slots");
     if (w->cparts_calls) add("checksum_parts", std::to_string(w->cparts_calls) + " calls; hashing kernel " + (w->custom_hashers ? "ggrs_jit_parts (generated: the world has a user-written hasher; module from " + w->cparts_origin + ", " +
                                              std::to_string(w->cparts_builds) + " built or loaded by this world)" : std::string("k_parts_hash (static)")));
     add("row_versions", w->knobs.row_versions ? "on" : "off (GGRS_ROW_VERSIONS=0)");

@@ -439,6 +439,11 @@ struct ggrs_world {
     hipFunction_t cparts_fn = nullptr; JitEntry* cparts_entry = nullptr; std::string cparts_origin; uint32_t cparts_builds = 0;
     bool cparts_timed = false; hipEvent_t cparts_ev[3] = {nullptr, nullptr, nullptr}; double cparts_us[2] = {0, 0};   // ggrs_dbg_parts_launch_us: the two launches of the last call by themselves
 
+    // ---- query (ggrs_hip_query / ggrs_hip_query_block): its scratch -- per 64-slot unit a match word and a first row -- is the state diff's (d_diff / h_diff: both
+    // calls are synchronous on the world's stream and never overlap).  query_max_wgs: ggrs_dbg_set_query_grid (0: by size)
+    uint32_t query_max_wgs = 0; uint64_t query_calls = 0; uint32_t query_last_words = 0, query_last_masks = 0, query_last_units = 0;
+    bool query_timed = false; hipEvent_t query_ev[4] = {nullptr, nullptr, nullptr, nullptr}; double query_us[3] = {0, 0, 0};   // ggrs_dbg_query_launch_us: match, scan, emit of the last call
+
     // ---- profiling
     bool nt_copy = false;              // non-temporal loads/stores in k_copy_state (A/B knob)
     bool prof = false;

@@ -1287,4 +1287,73 @@ __global__ __launch_bounds__(TPB) void k_parts_finish(PartsFinArgs f) {
     }
 }
 
+// ------------------------------------------------------------------ QUERY (ggrs_hip_query / ggrs_hip_query_block)
+// Query<(&A, &B), (With<C>, Without<D>)> over one packed block: the live entities below len that have every With component and no Without component, gathered
+// into dense output columns in ascending slot order.  The same stream compaction as the state diff with another predicate and a wide payload; three launches,
+// ordered by their boundaries alone (no compare-and-swap, no wait between workgroups):
+//   k_query_match  one 64-slot unit per LANE: the predicate needs only mask words (alive, one presence word per filtered component), and consecutive units' words
+//                  are consecutive, so every mask is one coalesced load.  The unit's match word is stored; the word behind the last unit is a zero sentinel.
+//   k_diff_scan    as it is, over n_units + 1 words: every unit's first row, and behind the last unit the number of matches.
+//   k_query_emit   one unit per wave-iteration; units without a match and units whose first row is at or beyond max_rows are skipped.  A matching lane loads its
+//                  fetched words (col_at, 1 / 2 / 4 / 8 bytes), QUERY_BATCH columns' loads before the first store, and stores them at row offset + (matching
+//                  lanes below it): a unit's rows are contiguous in every output column.  Nothing at or beyond row max_rows is written.
+constexpr uint32_t QUERY_BATCH = 4;                        // fetched columns whose loads are issued together
+struct QueryArgs {
+    const uint8_t* state; uint8_t* out;
+    uint64_t len, max_rows, off_alive, slots_off;
+    uint64_t off_mask[MAX_COMPS];                          // presence masks of the filtered components (With first or not: bit j of without says which)
+    uint64_t col_off[GGRS_QUERY_MAX_WORDS];                // per fetched word k: its column in the block ...
+    uint64_t out_off[GGRS_QUERY_MAX_WORDS];                // ... and in the output buffer
+    uint64_t* unit_match; uint64_t* unit_off;
+    uint32_t col_ts[GGRS_QUERY_MAX_WORDS];
+    uint32_t n_units, n_masks, without, n_words, slots;
+    uint8_t col_wb[GGRS_QUERY_MAX_WORDS];
+};
+__device__ __forceinline__ void query_store(uint8_t* p, uint64_t v, uint32_t wb) {
+    switch (wb) {
+    case 8: *reinterpret_cast<uint64_t*>(p) = v; break;
+    case 4: *reinterpret_cast<uint32_t*>(p) = (uint32_t)v; break;
+    case 2: *reinterpret_cast<uint16_t*>(p) = (uint16_t)v; break;
+    default: *p = (uint8_t)v;
+    }
+}
+__global__ __launch_bounds__(TPB) void k_query_match(QueryArgs a) {
+    for (uint32_t u = blockIdx.x * TPB + threadIdx.x; u <= a.n_units; u += gridDim.x * TPB) {
+        uint64_t m = 0;
+        if (u < a.n_units) {
+            m = *reinterpret_cast<const uint64_t*>(a.state + a.off_alive + (uint64_t)u * 8u) & diff_len_mask(a.len, (uint64_t)u * 64u);
+            for (uint32_t j = 0; j < a.n_masks; ++j) {
+                const uint64_t p = *reinterpret_cast<const uint64_t*>(a.state + a.off_mask[j] + (uint64_t)u * 8u);
+                m &= ((a.without >> j) & 1u) ? ~p : p;
+            }
+        }
+        a.unit_match[u] = m;
+    }
+}
+__global__ __launch_bounds__(TPB) void k_query_emit(QueryArgs a) {
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
+    for (uint32_t u = blockIdx.x * (TPB / 64) + wave; u < a.n_units; u += gridDim.x * (TPB / 64)) {
+        const uint64_t m = a.unit_match[u], off = a.unit_off[u];
+        if (!m || off >= a.max_rows) continue;                                   // (wave-uniform)
+        const uint64_t e = (uint64_t)u * 64u + lane, row = off + (uint64_t)__popcll(m & ((1ull << lane) - 1ull));
+        if (!((m >> lane) & 1ull) || row >= a.max_rows) continue;                // (no ballot, no barrier below: the lanes need not meet again)
+        for (uint32_t k0 = 0; k0 < a.n_words; k0 += QUERY_BATCH) {
+            uint64_t v[QUERY_BATCH];
+#pragma unroll
+            for (uint32_t i = 0; i < QUERY_BATCH; ++i) {
+                v[i] = 0;
+                if (k0 + i < a.n_words) {                                        // (uniform)
+                    const uint32_t wb = a.col_wb[k0 + i];
+                    v[i] = diff_load(a.state + col_at(a.col_off[k0 + i], a.col_ts[k0 + i], wb, e), wb);   // e < len <= the capacity: inside the column
+                }
+            }
+#pragma unroll
+            for (uint32_t i = 0; i < QUERY_BATCH; ++i)
+                if (k0 + i < a.n_words) { const uint32_t wb = a.col_wb[k0 + i]; query_store(a.out + a.out_off[k0 + i] + row * wb, v[i], wb); }
+        }
+        if (a.slots) *reinterpret_cast<uint32_t*>(a.out + a.slots_off + row * 4u) = (uint32_t)e;
+    }
+}
+
 }  // namespace ggrs

@@ -105,6 +105,27 @@ class ChecksumParts:
         return "\n".join(out)
 
 
+@dataclass
+class QueryResult:
+    """World.query: the matching entities of one world state as dense device columns (ggrs_query_report + views into the one output buffer).  Row i is the
+    i-th matching slot, ascending.  `columns[k]` holds fetched word k (`words[k]` = (component, word)) of the n_rows rows as a zero-copy torch view of
+    `buffer` with the word's width (uint8 / int16 / int32 / int64: the words' bits, reinterpret them with .view(torch.float32) and the like); `slots` the
+    rows' slots (int32 bits of a u32; None without slots=True).  n_matched is exact whatever max_rows was."""
+    len: int
+    n_matched: int
+    n_rows: int
+    slots: object
+    columns: list
+    words: List[tuple]
+    buffer: object
+
+    def numpy(self):
+        """Host copies: (slots or None, [columns]) as unsigned numpy arrays, the dtypes World.download_word returns."""
+        un = {1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}
+        cols = [c.cpu().numpy().view(un[c.element_size()]) for c in self.columns]
+        return (None if self.slots is None else self.slots.cpu().numpy().view(np.uint32)), cols
+
+
 class WorldBase:
     """Backend-neutral surface.  `bevy_ggrs_amd.World` binds it to libggrs_hip.so; the CPU
     oracle (tests only) binds the same surface to oracle/_build/libggrs_oracle.so."""
@@ -713,6 +734,61 @@ class World(WorldBase):
             name = "Entity" if p.kind == _ffi.PART_ENTITY else self._comps[p.id][0] if p.kind == _ffi.PART_COMPONENT else res_names[p.id]
             parts[name] = int(p.value); counts[name] = int(p.n_hashed)
         return ChecksumParts(parts=parts, counts=counts, len=int(rep.len), active=int(rep.active), checksum=int(rep.checksum_lo) | (int(rep.checksum_hi) << 64))
+
+    # ---- query (include/ggrs_hip.h: ggrs_hip_query_layout / ggrs_hip_query / ggrs_hip_query_block)
+    def query_desc(self, fetch=(), with_=(), without=(), slots=True) -> "_ffi.QueryDesc":
+        """The ggrs_query_desc of World.query's arguments: `fetch` items are component ids (all words of each) or (comp, word) pairs."""
+        words = []
+        for f in fetch:
+            if isinstance(f, (tuple, list)): words.append((int(f[0]), int(f[1])))
+            else:
+                if not 0 <= int(f) < len(self._comps): raise ValueError(f"fetch names component {f}: the world has {len(self._comps)}")
+                words += [(int(f), k) for k in range(self._comps[int(f)][2])]
+        if len(words) > _ffi.QUERY_MAX_WORDS: raise ValueError(f"a query fetches at most {_ffi.QUERY_MAX_WORDS} words, not {len(words)}")
+        d = _ffi.QueryDesc()
+        d.with_mask = sum(1 << int(c) for c in set(with_)); d.without_mask = sum(1 << int(c) for c in set(without))
+        d.n_words = len(words); d.flags = _ffi.QUERY_SLOTS if slots else 0
+        for k, (c, wd) in enumerate(words): d.words[k].comp = c; d.words[k].word = wd
+        return d
+
+    def query_layout(self, desc: "_ffi.QueryDesc", max_rows: int) -> "_ffi.QueryLayout":
+        """Where a query of max_rows rows puts its columns in the one output buffer (host arithmetic: also on a layout-only world)."""
+        lay = _ffi.QueryLayout()
+        self._check(self._lib.ggrs_hip_query_layout(self._p, C.byref(desc), max_rows, C.byref(lay)))
+        return lay
+
+    def query(self, state, fetch, *, with_=(), without=(), slots=True, max_rows: Optional[int] = None, out=None) -> QueryResult:
+        """Query<(fetch ..), (With<..>, Without<..>)> over one world state: the live entities below len that have every fetched and every with_ component and no
+        without component, in ascending slot order, gathered into dense columns on the device.  `state`: a ring frame, LIVE, or a block tensor from snapshot_copy.
+        `fetch`: component ids (all words of each) or (comp, word) pairs.  max_rows=None: the world's len.  `out`: a torch.uint8 device tensor to write into
+        (at least the layout's total_bytes) instead of a new one.  Returns a QueryResult of zero-copy views into the buffer."""
+        import torch
+        desc = self.query_desc(fetch, with_, without, slots)
+        if max_rows is None: max_rows = self.len
+        lay = self.query_layout(desc, max_rows)
+        need = int(lay.total_bytes)
+        if out is None:
+            out = torch.empty(max(need, 1), dtype=torch.uint8, device=f"cuda:{self.device}")
+        elif out.dtype != torch.uint8 or out.numel() < need or not out.is_cuda or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous torch.uint8 device tensor of at least {need} bytes")
+        torch.cuda.current_stream(out.device).synchronize()       # (the launches run on the world's stream)
+        rep = _ffi.QueryReport()
+        if hasattr(state, "data_ptr"):
+            if state.dtype != torch.uint8 or state.numel() != self.state_bytes() or not state.is_cuda or not state.is_contiguous():
+                raise ValueError(f"a block is a contiguous torch.uint8 device tensor of {self.state_bytes()} bytes")
+            torch.cuda.current_stream(state.device).synchronize()
+            self._check(self._lib.ggrs_hip_query_block(self._p, state.data_ptr(), C.byref(desc), out.data_ptr(), max_rows, C.byref(rep)))
+        else:
+            self._check(self._lib.ggrs_hip_query(self._p, int(state), C.byref(desc), out.data_ptr(), max_rows, C.byref(rep)))
+        n = int(rep.n_rows)
+        dt = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
+        columns = []
+        for k in range(desc.n_words):
+            wb, off = int(lay.word_bytes[k]), int(lay.col_off[k])
+            columns.append(out[off:off + n * wb].view(dt[wb]))
+        slot_col = out[int(lay.slots_off):int(lay.slots_off) + n * 4].view(torch.int32) if slots else None
+        return QueryResult(len=int(rep.len), n_matched=int(rep.n_matched), n_rows=n, slots=slot_col, columns=columns,
+                           words=[(int(desc.words[k].comp), int(desc.words[k].word)) for k in range(desc.n_words)], buffer=out)
 
     def live_state_ptr(self) -> int:
         p = C.c_void_p()

@@ -494,6 +494,19 @@ struct HipBackend {
         parts->resize(rc == GGRS_OK ? report->n_parts : 0);
         return rc;
     }
+    // query (include/ggrs_hip.h): reading the world back -- Query<(&A, ..), (With<..>, Without<..>)> in PostUpdate or the render extract.  The matching live entities of
+    // a ring frame, the live world (GGRS_DIFF_LIVE) or a block in ring-slot form, gathered in ascending slot order into the caller's device buffer of at least
+    // query_layout(..).total_bytes bytes; the report says how many matched and how many rows were written
+    static ggrs_query_desc query_desc(const std::vector<ggrs_query_word>& fetch, uint64_t with_mask = 0, uint64_t without_mask = 0, bool slots = true) {
+        ggrs_query_desc d{};
+        d.with_mask = with_mask; d.without_mask = without_mask; d.flags = slots ? GGRS_QUERY_SLOTS : 0u;
+        d.n_words = (uint32_t)(fetch.size() < GGRS_QUERY_MAX_WORDS ? fetch.size() : GGRS_QUERY_MAX_WORDS);
+        for (uint32_t k = 0; k < d.n_words; ++k) d.words[k] = fetch[k];
+        return d;
+    }
+    int query_layout(const ggrs_query_desc& desc, uint64_t max_rows, ggrs_query_layout* out) { return ggrs_hip_query_layout(w, &desc, max_rows, out); }
+    int query(int32_t frame, const ggrs_query_desc& desc, void* out_dev, uint64_t max_rows, ggrs_query_report* report) { return ggrs_hip_query(w, frame, &desc, out_dev, max_rows, report); }
+    int query_block(const void* block_dev, const ggrs_query_desc& desc, void* out_dev, uint64_t max_rows, ggrs_query_report* report) { return ggrs_hip_query_block(w, block_dev, &desc, out_dev, max_rows, report); }
 };
 
 // ---------------------------------------------------------------- speculative fan-out (no reference analogue: SURVEY.md 8e)

@@ -1020,6 +1020,53 @@ int ggrs_hip_checksum_parts(ggrs_world* w, int32_t frame, ggrs_parts_report* rep
 int ggrs_hip_checksum_parts_block(ggrs_world* w, const void* block_dev, ggrs_parts_report* report, ggrs_checksum_part* parts, uint32_t max_parts);
 
 /* -------------------------------------------------------------------------------------------
+ * QUERY: gather the matching live entities of one world state into dense columns in device memory -- what a bevy_ggrs game does every rendered frame with
+ * Query<(&Transform, &Velocity), (With<Rollback>, Without<Stunned>)>: only live entities, only those that match, packed, in a stable order.  The state is a
+ * complete packed block; three small launches (match, scan, emit) read its masks once and the fetched columns once, beside the tick and never on its path.
+ *
+ *   ggrs_hip_query_layout   where things land in the ONE output buffer for max_rows rows: pure host arithmetic, also on a GGRS_WORLD_LAYOUT_ONLY world.
+ *                           Column starts are 256-byte aligned, columns are in desc order, the slots last; total_bytes is what the caller allocates.
+ *   ggrs_hip_query          the state is ring frame `frame`, or the live world (GGRS_DIFF_LIVE).
+ *   ggrs_hip_query_block    the state is a block in ring-slot form somewhere in device memory: what ggrs_hip_snapshot_copy or a GGRS_ADOPT_BROADCAST
+ *                           produces.  Its RollbackOrdered::len is read from its header.
+ *
+ * Slot s matches iff s < len, its alive bit is set, every component of with_mask is present and no component of without_mask is.  The component of every
+ * fetched word counts as named in with_mask.  An entity marked RollbackDespawned has its alive bit clear and does not match (a disabled entity is invisible
+ * to default queries).  Rows are in ascending slot order (the RollbackOrdered order); row i is the i-th matching slot; fetched word k of row i is at
+ * out_dev + col_off[k] + i * word_bytes[k], its slot a uint32_t at out_dev + slots_off + i * 4.  n_matched is exact whatever max_rows is;
+ * n_rows = min(n_matched, max_rows); bytes at or beyond row n_rows of any column, and between columns, are not written.  The result is byte-identical for
+ * every launch geometry and from run to run.  Both query calls bring deferred Saves and a lazily skipped live block up to date first and return when out_dev
+ * is written.
+ * Errors, GGRS_E_INVALID with a message: a component id the world does not have or a word index beyond the component; n_words above
+ * GGRS_QUERY_MAX_WORDS; the same component in with_mask (named, or implied by a fetch) and in without_mask; unknown flags; out_dev == NULL with
+ * max_rows > 0; fetching words of a component under a Strategy from a ring frame or a block (the slot holds Stored words; GGRS_DIFF_LIVE is served, and
+ * filtering on its presence is served everywhere); naming a GGRS_COMP_NO_ROLLBACK component in a fetch or a filter against a ring frame or a block (it is
+ * live-only; GGRS_DIFF_LIVE is served); GGRS_QUERY_SLOTS in a world whose capacity exceeds 2^32; enqueued batches that are uncollected.  GGRS_E_NO_SNAPSHOT
+ * for a frame the ring does not hold; GGRS_E_NO_DEVICE from the two query calls on a layout-only world.
+ * Out of scope: interleaved (AoS) rows, Option<&C> fetches, a slot-range restriction, an asynchronous form without the stream wait, device resources
+ * (ggrs_hip_resource_read), the fan-out's retained branches beyond what ggrs_hip_query_block serves, Stored-form fetches. */
+#define GGRS_QUERY_MAX_WORDS 32
+#define GGRS_QUERY_SLOTS     1u            /* flags: also write each row's slot (u32) */
+typedef struct { uint32_t comp; uint32_t word; } ggrs_query_word;
+typedef struct {
+    uint64_t with_mask;          /* bit c: the entity must have component c        (With<C>)    */
+    uint64_t without_mask;       /* bit c: the entity must NOT have component c    (Without<C>) */
+    uint32_t n_words;            /* fetched words, 0 .. GGRS_QUERY_MAX_WORDS */
+    uint32_t flags;              /* GGRS_QUERY_SLOTS */
+    ggrs_query_word words[GGRS_QUERY_MAX_WORDS];
+} ggrs_query_desc;
+typedef struct {                 /* where things land in the one output buffer */
+    uint64_t total_bytes;
+    uint64_t slots_off;          /* valid with GGRS_QUERY_SLOTS */
+    uint64_t col_off[GGRS_QUERY_MAX_WORDS];
+    uint32_t word_bytes[GGRS_QUERY_MAX_WORDS];
+} ggrs_query_layout;
+typedef struct { uint64_t len; uint64_t n_matched; uint64_t n_rows; } ggrs_query_report;
+int ggrs_hip_query_layout(ggrs_world* w, const ggrs_query_desc* desc, uint64_t max_rows, ggrs_query_layout* out);
+int ggrs_hip_query(ggrs_world* w, int32_t frame, const ggrs_query_desc* desc, void* out_dev, uint64_t max_rows, ggrs_query_report* report);
+int ggrs_hip_query_block(ggrs_world* w, const void* block_dev, const ggrs_query_desc* desc, void* out_dev, uint64_t max_rows, ggrs_query_report* report);
+
+/* -------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): per-kernel-class HIP-event timing on the world's stream.
  * ------------------------------------------------------------------------------------------- */
 #define GGRS_KERNEL_SAVE     0u
@@ -1048,7 +1095,7 @@ int ggrs_hip_host_timeline(ggrs_world* w, int enable, double* us_out, uint64_t* 
  * Introspection: which kernel serves this world's request lists right now and why, what kind of arena
  * it lives on, whether the run-time compiler (libhiprtc.so, dlopen'ed) is available.  `key=value` lines,
  * NUL-terminated; *needed = bytes incl. the NUL, min(cap, *needed) are copied.  Keys: sealed, arena,
- * arena_bytes, hiprtc, generated_kernel, generated_kernel_origin, request_group_kernel, checksum_fold, kernarg_bytes, group_caps, specialised_kernel, slots_covered, row_versions, peer_view (worlds with peer bindings), effect_inbox (worlds with effect bindings), device_resources (worlds with device resources), depth_parallel_roles, reduce_inbox (worlds with reduce bindings: stripes, words, applies so far), remote_inbox (worlds with remote bindings: components, applies so far), sum_partials (worlds with sum bindings: units, words, applies so far), value_inbox (worlds with value bindings: components, bindings, bytes allocated, applies so far), state_diff (once a state diff ran: calls, and the columns, bytes per slot and units of the last one), checksum_parts (once a parts call ran: calls, the hashing kernel and where its module came from, builds).
+ * arena_bytes, hiprtc, generated_kernel, generated_kernel_origin, request_group_kernel, checksum_fold, kernarg_bytes, group_caps, specialised_kernel, slots_covered, row_versions, peer_view (worlds with peer bindings), effect_inbox (worlds with effect bindings), device_resources (worlds with device resources), depth_parallel_roles, reduce_inbox (worlds with reduce bindings: stripes, words, applies so far), remote_inbox (worlds with remote bindings: components, applies so far), sum_partials (worlds with sum bindings: units, words, applies so far), value_inbox (worlds with value bindings: components, bindings, bytes allocated, applies so far), state_diff (once a state diff ran: calls, and the columns, bytes per slot and units of the last one), checksum_parts (once a parts call ran: calls, the hashing kernel and where its module came from, builds), query (once a query ran: calls, and the fetched words, masks and units of the last one).
  * ------------------------------------------------------------------------------------------- */
 int ggrs_hip_world_kernel_info(ggrs_world* w, char* buf, uint64_t cap, uint64_t* needed);
 

@@ -332,6 +332,49 @@ pub struct ggrs_parts_report {
     pub n_parts: u32,
 }
 
+/// A query fetches at most this many words.
+pub const GGRS_QUERY_MAX_WORDS: usize = 32;
+/// Query flag: also write each row's slot (u32).
+pub const GGRS_QUERY_SLOTS: u32 = 1;
+
+/// One fetched word of a query: word `word` of component `comp`.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct ggrs_query_word {
+    pub comp: u32,
+    pub word: u32,
+}
+
+/// `Query<(fetched words ..), (With<..>, Without<..>)>`: a fetched word's component counts as named in `with_mask`.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct ggrs_query_desc {
+    pub with_mask: u64,
+    pub without_mask: u64,
+    pub n_words: u32,
+    pub flags: u32,
+    pub words: [ggrs_query_word; GGRS_QUERY_MAX_WORDS],
+}
+
+/// Where a query's columns land in its one output buffer.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct ggrs_query_layout {
+    pub total_bytes: u64,
+    pub slots_off: u64,
+    pub col_off: [u64; GGRS_QUERY_MAX_WORDS],
+    pub word_bytes: [u32; GGRS_QUERY_MAX_WORDS],
+}
+
+/// What a query found: `n_matched` is exact, `n_rows = min(n_matched, max_rows)` rows were written.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct ggrs_query_report {
+    pub len: u64,
+    pub n_matched: u64,
+    pub n_rows: u64,
+}
+
 impl ggrs_request {
     pub const fn zeroed() -> Self {
         Self { kind: 0, frame: 0, dt_bits: 0, n_inputs: 0, inputs: core::ptr::null(), status: core::ptr::null(), spawn_count: 0, spawn_vx: core::ptr::null(), spawn_vy: core::ptr::null(),
@@ -418,6 +461,10 @@ unsafe extern "C" {
     // ---- checksum parts: the per-component ChecksumParts of a ring frame, the live world (GGRS_DIFF_LIVE) or a block in ring-slot form
     pub fn ggrs_hip_checksum_parts(w: *mut ggrs_world, frame: i32, report: *mut ggrs_parts_report, parts: *mut ggrs_checksum_part, max_parts: u32) -> c_int;
     pub fn ggrs_hip_checksum_parts_block(w: *mut ggrs_world, block_dev: *const c_void, report: *mut ggrs_parts_report, parts: *mut ggrs_checksum_part, max_parts: u32) -> c_int;
+    // ---- query: the matching live entities of a ring frame, the live world or a block, gathered into dense device columns (the render extract reads these)
+    pub fn ggrs_hip_query_layout(w: *mut ggrs_world, desc: *const ggrs_query_desc, max_rows: u64, out: *mut ggrs_query_layout) -> c_int;
+    pub fn ggrs_hip_query(w: *mut ggrs_world, frame: i32, desc: *const ggrs_query_desc, out_dev: *mut c_void, max_rows: u64, report: *mut ggrs_query_report) -> c_int;
+    pub fn ggrs_hip_query_block(w: *mut ggrs_world, block_dev: *const c_void, desc: *const ggrs_query_desc, out_dev: *mut c_void, max_rows: u64, report: *mut ggrs_query_report) -> c_int;
     // ---- speculative fan-out across GPUs (RCCL behind the C ABI; the host carries the 128-byte ncclUniqueId between ranks)
     pub fn ggrs_hip_fanout_unique_id(id_out: *mut u8) -> c_int;
     pub fn ggrs_hip_fanout_init(w: *mut ggrs_world, id: *const u8, rank: c_int, world_size: c_int, out: *mut *mut ggrs_fanout) -> c_int;

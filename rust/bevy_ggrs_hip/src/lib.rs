@@ -126,6 +126,32 @@ impl HipWorld {
         self.check(unsafe { ffi::ggrs_hip_download_alive(self.raw, m.as_mut_ptr(), m.len() as u64) });
         m
     }
+    /// The desc of `Query<(fetch ..), (With<with ..>, Without<without ..>)>`: `fetch` holds (component id, word) pairs.
+    pub fn query_desc(fetch: &[(u32, u32)], with: &[u32], without: &[u32], slots: bool) -> ffi::ggrs_query_desc {
+        assert!(fetch.len() <= ffi::GGRS_QUERY_MAX_WORDS, "a query fetches at most GGRS_QUERY_MAX_WORDS words");
+        let mut d = ffi::ggrs_query_desc { with_mask: 0, without_mask: 0, n_words: fetch.len() as u32, flags: if slots { ffi::GGRS_QUERY_SLOTS } else { 0 },
+                                           words: [ffi::ggrs_query_word { comp: 0, word: 0 }; ffi::GGRS_QUERY_MAX_WORDS] };
+        for c in with { d.with_mask |= 1u64 << c; }
+        for c in without { d.without_mask |= 1u64 << c; }
+        for (k, (comp, word)) in fetch.iter().enumerate() { d.words[k] = ffi::ggrs_query_word { comp: *comp, word: *word }; }
+        d
+    }
+    /// Where a query of `max_rows` rows puts its columns in the one output buffer; `total_bytes` is what the caller allocates on the device.
+    pub fn query_layout(&self, desc: &ffi::ggrs_query_desc, max_rows: u64) -> ffi::ggrs_query_layout {
+        let mut lay: ffi::ggrs_query_layout = unsafe { core::mem::zeroed() };
+        self.check(unsafe { ffi::ggrs_hip_query_layout(self.raw, desc, max_rows, &mut lay) });
+        lay
+    }
+    /// Reading the world back (`Query<..>` in `PostUpdate` / the render extract): the matching live entities of ring frame `frame`, or of the live
+    /// world (`None`), gathered in ascending slot order into the caller's device buffer of at least `query_layout(..).total_bytes` bytes.
+    ///
+    /// # Safety
+    /// `out_dev` must be device memory of that size on the world's device, not in use by other streams.
+    pub unsafe fn query(&self, frame: Option<i32>, desc: &ffi::ggrs_query_desc, out_dev: *mut core::ffi::c_void, max_rows: u64) -> ffi::ggrs_query_report {
+        let mut rep = ffi::ggrs_query_report { len: 0, n_matched: 0, n_rows: 0 };
+        self.check(unsafe { ffi::ggrs_hip_query(self.raw, frame.unwrap_or(ffi::GGRS_DIFF_LIVE), desc, out_dev, max_rows, &mut rep) });
+        rep
+    }
 }
 impl Drop for HipWorld {
     fn drop(&mut self) {
