@@ -309,7 +309,7 @@ def _extra_state(w, more=None):
 
 
 def run(seed, make_a, make_b, n_lists=30, big=False, state_every=6, generic=False, max_n=None, box=False, start_frame=None, variant=None, ring_sweep=False, on_end=None,
-        scenario=None, after_list=None, extra_state=None):
+        scenario=None, after_list=None, extra_state=None, witness=None):
     """variant: keywords of the scenario (GenericScenario(plain=True), BoxScenario(player_rollback=True)).
     ring_sweep: once mid-session (after list n_lists // 2) and after the last list, every frame the ring holds at or above ConfirmedFrameCount is loaded,
     newest first (a rollback pops what is newer), by a list [LoadGameState(f)] of its own on both backends, and the WHOLE state is compared: what a ring slot
@@ -320,7 +320,11 @@ def run(seed, make_a, make_b, n_lists=30, big=False, state_every=6, generic=Fals
     n, depth, capacity, with_spawn, spawn_budget, describe(), build(world)) and may have advance(frame, spawn), words(comp, word, count), extra_edit(x, A, B, ids), spawns(request) and no_despawn_rollback: see _adv, _mutate and the log line below.
     after_list(A, B, k, ctx): called after a list was handled synchronously and after every drain that collected something -- never while a list is in flight.
     extra_state(world) -> dict: merged into what is compared beside the component state, after lists and in the ring sweep.
-    With these three at their defaults the random draws are the ones made without them (test_the_streams_of_existing_seeds_did_not_move)."""
+    witness: an object that is shown what the run holds (tests/inspect_witness.py): on_list(A, B, reqs, checksums) after a list was handled synchronously and -- with
+    in_flight=True: B may still hold uncollected lists and A is ahead of it -- for every enqueued list once it has been drained, in order, with the oracle's checksums;
+    before_sweep(A, B, frames) after the drain and before the first Load of a ring sweep; on_sweep_frame(A, B, f) after both backends loaded f and their states
+    compared equal; after_sweep(A, B, ctx) at the end of the sweep.  It draws nothing from sc.rng.
+    With these four at their defaults the random draws are the ones made without them (test_the_streams_of_existing_seeds_did_not_move)."""
     if scenario is not None: sc = scenario(seed, big, max_n)
     else: sc = (BoxScenario if box else GenericScenario if generic else Scenario)(seed, big=big, max_n=max_n, **(variant or {}))
     A, B = make_a(sc), make_b(sc)
@@ -339,13 +343,15 @@ def run(seed, make_a, make_b, n_lists=30, big=False, state_every=6, generic=Fals
         def drain():
             k0 = None
             while pending:
-                k0, want, ctx0 = pending.pop(0)
+                k0, want, ctx0, reqs0 = pending.pop(0)
                 got = B.collect_checksums()
                 assert want == list(got), f"checksums of the enqueued list {k0} differ:\n{ctx0}\n{want}\n{got}"
+                if witness is not None: witness.on_list(A, B, reqs0, want, in_flight=True)
             if k0 is not None and after_list is not None: after_list(A, B, k0, "\n".join(log[:1] + log[-6:]))
 
         def sweep(when):
             drain()
+            if witness is not None: witness.before_sweep(A, B, [f for f in st["ring"].frames if f >= st["confirmed"]])
             for f in [f for f in st["ring"].frames if f >= st["confirmed"]]:
                 log.append(f"L{f}   (sweep)")
                 ctx = f"ring sweep {when}, frame {f}:\n" + "\n".join(log[:1] + log[-10:]) + "\n"
@@ -356,6 +362,8 @@ def run(seed, make_a, make_b, n_lists=30, big=False, state_every=6, generic=Fals
                     f"frame / len / snapshots differ: {(A.frame, A.len, A.snapshot_count())} vs {(B.frame, B.len, B.snapshot_count())} (model frame {f}) in the {ctx}"
                 cm.assert_states_equal(cm.snapshot_state(A, ids), cm.snapshot_state(B, ids), ctx)
                 cm.assert_states_equal(_extra_state(A, extra_state), _extra_state(B, extra_state), "RollbackDespawned markers, " + ctx)
+                if witness is not None: witness.on_sweep_frame(A, B, f)
+            if witness is not None: witness.after_sweep(A, B, f"ring sweep {when}:\n" + "\n".join(log[:1] + log[-10:]) + "\n")
 
         for k in range(n_lists):
             if ring_sweep and k == n_lists // 2 + 1: sweep("mid-session")
@@ -369,7 +377,7 @@ def run(seed, make_a, make_b, n_lists=30, big=False, state_every=6, generic=Fals
             ctx = "\n".join(log[:1] + log[-6:])
             if use_async and sc.rng.random() < 0.4 and len(pending) < 3 and k != n_lists - 1:
                 # up to three lists in flight on B (enqueue / collect: the host-side bookkeeping of a list happens at enqueue time)
-                B.enqueue_requests(reqs); pending.append((k, list(ca), ctx))
+                B.enqueue_requests(reqs); pending.append((k, list(ca), ctx, reqs))
                 log[-1] += "   (enqueued)"
                 continue
             drain()
@@ -378,6 +386,7 @@ def run(seed, make_a, make_b, n_lists=30, big=False, state_every=6, generic=Fals
             assert (A.frame, A.len, A.snapshot_count()) == (B.frame, B.len, B.snapshot_count()) == (st["F"], A.len, A.snapshot_count()), \
                 f"frame / len / snapshots differ after list {k}: {(A.frame, A.len, A.snapshot_count())} vs {(B.frame, B.len, B.snapshot_count())} (model frame {st['F']})\n{ctx}"
             if after_list is not None: after_list(A, B, k, ctx)
+            if witness is not None: witness.on_list(A, B, reqs, list(ca))
             if k % state_every == state_every - 1 or k == n_lists - 1:
                 cm.assert_states_equal(cm.snapshot_state(A, ids), cm.snapshot_state(B, ids), f"after list {k}:\n{ctx}\n")
                 cm.assert_states_equal(_extra_state(A, extra_state), _extra_state(B, extra_state), f"RollbackDespawned markers after list {k}:\n{ctx}\n")
