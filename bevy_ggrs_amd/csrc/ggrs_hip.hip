@@ -1490,7 +1490,7 @@ int ggrs_hip_world_kernel_info(ggrs_world* w, char* buf, uint64_t cap, uint64_t*
                              : "k_gen_finalize";
         add("checksum_fold", f);
         add("kernarg_bytes", std::to_string(w->jl ? w->jl->bytes : 0));
-        add("lazy_live_block", !lazy_live_possible(w) ? "off (live-only state, a handed-out pointer, results on the device, or per-request launches)"
+        add("lazy_live_block", !lazy_live_possible(w) ? "off (live-only state, a component under a Strategy, a handed-out pointer, results on the device, or per-request launches)"
                                    : cover <= JIT_NT_MIN_SLOTS ? "off (the world fits the caches: the live block's bytes are not what bounds the launch)"
                                    : "on after " + std::to_string(LAZY_LIVE_STREAK) + " lists in a row that open with a LoadGameState: " + std::to_string(w->lazy_skips) + " lists left it unwritten, " +
                                      std::to_string(w->lazy_materialised) + " materialised on demand");

@@ -487,6 +487,9 @@ struct JitBatch {
 constexpr uint32_t LAZY_LIVE_STREAK = 8;
 inline bool lazy_live_allowed(const ggrs_world* w) {                 // (what a layout-only world -- `make aot` on a machine without a GPU -- can tell)
     if (!w->lazy_live_on || w->live_handed_out || w->has_nr || w->marks_possible || w->device_results_only || jit_dev_spawn(w)) return false;
+    // a component under a Strategy: a ring slot holds store(x), and materialise_live would build the live world from load(store(x)) where the list that left
+    // it unwritten had advanced x itself -- one Strategy::load more than the request list holds (a lossy or a non-idempotent Strategy shows it in the next Save)
+    for (const Comp& c : w->comps) if (c.s_n_words && !c.no_rollback) return false;
     if (world_has_peers(w)) return false;                            // peer bindings: the next group's publish reads what this one leaves -- every block is written (no deferred Saves either)
     if (world_has_effects(w)) return false;                          // effect bindings: k_apply_effects combines the frame's sends into the live block -- every group writes it (no deferred Saves either)
     if (world_has_remote(w)) return false;                           // remote bindings: k_apply_remote edits the live block's masks and columns behind the group's launch -- every group writes it (no deferred Saves either)

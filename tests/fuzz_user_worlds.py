@@ -40,12 +40,17 @@ class OracleAdapter:
     """An OracleWorld (+ the resource model of the skirmish) behind the surface fuzz_util.run drives.  Everything but handle_requests, resource_write and close is the
     oracle's own.  handle_requests walks the list request by request (w.land() behind an AdvanceFrame, w.on_load() behind a Load): the model snapshots on Save, restores on Load, runs the resource system in front of an
     AdvanceFrame and lands the frame's reductions and sums behind it; a Save's checksum is the oracle's XOR the model's resource parts.  begin_frame (the hook the
-    build functions hand out) is called before EVERY AdvanceFrame -- hook=False leaves it out: what the hazard tests compare with."""
+    build functions hand out) is called before EVERY AdvanceFrame -- hook=False leaves it out: what the hazard tests compare with.
+    Worlds of other helper modules (fuzz_feature_worlds.py) use the same walk: a world without begin_frame / land / on_load passes hook=False, host_apply=False and
+    sets no on_load; a model that has its own `write(res, words)` takes the host's resource writes that way; `more` are further attributes of the adapter; and
+    `one(r)` -- what hands ONE request to the oracle -- is there to be overridden (a per-frame count, a deliberately wrong restatement)."""
 
-    def __init__(self, oracle, model=None, stats=None, hook=True, host_apply=True):
-        self.__dict__.update(oracle=oracle, model=model, stats=stats, hook=hook, host_apply=host_apply)
+    def __init__(self, oracle, model=None, stats=None, hook=True, host_apply=True, **more):
+        self.__dict__.update(oracle=oracle, model=model, stats=stats, hook=hook, host_apply=host_apply, **more)
 
     def __getattr__(self, k): return getattr(self.oracle, k)
+
+    def one(self, r): return self.oracle.handle_requests([r])
 
     def handle_requests(self, reqs):
         o, model, out = self.oracle, self.model, []
@@ -56,14 +61,15 @@ class OracleAdapter:
                 elif isinstance(r, bg.LoadGameState): model.load(r.frame)
                 else: model.begin(int(r.inputs[0]) if len(r.inputs) else 0)
             if adv and self.hook: o.begin_frame()
-            cs = o.handle_requests([r])
+            cs = self.one(r)
             if adv and self.host_apply: o.land()
-            if isinstance(r, bg.LoadGameState): o.on_load()
+            if isinstance(r, bg.LoadGameState) and hasattr(o, "on_load"): o.on_load()
             if adv and model is not None: model.end()
             if isinstance(r, bg.SaveGameState): out.append(cs[0] ^ (model.part() if model is not None else 0))
         return out
 
     def resource_write(self, res, words):
+        if hasattr(self.model, "write"): return self.model.write(res, words)
         self.model.cur[res] = [int(x) for x in words]
 
     def close(self): self.oracle.close()
