@@ -211,6 +211,18 @@ class QueryReport(C.Structure):
     _fields_ = [("len", C.c_uint64), ("n_matched", C.c_uint64), ("n_rows", C.c_uint64)]
 
 
+SCATTER_WRITE, SCATTER_INSERT, SCATTER_REMOVE, SCATTER_DESPAWN = 0, 1, 2, 3      # GGRS_SCATTER_*
+SCATTER_OPS = {"write": SCATTER_WRITE, "insert": SCATTER_INSERT, "remove": SCATTER_REMOVE, "despawn": SCATTER_DESPAWN}
+
+
+class ScatterDesc(C.Structure):
+    _fields_ = [("op", C.c_uint32), ("flags", C.c_uint32), ("comp_mask", C.c_uint64), ("n_words", C.c_uint32), ("pad", C.c_uint32), ("words", QueryWord * QUERY_MAX_WORDS)]
+
+
+class ScatterReport(C.Structure):
+    _fields_ = [("len", C.c_uint64), ("n_rows", C.c_uint64), ("n_applied", C.c_uint64), ("n_dead", C.c_uint64), ("n_absent", C.c_uint64), ("first_bad_row", C.c_uint64)]
+
+
 # every symbol include/ggrs_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SIGNATURES = {
@@ -298,6 +310,7 @@ SIGNATURES = {
     "ggrs_hip_query_layout": (C.c_int, [_P, C.POINTER(QueryDesc), C.c_uint64, C.POINTER(QueryLayout)]),
     "ggrs_hip_query": (C.c_int, [_P, C.c_int32, C.POINTER(QueryDesc), _P, C.c_uint64, C.POINTER(QueryReport)]),
     "ggrs_hip_query_block": (C.c_int, [_P, _P, C.POINTER(QueryDesc), _P, C.c_uint64, C.POINTER(QueryReport)]),
+    "ggrs_hip_scatter": (C.c_int, [_P, C.POINTER(ScatterDesc), _P, C.c_uint64, C.c_uint64, C.POINTER(ScatterReport)]),
     "ggrs_hip_fanout_unique_id": (C.c_int, [C.POINTER(C.c_uint8)]),
     "ggrs_hip_fanout_init": (C.c_int, [_P, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.POINTER(_P)]),
     "ggrs_hip_fanout_sync_confirmed": (C.c_int, [_P, C.c_int]),
@@ -324,6 +337,7 @@ DEBUG_SIGNATURES = {
     "ggrs_dbg_parts_launch_us": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double)]),
     "ggrs_dbg_set_query_grid": (C.c_int, [_P, C.c_int]),
     "ggrs_dbg_query_launch_us": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double)]),
+    "ggrs_dbg_scatter_launch_us": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double)]),
     "ggrs_dbg_parts_kernel_source": (C.c_int, [_P, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_int]),
 }
 

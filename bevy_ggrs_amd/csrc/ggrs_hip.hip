@@ -135,6 +135,7 @@ void ggrs_hip_world_destroy(ggrs_world* w) {
     if (w->h_cparts) (void)hipHostFree(w->h_cparts);
     for (hipEvent_t e : w->cparts_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : w->query_ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : w->scatter_ev) if (e) (void)hipEventDestroy(e);
     jit_release(w->cparts_entry);
     sp_release(w);
     peer_view_release(w);
@@ -1442,6 +1443,115 @@ int ggrs_hip_query_block(ggrs_world* w, const void* block_dev, const ggrs_query_
     return query_run(w, S, desc, out_dev, max_rows, report);
 }
 
+// ---- SCATTER (include/ggrs_hip.h; the kernels: kernels.hpp k_scatter_check / k_scatter_apply) ------------------------------------------------------------------------
+// Nothing here is on the tick's path.  The target is the live block; the input buffer's layout is the query's (query_layout); the record and the report travel as
+// the query's count does (diff_scratch and its pinned page).  The host's bookkeeping is what ggrs_hip_upload_word / _insert_component / _remove_component / _despawn
+// do per call, done once -- and only when the rows were applied.
+namespace {
+constexpr uint32_t SCATTER_MAX_WGS = 2048;                 // 8 workgroups per CU: full occupancy; beyond it a lane takes several rows (grid-stride)
+// what needs no state: the desc against the world's components.  *masks: the components whose presence word the apply launch reads (WRITE) or edits (INSERT, REMOVE)
+int scatter_check(ggrs_world* w, const ggrs_scatter_desc* d, const void* in_dev, uint64_t stride_rows, uint64_t n_rows, const ggrs_scatter_report* rep, uint64_t* masks) {
+    static const char* const OPS[] = {"WRITE", "INSERT", "REMOVE", "DESPAWN"};
+    if (!d) return w->fail(GGRS_E_INVALID, "scatter without a desc");
+    if (d->op > GGRS_SCATTER_DESPAWN) return w->fail(GGRS_E_INVALID, "unknown scatter op %u", d->op);
+    if (d->flags) return w->fail(GGRS_E_INVALID, "unknown scatter flags 0x%x", d->flags);
+    const bool carries = d->op <= GGRS_SCATTER_INSERT;
+    const uint64_t known = w->comps.size() >= 64 ? ~0ull : (1ull << w->comps.size()) - 1ull;
+    if (carries && d->n_words == 0) return w->fail(GGRS_E_INVALID, "a scatter %s names no word", OPS[d->op]);
+    if (d->n_words > GGRS_QUERY_MAX_WORDS) return w->fail(GGRS_E_INVALID, "a scatter carries at most %d words, not %u", GGRS_QUERY_MAX_WORDS, d->n_words);
+    if (!carries && d->n_words) return w->fail(GGRS_E_INVALID, "a scatter %s carries no words, not %u", OPS[d->op], d->n_words);
+    if (d->op != GGRS_SCATTER_REMOVE && d->comp_mask) return w->fail(GGRS_E_INVALID, "comp_mask 0x%llx in a scatter %s: it names what REMOVE removes and is 0 otherwise", (unsigned long long)d->comp_mask, OPS[d->op]);
+    if (d->op == GGRS_SCATTER_REMOVE && !d->comp_mask) return w->fail(GGRS_E_INVALID, "a scatter REMOVE with an empty comp_mask removes nothing");
+    if (d->comp_mask & ~known) return w->fail(GGRS_E_INVALID, "a scatter REMOVE names a component the world does not have (comp_mask 0x%llx, %zu components)", (unsigned long long)d->comp_mask, w->comps.size());
+    uint64_t m = d->comp_mask;
+    uint32_t named[MAX_COMPS] = {0};
+    for (uint32_t k = 0; k < d->n_words; ++k) {
+        const ggrs_query_word& q = d->words[k];
+        if (q.comp >= w->comps.size()) return w->fail(GGRS_E_INVALID, "scatter word %u names component %u: the world has %zu", k, q.comp, w->comps.size());
+        if (q.word >= w->comps[q.comp].n_words) return w->fail(GGRS_E_INVALID, "scatter word %u names word %u of component %s, which has %u", k, q.word, w->comps[q.comp].name.c_str(), w->comps[q.comp].n_words);
+        for (uint32_t j = 0; j < k; ++j) if (d->words[j].comp == q.comp && d->words[j].word == q.word)
+            return w->fail(GGRS_E_INVALID, "scatter words %u and %u both name word %u of component %s", j, k, q.word, w->comps[q.comp].name.c_str());
+        m |= 1ull << q.comp; ++named[q.comp];
+    }
+    if (d->op == GGRS_SCATTER_INSERT) for (uint32_t c = 0; c < w->comps.size(); ++c) if (named[c] && named[c] != w->comps[c].n_words)
+        return w->fail(GGRS_E_INVALID, "a scatter INSERT names %u of the %u words of component %s: an inserted component brings every word (defaults are out of scope)", named[c], w->comps[c].n_words, w->comps[c].name.c_str());
+    if (!in_dev && n_rows) return w->fail(GGRS_E_INVALID, "scatter of %llu rows and no input buffer", (unsigned long long)n_rows);
+    if (n_rows > stride_rows) return w->fail(GGRS_E_INVALID, "scatter of %llu rows from a buffer laid out for %llu", (unsigned long long)n_rows, (unsigned long long)stride_rows);
+    if (stride_rows > (1ull << 48)) return w->fail(GGRS_E_INVALID, "scatter from a buffer laid out for %llu rows", (unsigned long long)stride_rows);
+    if (!rep) return w->fail(GGRS_E_INVALID, "scatter without a report");
+    if (w->capacity > (1ull << 32)) return w->fail(GGRS_E_INVALID, "scatter rows carry 32-bit slots: the world's capacity %llu exceeds 2^32", (unsigned long long)w->capacity);
+    *masks = m;
+    return GGRS_OK;
+}
+}  // namespace
+//   ggrs_dbg_scatter_launch_us  enable != 0: every later scatter call puts HIP events around its launches; us_out (may be NULL) receives what the check and apply
+//                               launches of the last timed call took by themselves, in microseconds (scripts/bench_scatter.py)
+int ggrs_dbg_scatter_launch_us(ggrs_world* w, int enable, double* us_out) {
+    if (!w) return -1;
+    w->scatter_timed = enable != 0;
+    if (us_out) { us_out[0] = w->scatter_us[0]; us_out[1] = w->scatter_us[1]; }
+    return 0;
+}
+int ggrs_hip_scatter(ggrs_world* w, const ggrs_scatter_desc* desc, const void* in_dev, uint64_t stride_rows, uint64_t n_rows, ggrs_scatter_report* report) {
+    if (!w) return GGRS_E_INVALID;
+    uint64_t masks = 0;
+    int rc = scatter_check(w, desc, in_dev, stride_rows, n_rows, report, &masks); if (rc) return rc;
+    if (w->layout_only) return w->fail(GGRS_E_NO_DEVICE, "a layout-only world has no state to scatter into");
+    DeviceGuard dg(w);
+    if (w->dev_spawn && !w->pending.empty())
+        return w->fail(GGRS_E_INVALID, "scatter into a world whose systems spawn on the device while %zu enqueued batches are uncollected: its len is not known to the host", w->pending.size());
+    rc = seal_live(w); if (rc) return rc;
+    memset(report, 0, sizeof *report);
+    report->len = w->len; report->n_rows = n_rows; report->first_bad_row = ~0ull;
+    if (n_rows == 0) return GGRS_OK;
+    // the input buffer's layout is a query's: the same words, the slots behind them
+    ggrs_query_desc qd; memset(&qd, 0, sizeof qd);
+    qd.n_words = desc->n_words; qd.flags = GGRS_QUERY_SLOTS;
+    for (uint32_t k = 0; k < desc->n_words; ++k) qd.words[k] = desc->words[k];
+    ggrs_query_layout lay; query_layout(w, &qd, stride_rows, &lay);
+    ScatterArgs a; memset(&a, 0, sizeof a);
+    a.state = w->live.ptr; a.in = (const uint8_t*)in_dev; a.len = std::min<uint64_t>(w->len, w->capacity); a.n_rows = n_rows; a.off_alive = w->off_alive; a.slots_off = lay.slots_off;
+    a.op = desc->op; a.n_words = desc->n_words;
+    if (desc->op != GGRS_SCATTER_DESPAWN) for (uint32_t c = 0; c < w->comps.size() && c < 64u; ++c) if ((masks >> c) & 1ull) a.off_mask[a.n_masks++] = w->off_present[c];
+    for (uint32_t k = 0; k < desc->n_words; ++k) {
+        const uint32_t col = w->comps[desc->words[k].comp].col_base + desc->words[k].word;
+        a.col_off[k] = w->col_off[col]; a.col_ts[k] = w->col_ts[col]; a.col_wb[k] = (uint8_t)w->col_wb[col]; a.in_off[k] = lay.col_off[k];
+    }
+    rc = diff_scratch(w, (uint64_t)SCAT_REC_WORDS * 8u); if (rc) return rc;
+    a.rec = reinterpret_cast<unsigned long long*>(w->d_diff);
+    const uint32_t cap = w->query_max_wgs ? w->query_max_wgs : SCATTER_MAX_WGS;
+    const uint32_t g = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n_rows + TPB - 1) / TPB, cap));
+    // the record: every count 0, the lowest bad row (kept as its complement) none
+    HIPCHK(w, hipMemsetAsync(a.rec, 0, (size_t)SCAT_REC_WORDS * 8u, w->stream));
+    if (w->scatter_timed) { for (hipEvent_t& e : w->scatter_ev) if (!e) HIPCHK(w, hipEventCreate(&e)); HIPCHK(w, hipEventRecord(w->scatter_ev[0], w->stream)); }
+    hipLaunchKernelGGL(k_scatter_check, dim3(g), dim3(TPB), 0, w->stream, a);
+    HIPCHK(w, hipGetLastError());
+    if (w->scatter_timed) HIPCHK(w, hipEventRecord(w->scatter_ev[1], w->stream));
+    hipLaunchKernelGGL(k_scatter_apply, dim3(g), dim3(TPB), 0, w->stream, a);
+    HIPCHK(w, hipGetLastError());
+    if (w->scatter_timed) HIPCHK(w, hipEventRecord(w->scatter_ev[2], w->stream));
+    HIPCHK(w, hipMemcpyAsync(w->h_diff, a.rec, (size_t)SCAT_REC_WORDS * 8u, hipMemcpyDeviceToHost, w->stream));
+    HIPCHK(w, hipStreamSynchronize(w->stream));
+    if (w->scatter_timed) for (int k = 0; k < 2; ++k) { float ms = 0; HIPCHK(w, hipEventElapsedTime(&ms, w->scatter_ev[k], w->scatter_ev[k + 1])); w->scatter_us[k] = (double)ms * 1e3; }
+    const uint64_t* r = (const uint64_t*)w->h_diff;
+    ++w->scatter_calls; w->scatter_last_rows = n_rows; w->scatter_last_op = desc->op; w->scatter_last_words = desc->n_words;
+    if (r[SCAT_BAD]) {                                              // the apply launch returned at once: not a byte, not a version, not a tag bit has changed
+        report->first_bad_row = ~r[SCAT_FIRST_BAD];
+        return w->fail(GGRS_E_INVALID, "scatter rows must be strictly ascending slots below len %llu: %llu of %llu rows are not, first_bad_row %llu",
+                       (unsigned long long)w->len, (unsigned long long)r[SCAT_BAD], (unsigned long long)n_rows, (unsigned long long)~r[SCAT_FIRST_BAD]);
+    }
+    report->n_dead = r[SCAT_DEAD]; report->n_absent = r[SCAT_ABSENT]; report->n_applied = n_rows - r[SCAT_DEAD] - r[SCAT_ABSENT];
+    for (uint32_t k = 0; k < desc->n_words; ++k) {                  // written columns (WRITE, INSERT)
+        const uint32_t col = w->comps[desc->words[k].comp].col_base + desc->words[k].word;
+        ver_touch(w, col); live_tags_lost(w, col);
+    }
+    if (desc->op == GGRS_SCATTER_INSERT || desc->op == GGRS_SCATTER_REMOVE)
+        for (uint32_t c = 0; c < w->comps.size() && c < 64u; ++c) if ((masks >> c) & 1ull) ver_touch(w, ver_presence(w, c));
+    ver_sync_live(w);
+    w->pending_valid = false;
+    return GGRS_OK;
+}
+
 // Which kernel serves this world's request lists right now, on what kind of arena, and the state of the run-time
 // compiler -- `key=value` lines (NUL-terminated, truncated to cap).  Nothing here is needed to USE the library: it is what an
 // operator reads when a world is slower than expected (e.g. libhiprtc.so missing from a deployment image).
@@ -1531,6 +1641,8 @@ int ggrs_hip_world_kernel_info(ggrs_world* w, char* buf, uint64_t cap, uint64_t*
                                          " bytes per slot and side) and " + std::to_string(w->plan.n_masks) + " masks over " + std::to_string(w->diff_last_units) + " units of 64 slots");
     if (w->query_calls) add("query", std::to_string(w->query_calls) + " calls; the last one fetched " + std::to_string(w->query_last_words) + " words and read " + std::to_string(w->query_last_masks) +
                                      " masks over " + std::to_string(w->query_last_units) + " units of 64 slots");
+    if (w->scatter_calls) add("scatter", std::to_string(w->scatter_calls) + " calls; the last one was op " + std::to_string(w->scatter_last_op) + " over " + std::to_string(w->scatter_last_rows) + " rows of " +
+                                         std::to_string(w->scatter_last_words) + " words");
     if (w->cparts_calls) add("checksum_parts", std::to_string(w->cparts_calls) + " calls; hashing kernel " + (w->custom_hashers ? "ggrs_jit_parts (generated: the world has a user-written hasher; module from " + w->cparts_origin + ", " +
                                              std::to_string(w->cparts_builds) + " built or loaded by this world)" : std::string("k_parts_hash (static)")));
     add("row_versions", w->knobs.row_versions ? "on" : "off (GGRS_ROW_VERSIONS=0)");

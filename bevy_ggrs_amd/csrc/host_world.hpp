@@ -443,6 +443,9 @@ struct ggrs_world {
     // calls are synchronous on the world's stream and never overlap).  query_max_wgs: ggrs_dbg_set_query_grid (0: by size)
     uint32_t query_max_wgs = 0; uint64_t query_calls = 0; uint32_t query_last_words = 0, query_last_masks = 0, query_last_units = 0;
     bool query_timed = false; hipEvent_t query_ev[4] = {nullptr, nullptr, nullptr, nullptr}; double query_us[3] = {0, 0, 0};   // ggrs_dbg_query_launch_us: match, scan, emit of the last call
+    // ---- scatter (ggrs_hip_scatter): its record lives in the same scratch; query_max_wgs caps its two launches too
+    uint64_t scatter_calls = 0, scatter_last_rows = 0; uint32_t scatter_last_op = 0, scatter_last_words = 0;
+    bool scatter_timed = false; hipEvent_t scatter_ev[3] = {nullptr, nullptr, nullptr}; double scatter_us[2] = {0, 0};           // ggrs_dbg_scatter_launch_us: check, apply of the last call
 
     // ---- profiling
     bool nt_copy = false;              // non-temporal loads/stores in k_copy_state (A/B knob)

@@ -1356,4 +1356,108 @@ __global__ __launch_bounds__(TPB) void k_query_emit(QueryArgs a) {
     }
 }
 
+// ------------------------------------------------------------------ SCATTER (ggrs_hip_scatter)
+// The inverse of the query: rows of (slot, words..) in device memory, in the query's output layout, applied to the LIVE block.  Two launches, ordered by their
+// boundary alone; the host waits once, for the record:
+//   k_scatter_check  one row per lane, grid-stride.  Row i is bad iff its slot is at or beyond len or the slot of row i-1 is not smaller (it reads slots i-1 and i):
+//                    what is left is strictly ascending, so no two rows name one slot and the outcome cannot depend on the geometry.  Bad rows are counted and the
+//                    lowest is kept (a 64-bit atomic min, spelled as the max of the row's complement so that one clear to zero initialises the whole record), one
+//                    atomic each per wave that saw any, behind a __ballot.
+//   k_scatter_apply  reads the count with a wave-uniform load and returns at once when it is not zero: nothing is written, and no host round trip sits between the
+//                    launches.  Otherwise one row per lane, grid-stride: the lane loads its slot, the alive word and (WRITE, INSERT, REMOVE) the named presence words
+//                    of unit slot >> 6 -- the lanes of one unit load the same words -- and is applied, dead or absent by ITS OWN bits of them, which no other row
+//                    edits (no two rows share a slot): the verdict is the one of the state before the call whatever the other waves have done so far.  An applied
+//                    lane of WRITE / INSERT loads its input words, QUERY_BATCH columns ahead of the first store, and stores them through col_at.  Mask edits are
+//                    64-bit no-return atomics, OR (INSERT) or AND (REMOVE, DESPAWN), issued only where the bit changes: rows of one unit may sit in different waves
+//                    and workgroups, a plain read-modify-write would lose bits.  The counts: dead and absent rows by one __ballot + popcount per wave-iteration into
+//                    a wave-uniform sum, one LDS add per wave and one global atomic add per workgroup that saw any; the applied rows are n_rows minus the two,
+//                    taken on the host.  (One global atomic add per wave-iteration and count, all to one address, measured 13 x slower at 1 M rows: the two
+//                    series are in profiles/scatter/README.md and DESIGN.md section 3.17.)
+enum : uint32_t { SCAT_BAD = 0, SCAT_FIRST_BAD = 1, SCAT_DEAD = 2, SCAT_ABSENT = 3, SCAT_REC_WORDS = 4 };   // the record, u64 words (SCAT_FIRST_BAD: ~row)
+struct ScatterArgs {
+    uint8_t* state; const uint8_t* in;
+    unsigned long long* rec;
+    uint64_t len, n_rows, off_alive, slots_off;
+    uint64_t off_mask[MAX_COMPS];                          // presence masks: WRITE the named words' components (all must be present), INSERT / REMOVE the edited ones
+    uint64_t col_off[GGRS_QUERY_MAX_WORDS];                // per word k: its column in the live block ...
+    uint64_t in_off[GGRS_QUERY_MAX_WORDS];                 // ... and in the input buffer
+    uint32_t col_ts[GGRS_QUERY_MAX_WORDS];
+    uint32_t op, n_masks, n_words, pad;
+    uint8_t col_wb[GGRS_QUERY_MAX_WORDS];
+};
+__global__ __launch_bounds__(TPB) void k_scatter_check(ScatterArgs a) {
+    const uint32_t* const slots = reinterpret_cast<const uint32_t*>(a.in + a.slots_off);
+    const uint64_t stride = (uint64_t)gridDim.x * TPB, n_pad = (a.n_rows + 63u) & ~63ull;      // (whole waves stay in the loop: the ballot below is over all 64 lanes)
+    for (uint64_t i = (uint64_t)blockIdx.x * TPB + threadIdx.x; i < n_pad; i += stride) {
+        bool bad = false;
+        if (i < a.n_rows) {
+            const uint32_t s = slots[i];
+            bad = s >= a.len || (i > 0 && slots[i - 1] >= s);
+        }
+        const uint64_t b = __ballot(bad);
+        if (b && (threadIdx.x & 63u) == 0u) {                                     // (the wave's rows ascend with the lane: its lowest bad row is its lowest set bit)
+            atomicAdd(a.rec + SCAT_BAD, (unsigned long long)__popcll(b));
+            atomicMax(a.rec + SCAT_FIRST_BAD, ~(unsigned long long)(i + (uint64_t)__ffsll((long long)b) - 1u));
+        }
+    }
+}
+__global__ __launch_bounds__(TPB) void k_scatter_apply(ScatterArgs a) {
+    if (a.rec[SCAT_BAD]) return;                                                 // (wave-uniform: the check launch found a bad row -- nothing is applied)
+    const uint32_t* const slots = reinterpret_cast<const uint32_t*>(a.in + a.slots_off);
+    const uint64_t stride = (uint64_t)gridDim.x * TPB, n_pad = (a.n_rows + 63u) & ~63ull;
+    const bool lane0 = (threadIdx.x & 63u) == 0u;
+    __shared__ unsigned long long s_cnt[2];
+    if (threadIdx.x < 2u) s_cnt[threadIdx.x] = 0;
+    __syncthreads();
+    uint64_t n_dead = 0, n_absent = 0;                                           // (wave-uniform)
+    for (uint64_t i = (uint64_t)blockIdx.x * TPB + threadIdx.x; i < n_pad; i += stride) {
+        const bool row = i < a.n_rows;
+        uint64_t e = 0, bit = 0, alive = 0, have = ~0ull, wi = 0;
+        if (row) {
+            e = slots[i]; wi = (e >> 6) * 8u; bit = 1ull << (e & 63u);              // e < len <= the capacity (k_scatter_check): inside every mask and column
+            alive = *reinterpret_cast<const uint64_t*>(a.state + a.off_alive + wi) & bit;
+        }
+        const bool dead = row && !alive;
+        bool absent = false;
+        if (row && alive && a.op == GGRS_SCATTER_WRITE) {
+            for (uint32_t j = 0; j < a.n_masks; ++j) have &= *reinterpret_cast<const uint64_t*>(a.state + a.off_mask[j] + wi);
+            absent = !(have & bit);
+        }
+        const bool on = row && alive && !absent;
+        if (on && a.op <= GGRS_SCATTER_INSERT) {
+            for (uint32_t k0 = 0; k0 < a.n_words; k0 += QUERY_BATCH) {
+                uint64_t v[QUERY_BATCH];
+#pragma unroll
+                for (uint32_t q = 0; q < QUERY_BATCH; ++q) {
+                    v[q] = 0;
+                    if (k0 + q < a.n_words) { const uint32_t wb = a.col_wb[k0 + q]; v[q] = diff_load(a.in + a.in_off[k0 + q] + i * wb, wb); }   // (uniform)
+                }
+#pragma unroll
+                for (uint32_t q = 0; q < QUERY_BATCH; ++q)
+                    if (k0 + q < a.n_words) { const uint32_t wb = a.col_wb[k0 + q]; query_store(a.state + col_at(a.col_off[k0 + q], a.col_ts[k0 + q], wb, e), v[q], wb); }
+            }
+        }
+        if (on && a.op == GGRS_SCATTER_INSERT) {
+            for (uint32_t j = 0; j < a.n_masks; ++j) {
+                unsigned long long* const p = reinterpret_cast<unsigned long long*>(a.state + a.off_mask[j] + wi);
+                if (!(*p & bit)) (void)atomicOr(p, (unsigned long long)bit);
+            }
+        } else if (on && a.op == GGRS_SCATTER_REMOVE) {
+            for (uint32_t j = 0; j < a.n_masks; ++j) {
+                unsigned long long* const p = reinterpret_cast<unsigned long long*>(a.state + a.off_mask[j] + wi);
+                if (*p & bit) (void)atomicAnd(p, (unsigned long long)~bit);
+            }
+        } else if (on && a.op == GGRS_SCATTER_DESPAWN) {
+            (void)atomicAnd(reinterpret_cast<unsigned long long*>(a.state + a.off_alive + wi), (unsigned long long)~bit);      // (on: the bit is set)
+        }
+        n_dead += (uint64_t)__popcll(__ballot(dead)); n_absent += (uint64_t)__popcll(__ballot(absent));
+    }
+    if (lane0) {
+        if (n_dead) atomicAdd(&s_cnt[0], (unsigned long long)n_dead);
+        if (n_absent) atomicAdd(&s_cnt[1], (unsigned long long)n_absent);
+    }
+    __syncthreads();
+    if (threadIdx.x < 2u && s_cnt[threadIdx.x]) atomicAdd(a.rec + SCAT_DEAD + threadIdx.x, s_cnt[threadIdx.x]);
+}
+
 }  // namespace ggrs

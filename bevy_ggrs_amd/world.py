@@ -22,6 +22,7 @@ def _as_c(arr: np.ndarray):
 
 LIVE = _ffi.DIFF_LIVE      # World.diff: as a frame, the live world
 _NO_WORD = 0xFFFFFFFF
+_NO_ROW = 0xFFFFFFFFFFFFFFFF                               # ggrs_scatter_report.first_bad_row when no row is bad
 
 
 @dataclass
@@ -118,12 +119,27 @@ class QueryResult:
     columns: list
     words: List[tuple]
     buffer: object
+    max_rows: int = 0           # the rows the buffer is laid out for (World.scatter hands it back as stride_rows)
+    slots_off: int = 0          # where the slots start in the buffer
 
     def numpy(self):
         """Host copies: (slots or None, [columns]) as unsigned numpy arrays, the dtypes World.download_word returns."""
         un = {1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}
         cols = [c.cpu().numpy().view(un[c.element_size()]) for c in self.columns]
         return (None if self.slots is None else self.slots.cpu().numpy().view(np.uint32)), cols
+
+
+@dataclass
+class ScatterReport:
+    """World.scatter: what became of the rows (ggrs_scatter_report).  n_applied + n_dead + n_absent == n_rows: a row is applied iff its entity is alive and, for
+    op="write", has every named component; n_dead rows named a slot that is not alive, n_absent rows an alive slot lacking a named component.  first_bad_row is
+    None: a call whose rows are not strictly ascending slots below len raises instead and changes nothing."""
+    len: int
+    n_rows: int
+    n_applied: int
+    n_dead: int
+    n_absent: int
+    first_bad_row: Optional[int]
 
 
 class WorldBase:
@@ -788,7 +804,77 @@ class World(WorldBase):
             columns.append(out[off:off + n * wb].view(dt[wb]))
         slot_col = out[int(lay.slots_off):int(lay.slots_off) + n * 4].view(torch.int32) if slots else None
         return QueryResult(len=int(rep.len), n_matched=int(rep.n_matched), n_rows=n, slots=slot_col, columns=columns,
-                           words=[(int(desc.words[k].comp), int(desc.words[k].word)) for k in range(desc.n_words)], buffer=out)
+                           words=[(int(desc.words[k].comp), int(desc.words[k].word)) for k in range(desc.n_words)], buffer=out, max_rows=int(max_rows),
+                           slots_off=int(lay.slots_off))
+
+    # ---- scatter (include/ggrs_hip.h: ggrs_hip_scatter)
+    def scatter_desc(self, op="write", words=(), comps=()) -> "_ffi.ScatterDesc":
+        """The ggrs_scatter_desc of World.scatter's arguments: `words` are (comp, word) pairs (write, insert), `comps` the components a remove removes."""
+        if op not in _ffi.SCATTER_OPS: raise ValueError(f"op is one of {sorted(_ffi.SCATTER_OPS)}, not {op!r}")
+        words = [(int(c), int(k)) for c, k in words]
+        if len(words) > _ffi.QUERY_MAX_WORDS: raise ValueError(f"a scatter carries at most {_ffi.QUERY_MAX_WORDS} words, not {len(words)}")
+        d = _ffi.ScatterDesc()
+        d.op = _ffi.SCATTER_OPS[op]; d.comp_mask = sum(1 << int(c) for c in set(comps)); d.n_words = len(words)
+        for k, (c, wd) in enumerate(words): d.words[k].comp = c; d.words[k].word = wd
+        return d
+
+    def scatter(self, rows, values=None, *, op="write", comps=()) -> ScatterReport:
+        """The inverse of World.query: rows of (slot, words ..) on the device applied to the live world in one call.  `rows` is a QueryResult (with slots): its
+        buffer goes back as it is, so values edited in place through .columns[k] are written without a copy -- or a 1-D array / tensor of slots, with `values`
+        a {(comp, word): array or tensor of the word's width} mapping for "write" and "insert".  op: "write" (Query<&mut C>: the named words, where the entity
+        is alive and has every named component), "insert" (the words and the presence bits; every word of each inserted component), "remove" (the presence
+        bits of `comps`), "despawn".  The slots must be strictly ascending and below len: otherwise GgrsHipError (its message names first_bad_row) and
+        nothing in the world has changed.  Rows whose entity has died since are counted (ScatterReport), not applied."""
+        import torch
+        carries = op in ("write", "insert")
+        dev = f"cuda:{self.device}"
+        if isinstance(rows, QueryResult):
+            if rows.slots is None: raise ValueError("scatter needs the rows' slots: query with slots=True")
+            if values is not None: raise ValueError("a QueryResult brings its values: edit .columns in place")
+            n, stride = rows.n_rows, rows.max_rows
+            words = rows.words if carries else ()
+            # "remove" / "despawn" read the slots only: a buffer of no words, whose slots start at offset 0
+            ptr = rows.buffer.data_ptr() + (0 if carries else rows.slots_off)
+            keep = rows.buffer
+        else:
+            if hasattr(rows, "data_ptr"):
+                s = rows.reshape(-1).to(dev)
+                if s.dtype != torch.int32:                                # (int32: the bits of a u32, what QueryResult.slots holds)
+                    if s.dtype.is_floating_point or (s.numel() and (int(s.min()) < 0 or int(s.max()) >= 1 << 32)): raise ValueError("slots are unsigned 32-bit integers")
+                    s = s.to(torch.int32)                                 # (checked above to lie in [0, 2^32): the integer conversion wraps, i.e. keeps the low 32 bits -- the u32's bits.  The check reads min and max back: pass int32 bits, as QueryResult.slots holds them, to avoid the two waits)
+                s = s.contiguous()
+            else:
+                a = np.asarray(rows).reshape(-1)
+                if a.size and (a.dtype.kind not in "ui" or int(a.min()) < 0 or int(a.max()) >= 1 << 32): raise ValueError("slots are unsigned 32-bit integers")
+                s = torch.from_numpy(a.astype(np.uint32).view(np.int32)).to(dev)
+            n = stride = int(s.numel())
+            values = dict(values or {})
+            if not carries and values: raise ValueError(f"op {op!r} carries no values")
+            words = [(int(c), int(k)) for c, k in values]
+            qd = self.query_desc(words, slots=True)
+            lay = self.query_layout(qd, stride)
+            keep = torch.empty(max(int(lay.total_bytes), 1), dtype=torch.uint8, device=dev)
+            for k, key in enumerate(values):
+                wb, off, v = int(lay.word_bytes[k]), int(lay.col_off[k]), values[key]
+                if hasattr(v, "data_ptr"): v = v.reshape(-1).contiguous()
+                else:
+                    a = np.ascontiguousarray(v).reshape(-1)
+                    v = torch.from_numpy(a.view({1: np.uint8, 2: np.int16, 4: np.int32, 8: np.int64}.get(a.dtype.itemsize, np.uint8)))
+                if v.element_size() != wb or v.numel() != n: raise ValueError(f"values[{key}] must hold {n} words of {wb} bytes")
+                if n: keep[off:off + n * wb].copy_(v.view(torch.uint8).to(dev))
+            if n: keep[int(lay.slots_off):int(lay.slots_off) + n * 4].copy_(s.view(torch.uint8))
+            ptr = keep.data_ptr()
+        desc = self.scatter_desc(op, words, comps)
+        torch.cuda.current_stream(keep.device).synchronize()      # (the launches run on the world's stream)
+        rep = _ffi.ScatterReport()
+        rep.first_bad_row = _NO_ROW
+        try:
+            self._check(self._lib.ggrs_hip_scatter(self._p, C.byref(desc), ptr, stride, n, C.byref(rep)))
+        except GgrsHipError as e:
+            if rep.first_bad_row != _NO_ROW:                      # the rows were refused: the report says where (the exception carries it as .report)
+                e.report = ScatterReport(len=int(rep.len), n_rows=int(rep.n_rows), n_applied=0, n_dead=0, n_absent=0, first_bad_row=int(rep.first_bad_row))
+            raise
+        return ScatterReport(len=int(rep.len), n_rows=int(rep.n_rows), n_applied=int(rep.n_applied), n_dead=int(rep.n_dead), n_absent=int(rep.n_absent), first_bad_row=None)
 
     def live_state_ptr(self) -> int:
         p = C.c_void_p()

@@ -507,6 +507,17 @@ struct HipBackend {
     int query_layout(const ggrs_query_desc& desc, uint64_t max_rows, ggrs_query_layout* out) { return ggrs_hip_query_layout(w, &desc, max_rows, out); }
     int query(int32_t frame, const ggrs_query_desc& desc, void* out_dev, uint64_t max_rows, ggrs_query_report* report) { return ggrs_hip_query(w, frame, &desc, out_dev, max_rows, report); }
     int query_block(const void* block_dev, const ggrs_query_desc& desc, void* out_dev, uint64_t max_rows, ggrs_query_report* report) { return ggrs_hip_query_block(w, block_dev, &desc, out_dev, max_rows, report); }
+    // scatter (include/ggrs_hip.h): writing back -- Query<&mut C>, commands.entity(e).insert(..) / .remove::<C>() / .despawn() over a whole query result.  Rows of
+    // (slot, words..) in device memory, in the layout query_layout gives for the same words with slots, applied to the live world in one call; a query's output buffer
+    // can be handed back unchanged (stride_rows = its max_rows, n_rows = its report's n_rows).  The slots must be strictly ascending and below len
+    static ggrs_scatter_desc scatter_desc(uint32_t op, const std::vector<ggrs_query_word>& words = {}, uint64_t comp_mask = 0) {
+        ggrs_scatter_desc d{};
+        d.op = op; d.comp_mask = comp_mask;
+        d.n_words = (uint32_t)(words.size() < 0xFFFFFFFFu ? words.size() : 0xFFFFFFFFu);      // (more than GGRS_QUERY_MAX_WORDS: handed through, ggrs_hip_scatter refuses it)
+        for (uint32_t k = 0; k < d.n_words && k < GGRS_QUERY_MAX_WORDS; ++k) d.words[k] = words[k];
+        return d;
+    }
+    int scatter(const ggrs_scatter_desc& desc, const void* in_dev, uint64_t stride_rows, uint64_t n_rows, ggrs_scatter_report* report) { return ggrs_hip_scatter(w, &desc, in_dev, stride_rows, n_rows, report); }
 };
 
 // ---------------------------------------------------------------- speculative fan-out (no reference analogue: SURVEY.md 8e)

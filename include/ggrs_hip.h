@@ -1067,6 +1067,46 @@ int ggrs_hip_query(ggrs_world* w, int32_t frame, const ggrs_query_desc* desc, vo
 int ggrs_hip_query_block(ggrs_world* w, const void* block_dev, const ggrs_query_desc* desc, void* out_dev, uint64_t max_rows, ggrs_query_report* report);
 
 /* -------------------------------------------------------------------------------------------
+ * SCATTER: the inverse of the query -- rows of (slot, words..) in device memory applied to the LIVE world in one call: what a game does with
+ * Query<&mut C>, or with commands.entity(e).insert(..) / .remove::<C>() / .despawn() over a whole result, without the state leaving the device.  Two small
+ * launches (check, apply) and one wait, beside the tick and never on its path.  Ring frames are history and are never the target.
+ *
+ * in_dev has exactly the layout ggrs_hip_query_layout gives for the same `words` with GGRS_QUERY_SLOTS set and max_rows = stride_rows: word k of row i at
+ * in_dev + col_off[k] + i * word_bytes[k], its slot a uint32_t at in_dev + slots_off + i * 4.  A query's output buffer can be handed back unchanged
+ * (stride_rows = its max_rows, n_rows = its report's n_rows).  REMOVE and DESPAWN read the slots only (n_words = 0: the slots sit at offset 0).
+ *
+ * The slots of rows 0 .. n_rows must be strictly ascending and below len (the host's RollbackOrdered::len): what a query produces.  No two rows then name one
+ * slot, and the result is the same for every launch geometry.  A violation is GGRS_E_INVALID: report->first_bad_row holds the lowest offending row (a row is
+ * bad iff its slot is at or beyond len or its predecessor's slot is not smaller) and NOTHING in the world is changed.  A valid row is applied iff its slot's
+ * alive bit is set and, for WRITE only, every component named by a word is present -- judged on the state before the call.  Rows that are not applied are
+ * counted and otherwise ignored (the entity may have died since the query ran): n_dead rows whose slot is not alive (an entity marked RollbackDespawned counts
+ * as dead, as in the query), n_absent rows of an alive slot that lacks a named component; n_applied + n_dead + n_absent == n_rows, every count exact.
+ * first_bad_row is UINT64_MAX when no row is bad.  INSERT on a slot that already has the component replaces its words.  The live world's value form is always
+ * plain: a component under a Strategy and a GGRS_COMP_NO_ROLLBACK component are served.  n_rows == 0 is a no-op that still fills the report.
+ * Like ggrs_hip_upload_word the call is ordered on the world's stream behind request lists still in flight and returns once its report is in.
+ * Errors, GGRS_E_INVALID with a message: an unknown op or flags that are not 0; a component or word the world does not have; the same (comp, word) named
+ * twice; n_words of 0 for WRITE / INSERT, or above GGRS_QUERY_MAX_WORDS; n_words not 0 for REMOVE / DESPAWN; a nonzero comp_mask outside REMOVE; an empty
+ * comp_mask in REMOVE or one naming an unknown component; INSERT that does not name every word of each component it inserts; in_dev == NULL with n_rows > 0;
+ * n_rows > stride_rows; stride_rows above 2^48; no report; a world whose capacity exceeds 2^32 (the rows' slots are 32-bit); a world with device-decided spawns that has uncollected batches (its len is not known to the host).  The descriptor is
+ * validated before the device is looked at: a GGRS_WORLD_LAYOUT_ONLY world returns these errors for a bad descriptor and GGRS_E_NO_DEVICE for a good one.
+ * Out of scope: rows in arbitrary order, bulk despawn_rollback markers, bulk spawn (ggrs_hip_spawn takes a count), defaults for unnamed words of an INSERT,
+ * an asynchronous form, ring frames and blocks as targets, device resources (ggrs_hip_resource_write). */
+#define GGRS_SCATTER_WRITE   0u  /* Query<&mut C>: overwrite the named words where the entity is alive and has every named component */
+#define GGRS_SCATTER_INSERT  1u  /* commands.entity(e).insert(C{..}): write the words and set the presence bits; alive entities only */
+#define GGRS_SCATTER_REMOVE  2u  /* commands.entity(e).remove::<C>(): clear the presence bits named in comp_mask; alive entities only */
+#define GGRS_SCATTER_DESPAWN 3u  /* what ggrs_hip_despawn does, for every row */
+typedef struct {
+    uint32_t op;                 /* GGRS_SCATTER_* */
+    uint32_t flags;              /* 0 */
+    uint64_t comp_mask;          /* REMOVE: the components to remove; must be 0 otherwise */
+    uint32_t n_words;            /* WRITE / INSERT: 1 .. GGRS_QUERY_MAX_WORDS; REMOVE / DESPAWN: 0 */
+    uint32_t pad;
+    ggrs_query_word words[GGRS_QUERY_MAX_WORDS];
+} ggrs_scatter_desc;
+typedef struct { uint64_t len; uint64_t n_rows; uint64_t n_applied; uint64_t n_dead; uint64_t n_absent; uint64_t first_bad_row; } ggrs_scatter_report;
+int ggrs_hip_scatter(ggrs_world* w, const ggrs_scatter_desc* desc, const void* in_dev, uint64_t stride_rows, uint64_t n_rows, ggrs_scatter_report* report);
+
+/* -------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): per-kernel-class HIP-event timing on the world's stream.
  * ------------------------------------------------------------------------------------------- */
 #define GGRS_KERNEL_SAVE     0u

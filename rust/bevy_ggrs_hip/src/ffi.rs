@@ -375,6 +375,36 @@ pub struct ggrs_query_report {
     pub n_rows: u64,
 }
 
+/// Scatter ops: `Query<&mut C>`; `commands.entity(e).insert(C{..})`; `.remove::<C>()`; `.despawn()`.
+pub const GGRS_SCATTER_WRITE: u32 = 0;
+pub const GGRS_SCATTER_INSERT: u32 = 1;
+pub const GGRS_SCATTER_REMOVE: u32 = 2;
+pub const GGRS_SCATTER_DESPAWN: u32 = 3;
+
+/// What a scatter does with its rows: `words` as in a query desc (WRITE / INSERT), `comp_mask` the components REMOVE removes.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct ggrs_scatter_desc {
+    pub op: u32,
+    pub flags: u32,
+    pub comp_mask: u64,
+    pub n_words: u32,
+    pub pad: u32,
+    pub words: [ggrs_query_word; GGRS_QUERY_MAX_WORDS],
+}
+
+/// What a scatter did: `n_applied + n_dead + n_absent == n_rows`; `first_bad_row` is `u64::MAX` unless the rows were refused.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct ggrs_scatter_report {
+    pub len: u64,
+    pub n_rows: u64,
+    pub n_applied: u64,
+    pub n_dead: u64,
+    pub n_absent: u64,
+    pub first_bad_row: u64,
+}
+
 impl ggrs_request {
     pub const fn zeroed() -> Self {
         Self { kind: 0, frame: 0, dt_bits: 0, n_inputs: 0, inputs: core::ptr::null(), status: core::ptr::null(), spawn_count: 0, spawn_vx: core::ptr::null(), spawn_vy: core::ptr::null(),
@@ -465,6 +495,8 @@ unsafe extern "C" {
     pub fn ggrs_hip_query_layout(w: *mut ggrs_world, desc: *const ggrs_query_desc, max_rows: u64, out: *mut ggrs_query_layout) -> c_int;
     pub fn ggrs_hip_query(w: *mut ggrs_world, frame: i32, desc: *const ggrs_query_desc, out_dev: *mut c_void, max_rows: u64, report: *mut ggrs_query_report) -> c_int;
     pub fn ggrs_hip_query_block(w: *mut ggrs_world, block_dev: *const c_void, desc: *const ggrs_query_desc, out_dev: *mut c_void, max_rows: u64, report: *mut ggrs_query_report) -> c_int;
+    // ---- scatter: rows of (slot, words..) in device memory, in a query's output layout, applied to the live world (the inverse of the query)
+    pub fn ggrs_hip_scatter(w: *mut ggrs_world, desc: *const ggrs_scatter_desc, in_dev: *const c_void, stride_rows: u64, n_rows: u64, report: *mut ggrs_scatter_report) -> c_int;
     // ---- speculative fan-out across GPUs (RCCL behind the C ABI; the host carries the 128-byte ncclUniqueId between ranks)
     pub fn ggrs_hip_fanout_unique_id(id_out: *mut u8) -> c_int;
     pub fn ggrs_hip_fanout_init(w: *mut ggrs_world, id: *const u8, rank: c_int, world_size: c_int, out: *mut *mut ggrs_fanout) -> c_int;

@@ -152,6 +152,27 @@ impl HipWorld {
         self.check(unsafe { ffi::ggrs_hip_query(self.raw, frame.unwrap_or(ffi::GGRS_DIFF_LIVE), desc, out_dev, max_rows, &mut rep) });
         rep
     }
+    /// The desc of a scatter: `op` is `ffi::GGRS_SCATTER_*`, `words` holds the (component id, word) pairs the rows carry (WRITE / INSERT), `remove` the
+    /// components a REMOVE removes.
+    pub fn scatter_desc(op: u32, words: &[(u32, u32)], remove: &[u32]) -> ffi::ggrs_scatter_desc {
+        assert!(words.len() <= ffi::GGRS_QUERY_MAX_WORDS, "a scatter carries at most GGRS_QUERY_MAX_WORDS words");
+        let mut d = ffi::ggrs_scatter_desc { op, flags: 0, comp_mask: 0, n_words: words.len() as u32, pad: 0,
+                                             words: [ffi::ggrs_query_word { comp: 0, word: 0 }; ffi::GGRS_QUERY_MAX_WORDS] };
+        for c in remove { d.comp_mask |= 1u64 << c; }
+        for (k, (comp, word)) in words.iter().enumerate() { d.words[k] = ffi::ggrs_query_word { comp: *comp, word: *word }; }
+        d
+    }
+    /// Writing back (`Query<&mut C>`, `Commands` over a whole query result): rows of (slot, words ..) in device memory, laid out as
+    /// `query_layout` lays out the same words with slots for `stride_rows` rows, applied to the live world in one call.  A query's output buffer
+    /// can be handed back unchanged.  The slots must be strictly ascending and below `len`; rows whose entity has died are counted, not applied.
+    ///
+    /// # Safety
+    /// `in_dev` must be device memory of the layout's size on the world's device, not being written by other streams.
+    pub unsafe fn scatter(&self, desc: &ffi::ggrs_scatter_desc, in_dev: *const core::ffi::c_void, stride_rows: u64, n_rows: u64) -> ffi::ggrs_scatter_report {
+        let mut rep = ffi::ggrs_scatter_report { len: 0, n_rows: 0, n_applied: 0, n_dead: 0, n_absent: 0, first_bad_row: u64::MAX };
+        self.check(unsafe { ffi::ggrs_hip_scatter(self.raw, desc, in_dev, stride_rows, n_rows, &mut rep) });
+        rep
+    }
 }
 impl Drop for HipWorld {
     fn drop(&mut self) {
