@@ -12,6 +12,6 @@ from ._ffi import (COMP_NO_ROLLBACK, COMP_ROLLBACK, DESPAWN_IMMEDIATE, DESPAWN_R
                    SYS_RESOURCE, RESOURCE_MAX, RESOURCE_MAX_BYTES, RESOURCE_MAX_BINDINGS, REDUCE_MAX_BINDINGS,
                    REMOTE_INSERT, REMOTE_REMOVE, REMOTE_DESPAWN, REMOTE_ENTITY, REMOTE_MAX_BINDINGS, REMOTE_MAX_COMPONENTS,
                    SUM_MAX_BINDINGS, SUM_MAX_WORDS,
-                   VALUE_MAX_BINDINGS, VALUE_MAX_WORDS, VALUE_MAX_WORLD_BINDINGS)
+                   VALUE_MAX_BINDINGS, VALUE_MAX_WORDS, VALUE_MAX_WORLD_BINDINGS, PEER_INDEX_MAX_BUCKETS)
 from .requests import AdvanceFrame, LoadGameState, SaveGameState  # noqa: F401
 from .world import LIVE, ChecksumParts, DiffEntry, QueryResult, ScatterReport, StateDiff, World  # noqa: F401

@@ -223,6 +223,12 @@ class ScatterReport(C.Structure):
     _fields_ = [("len", C.c_uint64), ("n_rows", C.c_uint64), ("n_applied", C.c_uint64), ("n_dead", C.c_uint64), ("n_absent", C.c_uint64), ("first_bad_row", C.c_uint64)]
 
 
+class PeerIndexDesc(C.Structure):
+    _fields_ = [("comp", C.c_uint32), ("word", C.c_uint32), ("n_buckets", C.c_uint32), ("flags", C.c_uint32)]
+
+
+PEER_INDEX_MAX_BUCKETS = 65535                                 # GGRS_PEER_INDEX_MAX_BUCKETS
+
 # every symbol include/ggrs_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SIGNATURES = {
@@ -241,6 +247,8 @@ SIGNATURES = {
     "ggrs_hip_add_system": (C.c_int, [_P, C.POINTER(SystemDesc)]),
     "ggrs_hip_add_custom_system": (C.c_int, [_P, C.POINTER(CustomSystemDesc)]),
     "ggrs_hip_add_custom_system_peers": (C.c_int, [_P, C.POINTER(CustomSystemDesc), C.POINTER(PeerBinding), C.c_uint32]),
+    "ggrs_hip_register_peer_index": (C.c_int, [_P, C.POINTER(PeerIndexDesc)]),
+    "ggrs_hip_peer_index_read": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "ggrs_hip_add_custom_system_effects": (C.c_int, [_P, C.POINTER(CustomSystemDesc), C.POINTER(PeerBinding), C.c_uint32, C.POINTER(EffectBinding), C.c_uint32]),
     "ggrs_hip_add_custom_system_commands": (C.c_int, [_P, C.POINTER(CustomSystemDesc), C.POINTER(PeerBinding), C.c_uint32, C.POINTER(EffectBinding), C.c_uint32,
                                                       C.POINTER(CommandBinding), C.c_uint32]),

@@ -376,6 +376,19 @@ int ggrs_hip_add_custom_system_values(ggrs_world* w, const ggrs_custom_system_de
     w->systems.push_back(sd);
     return GGRS_OK;
 }
+// THE PEER INDEX (include/ggrs_hip.h): registration only records; seal validates (host_seal.hpp peers_validate) and allocates the arrays next to the peer view.
+int ggrs_hip_register_peer_index(ggrs_world* w, const ggrs_peer_index_desc* d) {
+    if (!w) return GGRS_E_INVALID;
+    if (!d) return w->fail(GGRS_E_INVALID, "register_peer_index without a desc");
+    if (w->sealed) return w->fail(GGRS_E_INVALID, "register_peer_index after the world was sealed");
+    if (w->peer_index.on) return w->fail(GGRS_E_INVALID, "register_peer_index: the world already has a peer index (over word %u of component %u, '%s'): one index per world in this version", w->peer_index.word, w->peer_index.comp, w->comps[w->peer_index.comp].name.c_str());
+    if (d->comp >= w->comps.size() || d->word >= w->comps[d->comp].n_words) return w->fail(GGRS_E_INVALID, "register_peer_index names word %u of component %u, which is not registered", d->word, d->comp);
+    if (d->flags) return w->fail(GGRS_E_INVALID, "register_peer_index over word %u of component %u ('%s'): unknown flags 0x%x", d->word, d->comp, w->comps[d->comp].name.c_str(), d->flags);
+    if (d->n_buckets == 0 || d->n_buckets > GGRS_PEER_INDEX_MAX_BUCKETS)
+        return w->fail(GGRS_E_INVALID, "register_peer_index over word %u of component %u ('%s'): n_buckets must be 1 .. %u (GGRS_PEER_INDEX_MAX_BUCKETS), not %u", d->word, d->comp, w->comps[d->comp].name.c_str(), GGRS_PEER_INDEX_MAX_BUCKETS, d->n_buckets);
+    w->peer_index.on = true; w->peer_index.comp = d->comp; w->peer_index.word = d->word; w->peer_index.n_buckets = d->n_buckets;
+    return GGRS_OK;
+}
 // DEVICE-RESIDENT ROLLBACK RESOURCES (include/ggrs_hip.h): init_resource + rollback_resource_with_copy, checksum_resource_with_hash, and the once-per-frame systems
 // that mutate them.  Registration only records; seal validates the world (host_seal.hpp resources_validate) and puts the initial values into the live block.
 int ggrs_hip_register_resource(ggrs_world* w, const char* name, uint32_t word_bytes, uint32_t n_words, const void* init_words, uint32_t* res_id_out) {
@@ -1429,6 +1442,32 @@ int ggrs_hip_query(ggrs_world* w, int32_t frame, const ggrs_query_desc* desc, vo
     DiffSide S; rc = diff_side(w, frame, &S); if (rc) return rc;
     return query_run(w, S, desc, out_dev, max_rows, report);
 }
+// inspection: the index of a ring frame or of the live world, built exactly as ahead of a request group (publish, then the k_ix_* launches) and copied out.  The
+// view and the index are rebuilt ahead of every group that reads them, so overwriting them here disturbs nothing.
+int ggrs_hip_peer_index_read(ggrs_world* w, int32_t frame, uint32_t* start, uint32_t* slots, uint64_t* n_indexed) {
+    if (!w) return GGRS_E_INVALID;
+    if (!w->peer_index.on) return w->fail(GGRS_E_INVALID, "peer_index_read: the world has no peer index (ggrs_hip_register_peer_index)");
+    if (w->layout_only) return w->fail(GGRS_E_NO_DEVICE, "a layout-only world has no state to index");
+    DeviceGuard dg(w);
+    int rc = diff_ready(w); if (rc) return rc;
+    DiffSide S; rc = diff_side(w, frame, &S); if (rc) return rc;
+    const ggrs_world::PeerIndex& ix = w->peer_index;
+    std::vector<uint32_t> st((size_t)ix.n_buckets + 1, 0);
+    if (S.len) {
+        GgrsJitArgs j; memset(&j, 0, offsetof(GgrsJitArgs, inputs));
+        rc = publish_peers(w, S.ptr, S.len, j); if (rc) return rc;
+        HIPCHK(w, hipMemcpyAsync(st.data(), ix.d_start, st.size() * 4, hipMemcpyDeviceToHost, w->stream));
+        HIPCHK(w, hipStreamSynchronize(w->stream));
+        if (st.back() > S.len) return w->fail(GGRS_E_HIP, "peer index: %u indexed slots in a state of len %llu", st.back(), (unsigned long long)S.len);
+        if (slots && st.back()) {
+            HIPCHK(w, hipMemcpyAsync(slots, ix.d_slots, (size_t)st.back() * 4, hipMemcpyDeviceToHost, w->stream));
+            HIPCHK(w, hipStreamSynchronize(w->stream));
+        }
+    }
+    if (start) memcpy(start, st.data(), st.size() * 4);
+    if (n_indexed) *n_indexed = st.back();
+    return GGRS_OK;
+}
 int ggrs_hip_query_block(ggrs_world* w, const void* block_dev, const ggrs_query_desc* desc, void* out_dev, uint64_t max_rows, ggrs_query_report* report) {
     if (!w) return GGRS_E_INVALID;
     if (w->layout_only) return w->fail(GGRS_E_NO_DEVICE, "a layout-only world has no state to query");
@@ -1610,6 +1649,8 @@ int ggrs_hip_world_kernel_info(ggrs_world* w, char* buf, uint64_t cap, uint64_t*
         add("group_caps", std::to_string(w->cap_saves) + " saves / " + std::to_string(w->cap_steps) + " steps");
         if (w->has_peers) add("peer_view", std::to_string(w->peer_view.n_cols) + " linear columns + visibility words, published from the group's source block ahead of every request group that holds an AdvanceWorld (" +
                                            std::to_string(w->peer_view.publishes) + " publishes so far)");
+        if (w->peer_index.on) add("peer_index", std::to_string(w->peer_index.n_buckets) + " buckets over word " + std::to_string(w->peer_index.word) + " of component " + w->comps[w->peer_index.comp].name +
+                                                ", rebuilt from the view behind every publish (" + std::to_string(w->peer_index.builds) + " builds, " + std::to_string(w->peer_index.launches) + " launches so far)");
         if (w->has_commands) add("command_bindings", std::to_string(__builtin_popcountll(w->cmd_mut_comps)) + " components a system may insert or remove: their presence bits are registers of the generated kernel, "
                                                      "their mask words are rebuilt per Save, and every AdvanceWorld gives their masks and columns fresh row versions");
         if (w->has_resources) add("device_resources", std::to_string(w->resources.size()) + " resources, " + std::to_string(res_total_bytes(w)) + " bytes: wave-uniform registers of the generated kernel, loaded from the source block's current cell "

@@ -817,13 +817,57 @@ inline bool group_aliases(const GgrsJitArgs& j, bool wrote_live) {
 }
 // Peer bindings: the peer view is filled from the group's SOURCE block -- the ring slot the group loads, else the live block: the world at the start of the group's one
 // AdvanceWorld -- by a launch of its own on the world's stream ahead of the group's.  The kernel boundary is the only synchronisation.
-int publish_peers(ggrs_world* w, const Block& src, uint64_t len, GgrsJitArgs& j) {
+// The peer index (ggrs_hip_register_peer_index) is rebuilt from the view the publish just wrote, on the same stream: per radix pass a histogram, a scan and a
+// scatter launch, then the bounds launch (kernels.hpp k_ix_*): 4 launches when n_buckets <= 255, else 7.  A world of at most IX_SMALL_TILES tiles is sorted by
+// one workgroup in one launch (k_ix_small): 2 launches.
+int build_peer_index(ggrs_world* w, uint64_t len) {
+    ggrs_world::PeerIndex& ix = w->peer_index;
+    const ggrs_world::PeerView& pv = w->peer_view;
+    uint32_t at = 0; while (at < pv.n_cols && pv.col[at] != w->comps[ix.comp].col_base + ix.word) ++at;
+    if (at == pv.n_cols) return w->fail(GGRS_E_INVALID, "peer index: its key column is not in the peer view");
+    const uint32_t passes = ix.n_buckets <= 255u ? 1u : 2u, n_tiles = (uint32_t)((len + IX_TILE - 1) / IX_TILE);
+    const double t0 = w->tl.on ? tl_now_us() : 0;
+    const bool small = n_tiles <= IX_SMALL_TILES;                       // one workgroup, one launch: such a world sits on the launch floor
+    IxArgs pa[2]; memset(pa, 0, sizeof pa);
+    for (uint32_t p = 0; p < passes; ++p) {
+        IxArgs& a = pa[p];
+        a.key_col = reinterpret_cast<const uint32_t*>(pv.d_col[at]); a.vis = pv.d_vis; a.key_in = ix.d_key[0]; a.val_in = ix.d_val;
+        a.key_out = ix.d_key[p]; a.val_out = p + 1 == passes ? ix.d_slots : ix.d_val; a.hist = ix.d_hist;
+        a.n = len; a.n_tiles = n_tiles; a.n_buckets = ix.n_buckets; a.shift = 8u * p;
+    }
+    if (small) { ProfScope ps(w, GGRS_KERNEL_ADVANCE, passes * len * 16u); hipLaunchKernelGGL(k_ix_small, dim3(1), dim3(IX_TPB), 0, w->stream, pa[0], pa[1], passes); }
+    else for (uint32_t p = 0; p < passes; ++p) {
+        const IxArgs& a = pa[p];
+        const uint64_t rd = p == 0 ? len * 4u + (len + 7) / 8 : len * 8u, tab = (uint64_t)n_tiles * 256u * 4u;
+        if (p == 0) {
+            { ProfScope ps(w, GGRS_KERNEL_ADVANCE, rd + tab); hipLaunchKernelGGL((k_ix_hist<true>), dim3(n_tiles), dim3(IX_TPB), 0, w->stream, a); }
+            { ProfScope ps(w, GGRS_KERNEL_ADVANCE, 2 * tab); hipLaunchKernelGGL(k_ix_scan, dim3(1), dim3(IX_SCAN_TPB), 0, w->stream, ix.d_hist, n_tiles); }
+            { ProfScope ps(w, GGRS_KERNEL_ADVANCE, rd + tab + len * 8u); hipLaunchKernelGGL((k_ix_scatter<true>), dim3(n_tiles), dim3(IX_TPB), 0, w->stream, a); }
+        } else {
+            { ProfScope ps(w, GGRS_KERNEL_ADVANCE, len * 4u + tab); hipLaunchKernelGGL((k_ix_hist<false>), dim3(n_tiles), dim3(IX_TPB), 0, w->stream, a); }
+            { ProfScope ps(w, GGRS_KERNEL_ADVANCE, 2 * tab); hipLaunchKernelGGL(k_ix_scan, dim3(1), dim3(IX_SCAN_TPB), 0, w->stream, ix.d_hist, n_tiles); }
+            { ProfScope ps(w, GGRS_KERNEL_ADVANCE, rd + tab + len * 8u); hipLaunchKernelGGL((k_ix_scatter<false>), dim3(n_tiles), dim3(IX_TPB), 0, w->stream, a); }
+        }
+    }
+    {
+        uint32_t lg = 1; while ((1ull << lg) < len) ++lg;
+        ProfScope ps(w, GGRS_KERNEL_ADVANCE, (uint64_t)(ix.n_buckets + 1u) * 4u * (lg + 1u));
+        hipLaunchKernelGGL(k_ix_bounds, dim3((ix.n_buckets + 1u + IX_TPB - 1) / IX_TPB), dim3(IX_TPB), 0, w->stream, ix.d_key[passes - 1], ix.d_start, len, ix.n_buckets);
+    }
+    HIPCHK(w, hipGetLastError());
+    const uint32_t n_launches = small ? 2u : 3u * passes + 1u;
+    if (w->tl.on) { w->tl.launch_us += tl_now_us() - t0; w->tl.n_launches += n_launches; }
+    ++ix.builds; ix.launches += n_launches;
+    return GGRS_OK;
+}
+int publish_peers(ggrs_world* w, const uint8_t* src_ptr, uint64_t len, GgrsJitArgs& j) {
     ggrs_world::PeerView& pv = w->peer_view;
     for (uint32_t k = 0; k < pv.n_cols; ++k) j.pv_col[k] = pv.d_col[k];
     j.pv_vis = reinterpret_cast<const ggrs_u64*>(pv.d_vis); j.pv_len = len;
+    if (w->peer_index.on) { j.ix_start = w->peer_index.d_start; j.ix_slots = w->peer_index.d_slots; j.ix_buckets = len ? w->peer_index.n_buckets : 0u; }   // (an empty world: no launch, every bucket empty)
     if (!len) return GGRS_OK;                                          // an empty world: every bounds test fails, nothing is read
     PeerPubArgs a; memset(&a, 0, sizeof a);
-    a.src = src.ptr; a.vis = pv.d_vis; a.len = len; a.off_alive = w->off_alive;
+    a.src = src_ptr; a.vis = pv.d_vis; a.len = len; a.off_alive = w->off_alive;
     a.n_pres = pv.n_pres; a.n_cols = pv.n_cols; a.n_units = (uint32_t)((len + 63) / 64);
     uint64_t bytes_slot = 0;
     for (uint32_t k = 0; k < pv.n_pres; ++k) a.off_present[k] = w->off_present[pv.pres_comp[k]];
@@ -838,8 +882,9 @@ int publish_peers(ggrs_world* w, const Block& src, uint64_t len, GgrsJitArgs& j)
     HIPCHK(w, hipGetLastError());
     if (w->tl.on) { w->tl.launch_us += tl_now_us() - t0; ++w->tl.n_launches; }
     ++pv.publishes;
-    return GGRS_OK;
+    return w->peer_index.on ? build_peer_index(w, len) : GGRS_OK;
 }
+int publish_peers(ggrs_world* w, const Block& src, uint64_t len, GgrsJitArgs& j) { return publish_peers(w, src.ptr, len, j); }
 // Effect bindings: the sends the group's launch left in the inbox are combined into the live block -- and the identities put back -- by a launch of its own on the
 // world's stream right BEHIND the group's, enqueued with it (never lazily): whatever follows on the stream -- a Save, a download, the next group's peer publish -- sees
 // the frame with its effects, and the inbox holds identities again.  The kernel boundary is the only synchronisation.

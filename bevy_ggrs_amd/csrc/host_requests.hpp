@@ -329,7 +329,7 @@ std::string custom_source(const ggrs_world* w, const ggrs_world::Custom& c, cons
     snprintf(buf, sizeof buf, "static_assert(sizeof(GgrsCustomArgs) == %zu, \"host/device argument block mismatch\");\n", sizeof(GgrsCustomArgs));
     s += buf;
     s += GGRS_FRAME_TEXT;
-    s += entity_text(c.n_fx != 0, c.n_peer != 0, c.n_cmd != 0, false, c.n_res != 0, c.n_red != 0, c.n_rem != 0 || c.n_val != 0, c.n_sum != 0, c.n_val != 0);   // (a system with peer, effect or command bindings only ever RUNS inside the generated kernel: here its text is compiled against an empty view, an empty inbox and unset opt words)
+    s += entity_text(c.n_fx != 0, c.n_peer != 0, c.n_cmd != 0, false, c.n_res != 0, c.n_red != 0, c.n_rem != 0 || c.n_val != 0, c.n_sum != 0, c.n_val != 0, w->peer_index.on);   // (a system with peer, effect or command bindings only ever RUNS inside the generated kernel: here its text is compiled against an empty view, an empty inbox and unset opt words)
     if (c.n_cmd || c.n_rem || c.n_val) s += cmd_entity_typedef(w, c, c.n_rem != 0 || c.n_val != 0, c.n_val != 0);
     s += "#line 1 \"ggrs_system\"\n";
     s += user;

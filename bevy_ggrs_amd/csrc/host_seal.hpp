@@ -33,12 +33,15 @@ void sp_release(ggrs_world* w) {
 void peer_view_release(ggrs_world* w) {
     if (w->peer_view.alloc) (void)hipFree(w->peer_view.alloc);
     w->peer_view = ggrs_world::PeerView{};
+    ggrs_world::PeerIndex& ix = w->peer_index;                          // the index keeps its registration (on, comp, word, n_buckets): only the buffers go
+    if (ix.alloc) (void)hipFree(ix.alloc);
+    ix.alloc = nullptr; ix.d_start = ix.d_slots = ix.d_key[0] = ix.d_key[1] = ix.d_val = ix.d_hist = nullptr;
 }
 // Peer bindings (ggrs_hip_add_custom_system_peers): what the first version refuses, and the registration-order rules under which the values at the START of the
 // frame are what Bevy's sequential schedule would show a second Query.  After build_layout (the systems' write sets); no device needed -- a GGRS_WORLD_LAYOUT_ONLY
 // world is checked by ggrs_hip_generated_kernel_source.
 int peers_validate(ggrs_world* w) {
-    if (!world_has_peers(w)) return GGRS_OK;
+    if (!world_has_peers(w) && !w->peer_index.on) return GGRS_OK;
     auto cname = [&](uint32_t c) { return w->comps[c].name.c_str(); };
     auto can_despawn = [&](size_t k) {
         const ggrs_system_desc& d = w->systems[k];
@@ -48,6 +51,32 @@ int peers_validate(ggrs_world* w) {
         for (uint32_t j = 0; j < w->customs[d.comp[0]].n_rem; ++j) if (w->customs[d.comp[0]].xflags[j] & GGRS_REMOTE_DESPAWN) return true;      // a remote despawner (e.send_despawn)
         return source_has_token(src, "despawn") || source_has_token(src, "despawn_rollback") || source_has_token(src, "kill");
     };
+    if (w->peer_index.on) {
+        // The peer index (ggrs_hip_register_peer_index): the key column is peer binding "key" of every system that uses the index -- a system whose source holds the
+        // token `bucket` -- and the peer rules apply to it: the members of a bucket are the entities whose key had that value at the START of the frame
+        const ggrs_world::PeerIndex& ix = w->peer_index;
+        const Comp& kc = w->comps[ix.comp];
+        const uint32_t kcl = kc.col_base + ix.word;
+        if (kc.word_bytes != 4) return w->fail(GGRS_E_INVALID, "peer index: its key, word %u of component %u ('%s'), has %u bytes: a key is a 4-byte word", ix.word, ix.comp, cname(ix.comp), kc.word_bytes);
+        if (kc.s_n_words) return w->fail(GGRS_E_INVALID, "peer index: its key, word %u of component %u ('%s'), belongs to a component with a Strategy: not supported", ix.word, ix.comp, cname(ix.comp));
+        if (kc.no_rollback) return w->fail(GGRS_E_INVALID, "peer index: its key, word %u of component %u ('%s'), belongs to a component that is not registered for rollback (GGRS_COMP_NO_ROLLBACK): not supported", ix.word, ix.comp, cname(ix.comp));
+        if (w->capacity > (1ull << 32)) return w->fail(GGRS_E_INVALID, "peer index over word %u of component %u ('%s'): its slots are 32-bit, the world's capacity %llu exceeds 2^32", ix.word, ix.comp, cname(ix.comp), (unsigned long long)w->capacity);
+        size_t users = 0;
+        for (size_t i = 0; i < w->systems.size(); ++i) {
+            if (w->systems[i].kind != GGRS_SYS_CUSTOM) continue;
+            const ggrs_world::Custom& c = w->customs[w->systems[i].comp[0]];
+            if (!source_has_token(c.source, "bucket")) continue;
+            ++users;
+            if (!c.n_peer) return w->fail(GGRS_E_INVALID, "custom system '%s' (system %zu) uses the peer index over word %u of component %u ('%s') and has no peer binding: e.bucket(..) hands out slots for e.peer(..)", c.name.c_str(), i, ix.word, ix.comp, cname(ix.comp));
+            for (uint32_t b = 0; b < c.n_bind; ++b) if (w->comps[c.comp[b]].col_base + c.word[b] == kcl)
+                return w->fail(GGRS_E_INVALID, "custom system '%s' (system %zu) uses the peer index and binds its key, word %u of component %u ('%s'), as its own binding %u: a system's own bindings and the index key share no column", c.name.c_str(), i, ix.word, ix.comp, cname(ix.comp), b);
+            for (size_t k = 0; k < i; ++k) for (uint32_t wc : w->sys_writes[k]) if (wc == kcl)
+                return w->fail(GGRS_E_INVALID, "custom system '%s' (system %zu) uses the peer index over word %u of component %u ('%s'), which system %zu, registered before it, writes: every system that uses the index is registered before every system that writes its key", c.name.c_str(), i, ix.word, ix.comp, cname(ix.comp), k);
+            for (size_t k = 0; k < i; ++k) if (can_despawn(k))
+                return w->fail(GGRS_E_INVALID, "custom system '%s' (system %zu) uses the peer index over word %u of component %u ('%s') and system %zu, registered before it, can despawn: every system that uses the index is registered before every other system that can despawn", c.name.c_str(), i, ix.word, ix.comp, cname(ix.comp), k);
+        }
+        if (!users) return w->fail(GGRS_E_INVALID, "peer index over word %u of component %u ('%s'): no system of this world uses it (no ggrs_system source names `bucket`)", ix.word, ix.comp, cname(ix.comp));
+    }
     uint32_t cols[GGRS_PEER_MAX_COLUMNS];
     const uint32_t n_cols = peer_cols(w, cols);
     if (n_cols > GGRS_PEER_MAX_COLUMNS) return w->fail(GGRS_E_INVALID, "peer bindings: %u distinct peer-bound columns in this world, at most %d (GGRS_PEER_MAX_COLUMNS)", n_cols, GGRS_PEER_MAX_COLUMNS);
@@ -98,6 +127,7 @@ int effects_validate(ggrs_world* w) {
             const ggrs_world::Custom& c = w->customs[d.comp[0]];
             for (uint32_t b = 0; b < c.n_bind; ++b) if (colof(c.comp[b], c.word[b]) == cl) return true;
             for (uint32_t j = 0; j < c.n_peer; ++j) if (colof(c.pcomp[j], c.pword[j]) == cl) return true;
+            if (w->peer_index.on && colof(w->peer_index.comp, w->peer_index.word) == cl && source_has_token(c.source, "bucket")) return true;      // the index key: peer binding "key" of every system that uses the index
             for (uint32_t j = 0; j < c.n_cmd; ++j) if (span(c.ccomp[j], 0, w->comps[c.ccomp[j]].n_words)) return true;      // a command-bound component: every column
             return false;
         }
@@ -245,6 +275,7 @@ int remote_validate(ggrs_world* w) {
             const ggrs_world::Custom& c = w->customs[d.comp[0]];
             for (uint32_t b = 0; b < c.n_bind; ++b) if (c.comp[b] == cc) return true;
             for (uint32_t j = 0; j < c.n_peer; ++j) if (c.pcomp[j] == cc) return true;
+            if (w->peer_index.on && w->peer_index.comp == cc && source_has_token(c.source, "bucket")) return true;      // the index key's component: peer-bound by every system that uses the index
             for (uint32_t j = 0; j < c.n_cmd; ++j) if (c.ccomp[j] == cc) return true;
             for (uint32_t j = 0; j < c.n_fx; ++j) if (c.fcomp[j] == cc) return true;
             return false;
@@ -645,6 +676,24 @@ int seal_impl(ggrs_world* w) {
         pv.d_vis = reinterpret_cast<uint64_t*>(pv.alloc + vis_off);
         if (w->knobs.debug_poison) HIPCHK(w, hipMemsetAsync(pv.alloc, 0xA5, bytes, w->stream));
         HIPCHK(w, hipMemsetAsync(pv.d_vis, 0, vis_bytes, w->stream));
+    }
+    if (w->peer_index.on) {
+        // the peer index, next to the view: ix_start (zeroed: every bucket empty before the first build), ix_slots, the two key arrays and the slot array of the radix
+        // passes (cap_pad words each), the digit-major tile histograms
+        ggrs_world::PeerIndex& ix = w->peer_index;
+        const uint64_t start_bytes = align_up(((uint64_t)ix.n_buckets + 1u) * 4u, ALIGN), col_bytes = align_up(w->cap_pad * 4u, ALIGN);
+        const uint64_t hist_bytes = align_up((w->cap_pad + IX_TILE - 1) / IX_TILE * 256u * 4u, ALIGN), bytes = start_bytes + 4 * col_bytes + hist_bytes;
+        HIPCHK(w, hipMalloc((void**)&ix.alloc, bytes));
+        uint8_t* q = ix.alloc;
+        ix.d_start = reinterpret_cast<uint32_t*>(q); q += start_bytes;
+        ix.d_slots = reinterpret_cast<uint32_t*>(q); q += col_bytes;
+        ix.d_key[0] = reinterpret_cast<uint32_t*>(q); q += col_bytes;
+        ix.d_key[1] = reinterpret_cast<uint32_t*>(q); q += col_bytes;
+        ix.d_val = reinterpret_cast<uint32_t*>(q); q += col_bytes;
+        ix.d_hist = reinterpret_cast<uint32_t*>(q);
+        if (w->knobs.debug_poison) HIPCHK(w, hipMemsetAsync(ix.alloc, 0xA5, bytes, w->stream));
+        HIPCHK(w, hipMemsetAsync(ix.d_start, 0, start_bytes, w->stream));
+        ix.builds = ix.launches = 0;
     }
     if (w->has_effects) {
         // the inbox: one linear array of cap_pad words per distinct effect column, filled with the op's identity -- what it holds whenever no group-and-apply pair is in flight

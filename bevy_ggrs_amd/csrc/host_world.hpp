@@ -204,6 +204,14 @@ struct ggrs_world {
         uint64_t publishes = 0;
     } peer_view;
     bool has_peers = false;              // some system has peer bindings (set at seal: peer_cols)
+    // THE PEER INDEX (ggrs_hip_register_peer_index): the multimap key -> slots over the peer view, rebuilt right behind every publish.  d_start[0 .. n_buckets] =
+    // exclusive prefix counts, d_slots = the members bucket by bucket, ascending slot inside a bucket.  The key column is a peer-bound column of the world (peer_cols).
+    // d_key[2] / d_val = the ping-pong (key, slot) pairs of the radix passes, d_hist = the digit-major tile histograms (kernels.hpp k_ix_*)
+    struct PeerIndex {
+        bool on = false; uint32_t comp = 0, word = 0, n_buckets = 0;
+        uint32_t* d_start = nullptr; uint32_t* d_slots = nullptr; uint32_t* d_key[2] = {}; uint32_t* d_val = nullptr; uint32_t* d_hist = nullptr; uint8_t* alloc = nullptr;
+        uint64_t builds = 0, launches = 0;
+    } peer_index;
     // THE INBOX of a world with effect bindings (allocated at seal): one LINEAR array of cap_pad words per distinct effect column, holding the op's identity
     // whenever no group-and-apply pair is in flight.  A send of the generated kernel is one relaxed atomic into it; k_apply_effects, on the world's stream right
     // behind every request group that holds an AdvanceWorld, combines it into the live block and puts the identities back.  Not snapshot state

@@ -356,8 +356,31 @@ inline std::string res_system_typedef(const ggrs_world* w, const ggrs_world::Res
     GGRS_VAL_ACC_("val_f32", "float", "0u", "4") \
     GGRS_VAL_ACC_("val_u64", "ggrs_u64", "1u", "8") \
     "    __device__ void send_value(ggrs_u64 s, int j) __attribute__((enable_if(j >= 0 && j < 4 && ((GGRS_XV >> j) & 1u), \"e.send_value(slot, j): value binding j (a constant) must be declared\"))) { vt_[j] = s; }\n"
-inline std::string entity_text(bool effects, bool peers, bool commands, bool default_typedef = true, bool resources = false, bool reduces = false, bool remote = false, bool sums = false, bool values = false) {
+// ... in a world with a peer index (ggrs_hip_register_peer_index): e.bucket(key) looks a bucket of the frame's multimap key -> slots up -- a bounds test on the key
+// and two 4-byte loads, ix_start[key] and ix_start[key + 1]; b.slot(i) is one 4-byte load of ix_slots[start + i], members in ASCENDING slot order.  Plain loads, as
+// the gather's: an earlier launch wrote the arrays, neighbours share their lines.  Nothing of GgrsBucket lives in memory once ggrs_system is inlined.
+#define GGRS_BUCKET_TYPE_TEXT \
+    "#ifndef GGRS_G\n#define GGRS_G __attribute__((address_space(1)))\n#endif\n" \
+    "struct GgrsBucket {\n" \
+    "    unsigned long sl_; ggrs_u32 b_, n_;\n" \
+    "    __device__ ggrs_u32 count() const { return n_; }\n" \
+    "    __device__ ggrs_u64 slot(ggrs_u32 i) const {          /* the i-th member in ascending slot order; ~0 beyond count(): e.peer(~0) is !ok() */\n" \
+    "        return i < n_ ? (ggrs_u64)*(const GGRS_G ggrs_u32*)(sl_ + ((ggrs_u64)b_ + i) * 4ul) : ~0ull;\n" \
+    "    }\n" \
+    "};\n"
+#define GGRS_BUCKET_MEMBERS_TEXT \
+    "    unsigned long ixs_ = 0, ixl_ = 0; ggrs_u32 ixn_ = 0;   /* 0 buckets: a system that does not use the index sees every bucket empty */\n" \
+    "    __device__ GgrsBucket bucket(ggrs_u32 key) const {    /* the entities whose key word was `key` at the start of the frame */\n" \
+    "        GgrsBucket b; b.sl_ = ixl_; b.b_ = 0u; b.n_ = 0u;\n" \
+    "        if (key < ixn_) {\n" \
+    "            const ggrs_u32 s0 = *(const GGRS_G ggrs_u32*)(ixs_ + (ggrs_u64)key * 4ul), s1 = *(const GGRS_G ggrs_u32*)(ixs_ + (ggrs_u64)key * 4ul + 4ul);\n" \
+    "            b.b_ = s0; b.n_ = s1 - s0;\n" \
+    "        }\n" \
+    "        return b;\n" \
+    "    }\n"
+inline std::string entity_text(bool effects, bool peers, bool commands, bool default_typedef = true, bool resources = false, bool reduces = false, bool remote = false, bool sums = false, bool values = false, bool index = false) {
     std::string t = effects ? GGRS_ENTITY_EFFECTS_TEXT : (peers ? GGRS_ENTITY_PEERS_TEXT : GGRS_ENTITY_TEXT);
+    if (index) { t.insert(t.rfind("};\n"), GGRS_BUCKET_MEMBERS_TEXT); t.insert(t.find("struct GgrsEntity {\n"), GGRS_BUCKET_TYPE_TEXT); }
     if (resources) t.insert(t.rfind("};\n"), GGRS_RES_MEMBERS_TEXT);
     if (reduces) t.insert(t.rfind("};\n"), GGRS_RED_MEMBERS_TEXT);
     if (sums) t.insert(t.rfind("};\n"), GGRS_SUM_MEMBERS_TEXT);
@@ -758,6 +781,9 @@ struct GgrsJitArgs {
     // THE PEER VIEW of a world with peer bindings (host_world.hpp PeerView; present only in such worlds): the linear arrays of the distinct peer-bound columns, the
     // visibility words and the len of the block k_publish_peers copied them from -- the group's source block, i.e. the world at the start of the group's one AdvanceWorld
     const unsigned char* pv_col[16]; const ggrs_u64* pv_vis; ggrs_u64 pv_len;
+    // THE PEER INDEX of a world that registered one (host_world.hpp PeerIndex; present only in such worlds): the exclusive prefix counts of the buckets, the members
+    // bucket by bucket in ascending slot order, and the number of buckets -- 0 when the group's source block is empty (nothing was built: every bucket is empty)
+    const ggrs_u32* ix_start; const ggrs_u32* ix_slots; ggrs_u32 ix_buckets;
     // THE INBOX of a world with effect bindings (host_world.hpp EffectInbox; present only in such worlds): the linear arrays of the distinct effect columns and the
     // len of the group's source block -- RollbackOrdered::len at the start of the group's one AdvanceWorld: a send to a slot at or beyond it is dropped
     unsigned char* fx_col[8]; ggrs_u64 fx_len;
@@ -800,7 +826,7 @@ struct JitLayout {
     struct Member { uint32_t bytes = 0, save_dst = 0, save_rows = 0, save_len = 0, spawn_payload = 0, spawn_first = 0, live = 0, live_rows = 0, marks_dst = 0, save_pmask = 0, live_pmask = 0,
                     spawn_count = 0, n_inputs = 0, inputs = 0, save_tagok = 0, live_tagok = 0; } m;
 };
-struct JitNeeds { bool spawn, inputs, marks, box, vtags, devspawn, devstream, nr, peers, effects, commands, res, red, rem, sum, val; };
+struct JitNeeds { bool spawn, inputs, marks, box, vtags, devspawn, devstream, nr, peers, effects, commands, res, red, rem, sum, val, index; };
 // the distinct peer-bound columns of the world in order of first use (systems in registration order, peer bindings in order) and the components they belong to;
 // returns how many there are (more than GGRS_PEER_MAX_COLUMNS: only the first ones are written -- peers_validate refuses such a world)
 inline uint32_t peer_cols(const ggrs_world* w, uint32_t* cols, uint32_t* n_pres = nullptr, uint32_t* pres = nullptr) {
@@ -814,6 +840,15 @@ inline uint32_t peer_cols(const ggrs_world* w, uint32_t* cols, uint32_t* n_pres 
         bool pseen = false;
         for (uint32_t k = 0; k < np; ++k) pseen |= pres && pres[k] == c.pcomp[j];
         if (pres && !pseen && np < GGRS_PEER_MAX_COLUMNS) pres[np++] = c.pcomp[j];
+    }
+    if (w->peer_index.on && w->peer_index.comp < w->comps.size()) {       // the peer index's key column is a peer-bound column of the world; its component's presence joins the visibility bit
+        const uint32_t cl = w->comps[w->peer_index.comp].col_base + w->peer_index.word;
+        bool seen = false;
+        for (uint32_t k = 0; k < n && k < GGRS_PEER_MAX_COLUMNS; ++k) seen |= cols[k] == cl;
+        if (!seen) { if (n < GGRS_PEER_MAX_COLUMNS) cols[n] = cl; ++n; }
+        bool pseen = false;
+        for (uint32_t k = 0; k < np; ++k) pseen |= pres && pres[k] == w->peer_index.comp;
+        if (pres && !pseen && np < GGRS_PEER_MAX_COLUMNS) pres[np++] = w->peer_index.comp;
     }
     if (n_pres) *n_pres = np;
     return n;
@@ -869,6 +904,7 @@ JitLayout jit_layout(const ggrs_world* w) {
         F1("ggrs_u64", src_tagok, need.vtags); F1("ggrs_u64", live_tagok, need.vtags); F1("ggrs_u64*", skip_count, need.vtags); FA("ggrs_u64", save_tagok, S, need.vtags);
         F1("ggrs_u64*", gone, need.nr);
         FA("const unsigned char*", pv_col, n_pv, need.peers); F1("const ggrs_u64*", pv_vis, need.peers); F1("ggrs_u64", pv_len, need.peers);
+        F1("const ggrs_u32*", ix_start, need.index); F1("const ggrs_u32*", ix_slots, need.index);
         FA("unsigned char*", fx_col, n_fx, need.effects); F1("ggrs_u64", fx_len, need.effects);
         F1("const unsigned char*", res_src, need.res); F1("unsigned char*", rd_inbox, need.red);
         F1("ggrs_u32*", rx_inbox, need.rem); F1("ggrs_u64", rx_len, need.rem && !need.effects);
@@ -883,7 +919,7 @@ JitLayout jit_layout(const ggrs_world* w) {
         F1("ggrs_u64*", sp_sums, resident); F1("ggrs_u32", sp_epoch, need.devspawn); F1("unsigned char*", sp_prec, resident); F1("ggrs_u64*", sp_link, resident);
         F1("ggrs_u64*", sp_len, need.devspawn); F1("ggrs_u64", sp_cap, need.devspawn);
         F1("ggrs_u64*", sp_ctl, need.devstream); F1("ggrs_u64*", sp_desc, need.devstream); F1("ggrs_u64*", sp_recs, need.devstream); F1("ggrs_u64", sp_ticket_base, need.devstream);
-        F1("ggrs_u32", res_alt, need.res);
+        F1("ggrs_u32", res_alt, need.res); F1("ggrs_u32", ix_buckets, need.index);
         F1("ggrs_u32", n_units, true); F1("ggrs_u32", sp_tiles, need.devspawn); F1("ggrs_u32", vtags, need.vtags); F1("ggrs_u32", tag_base, need.vtags); F1("ggrs_u32", cached_saves, true); F1("ggrs_u32", ff_blocks, true); F1("ggrs_u32", ff_nvals, true); F1("ggrs_u32", ff_g, true); F1("ggrs_u32", ff_stride, true); F1("ggrs_u32", ff_istride, true); F1("ggrs_u32", ff_split, true); F1("ggrs_u32", ff_self, true);
         FS("ggrs_u32", dt_bits, true); FS("ggrs_u32", aux_bits, need.box); FS("int", step_frame, true); FS("int", step_confirmed, need.marks);
         FS("ggrs_u32", spawn_count, need.spawn);
@@ -1101,7 +1137,8 @@ inline uint64_t jit_marks_rec_frames_off(const ggrs_world* w) { return align_up(
 inline uint64_t jit_marks_rec_bytes(const ggrs_world* w) { return jit_marks_rec_frames_off(w) + align_up(w->cap_pad * 4, ALIGN); }
 // which optional parts of the argument block this world's kernel reads
 JitNeeds jit_needs(const ggrs_world* w) {
-    JitNeeds n{false, false, false, false, false, false, false, false, false, false, false, false, false, false, false, false};
+    JitNeeds n{false, false, false, false, false, false, false, false, false, false, false, false, false, false, false, false, false};
+    n.index = w->peer_index.on;
     n.val = world_has_values(w);
     n.sum = world_has_sums(w);
     n.rem = world_has_remote(w);
@@ -1271,7 +1308,7 @@ struct JitGen {
                                     "#define GGRS_SP_READ %uu                                                           // sp_desc[GGRS_SP_READ x tiles + tile]: that tile has read its starting len\n",
                          2u + (unsigned)MAX_TICK_SAVES, 2u * (unsigned)MAX_TICK_STEPS);
         s += GGRS_FRAME_TEXT;
-        s += entity_text(need.effects, need.peers, need.commands, true, need.res, need.red, need.rem, need.sum, need.val);
+        s += entity_text(need.effects, need.peers, need.commands, true, need.res, need.red, need.rem, need.sum, need.val, need.index);
         if (need.res) s += GGRS_RESOURCES_TEXT;
         if (need.red) s += GGRS_REDUCE_WAVE_TEXT;
         if (need.sum) s += GGRS_SUM_WAVE_TEXT;
@@ -1944,6 +1981,8 @@ struct JitGen {
                 sfmt(s, "                ent.pv_.col[%u] = (unsigned long)a.pv_col[%u]; ent.pv_.wb[%u] = %uu;\n", j, at, j, w->comps[c.pcomp[j]].word_bytes);
             }
         }
+        if (need.index && source_has_token(c.source, "bucket"))            // the system uses the peer index: the arrays the build behind the publish left
+            s += "                ent.ixs_ = (unsigned long)a.ix_start; ent.ixl_ = (unsigned long)a.ix_slots; ent.ixn_ = a.ix_buckets;\n";
         if (c.n_fx) {
             // effect bindings: binding j sends into its column's linear array of the world's inbox, with the column's op; the bounds length is the source block's len
             uint32_t fx_cols[GGRS_EFFECT_MAX_COLUMNS]; const uint32_t n_fx = std::min<uint32_t>(effect_cols(w, fx_cols), GGRS_EFFECT_MAX_COLUMNS);

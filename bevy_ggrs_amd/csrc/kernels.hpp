@@ -636,6 +636,159 @@ __global__ __launch_bounds__(TPB) void k_publish_peers(PeerPubArgs a) {
     }
 }
 
+// THE PEER INDEX (ggrs_hip_register_peer_index; host_world.hpp ggrs_world::PeerIndex).  Right behind every publish, the multimap key -> slots is rebuilt from the
+// VIEW (the linear key column and the visibility words): a stable LSD radix sort of (key16, slot) pairs with 8-bit digits -- the input order is slot order, so
+// stability alone gives ascending slots inside a bucket; a slot that is not indexed (not visible, or its key >= n_buckets) sorts as key 65535, behind every bucket.
+// One pass when n_buckets <= 255, else two.  Per pass: k_ix_hist (a tile's digit histogram, into the digit-major table), k_ix_scan (one workgroup: the table's
+// exclusive prefix sums), k_ix_scatter (the stable scatter).  Then k_ix_bounds writes ix_start from the sorted keys.  Nothing here depends on the order in which
+// lanes, waves or workgroups arrive: the atomics only COUNT (integer adds commute), every position is counts + a rank built from ballots; and the work per slot does
+// not depend on how the keys are distributed (a wave adds its digit count once per distinct digit: one bucket for everyone is the CHEAPEST case).  The kernel
+// boundary is the only synchronisation.
+constexpr uint32_t IX_TPB = 256, IX_ROUNDS = 8, IX_TILE = IX_TPB * IX_ROUNDS;      // a workgroup walks its 2048-slot tile in 8 rounds of 256, in slot order
+constexpr uint32_t IX_NONE = 65535u, IX_SCAN_TPB = 1024;
+struct IxArgs {
+    const uint32_t* key_col; const uint64_t* vis;        // the first pass reads the view ...
+    const uint32_t* key_in; const uint32_t* val_in;      // ... a later one the pairs the pass before it left
+    uint32_t* key_out; uint32_t* val_out; uint32_t* hist;
+    uint64_t n; uint32_t n_tiles, n_buckets, shift;
+};
+template <bool FIRST> __device__ __forceinline__ uint32_t ix_key(const IxArgs& a, uint64_t i) {
+    if (!FIRST) return a.key_in[i];
+    const uint32_t k = a.key_col[i];
+    return ((a.vis[i >> 6] >> (i & 63ull)) & 1ull) && k < a.n_buckets ? k : IX_NONE;
+}
+// the lanes of the wave that hold the same digit as this one (a lane beyond the data matches nobody): one wave64 ballot per digit bit
+__device__ __forceinline__ uint64_t ix_match(uint32_t d, bool act) {
+    uint64_t m = __ballot(act);
+#pragma unroll
+    for (uint32_t b = 0; b < 8; ++b) { const bool bit = (d >> b) & 1u; const uint64_t bal = __ballot(act && bit); m &= bit ? bal : ~bal; }
+    return act ? m : 0ull;
+}
+// one tile's digit histogram into h (LDS, zeroed, a barrier behind the zeroing): 8 rounds; the caller puts a barrier behind it
+template <bool FIRST> __device__ __forceinline__ void ix_hist_tile(const IxArgs& a, uint32_t tile, uint32_t* h) {
+    const uint32_t t = threadIdx.x, lane = t & 63u;
+    for (uint32_t r = 0; r < IX_ROUNDS; ++r) {
+        const uint64_t i = (uint64_t)tile * IX_TILE + r * IX_TPB + t;
+        const bool act = i < a.n;
+        const uint32_t d = act ? (ix_key<FIRST>(a, i) >> a.shift) & 255u : 0u;
+        const uint64_t m = ix_match(d, act);
+        if (act && !(m & ((1ull << lane) - 1ull))) atomicAdd(&h[d], (uint32_t)__popcll(m));      // the lowest lane of every digit group adds the group's count
+    }
+}
+template <bool FIRST> __global__ __launch_bounds__(IX_TPB) void k_ix_hist(IxArgs a) {
+    __shared__ uint32_t h[256];
+    const uint32_t t = threadIdx.x;
+    h[t] = 0;
+    __syncthreads();
+    ix_hist_tile<FIRST>(a, blockIdx.x, h);
+    __syncthreads();
+    a.hist[(uint64_t)t * a.n_tiles + blockIdx.x] = h[t];
+}
+// exclusive prefix sums over the 256 x n_tiles table entries, in place, by ONE workgroup of 16 waves (as k_diff_scan: no look-back, nothing waits on another
+// workgroup).  The table is n_tiles units of 256 words; a wave owns a contiguous run of units and walks it twice with 16-byte loads -- 64 lanes x 4 words, coalesced --:
+// once for the run's total (the 16 totals meet in LDS), once to write the prefixes: a lane's four words, a shuffle scan across the wave, the wave's running carry
+__global__ __launch_bounds__(IX_SCAN_TPB) void k_ix_scan(uint32_t* hist, uint32_t n_units) {
+    __shared__ uint32_t tot[IX_SCAN_TPB / 64];
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    const uint32_t u0 = (uint32_t)((uint64_t)wv * n_units / (IX_SCAN_TPB / 64)), u1 = (uint32_t)((uint64_t)(wv + 1u) * n_units / (IX_SCAN_TPB / 64));
+    uint4* const h4 = reinterpret_cast<uint4*>(hist);
+    uint32_t s = 0;
+    for (uint32_t u = u0; u < u1; ++u) { const uint4 v = h4[(uint64_t)u * 64u + lane]; s += v.x + v.y + v.z + v.w; }
+    for (uint32_t off = 32; off; off >>= 1) s += __shfl_xor(s, off);
+    if (lane == 0) tot[wv] = s;
+    __syncthreads();
+    uint32_t carry = 0;
+    for (uint32_t q = 0; q < wv; ++q) carry += tot[q];
+    for (uint32_t u = u0; u < u1; ++u) {
+        const uint4 v = h4[(uint64_t)u * 64u + lane];
+        const uint32_t t = v.x + v.y + v.z + v.w;
+        uint32_t inc = t;
+        for (uint32_t off = 1; off < 64; off <<= 1) { const uint32_t o = __shfl_up(inc, off); if (lane >= off) inc += o; }
+        const uint32_t ex = carry + inc - t;
+        h4[(uint64_t)u * 64u + lane] = make_uint4(ex, ex + v.x, ex + v.x + v.y, ex + v.x + v.y + v.z);
+        carry += __shfl(inc, 63);
+    }
+}
+// one tile's stable scatter: base[d] (LDS) = where the tile's first pair of digit d goes, cnt (LDS) zeroed, a barrier behind both; ends on a barrier
+template <bool FIRST> __device__ __forceinline__ void ix_scatter_tile(const IxArgs& a, uint32_t tile, uint32_t* base, uint32_t (*cnt)[256]) {
+    const uint32_t t = threadIdx.x, lane = t & 63u, wv = t >> 6;
+    for (uint32_t r = 0; r < IX_ROUNDS; ++r) {
+        const uint64_t i = (uint64_t)tile * IX_TILE + r * IX_TPB + t;
+        const bool act = i < a.n;
+        const uint32_t k = act ? ix_key<FIRST>(a, i) : 0u, d = (k >> a.shift) & 255u;
+        const uint32_t v = FIRST ? (uint32_t)i : (act ? a.val_in[i] : 0u);
+        const uint64_t m = ix_match(d, act), below = m & ((1ull << lane) - 1ull);
+        if (act && !below) cnt[wv][d] = (uint32_t)__popcll(m);        // one plain store per distinct digit of the wave
+        __syncthreads();
+        if (act) {
+            uint32_t pos = base[d] + (uint32_t)__popcll(below);         // the rank inside the wave: the lanes below with the same digit
+            for (uint32_t q = 0; q < wv; ++q) pos += cnt[q][d];         // ... and the waves before it
+            a.key_out[pos] = k; a.val_out[pos] = v;
+        }
+        __syncthreads();
+        uint32_t add = 0;
+        for (uint32_t q = 0; q < IX_TPB / 64; ++q) { add += cnt[q][t]; cnt[q][t] = 0; }
+        base[t] += add;
+        __syncthreads();
+    }
+}
+template <bool FIRST> __global__ __launch_bounds__(IX_TPB) void k_ix_scatter(IxArgs a) {
+    __shared__ uint32_t base[256], cnt[IX_TPB / 64][256];
+    const uint32_t t = threadIdx.x;
+    base[t] = a.hist[(uint64_t)t * a.n_tiles + blockIdx.x];            // where this tile's first pair of digit t goes
+    for (uint32_t q = 0; q < IX_TPB / 64; ++q) cnt[q][t] = 0;
+    __syncthreads();
+    ix_scatter_tile<FIRST>(a, blockIdx.x, base, cnt);
+}
+// THE SMALL FORM: a world of at most IX_SMALL_TILES tiles (2048 slots) is sorted by ONE workgroup in ONE launch -- the same tile bodies, the tiles one after the
+// other, the digit-major table and its scan in LDS, a barrier where the large form has a kernel boundary (the second pass reads pairs that other waves of this
+// workgroup stored: a workgroup-scope fence and the barrier order them).  Such a world sits on the launch floor: 2 launches (this one, k_ix_bounds) instead of 4 or 7
+constexpr uint32_t IX_SMALL_TILES = 1;      // measured (profiles/peer_index): one workgroup walks a tile in ~14 us per pass -- a win over 3 launches per pass for one tile, a loss from two tiles on
+template <bool FIRST> __device__ __forceinline__ void ix_small_pass(const IxArgs& a, uint32_t* h, uint32_t* tab, uint32_t* base, uint32_t (*cnt)[256]) {
+    const uint32_t t = threadIdx.x, T = a.n_tiles;
+    for (uint32_t b = 0; b < T; ++b) {
+        h[t] = 0;
+        __syncthreads();
+        ix_hist_tile<FIRST>(a, b, h);
+        __syncthreads();
+        tab[t * T + b] = h[t];
+    }
+    uint32_t sum = 0;                                                    // lane t owns digit t's T entries: the table is digit-major
+    for (uint32_t b = 0; b < T; ++b) sum += tab[t * T + b];
+    h[t] = sum;
+    __syncthreads();
+    for (uint32_t off = 1; off < IX_TPB; off <<= 1) {
+        const uint32_t v = t >= off ? h[t - off] : 0u;
+        __syncthreads();
+        h[t] += v;
+        __syncthreads();
+    }
+    uint32_t run = h[t] - sum;
+    for (uint32_t b = 0; b < T; ++b) { const uint32_t v = tab[t * T + b]; tab[t * T + b] = run; run += v; }
+    for (uint32_t b = 0; b < T; ++b) {
+        base[t] = tab[t * T + b];
+        for (uint32_t q = 0; q < IX_TPB / 64; ++q) cnt[q][t] = 0;
+        __syncthreads();
+        ix_scatter_tile<FIRST>(a, b, base, cnt);
+    }
+    __threadfence_block();
+    __syncthreads();
+}
+__global__ __launch_bounds__(IX_TPB) void k_ix_small(IxArgs a0, IxArgs a1, uint32_t passes) {
+    __shared__ uint32_t h[256], tab[256 * IX_SMALL_TILES], base[256], cnt[IX_TPB / 64][256];
+    ix_small_pass<true>(a0, h, tab, base, cnt);
+    if (passes > 1) ix_small_pass<false>(a1, h, tab, base, cnt);
+}
+// ix_start[b], b = 0 .. n_buckets: the first position whose sorted key is >= b -- a binary search per bucket (n_buckets x log2 n loads whatever the keys are; empty
+// buckets need no gap fill by a neighbour).  ix_start[n_buckets] is the number of indexed slots: every pair behind it carries IX_NONE
+__global__ __launch_bounds__(IX_TPB) void k_ix_bounds(const uint32_t* keys, uint32_t* start, uint64_t n, uint32_t n_buckets) {
+    const uint32_t b = blockIdx.x * IX_TPB + threadIdx.x;
+    if (b > n_buckets) return;
+    uint64_t lo = 0, hi = n;
+    while (lo < hi) { const uint64_t mid = (lo + hi) >> 1; if (keys[mid] < b) lo = mid + 1; else hi = mid; }
+    start[b] = (uint32_t)lo;
+}
+
 // THE INBOX (ggrs_hip_add_custom_system_effects; host_world.hpp ggrs_world::EffectInbox).  Right behind every request group that holds an AdvanceWorld, the sends the
 // group's launch left in the inbox -- linear arrays, one word per slot and effect column, the op's identity where nothing was sent -- are combined into the LIVE block
 // (tile-major) and the identities are put back.  One 64-slot unit per wave: a lane reads its inbox word (coalesced); a word that is not the identity is combined into

@@ -807,6 +807,23 @@ class World(WorldBase):
                            words=[(int(desc.words[k].comp), int(desc.words[k].word)) for k in range(desc.n_words)], buffer=out, max_rows=int(max_rows),
                            slots_off=int(lay.slots_off))
 
+    # ---- the peer index (include/ggrs_hip.h: ggrs_hip_register_peer_index / ggrs_hip_peer_index_read)
+    def register_peer_index(self, comp, word, n_buckets) -> None:
+        """A deterministic multimap key -> slots over word `word` of component `comp` (a 4-byte word), rebuilt at the start of every frame: systems added AFTER
+        this call iterate the entities that share a key with e.bucket(key) / b.count() / b.slot(i), members in ascending slot order.  Before seal; one per world."""
+        d = _ffi.PeerIndexDesc(int(comp), int(word), int(n_buckets), 0)
+        self._check(self._lib.ggrs_hip_register_peer_index(self._p, C.byref(d)))
+        self._peer_index_buckets = int(n_buckets)
+
+    def peer_index(self, state=LIVE):
+        """Inspection: the index of ring frame `state`, or of the live world (LIVE), built on the device and copied out as numpy arrays (start, slots):
+        bucket k holds slots[start[k]:start[k + 1]], ascending; start has n_buckets + 1 entries and slots start[-1]."""
+        nb = getattr(self, "_peer_index_buckets", 0)
+        if not nb: raise ValueError("this world has no peer index: call register_peer_index first")
+        start = np.zeros(nb + 1, dtype=np.uint32); slots = np.zeros(max(1, int(self.capacity)), dtype=np.uint32); n = C.c_uint64(0)
+        self._check(self._lib.ggrs_hip_peer_index_read(self._p, int(state), start.ctypes.data_as(C.POINTER(C.c_uint32)), slots.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(n)))
+        return start, slots[:int(n.value)].copy()
+
     # ---- scatter (include/ggrs_hip.h: ggrs_hip_scatter)
     def scatter_desc(self, op="write", words=(), comps=()) -> "_ffi.ScatterDesc":
         """The ggrs_scatter_desc of World.scatter's arguments: `words` are (comp, word) pairs (write, insert), `comps` the components a remove removes."""

@@ -423,6 +423,10 @@ struct HipBackend {
     int add_custom_system_commands(const ggrs_custom_system_desc* d, const ggrs_peer_binding* peers, uint32_t n_peers, const ggrs_effect_binding* effects, uint32_t n_effects, const ggrs_command_binding* cmds, uint32_t n_cmds) { return ggrs_hip_add_custom_system_commands(w, d, peers, n_peers, effects, n_effects, cmds, n_cmds); }
     int add_spawn_system(const ggrs_spawn_system_desc* d) { return ggrs_hip_add_spawn_system(w, d); }
     // device-resident rollback resources (include/ggrs_hip.h): thin forwards -- init_resource + rollback_resource_with_copy, checksum_resource_with_hash, the systems over them
+    // the peer index (include/ggrs_hip.h): systems added after this call iterate the entities that share a key -- e.bucket(key), b.count(), b.slot(i), ascending slots
+    int register_peer_index(uint32_t comp, uint32_t word, uint32_t n_buckets) { ggrs_peer_index_desc d{comp, word, n_buckets, 0u}; return ggrs_hip_register_peer_index(w, &d); }
+    // inspection: start receives n_buckets + 1 words, slots up to capacity words (the first *n_indexed are the members); frame: a ring frame or GGRS_DIFF_LIVE
+    int peer_index_read(int32_t frame, uint32_t* start, uint32_t* slots, uint64_t* n_indexed) { return ggrs_hip_peer_index_read(w, frame, start, slots, n_indexed); }
     int register_resource(const char* n, uint32_t wb, uint32_t nw, const void* init, uint32_t* id) { return ggrs_hip_register_resource(w, n, wb, nw, init, id); }
     int checksum_resource(uint32_t r, const uint32_t* idx, uint32_t n) { return ggrs_hip_checksum_resource(w, r, idx, n); }
     int add_resource_system(const ggrs_resource_system_desc* d) { return ggrs_hip_add_resource_system(w, d); }

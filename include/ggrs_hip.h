@@ -244,6 +244,38 @@ typedef struct { uint32_t comp; uint32_t word; } ggrs_peer_binding;   /* peer bi
 int ggrs_hip_add_custom_system_peers(ggrs_world* w, const ggrs_custom_system_desc* desc,
                                      const ggrs_peer_binding* peers, uint32_t n_peers);
 
+/* THE PEER INDEX: iterate the entities that share a key.  e.peer(slot) needs the slot; the index answers "who is on my tile / in my cell / in my squad / whose
+ * parent am I" -- in the reference the commonest second Query there is: iterate the others and filter by a cheap key (tests/hierarchy.rs, parent -> children, is
+ * the same shape).  It is a deterministic multimap key -> slots, rebuilt from the world at the START of every frame.  The key is word `word` of component `comp`:
+ * a 4-byte word of a rollback component without a Strategy.  Register it before the systems that use it (their text is compiled when they are added) and before
+ * seal; one index per world in this version.  The key column becomes a peer-bound column of the world (it counts against GGRS_PEER_MAX_COLUMNS) and its
+ * component's presence joins the visibility bit.  Inside ggrs_system, in a world with a registered index:
+ *
+ *     GgrsBucket b = e.bucket(key);                           key: ggrs_u32; key >= n_buckets gives an empty bucket
+ *     b.count()                                               ggrs_u32
+ *     b.slot(i)                                               ggrs_u64: the i-th member in ASCENDING slot order; i >= count() returns ~0ull (e.peer(~0ull) is !ok())
+ *
+ *   - The entity at slot s is a member of bucket k in a frame iff its visibility bit was set at the start of the frame (s < RollbackOrdered::len then, alive then,
+ *     every peer-bound component present then) and its key word then equalled k, with k < n_buckets.  Every other slot is in no bucket.
+ *   - So every member is ok() for e.peer; entities spawned in the frame are not members, entities despawned in the frame still are: the rules e.peer has.
+ *   - The member order is part of the contract: a float sum over the members gives the same bits on every replay, rank and launch geometry.
+ *
+ * A system "uses the index" when its source holds the token `bucket`.  For the peer rules above the key column is a peer binding of every such system.  Seal
+ * refuses (GGRS_E_INVALID, the message names the system and the column): a system that uses the index and has no peer binding; one registered after a writer of
+ * the key column or after another system that can despawn; one that binds the key column as its own; a key word that is not 4 bytes; a key component with a
+ * Strategy or outside rollback; an index no system uses; a world whose capacity exceeds 2^32 (the slots are 32-bit).  Registration refuses n_buckets == 0 or above
+ * GGRS_PEER_INDEX_MAX_BUCKETS, flags that are not 0, a second index, and a sealed world.  Everything peers refuse stays refused.
+ * How it runs: right behind the launch that fills the peer view, a stable radix sort of (key, slot) pairs over the view -- 4 small launches when n_buckets <= 255,
+ * else 7; 2 for a world of at most 2048 slots -- leaves ix_start[0 .. n_buckets] (exclusive prefix counts) and ix_slots (the members, bucket by bucket).  e.bucket is a bounds test and two 4-byte loads,
+ * b.slot(i) one.  The kernel boundary is the only synchronisation, and no position depends on the order in which atomics arrive.
+ * ggrs_hip_peer_index_read is for inspection: it builds the index of ring frame `frame` or of the live world (GGRS_DIFF_LIVE) and copies it out: start receives
+ * n_buckets + 1 words, slots up to `capacity` words of which the first *n_indexed (== start[n_buckets]) are the members; each of the three may be NULL.  It refuses
+ * while enqueued batches are uncollected (GGRS_E_INVALID), and a frame the ring does not hold (GGRS_E_NO_SNAPSHOT). */
+typedef struct { uint32_t comp; uint32_t word; uint32_t n_buckets; uint32_t flags; } ggrs_peer_index_desc;   /* the key = word `word` of component `comp`; flags: 0 */
+#define GGRS_PEER_INDEX_MAX_BUCKETS 65535u
+int ggrs_hip_register_peer_index(ggrs_world* w, const ggrs_peer_index_desc* d);
+int ggrs_hip_peer_index_read(ggrs_world* w, int32_t frame, uint32_t* start, uint32_t* slots, uint64_t* n_indexed);
+
 /* CROSS-ENTITY WRITES (effect bindings).  In the reference a system takes a second Query<&mut Health> and calls get_mut(target): a projectile damages
  * what it hits, a healer tops up a squad, a unit marks a tile.  A system registered through this entry point may SEND to another entity.
  * effects[j] = {comp, word, op} names effect binding j (at most GGRS_EFFECT_MAX_BINDINGS); peers / n_peers are as in
@@ -1135,7 +1167,7 @@ int ggrs_hip_host_timeline(ggrs_world* w, int enable, double* us_out, uint64_t* 
  * Introspection: which kernel serves this world's request lists right now and why, what kind of arena
  * it lives on, whether the run-time compiler (libhiprtc.so, dlopen'ed) is available.  `key=value` lines,
  * NUL-terminated; *needed = bytes incl. the NUL, min(cap, *needed) are copied.  Keys: sealed, arena,
- * arena_bytes, hiprtc, generated_kernel, generated_kernel_origin, request_group_kernel, checksum_fold, kernarg_bytes, group_caps, specialised_kernel, slots_covered, row_versions, peer_view (worlds with peer bindings), effect_inbox (worlds with effect bindings), device_resources (worlds with device resources), depth_parallel_roles, reduce_inbox (worlds with reduce bindings: stripes, words, applies so far), remote_inbox (worlds with remote bindings: components, applies so far), sum_partials (worlds with sum bindings: units, words, applies so far), value_inbox (worlds with value bindings: components, bindings, bytes allocated, applies so far), state_diff (once a state diff ran: calls, and the columns, bytes per slot and units of the last one), checksum_parts (once a parts call ran: calls, the hashing kernel and where its module came from, builds), query (once a query ran: calls, and the fetched words, masks and units of the last one).
+ * arena_bytes, hiprtc, generated_kernel, generated_kernel_origin, request_group_kernel, checksum_fold, kernarg_bytes, group_caps, specialised_kernel, slots_covered, row_versions, peer_view (worlds with peer bindings), peer_index (worlds with a peer index: buckets, key, builds and launches so far), effect_inbox (worlds with effect bindings), device_resources (worlds with device resources), depth_parallel_roles, reduce_inbox (worlds with reduce bindings: stripes, words, applies so far), remote_inbox (worlds with remote bindings: components, applies so far), sum_partials (worlds with sum bindings: units, words, applies so far), value_inbox (worlds with value bindings: components, bindings, bytes allocated, applies so far), state_diff (once a state diff ran: calls, and the columns, bytes per slot and units of the last one), checksum_parts (once a parts call ran: calls, the hashing kernel and where its module came from, builds), query (once a query ran: calls, and the fetched words, masks and units of the last one).
  * ------------------------------------------------------------------------------------------- */
 int ggrs_hip_world_kernel_info(ggrs_world* w, char* buf, uint64_t cap, uint64_t* needed);
 

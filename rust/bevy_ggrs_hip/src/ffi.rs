@@ -405,6 +405,17 @@ pub struct ggrs_scatter_report {
     pub first_bad_row: u64,
 }
 
+/// The peer index: the key is word `word` of component `comp` (a 4-byte word); `flags` is 0.
+pub const GGRS_PEER_INDEX_MAX_BUCKETS: u32 = 65535;
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct ggrs_peer_index_desc {
+    pub comp: u32,
+    pub word: u32,
+    pub n_buckets: u32,
+    pub flags: u32,
+}
+
 impl ggrs_request {
     pub const fn zeroed() -> Self {
         Self { kind: 0, frame: 0, dt_bits: 0, n_inputs: 0, inputs: core::ptr::null(), status: core::ptr::null(), spawn_count: 0, spawn_vx: core::ptr::null(), spawn_vy: core::ptr::null(),
@@ -495,6 +506,9 @@ unsafe extern "C" {
     pub fn ggrs_hip_query_layout(w: *mut ggrs_world, desc: *const ggrs_query_desc, max_rows: u64, out: *mut ggrs_query_layout) -> c_int;
     pub fn ggrs_hip_query(w: *mut ggrs_world, frame: i32, desc: *const ggrs_query_desc, out_dev: *mut c_void, max_rows: u64, report: *mut ggrs_query_report) -> c_int;
     pub fn ggrs_hip_query_block(w: *mut ggrs_world, block_dev: *const c_void, desc: *const ggrs_query_desc, out_dev: *mut c_void, max_rows: u64, report: *mut ggrs_query_report) -> c_int;
+    // ---- the peer index: a deterministic multimap key -> slots, rebuilt at the start of every frame; user systems iterate it with e.bucket(key)
+    pub fn ggrs_hip_register_peer_index(w: *mut ggrs_world, d: *const ggrs_peer_index_desc) -> c_int;
+    pub fn ggrs_hip_peer_index_read(w: *mut ggrs_world, frame: i32, start: *mut u32, slots: *mut u32, n_indexed: *mut u64) -> c_int;
     // ---- scatter: rows of (slot, words..) in device memory, in a query's output layout, applied to the live world (the inverse of the query)
     pub fn ggrs_hip_scatter(w: *mut ggrs_world, desc: *const ggrs_scatter_desc, in_dev: *const c_void, stride_rows: u64, n_rows: u64, report: *mut ggrs_scatter_report) -> c_int;
     // ---- speculative fan-out across GPUs (RCCL behind the C ABI; the host carries the 128-byte ncclUniqueId between ranks)

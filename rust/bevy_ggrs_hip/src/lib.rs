@@ -152,6 +152,21 @@ impl HipWorld {
         self.check(unsafe { ffi::ggrs_hip_query(self.raw, frame.unwrap_or(ffi::GGRS_DIFF_LIVE), desc, out_dev, max_rows, &mut rep) });
         rep
     }
+    /// A deterministic multimap key -> slots over word `word` of component `comp` (a 4-byte word), rebuilt at the start of every frame: systems added
+    /// after this call iterate the entities that share a key with `e.bucket(key)`, members in ascending slot order.  Before seal; one per world.
+    pub fn register_peer_index(&self, comp: u32, word: u32, n_buckets: u32) {
+        let d = ffi::ggrs_peer_index_desc { comp, word, n_buckets, flags: 0 };
+        self.check(unsafe { ffi::ggrs_hip_register_peer_index(self.raw, &d) });
+    }
+    /// Inspection: the index of ring frame `frame`, or of the live world (`None`): `(start, slots)` with bucket k = `slots[start[k] .. start[k + 1]]`.
+    pub fn peer_index(&self, frame: Option<i32>, n_buckets: u32, capacity: usize) -> (Vec<u32>, Vec<u32>) {
+        let mut start = vec![0u32; n_buckets as usize + 1];
+        let mut slots = vec![0u32; capacity.max(1)];
+        let mut n = 0u64;
+        self.check(unsafe { ffi::ggrs_hip_peer_index_read(self.raw, frame.unwrap_or(ffi::GGRS_DIFF_LIVE), start.as_mut_ptr(), slots.as_mut_ptr(), &mut n) });
+        slots.truncate(n as usize);
+        (start, slots)
+    }
     /// The desc of a scatter: `op` is `ffi::GGRS_SCATTER_*`, `words` holds the (component id, word) pairs the rows carry (WRITE / INSERT), `remove` the
     /// components a REMOVE removes.
     pub fn scatter_desc(op: u32, words: &[(u32, u32)], remove: &[u32]) -> ffi::ggrs_scatter_desc {
