@@ -14,4 +14,4 @@ from ._ffi import (COMP_NO_ROLLBACK, COMP_ROLLBACK, DESPAWN_IMMEDIATE, DESPAWN_R
                    SUM_MAX_BINDINGS, SUM_MAX_WORDS,
                    VALUE_MAX_BINDINGS, VALUE_MAX_WORDS, VALUE_MAX_WORLD_BINDINGS, PEER_INDEX_MAX_BUCKETS)
 from .requests import AdvanceFrame, LoadGameState, SaveGameState  # noqa: F401
-from .world import LIVE, ChecksumParts, DiffEntry, QueryResult, ScatterReport, StateDiff, World  # noqa: F401
+from .world import LIVE, ChecksumParts, DeltaResult, DiffEntry, QueryResult, ScatterReport, StateDiff, World  # noqa: F401

@@ -223,6 +223,19 @@ class ScatterReport(C.Structure):
     _fields_ = [("len", C.c_uint64), ("n_rows", C.c_uint64), ("n_applied", C.c_uint64), ("n_dead", C.c_uint64), ("n_absent", C.c_uint64), ("first_bad_row", C.c_uint64)]
 
 
+DELTA_CHANGED, DELTA_ADDED, DELTA_REMOVED, DELTA_DESPAWNED = 0, 1, 2, 3         # GGRS_DELTA_*
+DELTA_KINDS = {"changed": DELTA_CHANGED, "added": DELTA_ADDED, "removed": DELTA_REMOVED, "despawned": DELTA_DESPAWNED}
+DELTA_TRUST_VERSIONS = 1                                                        # GGRS_DELTA_TRUST_VERSIONS
+
+
+class DeltaDesc(C.Structure):
+    _fields_ = [("q", QueryDesc), ("changed_mask", C.c_uint64), ("kind", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class DeltaReport(C.Structure):
+    _fields_ = [("len_new", C.c_uint64), ("len_old", C.c_uint64), ("n_matched", C.c_uint64), ("n_rows", C.c_uint64), ("n_beyond_old_len", C.c_uint64)]
+
+
 class PeerIndexDesc(C.Structure):
     _fields_ = [("comp", C.c_uint32), ("word", C.c_uint32), ("n_buckets", C.c_uint32), ("flags", C.c_uint32)]
 
@@ -319,6 +332,8 @@ SIGNATURES = {
     "ggrs_hip_query": (C.c_int, [_P, C.c_int32, C.POINTER(QueryDesc), _P, C.c_uint64, C.POINTER(QueryReport)]),
     "ggrs_hip_query_block": (C.c_int, [_P, _P, C.POINTER(QueryDesc), _P, C.c_uint64, C.POINTER(QueryReport)]),
     "ggrs_hip_scatter": (C.c_int, [_P, C.POINTER(ScatterDesc), _P, C.c_uint64, C.c_uint64, C.POINTER(ScatterReport)]),
+    "ggrs_hip_delta_frames": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(DeltaDesc), _P, C.c_uint64, C.POINTER(DeltaReport)]),
+    "ggrs_hip_delta_block": (C.c_int, [_P, C.c_int32, _P, C.POINTER(DeltaDesc), _P, C.c_uint64, C.POINTER(DeltaReport)]),
     "ggrs_hip_fanout_unique_id": (C.c_int, [C.POINTER(C.c_uint8)]),
     "ggrs_hip_fanout_init": (C.c_int, [_P, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.POINTER(_P)]),
     "ggrs_hip_fanout_sync_confirmed": (C.c_int, [_P, C.c_int]),

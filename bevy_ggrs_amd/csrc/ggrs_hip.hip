@@ -1354,22 +1354,21 @@ void query_layout(const ggrs_world* w, const ggrs_query_desc* d, uint64_t max_ro
     if (d->flags & GGRS_QUERY_SLOTS) { out->slots_off = off; off = align_up(off + max_rows * 4u, 256); }
     out->total_bytes = off;
 }
-int query_run(ggrs_world* w, const DiffSide& S, const ggrs_query_desc* d, void* out_dev, uint64_t max_rows, ggrs_query_report* rep) {
-    uint64_t with = 0;
-    int rc = query_check(w, d, &with); if (rc) return rc;
-    if (!rep) return w->fail(GGRS_E_INVALID, "query without a report");
-    if (!out_dev && max_rows) return w->fail(GGRS_E_INVALID, "query with max_rows %llu and no output buffer", (unsigned long long)max_rows);
-    if (!S.live_form) {
-        for (uint32_t c = 0; c < w->comps.size(); ++c) if (((with | d->without_mask) >> c) & 1ull) {
-            if (w->comps[c].no_rollback) return w->fail(GGRS_E_INVALID, "a query of a snapshot names component %s, which is not registered for rollback: no snapshot holds it (GGRS_DIFF_LIVE is served)", w->comps[c].name.c_str());
-        }
-        for (uint32_t k = 0; k < d->n_words; ++k) {
-            const Comp& cc = w->comps[d->words[k].comp];
-            if (cc.s_n_words) return w->fail(GGRS_E_INVALID, "a query of a snapshot fetches words of component %s, which is under a Strategy: the slot holds Stored words (GGRS_DIFF_LIVE is served)", cc.name.c_str());
-        }
+// what a desc that passed query_check may not ask of a ring frame or a block (ring-slot form)
+int query_check_snapshot(ggrs_world* w, const ggrs_query_desc* d, uint64_t with) {
+    for (uint32_t c = 0; c < w->comps.size(); ++c) if (((with | d->without_mask) >> c) & 1ull) {
+        if (w->comps[c].no_rollback) return w->fail(GGRS_E_INVALID, "a query of a snapshot names component %s, which is not registered for rollback: no snapshot holds it (GGRS_DIFF_LIVE is served)", w->comps[c].name.c_str());
     }
+    for (uint32_t k = 0; k < d->n_words; ++k) {
+        const Comp& cc = w->comps[d->words[k].comp];
+        if (cc.s_n_words) return w->fail(GGRS_E_INVALID, "a query of a snapshot fetches words of component %s, which is under a Strategy: the slot holds Stored words (GGRS_DIFF_LIVE is served)", cc.name.c_str());
+    }
+    return GGRS_OK;
+}
+// the launches' arguments for a checked desc over state S (the scratch pointers are the caller's)
+void query_args(const ggrs_world* w, const DiffSide& S, const ggrs_query_desc* d, uint64_t with, void* out_dev, uint64_t max_rows, QueryArgs& a) {
     ggrs_query_layout lay; query_layout(w, d, max_rows, &lay);
-    QueryArgs a; memset(&a, 0, sizeof a);
+    memset(&a, 0, sizeof a);
     a.state = S.ptr; a.out = (uint8_t*)out_dev; a.len = std::min<uint64_t>(S.len, w->capacity); a.max_rows = max_rows; a.off_alive = w->off_alive; a.slots_off = lay.slots_off;
     for (uint32_t c = 0; c < w->comps.size() && c < 64u; ++c) {
         const bool wi = (with >> c) & 1ull, wo = (d->without_mask >> c) & 1ull;
@@ -1383,6 +1382,14 @@ int query_run(ggrs_world* w, const DiffSide& S, const ggrs_query_desc* d, void* 
         a.col_off[k] = w->col_off[col]; a.col_ts[k] = w->col_ts[col]; a.col_wb[k] = (uint8_t)w->col_wb[col]; a.out_off[k] = lay.col_off[k];
     }
     a.n_units = (uint32_t)((a.len + 63) / 64);
+}
+int query_run(ggrs_world* w, const DiffSide& S, const ggrs_query_desc* d, void* out_dev, uint64_t max_rows, ggrs_query_report* rep) {
+    uint64_t with = 0;
+    int rc = query_check(w, d, &with); if (rc) return rc;
+    if (!rep) return w->fail(GGRS_E_INVALID, "query without a report");
+    if (!out_dev && max_rows) return w->fail(GGRS_E_INVALID, "query with max_rows %llu and no output buffer", (unsigned long long)max_rows);
+    if (!S.live_form) { rc = query_check_snapshot(w, d, with); if (rc) return rc; }
+    QueryArgs a; query_args(w, S, d, with, out_dev, max_rows, a);
     memset(rep, 0, sizeof *rep);
     rep->len = S.len;
     // scratch: match word per unit + the sentinel | first row per unit + the total
@@ -1480,6 +1487,135 @@ int ggrs_hip_query_block(ggrs_world* w, const void* block_dev, const ggrs_query_
     if (h.len > w->capacity) return w->fail(GGRS_E_INVALID, "the block's header has len %llu > capacity %llu: not a block of this world", (unsigned long long)h.len, (unsigned long long)w->capacity);
     DiffSide S; S.ptr = (const uint8_t*)block_dev; S.len = h.len; S.ver = nullptr; S.res_cell = 0; S.live_form = false;
     return query_run(w, S, desc, out_dev, max_rows, report);
+}
+
+// ---- DELTA (include/ggrs_hip.h; the kernels: kernels.hpp k_delta_match_masks / k_delta_match_values, then k_diff_scan / k_query_emit as they are) --------------------
+// Nothing here is on the tick's path.  The two states are sides of a state diff (diff_ready / diff_side above); the scratch, the grid cap and the launch timer are
+// the query's.  The descriptor is judged before the device is looked at: which side is the live world is known from the frame numbers alone.
+namespace {
+const char* const DELTA_KINDS[] = {"CHANGED", "ADDED", "REMOVED", "DESPAWNED"};
+int delta_check(ggrs_world* w, const ggrs_delta_desc* d, bool new_live, bool old_live, bool old_block, const void* out_dev, uint64_t max_rows, const ggrs_delta_report* rep, uint64_t* with) {
+    if (!d) return w->fail(GGRS_E_INVALID, "delta without a desc");
+    int rc = query_check(w, &d->q, with); if (rc) return rc;
+    if (d->kind > GGRS_DELTA_DESPAWNED) return w->fail(GGRS_E_INVALID, "unknown delta kind %u", d->kind);
+    if (d->flags & ~GGRS_DELTA_TRUST_VERSIONS) return w->fail(GGRS_E_INVALID, "unknown delta flags 0x%x", d->flags);
+    const bool base_live = d->kind <= GGRS_DELTA_ADDED ? new_live : old_live;
+    if (!base_live) { rc = query_check_snapshot(w, &d->q, *with); if (rc) return rc; }
+    const uint64_t known = w->comps.size() >= 64 ? ~0ull : (1ull << w->comps.size()) - 1ull;
+    if (d->changed_mask & ~known) return w->fail(GGRS_E_INVALID, "changed_mask 0x%llx names a component the world does not have (%zu components)", (unsigned long long)d->changed_mask, w->comps.size());
+    if (d->kind == GGRS_DELTA_DESPAWNED && d->changed_mask) return w->fail(GGRS_E_INVALID, "changed_mask 0x%llx in a delta DESPAWNED: it asks about no component and must be 0", (unsigned long long)d->changed_mask);
+    if (d->kind != GGRS_DELTA_DESPAWNED && !d->changed_mask) return w->fail(GGRS_E_INVALID, "a delta %s with an empty changed_mask asks about no component", DELTA_KINDS[d->kind]);
+    uint32_t ncols = 0;
+    for (uint32_t c = 0; c < w->comps.size() && c < 64u; ++c) if ((d->changed_mask >> c) & 1ull) {
+        const Comp& cc = w->comps[c];
+        if (cc.no_rollback && !(new_live && old_live)) return w->fail(GGRS_E_INVALID, "changed_mask names component %s, which is not registered for rollback: no snapshot holds it", cc.name.c_str());
+        if (d->kind != GGRS_DELTA_CHANGED) continue;
+        if (cc.s_n_words && !cc.no_rollback && new_live != old_live)
+            return w->fail(GGRS_E_INVALID, "a delta CHANGED of component %s, which is under a Strategy, between the live world and a snapshot: live form and Stored form are not comparable", cc.name.c_str());
+        ncols += (cc.s_n_words && !cc.no_rollback && !new_live) ? cc.s_n_words : cc.n_words;
+    }
+    if (ncols > (uint32_t)DIFF_MAX_COLS) return w->fail(GGRS_E_INVALID, "a delta CHANGED compares at most %d columns, not %u", DIFF_MAX_COLS, ncols);
+    if ((d->flags & GGRS_DELTA_TRUST_VERSIONS) && old_block) return w->fail(GGRS_E_INVALID, "GGRS_DELTA_TRUST_VERSIONS with a foreign block: it carries no row versions");
+    if (!rep) return w->fail(GGRS_E_INVALID, "delta without a report");
+    if (!out_dev && max_rows) return w->fail(GGRS_E_INVALID, "delta with max_rows %llu and no output buffer", (unsigned long long)max_rows);
+    return GGRS_OK;
+}
+int delta_run(ggrs_world* w, const DiffSide& N, const DiffSide& O, const ggrs_delta_desc* d, uint64_t with, void* out_dev, uint64_t max_rows, ggrs_delta_report* rep) {
+    const bool new_based = d->kind <= GGRS_DELTA_ADDED;
+    const DiffSide& S = new_based ? N : O;                              // the base side: the filter and the fetched words are taken there
+    const DiffSide& X = new_based ? O : N;
+    QueryArgs qa; query_args(w, S, &d->q, with, out_dev, max_rows, qa);
+    DeltaArgs a; memset(&a, 0, sizeof a);
+    a.base = S.ptr; a.other = X.ptr; a.len_base = qa.len; a.len_other = std::min<uint64_t>(X.len, w->capacity); a.off_alive = w->off_alive;
+    a.n_units = qa.n_units; a.n_masks = qa.n_masks; a.without = qa.without; a.kind = d->kind;
+    for (uint32_t j = 0; j < qa.n_masks; ++j) a.off_mask[j] = qa.off_mask[j];
+    const bool trust = (d->flags & GGRS_DELTA_TRUST_VERSIONS) && N.ver && O.ver && w->knobs.row_versions;
+    uint32_t nq = 0;
+    for (uint32_t c = 0; c < w->comps.size() && c < 64u; ++c) if ((d->changed_mask >> c) & 1ull) {
+        const Comp& cc = w->comps[c];
+        const uint32_t j = a.n_comps++;
+        a.off_present[j] = w->off_present[c]; a.comp_col0[j] = (uint8_t)nq;
+        if (d->kind != GGRS_DELTA_CHANGED) continue;
+        const bool stored = cc.s_n_words && !cc.no_rollback && !N.live_form;    // ring-slot form holds Strategy::Stored (delta_check: both sides have one form)
+        const uint32_t base = stored ? cc.scol_base : cc.col_base, nw = stored ? cc.s_n_words : cc.n_words;
+        bool same = trust && !stored;                                  // the same version of every column and of the presence row on both sides: the same words
+        if (same) { const uint32_t p = ver_presence(w, c); same = (*N.ver)[p] != VER_NONE && (*N.ver)[p] == (*O.ver)[p]; }
+        for (uint32_t k = 0; k < nw && same; ++k) same = !w->col_ext[base + k] && (*N.ver)[base + k] != VER_NONE && (*N.ver)[base + k] == (*O.ver)[base + k];
+        if (same) continue;                                            // (its masks are still compared: added needs no column)
+        for (uint32_t k = 0; k < nw; ++k, ++nq) { a.col_off[nq] = w->col_off[base + k]; a.col_ts[nq] = w->col_ts[base + k]; a.col_wb[nq] = (uint8_t)w->col_wb[base + k]; }
+        a.comp_ncols[j] = (uint8_t)(nq - a.comp_col0[j]);
+    }
+    memset(rep, 0, sizeof *rep);
+    rep->len_new = N.len; rep->len_old = O.len;
+    // scratch: match word per unit + the sentinel | first row per unit + the total
+    const uint64_t words = (uint64_t)a.n_units + 1u, o_off = align_up(words * 8, ALIGN);
+    int rc = diff_scratch(w, o_off + align_up(words * 8, ALIGN)); if (rc) return rc;
+    a.unit_match = qa.unit_match = (uint64_t*)w->d_diff; qa.unit_off = (uint64_t*)(w->d_diff + o_off);
+    const uint32_t cap = w->query_max_wgs ? w->query_max_wgs : 4096u;
+    const uint32_t g_lane = std::max<uint32_t>(1, std::min<uint32_t>((uint32_t)((words + TPB - 1) / TPB), cap));
+    const uint32_t g_wave = std::max<uint32_t>(1, std::min<uint32_t>((uint32_t)((words + TPB / 64 - 1) / (TPB / 64)), cap));
+    const uint32_t g_emit = std::max<uint32_t>(1, std::min<uint32_t>((a.n_units + TPB / 64 - 1) / (TPB / 64), cap));
+    const bool emit = max_rows && qa.n_units && (qa.n_words || qa.slots);
+    if (w->query_timed) { for (hipEvent_t& e : w->query_ev) if (!e) HIPCHK(w, hipEventCreate(&e)); HIPCHK(w, hipEventRecord(w->query_ev[0], w->stream)); }
+    if (d->kind == GGRS_DELTA_CHANGED) hipLaunchKernelGGL(k_delta_match_values, dim3(g_wave), dim3(TPB), 0, w->stream, a);
+    else hipLaunchKernelGGL(k_delta_match_masks, dim3(g_lane), dim3(TPB), 0, w->stream, a);
+    HIPCHK(w, hipGetLastError());
+    if (w->query_timed) HIPCHK(w, hipEventRecord(w->query_ev[1], w->stream));
+    hipLaunchKernelGGL(k_diff_scan, dim3(1), dim3(TPB), 0, w->stream, (const uint64_t*)qa.unit_match, qa.unit_off, (uint32_t)words);
+    HIPCHK(w, hipGetLastError());
+    if (w->query_timed) HIPCHK(w, hipEventRecord(w->query_ev[2], w->stream));
+    if (emit) {
+        hipLaunchKernelGGL(k_query_emit, dim3(g_emit), dim3(TPB), 0, w->stream, qa);
+        HIPCHK(w, hipGetLastError());
+    }
+    if (w->query_timed) HIPCHK(w, hipEventRecord(w->query_ev[3], w->stream));
+    // the count: the scan's word behind the last unit.  The rows beyond old's len (NEW-based kinds, new longer than old): all rows less those below it, which the
+    // scan word and the match word of unit len_old >> 6 give -- no counter, no atomic
+    uint64_t* const h = (uint64_t*)w->h_diff;
+    const uint64_t cut = a.len_other >> 6;
+    const bool tail = new_based && a.len_other < a.len_base;           // (then cut < n_units)
+    HIPCHK(w, hipMemcpyAsync(h, qa.unit_off + a.n_units, 8, hipMemcpyDeviceToHost, w->stream));
+    if (tail) {
+        HIPCHK(w, hipMemcpyAsync(h + 1, qa.unit_off + cut, 8, hipMemcpyDeviceToHost, w->stream));
+        HIPCHK(w, hipMemcpyAsync(h + 2, qa.unit_match + cut, 8, hipMemcpyDeviceToHost, w->stream));
+    }
+    HIPCHK(w, hipStreamSynchronize(w->stream));
+    if (w->query_timed) for (int k = 0; k < 3; ++k) { float ms = 0; HIPCHK(w, hipEventElapsedTime(&ms, w->query_ev[k], w->query_ev[k + 1])); w->query_us[k] = (double)ms * 1e3; }
+    rep->n_matched = h[0];
+    rep->n_rows = std::min<uint64_t>(rep->n_matched, max_rows);
+    if (tail) rep->n_beyond_old_len = rep->n_matched - (h[1] + (uint64_t)__builtin_popcountll(h[2] & ((1ull << (a.len_other & 63u)) - 1ull)));
+    ++w->delta_calls; w->delta_last_kind = d->kind; w->delta_last_cols = nq; w->delta_last_comps = a.n_comps; w->delta_last_units = a.n_units;
+    return GGRS_OK;
+}
+}  // namespace
+int ggrs_hip_delta_frames(ggrs_world* w, int32_t frame_new, int32_t frame_old, const ggrs_delta_desc* desc, void* out_dev, uint64_t max_rows, ggrs_delta_report* report) {
+    if (!w) return GGRS_E_INVALID;
+    uint64_t with = 0;
+    int rc = delta_check(w, desc, frame_new == GGRS_DIFF_LIVE, frame_old == GGRS_DIFF_LIVE, false, out_dev, max_rows, report, &with); if (rc) return rc;
+    if (w->layout_only) return w->fail(GGRS_E_NO_DEVICE, "a layout-only world has no states to take a delta of");
+    DeviceGuard dg(w);
+    rc = diff_ready(w); if (rc) return rc;
+    DiffSide N, O;
+    rc = diff_side(w, frame_new, &N); if (rc) return rc;
+    rc = diff_side(w, frame_old, &O); if (rc) return rc;
+    return delta_run(w, N, O, desc, with, out_dev, max_rows, report);
+}
+int ggrs_hip_delta_block(ggrs_world* w, int32_t frame_new, const void* block_old_dev, const ggrs_delta_desc* desc, void* out_dev, uint64_t max_rows, ggrs_delta_report* report) {
+    if (!w) return GGRS_E_INVALID;
+    if (!block_old_dev) return w->fail(GGRS_E_INVALID, "delta_block without a block");
+    uint64_t with = 0;
+    int rc = delta_check(w, desc, frame_new == GGRS_DIFF_LIVE, false, true, out_dev, max_rows, report, &with); if (rc) return rc;
+    if (w->layout_only) return w->fail(GGRS_E_NO_DEVICE, "a layout-only world has no states to take a delta of");
+    DeviceGuard dg(w);
+    rc = diff_ready(w); if (rc) return rc;
+    DiffSide N, O;
+    rc = diff_side(w, frame_new, &N); if (rc) return rc;
+    Header h;
+    HIPCHK(w, hipMemcpyAsync(&h, block_old_dev, sizeof h, hipMemcpyDeviceToHost, w->stream));
+    HIPCHK(w, hipStreamSynchronize(w->stream));
+    if (h.len > w->capacity) return w->fail(GGRS_E_INVALID, "the block's header has len %llu > capacity %llu: not a block of this world", (unsigned long long)h.len, (unsigned long long)w->capacity);
+    O.ptr = (const uint8_t*)block_old_dev; O.len = h.len; O.ver = nullptr; O.res_cell = 0; O.live_form = false;
+    return delta_run(w, N, O, desc, with, out_dev, max_rows, report);
 }
 
 // ---- SCATTER (include/ggrs_hip.h; the kernels: kernels.hpp k_scatter_check / k_scatter_apply) ------------------------------------------------------------------------
@@ -1682,6 +1818,8 @@ int ggrs_hip_world_kernel_info(ggrs_world* w, char* buf, uint64_t cap, uint64_t*
                                          " bytes per slot and side) and " + std::to_string(w->plan.n_masks) + " masks over " + std::to_string(w->diff_last_units) + " units of 64 slots");
     if (w->query_calls) add("query", std::to_string(w->query_calls) + " calls; the last one fetched " + std::to_string(w->query_last_words) + " words and read " + std::to_string(w->query_last_masks) +
                                      " masks over " + std::to_string(w->query_last_units) + " units of 64 slots");
+    if (w->delta_calls) add("delta", std::to_string(w->delta_calls) + " calls; the last one was kind " + std::to_string(w->delta_last_kind) + " over " + std::to_string(w->delta_last_comps) + " components, compared " +
+                                     std::to_string(w->delta_last_cols) + " columns over " + std::to_string(w->delta_last_units) + " units of 64 slots");
     if (w->scatter_calls) add("scatter", std::to_string(w->scatter_calls) + " calls; the last one was op " + std::to_string(w->scatter_last_op) + " over " + std::to_string(w->scatter_last_rows) + " rows of " +
                                          std::to_string(w->scatter_last_words) + " words");
     if (w->cparts_calls) add("checksum_parts", std::to_string(w->cparts_calls) + " calls; hashing kernel " + (w->custom_hashers ? "ggrs_jit_parts (generated: the world has a user-written hasher; module from " + w->cparts_origin + ", " +

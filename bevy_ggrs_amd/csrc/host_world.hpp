@@ -454,6 +454,8 @@ struct ggrs_world {
     // ---- scatter (ggrs_hip_scatter): its record lives in the same scratch; query_max_wgs caps its two launches too
     uint64_t scatter_calls = 0, scatter_last_rows = 0; uint32_t scatter_last_op = 0, scatter_last_words = 0;
     bool scatter_timed = false; hipEvent_t scatter_ev[3] = {nullptr, nullptr, nullptr}; double scatter_us[2] = {0, 0};           // ggrs_dbg_scatter_launch_us: check, apply of the last call
+    // ---- delta (ggrs_hip_delta_frames / ggrs_hip_delta_block): the query's scratch, grid cap and launch timer (its match, scan, emit are what ggrs_dbg_query_launch_us reports)
+    uint64_t delta_calls = 0; uint32_t delta_last_kind = 0, delta_last_cols = 0, delta_last_comps = 0, delta_last_units = 0;
 
     // ---- profiling
     bool nt_copy = false;              // non-temporal loads/stores in k_copy_state (A/B knob)

@@ -1613,4 +1613,94 @@ __global__ __launch_bounds__(TPB) void k_scatter_apply(ScatterArgs a) {
     if (threadIdx.x < 2u && s_cnt[threadIdx.x]) atomicAdd(a.rec + SCAT_DEAD + threadIdx.x, s_cnt[threadIdx.x]);
 }
 
+// ------------------------------------------------------------------ DELTA (ggrs_hip_delta_frames / ggrs_hip_delta_block)
+// Query<.., Changed<C>> / Added<C> / RemovedComponents<C> / despawns between TWO packed blocks: the query's stream compaction with a predicate that looks at both
+// sides.  The BASE side is the one rows are fetched from and the filter is judged on (NEW for CHANGED and ADDED, OLD for REMOVED and DESPAWNED); the OTHER side only
+// says what was there.  A_x(s): s below the side's len and alive; P_x(c, s): A_x(s) and component c present.  With F the query's match word on the base side:
+//   ADDED / REMOVED   F & OR_c (P_base(c) & ~P_other(c))          DESPAWNED   F & ~A_other          CHANGED   F & OR_c (P_base(c) & (~P_other(c) | a word of c differs))
+// One match launch, then k_diff_scan and k_query_emit as they are, over the base side (no compare-and-swap, no wait between workgroups, no atomic at all):
+//   k_delta_match_masks   ADDED, REMOVED, DESPAWNED need mask words only: one 64-slot unit per LANE as in k_query_match, every mask of both sides one coalesced load.
+//   k_delta_match_values  CHANGED: one unit per wave-iteration, one slot per lane.  The mask words are wave-uniform loads and F comes first; per component
+//                         added = P_new & ~P_old joins the match word without a column being read, and the component's columns are read only while
+//                         common & F & ~match has a bit left (tile-major through col_at, DIFF_BATCH columns of both sides in flight before the first __ballot).
+//                         A unit whose match word has reached F reads nothing more.  Lane 0 stores the word.
+// Both store a zero sentinel behind the last unit: the scan's word there is the number of matches.
+struct DeltaArgs {
+    const uint8_t* base; const uint8_t* other;
+    uint64_t len_base, len_other, off_alive;
+    uint64_t off_mask[MAX_COMPS];                          // presence masks of q's filtered components on the base side (bit j of without says which way)
+    uint64_t off_present[MAX_COMPS];                       // per component j of changed_mask
+    uint64_t col_off[DIFF_MAX_COLS];                       // per compared column (grouped by component)
+    uint64_t* unit_match;
+    uint32_t col_ts[DIFF_MAX_COLS];
+    uint32_t n_units, n_masks, without, n_comps, kind;
+    uint8_t comp_col0[MAX_COMPS], comp_ncols[MAX_COMPS];   // a component's first compared column and how many (0: the host knows its words are equal)
+    uint8_t col_wb[DIFF_MAX_COLS];
+};
+__global__ __launch_bounds__(TPB) void k_delta_match_masks(DeltaArgs a) {
+    for (uint32_t u = blockIdx.x * TPB + threadIdx.x; u <= a.n_units; u += gridDim.x * TPB) {
+        uint64_t m = 0;
+        if (u < a.n_units) {                                                     // (u < n_units <= the padded capacity / 64: inside every mask of both blocks)
+            const uint64_t lo = (uint64_t)u * 64u, wo = (uint64_t)u * 8u;
+            const uint64_t ab = *reinterpret_cast<const uint64_t*>(a.base + a.off_alive + wo) & diff_len_mask(a.len_base, lo);
+            const uint64_t ao = *reinterpret_cast<const uint64_t*>(a.other + a.off_alive + wo) & diff_len_mask(a.len_other, lo);
+            uint64_t f = ab;
+            for (uint32_t j = 0; j < a.n_masks; ++j) {
+                const uint64_t p = *reinterpret_cast<const uint64_t*>(a.base + a.off_mask[j] + wo);
+                f &= ((a.without >> j) & 1u) ? ~p : p;
+            }
+            if (a.kind == GGRS_DELTA_DESPAWNED) m = f & ~ao;
+            else {
+                uint64_t acc = 0;
+                for (uint32_t j = 0; j < a.n_comps; ++j) {
+                    const uint64_t pb = *reinterpret_cast<const uint64_t*>(a.base + a.off_present[j] + wo);
+                    const uint64_t po = *reinterpret_cast<const uint64_t*>(a.other + a.off_present[j] + wo) & ao;
+                    acc |= pb & ~po;
+                }
+                m = f & acc;                                                     // (f is inside the base's alive word: pb needs no cut of its own)
+            }
+        }
+        a.unit_match[u] = m;
+    }
+}
+__global__ __launch_bounds__(TPB) void k_delta_match_values(DeltaArgs a) {
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
+    for (uint32_t u = blockIdx.x * (TPB / 64) + wave; u <= a.n_units; u += gridDim.x * (TPB / 64)) {
+        uint64_t match = 0;
+        if (u < a.n_units) {                                                     // (wave-uniform, as everything below that decides a branch)
+            const uint64_t lo = (uint64_t)u * 64u, e = lo + lane, wo = (uint64_t)u * 8u;
+            const uint64_t ab = *reinterpret_cast<const uint64_t*>(a.base + a.off_alive + wo) & diff_len_mask(a.len_base, lo);
+            const uint64_t ao = *reinterpret_cast<const uint64_t*>(a.other + a.off_alive + wo) & diff_len_mask(a.len_other, lo);
+            uint64_t f = ab;
+            for (uint32_t j = 0; j < a.n_masks; ++j) {
+                const uint64_t p = *reinterpret_cast<const uint64_t*>(a.base + a.off_mask[j] + wo);
+                f &= ((a.without >> j) & 1u) ? ~p : p;
+            }
+            for (uint32_t j = 0; j < a.n_comps && match != f; ++j) {
+                const uint64_t pb = *reinterpret_cast<const uint64_t*>(a.base + a.off_present[j] + wo) & f;
+                const uint64_t po = *reinterpret_cast<const uint64_t*>(a.other + a.off_present[j] + wo) & ao;
+                const uint64_t added = pb & ~po, common = pb & po;
+                match |= added;
+                const uint32_t q1 = (uint32_t)a.comp_col0[j] + a.comp_ncols[j];
+                for (uint32_t q0 = a.comp_col0[j]; q0 < q1 && (common & ~match); q0 += DIFF_BATCH) {   // nobody left to decide -> the columns are not read
+                    uint64_t va[DIFF_BATCH], vb[DIFF_BATCH];
+#pragma unroll
+                    for (uint32_t i = 0; i < DIFF_BATCH; ++i) {
+                        va[i] = 0; vb[i] = 0;
+                        if (q0 + i < q1) {
+                            const uint32_t wb = a.col_wb[q0 + i];
+                            const uint64_t off = col_at(a.col_off[q0 + i], a.col_ts[q0 + i], wb, e);   // e < the padded capacity: inside the column for every lane
+                            va[i] = diff_load(a.base + off, wb); vb[i] = diff_load(a.other + off, wb);
+                        }
+                    }
+#pragma unroll
+                    for (uint32_t i = 0; i < DIFF_BATCH; ++i) match |= __ballot(va[i] != vb[i]) & common;   // (a column beyond the component's last: 0 != 0 for nobody)
+                }
+            }
+        }
+        if (lane == 0) a.unit_match[u] = match;
+    }
+}
+
 }  // namespace ggrs

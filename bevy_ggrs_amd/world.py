@@ -130,6 +130,17 @@ class QueryResult:
 
 
 @dataclass
+class DeltaResult(QueryResult):
+    """World.delta: the rows that differ between two world states, as a QueryResult over the base side (new for "changed" / "added", old for "removed" /
+    "despawned"; `len` is that side's).  n_beyond_old_len: matched rows whose slot is at or beyond old's len -- what a consumer must spawn before it can insert
+    them (0 for the old-based kinds).  World.scatter takes it as `rows` unchanged."""
+    len_new: int = 0
+    len_old: int = 0
+    n_beyond_old_len: int = 0
+    kind: str = "changed"
+
+
+@dataclass
 class ScatterReport:
     """World.scatter: what became of the rows (ggrs_scatter_report).  n_applied + n_dead + n_absent == n_rows: a row is applied iff its entity is alive and, for
     op="write", has every named component; n_dead rows named a slot that is not alive, n_absent rows an alive slot lacking a named component.  first_bad_row is
@@ -806,6 +817,53 @@ class World(WorldBase):
         return QueryResult(len=int(rep.len), n_matched=int(rep.n_matched), n_rows=n, slots=slot_col, columns=columns,
                            words=[(int(desc.words[k].comp), int(desc.words[k].word)) for k in range(desc.n_words)], buffer=out, max_rows=int(max_rows),
                            slots_off=int(lay.slots_off))
+
+    # ---- delta (include/ggrs_hip.h: ggrs_hip_delta_frames / ggrs_hip_delta_block)
+    def delta_desc(self, fetch=(), *, kind="changed", changed=(), with_=(), without=(), slots=True, trust_versions=False) -> "_ffi.DeltaDesc":
+        """The ggrs_delta_desc of World.delta's arguments."""
+        if kind not in _ffi.DELTA_KINDS: raise ValueError(f"kind is one of {sorted(_ffi.DELTA_KINDS)}, not {kind!r}")
+        d = _ffi.DeltaDesc()
+        d.q = self.query_desc(fetch, with_, without, slots)
+        d.changed_mask = sum(1 << int(c) for c in set(changed)); d.kind = _ffi.DELTA_KINDS[kind]; d.flags = _ffi.DELTA_TRUST_VERSIONS if trust_versions else 0
+        return d
+
+    def delta(self, new, old, fetch=(), *, kind="changed", changed=(), with_=(), without=(), slots=True, max_rows: Optional[int] = None, out=None,
+              trust_versions: bool = False) -> DeltaResult:
+        """The rows that differ between two world states, gathered like World.query: Query<fetch, (Changed<changed ..>, With<..>, Without<..>)> for
+        kind="changed" (Bevy's Changed includes Added), Added<..> for "added", RemovedComponents<..> for "removed" (a despawn removes too; the fetched words
+        are the entity's last values), the entities alive in old and not in new for "despawned" (changed must be empty).  `new`: a ring frame or LIVE; `old`:
+        a ring frame, LIVE, or a block tensor from snapshot_copy.  Filter and fetched words are taken on new ("changed", "added") or old ("removed",
+        "despawned").  Words are compared as bits; dead slots and absent components hold no state.  max_rows=None: the world's capacity.  trust_versions skips
+        the words of components whose row versions agree (not with a tensor).  Returns a DeltaResult of zero-copy views; World.scatter takes it as rows."""
+        import torch
+        desc = self.delta_desc(fetch, kind=kind, changed=changed, with_=with_, without=without, slots=slots, trust_versions=trust_versions)
+        if max_rows is None: max_rows = int(self.capacity)
+        lay = self.query_layout(desc.q, max_rows)
+        need = int(lay.total_bytes)
+        if out is None:
+            out = torch.empty(max(need, 1), dtype=torch.uint8, device=f"cuda:{self.device}")
+        elif out.dtype != torch.uint8 or out.numel() < need or not out.is_cuda or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous torch.uint8 device tensor of at least {need} bytes")
+        torch.cuda.current_stream(out.device).synchronize()       # (the launches run on the world's stream)
+        rep = _ffi.DeltaReport()
+        if hasattr(old, "data_ptr"):
+            if old.dtype != torch.uint8 or old.numel() != self.state_bytes() or not old.is_cuda or not old.is_contiguous():
+                raise ValueError(f"a block is a contiguous torch.uint8 device tensor of {self.state_bytes()} bytes")
+            torch.cuda.current_stream(old.device).synchronize()
+            self._check(self._lib.ggrs_hip_delta_block(self._p, int(new), old.data_ptr(), C.byref(desc), out.data_ptr(), max_rows, C.byref(rep)))
+        else:
+            self._check(self._lib.ggrs_hip_delta_frames(self._p, int(new), int(old), C.byref(desc), out.data_ptr(), max_rows, C.byref(rep)))
+        n = int(rep.n_rows)
+        dt = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
+        columns = []
+        for k in range(desc.q.n_words):
+            wb, off = int(lay.word_bytes[k]), int(lay.col_off[k])
+            columns.append(out[off:off + n * wb].view(dt[wb]))
+        slot_col = out[int(lay.slots_off):int(lay.slots_off) + n * 4].view(torch.int32) if slots else None
+        new_based = kind in ("changed", "added")
+        return DeltaResult(len=int(rep.len_new if new_based else rep.len_old), n_matched=int(rep.n_matched), n_rows=n, slots=slot_col, columns=columns,
+                           words=[(int(desc.q.words[k].comp), int(desc.q.words[k].word)) for k in range(desc.q.n_words)], buffer=out, max_rows=int(max_rows),
+                           slots_off=int(lay.slots_off), len_new=int(rep.len_new), len_old=int(rep.len_old), n_beyond_old_len=int(rep.n_beyond_old_len), kind=kind)
 
     # ---- the peer index (include/ggrs_hip.h: ggrs_hip_register_peer_index / ggrs_hip_peer_index_read)
     def register_peer_index(self, comp, word, n_buckets) -> None:

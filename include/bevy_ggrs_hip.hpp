@@ -522,6 +522,16 @@ struct HipBackend {
         return d;
     }
     int scatter(const ggrs_scatter_desc& desc, const void* in_dev, uint64_t stride_rows, uint64_t n_rows, ggrs_scatter_report* report) { return ggrs_hip_scatter(w, &desc, in_dev, stride_rows, n_rows, report); }
+    // delta (include/ggrs_hip.h): the rows that differ between two states -- Query<&C, Changed<C>>, Added<C>, RemovedComponents<C> and despawns when the rollback world
+    // is mirrored into Bevy's own ECS.  kind is GGRS_DELTA_*; `q` is the filter and the fetched words, judged on the new state (CHANGED, ADDED) or the old one (REMOVED,
+    // DESPAWNED); out_dev is laid out as query_layout(desc.q, max_rows) says and can go to scatter unchanged
+    static ggrs_delta_desc delta_desc(uint32_t kind, uint64_t changed_mask, const ggrs_query_desc& q, bool trust_versions = false) {
+        ggrs_delta_desc d{};
+        d.q = q; d.changed_mask = changed_mask; d.kind = kind; d.flags = trust_versions ? GGRS_DELTA_TRUST_VERSIONS : 0u;
+        return d;
+    }
+    int delta_frames(int32_t frame_new, int32_t frame_old, const ggrs_delta_desc& desc, void* out_dev, uint64_t max_rows, ggrs_delta_report* report) { return ggrs_hip_delta_frames(w, frame_new, frame_old, &desc, out_dev, max_rows, report); }
+    int delta_block(int32_t frame_new, const void* block_old_dev, const ggrs_delta_desc& desc, void* out_dev, uint64_t max_rows, ggrs_delta_report* report) { return ggrs_hip_delta_block(w, frame_new, block_old_dev, &desc, out_dev, max_rows, report); }
 };
 
 // ---------------------------------------------------------------- speculative fan-out (no reference analogue: SURVEY.md 8e)

@@ -1139,6 +1139,47 @@ typedef struct { uint64_t len; uint64_t n_rows; uint64_t n_applied; uint64_t n_d
 int ggrs_hip_scatter(ggrs_world* w, const ggrs_scatter_desc* desc, const void* in_dev, uint64_t stride_rows, uint64_t n_rows, ggrs_scatter_report* report);
 
 /* -------------------------------------------------------------------------------------------
+ * DELTA: gather the rows that changed between TWO world states -- what a bevy_ggrs game that mirrors the rollback world into Bevy's own ECS asks every rendered
+ * frame with Query<&C, Changed<C>>, Added<C>, RemovedComponents<C> and despawn events; also a spectator or save-game delta, and the rows that bring a second
+ * world from one state to the other with ggrs_hip_scatter.  Both states are complete packed blocks; three small launches (match, scan, emit) beside the tick.
+ *
+ *   ggrs_hip_delta_frames   NEW = frame_new, OLD = frame_old; either may be GGRS_DIFF_LIVE.
+ *   ggrs_hip_delta_block    NEW = frame_new, OLD = a block in ring-slot form somewhere in device memory (ggrs_hip_snapshot_copy, GGRS_ADOPT_BROADCAST).
+ *
+ * out_dev has exactly the layout ggrs_hip_query_layout(w, &desc->q, max_rows, ..) gives: a delta result is a valid scatter input, as a query result is.
+ * Write A_x(s) for "s < len_x and the alive bit is set" on side x, P_x(c, s) for "A_x(s) and component c is present".  Bits are compared: -0.0 != 0.0, NaN
+ * payloads count; a slot dead on both sides is never a row whatever bytes lie under it; a component absent on both sides is never a difference.
+ *   CHANGED    base NEW: s matches desc->q on NEW exactly as ggrs_hip_query would, and some c of changed_mask has P_new(c, s) and (not P_old(c, s), or a word of c
+ *              differs).  Bevy's Changed includes Added.  A component of changed_mask is not an implied With.
+ *   ADDED      base NEW: as CHANGED without the word compare.
+ *   REMOVED    base OLD: s matches desc->q on OLD, and some c of changed_mask has P_old(c, s) and not P_new(c, s) -- a despawn removes too.  The fetched words are
+ *              the entity's last values.
+ *   DESPAWNED  base OLD: s matches desc->q on OLD and not A_new(s).  changed_mask must be 0.
+ * The filter and the fetched words are taken on the base side.  Rows ascend by slot; n_matched is exact whatever max_rows is; n_rows = min(n_matched, max_rows);
+ * n_beyond_old_len counts the matched rows with slot >= len_old -- the tail a consumer must ggrs_hip_spawn before it can INSERT -- and is 0 for the OLD-based
+ * kinds.  Nothing is written at or beyond row n_rows, nor between columns.  The result is byte-identical for every launch geometry and from run to run.
+ * A component under a Strategy that is named in changed_mask is compared in its Stored words when both sides are in ring-slot form, in its live words when both
+ * are the live world; CHANGED with one side GGRS_DIFF_LIVE and the other not is refused for it (the forms are not comparable).  Fetching it is refused as the
+ * query refuses it.  GGRS_DELTA_TRUST_VERSIONS is handled on the host: the words of a component of changed_mask whose columns and presence row carry the same
+ * row versions on both sides are not compared (its masks still are); refused with a block, ignored with the row_versions knob off, as for the diff.
+ * Both calls bring deferred Saves and a lazily skipped live block up to date first; the len of a world with device-decided spawns is read from the slot header.
+ * Errors, GGRS_E_INVALID with a message, issued before the device is looked at (a GGRS_WORLD_LAYOUT_ONLY world returns them for a bad descriptor and
+ * GGRS_E_NO_DEVICE for a good one): everything the query refuses for desc->q on the base side; an unknown kind or unknown flags; changed_mask naming a component
+ * the world does not have, or a GGRS_COMP_NO_ROLLBACK component against a ring frame or a block; changed_mask == 0 for CHANGED, ADDED, REMOVED and != 0 for
+ * DESPAWNED; more than 64 compared columns; the Strategy case above; no report; out_dev == NULL with max_rows > 0.  Also GGRS_E_INVALID while enqueued batches
+ * are uncollected; GGRS_E_NO_SNAPSHOT for a frame the ring does not hold.
+ * Out of scope: device resources (ggrs_hip_resource_read), a "which word changed" column, an asynchronous form. */
+#define GGRS_DELTA_CHANGED    0u   /* Query<.., Or<(Changed<C>..)>>  (Bevy's Changed includes Added) */
+#define GGRS_DELTA_ADDED      1u   /* Query<.., Or<(Added<C>..)>>                                    */
+#define GGRS_DELTA_REMOVED    2u   /* RemovedComponents<C> (a despawn removes too)                   */
+#define GGRS_DELTA_DESPAWNED  3u   /* alive in old, not alive in new                                 */
+#define GGRS_DELTA_TRUST_VERSIONS 1u  /* flags; same meaning and caveat as GGRS_DIFF_TRUST_VERSIONS  */
+typedef struct { ggrs_query_desc q; uint64_t changed_mask; uint32_t kind; uint32_t flags; } ggrs_delta_desc;
+typedef struct { uint64_t len_new; uint64_t len_old; uint64_t n_matched; uint64_t n_rows; uint64_t n_beyond_old_len; } ggrs_delta_report;
+int ggrs_hip_delta_frames(ggrs_world* w, int32_t frame_new, int32_t frame_old, const ggrs_delta_desc* desc, void* out_dev, uint64_t max_rows, ggrs_delta_report* report);
+int ggrs_hip_delta_block(ggrs_world* w, int32_t frame_new, const void* block_old_dev, const ggrs_delta_desc* desc, void* out_dev, uint64_t max_rows, ggrs_delta_report* report);
+
+/* -------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): per-kernel-class HIP-event timing on the world's stream.
  * ------------------------------------------------------------------------------------------- */
 #define GGRS_KERNEL_SAVE     0u
@@ -1167,7 +1208,7 @@ int ggrs_hip_host_timeline(ggrs_world* w, int enable, double* us_out, uint64_t* 
  * Introspection: which kernel serves this world's request lists right now and why, what kind of arena
  * it lives on, whether the run-time compiler (libhiprtc.so, dlopen'ed) is available.  `key=value` lines,
  * NUL-terminated; *needed = bytes incl. the NUL, min(cap, *needed) are copied.  Keys: sealed, arena,
- * arena_bytes, hiprtc, generated_kernel, generated_kernel_origin, request_group_kernel, checksum_fold, kernarg_bytes, group_caps, specialised_kernel, slots_covered, row_versions, peer_view (worlds with peer bindings), peer_index (worlds with a peer index: buckets, key, builds and launches so far), effect_inbox (worlds with effect bindings), device_resources (worlds with device resources), depth_parallel_roles, reduce_inbox (worlds with reduce bindings: stripes, words, applies so far), remote_inbox (worlds with remote bindings: components, applies so far), sum_partials (worlds with sum bindings: units, words, applies so far), value_inbox (worlds with value bindings: components, bindings, bytes allocated, applies so far), state_diff (once a state diff ran: calls, and the columns, bytes per slot and units of the last one), checksum_parts (once a parts call ran: calls, the hashing kernel and where its module came from, builds), query (once a query ran: calls, and the fetched words, masks and units of the last one).
+ * arena_bytes, hiprtc, generated_kernel, generated_kernel_origin, request_group_kernel, checksum_fold, kernarg_bytes, group_caps, specialised_kernel, slots_covered, row_versions, peer_view (worlds with peer bindings), peer_index (worlds with a peer index: buckets, key, builds and launches so far), effect_inbox (worlds with effect bindings), device_resources (worlds with device resources), depth_parallel_roles, reduce_inbox (worlds with reduce bindings: stripes, words, applies so far), remote_inbox (worlds with remote bindings: components, applies so far), sum_partials (worlds with sum bindings: units, words, applies so far), value_inbox (worlds with value bindings: components, bindings, bytes allocated, applies so far), state_diff (once a state diff ran: calls, and the columns, bytes per slot and units of the last one), checksum_parts (once a parts call ran: calls, the hashing kernel and where its module came from, builds), query (once a query ran: calls, and the fetched words, masks and units of the last one), delta (once a delta ran: calls, and the kind, components, compared columns and units of the last one).
  * ------------------------------------------------------------------------------------------- */
 int ggrs_hip_world_kernel_info(ggrs_world* w, char* buf, uint64_t cap, uint64_t* needed);
 

@@ -405,6 +405,35 @@ pub struct ggrs_scatter_report {
     pub first_bad_row: u64,
 }
 
+/// Delta kinds: `Query<.., Changed<C>>` (includes Added); `Added<C>`; `RemovedComponents<C>` (a despawn removes too); alive in old and not in new.
+pub const GGRS_DELTA_CHANGED: u32 = 0;
+pub const GGRS_DELTA_ADDED: u32 = 1;
+pub const GGRS_DELTA_REMOVED: u32 = 2;
+pub const GGRS_DELTA_DESPAWNED: u32 = 3;
+/// Delta flags: skip the words of components whose row versions agree on both sides.
+pub const GGRS_DELTA_TRUST_VERSIONS: u32 = 1;
+
+/// Which rows of two states a delta gathers: `q` is the filter and the fetched words on the base side, `changed_mask` the components asked about.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct ggrs_delta_desc {
+    pub q: ggrs_query_desc,
+    pub changed_mask: u64,
+    pub kind: u32,
+    pub flags: u32,
+}
+
+/// What a delta found: `n_beyond_old_len` of the `n_matched` rows lie at or beyond old's len.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct ggrs_delta_report {
+    pub len_new: u64,
+    pub len_old: u64,
+    pub n_matched: u64,
+    pub n_rows: u64,
+    pub n_beyond_old_len: u64,
+}
+
 /// The peer index: the key is word `word` of component `comp` (a 4-byte word); `flags` is 0.
 pub const GGRS_PEER_INDEX_MAX_BUCKETS: u32 = 65535;
 #[repr(C)]
@@ -511,6 +540,9 @@ unsafe extern "C" {
     pub fn ggrs_hip_peer_index_read(w: *mut ggrs_world, frame: i32, start: *mut u32, slots: *mut u32, n_indexed: *mut u64) -> c_int;
     // ---- scatter: rows of (slot, words..) in device memory, in a query's output layout, applied to the live world (the inverse of the query)
     pub fn ggrs_hip_scatter(w: *mut ggrs_world, desc: *const ggrs_scatter_desc, in_dev: *const c_void, stride_rows: u64, n_rows: u64, report: *mut ggrs_scatter_report) -> c_int;
+    // ---- delta: the rows that differ between two states, in a query's output layout
+    pub fn ggrs_hip_delta_frames(w: *mut ggrs_world, frame_new: i32, frame_old: i32, desc: *const ggrs_delta_desc, out_dev: *mut c_void, max_rows: u64, report: *mut ggrs_delta_report) -> c_int;
+    pub fn ggrs_hip_delta_block(w: *mut ggrs_world, frame_new: i32, block_old_dev: *const c_void, desc: *const ggrs_delta_desc, out_dev: *mut c_void, max_rows: u64, report: *mut ggrs_delta_report) -> c_int;
     // ---- speculative fan-out across GPUs (RCCL behind the C ABI; the host carries the 128-byte ncclUniqueId between ranks)
     pub fn ggrs_hip_fanout_unique_id(id_out: *mut u8) -> c_int;
     pub fn ggrs_hip_fanout_init(w: *mut ggrs_world, id: *const u8, rank: c_int, world_size: c_int, out: *mut *mut ggrs_fanout) -> c_int;

@@ -188,6 +188,21 @@ impl HipWorld {
         self.check(unsafe { ffi::ggrs_hip_scatter(self.raw, desc, in_dev, stride_rows, n_rows, &mut rep) });
         rep
     }
+    /// Mirroring into Bevy's own ECS (`Query<&C, Changed<C>>`, `Added<C>`, `RemovedComponents<C>`, despawn events): the rows that differ between two
+    /// states -- ring frames, or the live world (`None`) -- gathered like `query` into the caller's device buffer of `query_layout(&q, max_rows)`.
+    /// `kind` is `ffi::GGRS_DELTA_*`, `changed` the components asked about (empty for DESPAWNED); `q` is judged on the new state for CHANGED and
+    /// ADDED, on the old one for REMOVED and DESPAWNED.  The buffer can go to `scatter` unchanged.
+    ///
+    /// # Safety
+    /// `out_dev` must be device memory of that size on the world's device, not in use by other streams.
+    pub unsafe fn delta(&self, frame_new: Option<i32>, frame_old: Option<i32>, kind: u32, changed: &[u32], q: &ffi::ggrs_query_desc, out_dev: *mut core::ffi::c_void,
+                        max_rows: u64) -> ffi::ggrs_delta_report {
+        let mut d = ffi::ggrs_delta_desc { q: *q, changed_mask: 0, kind, flags: 0 };
+        for c in changed { d.changed_mask |= 1u64 << c; }
+        let mut rep = ffi::ggrs_delta_report { len_new: 0, len_old: 0, n_matched: 0, n_rows: 0, n_beyond_old_len: 0 };
+        self.check(unsafe { ffi::ggrs_hip_delta_frames(self.raw, frame_new.unwrap_or(ffi::GGRS_DIFF_LIVE), frame_old.unwrap_or(ffi::GGRS_DIFF_LIVE), &d, out_dev, max_rows, &mut rep) });
+        rep
+    }
 }
 impl Drop for HipWorld {
     fn drop(&mut self) {
