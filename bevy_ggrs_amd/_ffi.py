@@ -236,6 +236,19 @@ class DeltaReport(C.Structure):
     _fields_ = [("len_new", C.c_uint64), ("len_old", C.c_uint64), ("n_matched", C.c_uint64), ("n_rows", C.c_uint64), ("n_beyond_old_len", C.c_uint64)]
 
 
+SORT_MAX_KEYS = 4                                                               # GGRS_SORT_MAX_KEYS
+SORT_U, SORT_I, SORT_F, SORT_DESC = 0, 1, 2, 0x100                              # GGRS_SORT_*
+SORT_KINDS = {"u": SORT_U, "i": SORT_I, "f": SORT_F}
+
+
+class SortKey(C.Structure):
+    _fields_ = [("comp", C.c_uint32), ("word", C.c_uint32), ("kind", C.c_uint32)]
+
+
+class SortDesc(C.Structure):
+    _fields_ = [("keys", SortKey * SORT_MAX_KEYS), ("n_keys", C.c_uint32), ("flags", C.c_uint32)]
+
+
 class PeerIndexDesc(C.Structure):
     _fields_ = [("comp", C.c_uint32), ("word", C.c_uint32), ("n_buckets", C.c_uint32), ("flags", C.c_uint32)]
 
@@ -331,6 +344,8 @@ SIGNATURES = {
     "ggrs_hip_query_layout": (C.c_int, [_P, C.POINTER(QueryDesc), C.c_uint64, C.POINTER(QueryLayout)]),
     "ggrs_hip_query": (C.c_int, [_P, C.c_int32, C.POINTER(QueryDesc), _P, C.c_uint64, C.POINTER(QueryReport)]),
     "ggrs_hip_query_block": (C.c_int, [_P, _P, C.POINTER(QueryDesc), _P, C.c_uint64, C.POINTER(QueryReport)]),
+    "ggrs_hip_query_sorted": (C.c_int, [_P, C.c_int32, C.POINTER(QueryDesc), C.POINTER(SortDesc), _P, C.c_uint64, C.POINTER(QueryReport)]),
+    "ggrs_hip_query_sorted_block": (C.c_int, [_P, _P, C.POINTER(QueryDesc), C.POINTER(SortDesc), _P, C.c_uint64, C.POINTER(QueryReport)]),
     "ggrs_hip_scatter": (C.c_int, [_P, C.POINTER(ScatterDesc), _P, C.c_uint64, C.c_uint64, C.POINTER(ScatterReport)]),
     "ggrs_hip_delta_frames": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(DeltaDesc), _P, C.c_uint64, C.POINTER(DeltaReport)]),
     "ggrs_hip_delta_block": (C.c_int, [_P, C.c_int32, _P, C.POINTER(DeltaDesc), _P, C.c_uint64, C.POINTER(DeltaReport)]),
@@ -361,6 +376,8 @@ DEBUG_SIGNATURES = {
     "ggrs_dbg_set_query_grid": (C.c_int, [_P, C.c_int]),
     "ggrs_dbg_query_launch_us": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double)]),
     "ggrs_dbg_scatter_launch_us": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double)]),
+    "ggrs_dbg_set_sort_form": (C.c_int, [_P, C.c_int]),
+    "ggrs_dbg_sorted_query_launch_us": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double)]),
     "ggrs_dbg_parts_kernel_source": (C.c_int, [_P, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_int]),
 }
 

@@ -136,6 +136,7 @@ void ggrs_hip_world_destroy(ggrs_world* w) {
     for (hipEvent_t e : w->cparts_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : w->query_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : w->scatter_ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : w->sort_ev) if (e) (void)hipEventDestroy(e);
     jit_release(w->cparts_entry);
     sp_release(w);
     peer_view_release(w);
@@ -1487,6 +1488,160 @@ int ggrs_hip_query_block(ggrs_world* w, const void* block_dev, const ggrs_query_
     if (h.len > w->capacity) return w->fail(GGRS_E_INVALID, "the block's header has len %llu > capacity %llu: not a block of this world", (unsigned long long)h.len, (unsigned long long)w->capacity);
     DiffSide S; S.ptr = (const uint8_t*)block_dev; S.len = h.len; S.ver = nullptr; S.res_cell = 0; S.live_form = false;
     return query_run(w, S, desc, out_dev, max_rows, report);
+}
+
+// ---- SORTED QUERY (include/ggrs_hip.h; the kernels: kernels.hpp k_query_match / k_diff_scan as they are, k_sort_rows, k_sort_rekey + the k_ix_* passes or k_sort_small,
+// k_sort_emit) -----------------------------------------------------------------------------------------------------------------------------------------------------
+// Nothing here is on the tick's path.  Both descs are judged before the device is looked at: whether the state is the live world is known from the frame number.
+namespace {
+// *with gains the keys' components (a key's component counts as named in with_mask)
+int sort_check(ggrs_world* w, const ggrs_query_desc* d, const ggrs_sort_desc* s, bool live, const void* out_dev, uint64_t max_rows, const ggrs_query_report* rep, uint64_t* with) {
+    int rc = query_check(w, d, with); if (rc) return rc;
+    if (!s) return w->fail(GGRS_E_INVALID, "sorted query without a sort desc");
+    if (s->n_keys == 0) return w->fail(GGRS_E_INVALID, "a sorted query with n_keys 0 has nothing to order by: use ggrs_hip_query");
+    if (s->n_keys > GGRS_SORT_MAX_KEYS) return w->fail(GGRS_E_INVALID, "a sorted query takes at most %d keys, not n_keys %u", GGRS_SORT_MAX_KEYS, s->n_keys);
+    if (s->flags) return w->fail(GGRS_E_INVALID, "unknown sort flags 0x%x", s->flags);
+    for (uint32_t k = 0; k < s->n_keys; ++k) {
+        const ggrs_sort_key& q = s->keys[k];
+        if ((q.kind & ~GGRS_SORT_DESC) > GGRS_SORT_F) return w->fail(GGRS_E_INVALID, "sort key %u has unknown kind 0x%x (GGRS_SORT_U / _I / _F, | GGRS_SORT_DESC)", k, q.kind);
+        if (q.comp >= w->comps.size()) return w->fail(GGRS_E_INVALID, "sort key %u names component %u: the world has %zu", k, q.comp, w->comps.size());
+        const Comp& cc = w->comps[q.comp];
+        if (q.word >= cc.n_words) return w->fail(GGRS_E_INVALID, "sort key %u names word %u of component %s, which has %u", k, q.word, cc.name.c_str(), cc.n_words);
+        if ((q.kind & ~GGRS_SORT_DESC) == GGRS_SORT_F && cc.word_bytes < 4) return w->fail(GGRS_E_INVALID, "sort key %u is GGRS_SORT_F on the %u-byte words of component %s: 4- and 8-byte words only", k, cc.word_bytes, cc.name.c_str());
+        if ((d->without_mask >> q.comp) & 1ull) return w->fail(GGRS_E_INVALID, "sort key %u names component %s, which is also in without_mask: nothing can match", k, cc.name.c_str());
+        if (!live && cc.s_n_words) return w->fail(GGRS_E_INVALID, "sort key %u names a word of component %s, which is under a Strategy: a snapshot holds Stored words (GGRS_DIFF_LIVE is served)", k, cc.name.c_str());
+        if (!live && cc.no_rollback) return w->fail(GGRS_E_INVALID, "sort key %u names a word of component %s, which is not registered for rollback: no snapshot holds it (GGRS_DIFF_LIVE is served)", k, cc.name.c_str());
+        *with |= 1ull << q.comp;
+    }
+    if (!live) { rc = query_check_snapshot(w, d, *with); if (rc) return rc; }
+    if (w->capacity > (1ull << 32)) return w->fail(GGRS_E_INVALID, "a sorted query orders 32-bit slots: the world's capacity %llu exceeds 2^32", (unsigned long long)w->capacity);
+    if (!rep) return w->fail(GGRS_E_INVALID, "sorted query without a report");
+    if (!out_dev && max_rows) return w->fail(GGRS_E_INVALID, "sorted query with max_rows %llu and no output buffer", (unsigned long long)max_rows);
+    return GGRS_OK;
+}
+int sort_run(ggrs_world* w, const DiffSide& S, const ggrs_query_desc* d, const ggrs_sort_desc* sd, uint64_t with, void* out_dev, uint64_t max_rows, ggrs_query_report* rep) {
+    QueryArgs a; query_args(w, S, d, with, out_dev, max_rows, a);
+    SortArgs s; memset(&s, 0, sizeof s);
+    s.state = S.ptr;
+    for (uint32_t k = sd->n_keys; k-- > 0;) {                          // stages, least significant first: keys[n_keys-1] .. keys[0], an 8-byte word's low half before its high half
+        const ggrs_sort_key& q = sd->keys[k];
+        const uint32_t col = w->comps[q.comp].col_base + q.word, wb = w->col_wb[col];
+        for (uint32_t half = 0; half < (wb == 8 ? 2u : 1u); ++half) {
+            SortStage& st = s.st[s.n_stages++];
+            st.col_off = w->col_off[col]; st.col_ts = w->col_ts[col]; st.passes = wb >= 4 ? 4u : wb; st.wb = (uint8_t)wb;
+            st.kind = (uint8_t)(q.kind & ~GGRS_SORT_DESC); st.desc = (q.kind & GGRS_SORT_DESC) ? 1 : 0; st.half = (uint8_t)half;
+        }
+    }
+    memset(rep, 0, sizeof *rep);
+    rep->len = S.len;
+    // scratch: match word per unit + the sentinel | first row per unit + the total | key 0 | key 1 | val 0 | val 1 | the digit-major table (256 words per tile)
+    const uint64_t words = (uint64_t)a.n_units + 1u, o_off = align_up(words * 8, ALIGN), tiles_max = std::max<uint64_t>(1, (a.len + IX_TILE - 1) / IX_TILE);
+    const uint64_t pair_bytes = align_up(tiles_max * IX_TILE * 4u, ALIGN), o_pair = o_off + align_up(words * 8, ALIGN), o_hist = o_pair + 4 * pair_bytes;
+    static_assert(ALIGN % 16 == 0, "k_ix_scan loads the table as uint4");
+    int rc = diff_scratch(w, o_hist + align_up(tiles_max * 256u * 4u, ALIGN)); if (rc) return rc;
+    a.unit_match = (uint64_t*)w->d_diff; a.unit_off = (uint64_t*)(w->d_diff + o_off);
+    for (uint32_t i = 0; i < 2; ++i) { s.key[i] = (uint32_t*)(w->d_diff + o_pair + i * pair_bytes); s.val[i] = (uint32_t*)(w->d_diff + o_pair + (2 + i) * pair_bytes); }
+    uint32_t* const hist = (uint32_t*)(w->d_diff + o_hist);
+    const uint32_t cap = w->query_max_wgs ? w->query_max_wgs : 4096u;
+    const uint32_t g_match = std::max<uint32_t>(1, std::min<uint32_t>((uint32_t)((words + TPB - 1) / TPB), cap));
+    const uint32_t g_unit = std::max<uint32_t>(1, std::min<uint32_t>((a.n_units + TPB / 64 - 1) / (TPB / 64), cap));
+    const bool timed = w->sort_timed;
+    if (timed) { for (hipEvent_t& e : w->sort_ev) if (!e) HIPCHK(w, hipEventCreate(&e)); HIPCHK(w, hipEventRecord(w->sort_ev[0], w->stream)); }
+    hipLaunchKernelGGL(k_query_match, dim3(g_match), dim3(TPB), 0, w->stream, a);
+    HIPCHK(w, hipGetLastError());
+    if (timed) HIPCHK(w, hipEventRecord(w->sort_ev[1], w->stream));
+    hipLaunchKernelGGL(k_diff_scan, dim3(1), dim3(TPB), 0, w->stream, (const uint64_t*)a.unit_match, a.unit_off, (uint32_t)words);
+    HIPCHK(w, hipGetLastError());
+    if (timed) HIPCHK(w, hipEventRecord(w->sort_ev[2], w->stream));
+    // the count, before anything else is launched: the radix kernels take n and n_tiles by value
+    HIPCHK(w, hipMemcpyAsync(w->h_diff, a.unit_off + a.n_units, 8, hipMemcpyDeviceToHost, w->stream));
+    HIPCHK(w, hipStreamSynchronize(w->stream));
+    const uint64_t n = *(const uint64_t*)w->h_diff;
+    if (n > a.len) return w->fail(GGRS_E_HIP, "sorted query: %llu matches in a state of len %llu", (unsigned long long)n, (unsigned long long)a.len);
+    rep->n_matched = n;
+    rep->n_rows = std::min<uint64_t>(n, max_rows);
+    uint32_t launches = 2;
+    const bool sorts = n && max_rows && (a.n_words || a.slots);          // a desc that fetches no word and no slot writes nothing: a count, whatever max_rows is
+    if (sorts) {
+        s.n = n;
+        hipLaunchKernelGGL(k_sort_rows, dim3(g_unit), dim3(TPB), 0, w->stream, a, s);
+        HIPCHK(w, hipGetLastError());
+        ++launches;
+        if (timed) HIPCHK(w, hipEventRecord(w->sort_ev[3], w->stream));
+        uint32_t cur = 0;
+        if (n <= IX_TILE && !w->sort_force_large) {
+            hipLaunchKernelGGL(k_sort_small, dim3(1), dim3(IX_TPB), 0, w->stream, s);
+            HIPCHK(w, hipGetLastError());
+            ++launches;
+            for (uint32_t g = 0; g < s.n_stages; ++g) cur ^= s.st[g].passes & 1u;
+        } else {
+            const uint32_t n_tiles = (uint32_t)((n + IX_TILE - 1) / IX_TILE);
+            const uint32_t g_row = std::max<uint32_t>(1, std::min<uint32_t>((uint32_t)((n + TPB - 1) / TPB), cap));
+            for (uint32_t g = 0; g < s.n_stages; ++g) {
+                if (g) { hipLaunchKernelGGL(k_sort_rekey, dim3(g_row), dim3(TPB), 0, w->stream, s, g, cur); HIPCHK(w, hipGetLastError()); ++launches; }
+                for (uint32_t p = 0; p < s.st[g].passes; ++p, cur ^= 1u) {
+                    IxArgs x; memset(&x, 0, sizeof x);
+                    x.key_in = s.key[cur]; x.val_in = s.val[cur]; x.key_out = s.key[cur ^ 1u]; x.val_out = s.val[cur ^ 1u]; x.hist = hist;
+                    x.n = n; x.n_tiles = n_tiles; x.shift = 8u * p;
+                    hipLaunchKernelGGL((k_ix_hist<false>), dim3(n_tiles), dim3(IX_TPB), 0, w->stream, x);
+                    hipLaunchKernelGGL(k_ix_scan, dim3(1), dim3(IX_SCAN_TPB), 0, w->stream, hist, n_tiles);
+                    hipLaunchKernelGGL((k_ix_scatter<false>), dim3(n_tiles), dim3(IX_TPB), 0, w->stream, x);
+                    HIPCHK(w, hipGetLastError());
+                    launches += 3;
+                }
+            }
+        }
+        if (timed) HIPCHK(w, hipEventRecord(w->sort_ev[4], w->stream));
+        const uint32_t g_out = std::max<uint32_t>(1, std::min<uint32_t>((uint32_t)((rep->n_rows + TPB - 1) / TPB), cap));
+        hipLaunchKernelGGL(k_sort_emit, dim3(g_out), dim3(TPB), 0, w->stream, a, (const uint32_t*)s.val[cur], rep->n_rows);
+        HIPCHK(w, hipGetLastError());
+        ++launches;
+        if (timed) HIPCHK(w, hipEventRecord(w->sort_ev[5], w->stream));
+        HIPCHK(w, hipStreamSynchronize(w->stream));
+    }
+    if (timed) {
+        const int last = sorts ? 5 : 2;
+        for (int k = 0; k < 5; ++k) w->sort_us[k] = 0;
+        for (int k = 0; k < last; ++k) { float ms = 0; HIPCHK(w, hipEventElapsedTime(&ms, w->sort_ev[k], w->sort_ev[k + 1])); w->sort_us[k] = (double)ms * 1e3; }
+    }
+    ++w->sort_calls; w->sort_last_stages = s.n_stages; w->sort_last_launches = launches;
+    return GGRS_OK;
+}
+}  // namespace
+//   ggrs_dbg_set_sort_form             0: one workgroup sorts a result of at most IX_TILE rows in one launch (k_sort_small), 1: always the large form; the output must not depend on it
+int ggrs_dbg_set_sort_form(ggrs_world* w, int form) { if (!w || form < 0 || form > 1) return -1; w->sort_force_large = form == 1; return 0; }
+//   ggrs_dbg_sorted_query_launch_us    enable != 0: every later sorted query puts HIP events around its phases; us_out (may be NULL) receives what match, scan, the host's
+//                                      read of the count together with the rows launch (one figure, mostly the wait), the stages and the emit of the last timed call took, in microseconds (scripts/bench_sorted_query.py)
+int ggrs_dbg_sorted_query_launch_us(ggrs_world* w, int enable, double* us_out) {
+    if (!w) return -1;
+    w->sort_timed = enable != 0;
+    if (us_out) for (int k = 0; k < 5; ++k) us_out[k] = w->sort_us[k];
+    return 0;
+}
+int ggrs_hip_query_sorted(ggrs_world* w, int32_t frame, const ggrs_query_desc* query_desc, const ggrs_sort_desc* sort_desc, void* out_dev, uint64_t max_rows, ggrs_query_report* report) {
+    if (!w) return GGRS_E_INVALID;
+    uint64_t with = 0;
+    int rc = sort_check(w, query_desc, sort_desc, frame == GGRS_DIFF_LIVE, out_dev, max_rows, report, &with); if (rc) return rc;
+    if (w->layout_only) return w->fail(GGRS_E_NO_DEVICE, "a layout-only world has no state to query");
+    DeviceGuard dg(w);
+    rc = diff_ready(w); if (rc) return rc;
+    DiffSide S; rc = diff_side(w, frame, &S); if (rc) return rc;
+    return sort_run(w, S, query_desc, sort_desc, with, out_dev, max_rows, report);
+}
+int ggrs_hip_query_sorted_block(ggrs_world* w, const void* block_dev, const ggrs_query_desc* query_desc, const ggrs_sort_desc* sort_desc, void* out_dev, uint64_t max_rows, ggrs_query_report* report) {
+    if (!w) return GGRS_E_INVALID;
+    if (!block_dev) return w->fail(GGRS_E_INVALID, "query_sorted_block without a block");
+    uint64_t with = 0;
+    int rc = sort_check(w, query_desc, sort_desc, false, out_dev, max_rows, report, &with); if (rc) return rc;
+    if (w->layout_only) return w->fail(GGRS_E_NO_DEVICE, "a layout-only world has no state to query");
+    DeviceGuard dg(w);
+    rc = diff_ready(w); if (rc) return rc;
+    Header h;
+    HIPCHK(w, hipMemcpyAsync(&h, block_dev, sizeof h, hipMemcpyDeviceToHost, w->stream));
+    HIPCHK(w, hipStreamSynchronize(w->stream));
+    if (h.len > w->capacity) return w->fail(GGRS_E_INVALID, "the block's header has len %llu > capacity %llu: not a block of this world", (unsigned long long)h.len, (unsigned long long)w->capacity);
+    DiffSide S; S.ptr = (const uint8_t*)block_dev; S.len = h.len; S.ver = nullptr; S.res_cell = 0; S.live_form = false;
+    return sort_run(w, S, query_desc, sort_desc, with, out_dev, max_rows, report);
 }
 
 // ---- DELTA (include/ggrs_hip.h; the kernels: kernels.hpp k_delta_match_masks / k_delta_match_values, then k_diff_scan / k_query_emit as they are) --------------------

@@ -456,6 +456,10 @@ struct ggrs_world {
     bool scatter_timed = false; hipEvent_t scatter_ev[3] = {nullptr, nullptr, nullptr}; double scatter_us[2] = {0, 0};           // ggrs_dbg_scatter_launch_us: check, apply of the last call
     // ---- delta (ggrs_hip_delta_frames / ggrs_hip_delta_block): the query's scratch, grid cap and launch timer (its match, scan, emit are what ggrs_dbg_query_launch_us reports)
     uint64_t delta_calls = 0; uint32_t delta_last_kind = 0, delta_last_cols = 0, delta_last_comps = 0, delta_last_units = 0;
+    // ---- sorted query (ggrs_hip_query_sorted / ggrs_hip_query_sorted_block): the query's scratch (grown by the key / val pairs and the digit table) and grid cap.
+    // sort_force_large: ggrs_dbg_set_sort_form (0: the small form where it fits, 1: always the large form)
+    uint64_t sort_calls = 0; uint32_t sort_last_stages = 0, sort_last_launches = 0; bool sort_force_large = false;
+    bool sort_timed = false; hipEvent_t sort_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; double sort_us[5] = {0, 0, 0, 0, 0};   // ggrs_dbg_sorted_query_launch_us: match, scan, rows, stages, emit
 
     // ---- profiling
     bool nt_copy = false;              // non-temporal loads/stores in k_copy_state (A/B knob)

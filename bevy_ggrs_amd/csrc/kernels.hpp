@@ -1703,4 +1703,97 @@ __global__ __launch_bounds__(TPB) void k_delta_match_values(DeltaArgs a) {
     }
 }
 
+// ------------------------------------------------------------------ SORTED QUERY (ggrs_hip_query_sorted / ggrs_hip_query_sorted_block)
+// query.iter().sort_by(..) over one packed block: the query's rows, ordered by up to GGRS_SORT_MAX_KEYS key words instead of by slot.  k_query_match and k_diff_scan
+// as they are; the host reads the number of matches (the radix launches take n and n_tiles by value); then
+//   k_sort_rows    one 64-slot unit per wave-iteration, as k_query_emit walks them: a matching lane stores its slot at val[row] and the least significant stage's
+//                  transformed key at key[row], for ALL matching rows (max_rows cuts the emit, not the sort).
+//   the stages     least significant first.  A stage is one 32-bit key: a key word of up to 4 bytes is one stage, an 8-byte word two (low half, then high half).
+//                  The transform is taken at the word's width before it is split: U the bits, I the bits ^ the sign bit, F the bits ^ (sign set ? all ones : the
+//                  sign bit) -- IEEE-754 total order --, DESC the complement of that.  Every stage but the first begins with k_sort_rekey (key[i] = the transformed
+//                  word of slot val[i]: a gather through col_at); then k_ix_hist<false> / k_ix_scan / k_ix_scatter<false> as they are, one pass per byte of the
+//                  stage, ping-ponging two key and two val arrays.  The passes are stable, the rows start in slot order: stability gives the precedence of the
+//                  keys and the ascending-slot tie-break, also under DESC.
+//   k_sort_small   at most IX_TILE matches: ONE workgroup does every stage in one launch, from the tile bodies as ix_small_pass uses them, the rekey between the
+//                  stages inside the launch; a workgroup fence and a barrier stand where the large form has a kernel boundary.
+//   k_sort_emit    one row per lane, grid-stride over [0, n_rows): slot = val[row]; the fetched words are gathered through col_at, QUERY_BATCH columns' loads ahead of
+//                  the first store, and stored at `row`, coalesced; the slots column is val[row].
+// No compare-and-swap, no wait between workgroups, no position from an atomic's return value; plain vector loads and stores.
+constexpr uint32_t SORT_MAX_STAGES = 2 * GGRS_SORT_MAX_KEYS;
+struct SortStage { uint64_t col_off; uint32_t col_ts, passes; uint8_t wb, kind, desc, half; uint32_t pad; };   // passes: the radix passes of this stage (1, 2 or 4)
+struct SortArgs {
+    const uint8_t* state;
+    uint32_t* key[2]; uint32_t* val[2];                    // the ping-pong pairs: k_sort_rows fills [0]
+    uint64_t n;                                            // the matching rows: every one of them is sorted
+    uint32_t n_stages, pad;
+    SortStage st[SORT_MAX_STAGES];
+};
+// the order-preserving unsigned image of the key word of slot e, at the word's width, and the stage's 32 bits of it
+__device__ __forceinline__ uint32_t sort_stage_key(const uint8_t* state, const SortStage& s, uint64_t e) {
+    const uint32_t wb = s.wb, bits = 8u * wb;
+    const uint64_t v = diff_load(state + col_at(s.col_off, s.col_ts, wb, e), wb);          // e < len <= the capacity: inside the column
+    const uint64_t mask = ~0ull >> (64u - bits), sign = 1ull << (bits - 1u);
+    uint64_t t = v;
+    if (s.kind == GGRS_SORT_I) t = v ^ sign;
+    else if (s.kind == GGRS_SORT_F) t = v ^ ((v & sign) ? mask : sign);
+    if (s.desc) t = ~t & mask;
+    return (uint32_t)(s.half ? t >> 32 : t);
+}
+__global__ __launch_bounds__(TPB) void k_sort_rows(QueryArgs a, SortArgs s) {
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t wave = tid >> 6;
+    for (uint32_t u = blockIdx.x * (TPB / 64) + wave; u < a.n_units; u += gridDim.x * (TPB / 64)) {
+        const uint64_t m = a.unit_match[u];
+        if (!((m >> lane) & 1ull)) continue;
+        const uint64_t e = (uint64_t)u * 64u + lane, row = a.unit_off[u] + (uint64_t)__popcll(m & ((1ull << lane) - 1ull));   // row < n: the scan's total
+        s.val[0][row] = (uint32_t)e;
+        s.key[0][row] = sort_stage_key(a.state, s.st[0], e);
+    }
+}
+__device__ __forceinline__ void sort_rekey(const SortArgs& s, const SortStage& st, uint32_t* key, const uint32_t* val, uint64_t first, uint64_t stride) {
+    for (uint64_t i = first; i < s.n; i += stride) key[i] = sort_stage_key(s.state, st, val[i]);
+}
+__global__ __launch_bounds__(TPB) void k_sort_rekey(SortArgs s, uint32_t stage, uint32_t cur) {
+    sort_rekey(s, s.st[stage], s.key[cur], s.val[cur], (uint64_t)blockIdx.x * TPB + threadIdx.x, (uint64_t)gridDim.x * TPB);
+}
+__global__ __launch_bounds__(IX_TPB) void k_sort_small(SortArgs s) {
+    __shared__ uint32_t h[256], tab[256], base[256], cnt[IX_TPB / 64][256];
+    uint32_t cur = 0;
+    for (uint32_t g = 0; g < s.n_stages; ++g) {
+        if (g) {                                                                 // (the vals were stored by other waves of this workgroup: the pass ended on a fence and a barrier)
+            sort_rekey(s, s.st[g], s.key[cur], s.val[cur], threadIdx.x, IX_TPB);
+            __threadfence_block();
+            __syncthreads();
+        }
+        for (uint32_t p = 0; p < s.st[g].passes; ++p, cur ^= 1u) {
+            IxArgs a;
+            a.key_col = nullptr; a.vis = nullptr; a.key_in = s.key[cur]; a.val_in = s.val[cur]; a.key_out = s.key[cur ^ 1u]; a.val_out = s.val[cur ^ 1u]; a.hist = nullptr;
+            a.n = s.n; a.n_tiles = 1; a.n_buckets = 0; a.shift = 8u * p;
+            ix_small_pass<false>(a, h, tab, base, cnt);
+        }
+    }
+}
+__global__ __launch_bounds__(TPB) void k_sort_emit(QueryArgs a, const uint32_t* __restrict__ val, uint64_t n_rows) {
+    const uint64_t stride = (uint64_t)gridDim.x * TPB;
+    for (uint64_t row = (uint64_t)blockIdx.x * TPB + threadIdx.x; row < n_rows; row += stride) {
+        const uint64_t e = val[row];                                             // a slot k_sort_rows stored: below len
+        for (uint32_t k0 = 0; k0 < a.n_words; k0 += QUERY_BATCH) {
+            uint64_t v[QUERY_BATCH];
+#pragma unroll
+            for (uint32_t i = 0; i < QUERY_BATCH; ++i) {
+                v[i] = 0;
+                if (k0 + i < a.n_words) {                                        // (uniform)
+                    const uint32_t wb = a.col_wb[k0 + i];
+                    v[i] = diff_load(a.state + col_at(a.col_off[k0 + i], a.col_ts[k0 + i], wb, e), wb);
+                }
+            }
+#pragma unroll
+            for (uint32_t i = 0; i < QUERY_BATCH; ++i)
+                if (k0 + i < a.n_words) { const uint32_t wb = a.col_wb[k0 + i]; query_store(a.out + a.out_off[k0 + i] + row * wb, v[i], wb); }
+        }
+        if (a.slots) *reinterpret_cast<uint32_t*>(a.out + a.slots_off + row * 4u) = (uint32_t)e;
+    }
+}
+// ------------------------------------------------------------------ END OF SORTED QUERY
+
 }  // namespace ggrs

@@ -818,6 +818,55 @@ class World(WorldBase):
                            words=[(int(desc.words[k].comp), int(desc.words[k].word)) for k in range(desc.n_words)], buffer=out, max_rows=int(max_rows),
                            slots_off=int(lay.slots_off))
 
+    # ---- sorted query (include/ggrs_hip.h: ggrs_hip_query_sorted / ggrs_hip_query_sorted_block)
+    def sort_desc(self, order_by) -> "_ffi.SortDesc":
+        """The ggrs_sort_desc of World.query_sorted's `order_by`: a sequence of (comp, word, kind) or (comp, word, kind, "desc"), kind in "u" | "i" | "f", the most
+        significant key first."""
+        order_by = list(order_by)
+        if len(order_by) > _ffi.SORT_MAX_KEYS: raise ValueError(f"a sorted query takes at most {_ffi.SORT_MAX_KEYS} keys, not {len(order_by)}")
+        d = _ffi.SortDesc()
+        d.n_keys = len(order_by); d.flags = 0
+        for k, key in enumerate(order_by):
+            if len(key) not in (3, 4) or (len(key) == 4 and key[3] != "desc"): raise ValueError(f"sort key {k} is (comp, word, kind) or (comp, word, kind, 'desc'), not {key!r}")
+            if key[2] not in _ffi.SORT_KINDS: raise ValueError(f"sort key {k}: kind is one of {sorted(_ffi.SORT_KINDS)}, not {key[2]!r}")
+            d.keys[k].comp = int(key[0]); d.keys[k].word = int(key[1]); d.keys[k].kind = _ffi.SORT_KINDS[key[2]] | (_ffi.SORT_DESC if len(key) == 4 else 0)
+        return d
+
+    def query_sorted(self, state, fetch, order_by, *, with_=(), without=(), slots=True, max_rows: Optional[int] = None, out=None) -> QueryResult:
+        """World.query's rows ordered on the device by `order_by` (World.sort_desc) instead of by slot: query.iter().sort_by(..).  The first key is the most
+        significant; rows equal on every key are in ascending slot order, also under "desc"; "f" is the IEEE-754 total order (f32::total_cmp).  max_rows is a
+        top-k: the first min(n_matched, max_rows) rows of the full order.  A key's component counts as With; a key word need not be fetched.  Everything else --
+        `state`, `fetch`, the buffer's layout, the QueryResult -- is World.query's."""
+        import torch
+        desc = self.query_desc(fetch, with_, without, slots)
+        sdesc = self.sort_desc(order_by)
+        if max_rows is None: max_rows = self.len
+        lay = self.query_layout(desc, max_rows)
+        need = int(lay.total_bytes)
+        if out is None:
+            out = torch.empty(max(need, 1), dtype=torch.uint8, device=f"cuda:{self.device}")
+        elif out.dtype != torch.uint8 or out.numel() < need or not out.is_cuda or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous torch.uint8 device tensor of at least {need} bytes")
+        torch.cuda.current_stream(out.device).synchronize()       # (the launches run on the world's stream)
+        rep = _ffi.QueryReport()
+        if hasattr(state, "data_ptr"):
+            if state.dtype != torch.uint8 or state.numel() != self.state_bytes() or not state.is_cuda or not state.is_contiguous():
+                raise ValueError(f"a block is a contiguous torch.uint8 device tensor of {self.state_bytes()} bytes")
+            torch.cuda.current_stream(state.device).synchronize()
+            self._check(self._lib.ggrs_hip_query_sorted_block(self._p, state.data_ptr(), C.byref(desc), C.byref(sdesc), out.data_ptr(), max_rows, C.byref(rep)))
+        else:
+            self._check(self._lib.ggrs_hip_query_sorted(self._p, int(state), C.byref(desc), C.byref(sdesc), out.data_ptr(), max_rows, C.byref(rep)))
+        n = int(rep.n_rows)
+        dt = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
+        columns = []
+        for k in range(desc.n_words):
+            wb, off = int(lay.word_bytes[k]), int(lay.col_off[k])
+            columns.append(out[off:off + n * wb].view(dt[wb]))
+        slot_col = out[int(lay.slots_off):int(lay.slots_off) + n * 4].view(torch.int32) if slots else None
+        return QueryResult(len=int(rep.len), n_matched=int(rep.n_matched), n_rows=n, slots=slot_col, columns=columns,
+                           words=[(int(desc.words[k].comp), int(desc.words[k].word)) for k in range(desc.n_words)], buffer=out, max_rows=int(max_rows),
+                           slots_off=int(lay.slots_off))
+
     # ---- delta (include/ggrs_hip.h: ggrs_hip_delta_frames / ggrs_hip_delta_block)
     def delta_desc(self, fetch=(), *, kind="changed", changed=(), with_=(), without=(), slots=True, trust_versions=False) -> "_ffi.DeltaDesc":
         """The ggrs_delta_desc of World.delta's arguments."""

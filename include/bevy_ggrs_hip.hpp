@@ -511,6 +511,16 @@ struct HipBackend {
     int query_layout(const ggrs_query_desc& desc, uint64_t max_rows, ggrs_query_layout* out) { return ggrs_hip_query_layout(w, &desc, max_rows, out); }
     int query(int32_t frame, const ggrs_query_desc& desc, void* out_dev, uint64_t max_rows, ggrs_query_report* report) { return ggrs_hip_query(w, frame, &desc, out_dev, max_rows, report); }
     int query_block(const void* block_dev, const ggrs_query_desc& desc, void* out_dev, uint64_t max_rows, ggrs_query_report* report) { return ggrs_hip_query_block(w, block_dev, &desc, out_dev, max_rows, report); }
+    // sorted query (include/ggrs_hip.h): query.iter().sort_by(..) on the device -- the query's rows, in the query's layout, ordered by up to GGRS_SORT_MAX_KEYS key words
+    // (keys[0] the most significant; ties in ascending slot order; GGRS_SORT_F is f32::total_cmp); max_rows is a top-k
+    static ggrs_sort_desc sort_desc(const std::vector<ggrs_sort_key>& keys) {
+        ggrs_sort_desc d{};
+        d.n_keys = (uint32_t)keys.size();                              // (more than GGRS_SORT_MAX_KEYS: the call refuses it)
+        for (uint32_t k = 0; k < d.n_keys && k < GGRS_SORT_MAX_KEYS; ++k) d.keys[k] = keys[k];
+        return d;
+    }
+    int query_sorted(int32_t frame, const ggrs_query_desc& desc, const ggrs_sort_desc& order, void* out_dev, uint64_t max_rows, ggrs_query_report* report) { return ggrs_hip_query_sorted(w, frame, &desc, &order, out_dev, max_rows, report); }
+    int query_sorted_block(const void* block_dev, const ggrs_query_desc& desc, const ggrs_sort_desc& order, void* out_dev, uint64_t max_rows, ggrs_query_report* report) { return ggrs_hip_query_sorted_block(w, block_dev, &desc, &order, out_dev, max_rows, report); }
     // scatter (include/ggrs_hip.h): writing back -- Query<&mut C>, commands.entity(e).insert(..) / .remove::<C>() / .despawn() over a whole query result.  Rows of
     // (slot, words..) in device memory, in the layout query_layout gives for the same words with slots, applied to the live world in one call; a query's output buffer
     // can be handed back unchanged (stride_rows = its max_rows, n_rows = its report's n_rows).  The slots must be strictly ascending and below len

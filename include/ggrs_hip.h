@@ -1180,6 +1180,35 @@ int ggrs_hip_delta_frames(ggrs_world* w, int32_t frame_new, int32_t frame_old, c
 int ggrs_hip_delta_block(ggrs_world* w, int32_t frame_new, const void* block_old_dev, const ggrs_delta_desc* desc, void* out_dev, uint64_t max_rows, ggrs_delta_report* report);
 
 /* -------------------------------------------------------------------------------------------
+ * SORTED QUERY: the rows of a query ordered by key words on the device -- query.iter().sort_by(..): draw order by depth, a leaderboard, nearest-first lists.
+ * Both calls return exactly the rows ggrs_hip_query / ggrs_hip_query_block would return for query_desc, in the layout ggrs_hip_query_layout gives for it,
+ * ordered by sort_desc instead of by slot.
+ *
+ * keys[0] is the most significant key.  Rows that compare equal on every key are in ascending slot order, also under GGRS_SORT_DESC:
+ * sort_by(|a, b| k0(a).cmp(k0(b)).then(k1 ..).then(slot(a).cmp(slot(b)))).  GGRS_SORT_F is the IEEE-754 total order on the bits (Rust f32::total_cmp /
+ * f64::total_cmp): -NaN < -inf < .. < -0.0 < +0.0 < .. < +inf < +NaN, NaNs ordered by payload; no row is ever unordered.  Key words are 1, 2, 4 or 8 bytes
+ * wide; a key's component counts as named in with_mask, as a fetched word's does; a key word need not be fetched.
+ * max_rows is a top-k: the rows written are the first min(n_matched, max_rows) of the full order; n_matched is exact whatever max_rows is; max_rows == 0
+ * is a count.  No byte at or beyond row n_rows of any column, and no padding byte, is written.  The result is byte-identical for every launch geometry and
+ * from run to run.  Sides, readiness and GGRS_E_NO_SNAPSHOT are the query's; the calls return when out_dev is written.
+ * Errors, GGRS_E_INVALID with a message naming the key (checked before the device is looked at; GGRS_E_NO_DEVICE on a layout-only world for a good desc):
+ * everything the query refuses for query_desc; n_keys == 0 (use ggrs_hip_query) or above GGRS_SORT_MAX_KEYS; flags != 0; an unknown kind or unknown bits
+ * in kind; a key component the world does not have, or a word beyond the component; GGRS_SORT_F on a 1- or 2-byte word; a key's component also in
+ * without_mask; a key word of a component under a Strategy, or of a GGRS_COMP_NO_ROLLBACK component, against a ring frame or a block (GGRS_DIFF_LIVE is
+ * served); a world whose capacity exceeds 2^32.
+ * Out of scope: a selection (top-k without a full sort), skipping passes whose digit is constant, sorted deltas, handing a sorted result to
+ * ggrs_hip_scatter (it needs strictly ascending slots and refuses it), composite keys beyond GGRS_SORT_MAX_KEYS words, an asynchronous form. */
+#define GGRS_SORT_MAX_KEYS 4
+#define GGRS_SORT_U    0u      /* the word's bits as an unsigned integer                                  */
+#define GGRS_SORT_I    1u      /* two's complement at the word's width                                    */
+#define GGRS_SORT_F    2u      /* IEEE-754 total order (Rust f32::total_cmp / f64::total_cmp): 4- and 8-byte words only */
+#define GGRS_SORT_DESC 0x100u  /* this key descending                                                      */
+typedef struct { uint32_t comp; uint32_t word; uint32_t kind; } ggrs_sort_key;          /* kind: one of U/I/F, | GGRS_SORT_DESC */
+typedef struct { ggrs_sort_key keys[GGRS_SORT_MAX_KEYS]; uint32_t n_keys; uint32_t flags; } ggrs_sort_desc;   /* flags: 0 */
+int ggrs_hip_query_sorted(ggrs_world* w, int32_t frame, const ggrs_query_desc* query_desc, const ggrs_sort_desc* sort_desc, void* out_dev, uint64_t max_rows, ggrs_query_report* report);
+int ggrs_hip_query_sorted_block(ggrs_world* w, const void* block_dev, const ggrs_query_desc* query_desc, const ggrs_sort_desc* sort_desc, void* out_dev, uint64_t max_rows, ggrs_query_report* report);
+
+/* -------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): per-kernel-class HIP-event timing on the world's stream.
  * ------------------------------------------------------------------------------------------- */
 #define GGRS_KERNEL_SAVE     0u

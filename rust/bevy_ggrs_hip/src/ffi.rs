@@ -434,6 +434,33 @@ pub struct ggrs_delta_report {
     pub n_beyond_old_len: u64,
 }
 
+/// A sorted query orders by at most this many key words.
+pub const GGRS_SORT_MAX_KEYS: usize = 4;
+/// Sort key kinds: the bits as an unsigned integer; two's complement at the word's width; the IEEE-754 total order (`f32::total_cmp`, 4- and 8-byte words).
+pub const GGRS_SORT_U: u32 = 0;
+pub const GGRS_SORT_I: u32 = 1;
+pub const GGRS_SORT_F: u32 = 2;
+/// Or-ed into a key's kind: this key descending (ties still in ascending slot order).
+pub const GGRS_SORT_DESC: u32 = 0x100;
+
+/// One sort key: word `word` of component `comp`, compared as `kind`.
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct ggrs_sort_key {
+    pub comp: u32,
+    pub word: u32,
+    pub kind: u32,
+}
+
+/// What a sorted query orders by: `keys[0]` is the most significant; `flags` is 0.
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct ggrs_sort_desc {
+    pub keys: [ggrs_sort_key; GGRS_SORT_MAX_KEYS],
+    pub n_keys: u32,
+    pub flags: u32,
+}
+
 /// The peer index: the key is word `word` of component `comp` (a 4-byte word); `flags` is 0.
 pub const GGRS_PEER_INDEX_MAX_BUCKETS: u32 = 65535;
 #[repr(C)]
@@ -538,6 +565,9 @@ unsafe extern "C" {
     // ---- the peer index: a deterministic multimap key -> slots, rebuilt at the start of every frame; user systems iterate it with e.bucket(key)
     pub fn ggrs_hip_register_peer_index(w: *mut ggrs_world, d: *const ggrs_peer_index_desc) -> c_int;
     pub fn ggrs_hip_peer_index_read(w: *mut ggrs_world, frame: i32, start: *mut u32, slots: *mut u32, n_indexed: *mut u64) -> c_int;
+    // ---- sorted query: the query's rows ordered by key words on the device (query.iter().sort_by(..)), in the query's output layout
+    pub fn ggrs_hip_query_sorted(w: *mut ggrs_world, frame: i32, query_desc: *const ggrs_query_desc, sort_desc: *const ggrs_sort_desc, out_dev: *mut c_void, max_rows: u64, report: *mut ggrs_query_report) -> c_int;
+    pub fn ggrs_hip_query_sorted_block(w: *mut ggrs_world, block_dev: *const c_void, query_desc: *const ggrs_query_desc, sort_desc: *const ggrs_sort_desc, out_dev: *mut c_void, max_rows: u64, report: *mut ggrs_query_report) -> c_int;
     // ---- scatter: rows of (slot, words..) in device memory, in a query's output layout, applied to the live world (the inverse of the query)
     pub fn ggrs_hip_scatter(w: *mut ggrs_world, desc: *const ggrs_scatter_desc, in_dev: *const c_void, stride_rows: u64, n_rows: u64, report: *mut ggrs_scatter_report) -> c_int;
     // ---- delta: the rows that differ between two states, in a query's output layout

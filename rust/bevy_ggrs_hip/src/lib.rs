@@ -152,6 +152,26 @@ impl HipWorld {
         self.check(unsafe { ffi::ggrs_hip_query(self.raw, frame.unwrap_or(ffi::GGRS_DIFF_LIVE), desc, out_dev, max_rows, &mut rep) });
         rep
     }
+    /// The desc of `sort_by`: (component id, word, `ffi::GGRS_SORT_U / _I / _F`, descending) per key, the most significant first.
+    pub fn sort_desc(keys: &[(u32, u32, u32, bool)]) -> ffi::ggrs_sort_desc {
+        assert!(!keys.is_empty() && keys.len() <= ffi::GGRS_SORT_MAX_KEYS, "a sorted query orders by 1 ..= GGRS_SORT_MAX_KEYS key words");
+        let mut d = ffi::ggrs_sort_desc::default();
+        d.n_keys = keys.len() as u32;
+        for (k, (comp, word, kind, desc)) in keys.iter().enumerate() {
+            d.keys[k] = ffi::ggrs_sort_key { comp: *comp, word: *word, kind: *kind | if *desc { ffi::GGRS_SORT_DESC } else { 0 } };
+        }
+        d
+    }
+    /// `query.iter().sort_by(..)` on the device: the rows `query` would write, in the same layout, ordered by `order` instead of by slot.  Rows equal on
+    /// every key are in ascending slot order; `GGRS_SORT_F` is `f32::total_cmp`; `max_rows` is a top-k (the first rows of the full order).
+    ///
+    /// # Safety
+    /// `out_dev` must be device memory of `query_layout(..).total_bytes` bytes on the world's device, not in use by other streams.
+    pub unsafe fn query_sorted(&self, frame: Option<i32>, desc: &ffi::ggrs_query_desc, order: &ffi::ggrs_sort_desc, out_dev: *mut core::ffi::c_void, max_rows: u64) -> ffi::ggrs_query_report {
+        let mut rep = ffi::ggrs_query_report { len: 0, n_matched: 0, n_rows: 0 };
+        self.check(unsafe { ffi::ggrs_hip_query_sorted(self.raw, frame.unwrap_or(ffi::GGRS_DIFF_LIVE), desc, order, out_dev, max_rows, &mut rep) });
+        rep
+    }
     /// A deterministic multimap key -> slots over word `word` of component `comp` (a 4-byte word), rebuilt at the start of every frame: systems added
     /// after this call iterate the entities that share a key with `e.bucket(key)`, members in ascending slot order.  Before seal; one per world.
     pub fn register_peer_index(&self, comp: u32, word: u32, n_buckets: u32) {
